@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- assemblies typed per second (K + O databases back to back) on N MI355X GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--assemblies A] [--batch B] [--db kpsc|ab_k]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--assemblies A] [--batch B] [--db kpsc|ab_k] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (BASELINE.json config 3): A = 10 000 synthetic ~5 Mbp KpSC assemblies per GPU, typed against the synthetic
@@ -12,15 +12,17 @@ pieces, translation, protein DP and gene states on the GPU; the host does three 
 and batch and formats the TSV rows.  The two databases have their own contexts and streams and share one resident copy
 of the packed assemblies.  `--db ab_k` runs config 4 instead (A. baumannii K database, 4 Mbp, ~1 500 contigs).
 
-Three throughputs are reported in the one JSON line:
-  value                      packed assemblies resident in HBM before the timed region (the contract's number)
-  e2e.from_host_shards       every batch uploaded from pre-packed shards in pinned host memory inside the timed region
-                             (H2D on a copy stream, two batches ahead of the alignment pass), then typed
-  e2e.with_tsv               the same plus the TSV bytes of every row
-Ranks hold disjoint assemblies (weak scaling, no collective on the data path; torch.distributed is used for the
-barrier and the max-over-ranks of the elapsed time only).  Rank 0 prints the line.
+A plain run sets up (the workload is made by worker processes while the device and the contexts are set up beside them),
+warms up, times the K steps and prints one JSON line: `value` (assemblies typed per second with the packed assemblies
+resident in HBM before the timed region; the contract's number), `ms_per_step` and a description of the workload.
+`--dump-outputs DIR` writes what the last timed step returned (dump_outputs).  Ranks hold disjoint assemblies (weak
+scaling, no collective on the data path; torch.distributed is used for the barrier and the max-over-ranks of the elapsed
+time only).  Rank 0 prints the line.
 
-Extra objects in the line:
+`--full` adds to the line:
+  e2e           e2e.from_host_shards: every batch uploaded from pre-packed shards in pinned host memory inside the timed
+                region (H2D on a copy stream, two batches ahead of the alignment pass), then typed; e2e.with_tsv: the same
+                plus the TSV bytes of every row; e2e.cli_from_fasta: `kaptive_amd assembly` over FASTA files
   roofline      seed-scan kernel of the K database pass (the kernel that streams every base against the large
                 database): algorithmic bytes = 4 * packed words per launch, duration = mean over its launches in the
                 timed region, from HIP events the library records on the kernel's own stream (kp_batch_profile), peak =
@@ -28,6 +30,8 @@ Extra objects in the line:
   dp            banded Smith-Waterman kernels: DP cells per second (integer VALU work; no HBM or MFMA roofline applies).
   cpu_baseline  the CPU oracle (oracle/kp_oracle.c rebuilt -O3 -march=native on this box + the numpy reduction) typing
                 a bounded sample of the same assemblies: on every host core at once (value / cores) and on one core.
+  also          kernel milliseconds per step, row digests, host use per rank, FASTA ingest rates and the short secondary
+                legs (config 4, the non-iid background, a workload that joins), each a run of this script of its own.
 """
 
 from __future__ import annotations
@@ -87,19 +91,38 @@ def _make_one(job):
     return g.id, g.packed()
 
 
+class WorkloadStream:
+    """Packed assemblies of seeds seed0 .. seed0 + n_asm - 1, in seed order.  With workers > 1 they are made by worker
+    processes forked here, which must happen before any GPU state exists in this process; the caller may then set up the
+    device while they work, and `upto(k)` waits for the first k."""
+
+    def __init__(self, n_asm: int, seed0: int, length: float, workers: int):
+        jobs = [(seed0 + i, length) for i in range(n_asm)]
+        self.n, self.ids, self.packed, self.pool = n_asm, [], [], None
+        if workers > 1 and n_asm > 4:
+            self.pool = get_context("fork").Pool(workers)
+            self.rows = self.pool.imap(_make_one, jobs, chunksize=max(1, min(16, n_asm // (workers * 4))))
+        else:
+            self.rows = map(_make_one, jobs)
+
+    def upto(self, k: int) -> list:
+        while len(self.packed) < k:
+            i, pa = next(self.rows)
+            self.ids.append(i)
+            self.packed.append(pa)
+        if self.pool is not None and len(self.packed) == self.n:
+            # close + join, never terminate(): a SIGTERM to the workers wedges tools that hook signals (rocprofv3)
+            self.pool.close()
+            self.pool.join()
+            self.pool = None
+        return self.packed[:k]
+
+
 def build_workload(n_asm: int, seed0: int, length: float, workers: int):
     """Synthetic databases and packed assemblies, generated before any GPU state exists (forked workers)."""
-    jobs = [(seed0 + i, length) for i in range(n_asm)]
-    if workers > 1 and n_asm > 4:
-        pool = get_context("fork").Pool(workers)
-        try:
-            rows = pool.map(_make_one, jobs, chunksize=max(1, min(16, n_asm // (workers * 4))))
-        finally:  # close + join, never terminate(): a SIGTERM to the workers wedges tools that hook signals (rocprofv3)
-            pool.close()
-            pool.join()
-    else:
-        rows = [_make_one(j) for j in jobs]
-    return [r[0] for r in rows], [r[1] for r in rows]
+    w = WorkloadStream(n_asm, seed0, length, workers)
+    w.upto(n_asm)
+    return w.ids, w.packed
 
 
 # ---- CPU baseline (runs before any GPU state exists; workers are forked) ------------------------------------------------
@@ -452,7 +475,7 @@ def secondary_legs() -> dict:
 
     out = {}
     for key, what, extra in SECONDARY:
-        argv = [sys.executable, str(Path(__file__).resolve()), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+        argv = [sys.executable, str(Path(__file__).resolve()), "--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
                 "--no-e2e", "--no-secondary", *extra]
         t = time.perf_counter()
         try:
@@ -469,6 +492,46 @@ def secondary_legs() -> dict:
         except Exception as e:  # noqa: BLE001  (a secondary leg never costs the headline its line)
             out[key] = {"workload": what, "error": repr(e)[:300]}
     return out
+
+
+DUMP_SAMPLE = 1024  # assemblies whose kept gene hits --dump-outputs writes (a fixed, seeded choice)
+DUMP_LIMIT = 64 << 20
+ASM_COLUMNS = ("best_locus", "best_score", "completeness", "percent_identity", "percent_coverage", "length_discrepancy", "typeable",
+               "problems", "n_hits", "n_pieces")
+HIT_COLUMNS = ("gene", "contig", "q_start", "q_end", "t_start", "t_end", "score", "pident", "coverage", "strand", "state", "flags")
+
+
+def dump_outputs(out: Path, res: list, db_names: list, collect_order: list) -> None:
+    """What the timed path returned in its last step, as DIR/<database>_<column>.npy in float64 (every value is exact there):
+    each BatchTyping column of every assembly (length_discrepancy 0 where the product reports none: the locus is in more
+    than one piece), and the kept gene hits (what a result's gene_hits / states / identities are made from) of a seeded
+    sample of assemblies, with the index of the assembly each belongs to."""
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {}
+    for j, k in enumerate(collect_order):
+        bts = res[j :: len(collect_order)]  # run_pass appends batch by batch, the databases in collect_order
+        name = db_names[k]
+        for c in ASM_COLUMNS:
+            arrays[f"{name}_{c}"] = np.concatenate([np.asarray(getattr(bt, c), np.float64) for bt in bts])
+        arrays[f"{name}_length_discrepancy"] = np.nan_to_num(arrays[f"{name}_length_discrepancy"], nan=0.0)
+        n = len(arrays[f"{name}_best_locus"])
+        pick = np.sort(np.random.default_rng(0).choice(n, min(n, DUMP_SAMPLE), replace=False))
+        starts = np.cumsum([0] + [len(bt) for bt in bts])
+        hits = {c: [] for c in ("assembly", *HIT_COLUMNS)}
+        for a in pick:
+            b = int(np.searchsorted(starts, a, side="right")) - 1
+            bt, i = bts[b], int(a - starts[b])
+            kept = bt.kept[i][bt.alive[i]]
+            hits["assembly"].append(np.full(len(kept), a, np.float64))
+            for c in HIT_COLUMNS:
+                hits[c].append(kept[c].astype(np.float64))
+        for c, parts in hits.items():
+            arrays[f"{name}_hit_{c}"] = np.concatenate(parts)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes, more than the {DUMP_LIMIT} allowed")
+    for key, a in arrays.items():
+        np.save(out / f"{key}.npy", a)
 
 
 def rank_seed0(rank: int, assemblies_per_rank: int) -> int:
@@ -520,15 +583,22 @@ def main() -> None:
     ap.add_argument("--mix", choices=("plain", "joins"), default="plain",
                     help="joins: every fourth assembly with three 64-300 base insertions / deletions inside genes, every fourth with a "
                          "storm of six 33-300 base events in its locus (the kernels of kp_join.hip get work)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: CPU baseline and ingest rates, the end-to-end and command-line legs, "
+                         "per-kernel, roofline and DP figures, host use per rank, row digests and the secondary legs (the --no-* "
+                         "options below switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (float64): per-assembly columns of "
+                         "every database, and the kept gene hits of a fixed, seeded sample of 1024 assemblies")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the short secondary legs (config 4, the non-iid background, the join-heavy mix), each a run of this script of its own")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the two end-to-end legs (host shards -> rows)")
+                    help="--full: skip the short secondary legs (config 4, the non-iid background, the join-heavy mix), each a run of this script of its own")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and ingest rates")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the two end-to-end legs (host shards -> rows)")
     ap.add_argument("--upload-ahead", type=int, default=2,
                     help="end-to-end legs: uploads enqueued this many shards beyond the alignment passes in flight (the copy "
                          "engine must never wait for the driving thread, which spends most of its time waiting for results)")
-    ap.add_argument("--no-cli", action="store_true", help="skip the command-line leg (FASTA files on tmpfs -> `kaptive_amd assembly` -> TSV)")
-    ap.add_argument("--e2e-steps", type=int, default=3, help="steps per end-to-end leg (back to back: the pipeline fills and drains once per leg)")
+    ap.add_argument("--no-cli", action="store_true", help="--full: skip the command-line leg (FASTA files on tmpfs -> `kaptive_amd assembly` -> TSV)")
+    ap.add_argument("--e2e-steps", type=int, default=3, help="--full: steps per end-to-end leg (back to back: the pipeline fills and drains once per leg)")
     ap.add_argument("--workers", type=int, default=0, help="processes for workload generation (0 = auto, 1 = inline)")
     ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl",
                     help="torch.distributed backend of the barrier and the max-over-ranks of the elapsed time (nccl = RCCL)")
@@ -565,7 +635,10 @@ def main() -> None:
     from kaptive_amd import affinity
 
     placement = affinity.place(local_rank, list(range(world))) if world > 1 and not args.share_gpu else affinity.place(local_rank)
-    workers = args.workers or max(1, min(64, len(os.sched_getaffinity(0)) if world > 1 else (os.cpu_count() or 1) // max(world, 1)))
+    from kaptive_amd import usable_cpus
+
+    # (one worker per CPU the process is granted: a pool sized by the host's CPU count only adds switching)
+    workers = args.workers or max(1, min(64, len(os.sched_getaffinity(0)) if world > 1 else usable_cpus()))
     # torch (and with it the HIP runtime it bundles) has to be loaded before libkaptive_amd.so, which the packer below
     # already needs: in the other order the process ends up with two HIP runtimes and sees no device
     import torch  # noqa: F401
@@ -580,16 +653,19 @@ def main() -> None:
         raise SystemExit("--as-rank is for single-process runs")
     seed0 = rank_seed0(args.as_rank if args.as_rank >= 0 else rank, args.assemblies)
     t_gen = time.perf_counter()
-    ids, packed = build_workload(args.assemblies, seed0, length, workers)
-    t_gen = time.perf_counter() - t_gen
+    gen = WorkloadStream(args.assemblies, seed0, length, workers)
+    ids, packed = gen.ids, gen.packed  # (filled in seed order by gen.upto)
     cpu = ingest = cli_prep = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(seed0, length)
-        ingest = ingest_rate(seed0, length)
-    if world == 1 and rank == 0 and not args.no_e2e and not args.no_cli:
-        cli_prep = cli_prepare(seed0, length, workers)
-        if ingest is not None:
-            ingest.update(shard_ingest_rate(cli_prep))
+    if args.full:  # the CPU legs fork processes of their own and must have the host to themselves
+        gen.upto(args.assemblies)
+        t_gen = time.perf_counter() - t_gen
+        if world == 1 and rank == 0 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(seed0, length)
+            ingest = ingest_rate(seed0, length)
+        if world == 1 and rank == 0 and not args.no_e2e and not args.no_cli:
+            cli_prep = cli_prepare(seed0, length, workers)
+            if ingest is not None:
+                ingest.update(shard_ingest_rate(cli_prep))
 
     import torch
     import torch.distributed as dist
@@ -609,19 +685,21 @@ def main() -> None:
     torch.cuda.init()
     torch.zeros(1, device="cuda")
     torch.cuda.synchronize()
-    # the box's own device-copy rate (read + write), quoted beside the 8 TB/s of the data sheet
-    src_t = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
-    dst_t = torch.empty_like(src_t)
-    dst_t.copy_(src_t)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(8):
+    copy_gbps = None
+    if args.full:
+        # the box's own device-copy rate (read + write), quoted beside the 8 TB/s of the data sheet
+        src_t = torch.empty(1 << 30, dtype=torch.uint8, device="cuda")
+        dst_t = torch.empty_like(src_t)
         dst_t.copy_(src_t)
-    e1.record()
-    torch.cuda.synchronize()
-    copy_gbps = 8 * 2 * src_t.numel() / (e0.elapsed_time(e1) * 1e-3) / 1e9
-    del src_t, dst_t
-    torch.cuda.empty_cache()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(8):
+            dst_t.copy_(src_t)
+        e1.record()
+        torch.cuda.synchronize()
+        copy_gbps = 8 * 2 * src_t.numel() / (e0.elapsed_time(e1) * 1e-3) / 1e9
+        del src_t, dst_t
+        torch.cuda.empty_cache()
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if args.dist_backend == "nccl":
@@ -636,9 +714,8 @@ def main() -> None:
         torch.cuda.synchronize()
 
     dbs = [d for d in (_DBS["main"], _DBS["also"]) if d is not None]
-    n_batches = max(1, (len(packed) + args.batch - 1) // args.batch)
-    spans = [shard_bounds(len(packed), i, n_batches) for i in range(n_batches)]
-    batch_ids = [ids[lo:hi] for lo, hi in spans]
+    n_batches = max(1, (args.assemblies + args.batch - 1) // args.batch)
+    spans = [shard_bounds(args.assemblies, i, n_batches) for i in range(n_batches)]
     shared = len(dbs) > 1 and not args.separate_passes
     if shared:  # one context, one seed index over the genes of all databases; engines[k] = the engine as database k sees it
         both = Engine(dbs, device=local_rank)
@@ -730,12 +807,18 @@ def main() -> None:
         for b in reversed(distinct(bs)):
             b.close()
 
-    resident = [make_batches(i) for i in range(n_batches)]
+    resident = []
+    for i, (lo, hi) in enumerate(spans):  # each shard goes to the device as soon as its assemblies are made
+        gen.upto(hi)
+        resident.append(make_batches(i))
+    if not args.full:
+        t_gen = time.perf_counter() - t_gen  # (device set-up included: it ran beside the generation)
+    batch_ids = [ids[lo:hi] for lo, hi in spans]
     # (untimed) buffer sizing: the first pass of a context learns its work-buffer sizes and reruns until they fit; it also
     # takes every first-call cost of the measurement itself (event timing, statistics) out of the warm-up steps
-    run_pass(lambda i: resident[i], record=True)
+    run_pass(lambda i: resident[i], record=args.full)
     for _ in range(args.warmup):
-        run_pass(lambda i: resident[i], record=True)
+        run_pass(lambda i: resident[i], record=args.full)
     for lst in (*prof, *stats):
         lst.clear()
     sync_all()
@@ -746,43 +829,48 @@ def main() -> None:
     step_ms = []
     for _ in range(args.steps):
         t_step = time.perf_counter()
-        res = run_pass(lambda i: resident[i], record=True)
+        res = run_pass(lambda i: resident[i], record=args.full)
         step_ms.append(round((time.perf_counter() - t_step) * 1e3, 2))  # host view, no synchronisation added
     sync_all()
     elapsed = time.perf_counter() - t0
     host_busy = (time.thread_time() - cpu0) / max(elapsed, 1e-9)
-    import resource
-
-    host_rank = {"rank": rank, "numa_node": placement["numa_node"], "cpus_pinned": len(placement["cpus"] or []) if placement["applied"] else None,
-                 "driving_thread_cpu_s": round(time.thread_time() - cpu0, 3),
-                 "process_cpu_s": round(time.process_time() - proc0, 3), "elapsed_s": round(elapsed, 3),
-                 "max_rss_MB": round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024, 1),
-                 "pinned_host_MB": round(_native.pinned_bytes() / 2**20, 1),
-                 "buffer_growth_reruns_in_timed_steps": [sum(x["retries"] for x in slist) for slist in stats],
-                 "device_reallocations_in_timed_steps": _native.device_allocations() - allocs0}
-    # (untimed) the alignment kernels of one batch with nothing else on the device: what a launch takes on its own; in
-    # the timed steps the passes of consecutive batches overlap and stretch each other's kernels
-    alone = []
-    for bs in resident[: min(2, n_batches)]:
-        for b in distinct(bs)[:1]:
-            b.align_async()
-            b.wait()
-            alone.append(b.profile())
-    sync_all()
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        digests = [None] * world  # every rank's row digest, so that rank 0 can report what the whole job typed
-        dist.all_gather_object(digests, hashlib.sha1(b"".join(sorted(r for bt in res for r in bt.tsv().splitlines(keepends=True)))).hexdigest())
-        host_ranks = [None] * world  # what every rank took of the host while the clock ran
-        dist.all_gather_object(host_ranks, host_rank)
-    else:
-        host_ranks = [host_rank]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), res, [d.metadata.keyword for d in dbs], collect_order)
+
+    if args.full:
+        import resource
+
+        host_rank = {"rank": rank, "numa_node": placement["numa_node"], "cpus_pinned": len(placement["cpus"] or []) if placement["applied"] else None,
+                     "driving_thread_cpu_s": round(time.thread_time() - cpu0, 3),
+                     "process_cpu_s": round(time.process_time() - proc0, 3), "elapsed_s": round(elapsed, 3),
+                     "max_rss_MB": round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024, 1),
+                     "pinned_host_MB": round(_native.pinned_bytes() / 2**20, 1),
+                     "buffer_growth_reruns_in_timed_steps": [sum(x["retries"] for x in slist) for slist in stats],
+                     "device_reallocations_in_timed_steps": _native.device_allocations() - allocs0}
+        # (untimed) the alignment kernels of one batch with nothing else on the device: what a launch takes on its own; in
+        # the timed steps the passes of consecutive batches overlap and stretch each other's kernels
+        alone = []
+        for bs in resident[: min(2, n_batches)]:
+            for b in distinct(bs)[:1]:
+                b.align_async()
+                b.wait()
+                alone.append(b.profile())
+        sync_all()
+        if world > 1:
+            digests = [None] * world  # every rank's row digest, so that rank 0 can report what the whole job typed
+            dist.all_gather_object(digests, hashlib.sha1(b"".join(sorted(r for bt in res for r in bt.tsv().splitlines(keepends=True)))).hexdigest())
+            host_ranks = [None] * world  # what every rank took of the host while the clock ran
+            dist.all_gather_object(host_ranks, host_rank)
+        else:
+            host_ranks = [host_rank]
 
     # ---- legs 2 and 3: from pinned host shards, without and with TSV bytes (one GPU only) -------------------------------------
     e2e = None
-    if world == 1 and not args.no_e2e:
+    if args.full and world == 1 and not args.no_e2e:
         for bs in resident:
             close_all(bs)
         resident = []
@@ -858,36 +946,6 @@ def main() -> None:
 
     if rank == 0:
         n_total = args.assemblies * world * args.steps
-        scan_all = [p["scan"] for p in prof[0]]
-        scan_ms = float(np.mean(scan_all))
-        scan_bytes = float(np.mean([p["bytes_scanned"] for p in prof[0]]))
-        achieved = scan_bytes / (scan_ms * 1e-3) / 1e9
-        pmc = offline_pmc(args)
-        if pmc and pmc.get("tcc_req_per_launch"):
-            l2_req, l2_src = float(pmc["tcc_req_per_launch"]), "TCC_REQ_sum of the offline PMC collection (all of the kernel's L2 requests)"
-        else:
-            l2_req, l2_src = scan_bytes * 4.0 * 2.0 / 11.0, "estimate: one probe per seed, 2 / 11 of the bases"
-        scan_alone_ms = float(np.mean([p["scan"] for p in alone]))
-        fill_alone_ms = float(np.mean([p["sw16"] for p in alone]))
-        # per database: kernel milliseconds per step (sum over the step's batches, mean over steps)
-        mean_ms = [{k: float(np.sum([p[k] for p in plist])) / args.steps for k in plist[0] if k != "bytes_scanned"}
-                   for plist in prof]
-        sw_ms = sum(m["sw16"] + m["sw32"] + m["sw64"] + m["sw128"] for m in mean_ms)
-        per_step = [{k: sum(s[k] for s in slist) // args.steps for k in slist[0]} for slist in stats]
-        cells = sum(s["dp_cells"] for s in per_step)
-        typed = int(sum(bt.typeable.sum() for bt in res))
-        # a wave steps 2 x 64/P tasks of 4P diagonals each: 512 cells per wave-step whatever P
-        wave_steps = cells / n_batches / 512.0  # (cells: per step, all batches)
-        need = wave_steps * FILL_CYCLES_PER_WAVE_STEP / (256 * 4)
-        have_cycles = fill_alone_ms * 1e-3 * FILL_CLOCK_HZ
-        fill_model = {"cycles_per_wave_step": FILL_CYCLES_PER_WAVE_STEP, "wave_steps_per_launch": wave_steps,
-                      "ms_per_launch_alone": fill_alone_ms, "clock_hz": FILL_CLOCK_HZ,
-                      "simd_cycles_needed": need, "simd_cycles_available": have_cycles, "frac": need / have_cycles}
-        t_rows = time.perf_counter()
-        blobs = [bt.tsv() for bt in res]  # TSV bytes of the last step
-        t_rows = time.perf_counter() - t_rows
-        rows = [r for blob in blobs for r in blob.splitlines(keepends=True)]
-        rows_digest = hashlib.sha1(b"".join(sorted(rows))).hexdigest()  # same workload -> same digest, whatever the schedule
         what = ("typed against the synthetic K-locus database, then the O-locus database" if len(dbs) == 2
                 else "typed against the synthetic A. baumannii K-locus database (~1 500 contigs per assembly)")
         line = {
@@ -922,6 +980,41 @@ def main() -> None:
                 "batch": args.batch,
                 "databases": [f"{d.metadata.keyword}: {len(d.loci)} loci / {len(d.genes)} genes" for d in dbs],
                 "parallelism": f"{world} x independent shard, no collective",
+                "workload_generation_s": round(t_gen, 1),
+            },
+        }  # fmt: skip
+        if args.full:
+            scan_all = [p["scan"] for p in prof[0]]
+            scan_ms = float(np.mean(scan_all))
+            scan_bytes = float(np.mean([p["bytes_scanned"] for p in prof[0]]))
+            achieved = scan_bytes / (scan_ms * 1e-3) / 1e9
+            pmc = offline_pmc(args)
+            if pmc and pmc.get("tcc_req_per_launch"):
+                l2_req, l2_src = float(pmc["tcc_req_per_launch"]), "TCC_REQ_sum of the offline PMC collection (all of the kernel's L2 requests)"
+            else:
+                l2_req, l2_src = scan_bytes * 4.0 * 2.0 / 11.0, "estimate: one probe per seed, 2 / 11 of the bases"
+            scan_alone_ms = float(np.mean([p["scan"] for p in alone]))
+            fill_alone_ms = float(np.mean([p["sw16"] for p in alone]))
+            # per database: kernel milliseconds per step (sum over the step's batches, mean over steps)
+            mean_ms = [{k: float(np.sum([p[k] for p in plist])) / args.steps for k in plist[0] if k != "bytes_scanned"}
+                       for plist in prof]
+            sw_ms = sum(m["sw16"] + m["sw32"] + m["sw64"] + m["sw128"] for m in mean_ms)
+            per_step = [{k: sum(s[k] for s in slist) // args.steps for k in slist[0]} for slist in stats]
+            cells = sum(s["dp_cells"] for s in per_step)
+            typed = int(sum(bt.typeable.sum() for bt in res))
+            # a wave steps 2 x 64/P tasks of 4P diagonals each: 512 cells per wave-step whatever P
+            wave_steps = cells / n_batches / 512.0  # (cells: per step, all batches)
+            need = wave_steps * FILL_CYCLES_PER_WAVE_STEP / (256 * 4)
+            have_cycles = fill_alone_ms * 1e-3 * FILL_CLOCK_HZ
+            fill_model = {"cycles_per_wave_step": FILL_CYCLES_PER_WAVE_STEP, "wave_steps_per_launch": wave_steps,
+                          "ms_per_launch_alone": fill_alone_ms, "clock_hz": FILL_CLOCK_HZ,
+                          "simd_cycles_needed": need, "simd_cycles_available": have_cycles, "frac": need / have_cycles}
+            t_rows = time.perf_counter()
+            blobs = [bt.tsv() for bt in res]  # TSV bytes of the last step
+            t_rows = time.perf_counter() - t_rows
+            rows = [r for blob in blobs for r in blob.splitlines(keepends=True)]
+            rows_digest = hashlib.sha1(b"".join(sorted(rows))).hexdigest()  # same workload -> same digest, whatever the schedule
+            line["config"].update({
                 "typeable_in_last_step": typed,
                 "tsv_rows_per_s_host": round(len(rows) / max(t_rows, 1e-9), 1),
                 "tsv_rows_sha1": rows_digest,
@@ -930,10 +1023,9 @@ def main() -> None:
                 "host_per_rank": host_ranks,
                 "host_cores": len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count(),
                 "buffer_growth_reruns_in_timed_steps": [sum(s["retries"] for s in slist) for slist in stats],
-                "workload_generation_s": round(t_gen, 1),
-            },
-            "e2e": e2e,
-            "roofline": {
+            })
+            line["e2e"] = e2e
+            line["roofline"] = {
                 "bound": "hbm", "kernel": "kp_scan_dense_kernel (" + ("pass over K and O genes" if shared else "K database pass") + ")", "achieved": achieved, "peak": HBM_PEAK_GBPS,
                 "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
                 "device_copy_GBps_measured": round(copy_gbps, 1),  # torch copy of 1 GiB, read + write bytes
@@ -950,8 +1042,8 @@ def main() -> None:
                 "l2_requests": {"per_launch": l2_req, "per_launch_source": l2_src, "rate_alone_G_per_s": l2_req / (scan_alone_ms * 1e-3) / 1e9,
                                 "measured_roof_G_per_s": L2_GATHER_ROOF_G, "frac_alone": l2_req / (scan_alone_ms * 1e-3) / 1e9 / L2_GATHER_ROOF_G,
                                 "roof_source": "profiles/l2_gather_r2.txt (2 MB table, 8 loads in flight per lane)"},
-            },
-            "dp": {
+            }
+            line["dp"] = {
                 "kernel": "kp_sw_kernel", "cells_per_step": [s["dp_cells"] for s in per_step],
                 "ms_per_step": sw_ms, "gcups": cells / (sw_ms * 1e-3) / 1e9 if sw_ms > 0 else None,
                 "tasks_per_step": [s["tasks"] for s in per_step], "anchors_per_step": [s["anchors"] for s in per_step],
@@ -964,15 +1056,14 @@ def main() -> None:
                 # isa_cost.py with the per-opcode costs measured by tools/microbench/valu_rate*.hip) over the SIMD cycles
                 # the launch had, at the shader clock the PMC run saw (GRBM_GUI_ACTIVE / duration, profiles/)
                 "fill_issue_model": fill_model,
-            },
-            "kernel_ms_per_step": {k: [round(m[k], 3) for m in mean_ms] for k in ("scan", "sort", "chain", "sw16", "sw32")},
-        }  # fmt: skip
-        line["kernel_ms_per_step"]["join_fill_and_walk"] = [round(m["sw64"], 3) for m in mean_ms]  # (kp_join.hip; its chaining kernel is part of "chain")
-        if cpu is not None:
-            line["cpu_baseline"] = cpu
-            line["ingest"] = ingest
-        if world == 1 and not args.no_secondary and not args.no_e2e:
-            line["extra"] = secondary_legs()
+            }
+            line["kernel_ms_per_step"] = {k: [round(m[k], 3) for m in mean_ms] for k in ("scan", "sort", "chain", "sw16", "sw32")}
+            line["kernel_ms_per_step"]["join_fill_and_walk"] = [round(m["sw64"], 3) for m in mean_ms]  # (kp_join.hip; its chaining kernel is part of "chain")
+            if cpu is not None:
+                line["cpu_baseline"] = cpu
+                line["ingest"] = ingest
+            if world == 1 and not args.no_secondary and not args.no_e2e:
+                line["extra"] = secondary_legs()
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.barrier()

@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT; OUT=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $OUT
 (cd build/old_tree && python -m kaptive_amd.build > $OUT/fab2_old_build.log 2>&1)
 run() { name=$1; dir=$2; shift 2
-  (cd $dir && env "$@" python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --workers 16 > $OUT/fab2_$name.log 2> $OUT/fab2_$name.err)
+  (cd $dir && env "$@" python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --workers 16 > $OUT/fab2_$name.log 2> $OUT/fab2_$name.err)
   python - $OUT/fab2_$name.log $name <<'PY'
 import json, sys
 line = [l for l in open(sys.argv[1]) if l.startswith("{")]

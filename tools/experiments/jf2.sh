@@ -16,7 +16,7 @@ for r in rows[i0:i0+22]:
         print(f"{s:10.1f} {e:10.1f} {e-s:9.1f} {n}")
 PY
 run() { name=$1; shift
-  env "$@" python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --no-secondary --workers 16 > $OUT/jf2_$name.log 2> $OUT/jf2_$name.err
+  env "$@" python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --no-secondary --workers 16 > $OUT/jf2_$name.log 2> $OUT/jf2_$name.err
   python - $OUT/jf2_$name.log $name <<'PY'
 import json, sys
 line = [l for l in open(sys.argv[1]) if l.startswith("{")]

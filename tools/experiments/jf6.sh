@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT; OUT=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $OUT
 timeout 900 python -m pytest tests -m gpu -x -q -k "join or long or beyond or occurrence" 2>&1 | tail -2
 run() { name=$1; shift; extra=$1; shift
-  env "$@" python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --no-secondary --workers 16 $extra > $OUT/jf6_$name.log 2> $OUT/jf6_$name.err
+  env "$@" python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --no-secondary --workers 16 $extra > $OUT/jf6_$name.log 2> $OUT/jf6_$name.err
   python - $OUT/jf6_$name.log $name <<'PY'
 import json, sys
 line = [l for l in open(sys.argv[1]) if l.startswith("{")]

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT; OUT=gpurun_out; mkdir -p $OUT
 N=${1:-10000}
 run() { name=$1; shift
-  env "$@" python bench.py --assemblies $N --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --no-secondary --workers 16 $EXTRA > $OUT/jab_$name.log 2> $OUT/jab_$name.err
+  env "$@" python bench.py --full --assemblies $N --steps 3 --warmup 1 --no-cpu-baseline --no-e2e --no-secondary --workers 16 $EXTRA > $OUT/jab_$name.log 2> $OUT/jab_$name.err
   python - $OUT/jab_$name.log $name <<'PY'
 import json, sys
 line = [l for l in open(sys.argv[1]) if l.startswith("{")]

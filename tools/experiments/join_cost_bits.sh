@@ -3,7 +3,7 @@
 # 1 = no chaining of groups, 2 = no joined fill, 4 = no walk-back; twice each, interleaved
 cd $GRAFT_REPO_ROOT; OUT=gpurun_out; mkdir -p $OUT
 run() { name=$1; shift
-  env "$@" python bench.py --assemblies 10000 --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --no-secondary --workers 16 > $OUT/jbits_$name.log 2> $OUT/jbits_$name.err
+  env "$@" python bench.py --full --assemblies 10000 --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --no-secondary --workers 16 > $OUT/jbits_$name.log 2> $OUT/jbits_$name.err
   python - $OUT/jbits_$name.log $name <<'PY'
 import json, sys
 line = [l for l in open(sys.argv[1]) if l.startswith("{")]

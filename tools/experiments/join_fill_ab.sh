@@ -2,7 +2,7 @@
 # round 6: what about the joined fill costs the headline workload (20 joins per batch): grid, wave priority, the launch itself
 cd $GRAFT_REPO_ROOT; OUT=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $OUT
 run() { name=$1; shift
-  env "$@" python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --no-secondary --workers 16 > $OUT/jf_$name.log 2> $OUT/jf_$name.err
+  env "$@" python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --no-secondary --workers 16 > $OUT/jf_$name.log 2> $OUT/jf_$name.err
   python - $OUT/jf_$name.log $name <<'PY'
 import json, sys
 line = [l for l in open(sys.argv[1]) if l.startswith("{")]

@@ -7,7 +7,7 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $OUT; cd $GRAFT_REPO_ROOT
 for v in "$@"; do
   name=${v%%=*}; flags=${v#*=}
   KAPTIVE_AMD_EXTRA_FLAGS="$flags" python -m kaptive_amd.build --force > $OUT/${TAG}_${name}_build.log 2>&1 || { tail -5 $OUT/${TAG}_${name}_build.log; continue; }
-  python bench.py --assemblies ${AB_N:-3000} --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --workers 16 $AB_EXTRA > $OUT/${TAG}_${name}.log 2> $OUT/${TAG}_${name}.err
+  python bench.py --full --assemblies ${AB_N:-3000} --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --workers 16 $AB_EXTRA > $OUT/${TAG}_${name}.log 2> $OUT/${TAG}_${name}.err
   python - $OUT/${TAG}_${name}.log $name <<'PY'
 import json, sys
 line = [l for l in open(sys.argv[1]) if l.startswith("{")]

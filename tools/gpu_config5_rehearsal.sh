@@ -5,7 +5,7 @@
 cd $GRAFT_REPO_ROOT; OUT=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $OUT
 free -g | head -2; nproc; cat /sys/fs/cgroup/cpu.max 2>/dev/null
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-timeout 1700 python -m torch.distributed.run --nnodes=1 --nproc-per-node=8 --master-addr 127.0.0.1 --master-port 29533 bench.py \
+timeout 1700 python -m torch.distributed.run --nnodes=1 --nproc-per-node=8 --master-addr 127.0.0.1 --master-port 29533 bench.py --full \
   --gpus 8 --assemblies-total 8000 --batch 500 --steps 1 --warmup 1 --no-cpu-baseline --dist-backend gloo --share-gpu --workers 2 \
   > $OUT/config5_rehearsal.log 2> $OUT/config5_rehearsal.err
 tail -3 $OUT/config5_rehearsal.err | cut -c1-300

@@ -11,10 +11,10 @@ for what in "$@"; do
     tests)
       timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/${TAG}_tests.log 2>&1; tail -5 $OUT/${TAG}_tests.log;;
     bench)
-      timeout 900 python bench.py --assemblies 3000 --steps 4 --warmup 1 --no-cpu-baseline $BENCH_EXTRA > $OUT/${TAG}_bench.log 2> $OUT/${TAG}_bench.err
+      timeout 900 python bench.py --full --assemblies 3000 --steps 4 --warmup 1 --no-cpu-baseline $BENCH_EXTRA > $OUT/${TAG}_bench.log 2> $OUT/${TAG}_bench.err
       tail -c 2500 $OUT/${TAG}_bench.log; tail -3 $OUT/${TAG}_bench.err;;
     full)
-      timeout 1500 python bench.py > $OUT/${TAG}_full.log 2> $OUT/${TAG}_full.err
+      timeout 1500 python bench.py --full > $OUT/${TAG}_full.log 2> $OUT/${TAG}_full.err
       tail -c 4000 $OUT/${TAG}_full.log; tail -3 $OUT/${TAG}_full.err;;
     trace)
       (cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace -- python $GRAFT_REPO_ROOT/bench.py $SMALL > $OUT/${TAG}_trace.log 2>&1)
