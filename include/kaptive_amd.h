@@ -57,9 +57,12 @@ KP_API const char *kp_last_error(const kp_ctx *ctx);
  * stream of the work set they take, so that the passes of consecutive batches overlap; their stage times: kp_batch_profile.) */
 KP_API void *kp_ctx_stream(kp_ctx *ctx);
 /* Tuning knobs.  Defaults are read from the environment once, in kp_ctx_create (KAPTIVE_AMD_<NAME in upper case>);
- * names: anchor_cap, tasks_per_asm, hit_cap, trace_kb_per_asm, kept_cap, piece_cap, prot_cap (initial sizes of the work
- * buffers; trace_kb_per_asm: direction bits of the banded Smith-Waterman, KiB per assembly of a batch -- setting
- * one also forgets what the context has learnt for it), library_sort (anchors are sorted by the library's segmented radix sort instead of
+ * names: anchor_cap, tasks_per_asm, hit_cap, trace_kb_per_asm, cand_cap, group_cap, join_cap, occ_slots, kept_cap,
+ * piece_cap, prot_cap (initial sizes of the work buffers, at least 1; trace_kb_per_asm: direction bits of the banded
+ * Smith-Waterman, KiB per assembly of a batch; cand_cap: seed candidates of the scan, entries per batch -- unset, both are
+ * sized from the batch with a floor of 64 Ki entries and 64 KiB; group_cap, join_cap: groups of clusters and joins per
+ * band class of a batch; occ_slots: counting tables of the occurrence cut, at most 65536 -- setting one also forgets
+ * what the context has learnt for it), library_sort (anchors are sorted by the library's segmented radix sort instead of
  * the bucket sort of kp_bsort.hip; same result), scan_mode (ablation modes of the scan kernel, tools/scan_ablate.py). */
 KP_API int kp_ctx_set_option(kp_ctx *ctx, const char *name, int64_t value);
 #define KP_WORK_SLOTS 3

@@ -129,10 +129,17 @@ struct KpTypingRun {
 
 struct kp_batch;
 
+// most counting tables of the occurrence cut a pass may hold (kp_chain.hip: block_mid_occ); a batch in which more assemblies
+// need their own mid_occ fails with KP_EOVERFLOW
+constexpr uint32_t KP_OCC_SLOTS_MAX = 1u << 16;
+
 // Options of a context: defaults come from the environment once, at kp_ctx_create; kp_ctx_set_option changes them.
 struct KpOptions {
     uint32_t anchor_cap = 1u << 17, tasks_per_asm = 4096, hit_cap = 4096;
     uint32_t trace_kb_per_asm = 2048;  // first guess for the DP trace buffer (a 5 Mbp K-locus assembly needs ~12 MB)
+    uint64_t cand_cap = 0;             // first candidate list of a pass (entries); 0: sized from the batch (size_work)
+    uint32_t group_cap = 1024, join_cap = 1024, occ_slots = 2;
+    bool trace_set = false;            // trace_kb_per_asm was given (environment or kp_ctx_set_option): no floor under it
     uint32_t kept_cap = 256, piece_cap = 32, prot_cap = 32768;
     int scan_mode = 0;           // KAPTIVE_AMD_SCAN_ABLATE (tools/scan_ablate.py)
     int library_sort = 0;        // anchors through kp_anchor_compact + rocPRIM's segmented radix sort instead of kp_bsort.hip
@@ -331,7 +338,7 @@ struct kp_ctx {
                                  // work set that meets a slightly larger batch than before does not re-allocate (and stall)
     uint64_t trace_units_per_asm = 0;  // trace buffer of a pass = n_asm * this many 16-byte units
     uint32_t group_cap = 0, join_cap = 0;  // group / join lists of a pass (entries; joins per band class)
-    uint32_t occ_slots = 2;                // counting tables of the occurrence cut's quantile a pass may use (learnt like the list sizes)
+    uint32_t occ_slots = 0;                // counting tables of the occurrence cut's quantile a pass may use (learnt like the list sizes)
     // resident database
     bool has_db = false;
     int32_t n_genes = 0;
@@ -415,6 +422,11 @@ void options_from_env(KpOptions &o) {
     o.tasks_per_asm = env_u32("KAPTIVE_AMD_TASKS_PER_ASM", o.tasks_per_asm);
     o.hit_cap = env_u32("KAPTIVE_AMD_HIT_CAP", o.hit_cap);
     o.trace_kb_per_asm = env_u32("KAPTIVE_AMD_TRACE_KB_PER_ASM", o.trace_kb_per_asm);
+    o.trace_set = env_u32("KAPTIVE_AMD_TRACE_KB_PER_ASM", 0) != 0;
+    o.cand_cap = env_u32("KAPTIVE_AMD_CAND_CAP", 0);
+    o.group_cap = env_u32("KAPTIVE_AMD_GROUP_CAP", o.group_cap);
+    o.join_cap = env_u32("KAPTIVE_AMD_JOIN_CAP", o.join_cap);
+    o.occ_slots = env_u32("KAPTIVE_AMD_OCC_SLOTS", o.occ_slots);
     o.kept_cap = env_u32("KAPTIVE_AMD_KEPT_CAP", o.kept_cap);
     o.piece_cap = env_u32("KAPTIVE_AMD_PIECE_CAP", o.piece_cap);
     o.prot_cap = env_u32("KAPTIVE_AMD_PROT_CAP", o.prot_cap);
@@ -775,7 +787,11 @@ int kp_ctx_set_option(kp_ctx *ctx, const char *name, int64_t value) {
     if (n == "anchor_cap") { o.anchor_cap = (uint32_t)std::max<int64_t>(value, 1); ctx->anchor_cap = 0; }
     else if (n == "tasks_per_asm") { o.tasks_per_asm = (uint32_t)std::max<int64_t>(value, 1); ctx->tasks_per_asm = 0; }
     else if (n == "hit_cap") { o.hit_cap = (uint32_t)std::max<int64_t>(value, 1); ctx->hit_cap = 0; }
-    else if (n == "trace_kb_per_asm") { o.trace_kb_per_asm = (uint32_t)std::max<int64_t>(value, 1); ctx->trace_units_per_asm = 0; }
+    else if (n == "trace_kb_per_asm") { o.trace_kb_per_asm = (uint32_t)std::max<int64_t>(value, 1); o.trace_set = true; ctx->trace_units_per_asm = 0; }
+    else if (n == "cand_cap") { o.cand_cap = (uint64_t)std::max<int64_t>(value, 1); ctx->cand_frac = 0.0; }
+    else if (n == "group_cap") { o.group_cap = (uint32_t)std::max<int64_t>(value, 1); ctx->group_cap = 0; }
+    else if (n == "join_cap") { o.join_cap = (uint32_t)std::max<int64_t>(value, 1); ctx->join_cap = 0; }
+    else if (n == "occ_slots") { o.occ_slots = (uint32_t)std::max<int64_t>(std::min<int64_t>(value, KP_OCC_SLOTS_MAX), 1); ctx->occ_slots = 0; }
     else if (n == "kept_cap") { o.kept_cap = (uint32_t)std::max<int64_t>(value, 1); for (auto &c : ctx->run_caps) c.kept_cap = 0; }
     else if (n == "piece_cap") { o.piece_cap = (uint32_t)std::max<int64_t>(value, 1); for (auto &c : ctx->run_caps) c.piece_cap = 0; }
     else if (n == "prot_cap") { o.prot_cap = (uint32_t)std::max<int64_t>(value, 1); for (auto &c : ctx->run_caps) c.prot_cap = 0; }
@@ -1084,7 +1100,7 @@ static int enqueue_align(kp_ctx *ctx, kp_batch *b, KpWork *w) {
         uint32_t lg = 12;
         while (((uint64_t)1 << lg) < (uint64_t)b->max_asm_bases * 2 / 5 + 1 && lg < 31) ++lg;
         w->occ_log2 = lg;
-        w->occ_slots = std::max<uint32_t>(ctx->occ_slots, 2u);
+        w->occ_slots = std::max<uint32_t>(ctx->occ_slots, 1u);
         KP_HIP_CHECK(ctx, w->d_occ_keys.reserve((size_t)w->occ_slots << lg));
         KP_HIP_CHECK(ctx, w->d_occ_cnts.reserve((size_t)w->occ_slots << lg));
         KP_HIP_CHECK(ctx, w->d_occ_state.reserve(kp_occ_state_words(n_asm, w->occ_slots)));
@@ -1180,17 +1196,21 @@ static void size_work(kp_ctx *ctx, const kp_batch *b, KpWork *w) {
     if (ctx->anchor_cap == 0) ctx->anchor_cap = ctx->opt.anchor_cap;
     ctx->anchor_cap = std::max<uint32_t>((ctx->anchor_cap + KP_ANCHOR_SUBS - 1) / KP_ANCHOR_SUBS, 16u) * KP_ANCHOR_SUBS;
     if (ctx->tasks_per_asm == 0) ctx->tasks_per_asm = ctx->opt.tasks_per_asm;
-    if (ctx->cand_frac <= 0.0) ctx->cand_frac = 0.004;  // 2 / 11 of the positions are seeds; ~1 % of those pass both filters
+    if (ctx->cand_frac <= 0.0 && !ctx->opt.cand_cap) ctx->cand_frac = 0.004;  // 2 / 11 of the positions are seeds; ~1 % of those pass both filters
     if (ctx->hit_cap == 0) ctx->hit_cap = ctx->opt.hit_cap;
     w->anchor_cap = ctx->anchor_cap;
     w->task_cap = (uint32_t)std::min<uint64_t>((uint64_t)std::max(b->n_asm, 1) * ctx->tasks_per_asm, 1u << 28);
     ctx->words_hw = std::max(ctx->words_hw, b->view.total_words + b->view.total_words / 64);  // (batches of one stream differ by a per cent or so)
-    w->cand_cap = std::max<uint64_t>(1 << 16, (uint64_t)((double)ctx->words_hw * 4.0 * ctx->cand_frac));
+    // (an explicit cand_cap / trace_kb_per_asm is taken as it is: the floors below are for sizes guessed from the batch)
+    const uint64_t cand_learnt = (uint64_t)((double)ctx->words_hw * 4.0 * ctx->cand_frac);
+    w->cand_cap = ctx->opt.cand_cap ? std::max<uint64_t>(ctx->opt.cand_cap, cand_learnt) : std::max<uint64_t>(1 << 16, cand_learnt);
     w->hit_cap = ctx->hit_cap;
     if (ctx->trace_units_per_asm == 0) ctx->trace_units_per_asm = (uint64_t)ctx->opt.trace_kb_per_asm * 64;
-    w->trace_cap = std::max<uint64_t>(4096, (uint64_t)std::max(b->n_asm, 1) * ctx->trace_units_per_asm);
-    if (ctx->group_cap == 0) ctx->group_cap = 1024;
-    if (ctx->join_cap == 0) ctx->join_cap = 1024;
+    const uint64_t trace_units = (uint64_t)std::max(b->n_asm, 1) * ctx->trace_units_per_asm;
+    w->trace_cap = ctx->opt.trace_set ? std::min<uint64_t>(trace_units, 1ull << 32) : std::max<uint64_t>(4096, trace_units);
+    if (ctx->group_cap == 0) ctx->group_cap = ctx->opt.group_cap;
+    if (ctx->join_cap == 0) ctx->join_cap = ctx->opt.join_cap;
+    if (ctx->occ_slots == 0) ctx->occ_slots = std::min(ctx->opt.occ_slots, KP_OCC_SLOTS_MAX);
     w->group_cap = ctx->group_cap; w->join_cap = ctx->join_cap;
 }
 
@@ -1269,7 +1289,7 @@ int kp_batch_wait(kp_ctx *ctx, kp_batch *b) {
     if (w->finalised) return KP_OK;
     KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     const size_t n_asm = (size_t)b->n_asm;
-    for (int attempt = 0;; ++attempt) {
+    for (;;) {
         // the post stream picks up where this batch's alignment pass ends; later passes on ctx->stream are not waited for
         KP_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->post, w->ev[3 + KP_N_CLASSES], 0));
         w->h_counts.resize(2 * n_asm + KP_N_CLASSES);
@@ -1314,29 +1334,42 @@ int kp_batch_wait(kp_ctx *ctx, kp_batch *b) {
             if (max_join + max_join / 4 > w->join_cap) ctx->join_cap = std::max(ctx->join_cap, 2 * max_join);
             break;
         }
-        if (attempt >= 4) return kp_fail(ctx, KP_EOVERFLOW, "anchor/task buffers overflowed repeatedly");
         // a region overflowed: counts kept counting, so they say how much room a clean rerun needs.  The context
-        // remembers it (with some headroom, later batches differ a little) for every later pass.
+        // remembers it (with some headroom, later batches differ a little) for every later pass.  The lists feed one
+        // another and a stage behind an overflow counts on truncated input, so a pass may uncover one overflow after
+        // another: there is another pass as long as this one grew a list (caps only grow, so this ends).
+        bool grew = false;
         if (n_cand > w->cand_cap) {
             w->cand_cap = n_cand + n_cand / 8;
             ctx->cand_frac = std::max(ctx->cand_frac, (double)w->cand_cap / ((double)b->view.total_words * 4.0) * 1.0001);
+            grew = true;
         }
         if (max_slice > sub_cap) {
             w->anchor_cap = ((max_slice + max_slice / 2 + 15u) & ~15u) * KP_ANCHOR_SUBS;
             ctx->anchor_cap = std::max(ctx->anchor_cap, w->anchor_cap);
+            grew = true;
         }
         if (trace_need > w->trace_cap) {  // (a pass cut short by another overflow reports less than it will need)
             if (trace_need > (1ull << 32)) return kp_fail(ctx, KP_EOVERFLOW, "DP trace would exceed 64 GB; use smaller batches");
             w->trace_cap = std::min<uint64_t>(trace_need + trace_need / 4, 1ull << 32);  // later batches differ by a few per cent
             ctx->trace_units_per_asm = std::max<uint64_t>(ctx->trace_units_per_asm, (w->trace_cap + n_asm - 1) / std::max<size_t>(n_asm, 1));
+            grew = true;
         }
-        if (n_group > w->group_cap) { w->group_cap = n_group + n_group / 4 + 64; ctx->group_cap = std::max(ctx->group_cap, w->group_cap); }
-        if (occ_need > w->occ_slots) ctx->occ_slots = std::max<uint32_t>(ctx->occ_slots, (uint32_t)std::min<unsigned long long>(occ_need + occ_need / 4 + 1, 1u << 16));
-        if (max_join > w->join_cap) { w->join_cap = max_join + max_join / 4 + 64; ctx->join_cap = std::max(ctx->join_cap, w->join_cap); }
+        if (n_group > w->group_cap) { w->group_cap = n_group + n_group / 4 + 64; ctx->group_cap = std::max(ctx->group_cap, w->group_cap); grew = true; }
+        if (occ_need > w->occ_slots) {
+            ctx->occ_slots = std::max<uint32_t>(ctx->occ_slots, (uint32_t)std::min<unsigned long long>(occ_need + occ_need / 4 + 1, KP_OCC_SLOTS_MAX));
+            if (ctx->occ_slots <= w->occ_slots)  // (the rerun's tables are the context's: enqueue_align)
+                return kp_fail(ctx, KP_EOVERFLOW, "occurrence-cut tables overflowed: " + std::to_string(occ_need) + " assemblies of the batch need their own mid_occ, at most " +
+                                                      std::to_string(KP_OCC_SLOTS_MAX) + " tables; use smaller batches");
+            grew = true;
+        }
+        if (max_join > w->join_cap) { w->join_cap = max_join + max_join / 4 + 64; ctx->join_cap = std::max(ctx->join_cap, w->join_cap); grew = true; }
         if (max_task > w->task_cap) {
             w->task_cap = (max_task + max_task / 8 + 1023u) & ~1023u;
             ctx->tasks_per_asm = std::max<uint32_t>(ctx->tasks_per_asm, (uint32_t)((w->task_cap + n_asm - 1) / std::max<size_t>(n_asm, 1)));
+            grew = true;
         }
+        if (!grew) return kp_fail(ctx, KP_EOVERFLOW, "alignment pass overflowed a list that could not grow");  // (unreachable: every overflow above grows or fails)
         w->stats[4] += 1;
         int rc = enqueue_align(ctx, b, w);
         if (rc) return rc;

@@ -316,6 +316,20 @@ def test_joins_across_mid_size_indels_match_oracle(ctx, small_setup, small_db):
     batch.close()
 
 
+def _repeats(rng, unit, copies):
+    """``copies`` copies of ``unit`` between random spacers, alternately reverse-complemented, each a little diverged (not
+    every seed survives in every copy)."""
+    from kaptive_amd.synth import revcomp
+
+    pad = lambda n: random_dna(rng, n, 0.5)  # noqa: E731
+    parts = []
+    for i in range(copies):
+        u = unit.copy()
+        u[rng.integers(0, len(u), size=max(1, len(u) // 300))] = ord("A")  # a little divergence: not every seed survives
+        parts += [pad(int(rng.integers(40, 400))), u if i % 2 else revcomp(u)]
+    return np.concatenate(parts + [pad(100)])
+
+
 def test_occurrence_cut_matches_oracle(oracle):
     """minimap2 drops a query seed that occurs more than mid_occ (>= 10) times among the target's minimizers
     (src/kaptive/core/genome.py:177-191 builds that index per assembly); kp_spec.h's KP_MID_OCC restates the floor: a gene
@@ -323,8 +337,6 @@ def test_occurrence_cut_matches_oracle(oracle):
     11, 12, 30 and 150 times on both strands, a whole gene in 14 copies, a repeat that lies beyond position 4096 of a 9 kb
     gene and one that straddles it (the second / both counting windows), next to assemblies without any repeat: anchors
     (after the cut), band tasks and hits equal the oracle's, and the cut removed what it should."""
-    from kaptive_amd.synth import revcomp
-
     rng = np.random.default_rng(4242)
     db = make_db("kpsc_k", seed=7, n_loci=4)
     long_gene = random_dna(rng, 9_000, 0.5)
@@ -336,13 +348,7 @@ def test_occurrence_cut_matches_oracle(oracle):
     pad = lambda n: random_dna(rng, n, 0.5)  # noqa: E731
     g3, g7 = np.frombuffer(db.genes[3].seq, np.uint8), np.frombuffer(db.genes[7].seq, np.uint8)
 
-    def repeats(unit, copies):
-        parts = []
-        for i in range(copies):
-            u = unit.copy()
-            u[rng.integers(0, len(u), size=max(1, len(u) // 300))] = ord("A")  # a little divergence: not every seed survives
-            parts += [pad(int(rng.integers(40, 400))), u if i % 2 else revcomp(u)]
-        return np.concatenate(parts + [pad(100)])
+    repeats = lambda unit, copies: _repeats(rng, unit, copies)  # noqa: E731
 
     # (round 6: the cut is minimap2's mid_occ of the assembly -- max(10, the 2e-4 quantile of its minimizers' occurrence counts) --,
     # worked out by the device for the assemblies that hold a gene seed beyond the floor.  It sits AT the floor only when fewer than
