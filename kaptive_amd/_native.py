@@ -16,6 +16,8 @@ LIB_PATH = Path(__file__).resolve().parent / "libkaptive_amd.so"
 MAX_GENE_LEN = 65535  # KP_MAX_GENE_LEN of include/kp_spec.h (tests/test_native_abi.py compares the two)
 FILL16_MAX_GENE_LEN = 15800  # KP_FILL16_MAX_GENE_LEN: longer genes are filled with 32-bit scores
 WORK_SLOTS = 3  # KP_WORK_SLOTS of include/kaptive_amd.h: alignment results a context keeps resident
+MAX_GENES = 131071  # KP_MAX_GENES of include/kp_spec.h: genes one context holds, all of its databases together
+MAX_TYPING_GROUPS = 16  # KP_MAX_TYPING_GROUPS of include/kaptive_amd.h: databases one context types
 
 HIT_DTYPE = np.dtype(
     [("gene", "<i4"), ("contig", "<i4"), ("q_start", "<i4"), ("q_end", "<i4"), ("t_start", "<i4"), ("t_end", "<i4"),

@@ -6,6 +6,13 @@ differs underneath: genomes are read and packed by a thread pool (``--threads`` 
 ignores it) while earlier ones are being typed, in batches, on the GPU(s) (``--devices``: one process per
 device; ``--batch-size``), and written in input order (``_TypingPipeline``).
 DATABASE is a ``.npz`` blob written by ``Database.save`` or a GenBank file with its ``.toml`` next to it.
+
+``--db DATABASE`` (repeatable) adds databases to the same run: ``kaptive_amd assembly kpsc_k.gbk genomes/*.fasta --db
+kpsc_o.gbk -o results.tsv`` reads every file once and types it against the positional database and then every ``--db``, in
+the order given (one alignment pass over the genes of all of them, ``MultiSerotyper``).  Each database's reports hold
+exactly the bytes a run with that database alone writes: files get the database's keyword before their last suffix
+(``results.kpsc_k.tsv``, ``results.kpsc_o.tsv``; ``.<keyword>`` appended to a name without one), ``-l/-g/-p`` write into
+``DIR/<keyword>/``, and a report on stdout has one header and then, genome by genome in input order, one line per database.
 """
 
 from __future__ import annotations
@@ -109,6 +116,9 @@ def build_parser() -> argparse.ArgumentParser:
     t = sub.add_parser("type", aliases=["assembly"], help="In silico serotyping of assemblies")
     t.add_argument("database", help="Database blob (.npz) or GenBank file with its .toml")
     t.add_argument("genomes", nargs="+", help="Genome assemblies in fasta format; can be compressed")
+    t.add_argument("--db", action="append", metavar="DATABASE",
+                   help="A further database to type every assembly against in the same pass (repeatable; same formats as the "
+                        "positional); reports are then written per database")
     _add_outputs(t, ("-o", "--out"), include_json=True)
     c = t.add_argument_group("Confidence options")
     c.add_argument("--max-other-genes", type=int, default=1, metavar="", help="Typeable if <= other genes (default: 1)")
@@ -209,6 +219,8 @@ class _TypingPipeline:
                 self._early.append((k, self.submit_read(paths)))
             self._unread = len(chunks) - len(self._early)
         self._own_typer = typer is None
+        from kaptive_amd.serotyping.core import MultiSerotyper
+
         early_ctx = None
         if typer is None:
             # the HIP runtime and the device context come up on a thread of their own (0.2 s, interpreter lock released) while this
@@ -220,10 +232,16 @@ class _TypingPipeline:
         try:
             if typer is None:
                 self.db = load_database(args.database)
+                more = [load_database(p) for p in getattr(args, "db", None) or []]
                 self.marks["database_loaded"] = time.perf_counter()
-                typer = Serotyper(self.db, max_other_genes=args.max_other_genes, min_completeness=args.min_completeness,
-                                  allow_below_threshold=args.below_threshold, partial_edge_tolerance=args.partial_edge_tolerance,
-                                  device=device)  # fmt: skip
+                if more:  # one pass for all of them; duplicate keywords and too many genes are refused here, before any typing
+                    typer = MultiSerotyper([self.db, *more], max_other_genes=args.max_other_genes, min_completeness=args.min_completeness,
+                                           allow_below_threshold=args.below_threshold, partial_edge_tolerance=args.partial_edge_tolerance,
+                                           device=device)  # fmt: skip
+                else:
+                    typer = Serotyper(self.db, max_other_genes=args.max_other_genes, min_completeness=args.min_completeness,
+                                      allow_below_threshold=args.below_threshold, partial_edge_tolerance=args.partial_edge_tolerance,
+                                      device=device)  # fmt: skip
                 typer._ctx_early = early_ctx
             self.typer = typer
             self.engine = self.typer.engine  # the context is created here, on the thread that will drive it
@@ -236,6 +254,8 @@ class _TypingPipeline:
             raise
         self.marks["context_ready"] = time.perf_counter()
         self.want_tsv = bool(getattr(args, "out", None))
+        # several databases: every chunk's outputs are ((keyword, outputs), ...), one entry per database in order
+        self.keywords = tuple(t._db.metadata.keyword for t in typer.serotypers) if isinstance(typer, MultiSerotyper) else None
 
     def _abandon_reads(self) -> None:
         """Cancel every queued read, drop what finished reads hold (shards' page-locked blocks), keep no worker waiting."""
@@ -391,13 +411,15 @@ class _TypingPipeline:
     # -- stage 3: records -> bytes ------------------------------------------------------------------------------------------------
     def run(self, chunks):
         """Yields ``(k, outputs)`` for every ``(k, paths)`` of ``chunks``, in order; ``outputs`` maps "tsv" / "pha4ge" /
-        "json" to the bytes this chunk adds to that stream (per-assembly fasta files are written here)."""
+        "json" to the bytes this chunk adds to that stream (per-assembly fasta files are written here).  With several
+        databases ``outputs`` is ``((keyword, that mapping), ...)``, one entry per database in order, and the fasta files of
+        a database go to ``DIR/<keyword>/``."""
         from collections import deque
 
         args = self.args
         self._order = []
 
-        def render(bt) -> dict:
+        def render(bt, keyword=None) -> dict:
             out = {}
             if self.want_tsv:
                 out["tsv"] = bt.tsv()
@@ -406,7 +428,8 @@ class _TypingPipeline:
             if getattr(args, "json", None):  # one native call per batch (kp_format_json): byte for byte result_to_json of every result
                 out["json"] = bt.jsonl()
             if self.fasta_outputs:  # a file per assembly and kind, as the reference writes them; the records come per batch (kp_format_fasta)
-                wanted = {flag: (Path(d), ext) for flag, ext in (("loci", "fna"), ("genes", "ffn"), ("proteins", "faa")) if (d := getattr(args, flag, None))}
+                wanted = {flag: (Path(d) if keyword is None else Path(d) / keyword, ext)
+                          for flag, ext in (("loci", "fna"), ("genes", "ffn"), ("proteins", "faa")) if (d := getattr(args, flag, None))}
                 for flag, per_asm in bt.fasta(tuple(wanted)).items():
                     d, ext = wanted[flag]
                     d.mkdir(parents=True, exist_ok=True)
@@ -418,12 +441,21 @@ class _TypingPipeline:
         # of JSON per 512 assemblies would otherwise stand between two submissions to the device); they leave in input order.
         rendering: deque = deque()
         done = 0
-        for bt, batch in self.engine.type_stream(self.typer, self._source(chunks)):
+        if self.keywords is None:
+            stream, job = self.engine.type_stream(self.typer, self._source(chunks)), render
+        else:  # every database's records from the one alignment pass of the batch, rendered by the same formatters
+            kws = self.keywords
+            stream = self.engine.type_stream_groups(self.typer.serotypers, self._source(chunks))
+
+            def job(bts) -> tuple:
+                return tuple((kw, render(bt, kw)) for kw, bt in zip(kws, bts))
+
+        for bt, batch in stream:
             pb, batch._pin = getattr(batch, "_pin", None), None
             batch.close()  # (waits for whatever of the batch is still in flight: the pinned words are free after it)
             if pb is not None:
                 self._give_back(pb)
-            rendering.append(self.formatters.submit(render, bt))
+            rendering.append(self.formatters.submit(job, bt))
             while rendering and (rendering[0].done() or len(rendering) > 2):
                 yield self._order[done], rendering.popleft().result()
                 done += 1
@@ -552,6 +584,87 @@ def _since_process_start() -> float:
         return 0.0
 
 
+def _is_stdout(path) -> bool:
+    return str(path) in ("-", "stdout")
+
+
+def per_database_path(path, keyword: str) -> str:
+    """Where a database's copy of a report goes when several databases are typed: its keyword before the last suffix
+    (``results.tsv`` -> ``results.kpsc_k.tsv``), or appended to a name without one (``results`` -> ``results.kpsc_k``)."""
+    head, name = os.path.split(os.fspath(path))
+    root, ext = os.path.splitext(name)
+    return os.path.join(head, f"{root}.{keyword}{ext}")
+
+
+def interleave_lines(blocks) -> bytes:
+    """Line j of every block in turn, for j = 0, 1, ...: the blocks hold one line per assembly of the same chunk (one
+    block per database), and a report on stdout lists every database's line of a genome before the next genome's.  A byte
+    gather in numpy: no object per line."""
+    if len(blocks) == 1:
+        return bytes(blocks[0])
+    arrs = [np.frombuffer(b, np.uint8) for b in blocks]
+    ends = [np.flatnonzero(a == 0x0A) + 1 for a in arrs]
+    n = len(ends[0])
+    if any(len(e) != n or (e[-1] if n else 0) != len(a) for a, e in zip(arrs, ends)):
+        raise RuntimeError("every database's report block must hold one whole line per assembly of the chunk")
+    if n == 0:
+        return b""
+    base = np.cumsum([0] + [len(a) for a in arrs[:-1]])
+    starts = np.stack([np.concatenate([[0], e[:-1]]) + b for e, b in zip(ends, base)], axis=1).ravel()  # line j of block d at j * D + d
+    lens = np.stack([np.diff(np.concatenate([[0], e])) for e in ends], axis=1).ravel()
+    out_start = np.cumsum(lens) - lens
+    gather = np.arange(int(lens.sum())) - np.repeat(out_start - starts, lens)
+    return np.concatenate(arrs)[gather].tobytes()
+
+
+class _PerDatabaseOutputs:
+    """The TSV / PHA4GE / JSON reports of a run with several databases: a file per database and report
+    (``per_database_path``), each with its own header line; a report on stdout gets one header and the databases' lines
+    genome by genome (``interleave_lines``).  The files are opened with the first chunk's outputs, which carry the
+    databases' keywords."""
+
+    KINDS = (("tsv", "out"), ("pha4ge", "pha4ge"), ("json", "json"))
+
+    def __init__(self, args: argparse.Namespace) -> None:
+        self.wanted = [(key, path) for key, attr in self.KINDS if (path := getattr(args, attr, None))]
+        self.streams: "dict | None" = None  # key -> one handle per database, or the shared stdout
+        self.files: list = []
+
+    def _open(self, keywords) -> None:
+        from kaptive_amd.serotyping.io import KaptiveRow, Pha4geRow
+
+        headers = {"tsv": KaptiveRow.header(), "pha4ge": Pha4geRow.header(), "json": b""}
+        self.streams = {}
+        for key, path in self.wanted:
+            if _is_stdout(path):
+                sys.stdout.buffer.write(headers[key])
+                self.streams[key] = sys.stdout.buffer
+                continue
+            self.streams[key] = []
+            for kw in keywords:
+                h = open(per_database_path(path, kw), "wb")
+                self.files.append(h)
+                h.write(headers[key])
+                self.streams[key].append(h)
+
+    def write(self, outs) -> None:
+        """``outs``: ``((keyword, {key: bytes}), ...)`` of one chunk, one entry per database in order."""
+        if self.streams is None:
+            self._open([kw for kw, _ in outs])
+        for key, target in self.streams.items():
+            if isinstance(target, list):
+                for h, (_, out) in zip(target, outs):
+                    h.write(out[key])
+            else:
+                target.write(interleave_lines([out[key] for _, out in outs]))
+
+    def close(self) -> None:
+        for h in self.files:
+            h.close()
+        if self.streams and any(not isinstance(t, list) for t in self.streams.values()):
+            sys.stdout.buffer.flush()
+
+
 def run_type(args: argparse.Namespace) -> int:
     entered = _since_process_start()
     if str(args.devices).strip().lower() == "all":
@@ -585,26 +698,31 @@ def run_type(args: argparse.Namespace) -> int:
     from kaptive_amd.serotyping.io import KaptiveRow, Pha4geRow
 
     handles = {}
+    per_db = _PerDatabaseOutputs(args) if getattr(args, "db", None) else None  # several databases: reports per database
 
     def stream(path):
         return sys.stdout.buffer if str(path) in ("-", "stdout") else open(path, "wb")
 
-    if tsv := getattr(args, "out", None):
-        handles["tsv"] = stream(tsv)
-        handles["tsv"].write(KaptiveRow.header())
-    if p := getattr(args, "pha4ge", None):
-        handles["pha4ge"] = stream(p)
-        handles["pha4ge"].write(Pha4geRow.header())
-    if j := getattr(args, "json", None):
-        handles["json"] = stream(j)
+    if per_db is None:
+        if tsv := getattr(args, "out", None):
+            handles["tsv"] = stream(tsv)
+            handles["tsv"].write(KaptiveRow.header())
+        if p := getattr(args, "pha4ge", None):
+            handles["pha4ge"] = stream(p)
+            handles["pha4ge"].write(Pha4geRow.header())
+        if j := getattr(args, "json", None):
+            handles["json"] = stream(j)
     done = 0
     timing_path = os.environ.get("KAPTIVE_AMD_CLI_TIMING")  # bench.py: when each chunk's rows were written
     t_start, chunk_times, phases = time.perf_counter(), [], {}
 
     def write(out, n):
         nonlocal done
-        for key, blob in out.items():
-            handles[key].write(blob)
+        if per_db is not None:
+            per_db.write(out)
+        else:
+            for key, blob in out.items():
+                handles[key].write(blob)
         done += n
         chunk_times.append((done, time.perf_counter() - t_start))
         if args.verbose:
@@ -673,6 +791,8 @@ def run_type(args: argparse.Namespace) -> int:
                 h.close()
             else:
                 h.flush()
+        if per_db is not None:
+            per_db.close()
     if FAST_EXIT:
         # every stream this command writes is closed or flushed: what is left (reader threads, page-locked shards, the device
         # context) may leave with the process.  Other subcommands, and a run that raised, end through the interpreter.

@@ -234,6 +234,78 @@ class Engine:
                 except Exception:  # noqa: BLE001
                     pass
 
+    def type_stream_groups(self, typers: Sequence, source):
+        """``type_stream`` for every typing group at once: ``typers[g]`` types database ``g`` of this engine (one per
+        database, in order).  Same sliding window and the same ``source``; what comes out, in order, is
+        ``(tuple of one BatchTyping per group, batch)`` -- the caller closes the batch.  Every batch is aligned once; then
+        the scores of all groups are read back and their best loci chosen, all groups' reductions are enqueued, and only
+        then are the previous batch's records collected (``score_batches``: no database's scores queue up behind another
+        one's reduction)."""
+        from collections import deque
+
+        from kaptive_amd.serotyping import batch as B
+
+        typers = tuple(typers)
+        if len(typers) != len(self.dbs):
+            raise ValueError(f"{len(typers)} typers for an engine of {len(self.dbs)} databases: one per database, in order")
+        params = [self.view(g).typing_params(t) for g, t in enumerate(typers)]
+        depth = _native.WORK_SLOTS
+        it = iter(source)
+        live: deque = deque()  # aligned, not yet scored
+        pending = None  # reductions enqueued, records not yet collected
+        exhausted = False
+
+        def collect(item):
+            batch, ids, genomes, staged = item
+            out = []
+            for g, (typer, (scores, best)) in enumerate(zip(typers, staged)):
+                sums, kept, pieces = batch.typing(g)
+                out.append(B.BatchTyping(typer, ids, sums, kept, pieces, scores, best, genomes))
+            return tuple(out), batch
+
+        can_pull = getattr(source, "ready", None)
+
+        def fill_ready() -> None:
+            nonlocal exhausted
+            while not exhausted and len(live) + (1 if pending is not None else 0) < depth:
+                if can_pull is not None and (live or pending is not None) and not can_pull():
+                    return
+                try:
+                    item = next(it)
+                except StopIteration:
+                    exhausted = True
+                    return
+                item[0].align_async()
+                live.append(item)
+
+        try:
+            while True:
+                fill_ready()
+                if live:
+                    batch, ids, genomes = live.popleft()
+                    staged = []
+                    for g, typer in enumerate(typers):
+                        scores, counts = batch.score(typer.min_gene_coverage, g)
+                        best, _, _ = B.choose_best_loci(scores, counts, typer._expected_genes_per_locus)
+                        staged.append((scores, best))
+                    for g, (_, best) in enumerate(staged):
+                        batch.reduce_async(best, params[g], g)
+                    if pending is not None:
+                        done, pending = pending, None
+                        yield collect(done)
+                    pending = (batch, ids, genomes, staged)
+                elif pending is not None:
+                    done, pending = pending, None
+                    yield collect(done)
+                elif exhausted:
+                    break
+        finally:  # (as in type_stream: what is still in the window is closed before the context goes)
+            for item in list(live) + ([pending] if pending is not None else []):
+                try:
+                    item[0].close()
+                except Exception:  # noqa: BLE001
+                    pass
+
     def reduce_batches(self, typer, batches: Sequence, aligned: bool = False) -> list:
         """Scores back, best loci chosen (numpy), reductions enqueued, for up to WORK_SLOTS batches at once.  Returns what
         ``collect_batches`` needs; callers driving several databases put the other database's host work in between

@@ -363,3 +363,104 @@ class Serotyper:
             ranked = appending[np.argsort(-rules.priorities[appending])]
             name += "".join(rules.ids[i].decode("utf-8") for i in ranked)
         return name
+
+
+def check_databases(dbs: Sequence[Database]) -> None:
+    """What one context can type together, checked before it is created: distinct keywords (each database's outputs are
+    named by its keyword), at most ``KP_MAX_TYPING_GROUPS`` databases and ``KP_MAX_GENES`` genes in all.  Raises
+    ``ValueError``."""
+    from kaptive_amd import _native
+
+    if not dbs:
+        raise ValueError("no database given")
+    seen: dict = {}
+    for d in dbs:
+        kw = d.metadata.keyword
+        if kw in seen:
+            raise ValueError(f"database keyword {kw!r} is given twice: every database is typed once, and its outputs are named by its keyword")
+        seen[kw] = d
+    if len(dbs) > _native.MAX_TYPING_GROUPS:
+        raise ValueError(f"{len(dbs)} databases, but one pass types at most {_native.MAX_TYPING_GROUPS} (KP_MAX_TYPING_GROUPS)")
+    n_genes = sum(len(d.genes) for d in dbs)
+    if n_genes > _native.MAX_GENES:
+        counts = ", ".join(f"{d.metadata.keyword} {len(d.genes)}" for d in dbs)
+        raise ValueError(f"the databases hold {n_genes} genes together ({counts}), but one pass holds at most "
+                         f"{_native.MAX_GENES} (KP_MAX_GENES)")  # fmt: skip
+
+
+class MultiSerotyper:
+    """Several databases typed in one pass (K and O loci): one ``Serotyper`` per database (``.serotypers``), all on one
+    ``Engine(dbs)`` -- the genes of every database in one seed index, so an assembly is read, uploaded, scanned, chained and
+    aligned once and then reduced once per database (``Engine.view(i)``).  Every result is that of ``Serotyper(db)`` alone.
+    The context is created on first use and closed by ``close()``."""
+
+    def __init__(
+        self,
+        dbs: Sequence[Database],
+        max_other_genes: int = 1,
+        min_completeness: float = 0.5,
+        allow_below_threshold: bool = False,
+        partial_edge_tolerance: int = 5,
+        *,
+        device: int = 0,
+    ) -> None:
+        self.dbs = list(dbs)
+        check_databases(self.dbs)
+        self._device = device
+        self._engine = None
+        self.serotypers = tuple(
+            Serotyper(db, max_other_genes, min_completeness, allow_below_threshold, partial_edge_tolerance=partial_edge_tolerance,
+                      device=device) for db in self.dbs
+        )  # fmt: skip
+
+    @property
+    def engine(self):
+        """The shared engine (one context); each of ``.serotypers`` is given its database's view of it."""
+        if self._engine is None:
+            from kaptive_amd.engine import Engine
+
+            early = getattr(self, "_ctx_early", None)  # (as Serotyper.engine: a context the command line started early)
+            self._ctx_early = None
+            self._engine = Engine(self.dbs, device=self._device, ctx=early.result() if early is not None else None)
+            for i, s in enumerate(self.serotypers):
+                s._engine = self._engine.view(i)
+        return self._engine
+
+    def close(self) -> None:
+        if self._engine is not None:
+            self._engine.close()
+            self._engine = None
+            for s in self.serotypers:
+                s._engine = None
+
+    def __call__(self, genome: GenomeAssembly | str | Path) -> tuple[SerotypingResult, ...]:
+        return self.type_many([genome])[0]
+
+    def type_many(self, genomes: Sequence[GenomeAssembly | str | Path]) -> list[tuple[SerotypingResult, ...]]:
+        """One device submission for all genomes, aligned once: a tuple of results per genome, in database order."""
+        loaded = [GenomeAssembly.ensure(g) for g in genomes]
+        engine = self.engine
+        batch = engine.ctx.batch([g.packed() for g in loaded])
+        try:
+            for groups, _ in engine.type_stream_groups(self.serotypers, [(batch, [g.id for g in loaded], loaded)]):
+                return list(zip(*(bt.results() for bt in groups)))
+            return []
+        finally:
+            batch.close()
+
+    def tsv_from_files(self, paths: Sequence[str | Path], batch_size: int = 512, threads: int = 0) -> "Iterator[tuple[bytes, ...]]":
+        """``Serotyper.tsv_from_files`` for every database in one pass: per chunk, a tuple of one block of ``KaptiveRow``
+        bytes per database (no header lines)."""
+        import argparse
+
+        from kaptive_amd.cli import _TypingPipeline
+
+        args = argparse.Namespace(out="-", threads=threads, json=None, loci=None, genes=None, proteins=None, pha4ge=None)
+        paths = [str(p) for p in paths]
+        chunks = [(k, paths[i : i + batch_size]) for k, i in enumerate(range(0, len(paths), batch_size))]
+        pipe = _TypingPipeline(args, self._device, typer=self)
+        try:
+            for _, outs in pipe.run(chunks):
+                yield tuple(out["tsv"] for _, out in outs)
+        finally:
+            pipe.close()
