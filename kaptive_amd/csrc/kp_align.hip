@@ -1,0 +1,417 @@
+// kp_align.hip -- the alignment pass of a batch on its work set's streams, the wait that grows what overflowed and runs the
+// pass again (sizes: kp_caps.h), finalisation of the hit table and the accessors of every stage's results.
+#include "kp_host.h"
+
+static const char *const NO_RESULTS = "this batch has no resident alignment results (not aligned yet, or displaced: a context keeps the results of its KP_WORK_SLOTS most recently aligned batches)";
+
+// What a pass enqueues between its fork onto the join stream and the join back: chaining of the groups, joined fill and walk-back on `jstream`; the band
+// tasks' order, fill and traceback on `stream`.  The caller joins the streams whatever this returns: the next pass never starts beside kernels of this one.
+static int enqueue_forked(kp_ctx *ctx, kp_batch *b, KpWork *w, hipStream_t stream, const uint32_t *d_task_count) {
+    kp_launch_join_chain(b->view, ctx->genes, w->d_anchors_a.p, w->anchor_cap, w->key_bits, w->d_tasks.p, w->task_cap, w->d_groups.p,
+                         w->d_join_counts.p, w->group_cap, w->d_joins.p, w->d_join_counts.p + 1, w->join_cap, w->d_jscratch.p, w->jstream);
+    kp_launch_join_fill(b->view, ctx->genes, w->d_joins.p, w->d_join_counts.p + 1, w->join_cap, w->d_trace.p, w->d_trace_top.p, w->trace_cap, w->jstream);
+    kp_launch_join_trace(b->view, ctx->genes, w->d_joins.p, w->d_join_counts.p + 1, w->join_cap, w->task_cap, w->d_trace.p, w->d_task_drop.p, w->jstream);
+    kp_launch_task_order(b->view, ctx->genes, w->d_anchors_a.p, w->anchor_cap, w->key_bits, w->d_tasks.p, d_task_count, w->task_cap,
+                         w->d_results.p, w->d_task_order.p, w->d_task_order.p + KP_ORDER_HEAD, stream);
+    KP_HIP_CHECK(ctx, hipEventRecord(w->ev[3], stream));
+    // all four band classes in one fill launch, then the traceback (kp_sw.hip): ev[3]..ev[4] is the fill, ev[4]..ev[5]
+    // the traceback; the remaining event slots stay in the layout and read 0
+    kp_launch_sw(b->view, ctx->genes, w->d_tasks.p, w->d_task_order.p + KP_ORDER_COUNTS, w->task_cap, w->d_task_order.p + KP_ORDER_HEAD,
+                 w->d_ends.p, w->d_trace.p, w->d_trace_top.p, w->trace_cap, w->d_results.p, ctx->max_gene_len > KP_FILL16_MAX_GENE_LEN,
+                 stream, w->ev[4]);
+    // ev[5]..ev[6]: what is left of the join kernels once the band tasks are through (the "sw64" slot of kp_batch_profile; the
+    // last slot reads 0)
+    KP_HIP_CHECK(ctx, hipEventRecord(w->ev[5], stream));
+    return KP_OK;
+}
+
+static int enqueue_align(kp_ctx *ctx, kp_batch *b, KpWork *w) {
+    const size_t n_asm = (size_t)b->n_asm;
+    for (auto &e : w->ev)
+        if (!e) KP_HIP_CHECK(ctx, hipEventCreate(&e.h));
+    if (!w->astream) KP_HIP_CHECK(ctx, hipStreamCreateWithFlags(&w->astream.h, hipStreamNonBlocking));
+    if (!w->jstream) {
+        KP_HIP_CHECK(ctx, hipStreamCreateWithFlags(&w->jstream.h, hipStreamNonBlocking));
+        KP_HIP_CHECK(ctx, hipEventCreateWithFlags(&w->ev_jfork.h, hipEventDisableTiming));
+        KP_HIP_CHECK(ctx, hipEventCreateWithFlags(&w->ev_jdone.h, hipEventDisableTiming));
+    }
+    hipStream_t stream = w->astream;
+    const Event *ev = w->ev;
+    if ((uint64_t)n_asm * w->anchor_cap > 0xFFFFFFF0ull)
+        return kp_fail(ctx, KP_EOVERFLOW, "anchor buffer would exceed 2^32 entries; use smaller batches");
+    if (((uint64_t)b->view.total_words << 4) >> KP_CAND_POS_BITS)
+        return kp_fail(ctx, KP_EOVERFLOW, "a batch holds at most 2^33 bases (candidate positions); use smaller batches");
+    KP_HIP_CHECK(ctx, w->d_anchors_a.reserve(n_asm * w->anchor_cap));
+    KP_HIP_CHECK(ctx, w->d_anchors_b.reserve(n_asm * w->anchor_cap));
+    KP_HIP_CHECK(ctx, w->d_counts.reserve(2 * n_asm + KP_N_CLASSES));
+    KP_HIP_CHECK(ctx, w->d_sub_counts.reserve(n_asm * KP_ANCHOR_SUBS));
+    KP_HIP_CHECK(ctx, w->d_seg.reserve(2 * n_asm));
+    KP_HIP_CHECK(ctx, w->d_tasks.reserve(KP_N_CLASSES * (size_t)w->task_cap));
+    KP_HIP_CHECK(ctx, w->d_results.reserve(KP_N_CLASSES * (size_t)w->task_cap));
+    KP_HIP_CHECK(ctx, w->d_task_drop.reserve(KP_N_CLASSES * (size_t)w->task_cap));
+    KP_HIP_CHECK(ctx, w->d_jscratch.reserve(kp_join_chain_scratch_bytes()));
+    {   // a table holds every distinct minimizer of the longest assembly (2 / 11 of its bases) at a load of at most a half
+        uint32_t lg = 12;
+        while (((uint64_t)1 << lg) < (uint64_t)b->max_asm_bases * 2 / 5 + 1 && lg < 31) ++lg;
+        w->occ_log2 = lg;
+        KP_HIP_CHECK(ctx, w->d_occ_keys.reserve((size_t)w->occ_slots << lg));
+        KP_HIP_CHECK(ctx, w->d_occ_cnts.reserve((size_t)w->occ_slots << lg));
+        KP_HIP_CHECK(ctx, w->d_occ_state.reserve(kp_occ_state_words(n_asm, w->occ_slots)));
+    }
+    KP_HIP_CHECK(ctx, w->d_task_order.reserve(KP_ORDER_HEAD + KP_N_CLASSES * (size_t)w->task_cap));
+    KP_HIP_CHECK(ctx, w->d_cand.reserve(w->cand_cap));
+    KP_HIP_CHECK(ctx, w->d_cand_count.reserve(2));  // [0] the streaming kernel's candidates (front), [1] the edge kernel's (back)
+    KP_HIP_CHECK(ctx, w->d_ends.reserve(KP_N_CLASSES * (size_t)w->task_cap));
+    KP_HIP_CHECK(ctx, w->d_trace_top.reserve(4));  // [0] trace units handed out, [1..2] the fill kernel's quad counters (four 32-bit words)
+    KP_HIP_CHECK(ctx, w->d_trace.reserve(w->trace_cap));
+    KP_HIP_CHECK(ctx, w->d_groups.reserve(w->group_cap));
+    KP_HIP_CHECK(ctx, w->d_joins.reserve(KP_N_CLASSES * (size_t)w->join_cap));
+    KP_HIP_CHECK(ctx, w->d_join_counts.reserve(1 + KP_N_CLASSES));
+    KP_HIP_CHECK(ctx, hipStreamWaitEvent(stream, b->in->ready, 0));  // the batch's H2D copies
+    if (b->after && b->after->in) KP_HIP_CHECK(ctx, hipStreamWaitEvent(stream, b->after->in->ready, 0));
+    KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_counts.p, 0, (2 * n_asm + KP_N_CLASSES) * sizeof(uint32_t), stream));
+    KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_sub_counts.p, 0, n_asm * KP_ANCHOR_SUBS * sizeof(uint32_t), stream));
+    KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_cand_count.p, 0, 2 * sizeof(unsigned long long), stream));
+    KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_task_order.p, 0, KP_ORDER_HEAD * sizeof(uint32_t), stream));
+    KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_trace_top.p, 0, 4 * sizeof(unsigned long long), stream));
+    KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_join_counts.p, 0, (1 + KP_N_CLASSES) * sizeof(uint32_t), stream));
+    uint32_t *d_task_count = w->d_counts.p + n_asm;
+    const uint32_t sub_cap = w->anchor_cap / KP_ANCHOR_SUBS;
+    // compact anchor keys: as many bits per field as this batch and database can set
+    auto bits_for = [](uint64_t max_value) { uint32_t n = 1; while (n < 63 && (max_value >> n)) ++n; return n; };
+    w->key_bits.qb = std::min<uint32_t>(16, bits_for((uint64_t)std::max(ctx->max_gene_len, 1)));
+    w->key_bits.db = std::min<uint32_t>(30, bits_for((uint64_t)b->max_asm_bases + KP_DIAG_BIAS));
+    KP_HIP_CHECK(ctx, hipEventRecord(ev[0], stream));
+    kp_launch_scan(b->view, ctx->index, w->d_cand.p, w->d_cand_count.p, w->cand_cap, w->d_anchors_a.p, w->d_sub_counts.p, sub_cap, w->key_bits, ctx->opt.scan_mode, b->n_ctg_total, stream, ev[1]);
+    if (!ctx->opt.library_sort && kp_bsort_fits(2u * (uint32_t)ctx->n_genes)) {
+        // buckets of the gene/strand field, each sorted on its own (kp_bsort.hip); sorted keys end up where the chaining reads them
+        kp_launch_anchor_bsort(b->view, w->d_anchors_a.p, w->d_sub_counts.p, sub_cap, w->d_anchors_b.p, w->d_anchors_a.p,
+                               w->d_counts.p, w->d_counts.p + n_asm + KP_N_CLASSES, 2u * (uint32_t)ctx->n_genes, w->key_bits, stream);
+    } else {  // `library_sort`: compaction + the library's segmented radix sort (tests compare the two)
+        kp_launch_anchor_compact(b->view, w->d_anchors_a.p, w->d_sub_counts.p, sub_cap, w->d_anchors_b.p, w->d_counts.p, w->d_counts.p + n_asm + KP_N_CLASSES, stream);
+        int rc = kp_sort_anchors(ctx, w->d_anchors_b.p, w->d_anchors_a.p, w->d_counts.p, w->anchor_cap, b->n_asm, &w->sort_temp.p, &w->sort_temp.bytes, w->d_seg.p, w->d_seg.p + n_asm,
+                                 (int)(w->key_bits.qb + w->key_bits.db) + ctx->gs_bits,
+                                 stream);
+        if (rc) return rc;
+    }
+    KP_HIP_CHECK(ctx, hipEventRecord(ev[2], stream));
+    kp_launch_occ_cut(b->view, ctx->d_gene_len.p, w->d_anchors_a.p, w->d_counts.p, w->anchor_cap, w->key_bits, w->d_occ_keys.p, w->d_occ_cnts.p,
+                      w->d_occ_state.p, w->d_trace_top.p + 3, w->occ_slots, w->occ_log2, stream);  // (words 1-2 of trace_top are the fill kernel's quad counters)
+    kp_launch_chain(b->view, w->d_anchors_a.p, w->d_counts.p, w->anchor_cap, w->key_bits, w->d_tasks.p, d_task_count, w->task_cap, w->d_groups.p, w->d_join_counts.p, w->group_cap, stream);
+    // kp-align v5: the chains of a group's anchors, their joined fill and walk-back need the groups and the sorted anchors only:
+    // they fork off here and run on the work set's second stream beside the band tasks' order, fill and traceback
+    KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_task_drop.p, 0, KP_N_CLASSES * (size_t)w->task_cap, stream));
+    KP_HIP_CHECK(ctx, hipEventRecord(w->ev_jfork, stream));
+    KP_HIP_CHECK(ctx, hipStreamWaitEvent(w->jstream, w->ev_jfork, 0));
+    const int rc = enqueue_forked(ctx, b, w, stream, d_task_count);
+    const hipError_t e_done = hipEventRecord(w->ev_jdone, w->jstream), e_join = hipStreamWaitEvent(stream, w->ev_jdone, 0);
+    if (rc) return rc;
+    KP_HIP_CHECK(ctx, e_done);
+    KP_HIP_CHECK(ctx, e_join);
+    for (int c = 2; c < KP_N_CLASSES; ++c) KP_HIP_CHECK(ctx, hipEventRecord(ev[4 + c], stream));
+    KP_HIP_CHECK(ctx, hipGetLastError());
+    return KP_OK;
+}
+
+// every stream the work set's reductions run on is idle (they read the hit tables that are about to be rewritten)
+static int sync_runs(kp_ctx *ctx, KpWork *w) {
+    KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->post));
+    for (auto &r : w->runs)
+        if (r && r->stream) { KP_HIP_CHECK(ctx, hipStreamSynchronize(r->stream)); if (r->aux) KP_HIP_CHECK(ctx, hipStreamSynchronize(r->aux)); }
+    return KP_OK;
+}
+
+// the batch's work set with finalised hit tables, or null after recording the error
+KpWork *finalised_work(kp_ctx *ctx, kp_batch *b) {
+    KpWork *w = work_of(b);
+    if (!w) { kp_fail(ctx, KP_ESTATE, NO_RESULTS); return nullptr; }
+    if (!w->finalised) { kp_fail(ctx, KP_ESTATE, "kp_batch_wait has not completed"); return nullptr; }
+    return w;
+}
+
+extern "C" {
+
+int kp_batch_align(kp_ctx *ctx, kp_batch *b) {
+    if (!ctx || !b || b->ctx != ctx) return kp_fail(ctx, KP_EINVAL, "bad context/batch");
+    if (!ctx->has_db) return kp_fail(ctx, KP_ESTATE, "no database loaded");
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    KpWork *w = work_of(b);
+    if (!w) {  // next work set, round-robin; whoever held it loses its results
+        w = &ctx->work[ctx->next_slot++ % KP_WORK_SLOTS];
+        if (w->owner) {
+            if (int rc = sync_runs(ctx, w)) return rc;  // its reductions may still be reading the hit tables
+            w->owner->w = nullptr;
+        }
+        w->owner = b;
+        b->w = w; b->last_w = w;
+    }
+    kp_caps_size(ctx->opt, ctx->learnt, b->n_asm, b->view.total_words, *w);
+    w->aligned = false; w->finalised = false;
+    for (auto &v : w->h_tasks) v.clear();
+    for (auto &r : w->runs)
+        if (r) { r->split = false; r->scored = false; r->reduced = false; r->sums_valid = false; }
+    w->stats[4] = 0;
+    int rc = enqueue_align(ctx, b, w);
+    if (rc) return rc;
+    w->aligned = true;
+    return KP_OK;
+}
+
+// hit-table finalisation on the device: compaction of the band-task results into per-assembly lists, emission order,
+// duplicates, mapq.  Grows hit_cap and repeats if an assembly produced more hits than its region holds.
+static int finalise_hits_on_device(kp_ctx *ctx, kp_batch *b, KpWork *w) {
+    const size_t n_asm = (size_t)b->n_asm;
+    for (int attempt = 0;; ++attempt) {
+        KP_HIP_CHECK(ctx, w->d_hits_raw.reserve(n_asm * w->hit_cap));
+        KP_HIP_CHECK(ctx, w->d_hits.reserve(n_asm * w->hit_cap));
+        KP_HIP_CHECK(ctx, w->d_keys.reserve(n_asm * w->hit_cap * 3));
+        KP_HIP_CHECK(ctx, w->d_hit_counts.reserve(2 * n_asm));
+        KP_HIP_CHECK(ctx, w->d_cells.reserve(1));
+        KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_hit_counts.p, 0, 2 * n_asm * sizeof(uint32_t), ctx->post));
+        KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_cells.p, 0, sizeof(unsigned long long), ctx->post));
+        kp_launch_hit_finalise(b->view, ctx->d_gene_len.p, w->d_tasks.p, w->d_results.p, w->d_task_drop.p, w->d_counts.p + n_asm,
+                               w->task_cap, w->d_hits_raw.p, w->d_hit_counts.p, w->hit_cap, w->d_keys.p, w->d_hits.p,
+                               w->d_hit_counts.p + n_asm, w->d_cells.p, ctx->d_ln.p, ctx->d_ln.p + KP_MAPQ_LN_HALF_SIZE, w->d_joins.p,
+                               w->d_join_counts.p + 1, w->join_cap, ctx->post);
+        KP_HIP_CHECK(ctx, hipGetLastError());
+        w->h_hit_counts.resize(2 * n_asm);
+        unsigned long long cells = 0;
+        if (int frc = fetch_all(ctx, ctx->post, {{w->h_hit_counts.data(), w->d_hit_counts.p, 2 * n_asm * sizeof(uint32_t)}, {&cells, w->d_cells.p, sizeof cells}}))
+            return frc;
+        uint32_t max_raw = 0;
+        for (size_t a = 0; a < n_asm; ++a) max_raw = std::max(max_raw, w->h_hit_counts[a]);
+        if (max_raw <= w->hit_cap) { w->stats[2] = (int64_t)cells; break; }
+        if (attempt >= 2) return kp_fail(ctx, KP_EOVERFLOW, "hit buffers overflowed repeatedly");
+        kp_caps_grow_hits(ctx->learnt, *w, max_raw, true);
+        w->stats[4] += 1;
+    }
+    w->hit_off.assign(n_asm + 1, 0);
+    for (size_t a = 0; a < n_asm; ++a) w->hit_off[a + 1] = w->hit_off[a] + (int64_t)w->h_hit_counts[n_asm + a];
+    return KP_OK;
+}
+
+int kp_batch_wait(kp_ctx *ctx, kp_batch *b) {
+    if (!ctx || !b || b->ctx != ctx) return kp_fail(ctx, KP_EINVAL, "bad context/batch");
+    KpWork *w = work_of(b);
+    if (!w || !w->aligned) return kp_fail(ctx, KP_ESTATE, w ? "kp_batch_align has not been called" : NO_RESULTS);
+    if (w->finalised) return KP_OK;
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    const size_t n_asm = (size_t)b->n_asm;
+    for (;;) {
+        // the post stream picks up where this batch's alignment pass ends; later passes on ctx->stream are not waited for
+        KP_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->post, w->ev[3 + KP_N_CLASSES], 0));
+        w->h_counts.resize(2 * n_asm + KP_N_CLASSES);
+        unsigned long long n_cand2[2] = {0, 0}, trace_top2[4] = {0, 0, 0, 0};
+        if (int frc = fetch_all(ctx, ctx->post, {{w->h_counts.data(), w->d_counts.p, (2 * n_asm + KP_N_CLASSES) * sizeof(uint32_t)},
+                                                 {n_cand2, w->d_cand_count.p, sizeof n_cand2}, {trace_top2, w->d_trace_top.p, sizeof trace_top2},
+                                                 {w->h_join_counts, w->d_join_counts.p, sizeof w->h_join_counts}}))
+            return frc;
+        KpPassSeen seen;
+        seen.n_asm = n_asm; seen.total_words = b->view.total_words; seen.n_cand = n_cand2[0] + n_cand2[1];
+        seen.trace_need = trace_top2[0]; seen.occ_need = trace_top2[3];
+        seen.n_group = w->h_join_counts[0];
+        for (int c = 0; c < KP_N_CLASSES; ++c) seen.max_join = std::max(seen.max_join, w->h_join_counts[1 + c]);
+        for (size_t a = 0; a < n_asm; ++a) seen.max_slice = std::max(seen.max_slice, w->h_counts[n_asm + KP_N_CLASSES + a]);
+        for (int c = 0; c < KP_N_CLASSES; ++c) seen.max_task = std::max(seen.max_task, w->h_counts[n_asm + c]);
+        if (ctx->opt.join_stats)
+            std::fprintf(stderr, "[kp_batch_wait] %zu assemblies: %u groups, joins per band class %u %u %u %u, %llu assemblies needed their mid_occ (%u tables)\n", n_asm, seen.n_group,
+                         w->h_join_counts[1], w->h_join_counts[2], w->h_join_counts[3], w->h_join_counts[4], (unsigned long long)seen.occ_need, w->occ_slots);
+        std::string err;
+        const KpCapsVerdict verdict = kp_caps_after_pass(ctx->learnt, *w, seen, err);
+        if (verdict == KP_CAPS_FITTED) break;
+        if (verdict == KP_CAPS_OVERFLOW) return kp_fail(ctx, KP_EOVERFLOW, err);
+        w->stats[4] += 1;
+        int rc = enqueue_align(ctx, b, w);
+        if (rc) return rc;
+    }
+    int64_t n_anchor = 0, n_task = 0;
+    for (size_t a = 0; a < n_asm; ++a) n_anchor += w->h_counts[a];
+    for (int c = 0; c < KP_N_CLASSES; ++c) n_task += w->h_counts[n_asm + c];
+    for (auto &v : w->h_tasks) v.clear();
+    w->h_joins.clear();
+    int rc = finalise_hits_on_device(ctx, b, w);
+    if (rc) return rc;
+    w->stats[0] = n_anchor; w->stats[1] = n_task; w->stats[3] = w->hit_off[n_asm];
+    w->finalised = true;
+    return KP_OK;
+}
+
+int kp_batch_hit_offsets(kp_ctx *ctx, kp_batch *b, int64_t *hit_off) {
+    if (!ctx || !b || b->ctx != ctx || !hit_off) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    std::memcpy(hit_off, w->hit_off.data(), w->hit_off.size() * sizeof(int64_t));
+    return KP_OK;
+}
+
+int kp_batch_hits(kp_ctx *ctx, kp_batch *b, kp_hit *out, int64_t cap) {
+    if (!ctx || !b || b->ctx != ctx || (!out && cap > 0)) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    const size_t n_asm = (size_t)b->n_asm;
+    const int64_t total = w->hit_off[n_asm];
+    if (cap < total) return kp_fail(ctx, KP_EINVAL, "hit buffer too small");
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    for (size_t a = 0; a < n_asm; ++a) {  // regions are contiguous per assembly; copy each used prefix
+        const int64_t n = w->hit_off[a + 1] - w->hit_off[a];
+        if (n > 0)
+            KP_HIP_CHECK(ctx, hipMemcpyAsync(out + w->hit_off[a], w->d_hits.p + a * (size_t)w->hit_cap, (size_t)n * sizeof(kp_hit), hipMemcpyDeviceToHost, ctx->post));
+    }
+    KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->post));
+    return KP_OK;
+}
+
+int kp_batch_set_hits(kp_ctx *ctx, kp_batch *b, const kp_hit *hits, const int64_t *hit_off) {
+    if (!ctx || !b || b->ctx != ctx || !hit_off) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    const size_t n_asm = (size_t)b->n_asm;
+    int64_t max_n = 0;
+    for (size_t a = 0; a < n_asm; ++a) {
+        const int64_t n = hit_off[a + 1] - hit_off[a];
+        if (n < 0 || (n > 0 && !hits)) return kp_fail(ctx, KP_EINVAL, "hit offsets must ascend");
+        max_n = std::max(max_n, n);
+    }
+    if (max_n > (1 << 24)) return kp_fail(ctx, KP_EOVERFLOW, "too many hits for one assembly");
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (int rc = sync_runs(ctx, w)) return rc;  // nothing may still be reading the table that is about to be replaced
+    if ((uint64_t)max_n > w->hit_cap) kp_caps_grow_hits(ctx->learnt, *w, (uint32_t)max_n, false);
+    KP_HIP_CHECK(ctx, w->d_hits.reserve(n_asm * w->hit_cap));
+    KP_HIP_CHECK(ctx, w->d_hit_counts.reserve(2 * n_asm));
+    w->h_hit_counts.resize(2 * n_asm);
+    w->hit_off.assign(n_asm + 1, 0);
+    for (size_t a = 0; a < n_asm; ++a) {
+        const int64_t n = hit_off[a + 1] - hit_off[a];
+        if (n > 0)
+            KP_HIP_CHECK(ctx, hipMemcpy(w->d_hits.p + a * (size_t)w->hit_cap, hits + hit_off[a], (size_t)n * sizeof(kp_hit), hipMemcpyHostToDevice));
+        w->h_hit_counts[n_asm + a] = (uint32_t)n;
+        w->hit_off[a + 1] = w->hit_off[a] + n;
+    }
+    if (n_asm)
+        KP_HIP_CHECK(ctx, hipMemcpy(w->d_hit_counts.p + n_asm, w->h_hit_counts.data() + n_asm, n_asm * sizeof(uint32_t), hipMemcpyHostToDevice));
+    w->stats[3] = w->hit_off[n_asm];
+    for (auto &r : w->runs)
+        if (r) { r->split = false; r->scored = false; r->reduced = false; r->sums_valid = false; }
+    return KP_OK;
+}
+
+int kp_batch_stats(kp_ctx *ctx, kp_batch *b, int64_t *stats5) {
+    if (!ctx || !b || b->ctx != ctx || !stats5) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    std::memcpy(stats5, w->stats, sizeof w->stats);
+    return KP_OK;
+}
+
+int kp_batch_profile(kp_ctx *ctx, kp_batch *b, float *ms7, int64_t *bytes_scanned) {
+    if (!ctx || !b || b->ctx != ctx || !ms7) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    for (int i = 0; i < 3 + KP_N_CLASSES; ++i)
+        if (hipEventElapsedTime(&ms7[i], w->ev[i], w->ev[i + 1]) != hipSuccess)
+            return kp_fail(ctx, KP_EHIP, "event timing failed");
+    if (bytes_scanned) *bytes_scanned = 4 * b->view.total_words;
+    return KP_OK;
+}
+
+int64_t kp_batch_anchors(kp_ctx *ctx, kp_batch *b, int32_t a, uint64_t *out, int64_t cap) {
+    if (!ctx || !b || b->ctx != ctx || a < 0 || a >= b->n_asm) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    const int64_t n = w->h_counts[(size_t)a];
+    const int64_t m = std::min(n, cap);
+    if (out && m > 0) {
+        if (hipMemcpy(out, w->d_anchors_a.p + (size_t)a * w->anchor_cap, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+            return kp_fail(ctx, KP_EHIP, "D2H anchors failed");
+        for (int64_t i = 0; i < m; ++i) out[i] = kp_key_unpack(out[i], w->key_bits);  // callers see the spec's layout
+    }
+    return n;
+}
+
+int64_t kp_batch_tasks(kp_ctx *ctx, kp_batch *b, int32_t a, int32_t *out8, int64_t cap) {
+    if (!ctx || !b || b->ctx != ctx || a < 0 || a >= b->n_asm) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    for (int c = 0; c < KP_N_CLASSES; ++c) {  // fetched on first use: only the stage tests look at tasks
+        const size_t nt = w->h_counts[(size_t)b->n_asm + c];
+        if (w->h_tasks[c].size() == nt) continue;
+        w->h_tasks[c].resize(nt);
+        if (nt && hipMemcpy(w->h_tasks[c].data(), w->d_tasks.p + (size_t)c * w->task_cap, nt * sizeof(KpTask), hipMemcpyDeviceToHost) != hipSuccess)
+            return kp_fail(ctx, KP_EHIP, "D2H tasks failed");
+    }
+    int64_t n = 0;
+    for (int c = 0; c < KP_N_CLASSES; ++c)
+        for (const KpTask &t : w->h_tasks[c]) {
+            if (t.asm_id != a || t.n_anchors == 0) continue;  // (n_anchors == 0: a cluster the chaining rejected)
+            if (out8 && n < cap) {
+                int32_t *o = out8 + 8 * n;
+                o[0] = t.gs; o[1] = t.contig; o[2] = t.lo; o[3] = t.width; o[4] = t.n_anchors; o[5] = (int32_t)(t.qspan & 0xFFFFu); o[6] = (int32_t)(t.qspan >> 16); o[7] = t.chain_score;
+            }
+            ++n;
+        }
+    return n;
+}
+
+int64_t kp_batch_task_results(kp_ctx *ctx, kp_batch *b, int32_t a, int32_t *out7, int64_t cap) {
+    if (!ctx || !b || b->ctx != ctx || a < 0 || a >= b->n_asm) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    const int64_t n_tasks = kp_batch_tasks(ctx, b, a, nullptr, 0);  // (also fetches the task lists)
+    if (n_tasks < 0) return n_tasks;
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    int64_t n = 0;
+    std::vector<KpSwResult> res;
+    for (int c = 0; c < KP_N_CLASSES; ++c) {
+        const size_t nt = w->h_tasks[c].size();
+        res.resize(nt);
+        if (nt && hipMemcpy(res.data(), w->d_results.p + (size_t)c * w->task_cap, nt * sizeof(KpSwResult), hipMemcpyDeviceToHost) != hipSuccess)
+            return kp_fail(ctx, KP_EHIP, "D2H task results failed");
+        for (size_t i = 0; i < nt; ++i) {
+            if (w->h_tasks[c][i].asm_id != a || w->h_tasks[c][i].n_anchors == 0) continue;
+            if (out7 && n < cap) {
+                const KpSwResult &r = res[i];
+                int32_t *o = out7 + 7 * n;
+                o[0] = r.score; o[1] = r.q_start; o[2] = r.q_end; o[3] = r.t_start; o[4] = r.t_end; o[5] = r.matches; o[6] = r.block_len;
+            }
+            ++n;
+        }
+    }
+    return n;
+}
+
+int64_t kp_batch_joins(kp_ctx *ctx, kp_batch *b, int32_t a, int32_t *out, int64_t cap) {
+    if (!ctx || !b || b->ctx != ctx || a < 0 || a >= b->n_asm) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    size_t total = 0;
+    for (int c = 0; c < KP_N_CLASSES; ++c) total += w->h_join_counts[1 + c];
+    if (w->h_joins.size() != total) {  // fetched on first use: only the stage tests look at joins
+        w->h_joins.resize(total);
+        size_t at = 0;
+        for (int c = 0; c < KP_N_CLASSES; ++c) {
+            const size_t nj = w->h_join_counts[1 + c];
+            if (nj && hipMemcpy(w->h_joins.data() + at, w->d_joins.p + (size_t)c * w->join_cap, nj * sizeof(KpJoin), hipMemcpyDeviceToHost) != hipSuccess)
+                return kp_fail(ctx, KP_EHIP, "D2H joins failed");
+            at += nj;
+        }
+    }
+    int64_t n = 0;
+    for (const KpJoin &J : w->h_joins) {
+        if (J.asm_id != a) continue;
+        if (out && n < cap) {
+            int32_t *o = out + KP_JOIN_ROW_INTS * n;
+            std::memset(o, 0, KP_JOIN_ROW_INTS * sizeof(int32_t));
+            o[0] = J.gs; o[1] = J.contig; o[2] = J.n_pieces; o[3] = J.n_anchors; o[4] = J.chain_score; o[5] = J.width;
+            for (int k = 0; k < J.n_pieces; ++k) {
+                o[6 + k] = J.lo[k];
+                int32_t *pr = o + 6 + KP_JOIN_MAX_PIECES + 11 * k;
+                pr[0] = J.state[k]; pr[1] = J.visited[k];
+                if (J.state[k] == 1) std::memcpy(pr + 2, J.res[k], 9 * sizeof(int32_t));
+            }
+        }
+        ++n;
+    }
+    return n;
+}
+
+}  // extern "C"

@@ -275,6 +275,22 @@ void kp_launch_join_trace(const KpBatchView &b, const KpGenes &genes, KpJoin *jo
 // indices relative to gene_lo; out_n[a] = how many
 void kp_launch_hit_split(const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap, int32_t gene_lo, int32_t gene_hi,
                          kp_hit *out, uint32_t *out_n, int32_t n_asm, hipStream_t stream);
+// kp_reduce.hip: hit-table finalisation, locus scores, the typing reduction and its gene states (types: kp_reduce_core.h)
+struct KpTypingDb;
+void kp_launch_hit_finalise(const KpBatchView &b, const int32_t *gene_len, const KpTask *tasks, const KpSwResult *results, const uint8_t *task_drop,
+                            const uint32_t *task_count, uint32_t task_cap, kp_hit *raw, uint32_t *n_raw, uint32_t hit_cap,
+                            uint64_t *keys, kp_hit *hits, uint32_t *n_hits, unsigned long long *cells, const float *ln_half,
+                            const float *ln_int, const KpJoin *joins, const uint32_t *join_count, uint32_t join_cap, hipStream_t stream);
+void kp_launch_score(const KpBatchView &b, const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap,
+                     const KpTypingDb &db, double min_cov, double *scores, int32_t *counts, hipStream_t stream);
+void kp_launch_reduce(const KpBatchView &b, const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap,
+                      const KpTypingDb &db, const kp_typing_params &prm, const int32_t *best, uint64_t *keys,
+                      uint32_t *order, uint8_t *kept_flag, kp_kept *kept, int kept_cap, kp_piece *pieces, int piece_cap,
+                      kp_asm_summary *summary, uint8_t *prot, int prot_cap, int32_t *pair_q_off, int32_t *pair_q_len,
+                      int32_t *pair_t_off, int32_t *pair_t_len, int32_t *n_pairs, int32_t *pair_base,
+                      hipStream_t stream);
+void kp_launch_states(const KpBatchView &b, const KpTypingDb &db, const kp_typing_params &prm, kp_kept *kept, int kept_cap,
+                      kp_asm_summary *summary, const int32_t *dp8, const int32_t *pair_base, hipStream_t stream);
 // kp_reduce.hip: `bytes` (a multiple of 4) of device memory into page-locked host memory, written by a kernel
 void kp_launch_read_back(const void *src, void *dst_pinned, size_t bytes, hipStream_t stream);
 void kp_launch_pack_rows(const uint32_t *src, size_t src_pitch, uint32_t *dst, size_t dst_pitch, size_t width, int rows,

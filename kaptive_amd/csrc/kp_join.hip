@@ -19,7 +19,7 @@
 //                          their drop flag (task_drop: read by the hit compaction -- the band fill is writing the task
 //                          results while this runs)
 //
-// All of it runs on a stream of its own beside the band tasks' fill and traceback (kp_capi.hip).  Plain 32-bit arithmetic:
+// All of it runs on a stream of its own beside the band tasks' fill and traceback (kp_align.hip).  Plain 32-bit arithmetic:
 // some twenty joins per thousand assemblies on the headline workload, 55 per assembly on `bench.py --mix joins`.
 #include "kp_internal.h"
 #include <cstdio>
@@ -667,7 +667,7 @@ void kp_launch_join_chain(const KpBatchView &b, const KpGenes &genes, const uint
 size_t kp_join_chain_scratch_bytes() { return (size_t)join_launch().chain_large * JOIN_CHAIN_SCRATCH; }
 
 // The join kernels need nothing of the band tasks' fill and traceback: they run beside them, on a stream of their own
-// (kp_capi.hip); the walk-back marks the band tasks whose hits a chain consumes (task_drop), which the hit compaction reads.
+// (kp_align.hip); the walk-back marks the band tasks whose hits a chain consumes (task_drop), which the hit compaction reads.
 void kp_launch_join_fill(const KpBatchView &b, const KpGenes &genes, KpJoin *joins, const uint32_t *join_count, uint32_t join_cap,
                          void *trace, unsigned long long *trace_top, uint64_t trace_cap_units, hipStream_t stream) {
     const char *skip_env = std::getenv("KAPTIVE_AMD_SKIP_JOINS");

@@ -540,7 +540,7 @@ __global__ __launch_bounds__(256) void kp_pack_rows_kernel(const uint32_t *__res
     for (size_t i = threadIdx.x; i < dst_pitch; i += blockDim.x) d[i] = i < width ? s[i] : 0u;
 }
 
-// device memory -> page-locked host memory by the shader instead of a copy engine (kp_capi.hip: Fetch)
+// device memory -> page-locked host memory by the shader instead of a copy engine (kp_host.h: Fetch)
 __global__ __launch_bounds__(256) void kp_read_back_kernel(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] = src[i];
 }

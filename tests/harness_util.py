@@ -26,14 +26,18 @@ class TypingParams(C.Structure):
                 ("edge_tolerance", C.c_int32)]  # fmt: skip
 
 
+def build_harness(name: str, header: str) -> C.CDLL:
+    """g++ build of tests/native_harness/<name>.cpp, redone when it or the csrc header it compiles is newer."""
+    so, src, core = HERE / f"lib{name}.so", HERE / f"{name}.cpp", ROOT / "kaptive_amd" / "csrc" / header
+    if not so.exists() or so.stat().st_mtime < max(src.stat().st_mtime, core.stat().st_mtime):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", str(so), str(src)], check=True)
+    return C.CDLL(str(so))
+
+
 def lib() -> C.CDLL:
     global _LIB
     if _LIB is None:
-        so, src = HERE / "libreduce_harness.so", HERE / "reduce_harness.cpp"
-        core = ROOT / "kaptive_amd" / "csrc" / "kp_reduce_core.h"
-        if not so.exists() or so.stat().st_mtime < max(src.stat().st_mtime, core.stat().st_mtime):
-            subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-o", str(so), str(src)], check=True)
-        _LIB = C.CDLL(str(so))
+        _LIB = build_harness("reduce_harness", "kp_reduce_core.h")
     return _LIB
 
 

@@ -16,7 +16,7 @@ e. per-assembly buffers the library could not index: anchor_cap * n_asm of 2^32 
 Every comparison covers every entry of its batch: hit tables field for field, report rows byte for byte.  Three limits
 are out of scope, because they cannot be reached without doing that much real work: 64 GB of DP trace, 2^24 hits in one
 assembly and 65 536 occurrence tables.  Each refusal tested here is a checked return at the head of enqueue_align /
-enqueue_reduce (kp_capi.hip), before the first reservation and the first launch of the pass."""
+enqueue_reduce (kp_align.hip, kp_typing.hip), before the first reservation and the first launch of the pass."""
 
 import json
 

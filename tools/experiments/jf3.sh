@@ -12,7 +12,5 @@ PY
 }
 for rep in a b; do
   run default_$rep X=1
-  run afterfill_$rep KAPTIVE_AMD_JOIN_AFTER_FILL=1
-  run afterfill_small_$rep KAPTIVE_AMD_JOIN_AFTER_FILL=1 KAPTIVE_AMD_JOIN_GRID=64,16,512,16
   run none_$rep KAPTIVE_AMD_SKIP_JOINS=7
 done

@@ -1,5 +1,5 @@
 #!/bin/bash
-# round 6: what about the joined fill costs the headline workload (20 joins per batch): grid, wave priority, the launch itself
+# round 6: what about the joined fill costs the headline workload (20 joins per batch): grid, wave priority
 cd $GRAFT_REPO_ROOT; OUT=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $OUT
 run() { name=$1; shift
   env "$@" python bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-e2e --no-secondary --workers 16 > $OUT/jf_$name.log 2> $OUT/jf_$name.err
@@ -17,5 +17,4 @@ for rep in a b; do
   run noprio_$rep KAPTIVE_AMD_JOIN_PRIO=0
   run small_noprio_$rep KAPTIVE_AMD_JOIN_GRID=32,8,64,8 KAPTIVE_AMD_JOIN_PRIO=0
   run nofill_$rep KAPTIVE_AMD_SKIP_JOINS=6
-  run d16_$rep KAPTIVE_AMD_DUMMY_LAUNCHES=16
 done
