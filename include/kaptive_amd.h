@@ -63,7 +63,9 @@ KP_API void *kp_ctx_stream(kp_ctx *ctx);
  * sized from the batch with a floor of 64 Ki entries and 64 KiB; group_cap, join_cap: groups of clusters and joins per
  * band class of a batch; occ_slots: counting tables of the occurrence cut, at most 65536 -- setting one also forgets
  * what the context has learnt for it), library_sort (anchors are sorted by the library's segmented radix sort instead of
- * the bucket sort of kp_bsort.hip; same result), scan_mode (ablation modes of the scan kernel, tools/scan_ablate.py). */
+ * the bucket sort of kp_bsort.hip; same result), scan_mode (ablation modes of the scan kernel, tools/scan_ablate.py),
+ * cigar (0 | 1: CIGARs of the hits, kp_batch_cigars; from the next kp_batch_align) and cigar_ops_per_hit (first size of their
+ * buffer; setting it forgets what the context has learnt for it). */
 KP_API int kp_ctx_set_option(kp_ctx *ctx, const char *name, int64_t value);
 #define KP_WORK_SLOTS 3
 
@@ -214,6 +216,18 @@ KP_API int kp_batch_hits(kp_ctx *ctx, kp_batch *batch, kp_hit *out, int64_t cap)
  * produce (equal scores, mapq 0 / 255 / 1 ties: src/kaptive/core/alignment.py:669-675) reach the device reduction in the
  * parity tests. */
 KP_API int kp_batch_set_hits(kp_ctx *ctx, kp_batch *batch, const kp_hit *hits, const int64_t *hit_off);
+/* CIGARs of the batch's hits (kp_spec.h, CIGAR): what the reference gets from Aligner(..., do_cigar=True)
+ * (src/kaptive/serotyping/core.py:148) and keeps in Alignments.cigars (src/kaptive/core/alignment.py:872).  Only for a batch
+ * whose kp_batch_align ran with the option `cigar` set (kp_ctx_set_option(ctx, "cigar", 1); default 0: nothing is computed,
+ * allocated or launched for them) -- otherwise, and after kp_batch_set_hits, both calls return KP_ESTATE.
+ *   kp_batch_cigar_offsets : cigar_off[total_hits + 1], rows as kp_batch_hits lists them: the ops of hit i are
+ *                            ops[cigar_off[i] .. cigar_off[i + 1])
+ *   kp_batch_cigars        : the ops, len << 4 | op with M = 0, I = 1, D = 2 (BAM), in the order of increasing target
+ *                            position; KP_EINVAL when cap < cigar_off[total_hits]
+ * The option `cigar_ops_per_hit` is the first guess for the size of the ops buffer (default 4); the context learns what its
+ * batches need, and a buffer that was too small is grown and the ops written again without another alignment pass. */
+KP_API int kp_batch_cigar_offsets(kp_ctx *ctx, kp_batch *batch, int64_t *cigar_off);
+KP_API int kp_batch_cigars(kp_ctx *ctx, kp_batch *batch, uint32_t *ops, int64_t cap);
 /* counters of the last kp_batch_align: [0] anchors, [1] band tasks, [2] DP cells, [3] hits, [4] overflow retries */
 KP_API int kp_batch_stats(kp_ctx *ctx, kp_batch *batch, int64_t *stats5);
 
@@ -321,6 +335,26 @@ typedef struct kp_row_columns {  /* per assembly of the batch */
 KP_API int64_t kp_format_rows(const kp_row_tables *tables, int32_t n_asm, const kp_asm_summary *summaries,
                               const kp_kept *kept, int32_t kept_stride, const kp_row_columns *columns, char *out,
                               int64_t cap);
+
+/* ---- PAF lines of a hit table (host only) -------------------------------------------------------------------------------------
+ * One line per hit, in the table's order, as minimap2 -c writes a mapping: gene name, gene length, q_start, q_end, strand,
+ * contig name, contig length, t_start, t_end, matches, block_len, mapq, AS:i:<score>, NM:i:<block_len - matches>,
+ * cg:Z:<ops>; tab-separated, '\n' at the end.  Names are byte blobs with n + 1 offsets; the contigs of all assemblies lie
+ * back to back, assembly a's are asm_first_ctg[a] .. asm_first_ctg[a + 1].  Returns the number of bytes the lines need
+ * (written to `out` while they fit `cap`), or a negative error code (KP_EINVAL also for a hit that names a gene or contig
+ * the tables do not have). */
+typedef struct kp_paf_tables {
+    const char *gene_names;
+    const int32_t *gene_name_off;
+    const int32_t *gene_len;
+    int32_t n_genes;
+    const char *ctg_names;
+    const int64_t *ctg_name_off;
+    const int32_t *ctg_len;
+    const int64_t *asm_first_ctg; /* n_asm + 1 */
+} kp_paf_tables;
+KP_API int64_t kp_format_paf(const kp_paf_tables *tables, int32_t n_asm, const kp_hit *hits, const int64_t *hit_off,
+                             const uint32_t *ops, const int64_t *cigar_off, char *out, int64_t cap);
 
 /* ---- JSON lines of a whole batch (host only) ----------------------------------------------------------------------------------
  * Replaces orjson.dumps(SerotypingResult.to_dict(), OPT_SERIALIZE_NUMPY | OPT_APPEND_NEWLINE) per genome

@@ -340,6 +340,35 @@ typedef struct kp_hit {
     uint8_t pad_;
 } kp_hit;
 
+/* ---- CIGAR (optional: computed only where the caller asks for it; no hit and no field of a hit depends on it) ----------------
+ * The CIGAR of a hit is the path its fields were computed from, as run-length ops in BAM encoding -- what the reference's
+ * parse_cigar_string produces (src/kaptive/core/alignment.py:872): uint32 len << KP_CIGAR_SHIFT | op, op M = 0, I = 1, D = 2.
+ * The query is the gene and the target the contig, as in minimap2 and PAF: a diagonal step of the path is an M column, a
+ * step in state E (gap in the query, moves along the target) a D column, a step in state F (gap in the target, moves along
+ * the query) an I column; the columns of a joined path's cross gap are D when the gap runs along a row (the later piece
+ * lies on higher diagonals) and I when it runs down a column.  Ops are listed in the order of increasing target position;
+ * for strand -1 that is the order of the reverse-complemented gene, as minimap2 writes them.
+ *
+ * CANONICAL FORM.  No op has length 0; no two neighbouring ops have the same kind -- a cross gap that touches an in-band gap
+ * of its kind is one op with it --; the first and the last op are M (a local path starts and ends on a diagonal step: a gap
+ * state lies strictly below the H it derives from).
+ *
+ * CONSISTENCY WITH THE HIT.  sum M + sum I = q_end - q_start; sum M + sum D = t_end - t_start; sum M + sum I + sum D =
+ * block_len; the M columns hold exactly `matches` pairs of equal unambiguous bases.  Scoring the ops again -- KP_SC_MATCH /
+ * KP_SC_MISMATCH / KP_SC_N per M column, min(4 + 2 n, 24 + n) per gap op of n columns -- gives exactly `score` for the hit of
+ * a band task, and at least `score` for a joined hit (a merged op is cheaper than the gaps it was made of).
+ *
+ * SAME-SPAN HITS.  Of hits with the same span one record is emitted (above); its CIGAR is the path of the source -- band task
+ * or joined path -- whose record that is, i.e. that agrees with it in every field.  Where several sources do, the CIGAR is that
+ * of the first of them in this order: band tasks before joins; then the lower band origin `lo` (of a joined path: of the
+ * piece it ends in); then the narrower band.  Sources that agree in these too fill the same band of the same contig with the
+ * same gene; for band tasks that is the same fill and the same path.  The rule reads nothing but the data: it never depends
+ * on the order in which the device appended records. */
+#define KP_CIGAR_M 0
+#define KP_CIGAR_I 1
+#define KP_CIGAR_D 2
+#define KP_CIGAR_SHIFT 4
+
 /* ---- records of the batched reduction (one assembly = one summary, its kept hits and its locus pieces) ------------------
  * They carry what SerotypingResult needs (src/kaptive/serotyping/models.py:513-536) minus strings and sequences. */
 #define KP_F_EXPECTED 1u /* gene belongs to the best locus and is not an extra gene (core.py:226-228) */

@@ -106,6 +106,8 @@ def _add_outputs(p: argparse.ArgumentParser, tsv_flags, include_json: bool) -> N
     if include_json:
         g.add_argument("-j", "--json", metavar="FILE", nargs="?", const="kaptive_results.jsonl",
                        help="Write serialised results to a newline-delimited JSON (default: %(const)s)")
+        g.add_argument("--paf", metavar="FILE", default=argparse.SUPPRESS,  # (absent from the namespace unless given)
+                       help="Write every gene hit (before the overlap cull, in the aligner's order) with its CIGAR as PAF lines to a file")
     g.add_argument("--pha4ge", metavar="FILE", nargs="?", const="kaptive_results.pha4ge", type=Path,
                    help="Write PHA4GE-compliant serotyping report to a TSV file (default: %(const)s)")
 
@@ -177,7 +179,8 @@ class _TypingPipeline:
 
         self.args = args
         self.marks = {"pipeline_start": time.perf_counter()}  # (KAPTIVE_AMD_CLI_TIMING: where the time before the first rows goes)
-        self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins"))  # the files' text is kept
+        self.want_paf = bool(getattr(args, "paf", None))  # every hit with its CIGAR: the alignment passes of this run leave them
+        self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins", "paf"))  # the files' text (and contig names) are kept
         self.fasta_outputs = any(getattr(args, f, None) for f in ("loci", "genes", "proteins"))  # ... and result objects are built
         self.threads = max(1, args.threads or usable_cpus())  # (the cgroup's quota, not the 256 CPUs a container may see)
         # PREFETCH + 1 chunks are being parsed at any time, each by one native call: the thread budget is shared out among them
@@ -252,6 +255,8 @@ class _TypingPipeline:
             if early_ctx is not None:
                 self._ctx_pool.shutdown(wait=False, cancel_futures=True)
             raise
+        if self.want_paf:
+            self.engine.ctx.set_option("cigar", 1)  # (this run's context only)
         self.marks["context_ready"] = time.perf_counter()
         self.want_tsv = bool(getattr(args, "out", None))
         # several databases: every chunk's outputs are ((keyword, outputs), ...), one entry per database in order
@@ -419,8 +424,10 @@ class _TypingPipeline:
         args = self.args
         self._order = []
 
-        def render(bt, keyword=None) -> dict:
+        def render(bt, keyword=None, aligned=None, group=0) -> dict:
             out = {}
+            if aligned is not None:
+                out["paf"] = hits_to_paf(self.engine.view(group), bt.genomes, *aligned)
             if self.want_tsv:
                 out["tsv"] = bt.tsv()
             if getattr(args, "pha4ge", None):
@@ -442,20 +449,24 @@ class _TypingPipeline:
         rendering: deque = deque()
         done = 0
         if self.keywords is None:
-            stream, job = self.engine.type_stream(self.typer, self._source(chunks)), render
+            stream = self.engine.type_stream(self.typer, self._source(chunks))
+
+            def job(bt, aligned=None) -> dict:
+                return render(bt, None, aligned)
         else:  # every database's records from the one alignment pass of the batch, rendered by the same formatters
             kws = self.keywords
             stream = self.engine.type_stream_groups(self.typer.serotypers, self._source(chunks))
 
-            def job(bts) -> tuple:
-                return tuple((kw, render(bt, kw)) for kw, bt in zip(kws, bts))
+            def job(bts, aligned=None) -> tuple:
+                return tuple((kw, render(bt, kw, aligned, g)) for g, (kw, bt) in enumerate(zip(kws, bts)))
 
         for bt, batch in stream:
             pb, batch._pin = getattr(batch, "_pin", None), None
+            aligned = (*batch.hits(), *batch.cigars()) if self.want_paf else None  # (the batch's results go with it)
             batch.close()  # (waits for whatever of the batch is still in flight: the pinned words are free after it)
             if pb is not None:
                 self._give_back(pb)
-            rendering.append(self.formatters.submit(job, bt))
+            rendering.append(self.formatters.submit(job, bt, aligned))
             while rendering and (rendering[0].done() or len(rendering) > 2):
                 yield self._order[done], rendering.popleft().result()
                 done += 1
@@ -519,6 +530,28 @@ class _ChunkSource:
         if prev is not None:
             pipe.release_pin(prev)
         return batch, ids, genomes if pipe.objects else None
+
+
+def hits_to_paf(engine, genomes, hits, hit_off, ops, cigar_off) -> bytes:
+    """PAF lines (``--paf``) of a batch's hit table for the database ``engine`` views: its genes' hits of every genome, in
+    the table's order, genomes in the batch's order.  Column-wise: the rows of the database are picked by a mask and the
+    lines come from one native call (``_native.format_paf``)."""
+    from kaptive_amd import _native
+    from kaptive_amd.core.alignment import Cigars
+
+    lo, hi = engine.gene_ranges[engine.group]
+    keep = (hits["gene"] >= lo) & (hits["gene"] < hi)
+    if not keep.all():
+        kept_before = np.concatenate([[0], np.cumsum(keep)])
+        hit_off = kept_before[hit_off]
+        cig = Cigars.from_offsets(ops, cigar_off)[keep]
+        ops, cigar_off = cig.data, np.concatenate([[0], np.cumsum(cig.lengths, dtype=np.int64)])
+        hits = hits[keep].copy()
+        hits["gene"] -= lo
+    first = np.concatenate([[0], np.cumsum([len(g.contigs.ids) for g in genomes])])
+    names = [n for g in genomes for n in g.contigs.ids]
+    lengths = np.concatenate([np.asarray(g.contigs.lengths, np.int32) for g in genomes]) if genomes else np.zeros(0, np.int32)
+    return _native.format_paf(engine.db.genes.ids, engine.db.genes.lengths, names, lengths, first, hits, hit_off, ops, cigar_off)
 
 
 def _read_ahead_bytes() -> int:
@@ -623,7 +656,7 @@ class _PerDatabaseOutputs:
     genome by genome (``interleave_lines``).  The files are opened with the first chunk's outputs, which carry the
     databases' keywords."""
 
-    KINDS = (("tsv", "out"), ("pha4ge", "pha4ge"), ("json", "json"))
+    KINDS = (("tsv", "out"), ("pha4ge", "pha4ge"), ("json", "json"), ("paf", "paf"))
 
     def __init__(self, args: argparse.Namespace) -> None:
         self.wanted = [(key, path) for key, attr in self.KINDS if (path := getattr(args, attr, None))]
@@ -633,7 +666,7 @@ class _PerDatabaseOutputs:
     def _open(self, keywords) -> None:
         from kaptive_amd.serotyping.io import KaptiveRow, Pha4geRow
 
-        headers = {"tsv": KaptiveRow.header(), "pha4ge": Pha4geRow.header(), "json": b""}
+        headers = {"tsv": KaptiveRow.header(), "pha4ge": Pha4geRow.header(), "json": b"", "paf": b""}
         self.streams = {}
         for key, path in self.wanted:
             if _is_stdout(path):
@@ -712,6 +745,8 @@ def run_type(args: argparse.Namespace) -> int:
             handles["pha4ge"].write(Pha4geRow.header())
         if j := getattr(args, "json", None):
             handles["json"] = stream(j)
+        if f := getattr(args, "paf", None):
+            handles["paf"] = stream(f)
     done = 0
     timing_path = os.environ.get("KAPTIVE_AMD_CLI_TIMING")  # bench.py: when each chunk's rows were written
     t_start, chunk_times, phases = time.perf_counter(), [], {}

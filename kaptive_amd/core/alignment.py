@@ -2,10 +2,12 @@
 
 Column names follow the reference's ``kaptive.core.alignment.Alignments`` (src/kaptive/core/alignment.py:262-317) so
 code written against it keeps working.  The way in is ``from_hit_table``: the HIP aligner already returns columns,
-nothing is parsed per hit (the reference loops over hit objects, alignment.py:392-474).  The aligner produces no CIGAR
-strings -- the reference parses them and never reads them on the typing path -- so the ``cigars``
-column exists for shape compatibility only and is always empty; the reference's CIGAR parser, ``swap_sides`` and ``best``
-have no counterpart here.
+nothing is parsed per hit (the reference loops over hit objects, alignment.py:392-474).  The ``cigars`` column holds
+BAM-encoded ops (``len << 4 | op``, M = 0, I = 1, D = 2: what the reference's ``parse_cigar_string`` produces,
+alignment.py:872) when the aligner was asked for them (``Engine(db, cigar=True)``: the device walks every path a second
+time, include/kp_spec.h, CIGAR); the typing path never reads them, so by default they are not
+computed and the column is empty.  ``to_paf`` writes a table with its CIGARs as PAF lines.  The reference's CIGAR string
+parser, ``swap_sides`` and ``best`` have no counterpart here.
 
 The reductions used by typing (``q_covs``, ``cull_overlaps``, ``is_partial``) follow
 src/kaptive/core/alignment.py:355-367, 643-686 and 774-809.
@@ -21,18 +23,21 @@ import numpy as np
 from kaptive_amd.core.interval import Intervals, Strand
 
 def _ragged_take(data: np.ndarray, offsets: np.ndarray, lengths: np.ndarray, idx: np.ndarray):
+    """Rows ``idx`` of a ragged array, gathered without a loop over the rows."""
     new_len = lengths[idx]
-    new_off = np.zeros(len(new_len), dtype=np.int32)
+    new_off = np.zeros(len(new_len), dtype=offsets.dtype)
     if len(new_len) > 1:
         np.cumsum(new_len[:-1], out=new_off[1:])
-    parts = [data[offsets[i] : offsets[i] + lengths[i]] for i in idx]
-    return (np.concatenate(parts) if parts else data[:0]), new_off, new_len
+    total = int(new_len.sum())
+    # element j of output row k comes from offsets[idx[k]] + j
+    src = np.repeat(offsets[idx].astype(np.int64) - new_off.astype(np.int64), new_len) + np.arange(total, dtype=np.int64)
+    return data[src], new_off, new_len
 
 
 @dataclass(frozen=True, slots=True)
 class Cigars:
     data: np.ndarray  # uint32
-    offsets: np.ndarray  # int32
+    offsets: np.ndarray  # int32 or int64: first op of every row in `data`
     lengths: np.ndarray  # int32
 
     def __len__(self) -> int:
@@ -61,6 +66,13 @@ class Cigars:
         return cls(np.empty(0, np.uint32), np.zeros(n, np.int32), np.zeros(n, np.int32))
 
     @classmethod
+    def from_offsets(cls, ops: np.ndarray, offsets: np.ndarray) -> "Cigars":
+        """Rows ``ops[offsets[i]:offsets[i + 1]]`` (what ``_native.Batch.cigars`` returns, or a slice of it: the offsets
+        need not start at 0 -- the rows of one assembly are ``from_offsets(ops, off[a0 : a1 + 1])``).  No copy of ``ops``."""
+        offsets = np.asarray(offsets)
+        return cls(np.asarray(ops, np.uint32), offsets[:-1].astype(np.int64), np.diff(offsets).astype(np.int32))
+
+    @classmethod
     def from_lists(cls, cigars: list[np.ndarray]) -> "Cigars":
         if not cigars:
             return cls.empty()
@@ -72,7 +84,18 @@ class Cigars:
 
     @classmethod
     def concat(cls, batches: Iterable["Cigars"]) -> "Cigars":
-        return cls.from_lists([b[i] for b in batches for i in range(len(b))])
+        bs = [b[:] for b in batches]  # (compact: every batch's ops back to back, offsets from 0; tables without CIGARs have rows of length 0)
+        if not bs:
+            return cls.empty()
+        lengths = np.concatenate([b.lengths for b in bs]).astype(np.int32)
+        offsets = np.zeros(len(lengths), np.int64)
+        if len(lengths) > 1:
+            np.cumsum(lengths[:-1], out=offsets[1:])
+        return cls(np.concatenate([b.data for b in bs]).astype(np.uint32), offsets, lengths)
+
+    def to_strings(self) -> list[str]:
+        """The CIGARs as text ("120M1I35M"); for display and tests -- bulk output goes through ``Alignments.to_paf``."""
+        return ["".join(f"{int(v) >> 4}{'MIDNSHP=XB'[int(v) & 15]}" for v in self[i]) for i in range(len(self))]
 
 class Alignment(NamedTuple):
     idx: int
@@ -162,6 +185,7 @@ class Alignments:
         matches: np.ndarray,
         scores: np.ndarray,
         mapqs: np.ndarray,
+        cigars: "Cigars | None" = None,
     ) -> "Alignments":
         """Wrap columns produced by the native aligner. ``q_ids``/``t_ids`` index ``q_names``/``t_names`` directly
         (the native path numbers contigs by their order in the assembly, not by first appearance in the hits)."""
@@ -180,7 +204,7 @@ class Alignments:
             t_ends=np.asarray(t_ends, np.int32),
             strands=np.asarray(strands, np.int8), lengths=block_lens, matches=matches,
             mismatches=(block_lens - matches).astype(np.int32), scores=np.asarray(scores, np.int32),
-            qualities=np.asarray(mapqs, np.uint8), cigars=Cigars.empty(n),
+            qualities=np.asarray(mapqs, np.uint8), cigars=Cigars.empty(n) if cigars is None else cigars,
             is_primary=primary, is_supplementary=np.zeros(n, np.bool_), is_spliced=np.zeros(n, np.bool_),
             divergence=div.astype(np.float64), cs=np.full(n, None, dtype=object), md=np.full(n, None, dtype=object),
         )  # fmt: skip
@@ -247,6 +271,29 @@ class Alignments:
         return Alignments(
             q_names_dict=self.q_names_dict, t_names_dict=self.t_names_dict, cigars=self.cigars[item], **cols
         )
+
+    def to_paf(self, q_names: "tuple[str, ...] | None" = None) -> bytes:
+        """The table as PAF lines, one per hit in the table's order (kp_format_paf, include/kaptive_amd.h): query name and
+        length, q_start, q_end, strand, target name and length, t_start, t_end, matches, block length, mapq, ``AS:i``,
+        ``NM:i`` (block length - matches) and ``cg:Z`` with the CIGAR -- empty where the table carries none.  ``q_names``
+        replaces ``q_names_dict`` (the engine numbers genes; the command line passes the database's gene names)."""
+        from kaptive_amd import _native
+
+        n = len(self)
+        names = tuple(self.q_names_dict if q_names is None else q_names)
+        hits = np.zeros(n, _native.HIT_DTYPE)
+        for col, src in (("gene", self.q_name_ids), ("contig", self.t_name_ids), ("q_start", self.q_starts), ("q_end", self.q_ends),
+                         ("t_start", self.t_starts), ("t_end", self.t_ends), ("score", self.scores), ("matches", self.matches),
+                         ("block_len", self.lengths), ("strand", self.strands), ("mapq", self.qualities)):  # fmt: skip
+            hits[col] = src
+        q_len = np.zeros(len(names), np.int32)
+        q_len[self.q_name_ids] = self.q_lengths
+        t_len = np.zeros(len(self.t_names_dict), np.int32)
+        t_len[self.t_name_ids] = self.t_lengths
+        cig = self.cigars[:] if len(self.cigars) == n and n else Cigars.empty(n)
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum(cig.lengths, out=off[1:])
+        return _native.format_paf(names, q_len, self.t_names_dict, t_len, [0, len(self.t_names_dict)], hits, [0, n], cig.data, off)
 
     @property
     def q_names(self) -> np.ndarray:

@@ -147,6 +147,7 @@ int kp_batch_align(kp_ctx *ctx, kp_batch *b) {
     }
     kp_caps_size(ctx->opt, ctx->learnt, b->n_asm, b->view.total_words, *w);
     w->aligned = false; w->finalised = false;
+    w->cigar_on = ctx->opt.cigar != 0; w->cigar_valid = false;
     for (auto &v : w->h_tasks) v.clear();
     for (auto &r : w->runs)
         if (r) { r->split = false; r->scored = false; r->reduced = false; r->sums_valid = false; }
@@ -190,6 +191,41 @@ static int finalise_hits_on_device(kp_ctx *ctx, kp_batch *b, KpWork *w) {
     return KP_OK;
 }
 
+// CIGARs of the finished hits (kp_cigar.hip): sources located, ops counted, scanned and written on the post stream.  The ops
+// buffer follows the policy of kp_caps.h; where it was too small only the writing kernel runs again -- the counts and offsets
+// are exact whatever the buffer held, and the direction bits of the pass are still in the work set's trace buffer.
+static int emit_cigars(kp_ctx *ctx, kp_batch *b, KpWork *w) {
+    const size_t n_asm = (size_t)b->n_asm;
+    const int64_t total = w->hit_off[n_asm];
+    w->cigar_cap = kp_caps_cigar_size(ctx->opt, ctx->learnt, (uint64_t)total);
+    KP_HIP_CHECK(ctx, w->d_cig_src.reserve(n_asm * w->hit_cap));
+    KP_HIP_CHECK(ctx, w->d_cig_cnt.reserve((size_t)total));
+    KP_HIP_CHECK(ctx, w->d_cig_off.reserve((size_t)total + 1));
+    KP_HIP_CHECK(ctx, w->d_cig_hit_off.reserve(n_asm + 1));
+    KP_HIP_CHECK(ctx, w->d_cig_ops.reserve(w->cigar_cap));
+    KP_HIP_CHECK(ctx, hipMemcpyAsync(w->d_cig_hit_off.p, w->hit_off.data(), (n_asm + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->post));
+    const uint32_t *n_hits = w->d_hit_counts.p + n_asm;
+    kp_launch_cigar_locate(b->view, ctx->d_gene_len.p, w->d_tasks.p, w->d_results.p, w->d_task_drop.p, w->d_counts.p + n_asm, w->task_cap, w->d_joins.p,
+                           w->d_join_counts.p + 1, w->join_cap, w->d_hits.p, n_hits, w->hit_cap, w->d_cig_src.p, ctx->post);
+    kp_launch_cigar_count(b->view, ctx->genes, w->d_tasks.p, w->d_ends.p, w->task_cap, w->d_joins.p, w->join_cap, w->d_trace.p, n_hits, w->hit_cap,
+                          w->d_cig_hit_off.p, w->d_cig_src.p, w->d_cig_cnt.p, total, w->d_cig_off.p, ctx->post);
+    for (int attempt = 0;; ++attempt) {
+        kp_launch_cigar_emit(b->view, ctx->genes, w->d_tasks.p, w->d_ends.p, w->task_cap, w->d_joins.p, w->join_cap, w->d_trace.p, n_hits, w->hit_cap,
+                             w->d_cig_hit_off.p, w->d_cig_src.p, w->d_cig_off.p, w->d_cig_ops.p, (int64_t)w->cigar_cap, ctx->post);
+        KP_HIP_CHECK(ctx, hipGetLastError());
+        int64_t need = 0;
+        if (int frc = fetch_all(ctx, ctx->post, {{&need, w->d_cig_off.p + total, sizeof need}})) return frc;
+        w->cigar_total = need;
+        if (kp_caps_after_cigar(ctx->learnt, w->cigar_cap, (uint64_t)total, (uint64_t)need)) break;
+        if (attempt >= 1) return kp_fail(ctx, KP_EOVERFLOW, "CIGAR buffer overflowed repeatedly");
+        KP_HIP_CHECK(ctx, w->d_cig_ops.reserve(w->cigar_cap));
+    }
+    w->cigar_valid = true;
+    return KP_OK;
+}
+
+static const char *const NO_CIGARS = "this batch has no CIGARs (aligned without the cigar option, or its hit table was replaced)";
+
 int kp_batch_wait(kp_ctx *ctx, kp_batch *b) {
     if (!ctx || !b || b->ctx != ctx) return kp_fail(ctx, KP_EINVAL, "bad context/batch");
     KpWork *w = work_of(b);
@@ -232,6 +268,8 @@ int kp_batch_wait(kp_ctx *ctx, kp_batch *b) {
     int rc = finalise_hits_on_device(ctx, b, w);
     if (rc) return rc;
     w->stats[0] = n_anchor; w->stats[1] = n_task; w->stats[3] = w->hit_off[n_asm];
+    if (w->cigar_on)
+        if (int crc = emit_cigars(ctx, b, w)) return crc;
     w->finalised = true;
     return KP_OK;
 }
@@ -290,8 +328,34 @@ int kp_batch_set_hits(kp_ctx *ctx, kp_batch *b, const kp_hit *hits, const int64_
     if (n_asm)
         KP_HIP_CHECK(ctx, hipMemcpy(w->d_hit_counts.p + n_asm, w->h_hit_counts.data() + n_asm, n_asm * sizeof(uint32_t), hipMemcpyHostToDevice));
     w->stats[3] = w->hit_off[n_asm];
+    w->cigar_valid = false;  // (they described the table that has just been replaced)
     for (auto &r : w->runs)
         if (r) { r->split = false; r->scored = false; r->reduced = false; r->sums_valid = false; }
+    return KP_OK;
+}
+
+int kp_batch_cigar_offsets(kp_ctx *ctx, kp_batch *b, int64_t *cigar_off) {
+    if (!ctx || !b || b->ctx != ctx || !cigar_off) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    if (!w->cigar_valid) return kp_fail(ctx, KP_ESTATE, NO_CIGARS);
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    KP_HIP_CHECK(ctx, hipMemcpyAsync(cigar_off, w->d_cig_off.p, ((size_t)w->hit_off[(size_t)b->n_asm] + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->post));
+    KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->post));
+    return KP_OK;
+}
+
+int kp_batch_cigars(kp_ctx *ctx, kp_batch *b, uint32_t *ops, int64_t cap) {
+    if (!ctx || !b || b->ctx != ctx || (!ops && cap > 0)) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    if (!w->cigar_valid) return kp_fail(ctx, KP_ESTATE, NO_CIGARS);
+    if (cap < w->cigar_total) return kp_fail(ctx, KP_EINVAL, "CIGAR buffer too small");
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (w->cigar_total > 0) {
+        KP_HIP_CHECK(ctx, hipMemcpyAsync(ops, w->d_cig_ops.p, (size_t)w->cigar_total * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->post));
+        KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->post));
+    }
     return KP_OK;
 }
 

@@ -21,6 +21,9 @@ struct KpCapOptions {
     uint32_t group_cap = 1024, join_cap = 1024, occ_slots = 2;
     bool trace_set = false;            // trace_kb_per_asm was given (environment or kp_ctx_set_option): no floor under it
     uint32_t kept_cap = 256, piece_cap = 32, prot_cap = 32768;
+    // first guess for the CIGAR ops of a pass, per hit (kp_caps_cigar_size).  Not measured: most hits of a typing run are one
+    // M op and a hit with one indel has three, so four leaves room; a batch that needs more grows the buffer once
+    uint32_t cigar_ops_per_hit = 4;
 };
 
 // learnt buffer sizes of a context (0 = not yet sized: first use takes the option's value); they only grow
@@ -33,6 +36,7 @@ struct KpLearnt {
     uint64_t trace_units_per_asm = 0;  // trace buffer of a pass = n_asm * this many 16-byte units
     uint32_t group_cap = 0, join_cap = 0;  // group / join lists of a pass (entries; joins per band class)
     uint32_t occ_slots = 0;                // counting tables of the occurrence cut's quantile a pass may use (learnt like the list sizes)
+    uint32_t cigar_ops_per_hit = 0;        // CIGAR ops buffer of a pass = its hits * this many ops
 };
 
 // what the buffers of a work set's most recent pass were sized for
@@ -147,6 +151,27 @@ inline void kp_caps_grow_hits(KpLearnt &L, KpPassCaps &w, uint32_t max_hits, boo
     L.hit_cap = std::max(L.hit_cap, w.hit_cap);
 }
 
+// CIGAR ops (kp_cigar.hip; only with the `cigar` option): the buffer of a pass holds total_hits * ops-per-hit entries, from what
+// the context has learnt (first use: the option).  The emission counts every hit's ops before it writes them, so `need`
+// is exact however small the buffer was.
+inline uint64_t kp_caps_cigar_size(const KpCapOptions &opt, KpLearnt &L, uint64_t total_hits) {
+    if (L.cigar_ops_per_hit == 0) L.cigar_ops_per_hit = std::max<uint32_t>(opt.cigar_ops_per_hit, 1u);
+    return std::max<uint64_t>(total_hits, 1) * L.cigar_ops_per_hit;
+}
+// true: the ops fitted (what came close makes room for later passes); false: `cap` has grown -- write the ops again, nothing
+// else: the alignment pass and its direction bits stand
+inline bool kp_caps_after_cigar(KpLearnt &L, uint64_t &cap, uint64_t total_hits, uint64_t need) {
+    const uint64_t hits = std::max<uint64_t>(total_hits, 1);
+    auto per_hit = [&](uint64_t ops) { return (uint32_t)std::min<uint64_t>((ops + hits - 1) / hits, 0xFFFFFFFFu); };
+    if (need <= cap) {
+        if (need + need / 8 > cap) L.cigar_ops_per_hit = std::max(L.cigar_ops_per_hit, per_hit(need + need / 4));
+        return true;
+    }
+    cap = need + need / 4;  // later batches differ a little
+    L.cigar_ops_per_hit = std::max(L.cigar_ops_per_hit, per_hit(cap));
+    return false;
+}
+
 // overflow flags of a reduction (KpAsmSummary::overflow: 1 kept hits, 2 pieces, 8 proteins); false: `err` says what cannot grow
 inline bool kp_caps_grow_run(KpRunCaps &c, int flags, std::string &err) {
     if (flags & 1) {
@@ -170,6 +195,7 @@ inline bool kp_caps_set_option(KpCapOptions &o, KpLearnt &L, std::vector<KpRunCa
     else if (n == "group_cap") { o.group_cap = v; L.group_cap = 0; }
     else if (n == "join_cap") { o.join_cap = v; L.join_cap = 0; }
     else if (n == "occ_slots") { o.occ_slots = (uint32_t)std::max<int64_t>(std::min<int64_t>(value, KP_OCC_SLOTS_MAX), 1); L.occ_slots = 0; }
+    else if (n == "cigar_ops_per_hit") { o.cigar_ops_per_hit = v; L.cigar_ops_per_hit = 0; }
     else if (n == "kept_cap") { o.kept_cap = v; for (auto &c : runs) c.kept_cap = 0; }
     else if (n == "piece_cap") { o.piece_cap = v; for (auto &c : runs) c.piece_cap = 0; }
     else if (n == "prot_cap") { o.prot_cap = v; for (auto &c : runs) c.prot_cap = 0; }

@@ -64,6 +64,7 @@ struct KpOptions : KpCapOptions {
     uint32_t upload_piece_mb = 4096;  // H2D copies of a batch's words are enqueued in pieces of this size (batch_make)
     int readback_copy_engine = 0;   // results read back with hipMemcpyAsync instead of the read-back kernel (see Fetch)
     int spin_wait = 0;              // host waits spin on the stream (the runtime's default) instead of blocking on an interrupt
+    int cigar = 0;                  // CIGARs of the finished hits (kp_cigar.hip): off unless asked for; applies from the next kp_batch_align
     bool join_stats = false;        // KAPTIVE_AMD_JOIN_STATS: kp_batch_wait reports the pass's group / join / mid_occ counts on stderr
 };
 
@@ -121,6 +122,14 @@ struct KpWork : KpPassCaps {
     DevBuf<uint32_t> d_hit_counts;  // [n_asm] raw, then [n_asm] final
     DevBuf<uint64_t> d_keys;        // 3 per hit row
     DevBuf<unsigned long long> d_cells;
+    // CIGARs of the finished hits (kp_cigar.hip), only where the pass was enqueued with the `cigar` option: nothing below is
+    // allocated otherwise.  They are results like the hit tables: theirs until the work set's next pass or kp_batch_set_hits.
+    bool cigar_on = false, cigar_valid = false;
+    uint64_t cigar_cap = 0;          // ops d_cig_ops was sized for
+    int64_t cigar_total = 0;         // ops of all hits
+    DevBuf<unsigned long long> d_cig_src;  // per row of the hit tables: the source of the hit (kp_cigar.hip: src_key)
+    DevBuf<uint32_t> d_cig_cnt, d_cig_ops;
+    DevBuf<int64_t> d_cig_off, d_cig_hit_off;  // [total_hits + 1] first op of every hit; [n_asm + 1] the host's hit_off
     // reduction: one run per typing group, created on first use
     std::vector<std::unique_ptr<KpTypingRun>> runs;
     // results

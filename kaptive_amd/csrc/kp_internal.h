@@ -270,6 +270,18 @@ void kp_launch_join_fill(const KpBatchView &b, const KpGenes &genes, KpJoin *joi
                          void *trace, unsigned long long *trace_top, uint64_t trace_cap_units, hipStream_t stream);
 void kp_launch_join_trace(const KpBatchView &b, const KpGenes &genes, KpJoin *joins, const uint32_t *join_count, uint32_t join_cap,
                           uint32_t task_cap, const void *trace, uint8_t *task_drop, hipStream_t stream);
+// kp_cigar.hip (only with the `cigar` option; after kp_launch_hit_finalise, while `trace` still holds the pass): which band task or
+// joined path every finished hit came from (src: one key per row of the hit tables), the ops of every hit counted (cnt, rows as
+// kp_batch_hits lists them: hit_off[a] + i) and scanned (off[total_hits + 1]), and the ops written -- stores beyond ops_cap are dropped.
+void kp_launch_cigar_locate(const KpBatchView &b, const int32_t *gene_len, const KpTask *tasks, const KpSwResult *results, const uint8_t *task_drop,
+                            const uint32_t *task_count, uint32_t task_cap, const KpJoin *joins, const uint32_t *join_count, uint32_t join_cap,
+                            const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap, unsigned long long *src, hipStream_t stream);
+void kp_launch_cigar_count(const KpBatchView &b, const KpGenes &genes, const KpTask *tasks, const KpSwEnd *ends, uint32_t task_cap, const KpJoin *joins,
+                           uint32_t join_cap, const void *trace, const uint32_t *n_hits, uint32_t hit_cap, const int64_t *hit_off,
+                           const unsigned long long *src, uint32_t *cnt, int64_t total_hits, int64_t *off, hipStream_t stream);
+void kp_launch_cigar_emit(const KpBatchView &b, const KpGenes &genes, const KpTask *tasks, const KpSwEnd *ends, uint32_t task_cap, const KpJoin *joins,
+                          uint32_t join_cap, const void *trace, const uint32_t *n_hits, uint32_t hit_cap, const int64_t *hit_off,
+                          const unsigned long long *src, const int64_t *off, uint32_t *ops, int64_t ops_cap, hipStream_t stream);
 // kp_prot.hip
 // kp_reduce.hip: assembly a's hits with gene in [gene_lo, gene_hi) (one run: hits are sorted by gene) -> out rows, gene
 // indices relative to gene_lo; out_n[a] = how many

@@ -22,6 +22,7 @@
 // All of it runs on a stream of its own beside the band tasks' fill and traceback (kp_align.hip).  Plain 32-bit arithmetic:
 // some twenty joins per thousand assemblies on the headline workload, 55 per assembly on `bench.py --mix joins`.
 #include "kp_internal.h"
+#include "kp_walk.h"
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -242,7 +243,6 @@ __global__ __launch_bounds__(64) void kp_join_chain_kernel(const uint64_t *__res
 }
 
 // ---- joined fill ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned nib4(unsigned word, int i) { return (word >> (4 * i)) & 15u; }
 
 // The pieces of a join are filled one after the other by the SAME lanes of one wave: what a piece exports is read by its own
 // wave only, so the exports' atomics, the loads that import them and the fences between pieces need the scope of a work group
@@ -255,8 +255,7 @@ __device__ __forceinline__ void join_export(unsigned long long *p, unsigned long
     (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-// Direction byte of a cell: bits 0-2 the source of H (XT_*), bit 3 "E was extended", bit 4 "F was extended".
-enum { XT_DIAG = 0, XT_E = 1, XT_F = 2, XT_RESTART = 3, XT_X1 = 4, XT_X2 = 5 };
+// Direction byte of a cell: bits 0-2 the source of H (XT_*, kp_walk.h), bit 3 "E was extended", bit 4 "F was extended".
 
 template <int P>
 __device__ __forceinline__ void join_fill_class(const KpBatchView &b, const KpGenes &genes, KpJoin *__restrict__ joins, uint32_t n_joins,
@@ -522,18 +521,19 @@ __global__ __launch_bounds__(64) void kp_join_trace_kernel(KpBatchView b, KpGene
     const int cls = blockIdx.y;
     uint32_t n = join_count[cls];
     if (n > join_cap) n = join_cap;
-    const int P = 4 << cls, W = 4 * P;
+    const int P = 4 << cls;
     if (prio) __builtin_amdgcn_s_setprio(3);  // (as the joined fill: few lanes, long dependent walks)
     for (uint32_t ji = blockIdx.x * blockDim.x + threadIdx.x; ji < n; ji += gridDim.x * blockDim.x) {
         KpJoin *J = joins + (size_t)cls * join_cap + ji;
         const int m = J->n_pieces, gs = J->gs, gene = gs >> 1, asm_id = J->asm_id;
-        const int qlen = genes.len[gene];
-        const uint32_t *qnib = genes.nib + genes.word_off[(gs & 1) ? genes.n_genes + gene : gene];
-        const uint32_t *asm_words = b.words + b.asm_word_off[asm_id];
         const int c_abs = b.asm_first_ctg[asm_id] + J->contig;
-        const int cstart = b.ctg_start[c_abs], cend = cstart + b.ctg_len[c_abs];
-        const int r0n = b.asm_first_nrun[asm_id], n_runs = b.asm_first_nrun[asm_id + 1] - r0n;
-        const int32_t *runs = b.n_runs + 2 * (size_t)r0n;
+        const int r0n = b.asm_first_nrun[asm_id];
+        KpJoinSeqs seqs;
+        seqs.qnib = genes.nib + genes.word_off[(gs & 1) ? genes.n_genes + gene : gene];
+        seqs.asm_words = b.words + b.asm_word_off[asm_id];
+        seqs.runs = b.n_runs + 2 * (size_t)r0n; seqs.n_runs = b.asm_first_nrun[asm_id + 1] - r0n;
+        seqs.qlen = genes.len[gene];
+        seqs.cstart = b.ctg_start[c_abs]; seqs.cend = seqs.cstart + b.ctg_len[c_abs];
         bool complete = true;
         for (int k = 0; k < m; ++k) complete = complete && J->trace_off[k] != 0xFFFFFFFFu;
         for (int k = 0; k < m; ++k) { J->state[k] = 0; J->visited[k] = 0; }
@@ -548,67 +548,12 @@ __global__ __launch_bounds__(64) void kp_join_trace_kernel(KpBatchView b, KpGene
             if (k < 0) break;
             if (J->end_r[k] < 0 || J->end_s[k] < KP_MIN_DP_SCORE) { alone_k = k; break; }
             if (k == 0) { J->visited[0] = 1; alone_k = 0; break; }  // (the first piece has no gap to cross: its path need not be walked to know that)
-            int pk = k, r = J->end_r[k], bi = J->end_b[k], state = 0, matches = 0, cols = 0, gap = 0, credit = 0;
-            int sr = r, sb = bi, spk = k, suf = 0, sufmax = 0, gsum = 0, visited = 1 << k, bonus = 0;
-            bool rejected = false;
-            int lo = J->lo[pk], q0 = 0, r_hi = 0;
-            kp_piece_rows(lo, W, cstart, cend, qlen, J->r0[pk], J->r1[pk], &q0, &r_hi);
-            const uint32_t *tr = reinterpret_cast<const uint32_t *>(trace + J->trace_off[pk]);
-            for (;;) {
-                const int t = r + lo + bi;
-                if (state == 0 && (r < q0 || r >= r_hi || bi < 0 || bi >= W || t < cstart || t >= cend)) break;
-                const uint32_t byte = (tr[(size_t)(r - q0 + (bi >> 2)) * P + (bi >> 2)] >> (8 * (bi & 3))) & 255u;
-                if (state == 0) {
-                    const uint32_t tb = byte & 7u;
-                    if (tb == XT_RESTART) break;
-                    // the drop test: at every cross gap, and at every cell once a gap has been crossed (cross-gap costs left out)
-                    if (suf + gsum > sufmax) sufmax = suf + gsum;
-                    else if ((tb >= XT_X1 || visited != (1 << k)) && sufmax - (suf + gsum) > KP_JOIN_DROP) { rejected = true; break; }
-                    if (tb == XT_DIAG) {
-                        sr = r; sb = bi; spk = pk; ++cols;
-                        const uint32_t qc = nib4(qnib[r >> 3], r & 7);
-                        uint32_t tc = (asm_words[t >> 4] >> (2 * (t & 15))) & 3u;
-                        if (n_runs > 0) {
-                            int a = 0, z = n_runs;
-                            while (a < z) {
-                                const int mid = (a + z) >> 1;
-                                if (runs[2 * mid + 1] <= t) a = mid + 1; else z = mid;
-                            }
-                            if (a < n_runs && runs[2 * a] <= t) tc = 4u;
-                        }
-                        if (qc < 4u && qc == tc) ++matches;
-                        suf += (qc > 3u || tc > 3u) ? KP_SC_N : (qc == tc ? KP_SC_MATCH : KP_SC_MISMATCH);
-                        --r;
-                    } else if (tb == XT_E || tb == XT_F) {
-                        state = (int)tb;
-                    } else {  // a cross gap: on to the cell of piece pk - 1 it came from
-                        const int lo_prev = J->lo[pk - 1];
-                        const bool horizontal = lo > lo_prev;
-                        const unsigned long long *exp = reinterpret_cast<const unsigned long long *>(trace + J->export_off[pk - 1]);
-                        const int xi = horizontal ? r : t - lo_prev;
-                        const unsigned long long key = exp[2 * xi + (tb == XT_X1 ? 0 : 1)];
-                        const int pos = (int)(0xFFFFFFFFu - (uint32_t)key);  // t' - lo_prev (horizontal) or r'
-                        const int ngap = horizontal ? (t - lo_prev) - pos : r - pos;
-                        cols += ngap;
-                        const int cost = tb == XT_X1 ? KP_GAP_OPEN + KP_GAP_EXT * ngap : KP_GAP_OPEN2 + KP_GAP_EXT2 * ngap;
-                        suf -= cost; gsum += cost;
-                        const int lg = KP_GAP_OPEN + kp_log2x2((uint32_t)ngap);
-                        if (cost > lg) bonus += cost - lg;
-                        if (horizontal) bi = pos - r;               // same row, column lo_prev + pos
-                        else { bi = t - pos - lo_prev; r = pos; }   // same column, row pos
-                        --pk; visited |= 1 << pk;
-                        lo = lo_prev;
-                        kp_piece_rows(lo, W, cstart, cend, qlen, J->r0[pk], J->r1[pk], &q0, &r_hi);
-                        tr = reinterpret_cast<const uint32_t *>(trace + J->trace_off[pk]);
-                    }
-                } else if (state == XT_E) {
-                    ++cols; ++gap; --bi; suf -= KP_GAP_EXT;
-                    if (!(byte & 8u)) { state = 0; suf -= KP_GAP_OPEN; credit += max(gap - KP_GAP_LONG, 0); gap = 0; }
-                } else {
-                    ++cols; ++gap; --r; ++bi; suf -= KP_GAP_EXT;
-                    if (!(byte & 16u)) { state = 0; suf -= KP_GAP_OPEN; credit += max(gap - KP_GAP_LONG, 0); gap = 0; }
-                }
-            }
+            KpJoinPath path;
+            KpNoVisit nobody;
+            kp_join_walk(J, k, P, seqs, trace, path, nobody);  // (kp_walk.h: shared with the CIGAR kernels)
+            const bool rejected = path.rejected;
+            const int visited = path.visited, sr = path.sr, sb = path.sb, spk = path.spk, matches = path.matches, cols = path.cols,
+                      credit = path.credit, bonus = path.bonus;
             J->visited[k] = visited;
             if (rejected) { J->state[k] = 2; any_rejected = true; settled |= 1 << k; continue; }
             if (visited == (1 << k)) { alone_k = k; break; }  // crosses no gap: the band task of the piece's cluster covers it

@@ -151,3 +151,58 @@ extern "C" int64_t kp_format_rows(const kp_row_tables *t, int32_t n_asm, const k
     }
     return o.n;
 }
+
+// ---- PAF lines of a hit table (kp_spec.h, CIGAR) ------------------------------------------------------------------------------
+// One line per hit, in the table's order: what minimap2 writes for a mapping with -c (the reference keeps the same columns and
+// the CIGAR in its Alignments table, src/kaptive/core/alignment.py:392-474, 872).  A loop over the hits in Python costs a
+// thousand times the typing of the batch it sits beside.
+namespace {
+
+inline void put_u(Out &o, unsigned long long v) {
+    char buf[24];
+    int at = 24;
+    do { buf[--at] = (char)('0' + v % 10); v /= 10; } while (v);
+    o.put(buf + at, 24 - at);
+}
+inline void put_i(Out &o, long long v) {
+    if (v < 0) { o.put('-'); put_u(o, (unsigned long long)(-v)); }
+    else put_u(o, (unsigned long long)v);
+}
+
+}  // namespace
+
+extern "C" int64_t kp_format_paf(const kp_paf_tables *t, int32_t n_asm, const kp_hit *hits, const int64_t *hit_off, const uint32_t *ops,
+                                 const int64_t *cigar_off, char *out, int64_t cap) {
+    if (!t || n_asm < 0 || !hit_off || !cigar_off || cap < 0 || (cap > 0 && !out)) return KP_EINVAL;
+    if (n_asm > 0 && (!t->asm_first_ctg || hit_off[n_asm] < hit_off[0] || (hit_off[n_asm] > 0 && !hits))) return KP_EINVAL;
+    Out o{out, cap};
+    for (int a = 0; a < n_asm; ++a) {
+        const int64_t c0 = t->asm_first_ctg[a], nc = t->asm_first_ctg[a + 1] - c0;
+        for (int64_t i = hit_off[a]; i < hit_off[a + 1]; ++i) {
+            const kp_hit &h = hits[i];
+            if (h.gene < 0 || h.gene >= t->n_genes || h.contig < 0 || h.contig >= nc) return KP_EINVAL;
+            const int64_t c = c0 + h.contig;
+            if (cigar_off[i + 1] < cigar_off[i] || (cigar_off[i + 1] > cigar_off[i] && !ops)) return KP_EINVAL;
+            o.put(t->gene_names + t->gene_name_off[h.gene], t->gene_name_off[h.gene + 1] - t->gene_name_off[h.gene]); o.put('\t');
+            put_i(o, t->gene_len[h.gene]); o.put('\t');
+            put_i(o, h.q_start); o.put('\t');
+            put_i(o, h.q_end); o.put('\t');
+            o.put(h.strand < 0 ? '-' : '+'); o.put('\t');
+            o.put(t->ctg_names + t->ctg_name_off[c], t->ctg_name_off[c + 1] - t->ctg_name_off[c]); o.put('\t');
+            put_i(o, t->ctg_len[c]); o.put('\t');
+            put_i(o, h.t_start); o.put('\t');
+            put_i(o, h.t_end); o.put('\t');
+            put_i(o, h.matches); o.put('\t');
+            put_i(o, h.block_len); o.put('\t');
+            put_u(o, h.mapq); o.lit("\tAS:i:");
+            put_i(o, h.score); o.lit("\tNM:i:");
+            put_i(o, (long long)h.block_len - h.matches); o.lit("\tcg:Z:");
+            for (int64_t z = cigar_off[i]; z < cigar_off[i + 1]; ++z) {
+                put_u(o, ops[z] >> 4);
+                o.put("MIDNSHP=XB??????"[ops[z] & 15u]);
+            }
+            o.put('\n');
+        }
+    }
+    return o.n;
+}

@@ -56,13 +56,11 @@
 //   * direction bits, four steps per 16 bits, eight steps per 32-bit word and cell: the two tasks' halves are
 //     separated with v_perm_b32 every eight steps and each task's 16 bytes go to its own trace block.
 #include "kp_internal.h"
+#include "kp_walk.h"
 
 namespace {
 
 constexpr int CH = 64;  // steps staged per chunk (multiple of 8)
-#ifndef KP_TRACE_GROUP
-#define KP_TRACE_GROUP 2
-#endif
 constexpr int TG = KP_TRACE_GROUP;  // consecutive 8-step trace pieces of a lane that are contiguous in memory (2 or 4)
 constexpr int OE = KP_GAP_OPEN + KP_GAP_EXT;
 constexpr int EX = KP_GAP_EXT;
@@ -792,26 +790,9 @@ __global__ __launch_bounds__(64) void kp_sw_long_kernel(KpBatchView b, KpGenes g
 }
 
 // ---- traceback: one lane per task -------------------------------------------------------------------------------------------
-// Cell (row r, band index bi) sits on target position lo + r + bi; a diagonal step keeps bi, a step to the left (E, gap
-// in the query) lowers it, a step up (F, gap in the target) raises it.  The nibble of (r, bi) is in lane stream bi / 4,
-// step r + bi / 4: piece j = step / 8 (at [j / TG][lane][j % TG] of the task's block), word bi % 4 (the cell); bit layout of a word: below.
-//
-// A path runs along a diagonal most of the time: it stays in one lane stream and walks it backwards.  The walk therefore
-// works on whole 16-byte pieces (8 steps x 4 cells) held in registers: when it stands on the last step of a piece and
-// all eight nibbles of its cell say "diagonal, not the start", it takes the eight steps at once; everything else (gaps,
-// the first and last steps of a path, tasks with an N, whose matches are counted base by base) goes step by step from
-// the same registers.  Pieces are fetched TG at a time (contiguous bytes) and the group
-// after the current one is requested a whole group ahead, so the dependent fetches of a path overlap with other
-// waves' work; the direction bits are read about once (a quarter of what the fill wrote).
-// Matches: without an N in the gene or the window every diagonal step scores +2 or -4, so
-// score = 6 * matches - 4 * diagonal_steps - gap_costs gives the matches in closed form; tasks that saw an N (flagged by
-// the fill kernel) compare the bases of every diagonal step instead.
+// The walk itself -- how a path is followed through the direction bits, piece by piece -- is kp_band_walk (kp_walk.h), shared
+// with the CIGAR kernels; this kernel reduces the path to the fields of the task's result.
 constexpr int TB_THREADS = 256;
-
-__device__ __forceinline__ uint32_t piece_word(const uint4 &v, int k) {  // cell k's word of a piece, in registers' terms
-    const uint32_t lo = (k & 1) ? v.y : v.x, hi = (k & 1) ? v.w : v.z;
-    return (k & 2) ? hi : lo;
-}
 
 __global__ __launch_bounds__(TB_THREADS) void kp_sw_traceback_kernel(KpBatchView b, KpGenes genes, const KpTask *__restrict__ tasks,
                                                               const uint32_t *__restrict__ task_count, uint32_t task_cap,
@@ -833,7 +814,7 @@ __global__ __launch_bounds__(TB_THREADS) void kp_sw_traceback_kernel(KpBatchView
         if (have) e = ends[at];
         KpSwResult out;
         out.score = e.score; out.q_start = out.q_end = out.t_start = out.t_end = out.matches = out.block_len = 0;
-        bool walking = have && e.score >= KP_MIN_DP_SCORE;  // the others are dropped by the hit filter anyway
+        const bool walking = have && e.score >= KP_MIN_DP_SCORE;  // the others are dropped by the hit filter anyway
         KpTask tk;
         tk.asm_id = 0; tk.gs = 0; tk.lo = 0;
         if (walking) tk = tasks[at];
@@ -854,98 +835,16 @@ __global__ __launch_bounds__(TB_THREADS) void kp_sw_traceback_kernel(KpBatchView
             kp_task_rows(tk.lo, 4 * P, cstart, cstart + b.ctg_len[c_abs], qlen, &q0, &r_hi);
         }
         const uint4 *tw = reinterpret_cast<const uint4 *>(trace) + e.trace_off;  // piece j of lane l at [(j / TG) * TG * P + TG * l + j % TG]
-        int r = e.er, bi = eb, state = 0, cols = 0, matches = 0, diag = 0, gap_cost = 0, gap = 0, credit = 0;
-        int sr = r, sb = bi;
-        // curq = the TG pieces (contiguous bytes) of the lane stream the walk stands in, nxtq = the TG before them
-        // (requested a whole group ahead).  A group is fetched with loads in a row: one trip to memory --
-        // with a load per piece the line had left the L2 by the time the walk came back for the next one (75 % misses,
-        // one random 64-byte fetch per piece: the kernel ran at the rate HBM serves those, tools/microbench/l2_gather.hip)
-        uint4 curq[TG], nxtq[TG];
-#pragma unroll
-        for (int i = 0; i < TG; ++i) curq[i] = nxtq[i] = make_uint4(0, 0, 0, 0);
-        int cur_tag = -1, nxt_tag = -1;  // (stream << 20) | group index
-        while (__any(walking)) {
-            if (!walking) continue;
-            const int l = bi >> 2, k = bi & 3, step = r - q0 + l;
-            const int pc = step >> 3, grp = pc / TG, tag = (l << 20) | grp;
-            if (tag != cur_tag) {
-                const uint4 *stream = tw + TG * l;
-                if (tag == nxt_tag) {
-#pragma unroll
-                    for (int i = 0; i < TG; ++i) curq[i] = nxtq[i];
-                } else {
-#pragma unroll
-                    for (int i = 0; i < TG; ++i) curq[i] = stream[(size_t)grp * (TG * P) + i];
-                }
-                cur_tag = tag;
-                if (grp > 0) {
-#pragma unroll
-                    for (int i = 0; i < TG; ++i) nxtq[i] = stream[(size_t)(grp - 1) * (TG * P) + i];
-                    nxt_tag = tag - 1;
-                }
-            }
-            uint4 cur = (pc & 1) ? curq[1] : curq[0];
-            if (TG == 4) {
-                const uint4 hi2 = (pc & 1) ? curq[TG - 1] : curq[TG - 2];
-                cur = (pc & 2) ? hi2 : cur;
-            }
-            const uint32_t word = piece_word(cur, k);
-            if (state == 0 && !has_n && (step & 7) == 7 && (word & 0xAAAAAAAAu) == 0u) {  // eight plain diagonal steps (D and L are stored inverted)
-                // ... and the eight before them when they are the same cell's other piece of the group in hand (a diagonal step
-                // stays on its lane and cell): a wave goes round this loop as often as its slowest lane, and most paths are plain
-                int n = 8;
-#ifndef KP_TB_NO16
-                if (TG == 2 && (pc & 1) && (piece_word(curq[0], k) & 0xAAAAAAAAu) == 0u) n = 16;
-#endif
-                cols += n; diag += n; r -= n;
-                continue;
-            }
-            // a cell's word: steps 0-3 in the low half, 4-7 in the high half; per half a byte of [L, F opened] pairs below
-            // a byte of [D, E opened] pairs, step j's pair at bits 2j+1, 2j
-            const uint32_t half = word >> (16 * ((step >> 2) & 1)), sh = 2 * (step & 3);
-            const uint32_t de = ((half >> (8 + sh)) & 3u) ^ 2u, lf = ((half >> sh) & 3u) ^ 2u;  // (D, L: stored inverted)
-            const uint32_t nib = ((de & 2u) << 2) | ((lf & 2u) << 1) | ((de & 1u) << 1) | (lf & 1u);  // [D][L][EO][FO]
-            // -> source 0 = diagonal, 1 = diagonal and the path starts here, 2 = E, 3 = F
-            const uint32_t src = (nib & 8u) ? ((nib & 4u) ? 0u : 1u) : ((nib & 4u) ? 2u : 3u);
-            if (state == 0) {
-                if (src <= 1u) {  // diagonal: one column
-                    ++cols; ++diag;
-                    if (has_n) {  // a match when both bases are the same unambiguous base
-                        const int t = tk.lo + r + bi;
-                        const uint32_t qc = nibble(qnib[r >> 3], r & 7);
-                        uint32_t tc = (asm_words[t >> 4] >> (2 * (t & 15))) & 3u;
-                        if (n_runs > 0) {
-                            int lo = 0, hi = n_runs;
-                            while (lo < hi) {
-                                const int mid = (lo + hi) >> 1;
-                                if (runs[2 * mid + 1] <= t) lo = mid + 1; else hi = mid;
-                            }
-                            if (lo < n_runs && runs[2 * lo] <= t) tc = 4u;
-                        }
-                        matches += (qc == tc && qc < 4u) ? 1 : 0;  // N against N scores KP_SC_N: not a match
-                    }
-                    if (src == 1u) { sr = r; sb = bi; walking = false; }
-                    --r;
-                } else {
-                    state = (int)src - 1;  // 1 = E, 2 = F: the gap's columns are counted in that state
-                }
-            } else if (state == 1) {  // E: gap in the query; this cell's E came from H (opened) or E (extended) of the left cell
-                ++cols; ++gap; gap_cost += EX;
-                --bi;
-                if (nib & 2u) { state = 0; gap_cost += KP_GAP_OPEN; credit += max(gap - KP_GAP_LONG, 0); gap = 0; }
-            } else {  // F: gap in the target
-                ++cols; ++gap; gap_cost += EX;
-                --r; ++bi;
-                if (nib & 1u) { state = 0; gap_cost += KP_GAP_OPEN; credit += max(gap - KP_GAP_LONG, 0); gap = 0; }
-            }
-        }
+        KpBandPath path;
+        KpNoVisit nobody;
+        kp_band_walk(walking, tk.lo, P, q0, e.er, eb, has_n, tw, qnib, asm_words, runs, n_runs, path, nobody);
         if (!have) continue;
         if (e.score < KP_MIN_DP_SCORE) { results[at] = out; continue; }
-        if (!has_n) matches = (e.score + 4 * diag + gap_cost) / 6;
-        out.score = e.score + credit;  // the path under the two-piece gap cost (kp_spec.h): long gaps get their credit
-        out.q_start = sr; out.q_end = e.er + 1;
-        out.t_start = sr + tk.lo + sb; out.t_end = e.er + tk.lo + eb + 1;
-        out.matches = matches; out.block_len = cols;
+        const int matches = has_n ? path.matches : (e.score + 4 * path.diag + path.gap_cost) / 6;
+        out.score = e.score + path.credit;  // the path under the two-piece gap cost (kp_spec.h): long gaps get their credit
+        out.q_start = path.sr; out.q_end = e.er + 1;
+        out.t_start = path.sr + tk.lo + path.sb; out.t_end = e.er + tk.lo + eb + 1;
+        out.matches = matches; out.block_len = path.cols;
         results[at] = out;
     }
 }

@@ -1,0 +1,238 @@
+// kp_walk.h -- the two walks back along an alignment path, over the direction bits the fill kernels left: the band tasks'
+// (kp_sw.hip: kp_sw_kernel / kp_sw_long_kernel) and the joins' (kp_join.hip: kp_join_fill_kernel).  Each is written once and
+// takes a VISITOR that is told every run of columns the path makes, in walking order (from the path's end to its start):
+// the tracebacks that reduce a path to the fields of its hit pass KpNoVisit, the CIGAR kernels (kp_cigar.hip) one that
+// counts or writes run-length ops.  Device code only.
+#pragma once
+
+#include "kp_internal.h"
+
+#ifndef KP_TRACE_GROUP
+#define KP_TRACE_GROUP 2
+#endif
+
+// Kinds of column, numbered as the ops of a CIGAR (kp_spec.h, CIGAR): a diagonal step, a step in state F (gap in the target,
+// moves along the query) and a step in state E (gap in the query, moves along the target).
+enum { KP_COL_M = 0, KP_COL_I = 1, KP_COL_D = 2 };
+
+struct KpNoVisit {
+    __device__ __forceinline__ void run(int, int) {}
+};
+
+__device__ __forceinline__ unsigned kp_nib(unsigned word, int i) { return (word >> (4 * i)) & 15u; }
+__device__ __forceinline__ uint32_t kp_piece_word(const uint4 &v, int k) {  // cell k's word of a piece, in registers' terms
+    const uint32_t lo = (k & 1) ? v.y : v.x, hi = (k & 1) ? v.w : v.z;
+    return (k & 2) ? hi : lo;
+}
+
+// ---- band tasks: one lane per task, whole waves together ---------------------------------------------------------------------
+// Cell (row r, band index bi) sits on target position lo + r + bi; a diagonal step keeps bi, a step to the left (E, gap
+// in the query) lowers it, a step up (F, gap in the target) raises it.  The nibble of (r, bi) is in lane stream bi / 4,
+// step r + bi / 4: piece j = step / 8 (at [j / TG][lane][j % TG] of the task's block), word bi % 4 (the cell); bit layout of a word: below.
+//
+// A path runs along a diagonal most of the time: it stays in one lane stream and walks it backwards.  The walk therefore
+// works on whole 16-byte pieces (8 steps x 4 cells) held in registers: when it stands on the last step of a piece and
+// all eight nibbles of its cell say "diagonal, not the start", it takes the eight steps at once; everything else (gaps,
+// the first and last steps of a path, tasks with an N, whose matches are counted base by base) goes step by step from
+// the same registers.  Pieces are fetched TG at a time (contiguous bytes) and the group
+// after the current one is requested a whole group ahead, so the dependent fetches of a path overlap with other
+// waves' work; the direction bits are read about once (a quarter of what the fill wrote).
+// Matches: without an N in the gene or the window every diagonal step scores +2 or -4, so
+// score = 6 * matches - 4 * diagonal_steps - gap_costs gives the matches in closed form; tasks that saw an N (flagged by
+// the fill kernel) compare the bases of every diagonal step instead.
+struct KpBandPath {
+    int sr, sb;  // row and band index of the path's first cell
+    int cols, matches /* counted base by base: has_n only */, diag, gap_cost, credit;
+};
+
+// Every lane of the wave calls it (walking = false: nothing to walk).  P = lanes of the task's band class, q0 = first row
+// the fill computed for the task (kp_task_rows), (er, eb) = its best cell, tw = the task's trace block.
+template <class V>
+__device__ __forceinline__ void kp_band_walk(bool walking, int lo, int P, int q0, int er, int eb, bool has_n, const uint4 *tw,
+                                             const uint32_t *qnib, const uint32_t *asm_words, const int32_t *runs, int n_runs,
+                                             KpBandPath &out, V &v) {
+    constexpr int TG = KP_TRACE_GROUP;
+    constexpr int EX = KP_GAP_EXT;
+    int r = er, bi = eb, state = 0, cols = 0, matches = 0, diag = 0, gap_cost = 0, gap = 0, credit = 0;
+    int sr = r, sb = bi;
+    // curq = the TG pieces (contiguous bytes) of the lane stream the walk stands in, nxtq = the TG before them
+    // (requested a whole group ahead).  A group is fetched with loads in a row: one trip to memory --
+    // with a load per piece the line had left the L2 by the time the walk came back for the next one (75 % misses,
+    // one random 64-byte fetch per piece: the kernel ran at the rate HBM serves those, tools/microbench/l2_gather.hip)
+    uint4 curq[TG], nxtq[TG];
+#pragma unroll
+    for (int i = 0; i < TG; ++i) curq[i] = nxtq[i] = make_uint4(0, 0, 0, 0);
+    int cur_tag = -1, nxt_tag = -1;  // (stream << 20) | group index
+    while (__any(walking)) {
+        if (!walking) continue;
+        const int l = bi >> 2, k = bi & 3, step = r - q0 + l;
+        const int pc = step >> 3, grp = pc / TG, tag = (l << 20) | grp;
+        if (tag != cur_tag) {
+            const uint4 *stream = tw + TG * l;
+            if (tag == nxt_tag) {
+#pragma unroll
+                for (int i = 0; i < TG; ++i) curq[i] = nxtq[i];
+            } else {
+#pragma unroll
+                for (int i = 0; i < TG; ++i) curq[i] = stream[(size_t)grp * (TG * P) + i];
+            }
+            cur_tag = tag;
+            if (grp > 0) {
+#pragma unroll
+                for (int i = 0; i < TG; ++i) nxtq[i] = stream[(size_t)(grp - 1) * (TG * P) + i];
+                nxt_tag = tag - 1;
+            }
+        }
+        uint4 cur = (pc & 1) ? curq[1] : curq[0];
+        if (TG == 4) {
+            const uint4 hi2 = (pc & 1) ? curq[TG - 1] : curq[TG - 2];
+            cur = (pc & 2) ? hi2 : cur;
+        }
+        const uint32_t word = kp_piece_word(cur, k);
+        if (state == 0 && !has_n && (step & 7) == 7 && (word & 0xAAAAAAAAu) == 0u) {  // eight plain diagonal steps (D and L are stored inverted)
+            // ... and the eight before them when they are the same cell's other piece of the group in hand (a diagonal step
+            // stays on its lane and cell): a wave goes round this loop as often as its slowest lane, and most paths are plain
+            int n = 8;
+#ifndef KP_TB_NO16
+            if (TG == 2 && (pc & 1) && (kp_piece_word(curq[0], k) & 0xAAAAAAAAu) == 0u) n = 16;
+#endif
+            cols += n; diag += n; r -= n;
+            v.run(KP_COL_M, n);
+            continue;
+        }
+        // a cell's word: steps 0-3 in the low half, 4-7 in the high half; per half a byte of [L, F opened] pairs below
+        // a byte of [D, E opened] pairs, step j's pair at bits 2j+1, 2j
+        const uint32_t half = word >> (16 * ((step >> 2) & 1)), sh = 2 * (step & 3);
+        const uint32_t de = ((half >> (8 + sh)) & 3u) ^ 2u, lf = ((half >> sh) & 3u) ^ 2u;  // (D, L: stored inverted)
+        const uint32_t nib = ((de & 2u) << 2) | ((lf & 2u) << 1) | ((de & 1u) << 1) | (lf & 1u);  // [D][L][EO][FO]
+        // -> source 0 = diagonal, 1 = diagonal and the path starts here, 2 = E, 3 = F
+        const uint32_t src = (nib & 8u) ? ((nib & 4u) ? 0u : 1u) : ((nib & 4u) ? 2u : 3u);
+        if (state == 0) {
+            if (src <= 1u) {  // diagonal: one column
+                ++cols; ++diag;
+                v.run(KP_COL_M, 1);
+                if (has_n) {  // a match when both bases are the same unambiguous base
+                    const int t = lo + r + bi;
+                    const uint32_t qc = kp_nib(qnib[r >> 3], r & 7);
+                    uint32_t tc = (asm_words[t >> 4] >> (2 * (t & 15))) & 3u;
+                    if (n_runs > 0) {
+                        int a = 0, z = n_runs;
+                        while (a < z) {
+                            const int mid = (a + z) >> 1;
+                            if (runs[2 * mid + 1] <= t) a = mid + 1; else z = mid;
+                        }
+                        if (a < n_runs && runs[2 * a] <= t) tc = 4u;
+                    }
+                    matches += (qc == tc && qc < 4u) ? 1 : 0;  // N against N scores KP_SC_N: not a match
+                }
+                if (src == 1u) { sr = r; sb = bi; walking = false; }
+                --r;
+            } else {
+                state = (int)src - 1;  // 1 = E, 2 = F: the gap's columns are counted in that state
+            }
+        } else if (state == 1) {  // E: gap in the query; this cell's E came from H (opened) or E (extended) of the left cell
+            ++cols; ++gap; gap_cost += EX;
+            v.run(KP_COL_D, 1);
+            --bi;
+            if (nib & 2u) { state = 0; gap_cost += KP_GAP_OPEN; credit += max(gap - KP_GAP_LONG, 0); gap = 0; }
+        } else {  // F: gap in the target
+            ++cols; ++gap; gap_cost += EX;
+            v.run(KP_COL_I, 1);
+            --r; ++bi;
+            if (nib & 1u) { state = 0; gap_cost += KP_GAP_OPEN; credit += max(gap - KP_GAP_LONG, 0); gap = 0; }
+        }
+    }
+    out.sr = sr; out.sb = sb; out.cols = cols; out.matches = matches; out.diag = diag; out.gap_cost = gap_cost; out.credit = credit;
+}
+
+// ---- joins: one lane per join, a path from the best cell of piece k back through the cross gaps ----------------------------
+// Direction byte of a cell: bits 0-2 the source of H (XT_*), bit 3 "E was extended", bit 4 "F was extended".
+enum { XT_DIAG = 0, XT_E = 1, XT_F = 2, XT_RESTART = 3, XT_X1 = 4, XT_X2 = 5 };
+
+struct KpJoinPath {
+    bool rejected;  // by the drop test (kp_spec.h, THE JOINED PATH)
+    int visited;    // mask of the pieces the path runs through
+    int sr, sb, spk;  // row, band index and piece of the path's first cell
+    int matches, cols, credit, bonus;
+};
+
+// what the walk reads of the join's assembly and gene
+struct KpJoinSeqs {
+    const uint32_t *qnib, *asm_words;
+    const int32_t *runs;
+    int n_runs, qlen, cstart, cend;
+};
+
+// A cross gap along a row (the later piece lies on higher diagonals) is a gap in the query: KP_COL_D; one down a column a
+// gap in the target: KP_COL_I.
+template <class V>
+__device__ __forceinline__ void kp_join_walk(const KpJoin *J, int k, int P, const KpJoinSeqs &s, const uint4 *trace, KpJoinPath &out, V &v) {
+    const int W = 4 * P;
+    int pk = k, r = J->end_r[k], bi = J->end_b[k], state = 0, matches = 0, cols = 0, gap = 0, credit = 0;
+    int sr = r, sb = bi, spk = k, suf = 0, sufmax = 0, gsum = 0, visited = 1 << k, bonus = 0;
+    bool rejected = false;
+    int lo = J->lo[pk], q0 = 0, r_hi = 0;
+    kp_piece_rows(lo, W, s.cstart, s.cend, s.qlen, J->r0[pk], J->r1[pk], &q0, &r_hi);
+    const uint32_t *tr = reinterpret_cast<const uint32_t *>(trace + J->trace_off[pk]);
+    for (;;) {
+        const int t = r + lo + bi;
+        if (state == 0 && (r < q0 || r >= r_hi || bi < 0 || bi >= W || t < s.cstart || t >= s.cend)) break;
+        const uint32_t byte = (tr[(size_t)(r - q0 + (bi >> 2)) * P + (bi >> 2)] >> (8 * (bi & 3))) & 255u;
+        if (state == 0) {
+            const uint32_t tb = byte & 7u;
+            if (tb == XT_RESTART) break;
+            // the drop test: at every cross gap, and at every cell once a gap has been crossed (cross-gap costs left out)
+            if (suf + gsum > sufmax) sufmax = suf + gsum;
+            else if ((tb >= XT_X1 || visited != (1 << k)) && sufmax - (suf + gsum) > KP_JOIN_DROP) { rejected = true; break; }
+            if (tb == XT_DIAG) {
+                sr = r; sb = bi; spk = pk; ++cols;
+                v.run(KP_COL_M, 1);
+                const uint32_t qc = kp_nib(s.qnib[r >> 3], r & 7);
+                uint32_t tc = (s.asm_words[t >> 4] >> (2 * (t & 15))) & 3u;
+                if (s.n_runs > 0) {
+                    int a = 0, z = s.n_runs;
+                    while (a < z) {
+                        const int mid = (a + z) >> 1;
+                        if (s.runs[2 * mid + 1] <= t) a = mid + 1; else z = mid;
+                    }
+                    if (a < s.n_runs && s.runs[2 * a] <= t) tc = 4u;
+                }
+                if (qc < 4u && qc == tc) ++matches;
+                suf += (qc > 3u || tc > 3u) ? KP_SC_N : (qc == tc ? KP_SC_MATCH : KP_SC_MISMATCH);
+                --r;
+            } else if (tb == XT_E || tb == XT_F) {
+                state = (int)tb;
+            } else {  // a cross gap: on to the cell of piece pk - 1 it came from
+                const int lo_prev = J->lo[pk - 1];
+                const bool horizontal = lo > lo_prev;
+                const unsigned long long *exp = reinterpret_cast<const unsigned long long *>(trace + J->export_off[pk - 1]);
+                const int xi = horizontal ? r : t - lo_prev;
+                const unsigned long long key = exp[2 * xi + (tb == XT_X1 ? 0 : 1)];
+                const int pos = (int)(0xFFFFFFFFu - (uint32_t)key);  // t' - lo_prev (horizontal) or r'
+                const int ngap = horizontal ? (t - lo_prev) - pos : r - pos;
+                cols += ngap;
+                v.run(horizontal ? KP_COL_D : KP_COL_I, ngap);
+                const int cost = tb == XT_X1 ? KP_GAP_OPEN + KP_GAP_EXT * ngap : KP_GAP_OPEN2 + KP_GAP_EXT2 * ngap;
+                suf -= cost; gsum += cost;
+                const int lg = KP_GAP_OPEN + kp_log2x2((uint32_t)ngap);
+                if (cost > lg) bonus += cost - lg;
+                if (horizontal) bi = pos - r;               // same row, column lo_prev + pos
+                else { bi = t - pos - lo_prev; r = pos; }   // same column, row pos
+                --pk; visited |= 1 << pk;
+                lo = lo_prev;
+                kp_piece_rows(lo, W, s.cstart, s.cend, s.qlen, J->r0[pk], J->r1[pk], &q0, &r_hi);
+                tr = reinterpret_cast<const uint32_t *>(trace + J->trace_off[pk]);
+            }
+        } else if (state == XT_E) {
+            ++cols; ++gap; --bi; suf -= KP_GAP_EXT;
+            v.run(KP_COL_D, 1);
+            if (!(byte & 8u)) { state = 0; suf -= KP_GAP_OPEN; credit += max(gap - KP_GAP_LONG, 0); gap = 0; }
+        } else {
+            ++cols; ++gap; --r; ++bi; suf -= KP_GAP_EXT;
+            v.run(KP_COL_I, 1);
+            if (!(byte & 16u)) { state = 0; suf -= KP_GAP_OPEN; credit += max(gap - KP_GAP_LONG, 0); gap = 0; }
+        }
+    }
+    out.rejected = rejected; out.visited = visited; out.sr = sr; out.sb = sb; out.spk = spk;
+    out.matches = matches; out.cols = cols; out.credit = credit; out.bonus = bonus;
+}

@@ -13,7 +13,7 @@ from typing import Sequence
 import numpy as np
 
 from kaptive_amd import _native
-from kaptive_amd.core.alignment import Alignments
+from kaptive_amd.core.alignment import Alignments, Cigars
 from kaptive_amd.core.genome import GenomeAssembly
 from kaptive_amd.core.pairwise import PairwiseAlignments
 from kaptive_amd.core.seq import Sequences
@@ -29,15 +29,21 @@ class Engine:
     typing tables as a *group* of the context and ``view(i)`` gives the engine as database ``i`` sees it.  The
     single-genome entry points (``align``, ``hits_to_alignments``) are those of a one-database engine."""
 
-    def __init__(self, db: "Database | Sequence[Database]", device: int = 0, ctx: "_native.Context | None" = None) -> None:
+    def __init__(self, db: "Database | Sequence[Database]", device: int = 0, ctx: "_native.Context | None" = None,
+                 cigar: bool = False) -> None:
         """``ctx``: a context of ``device`` the caller created ahead of time (the command line starts the runtime on a thread
-        of its own while the database file is still being read); otherwise one is created here."""
+        of its own while the database file is still being read); otherwise one is created here.  ``cigar``: alignment passes
+        also leave the CIGAR of every hit (``Batch.cigars``; ``align`` then fills ``Alignments.cigars``) -- a second walk of
+        every path on the device, off by default because typing never reads them."""
         dbs = list(db) if isinstance(db, (list, tuple)) else [db]
         self.dbs = dbs
         self.db = dbs[0]
         self.group = 0
         self.device = device
         self.ctx = ctx if ctx is not None else _native.Context(device)
+        self.cigar = bool(cigar)
+        if self.cigar:
+            self.ctx.set_option("cigar", 1)
         for d in dbs:  # KP_MAX_GENE_LEN (include/kp_spec.h): query positions are 16-bit fields of the anchor and hit keys
             too_long = np.flatnonzero(np.asarray(d.genes.lengths) > _native.MAX_GENE_LEN)
             if len(too_long):
@@ -82,7 +88,8 @@ class Engine:
         finally:
             batch.close()
 
-    def hits_to_alignments(self, genome: GenomeAssembly, hits: np.ndarray) -> Alignments:
+    def hits_to_alignments(self, genome: GenomeAssembly, hits: np.ndarray, cigars: "Cigars | None" = None) -> Alignments:
+        """``cigars``: the CIGARs of ``hits``, row for row (``Cigars.from_offsets`` of a slice of ``Batch.cigars``)."""
         if len(hits) == 0:
             return Alignments.empty()
         db = self.db
@@ -91,12 +98,21 @@ class Engine:
             q_ids=hits["gene"], q_lengths=db.genes.lengths[hits["gene"]], q_starts=hits["q_start"],
             q_ends=hits["q_end"], t_ids=hits["contig"], t_lengths=genome.contigs.lengths[hits["contig"]],
             t_starts=hits["t_start"], t_ends=hits["t_end"], strands=hits["strand"], block_lens=hits["block_len"],
-            matches=hits["matches"], scores=hits["score"], mapqs=hits["mapq"],
+            matches=hits["matches"], scores=hits["score"], mapqs=hits["mapq"], cigars=cigars,
         )  # fmt: skip
 
     def align(self, genomes: Sequence[GenomeAssembly]) -> list[Alignments]:
-        hits, off, _ = self.align_packed([g.packed() for g in genomes])
-        return [self.hits_to_alignments(g, hits[off[i] : off[i + 1]]) for i, g in enumerate(genomes)]
+        """One ``Alignments`` per genome; with ``cigar=True`` their ``cigars`` column is filled (every genome's is a view
+        of the batch's ops: no loop over the hits)."""
+        batch = self.ctx.batch([g.packed() for g in genomes])
+        try:
+            hits, off = batch.align()
+            ops, coff = batch.cigars() if self.cigar else (None, None)
+        finally:
+            batch.close()
+        return [self.hits_to_alignments(g, hits[off[i] : off[i + 1]],
+                                        Cigars.from_offsets(ops, coff[off[i] : off[i + 1] + 1]) if self.cigar else None)
+                for i, g in enumerate(genomes)]  # fmt: skip
 
     def protein_aligner(self, queries: Sequences, targets: Sequences) -> PairwiseAlignments:
         if len(queries.offsets) != len(targets.offsets):
