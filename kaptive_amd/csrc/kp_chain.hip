@@ -16,6 +16,7 @@
 // have to meet in one place for the joins of kp-align v4 (open sequences of clusters within KP_JOIN_BW diagonals,
 // JoinWave below; kp_join.hip chains and aligns them).
 #include "kp_internal.h"
+#include "kp_seqs.h"
 #include "kp_sketch.h"
 
 namespace {
@@ -483,12 +484,7 @@ __global__ __launch_bounds__(256) void kp_occ_sketch_kernel(KpBatchView b, OccSc
             const int64_t s0 = max(cs, s_pad), e0 = min(ce, s_pad + OCC_CHUNK);  // seeds whose 15-mer starts in [s0, e0) are this chunk's
             if (s0 >= e0) continue;
             const int64_t from = max(cs, s0 - OCC_WARM), to = min(ce, e0 + KP_K + KP_W + 1);  // (a seed is emitted at most K + W steps after its start)
-            int ri = 0;  // first N run that ends after `from`
-            {
-                int l2 = 0, h2 = nr;
-                while (l2 < h2) { const int mid = (l2 + h2) >> 1; if (runs[2 * mid + 1] <= from) l2 = mid + 1; else h2 = mid; }
-                ri = l2;
-            }
+            int ri = kp_first_run_after(runs, nr, (int32_t)from);  // (positions of an assembly fit 32 bits)
             auto emit = [&](int64_t t, uint32_t z, uint32_t x) {
                 (void)z;
                 if (t < s0 || t >= e0) return;

@@ -19,6 +19,7 @@
 // too small loses ops but nothing else, and the counts say how much room the repeat needs.
 #include <algorithm>
 
+#include "kp_hits.h"
 #include "kp_internal.h"
 #include "kp_reduce_core.h"
 #include "kp_walk.h"
@@ -57,12 +58,9 @@ __global__ __launch_bounds__(256) void kp_cigar_locate_tasks_kernel(KpBatchView 
     if (n > task_cap) n = task_cap;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const size_t at = (size_t)cls * task_cap + i;
-        const KpSwResult r = results[at];
-        if (r.score < KP_MIN_DP_SCORE || task_drop[at]) continue;  // (as kp_hit_compact_kernel)
         const KpTask t = tasks[at];
-        const int32_t cs = b.ctg_start[b.asm_first_ctg[t.asm_id] + t.contig];
-        const kp_hit mine = kp_make_hit(t.gs, t.contig, cs, gene_len[t.gs >> 1], r.score, r.q_start, r.q_end, r.t_start, r.t_end, r.matches,
-                                        r.block_len, t.n_anchors, t.chain_score);
+        kp_hit mine;
+        if (!kp_task_hit(b, gene_len, t, results[at], task_drop[at] != 0, &mine)) continue;
         claim(hits + (size_t)t.asm_id * hit_cap, (int)min(n_hits[t.asm_id], hit_cap), mine, src_key(false, t.lo, KP_TASK_REF(cls, i)),
               src + (size_t)t.asm_id * hit_cap);
     }
@@ -83,11 +81,8 @@ __global__ __launch_bounds__(64) void kp_cigar_locate_joins_kernel(KpBatchView b
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const KpJoin &J = joins[(size_t)cls * join_cap + i];
         for (int k = 1; k < J.n_pieces; ++k) {
-            if (J.state[k] != 1) continue;  // (as kp_join_hits_kernel)
-            const int32_t cs = b.ctg_start[b.asm_first_ctg[J.asm_id] + J.contig];
-            const int32_t *r = J.res[k];
-            const kp_hit mine = kp_make_hit(J.gs, J.contig, cs, gene_len[J.gs >> 1], (int)((uint32_t)r[7] | ((uint32_t)r[8] << KP_HIT_BONUS_SHIFT)),
-                                            r[1], r[2], r[3], r[4], r[5], r[6], J.n_anchors, J.chain_score);
+            kp_hit mine;
+            if (!kp_join_piece_hit(b, gene_len, J, k, &mine)) continue;
             claim(hits + (size_t)J.asm_id * hit_cap, (int)min(n_hits[J.asm_id], hit_cap), mine, src_key(true, J.lo[k], join_ref(cls, i, k)),
                   src + (size_t)J.asm_id * hit_cap);
         }
@@ -127,9 +122,6 @@ __global__ __launch_bounds__(WALK_THREADS) void kp_cigar_walk_kernel(KpBatchView
                                                                      const int64_t *__restrict__ off, uint32_t *__restrict__ ops, int64_t ops_cap) {
     for (int a = blockIdx.x; a < b.n_asm; a += gridDim.x) {
         const uint32_t n = min(n_hits[a], hit_cap);
-        const uint32_t *asm_words = b.words + b.asm_word_off[a];
-        const int r0n = b.asm_first_nrun[a], n_runs = b.asm_first_nrun[a + 1] - r0n;
-        const int32_t *runs = b.n_runs + 2 * (size_t)r0n;
         for (uint32_t i0 = 0; i0 < n; i0 += WALK_THREADS) {  // whole waves iterate together (kp_band_walk)
             const uint32_t i = i0 + threadIdx.x;
             const bool have = i < n;
@@ -145,24 +137,17 @@ __global__ __launch_bounds__(WALK_THREADS) void kp_cigar_walk_kernel(KpBatchView
             tk.asm_id = a; tk.gs = 0; tk.contig = 0; tk.lo = 0;
             KpSwEnd e;
             e.score = 0; e.er = 0; e.eb = 0; e.trace_off = 0;
-            int q0 = 0;
+            const KpJoin *J = joins + (size_t)cls * join_cap + (is_join ? (ref & 0x0FFFFFFFu) >> 3 : 0u);
             if (is_task) {
                 const size_t at = (size_t)cls * task_cap + KP_REF_SLOT(ref);
                 tk = tasks[at]; e = ends[at];
-                const int c_abs = b.asm_first_ctg[a] + tk.contig;
-                const int cstart = b.ctg_start[c_abs];
-                int r_hi;
-                kp_task_rows(tk.lo, 4 * P, cstart, cstart + b.ctg_len[c_abs], genes.len[tk.gs >> 1], &q0, &r_hi);
             }
+            const KpTaskSeqs s = kp_task_seqs(b, genes, a, is_join ? J->gs : tk.gs, is_join ? J->contig : tk.contig);
+            int q0 = 0, r_hi;
+            if (is_task) kp_task_rows(tk.lo, 4 * P, s.t.cstart, s.t.cend, s.q.len, &q0, &r_hi);
             KpBandPath bp;
-            kp_band_walk(is_task, tk.lo, P, q0, e.er, e.eb & 255, false, trace + e.trace_off, genes.nib, asm_words, runs, n_runs, bp, v);
+            kp_band_walk(is_task, tk.lo, P, q0, e.er, e.eb & 255, false, trace + e.trace_off, s, bp, v);
             if (is_join) {  // (rare: a lane each, after the wave's band tasks)
-                const KpJoin *J = joins + (size_t)cls * join_cap + ((ref & 0x0FFFFFFFu) >> 3);
-                const int gene = J->gs >> 1, c_abs = b.asm_first_ctg[a] + J->contig;
-                KpJoinSeqs s;
-                s.qnib = genes.nib + genes.word_off[(J->gs & 1) ? genes.n_genes + gene : gene];
-                s.asm_words = asm_words; s.runs = runs; s.n_runs = n_runs; s.qlen = genes.len[gene];
-                s.cstart = b.ctg_start[c_abs]; s.cend = s.cstart + b.ctg_len[c_abs];
                 KpJoinPath jp;
                 kp_join_walk(J, (int)(ref & 7u), P, s, trace, jp, v);
             }

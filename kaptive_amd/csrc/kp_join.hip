@@ -268,15 +268,8 @@ __device__ __forceinline__ void join_fill_class(const KpBatchView &b, const KpGe
         const bool have = slot < n_joins;
         KpJoin *J = joins + (have ? slot : 0u);
         const int n_pieces = have ? J->n_pieces : 0;
-        const int gs = have ? J->gs : 0, gene = gs >> 1, asm_id = have ? J->asm_id : 0;
-        const int qlen = have ? genes.len[gene] : 0;
-        const uint32_t *qnib = genes.nib + genes.word_off[(gs & 1) ? genes.n_genes + gene : gene];
-        const uint32_t *asm_words = b.words + b.asm_word_off[asm_id];
-        const int asm_n_words = (int)(b.asm_word_off[asm_id + 1] - b.asm_word_off[asm_id]);
-        const int c_abs = b.asm_first_ctg[asm_id] + (have ? J->contig : 0);
-        const int cstart = b.ctg_start[c_abs], cend = cstart + b.ctg_len[c_abs];
-        const int r0n = b.asm_first_nrun[asm_id], n_runs = b.asm_first_nrun[asm_id + 1] - r0n;
-        const int32_t *runs = b.n_runs + 2 * (size_t)r0n;
+        const KpTaskSeqs s = kp_task_seqs(b, genes, have ? J->asm_id : 0, have ? J->gs : 0, have ? J->contig : 0);
+        const int qlen = have ? s.q.len : 0;
         int max_pieces = n_pieces;
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) max_pieces = max(max_pieces, __shfl_xor(max_pieces, o));
@@ -291,7 +284,7 @@ __device__ __forceinline__ void join_fill_class(const KpBatchView &b, const KpGe
             const bool cont = k > 0;  // (pieces after the first take the cross gaps of the piece before; every piece is local: H >= 0, restarts)
             const int none = 0;
             int q0 = 0, r_hi = 0;
-            if (act) kp_piece_rows(lo, W, cstart, cend, qlen, J->r0[k], J->r1[k], &q0, &r_hi);
+            if (act) kp_piece_rows(lo, W, s.t.cstart, s.t.cend, qlen, J->r0[k], J->r1[k], &q0, &r_hi);
             const int steps = act ? (r_hi - q0) + P - 1 : 0;
             const int steps8 = (steps + 7) & ~7;
             const bool exports = act && k + 1 < n_pieces;
@@ -302,9 +295,7 @@ __device__ __forceinline__ void join_fill_class(const KpBatchView &b, const KpGe
             // (both multiples of eight 16-byte units: the band fill's task blocks -- same buffer, same bump counter -- count on
             // starting on 128-byte lines, kp_sw.hip; an export array of an odd length shifted every block allocated after it)
             const unsigned long long t_units = (unsigned long long)steps8 * P / 4, x_units = ((unsigned long long)exp_len + 7ull) & ~7ull;
-            unsigned long long toff = 0;
-            if (act && l == 0) toff = atomicAdd(trace_top, t_units + x_units);
-            toff = ((unsigned long long)__shfl((unsigned)(toff >> 32), g * P) << 32) | __shfl((unsigned)toff, g * P);
+            const unsigned long long toff = kp_trace_take(trace_top, act && l == 0, t_units + x_units, g * P);
             const bool fits = act && toff + t_units + x_units <= trace_cap && toff + t_units + x_units < 0xFFFFFFFFull;
             uint32_t *tr = reinterpret_cast<uint32_t *>(trace + toff);
             unsigned long long *exp = reinterpret_cast<unsigned long long *>(trace + toff + t_units);
@@ -335,12 +326,12 @@ __device__ __forceinline__ void join_fill_class(const KpBatchView &b, const KpGe
                 const int r0 = q0 + m0 - l;  // this lane's row at the chunk's first step
                 const int tb0 = lo + r0 + 4 * l;  // ... and the column of its cell 0 there: step s, cell c sits on tb0 + s + c
                 const int w0 = r0 >> 3, nq = (qlen + 7) >> 3;  // (arithmetic shifts: rows before the gene read as N)
-                const uint32_t lo_w = (fits && w0 >= 0 && w0 < nq) ? qnib[w0] : 0x44444444u;
-                const uint32_t hi_w = (fits && w0 + 1 >= 0 && w0 + 1 < nq) ? qnib[w0 + 1] : 0x44444444u;
+                const uint32_t lo_w = (fits && w0 >= 0 && w0 < nq) ? s.q.nib[w0] : 0x44444444u;
+                const uint32_t hi_w = (fits && w0 + 1 >= 0 && w0 + 1 < nq) ? s.q.nib[w0 + 1] : 0x44444444u;
                 qwin = (((uint64_t)hi_w << 32) | lo_w) >> (4 * (r0 & 7));
                 const int v0 = tb0 >> 4;
-                const uint32_t lo_t = (fits && v0 >= 0 && v0 < asm_n_words) ? asm_words[v0] : 0u;
-                const uint32_t hi_t = (fits && v0 + 1 >= 0 && v0 + 1 < asm_n_words) ? asm_words[v0 + 1] : 0u;
+                const uint32_t lo_t = (fits && v0 >= 0 && v0 < s.t.n_words) ? s.t.words[v0] : 0u;
+                const uint32_t hi_t = (fits && v0 + 1 >= 0 && v0 + 1 < s.t.n_words) ? s.t.words[v0 + 1] : 0u;
                 twin = (((uint64_t)hi_t << 32) | lo_t) >> (2 * (tb0 & 15));  // eleven bases: 22 of the 34 bits that are left
             };
             auto chunk = [&](const int m0, const uint64_t qwin, const uint64_t twin, auto io_tag, auto nr_tag) {
@@ -349,17 +340,7 @@ __device__ __forceinline__ void join_fill_class(const KpBatchView &b, const KpGe
                 const int tb0 = lo + r0 + 4 * l;
                 uint32_t nmask = 0;  // bit j: column tb0 + j lies in an N run
                 if constexpr (NR) {
-                    if (fits && n_runs > 0) {  // (rare: assemblies with scaffold gaps)
-                        int a2 = 0, z2 = n_runs;
-                        while (a2 < z2) {  // the first run that ends beyond tb0
-                            const int mid = (a2 + z2) >> 1;
-                            if (runs[2 * mid + 1] <= tb0) a2 = mid + 1; else z2 = mid;
-                        }
-                        for (; a2 < n_runs && runs[2 * a2] < tb0 + 11; ++a2) {
-                            const int s0 = max(runs[2 * a2] - tb0, 0), e0 = min(runs[2 * a2 + 1] - tb0, 11);
-                            if (e0 > s0) nmask |= ((1u << e0) - 1u) & ~((1u << s0) - 1u);
-                        }
-                    }
+                    if (fits && s.t.n_runs > 0) nmask = kp_n_mask(s.t.runs, s.t.n_runs, tb0, 11);  // (rare: assemblies with scaffold gaps)
                 }
                 unsigned long long kx1[IO ? 11 : 1], kx2[IO ? 11 : 1];  // cross-gap keys: of rows r0 + s (horizontal) or of columns tb0 + j (vertical)
                 if constexpr (IO) {
@@ -397,7 +378,7 @@ __device__ __forceinline__ void join_fill_class(const KpBatchView &b, const KpGe
                         }
                         const int t = tb0 + sidx + c;
                         int code = 5;  // 0..3, 4 = N, 5 = outside the contig
-                        if (row_ok && t >= cstart && t < cend) {
+                        if (row_ok && t >= s.t.cstart && t < s.t.cend) {
                             code = (int)((twin >> (2 * (sidx + c))) & 3u);
                             if constexpr (NR) {
                                 if ((nmask >> (sidx + c)) & 1u) code = 4;
@@ -413,8 +394,7 @@ __device__ __forceinline__ void join_fill_class(const KpBatchView &b, const KpGe
                         const uint32_t e_extd = e_open >= e_ext ? 0u : 1u, f_extd = f_open >= f_ext ? 0u : 1u;
                         if (dead(e)) e = JNEG;
                         if (dead(f)) f = JNEG;
-                        const int sc = (qc > 3 || code > 3) ? KP_SC_N : (qc == code ? KP_SC_MATCH : KP_SC_MISMATCH);
-                        int bv = hd + sc;
+                        int bv = hd + kp_sub_score(qc, code);
                         uint32_t tb = XT_DIAG;
                         if (e > bv) { bv = e; tb = XT_E; }
                         if (f > bv) { bv = f; tb = XT_F; }
@@ -458,7 +438,7 @@ __device__ __forceinline__ void join_fill_class(const KpBatchView &b, const KpGe
                     if (fits && m < steps8) tr[(size_t)m * P + l] = word;
                 }
             };
-            const bool nr_any = __any(n_runs > 0);
+            const bool nr_any = __any(s.t.n_runs > 0);
             uint64_t q_next = 0, t_next = 0;
             if (max_steps > 0) load_windows(0, q_next, t_next);
             for (int m0 = 0; m0 < max_steps; m0 += 8) {
@@ -473,12 +453,7 @@ __device__ __forceinline__ void join_fill_class(const KpBatchView &b, const KpGe
                     if (nr_any) chunk(m0, qwin, twin, std::false_type{}, std::true_type{}); else chunk(m0, qwin, twin, std::false_type{}, std::false_type{});
                 }
             }
-            // END of the piece: the largest score, then the first row, then the first column
-#pragma unroll
-            for (int o = 1; o < P; o <<= 1) {
-                const int s2 = __shfl_xor(best, o), r2 = __shfl_xor(best_r, o), b2 = __shfl_xor(best_b, o);
-                if (s2 > best || (s2 == best && (r2 < best_r || (r2 == best_r && b2 < best_b)))) { best = s2; best_r = r2; best_b = b2; }
-            }
+            kp_group_best<P>(best, best_r, best_b);  // END of the piece
             if (act && !fits) ok = false;
             if (act && l == 0) {
                 J->trace_off[k] = fits ? (uint32_t)toff : 0xFFFFFFFFu;
@@ -525,15 +500,8 @@ __global__ __launch_bounds__(64) void kp_join_trace_kernel(KpBatchView b, KpGene
     if (prio) __builtin_amdgcn_s_setprio(3);  // (as the joined fill: few lanes, long dependent walks)
     for (uint32_t ji = blockIdx.x * blockDim.x + threadIdx.x; ji < n; ji += gridDim.x * blockDim.x) {
         KpJoin *J = joins + (size_t)cls * join_cap + ji;
-        const int m = J->n_pieces, gs = J->gs, gene = gs >> 1, asm_id = J->asm_id;
-        const int c_abs = b.asm_first_ctg[asm_id] + J->contig;
-        const int r0n = b.asm_first_nrun[asm_id];
-        KpJoinSeqs seqs;
-        seqs.qnib = genes.nib + genes.word_off[(gs & 1) ? genes.n_genes + gene : gene];
-        seqs.asm_words = b.words + b.asm_word_off[asm_id];
-        seqs.runs = b.n_runs + 2 * (size_t)r0n; seqs.n_runs = b.asm_first_nrun[asm_id + 1] - r0n;
-        seqs.qlen = genes.len[gene];
-        seqs.cstart = b.ctg_start[c_abs]; seqs.cend = seqs.cstart + b.ctg_len[c_abs];
+        const int m = J->n_pieces;
+        const KpTaskSeqs seqs = kp_task_seqs(b, genes, J->asm_id, J->gs, J->contig);
         bool complete = true;
         for (int k = 0; k < m; ++k) complete = complete && J->trace_off[k] != 0xFFFFFFFFu;
         for (int k = 0; k < m; ++k) { J->state[k] = 0; J->visited[k] = 0; }

@@ -9,6 +9,7 @@
 // independent, so a batch of N assemblies keeps N waves busy; no step needs more than one wave's worth of LDS.
 #include <algorithm>
 
+#include "kp_hits.h"
 #include "kp_internal.h"
 #include "kp_reduce_core.h"
 
@@ -37,14 +38,15 @@ __global__ __launch_bounds__(256) void kp_hit_compact_kernel(KpBatchView b, cons
         t.asm_id = -1;
         KpSwResult r;
         r.score = 0;
-        int qlen = 0;
+        bool dropped = false;
         if (i < n) {
             t = tasks[(size_t)cls * task_cap + i];
             r = results[(size_t)cls * task_cap + i];
-            qlen = gene_len[t.gs >> 1];
-            if (t.n_anchors) my_cells += (unsigned long long)qlen * (unsigned)t.width;  // (0: rejected by the chaining)
+            dropped = task_drop[(size_t)cls * task_cap + i] != 0;
+            if (t.n_anchors) my_cells += (unsigned long long)gene_len[t.gs >> 1] * (unsigned)t.width;  // (0: rejected by the chaining)
         }
-        const bool hit = i < n && r.score >= KP_MIN_DP_SCORE && !task_drop[(size_t)cls * task_cap + i];  // (dropped: a chain consumed it, kp_join.hip)
+        kp_hit mine;
+        const bool hit = kp_task_hit(b, gene_len, t, r, dropped, &mine);
         uint32_t slot = 0;
         unsigned long long todo = __ballot(hit);
         while (todo) {
@@ -57,12 +59,7 @@ __global__ __launch_bounds__(256) void kp_hit_compact_kernel(KpBatchView b, cons
             if ((same >> lane) & 1ull) slot = base + (uint32_t)__builtin_popcountll(same & ((1ull << lane) - 1ull));
             todo &= ~same;
         }
-        if (hit && slot < hit_cap) {
-            const int32_t cs = b.ctg_start[b.asm_first_ctg[t.asm_id] + t.contig];
-            raw[(size_t)t.asm_id * hit_cap + slot] =
-                kp_make_hit(t.gs, t.contig, cs, qlen, r.score, r.q_start, r.q_end, r.t_start, r.t_end, r.matches, r.block_len,
-                            t.n_anchors, t.chain_score);
-        }
+        if (hit && slot < hit_cap) raw[(size_t)t.asm_id * hit_cap + slot] = mine;
     }
     if (my_cells) atomicAdd(cells, my_cells);
 }
@@ -82,14 +79,10 @@ __global__ __launch_bounds__(64) void kp_join_hits_kernel(KpBatchView b, const i
         for (int k = 0; k < J.n_pieces; ++k) rows += (unsigned long long)max(0, min(J.r1[k], qlen) - J.r0[k]);
         atomicAdd(cells, rows * (unsigned)J.width);
         for (int k = 1; k < J.n_pieces; ++k) {
-            if (J.state[k] != 1) continue;
+            kp_hit mine;
+            if (!kp_join_piece_hit(b, gene_len, J, k, &mine)) continue;
             const uint32_t slot = atomicAdd(&n_raw[J.asm_id], 1u);
-            if (slot >= hit_cap) continue;
-            const int32_t cs = b.ctg_start[b.asm_first_ctg[J.asm_id] + J.contig];
-            const int32_t *r = J.res[k];
-            raw[(size_t)J.asm_id * hit_cap + slot] =
-                kp_make_hit(J.gs, J.contig, cs, qlen, (int)((uint32_t)r[7] | ((uint32_t)r[8] << KP_HIT_BONUS_SHIFT)), r[1], r[2], r[3], r[4],
-                            r[5], r[6], J.n_anchors, J.chain_score);
+            if (slot < hit_cap) raw[(size_t)J.asm_id * hit_cap + slot] = mine;
         }
     }
 }

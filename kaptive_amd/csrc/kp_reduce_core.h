@@ -11,12 +11,8 @@
 #include <stdint.h>
 
 #include "../../include/kp_spec.h"
+#include "kp_seqs.h"
 
-#if defined(__HIPCC__)
-#define KP_HD __host__ __device__ __forceinline__
-#else
-#define KP_HD inline
-#endif
 #define KP_MAPQ_FN KP_HD
 #include "../../include/kp_mapq.h"
 
@@ -333,19 +329,7 @@ KP_HD void kp_cluster_and_pieces(KpKept *kept, int nk, const KpTypingDb &db, int
 }
 
 // ---- extraction + translation from the packed stream (seq.py:612-741; models.py:252-259) -----------------------------------
-// base code at assembly position t: 0..3, or 4 inside an N run
-KP_HD int kp_code_at(const uint32_t *asm_words, const int32_t *runs, int n_runs, int32_t t) {
-    if (n_runs > 0) {
-        int lo = 0, hi = n_runs;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (runs[2 * mid + 1] <= t) lo = mid + 1; else hi = mid;
-        }
-        if (lo < n_runs && runs[2 * lo] <= t) return 4;
-    }
-    return (int)((asm_words[t >> 4] >> (2 * (t & 15))) & 3u);
-}
-
+// (the base code at an assembly position: kp_code_at, kp_seqs.h)
 // amino acid of codon `c` (0-based) of the hit's extracted strand; the table is NCBI 11 indexed a*25+b*5+c with N=4
 KP_HD uint8_t kp_codon_aa(const uint32_t *asm_words, const int32_t *runs, int n_runs, int32_t abs_start,
                           int32_t abs_end, int strand, int frame, int c, const uint8_t *codon_table) {

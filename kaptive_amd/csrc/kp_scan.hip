@@ -13,6 +13,7 @@
 // kp_edge_kernel; a balanced kernel (kp_expand_kernel) probes the seed table, validates and expands the postings into
 // anchors.
 #include "kp_internal.h"
+#include "kp_seqs.h"
 #include "kp_sketch.h"
 
 namespace {
@@ -277,15 +278,7 @@ __global__ __launch_bounds__(256) void kp_edge_kernel(KpBatchView b, KpSeedIndex
     const uint32_t *aw = b.words + b.asm_word_off[a];
     const int64_t cs = b.ctg_start[c], ce = cs + b.ctg_len[c];
     const int r0 = b.asm_first_nrun[a], nr = b.asm_first_nrun[a + 1] - r0;
-    int r = 0;  // first N run that ends after the contig's start
-    {
-        int lo = 0, hi = nr;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (b.n_runs[2 * (r0 + mid) + 1] <= cs) lo = mid + 1; else hi = mid;
-        }
-        r = lo;
-    }
+    int r = kp_first_run_after(b.n_runs + 2 * (size_t)r0, nr, (int32_t)cs);  // first N run that ends after the contig's start
     int64_t S = cs;
     while (S < ce) {
         // the stretch [S, E): up to the next N run inside the contig
@@ -398,11 +391,7 @@ __global__ __launch_bounds__(256) void kp_expand_kernel(KpBatchView b, KpSeedInd
                             int64_t S = b.ctg_start[c0 + c], E = S + b.ctg_len[c0 + c];
                             const int r0 = b.asm_first_nrun[a], nr = b.asm_first_nrun[a + 1] - r0;
                             if (nr > 0) {
-                                int lo = 0, hi = nr;  // first run whose end is > t
-                                while (lo < hi) {
-                                    const int mid = (lo + hi) >> 1;
-                                    if (b.n_runs[2 * (r0 + mid) + 1] <= (int32_t)t) lo = mid + 1; else hi = mid;
-                                }
+                                const int lo = kp_first_run_after(b.n_runs + 2 * (size_t)r0, nr, (int32_t)t);
                                 if (lo < nr) E = min(E, (int64_t)b.n_runs[2 * (r0 + lo)]);  // (a run that holds t makes E <= t)
                                 if (lo > 0) S = max(S, (int64_t)b.n_runs[2 * (r0 + lo - 1) + 1]);
                             }

@@ -79,7 +79,6 @@ constexpr unsigned T_OUT = 12u;                             // shift amount of t
 // profile of a query row, per task 15 bits: field t (3 bits at 3t) = score against target code t (0..3 ACGT, 4 = N) + 4
 // (kp_row_profile, kp_internal.h: the database holds every gene as a stream of them)
 constexpr unsigned PROF_OUT = 0u;  // -4 everywhere
-__device__ __forceinline__ unsigned nibble(unsigned word, int i) { return (word >> (4 * i)) & 15u; }
 
 // One-lane shifts.  The lane without a source reads 0 (bound_ctrl); every group-edge lane overrides what it receives
 // anyway.  Groups of up to 16 lanes never straddle a DPP row, so the row shifts do; the 32-lane class needs wave shifts.
@@ -376,9 +375,7 @@ __device__ __forceinline__ void sw_class(const KpBatchView &b, const KpGenes &ge
         for (int o = 32; o >= 1; o >>= 1) max_steps = max(max_steps, __shfl_xor(max_steps, o));
         // the pair's trace blocks, X's then Y's: P lane streams of n_chunks 16-byte pieces each
         const unsigned long long want = (unsigned long long)P * (unsigned)((have[0] ? n_chunks[0] : 0) + (have[1] ? n_chunks[1] : 0));
-        unsigned long long toff = 0;
-        if (have[0] && l == 0) toff = atomicAdd(trace_top, want);
-        toff = ((unsigned long long)__shfl((unsigned)(toff >> 32), g * P) << 32) | __shfl((unsigned)toff, g * P);
+        const unsigned long long toff = kp_trace_take(trace_top, have[0] && l == 0, want, g * P);
         const bool fits = have[0] && toff + want <= trace_cap;  // else: counted, host reruns
         // piece j of lane l at [j / TG][l][j % TG]: TG consecutive pieces of a lane are contiguous, so the traceback -- it
         // follows one lane's pieces backwards -- fetches them in one go.  With TG = 2 a 128-byte line (four lanes) is
@@ -473,14 +470,7 @@ __device__ __forceinline__ void sw_class(const KpBatchView &b, const KpGenes &ge
                                 unsigned code = 5u;
                                 if (have[h] && t >= cstart[h] && t < cend[h]) {
                                     code = (s_tw[h][g][(t >> 4) - w0] >> (2 * (t & 15))) & 3u;
-                                    if (n_runs[h] > 0) {  // rare: assemblies with scaffold gaps
-                                        int a = 0, z = n_runs[h];
-                                        while (a < z) {
-                                            const int mid = (a + z) >> 1;
-                                            if (b.n_runs[run_off[h] + 2 * mid + 1] <= t) a = mid + 1; else z = mid;
-                                        }
-                                        if (a < n_runs[h] && b.n_runs[run_off[h] + 2 * a] <= t) code = 4u;
-                                    }
+                                    if (kp_in_n_run(b.n_runs + run_off[h], n_runs[h], t)) code = 4u;  // rare: assemblies with scaffold gaps
                                 }
                                 four[h] |= (code < 5u ? 3u * code : T_OUT) << (8 * i);
                                 saw_n[h] |= code == 4u;
@@ -663,43 +653,20 @@ __device__ __forceinline__ void sw_long_class(const KpBatchView &b, const KpGene
         KpTask tk;
         tk.asm_id = 0; tk.gs = 0; tk.contig = 0; tk.lo = 0;
         if (have) tk = tasks[ti];
-        const int gene = tk.gs >> 1;
-        const int qlen = have ? genes.len[gene] : 0;
-        const uint32_t *qnib = genes.nib + genes.word_off[(tk.gs & 1) ? genes.n_genes + gene : gene];
-        const uint32_t *asm_words = b.words + b.asm_word_off[tk.asm_id];
-        const int c_abs = b.asm_first_ctg[tk.asm_id] + tk.contig;
-        const int cstart = b.ctg_start[c_abs], cend = cstart + b.ctg_len[c_abs];
-        const int r0n = b.asm_first_nrun[tk.asm_id], n_runs = b.asm_first_nrun[tk.asm_id + 1] - r0n;
-        const int32_t *runs = b.n_runs + 2 * (size_t)r0n;
+        const KpTaskSeqs s = kp_task_seqs(b, genes, tk.asm_id, tk.gs, tk.contig);
         int q0, r_hi;
-        kp_task_rows(tk.lo, 4 * P, cstart, cend, qlen, &q0, &r_hi);
+        kp_task_rows(tk.lo, 4 * P, s.t.cstart, s.t.cend, have ? s.q.len : 0, &q0, &r_hi);
         const int steps = have ? (r_hi - q0) + P - 1 : 0;
         const int n_chunks = (((steps + 7) >> 3) + 3) & ~3;
         int max_steps = steps;
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) max_steps = max(max_steps, __shfl_xor(max_steps, o));
         const unsigned long long want = (unsigned long long)P * (unsigned)(have ? n_chunks : 0);
-        unsigned long long toff = 0;
-        if (have && l == 0) toff = atomicAdd(trace_top, want);
-        toff = ((unsigned long long)__shfl((unsigned)(toff >> 32), g * P) << 32) | __shfl((unsigned)toff, g * P);
+        const unsigned long long toff = kp_trace_take(trace_top, have && l == 0, want, g * P);
         const bool fits = have && toff + want <= trace_cap;
         uint4 *trace_x = trace + toff + TG * l;
-
-        auto target_code = [&](int t) -> int {  // 0..3, 4 = N, 5 = outside the contig
-            if (t < cstart || t >= cend) return 5;
-            int code = (int)((asm_words[t >> 4] >> (2 * (t & 15))) & 3u);
-            if (n_runs > 0) {
-                int a = 0, z = n_runs;
-                while (a < z) {
-                    const int mid = (a + z) >> 1;
-                    if (runs[2 * mid + 1] <= t) a = mid + 1; else z = mid;
-                }
-                if (a < n_runs && runs[2 * a] <= t) code = 4;
-            }
-            return code;
-        };
         int H[4] = {0, 0, 0, 0}, E[4], F[4], tc[4];
-        bool saw_n = have && genes.has_n[gene] != 0;
+        bool saw_n = have && genes.has_n[tk.gs >> 1] != 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) { E[k] = F[k] = LONG_NEG; tc[k] = 5; }
         int best = 0, best_r = 0, best_b = 4 * l;
@@ -708,11 +675,11 @@ __device__ __forceinline__ void sw_long_class(const KpBatchView &b, const KpGene
         for (int m = 0; m < steps8; ++m) {
             const int r = q0 + m - l;  // this lane's row
             const bool row_ok = have && r >= q0 && r < r_hi;
-            const int qc = row_ok ? (int)nibble(qnib[r >> 3], r & 7) : 4;
+            const int qc = row_ok ? s.q.code(r) : 4;
             // columns of the lane's cells: t0 + k, t0 = lo + r + 4l
             const int t0 = tk.lo + r + 4 * l;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) tc[k] = row_ok ? target_code(t0 + k) : 5;
+            for (int k = 0; k < 4; ++k) tc[k] = row_ok ? s.t.code(t0 + k) : 5;
             // left neighbour of A: lane l - 1's D as the previous step left it; upper neighbour of D: lane l + 1's A of this step
             int hl = __shfl_up(H[3], 1), el = __shfl_up(E[3], 1);
             if (l == 0) { hl = 0; el = LONG_NEG; }
@@ -733,8 +700,7 @@ __device__ __forceinline__ void sw_long_class(const KpBatchView &b, const KpGene
                 saw_n |= inside && code == 4;
                 const int e_open = hleft - OE, e_ext = eleft - EX, f_open = hup - OE, f_ext = fup - EX;
                 const int e = e_open >= e_ext ? e_open : e_ext, f = f_open >= f_ext ? f_open : f_ext;
-                const int s = (qc > 3 || code > 3) ? KP_SC_N : (qc == code ? KP_SC_MATCH : KP_SC_MISMATCH);
-                int bv = hd + s, tb = 0;
+                int bv = hd + kp_sub_score(qc, code), tb = 0;
                 if (e > bv) { bv = e; tb = 1; }
                 if (f > bv) { bv = f; tb = 2; }
                 const uint32_t not_d = tb != 0, not_l = tb == 0 ? (hd == 0) : (tb == 2);
@@ -755,13 +721,10 @@ __device__ __forceinline__ void sw_long_class(const KpBatchView &b, const KpGene
             }
         }
         // best cell of the task: the largest score, then the first row, then the first column
+        kp_group_best<P>(best, best_r, best_b);
         bool sn = saw_n;
 #pragma unroll
-        for (int o = 1; o < P; o <<= 1) {
-            const int s2 = __shfl_xor(best, o), r2 = __shfl_xor(best_r, o), b2 = __shfl_xor(best_b, o);
-            if (s2 > best || (s2 == best && (r2 < best_r || (r2 == best_r && b2 < best_b)))) { best = s2; best_r = r2; best_b = b2; }
-            sn |= __shfl_xor((int)sn, o) != 0;
-        }
+        for (int o = 1; o < P; o <<= 1) sn |= __shfl_xor((int)sn, o) != 0;
         if (have && l == 0) {
             KpSwEnd out;
             out.score = fits ? best : 0;
@@ -816,28 +779,17 @@ __global__ __launch_bounds__(TB_THREADS) void kp_sw_traceback_kernel(KpBatchView
         out.score = e.score; out.q_start = out.q_end = out.t_start = out.t_end = out.matches = out.block_len = 0;
         const bool walking = have && e.score >= KP_MIN_DP_SCORE;  // the others are dropped by the hit filter anyway
         KpTask tk;
-        tk.asm_id = 0; tk.gs = 0; tk.lo = 0;
+        tk.asm_id = 0; tk.gs = 0; tk.contig = 0; tk.lo = 0;
         if (walking) tk = tasks[at];
-        const int gene = tk.gs >> 1;
-        const int qlen = walking ? genes.len[gene] : 0;
         const bool has_n = (e.eb & KP_SWEND_HAS_N) != 0;
         const int eb = e.eb & 255;
-        const uint32_t *qnib = genes.nib + genes.word_off[(tk.gs & 1) ? genes.n_genes + gene : gene];
-        const uint32_t *asm_words = b.words + b.asm_word_off[tk.asm_id];
-        const int r0 = b.asm_first_nrun[tk.asm_id];
-        const int n_runs = b.asm_first_nrun[tk.asm_id + 1] - r0;
-        const int32_t *runs = b.n_runs + 2 * (size_t)r0;
-        int q0 = 0;  // first row the fill kernel computed for the task: its steps count from there
-        if (walking) {
-            const int c_abs = b.asm_first_ctg[tk.asm_id] + tk.contig;
-            const int cstart = b.ctg_start[c_abs];
-            int r_hi;
-            kp_task_rows(tk.lo, 4 * P, cstart, cstart + b.ctg_len[c_abs], qlen, &q0, &r_hi);
-        }
+        const KpTaskSeqs s = kp_task_seqs(b, genes, tk.asm_id, tk.gs, tk.contig);
+        int q0 = 0, r_hi;  // q0: first row the fill kernel computed for the task: its steps count from there
+        if (walking) kp_task_rows(tk.lo, 4 * P, s.t.cstart, s.t.cend, s.q.len, &q0, &r_hi);
         const uint4 *tw = reinterpret_cast<const uint4 *>(trace) + e.trace_off;  // piece j of lane l at [(j / TG) * TG * P + TG * l + j % TG]
         KpBandPath path;
         KpNoVisit nobody;
-        kp_band_walk(walking, tk.lo, P, q0, e.er, eb, has_n, tw, qnib, asm_words, runs, n_runs, path, nobody);
+        kp_band_walk(walking, tk.lo, P, q0, e.er, eb, has_n, tw, s, path, nobody);
         if (!have) continue;
         if (e.score < KP_MIN_DP_SCORE) { results[at] = out; continue; }
         const int matches = has_n ? path.matches : (e.score + 4 * path.diag + path.gap_cost) / 6;

@@ -2,10 +2,12 @@
 // (kp_sw.hip: kp_sw_kernel / kp_sw_long_kernel) and the joins' (kp_join.hip: kp_join_fill_kernel).  Each is written once and
 // takes a VISITOR that is told every run of columns the path makes, in walking order (from the path's end to its start):
 // the tracebacks that reduce a path to the fields of its hit pass KpNoVisit, the CIGAR kernels (kp_cigar.hip) one that
-// counts or writes run-length ops.  Device code only.
+// counts or writes run-length ops.  Ahead of them: the view of a task's two sequences that fills and walks read (kp_seqs.h) and
+// the two steps the scalar fills share.  Device code only.
 #pragma once
 
 #include "kp_internal.h"
+#include "kp_seqs.h"
 
 #ifndef KP_TRACE_GROUP
 #define KP_TRACE_GROUP 2
@@ -19,7 +21,43 @@ struct KpNoVisit {
     __device__ __forceinline__ void run(int, int) {}
 };
 
-__device__ __forceinline__ unsigned kp_nib(unsigned word, int i) { return (word >> (4 * i)) & 15u; }
+// ---- the two sequences of a band task or a join ------------------------------------------------------------------------------
+struct KpTaskSeqs {
+    KpQuerySeq q;
+    KpTargetSeq t;
+};
+__device__ __forceinline__ KpTaskSeqs kp_task_seqs(const KpBatchView &b, const KpGenes &genes, int asm_id, int gs, int contig) {
+    KpTaskSeqs s;
+    const int gene = gs >> 1, c_abs = b.asm_first_ctg[asm_id] + contig, r0 = b.asm_first_nrun[asm_id];
+    s.q.nib = genes.nib + genes.word_off[(gs & 1) ? genes.n_genes + gene : gene];
+    s.q.len = genes.len[gene];
+    s.t.words = b.words + b.asm_word_off[asm_id];
+    s.t.n_words = (int)(b.asm_word_off[asm_id + 1] - b.asm_word_off[asm_id]);
+    s.t.runs = b.n_runs + 2 * (size_t)r0;
+    s.t.n_runs = b.asm_first_nrun[asm_id + 1] - r0;
+    s.t.cstart = b.ctg_start[c_abs];
+    s.t.cend = s.t.cstart + b.ctg_len[c_abs];
+    return s;
+}
+
+// ---- shared by the fills: a task (a pair of them in the packed fill) belongs to a group of P lanes -----------------------------
+// Room in the trace buffer: the group's leader (lane `leader` of the wave; `takes` is set in that lane alone) bumps the counter
+// by `want` 16-byte units and every lane of the group gets the offset.
+__device__ __forceinline__ unsigned long long kp_trace_take(unsigned long long *trace_top, bool takes, unsigned long long want, int leader) {
+    unsigned long long toff = 0;
+    if (takes) toff = atomicAdd(trace_top, want);
+    return ((unsigned long long)__shfl((unsigned)(toff >> 32), leader) << 32) | __shfl((unsigned)toff, leader);
+}
+// Best cell over the group's lanes (the scalar fills; the packed one reduces a key): the largest score, then the first row, then the first column.
+template <int P>
+__device__ __forceinline__ void kp_group_best(int &best, int &best_r, int &best_b) {
+#pragma unroll
+    for (int o = 1; o < P; o <<= 1) {
+        const int s2 = __shfl_xor(best, o), r2 = __shfl_xor(best_r, o), b2 = __shfl_xor(best_b, o);
+        if (s2 > best || (s2 == best && (r2 < best_r || (r2 == best_r && b2 < best_b)))) { best = s2; best_r = r2; best_b = b2; }
+    }
+}
+
 __device__ __forceinline__ uint32_t kp_piece_word(const uint4 &v, int k) {  // cell k's word of a piece, in registers' terms
     const uint32_t lo = (k & 1) ? v.y : v.x, hi = (k & 1) ? v.w : v.z;
     return (k & 2) ? hi : lo;
@@ -49,8 +87,7 @@ struct KpBandPath {
 // the fill computed for the task (kp_task_rows), (er, eb) = its best cell, tw = the task's trace block.
 template <class V>
 __device__ __forceinline__ void kp_band_walk(bool walking, int lo, int P, int q0, int er, int eb, bool has_n, const uint4 *tw,
-                                             const uint32_t *qnib, const uint32_t *asm_words, const int32_t *runs, int n_runs,
-                                             KpBandPath &out, V &v) {
+                                             const KpTaskSeqs &s, KpBandPath &out, V &v) {
     constexpr int TG = KP_TRACE_GROUP;
     constexpr int EX = KP_GAP_EXT;
     int r = er, bi = eb, state = 0, cols = 0, matches = 0, diag = 0, gap_cost = 0, gap = 0, credit = 0;
@@ -112,18 +149,8 @@ __device__ __forceinline__ void kp_band_walk(bool walking, int lo, int P, int q0
                 ++cols; ++diag;
                 v.run(KP_COL_M, 1);
                 if (has_n) {  // a match when both bases are the same unambiguous base
-                    const int t = lo + r + bi;
-                    const uint32_t qc = kp_nib(qnib[r >> 3], r & 7);
-                    uint32_t tc = (asm_words[t >> 4] >> (2 * (t & 15))) & 3u;
-                    if (n_runs > 0) {
-                        int a = 0, z = n_runs;
-                        while (a < z) {
-                            const int mid = (a + z) >> 1;
-                            if (runs[2 * mid + 1] <= t) a = mid + 1; else z = mid;
-                        }
-                        if (a < n_runs && runs[2 * a] <= t) tc = 4u;
-                    }
-                    matches += (qc == tc && qc < 4u) ? 1 : 0;  // N against N scores KP_SC_N: not a match
+                    const int qc = s.q.code(r), tc = s.t.at(lo + r + bi);
+                    matches += (qc == tc && qc < 4) ? 1 : 0;  // N against N scores KP_SC_N: not a match
                 }
                 if (src == 1u) { sr = r; sb = bi; walking = false; }
                 --r;
@@ -156,27 +183,20 @@ struct KpJoinPath {
     int matches, cols, credit, bonus;
 };
 
-// what the walk reads of the join's assembly and gene
-struct KpJoinSeqs {
-    const uint32_t *qnib, *asm_words;
-    const int32_t *runs;
-    int n_runs, qlen, cstart, cend;
-};
-
 // A cross gap along a row (the later piece lies on higher diagonals) is a gap in the query: KP_COL_D; one down a column a
 // gap in the target: KP_COL_I.
 template <class V>
-__device__ __forceinline__ void kp_join_walk(const KpJoin *J, int k, int P, const KpJoinSeqs &s, const uint4 *trace, KpJoinPath &out, V &v) {
+__device__ __forceinline__ void kp_join_walk(const KpJoin *J, int k, int P, const KpTaskSeqs &s, const uint4 *trace, KpJoinPath &out, V &v) {
     const int W = 4 * P;
     int pk = k, r = J->end_r[k], bi = J->end_b[k], state = 0, matches = 0, cols = 0, gap = 0, credit = 0;
     int sr = r, sb = bi, spk = k, suf = 0, sufmax = 0, gsum = 0, visited = 1 << k, bonus = 0;
     bool rejected = false;
     int lo = J->lo[pk], q0 = 0, r_hi = 0;
-    kp_piece_rows(lo, W, s.cstart, s.cend, s.qlen, J->r0[pk], J->r1[pk], &q0, &r_hi);
+    kp_piece_rows(lo, W, s.t.cstart, s.t.cend, s.q.len, J->r0[pk], J->r1[pk], &q0, &r_hi);
     const uint32_t *tr = reinterpret_cast<const uint32_t *>(trace + J->trace_off[pk]);
     for (;;) {
         const int t = r + lo + bi;
-        if (state == 0 && (r < q0 || r >= r_hi || bi < 0 || bi >= W || t < s.cstart || t >= s.cend)) break;
+        if (state == 0 && (r < q0 || r >= r_hi || bi < 0 || bi >= W || t < s.t.cstart || t >= s.t.cend)) break;
         const uint32_t byte = (tr[(size_t)(r - q0 + (bi >> 2)) * P + (bi >> 2)] >> (8 * (bi & 3))) & 255u;
         if (state == 0) {
             const uint32_t tb = byte & 7u;
@@ -187,18 +207,9 @@ __device__ __forceinline__ void kp_join_walk(const KpJoin *J, int k, int P, cons
             if (tb == XT_DIAG) {
                 sr = r; sb = bi; spk = pk; ++cols;
                 v.run(KP_COL_M, 1);
-                const uint32_t qc = kp_nib(s.qnib[r >> 3], r & 7);
-                uint32_t tc = (s.asm_words[t >> 4] >> (2 * (t & 15))) & 3u;
-                if (s.n_runs > 0) {
-                    int a = 0, z = s.n_runs;
-                    while (a < z) {
-                        const int mid = (a + z) >> 1;
-                        if (s.runs[2 * mid + 1] <= t) a = mid + 1; else z = mid;
-                    }
-                    if (a < s.n_runs && s.runs[2 * a] <= t) tc = 4u;
-                }
-                if (qc < 4u && qc == tc) ++matches;
-                suf += (qc > 3u || tc > 3u) ? KP_SC_N : (qc == tc ? KP_SC_MATCH : KP_SC_MISMATCH);
+                const int qc = s.q.code(r), tc = s.t.at(t);
+                if (qc < 4 && qc == tc) ++matches;
+                suf += kp_sub_score(qc, tc);
                 --r;
             } else if (tb == XT_E || tb == XT_F) {
                 state = (int)tb;
@@ -220,7 +231,7 @@ __device__ __forceinline__ void kp_join_walk(const KpJoin *J, int k, int P, cons
                 else { bi = t - pos - lo_prev; r = pos; }   // same column, row pos
                 --pk; visited |= 1 << pk;
                 lo = lo_prev;
-                kp_piece_rows(lo, W, s.cstart, s.cend, s.qlen, J->r0[pk], J->r1[pk], &q0, &r_hi);
+                kp_piece_rows(lo, W, s.t.cstart, s.t.cend, s.q.len, J->r0[pk], J->r1[pk], &q0, &r_hi);
                 tr = reinterpret_cast<const uint32_t *>(trace + J->trace_off[pk]);
             }
         } else if (state == XT_E) {

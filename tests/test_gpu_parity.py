@@ -1519,3 +1519,106 @@ def test_genes_beyond_the_packed_score_range(oracle):
     with pytest.raises(ValueError):
         ctx.load_genes(c2, o2)
     ctx.close()
+
+
+def _n_run_contigs(db):
+    """Hand-made contigs that put an N under every reader of kp_seqs.h's look-ups: (a) copies of four genes on both strands, each
+    with a 1-base N run and, elsewhere, two runs one base apart -- the packed fill's slow path and the band walk; (b) a gene with a
+    90-base deletion and a 40-base N run 200 rows before the junction (five 8-step chunks, four 11-column windows), and the
+    same contig reverse-complemented -- the joined fill's masks and the join walk; (c) a whole gene between 12 N at either end of
+    its contig."""
+    from kaptive_amd.synth import revcomp
+
+    rng = np.random.default_rng(2024)
+    flank = lambda n: random_dna(rng, n, 0.5)  # noqa: E731
+    gene = lambda i: np.frombuffer(db.genes[i].seq, np.uint8).copy()  # noqa: E731
+    N = ord("N")
+    copies = []
+    for n, i in enumerate((4, 7, 8, 11)):
+        g = gene(i)
+        g[301 + 7 * n] = N
+        g[600:603] = N
+        g[604:609] = N
+        copies += [flank(120 + n), revcomp(g) if n & 1 else g]
+    a = np.concatenate([*copies, flank(90)])
+    g = gene(13)
+    half = len(g) // 2
+    b = np.concatenate([flank(200), g[:half], g[half + 90 :], flank(200)])
+    b[200 + half - 200 : 200 + half - 160] = N
+    c = np.concatenate([np.full(12, N, np.uint8), gene(16), np.full(12, N, np.uint8)])
+    return [SeqRecord("a_short_runs", a.tobytes()), SeqRecord("b_joined", b.tobytes()), SeqRecord("b_joined_rc", revcomp(b).tobytes()),
+            SeqRecord("c_n_at_both_ends", c.tobytes())]  # fmt: skip
+
+
+def _long_gene_with_n_runs():
+    """(d) A database with one gene beyond the packed fill's range (kp_sw_long_kernel) and an assembly that holds it twice: with a
+    200-base deletion that joins it and a 40-base N run inside the first piece, and whole with runs as in (a)."""
+    rng = np.random.default_rng(2025)
+    big = random_dna(rng, _native.FILL16_MAX_GENE_LEN + 400, 0.5)
+    genes = Sequences.from_records([SeqRecord("s0", random_dna(rng, 900, 0.5).tobytes()), SeqRecord("big", big.tobytes())])
+    N = ord("N")
+    joined = np.concatenate([random_dna(rng, 60, 0.5), big[:8000], big[8200:], random_dna(rng, 60, 0.5)])
+    joined[60 + 7000 : 60 + 7040] = N
+    whole = np.concatenate([random_dna(rng, 33, 0.5), big, random_dna(rng, 33, 0.5)])
+    whole[33 + 5001] = N
+    whole[33 + 9000 : 33 + 9003] = N
+    whole[33 + 9004 : 33 + 9009] = N
+    return genes, [SeqRecord("d_joined", joined.tobytes()), SeqRecord("d_whole", whole.tobytes())]
+
+
+def _hits_over_n(hits, joins, pa, gene_off):
+    """(joined hits, band-task hits) of an assembly's hit table whose target span holds an N column; joined: the record of a
+    join's piece in state 1."""
+    from tests import cigar_util as U
+
+    codes = U.assembly_codes(pa)
+    joined = set()
+    for j in joins:
+        gs = int(j["gs"])
+        qlen = int(gene_off[(gs >> 1) + 1] - gene_off[gs >> 1])
+        for p in j["piece"][: int(j["n_pieces"])]:
+            if p[0] == 1:
+                joined.add((gs >> 1, int(j["contig"]), *U.result_to_hit_fields([0, *p[3:7], 0, 0], gs, qlen, int(pa.ctg_start[j["contig"]]))))
+    n_joined = n_band = 0
+    for h in hits:
+        cs = int(pa.ctg_start[h["contig"]])
+        if not (codes[cs + int(h["t_start"]) : cs + int(h["t_end"])] == 4).any():
+            continue
+        rec = (int(h["gene"]), int(h["contig"]), int(h["q_start"]), int(h["q_end"]), int(h["t_start"]), int(h["t_end"]), int(h["strand"]))
+        n_joined += rec in joined
+        n_band += rec not in joined
+    return n_joined, n_band
+
+
+def test_n_runs_under_every_fill_and_walk_match_oracle(oracle, small_db):
+    """The packed fill, the 32-bit fill, the joined fill and both walks read target bases through one function (kp_seqs.h): every
+    one of them meets N runs here -- _n_run_contigs on the small database, _long_gene_with_n_runs on a database of its own.  Hits,
+    band tasks and join records equal the oracle's; with CIGARs on, the same hits and the invariants of kp_spec.h's CIGAR section."""
+    from tests.test_gpu_cigar import Run, _check_invariants
+
+    long_genes, long_recs = _long_gene_with_n_runs()
+    n_joined = n_band = n_joined_long = 0
+    for genes, recs in ((small_db.genes, _n_run_contigs(small_db)), (long_genes, long_recs)):
+        asm = GenomeAssembly("n_runs", Sequences.from_records(recs))
+        run = Run(genes, [asm], cigar=0)
+        pa = run.packed[0]
+        odb = oracle.OracleDB(run.codes, run.off)
+        want, want_j = odb.align(pa), np.sort(odb.joins(pa), order=["gs", "contig"])
+        _same_records(run.hits, want, "hits over N runs")
+        got_j = np.sort(run.batch.joins(0), order=["gs", "contig"])
+        assert len(want_j) == len(got_j)
+        for f in want_j.dtype.names:
+            assert np.array_equal(want_j[f], got_j[f]), (f, want_j[f][:2], got_j[f][:2])
+        want_t = np.sort(odb.tasks(pa), order=list(_native.TASK_DTYPE.names))
+        _same_records(np.sort(run.batch.tasks(0), order=list(_native.TASK_DTYPE.names)), want_t, "tasks over N runs")
+        run.close()
+        with_ops = Run(genes, [asm], cigar=1)
+        assert with_ops.hits.tobytes() == run.hits.tobytes()
+        checked, _ = _check_invariants(with_ops, lambda a: asm.id)
+        with_ops.close()
+        j, t = _hits_over_n(want, want_j, pa, run.off)  # (of the oracle's output alone)
+        assert checked >= j
+        n_joined, n_band = n_joined + j, n_band + t
+        n_joined_long = j if genes is long_genes else 0
+    # the comparison above was not vacuous: hits whose target span holds an N column
+    assert n_joined >= 2 and n_band >= 4 and n_joined_long >= 1, (n_joined, n_band, n_joined_long)
