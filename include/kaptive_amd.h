@@ -65,7 +65,9 @@ KP_API void *kp_ctx_stream(kp_ctx *ctx);
  * what the context has learnt for it), library_sort (anchors are sorted by the library's segmented radix sort instead of
  * the bucket sort of kp_bsort.hip; same result), scan_mode (ablation modes of the scan kernel, tools/scan_ablate.py),
  * cigar (0 | 1: CIGARs of the hits, kp_batch_cigars; from the next kp_batch_align) and cigar_ops_per_hit (first size of their
- * buffer; setting it forgets what the context has learnt for it). */
+ * buffer; setting it forgets what the context has learnt for it), cs (0 | 1: cs difference strings of the hits, kp_batch_cs;
+ * from the next kp_batch_align; such a pass computes the CIGARs as well) and cs_bytes_per_hit (first size of their buffer,
+ * likewise). */
 KP_API int kp_ctx_set_option(kp_ctx *ctx, const char *name, int64_t value);
 #define KP_WORK_SLOTS 3
 
@@ -228,6 +230,18 @@ KP_API int kp_batch_set_hits(kp_ctx *ctx, kp_batch *batch, const kp_hit *hits, c
  * batches need, and a buffer that was too small is grown and the ops written again without another alignment pass. */
 KP_API int kp_batch_cigar_offsets(kp_ctx *ctx, kp_batch *batch, int64_t *cigar_off);
 KP_API int kp_batch_cigars(kp_ctx *ctx, kp_batch *batch, uint32_t *ops, int64_t cap);
+/* cs difference strings of the batch's hits (kp_spec.h, CS): minimap2's short form of the cs:Z: tag, which says which bases
+ * differ where the CIGAR says only where the gaps are.  The reference's Alignments carries a cs column that it never fills
+ * (do_cs=False).  Only for a batch whose kp_batch_align ran with the option `cs` set (default 0: nothing is computed, allocated
+ * or launched for them; cs = 1 computes the CIGARs too, whatever `cigar` says) -- otherwise, and after kp_batch_set_hits, both
+ * calls return KP_ESTATE.
+ *   kp_batch_cs_offsets : cs_off[total_hits + 1], rows as kp_batch_hits lists them: the string of hit i is
+ *                         bytes[cs_off[i] .. cs_off[i + 1]) (no terminator)
+ *   kp_batch_cs         : the bytes; KP_EINVAL when cap < cs_off[total_hits]
+ * The option `cs_bytes_per_hit` is the first guess for the size of the byte buffer (default 64); the context learns what its
+ * batches need, and a buffer that was too small is grown and the bytes written again: no other kernel is rerun. */
+KP_API int kp_batch_cs_offsets(kp_ctx *ctx, kp_batch *batch, int64_t *cs_off);
+KP_API int kp_batch_cs(kp_ctx *ctx, kp_batch *batch, char *bytes, int64_t cap);
 /* counters of the last kp_batch_align: [0] anchors, [1] band tasks, [2] DP cells, [3] hits, [4] overflow retries */
 KP_API int kp_batch_stats(kp_ctx *ctx, kp_batch *batch, int64_t *stats5);
 
@@ -355,6 +369,16 @@ typedef struct kp_paf_tables {
 } kp_paf_tables;
 KP_API int64_t kp_format_paf(const kp_paf_tables *tables, int32_t n_asm, const kp_hit *hits, const int64_t *hit_off,
                              const uint32_t *ops, const int64_t *cigar_off, char *out, int64_t cap);
+/* The same lines with what the cs strings add (cs / cs_off as kp_batch_cs returns them; may be null when flags == 0):
+ *   KP_PAF_CS  : "\tcs:Z:<string>" after cg:Z:
+ *   KP_PAF_EQX : cg:Z: in =/X form (minimap2 --eqx), derived from the cs bytes (kp_spec.h, CS)
+ * flags == 0 gives the bytes of kp_format_paf.  A cs string that breaks the grammar or the canonical form, or whose column
+ * totals disagree with the hit's ops, is KP_EINVAL. */
+#define KP_PAF_CS 1
+#define KP_PAF_EQX 2
+KP_API int64_t kp_format_paf_tags(const kp_paf_tables *tables, int32_t n_asm, const kp_hit *hits, const int64_t *hit_off,
+                                  const uint32_t *ops, const int64_t *cigar_off, const char *cs, const int64_t *cs_off, int32_t flags,
+                                  char *out, int64_t cap);
 
 /* ---- JSON lines of a whole batch (host only) ----------------------------------------------------------------------------------
  * Replaces orjson.dumps(SerotypingResult.to_dict(), OPT_SERIALIZE_NUMPY | OPT_APPEND_NEWLINE) per genome

@@ -369,6 +369,27 @@ typedef struct kp_hit {
 #define KP_CIGAR_D 2
 #define KP_CIGAR_SHIFT 4
 
+/* ---- CS (optional, like the CIGAR: no hit, no op and no report byte depends on it) -------------------------------------------------
+ * The cs string of a hit is a pure function of its CIGAR ops and its two sequences; the direction bits of the fill are not read.
+ * The query is the gene AS ALIGNED -- its reverse complement for strand -1, starting at row len - q_end; at q_start for strand
+ * +1 -- and the target the contig, forward, from t_start.  Tokens are listed in the order of increasing target position, in the
+ * grammar of minimap2's short form:
+ *     :<n>        a maximal run of n identical columns
+ *     *<t><q>     one substituted column: target base, then gene base
+ *     +<bases>    the gene bases of an I op
+ *     -<bases>    the contig bases of a D op
+ * Letters are the lower-case acgtn of the packed alphabet: a contig position inside an N run is n, a gene code above 3 is n.
+ * A column is IDENTICAL iff both codes are <= 3 and equal -- the rule `matches` is counted by (KP_SC_MATCH pairs).  A column with
+ * an ambiguous base on either side is therefore a * token (*na, *nn, ...).  This is the one deviation from minimap2, which
+ * counts N against N as identical.
+ * CANONICAL FORM.  No :0; two : tokens never touch; neighbouring substituted columns give neighbouring * tokens, never merged.
+ * The first and last token of a hit are : tokens, since the first and last op are M and a local path begins and ends on a match.
+ * CONSISTENCY.  The : lengths sum to `matches`; the number of * tokens plus the : lengths is the sum of the M lengths; the
+ * letters behind + and - number the sums of the I and of the D lengths.
+ * =/X CIGAR.  Derived from the cs string: :n gives n=, a run of k * tokens kX, + and - give I and D (BAM codes 7 and 8). */
+#define KP_CIGAR_EQ 7
+#define KP_CIGAR_X 8
+
 /* ---- records of the batched reduction (one assembly = one summary, its kept hits and its locus pieces) ------------------
  * They carry what SerotypingResult needs (src/kaptive/serotyping/models.py:513-536) minus strings and sequences. */
 #define KP_F_EXPECTED 1u /* gene belongs to the best locus and is not an extra gene (core.py:226-228) */

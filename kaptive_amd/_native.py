@@ -38,7 +38,7 @@ EXPORTS = (
     "kp_ctx_create", "kp_ctx_destroy", "kp_last_error", "kp_ctx_stream", "kp_ctx_set_option", "kp_host_alloc",
     "kp_host_free", "kp_host_reserve", "kp_host_lock", "kp_host_pinned_bytes", "kp_device_allocations", "kp_db_load", "kp_db_n_postings", "kp_batch_create", "kp_batch_create_async",
     "kp_batch_upload_wait", "kp_batch_depends_on", "kp_batch_create_device", "kp_batch_device_words", "kp_batch_destroy", "kp_batch_align", "kp_batch_wait",
-    "kp_batch_hit_offsets", "kp_batch_hits", "kp_batch_set_hits", "kp_batch_cigar_offsets", "kp_batch_cigars", "kp_format_paf", "kp_batch_stats", "kp_batch_profile", "kp_batch_anchors",
+    "kp_batch_hit_offsets", "kp_batch_hits", "kp_batch_set_hits", "kp_batch_cigar_offsets", "kp_batch_cigars", "kp_batch_cs_offsets", "kp_batch_cs", "kp_format_paf", "kp_format_paf_tags", "kp_batch_stats", "kp_batch_profile", "kp_batch_anchors",
     "kp_batch_tasks", "kp_batch_task_results", "kp_batch_joins", "kp_db_load_typing", "kp_db_load_typing_group", "kp_batch_use_group", "kp_batch_score", "kp_batch_reduce", "kp_batch_typing_caps",
     "kp_device_count", "kp_device_numa_node", "kp_batch_typing", "kp_batch_proteins", "kp_protein_align", "kp_fasta_pack", "kp_fasta_ingest", "kp_fasta_ingest_many", "kp_fasta_ingest_file", "kp_fasta_ingest_shard", "kp_shard_words_into", "kp_shard_free", "kp_fasta_simd", "kp_pack_contigs",
     "kp_fasta_free", "kp_format_rows", "kp_format_json", "kp_format_fasta", "kp_protein_align_seeded", "kp_randstrobes", "kp_randstrobe_top_hits",
@@ -415,6 +415,45 @@ def format_paf(gene_names, gene_lengths, contig_names, contig_lengths, asm_first
             return out[:need].tobytes()
         out = np.empty(int(need), np.uint8)
     raise NativeError("kp_format_paf: size kept changing")
+
+
+PAF_CS, PAF_EQX = 1, 2  # KP_PAF_CS, KP_PAF_EQX
+
+
+def format_paf_tags(gene_names, gene_lengths, contig_names, contig_lengths, asm_first_ctg, hits, hit_off, ops, cigar_off, cs, cs_off,
+                    flags: int) -> bytes:
+    """``format_paf`` with what the cs strings add (kp_format_paf_tags): ``flags`` is ``PAF_CS`` (a ``cs:Z:`` tag behind ``cg:Z:``),
+    ``PAF_EQX`` (``cg:Z:`` in =/X form) or both; ``cs`` / ``cs_off`` as ``Batch.cs`` returns them.  A cs string that does not fit
+    its hit's ops raises ``ValueError``."""
+    gn_b, gn_o = _blob(gene_names)
+    cn_b, cn_o = _blob64(contig_names)
+    keep = dict(gene_len=_c(gene_lengths, np.int32), ctg_len=_c(contig_lengths, np.int32), first=_c(asm_first_ctg, np.int64),
+                hits=np.ascontiguousarray(hits, dtype=HIT_DTYPE), hit_off=_c(hit_off, np.int64),
+                ops=_c(ops, np.uint32), cigar_off=_c(cigar_off, np.int64), cs=_c(np.frombuffer(cs, np.uint8) if isinstance(cs, (bytes, bytearray)) else cs, np.uint8),
+                cs_off=_c(cs_off, np.int64))  # fmt: skip
+    n_asm = len(keep["hit_off"]) - 1
+    n_hits = len(keep["hits"])
+    if len(keep["first"]) != n_asm + 1 or len(keep["cigar_off"]) != n_hits + 1 or len(keep["cs_off"]) != n_hits + 1 or int(keep["hit_off"][-1]) != n_hits:
+        raise ValueError("offsets do not describe the hit table")
+    if int(keep["first"][-1]) > len(keep["ctg_len"]) or len(cn_o) != len(keep["ctg_len"]) + 1 or len(keep["gene_len"]) != len(gn_o) - 1:
+        raise ValueError("name and length tables disagree")
+    if int(keep["cs_off"][-1]) > len(keep["cs"]) or int(keep["cigar_off"][-1]) > len(keep["ops"]):
+        raise ValueError("offsets run past their arrays")
+    t = PafTables(gene_names=_p(gn_b).value, gene_name_off=_p(gn_o).value, gene_len=_p(keep["gene_len"]).value, n_genes=len(gn_o) - 1,
+                  ctg_names=_p(cn_b).value, ctg_name_off=_p(cn_o).value, ctg_len=_p(keep["ctg_len"]).value,
+                  asm_first_ctg=_p(keep["first"]).value)  # fmt: skip
+    h = lib()
+    h.kp_format_paf_tags.restype = C.c_int64
+    out = np.empty(max(4096, 176 * n_hits + 8 * len(keep["ops"]) + 2 * len(keep["cs"])), np.uint8)
+    for _ in range(2):
+        need = h.kp_format_paf_tags(C.byref(t), C.c_int32(n_asm), _p(keep["hits"]), _p(keep["hit_off"]), _p(keep["ops"]), _p(keep["cigar_off"]),
+                                    _p(keep["cs"]), _p(keep["cs_off"]), C.c_int32(int(flags)), _p(out), C.c_int64(len(out)))
+        if need < 0:
+            raise ValueError(f"kp_format_paf_tags failed ({need})")
+        if need <= len(out):
+            return out[:need].tobytes()
+        out = np.empty(int(need), np.uint8)
+    raise NativeError("kp_format_paf_tags: size kept changing")
 
 
 class JsonTables(C.Structure):  # kp_json_tables
@@ -854,6 +893,17 @@ class Batch:
         ops = np.zeros(int(off[-1]), np.uint32)
         self.ctx._check(lib().kp_batch_cigars(self.ctx._h, self._h, _p(ops), C.c_int64(len(ops))), "kp_batch_cigars")
         return ops, off
+
+    def cs(self) -> tuple[np.ndarray, np.ndarray]:
+        """(bytes uint8, offsets int64 [total hits + 1]): the cs string of row i of ``hits()`` is ``bytes[offsets[i]:offsets[i + 1]]``
+        (kp_batch_cs; include/kp_spec.h, CS).  Only for a batch aligned with the context's ``cs`` option set."""
+        hit_off = np.zeros(self.n_asm + 1, np.int64)
+        self.ctx._check(lib().kp_batch_hit_offsets(self.ctx._h, self._h, _p(hit_off)), "kp_batch_hit_offsets")
+        off = np.zeros(int(hit_off[-1]) + 1, np.int64)
+        self.ctx._check(lib().kp_batch_cs_offsets(self.ctx._h, self._h, _p(off)), "kp_batch_cs_offsets")
+        data = np.zeros(int(off[-1]), np.uint8)
+        self.ctx._check(lib().kp_batch_cs(self.ctx._h, self._h, _p(data), C.c_int64(len(data))), "kp_batch_cs")
+        return data, off
 
     def stats(self) -> dict[str, int]:
         s = np.zeros(5, np.int64)

@@ -108,12 +108,27 @@ def _add_outputs(p: argparse.ArgumentParser, tsv_flags, include_json: bool) -> N
                        help="Write serialised results to a newline-delimited JSON (default: %(const)s)")
         g.add_argument("--paf", metavar="FILE", default=argparse.SUPPRESS,  # (absent from the namespace unless given)
                        help="Write every gene hit (before the overlap cull, in the aligner's order) with its CIGAR as PAF lines to a file")
+        g.add_argument("--cs", action="store_true", default=argparse.SUPPRESS,
+                       help="With --paf: add a cs:Z: tag (minimap2's short form) that lists the differing bases of every hit")
+        g.add_argument("--eqx", action="store_true", default=argparse.SUPPRESS,
+                       help="With --paf: write the CIGARs with = and X ops in place of M")
     g.add_argument("--pha4ge", metavar="FILE", nargs="?", const="kaptive_results.pha4ge", type=Path,
                    help="Write PHA4GE-compliant serotyping report to a TSV file (default: %(const)s)")
 
 
+class _Parser(argparse.ArgumentParser):
+    """Reports options that only make sense beside another one as argparse reports any other error."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        for flag in ("cs", "eqx"):
+            if getattr(ns, flag, False) and not getattr(ns, "paf", None):
+                self.error(f"--{flag} requires --paf FILE")
+        return ns, rest
+
+
 def build_parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(prog="kaptive_amd", description="MI355X-native locus typing (Kaptive-compatible)")
+    ap = _Parser(prog="kaptive_amd", description="MI355X-native locus typing (Kaptive-compatible)")
     sub = ap.add_subparsers(dest="command", required=True)
     t = sub.add_parser("type", aliases=["assembly"], help="In silico serotyping of assemblies")
     t.add_argument("database", help="Database blob (.npz) or GenBank file with its .toml")
@@ -180,6 +195,7 @@ class _TypingPipeline:
         self.args = args
         self.marks = {"pipeline_start": time.perf_counter()}  # (KAPTIVE_AMD_CLI_TIMING: where the time before the first rows goes)
         self.want_paf = bool(getattr(args, "paf", None))  # every hit with its CIGAR: the alignment passes of this run leave them
+        self.paf_cs, self.paf_eqx = bool(getattr(args, "cs", False)), bool(getattr(args, "eqx", False))  # ... and its cs string
         self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins", "paf"))  # the files' text (and contig names) are kept
         self.fasta_outputs = any(getattr(args, f, None) for f in ("loci", "genes", "proteins"))  # ... and result objects are built
         self.threads = max(1, args.threads or usable_cpus())  # (the cgroup's quota, not the 256 CPUs a container may see)
@@ -257,6 +273,8 @@ class _TypingPipeline:
             raise
         if self.want_paf:
             self.engine.ctx.set_option("cigar", 1)  # (this run's context only)
+            if self.paf_cs or self.paf_eqx:
+                self.engine.ctx.set_option("cs", 1)
         self.marks["context_ready"] = time.perf_counter()
         self.want_tsv = bool(getattr(args, "out", None))
         # several databases: every chunk's outputs are ((keyword, outputs), ...), one entry per database in order
@@ -427,7 +445,7 @@ class _TypingPipeline:
         def render(bt, keyword=None, aligned=None, group=0) -> dict:
             out = {}
             if aligned is not None:
-                out["paf"] = hits_to_paf(self.engine.view(group), bt.genomes, *aligned)
+                out["paf"] = hits_to_paf(self.engine.view(group), bt.genomes, *aligned, cs_tag=self.paf_cs, eqx=self.paf_eqx)
             if self.want_tsv:
                 out["tsv"] = bt.tsv()
             if getattr(args, "pha4ge", None):
@@ -462,7 +480,7 @@ class _TypingPipeline:
 
         for bt, batch in stream:
             pb, batch._pin = getattr(batch, "_pin", None), None
-            aligned = (*batch.hits(), *batch.cigars()) if self.want_paf else None  # (the batch's results go with it)
+            aligned = (*batch.hits(), *batch.cigars(), *(batch.cs() if self.paf_cs or self.paf_eqx else ())) if self.want_paf else None  # (the batch's results go with it)
             batch.close()  # (waits for whatever of the batch is still in flight: the pinned words are free after it)
             if pb is not None:
                 self._give_back(pb)
@@ -532,12 +550,13 @@ class _ChunkSource:
         return batch, ids, genomes if pipe.objects else None
 
 
-def hits_to_paf(engine, genomes, hits, hit_off, ops, cigar_off) -> bytes:
+def hits_to_paf(engine, genomes, hits, hit_off, ops, cigar_off, cs=None, cs_off=None, cs_tag: bool = False, eqx: bool = False) -> bytes:
     """PAF lines (``--paf``) of a batch's hit table for the database ``engine`` views: its genes' hits of every genome, in
     the table's order, genomes in the batch's order.  Column-wise: the rows of the database are picked by a mask and the
-    lines come from one native call (``_native.format_paf``)."""
+    lines come from one native call (``_native.format_paf``; with ``--cs`` / ``--eqx`` ``_native.format_paf_tags``, which
+    takes the batch's cs bytes ``cs`` / ``cs_off`` as well)."""
     from kaptive_amd import _native
-    from kaptive_amd.core.alignment import Cigars
+    from kaptive_amd.core.alignment import Cigars, _ragged_take
 
     lo, hi = engine.gene_ranges[engine.group]
     keep = (hits["gene"] >= lo) & (hits["gene"] < hi)
@@ -546,11 +565,19 @@ def hits_to_paf(engine, genomes, hits, hit_off, ops, cigar_off) -> bytes:
         hit_off = kept_before[hit_off]
         cig = Cigars.from_offsets(ops, cigar_off)[keep]
         ops, cigar_off = cig.data, np.concatenate([[0], np.cumsum(cig.lengths, dtype=np.int64)])
+        if cs_off is not None:  # the cs bytes are sliced as the ops are
+            cs_off = np.asarray(cs_off, np.int64)
+            cs_len = np.diff(cs_off)
+            cs = _ragged_take(np.asarray(cs, np.uint8), cs_off[:-1], cs_len, np.flatnonzero(keep))[0]
+            cs_off = np.concatenate([[0], np.cumsum(cs_len[keep], dtype=np.int64)])
         hits = hits[keep].copy()
         hits["gene"] -= lo
     first = np.concatenate([[0], np.cumsum([len(g.contigs.ids) for g in genomes])])
     names = [n for g in genomes for n in g.contigs.ids]
     lengths = np.concatenate([np.asarray(g.contigs.lengths, np.int32) for g in genomes]) if genomes else np.zeros(0, np.int32)
+    if cs_tag or eqx:
+        return _native.format_paf_tags(engine.db.genes.ids, engine.db.genes.lengths, names, lengths, first, hits, hit_off, ops, cigar_off,
+                                       cs, cs_off, (_native.PAF_CS if cs_tag else 0) | (_native.PAF_EQX if eqx else 0))
     return _native.format_paf(engine.db.genes.ids, engine.db.genes.lengths, names, lengths, first, hits, hit_off, ops, cigar_off)
 
 

@@ -6,7 +6,10 @@ nothing is parsed per hit (the reference loops over hit objects, alignment.py:39
 BAM-encoded ops (``len << 4 | op``, M = 0, I = 1, D = 2: what the reference's ``parse_cigar_string`` produces,
 alignment.py:872) when the aligner was asked for them (``Engine(db, cigar=True)``: the device walks every path a second
 time, include/kp_spec.h, CIGAR); the typing path never reads them, so by default they are not
-computed and the column is empty.  ``to_paf`` writes a table with its CIGARs as PAF lines.  The reference's CIGAR string
+computed and the column is empty.  The ``cs`` column, which the reference's class carries and never fills, holds one ``bytes``
+per hit -- minimap2's short-form difference string (include/kp_spec.h, CS) -- with ``Engine(db, cs=True)`` and ``None``
+otherwise; ``Cigars.from_cs`` turns such strings into =/X CIGARs.  ``to_paf`` writes a table with its CIGARs (and, on request,
+its cs strings) as PAF lines.  The reference's CIGAR string
 parser, ``swap_sides`` and ``best`` have no counterpart here.
 
 The reductions used by typing (``q_covs``, ``cull_overlaps``, ``is_partial``) follow
@@ -92,6 +95,44 @@ class Cigars:
         if len(lengths) > 1:
             np.cumsum(lengths[:-1], out=offsets[1:])
         return cls(np.concatenate([b.data for b in bs]).astype(np.uint32), offsets, lengths)
+
+    @classmethod
+    def from_cs(cls, cs_bytes, offsets: np.ndarray) -> "Cigars":
+        """The =/X CIGARs that cs strings stand for (include/kp_spec.h, CS): ``:n`` is ``n=``, a run of k ``*`` tokens ``kX``,
+        ``+`` and ``-`` are I and D.  Row i is ``cs_bytes[offsets[i]:offsets[i + 1]]`` (what ``_native.Batch.cs`` returns, or a
+        slice of it).  Column-wise: no loop over hits or tokens."""
+        b = np.frombuffer(cs_bytes, np.uint8) if isinstance(cs_bytes, (bytes, bytearray)) else np.asarray(cs_bytes, np.uint8)
+        offsets = np.asarray(offsets, np.int64)
+        n = len(offsets) - 1
+        lo, hi = (int(offsets[0]), int(offsets[-1])) if n >= 0 and len(offsets) else (0, 0)
+        b = b[lo:hi]
+        is_start = (b == 58) | (b == 42) | (b == 43) | (b == 45)  # : * + -
+        starts = np.flatnonzero(is_start)
+        if len(starts) == 0:
+            return cls.empty(max(n, 0))
+        ends = np.append(starts[1:], len(b))
+        kind = b[starts]
+        tok = np.cumsum(is_start) - 1  # the token every byte belongs to
+        digit = (b >= 48) & (b <= 57) & (kind[tok] == 58)
+        value = np.zeros(len(starts), np.int64)
+        at = np.flatnonzero(digit)
+        np.add.at(value, tok[at], (b[at].astype(np.int64) - 48) * 10 ** (ends[tok[at]] - 1 - at))
+        length = np.where(kind == 58, value, np.where(kind == 42, 1, ends - starts - 1))
+        code = np.select([kind == 58, kind == 42, kind == 43], [7, 8, 1], 2)
+        row = np.searchsorted(offsets - lo, starts, side="right") - 1
+        first = np.ones(len(starts), np.bool_)  # a * token behind a * token of the same hit lengthens its X op
+        first[1:] = ~((kind[1:] == 42) & (kind[:-1] == 42) & (row[1:] == row[:-1]))
+        heads = np.flatnonzero(first)
+        ops = ((np.add.reduceat(length, heads) << 4) | code[heads]).astype(np.uint32)
+        lengths = np.bincount(row[heads], minlength=n).astype(np.int32)
+        off = np.zeros(n, np.int64)
+        if n > 1:
+            np.cumsum(lengths[:-1], out=off[1:])
+        return cls(ops, off, lengths)
+
+    def strings(self) -> list[str]:
+        """``to_strings``: M, I, D, and the ``=`` and ``X`` of a CIGAR made ``from_cs``."""
+        return self.to_strings()
 
     def to_strings(self) -> list[str]:
         """The CIGARs as text ("120M1I35M"); for display and tests -- bulk output goes through ``Alignments.to_paf``."""
@@ -186,6 +227,7 @@ class Alignments:
         scores: np.ndarray,
         mapqs: np.ndarray,
         cigars: "Cigars | None" = None,
+        cs: "np.ndarray | None" = None,
     ) -> "Alignments":
         """Wrap columns produced by the native aligner. ``q_ids``/``t_ids`` index ``q_names``/``t_names`` directly
         (the native path numbers contigs by their order in the assembly, not by first appearance in the hits)."""
@@ -206,7 +248,7 @@ class Alignments:
             mismatches=(block_lens - matches).astype(np.int32), scores=np.asarray(scores, np.int32),
             qualities=np.asarray(mapqs, np.uint8), cigars=Cigars.empty(n) if cigars is None else cigars,
             is_primary=primary, is_supplementary=np.zeros(n, np.bool_), is_spliced=np.zeros(n, np.bool_),
-            divergence=div.astype(np.float64), cs=np.full(n, None, dtype=object), md=np.full(n, None, dtype=object),
+            divergence=div.astype(np.float64), cs=np.full(n, None, dtype=object) if cs is None else cs, md=np.full(n, None, dtype=object),
         )  # fmt: skip
 
     @classmethod
@@ -272,11 +314,13 @@ class Alignments:
             q_names_dict=self.q_names_dict, t_names_dict=self.t_names_dict, cigars=self.cigars[item], **cols
         )
 
-    def to_paf(self, q_names: "tuple[str, ...] | None" = None) -> bytes:
+    def to_paf(self, q_names: "tuple[str, ...] | None" = None, cs: bool = False, eqx: bool = False) -> bytes:
         """The table as PAF lines, one per hit in the table's order (kp_format_paf, include/kaptive_amd.h): query name and
         length, q_start, q_end, strand, target name and length, t_start, t_end, matches, block length, mapq, ``AS:i``,
         ``NM:i`` (block length - matches) and ``cg:Z`` with the CIGAR -- empty where the table carries none.  ``q_names``
-        replaces ``q_names_dict`` (the engine numbers genes; the command line passes the database's gene names)."""
+        replaces ``q_names_dict`` (the engine numbers genes; the command line passes the database's gene names).  ``cs``: a
+        ``cs:Z:`` tag with the ``cs`` column follows; ``eqx``: ``cg:Z:`` is written in =/X form, derived from the ``cs`` column
+        (kp_format_paf_tags).  Both need a table whose ``cs`` column is filled (``Engine(db, cs=True)``)."""
         from kaptive_amd import _native
 
         n = len(self)
@@ -293,7 +337,14 @@ class Alignments:
         cig = self.cigars[:] if len(self.cigars) == n and n else Cigars.empty(n)
         off = np.zeros(n + 1, np.int64)
         np.cumsum(cig.lengths, out=off[1:])
-        return _native.format_paf(names, q_len, self.t_names_dict, t_len, [0, len(self.t_names_dict)], hits, [0, n], cig.data, off)
+        if not (cs or eqx):
+            return _native.format_paf(names, q_len, self.t_names_dict, t_len, [0, len(self.t_names_dict)], hits, [0, n], cig.data, off)
+        if any(c is None for c in self.cs):
+            raise ValueError("this table carries no cs strings (Engine(db, cs=True) fills them)")
+        cs_off = np.zeros(n + 1, np.int64)
+        np.cumsum([len(c) for c in self.cs], out=cs_off[1:])
+        return _native.format_paf_tags(names, q_len, self.t_names_dict, t_len, [0, len(self.t_names_dict)], hits, [0, n], cig.data, off,
+                                       b"".join(self.cs), cs_off, (_native.PAF_CS if cs else 0) | (_native.PAF_EQX if eqx else 0))
 
     @property
     def q_names(self) -> np.ndarray:

@@ -147,7 +147,8 @@ int kp_batch_align(kp_ctx *ctx, kp_batch *b) {
     }
     kp_caps_size(ctx->opt, ctx->learnt, b->n_asm, b->view.total_words, *w);
     w->aligned = false; w->finalised = false;
-    w->cigar_on = ctx->opt.cigar != 0; w->cigar_valid = false;
+    w->cs_on = ctx->opt.cs != 0; w->cs_valid = false;
+    w->cigar_on = ctx->opt.cigar != 0 || w->cs_on; w->cigar_valid = false;  // (cs reads the ops)
     for (auto &v : w->h_tasks) v.clear();
     for (auto &r : w->runs)
         if (r) { r->split = false; r->scored = false; r->reduced = false; r->sums_valid = false; }
@@ -224,6 +225,35 @@ static int emit_cigars(kp_ctx *ctx, kp_batch *b, KpWork *w) {
     return KP_OK;
 }
 
+// cs strings of the finished hits (kp_cs.hip), on the post stream behind emit_cigars -- whose ops are final by now, a grown and
+// rewritten buffer included.  Bytes counted, scanned and written; the byte buffer follows the policy of kp_caps.h, and where it was
+// too small only the writing kernel runs again: counts and offsets are exact whatever the buffer held.
+static int emit_cs(kp_ctx *ctx, kp_batch *b, KpWork *w) {
+    const size_t n_asm = (size_t)b->n_asm;
+    const int64_t total = w->hit_off[n_asm];
+    w->cs_cap = kp_caps_cs_size(ctx->cs_caps, (uint64_t)total);
+    KP_HIP_CHECK(ctx, w->d_cs_cnt.reserve((size_t)total));
+    KP_HIP_CHECK(ctx, w->d_cs_off.reserve((size_t)total + 1));
+    KP_HIP_CHECK(ctx, w->d_cs_bytes.reserve(w->cs_cap));
+    const uint32_t *n_hits = w->d_hit_counts.p + n_asm;
+    kp_launch_cs_count(b->view, ctx->genes, w->d_hits.p, n_hits, w->hit_cap, w->d_cig_hit_off.p, w->d_cig_ops.p, w->d_cig_off.p, (int64_t)w->cigar_cap,
+                       w->d_cs_cnt.p, total, w->d_cs_off.p, ctx->post);
+    for (int attempt = 0;; ++attempt) {
+        kp_launch_cs_emit(b->view, ctx->genes, w->d_hits.p, n_hits, w->hit_cap, w->d_cig_hit_off.p, w->d_cig_ops.p, w->d_cig_off.p, (int64_t)w->cigar_cap,
+                          w->d_cs_off.p, w->d_cs_bytes.p, (int64_t)w->cs_cap, ctx->post);
+        KP_HIP_CHECK(ctx, hipGetLastError());
+        int64_t need = 0;
+        if (int frc = fetch_all(ctx, ctx->post, {{&need, w->d_cs_off.p + total, sizeof need}})) return frc;
+        w->cs_total = need;
+        if (kp_caps_after_cs(ctx->cs_caps, w->cs_cap, (uint64_t)total, (uint64_t)need)) break;
+        if (attempt >= 1) return kp_fail(ctx, KP_EOVERFLOW, "cs buffer overflowed repeatedly");
+        KP_HIP_CHECK(ctx, w->d_cs_bytes.reserve(w->cs_cap));
+    }
+    w->cs_valid = true;
+    return KP_OK;
+}
+
+static const char *const NO_CS = "this batch has no cs strings (aligned without the cs option, or its hit table was replaced)";
 static const char *const NO_CIGARS = "this batch has no CIGARs (aligned without the cigar option, or its hit table was replaced)";
 
 int kp_batch_wait(kp_ctx *ctx, kp_batch *b) {
@@ -270,6 +300,8 @@ int kp_batch_wait(kp_ctx *ctx, kp_batch *b) {
     w->stats[0] = n_anchor; w->stats[1] = n_task; w->stats[3] = w->hit_off[n_asm];
     if (w->cigar_on)
         if (int crc = emit_cigars(ctx, b, w)) return crc;
+    if (w->cs_on)
+        if (int crc = emit_cs(ctx, b, w)) return crc;
     w->finalised = true;
     return KP_OK;
 }
@@ -328,7 +360,7 @@ int kp_batch_set_hits(kp_ctx *ctx, kp_batch *b, const kp_hit *hits, const int64_
     if (n_asm)
         KP_HIP_CHECK(ctx, hipMemcpy(w->d_hit_counts.p + n_asm, w->h_hit_counts.data() + n_asm, n_asm * sizeof(uint32_t), hipMemcpyHostToDevice));
     w->stats[3] = w->hit_off[n_asm];
-    w->cigar_valid = false;  // (they described the table that has just been replaced)
+    w->cigar_valid = false; w->cs_valid = false;  // (they described the table that has just been replaced)
     for (auto &r : w->runs)
         if (r) { r->split = false; r->scored = false; r->reduced = false; r->sums_valid = false; }
     return KP_OK;
@@ -354,6 +386,31 @@ int kp_batch_cigars(kp_ctx *ctx, kp_batch *b, uint32_t *ops, int64_t cap) {
     KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     if (w->cigar_total > 0) {
         KP_HIP_CHECK(ctx, hipMemcpyAsync(ops, w->d_cig_ops.p, (size_t)w->cigar_total * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->post));
+        KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->post));
+    }
+    return KP_OK;
+}
+
+int kp_batch_cs_offsets(kp_ctx *ctx, kp_batch *b, int64_t *cs_off) {
+    if (!ctx || !b || b->ctx != ctx || !cs_off) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    if (!w->cs_valid) return kp_fail(ctx, KP_ESTATE, NO_CS);
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    KP_HIP_CHECK(ctx, hipMemcpyAsync(cs_off, w->d_cs_off.p, ((size_t)w->hit_off[(size_t)b->n_asm] + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->post));
+    KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->post));
+    return KP_OK;
+}
+
+int kp_batch_cs(kp_ctx *ctx, kp_batch *b, char *bytes, int64_t cap) {
+    if (!ctx || !b || b->ctx != ctx || (!bytes && cap > 0)) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    if (!w->cs_valid) return kp_fail(ctx, KP_ESTATE, NO_CS);
+    if (cap < w->cs_total) return kp_fail(ctx, KP_EINVAL, "cs buffer too small");
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (w->cs_total > 0) {
+        KP_HIP_CHECK(ctx, hipMemcpyAsync(bytes, w->d_cs_bytes.p, (size_t)w->cs_total, hipMemcpyDeviceToHost, ctx->post));
         KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->post));
     }
     return KP_OK;

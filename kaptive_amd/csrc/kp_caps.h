@@ -172,6 +172,39 @@ inline bool kp_caps_after_cigar(KpLearnt &L, uint64_t &cap, uint64_t total_hits,
     return false;
 }
 
+// cs strings (kp_cs.hip; only with the `cs` option): the same policy for their bytes, with its option and what the context has
+// learnt in a pair of their own.  The walk counts every hit's bytes before it writes them, so `need` is exact however small the
+// buffer was.
+struct KpCsCaps {
+    // first guess for the bytes of a pass's cs strings, per hit.  Not measured when it was chosen: a clean hit is 5 bytes (":1234")
+    // and a hit of 1000 columns at 1 % divergence about 75, so 64 is a guess between them; a batch that needs more grows the buffer once
+    uint32_t bytes_per_hit = 64;
+    uint32_t learnt = 0;  // cs byte buffer of a pass = its hits * this many bytes (0: not yet sized); only grows
+};
+inline uint64_t kp_caps_cs_size(KpCsCaps &c, uint64_t total_hits) {
+    if (c.learnt == 0) c.learnt = std::max<uint32_t>(c.bytes_per_hit, 1u);
+    return std::max<uint64_t>(total_hits, 1) * c.learnt;
+}
+// true: the bytes fitted (what came close makes room for later passes); false: `cap` has grown -- write the bytes again, nothing else
+inline bool kp_caps_after_cs(KpCsCaps &c, uint64_t &cap, uint64_t total_hits, uint64_t need) {
+    const uint64_t hits = std::max<uint64_t>(total_hits, 1);
+    auto per_hit = [&](uint64_t bytes) { return (uint32_t)std::min<uint64_t>((bytes + hits - 1) / hits, 0xFFFFFFFFu); };
+    if (need <= cap) {
+        if (need + need / 8 > cap) c.learnt = std::max(c.learnt, per_hit(need + need / 4));
+        return true;
+    }
+    cap = need + need / 4;  // later batches differ a little
+    c.learnt = std::max(c.learnt, per_hit(cap));
+    return false;
+}
+// kp_ctx_set_option of `cs_bytes_per_hit` (false: `name` is something else): it also resets what the context has learnt
+inline bool kp_caps_set_cs_option(KpCsCaps &c, const std::string &n, int64_t value) {
+    if (n != "cs_bytes_per_hit") return false;
+    c.bytes_per_hit = (uint32_t)std::max<int64_t>(std::min<int64_t>(value, 0xFFFFFFFFll), 1);
+    c.learnt = 0;
+    return true;
+}
+
 // overflow flags of a reduction (KpAsmSummary::overflow: 1 kept hits, 2 pieces, 8 proteins); false: `err` says what cannot grow
 inline bool kp_caps_grow_run(KpRunCaps &c, int flags, std::string &err) {
     if (flags & 1) {

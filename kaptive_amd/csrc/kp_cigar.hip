@@ -13,7 +13,7 @@
 //                       (kp_walk.h) with a visitor that merges columns of one kind into run-length ops; first to count the ops
 //                       of every hit, then -- after an exclusive scan of the counts -- to write them, last op first, since
 //                       the walk runs from the path's end to its start and ops are listed along the target
-//   kp_cigar_scan       the exclusive scan, one block (a million hits are a few microseconds of it)
+//   kp_cigar_scan       the exclusive scan, one block (measured: 3.7 ms for 1.16 M hits -- DESIGN.md section 3; kp_cs.hip scans its byte counts with it)
 //
 // The ops buffer is sized by the policy of kp_caps.h; the writing pass checks every store against its end, so a buffer that is
 // too small loses ops but nothing else, and the counts say how much room the repeat needs.
@@ -188,6 +188,11 @@ void kp_launch_cigar_locate(const KpBatchView &b, const int32_t *gene_len, const
                        task_cap, hits, n_hits, hit_cap, src);
     hipLaunchKernelGGL(kp_cigar_locate_joins_kernel, dim3(16, KP_N_CLASSES), dim3(64), 0, stream, b, gene_len, joins, join_count, join_cap, hits,
                        n_hits, hit_cap, src);
+}
+
+// off[0 .. n] = exclusive scan of cnt[0 .. n): the scan above for any per-hit counts (kp_cs.hip: bytes of the cs strings)
+void kp_launch_count_scan(const uint32_t *cnt, int64_t n, int64_t *off, hipStream_t stream) {
+    hipLaunchKernelGGL(kp_cigar_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, cnt, n, off);
 }
 
 static dim3 walk_grid(const KpBatchView &b) { return dim3((unsigned)std::min(std::max(b.n_asm, 1), 4096)); }

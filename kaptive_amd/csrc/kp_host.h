@@ -65,6 +65,7 @@ struct KpOptions : KpCapOptions {
     int readback_copy_engine = 0;   // results read back with hipMemcpyAsync instead of the read-back kernel (see Fetch)
     int spin_wait = 0;              // host waits spin on the stream (the runtime's default) instead of blocking on an interrupt
     int cigar = 0;                  // CIGARs of the finished hits (kp_cigar.hip): off unless asked for; applies from the next kp_batch_align
+    int cs = 0;                     // cs difference strings of the finished hits (kp_cs.hip); a pass with it computes the CIGARs too: cs reads them
     bool join_stats = false;        // KAPTIVE_AMD_JOIN_STATS: kp_batch_wait reports the pass's group / join / mid_occ counts on stderr
 };
 
@@ -130,6 +131,13 @@ struct KpWork : KpPassCaps {
     DevBuf<unsigned long long> d_cig_src;  // per row of the hit tables: the source of the hit (kp_cigar.hip: src_key)
     DevBuf<uint32_t> d_cig_cnt, d_cig_ops;
     DevBuf<int64_t> d_cig_off, d_cig_hit_off;  // [total_hits + 1] first op of every hit; [n_asm + 1] the host's hit_off
+    // cs strings of the finished hits (kp_cs.hip), only where the pass was enqueued with the `cs` option; results with the CIGARs' lifetime
+    bool cs_on = false, cs_valid = false;
+    uint64_t cs_cap = 0;             // bytes d_cs_bytes was sized for
+    int64_t cs_total = 0;            // bytes of all hits
+    DevBuf<uint32_t> d_cs_cnt;
+    DevBuf<int64_t> d_cs_off;        // [total_hits + 1] first byte of every hit
+    DevBuf<char> d_cs_bytes;
     // reduction: one run per typing group, created on first use
     std::vector<std::unique_ptr<KpTypingRun>> runs;
     // results
@@ -156,6 +164,7 @@ struct kp_ctx {
     std::string error;
     KpOptions opt;
     KpLearnt learnt;
+    KpCsCaps cs_caps;  // byte buffer of the cs strings: option and learnt size (kp_caps.h)
     // resident database
     bool has_db = false;
     int32_t n_genes = 0;

@@ -282,6 +282,16 @@ void kp_launch_cigar_count(const KpBatchView &b, const KpGenes &genes, const KpT
 void kp_launch_cigar_emit(const KpBatchView &b, const KpGenes &genes, const KpTask *tasks, const KpSwEnd *ends, uint32_t task_cap, const KpJoin *joins,
                           uint32_t join_cap, const void *trace, const uint32_t *n_hits, uint32_t hit_cap, const int64_t *hit_off,
                           const unsigned long long *src, const int64_t *off, uint32_t *ops, int64_t ops_cap, hipStream_t stream);
+void kp_launch_count_scan(const uint32_t *cnt, int64_t n, int64_t *off, hipStream_t stream);  // kp_cigar.hip's scan, for any per-hit counts
+// kp_cs.hip (only with the `cs` option; after the CIGAR ops are final): the bytes of every hit's cs string (kp_spec.h, CS) counted
+// (cnt, rows as kp_batch_hits lists them) and scanned (off[total_hits + 1]), and the bytes written forward from off[row] -- stores
+// beyond bytes_cap are dropped.  ops / cigar_off: what kp_launch_cigar_emit left; nothing here reads the trace buffer.
+void kp_launch_cs_count(const KpBatchView &b, const KpGenes &genes, const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap,
+                        const int64_t *hit_off, const uint32_t *ops, const int64_t *cigar_off, int64_t ops_cap, uint32_t *cnt,
+                        int64_t total_hits, int64_t *off, hipStream_t stream);
+void kp_launch_cs_emit(const KpBatchView &b, const KpGenes &genes, const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap,
+                       const int64_t *hit_off, const uint32_t *ops, const int64_t *cigar_off, int64_t ops_cap, const int64_t *off,
+                       char *bytes, int64_t bytes_cap, hipStream_t stream);
 // kp_prot.hip
 // kp_reduce.hip: assembly a's hits with gene in [gene_lo, gene_hi) (one run: hits are sorted by gene) -> out rows, gene
 // indices relative to gene_lo; out_n[a] = how many

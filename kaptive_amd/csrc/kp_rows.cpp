@@ -169,12 +169,52 @@ inline void put_i(Out &o, long long v) {
     else put_u(o, (unsigned long long)v);
 }
 
-}  // namespace
+// cs string of one hit (kp_spec.h, CS) checked against its ops: grammar, canonical form, column totals.  With `eqx` the =/X
+// CIGAR it stands for goes to `o`.
+bool cs_check(const char *cs, int64_t n, const uint32_t *ops, int64_t n_ops, Out *eqx) {
+    long long want[3] = {0, 0, 0}, got[3] = {0, 0, 0};
+    for (int64_t z = 0; z < n_ops; ++z) {
+        if ((ops[z] & 15u) > KP_CIGAR_D) return false;
+        want[ops[z] & 15u] += ops[z] >> KP_CIGAR_SHIFT;
+    }
+    auto base = [](char c) { return c == 'a' || c == 'c' || c == 'g' || c == 't' || c == 'n'; };
+    char prev = 0;
+    for (int64_t i = 0; i < n;) {
+        const char kind = cs[i++];
+        if (kind == ':') {
+            unsigned long long v = 0;
+            const int64_t i0 = i;
+            for (; i < n && cs[i] >= '0' && cs[i] <= '9' && i - i0 < 10; ++i) v = v * 10 + (unsigned)(cs[i] - '0');
+            if (i == i0 || cs[i0] == '0' || prev == ':') return false;  // no number, :0 or a leading zero, two : tokens touching
+            got[KP_CIGAR_M] += (long long)v;
+            if (eqx) { put_u(*eqx, v); eqx->put('='); }
+        } else if (kind == '*') {
+            if (i + 2 > n || !base(cs[i]) || !base(cs[i + 1])) return false;
+            i += 2;
+            got[KP_CIGAR_M] += 1;
+            if (eqx) {  // a run of * tokens is one X op
+                unsigned long long k = 1;
+                for (; i + 3 <= n && cs[i] == '*' && base(cs[i + 1]) && base(cs[i + 2]); i += 3) { ++k; got[KP_CIGAR_M] += 1; }
+                put_u(*eqx, k); eqx->put('X');
+            }
+        } else if (kind == '+' || kind == '-') {
+            const int64_t i0 = i;
+            while (i < n && base(cs[i])) ++i;
+            if (i == i0) return false;
+            got[kind == '+' ? KP_CIGAR_I : KP_CIGAR_D] += i - i0;
+            if (eqx) { put_u(*eqx, (unsigned long long)(i - i0)); eqx->put(kind == '+' ? 'I' : 'D'); }
+        } else return false;
+        prev = kind;
+    }
+    return got[0] == want[0] && got[1] == want[1] && got[2] == want[2];
+}
 
-extern "C" int64_t kp_format_paf(const kp_paf_tables *t, int32_t n_asm, const kp_hit *hits, const int64_t *hit_off, const uint32_t *ops,
-                                 const int64_t *cigar_off, char *out, int64_t cap) {
+int64_t format_paf(const kp_paf_tables *t, int32_t n_asm, const kp_hit *hits, const int64_t *hit_off, const uint32_t *ops,
+                   const int64_t *cigar_off, const char *cs, const int64_t *cs_off, int32_t flags, char *out, int64_t cap) {
     if (!t || n_asm < 0 || !hit_off || !cigar_off || cap < 0 || (cap > 0 && !out)) return KP_EINVAL;
     if (n_asm > 0 && (!t->asm_first_ctg || hit_off[n_asm] < hit_off[0] || (hit_off[n_asm] > 0 && !hits))) return KP_EINVAL;
+    if (flags & ~(KP_PAF_CS | KP_PAF_EQX)) return KP_EINVAL;
+    if (flags && !cs_off) return KP_EINVAL;
     Out o{out, cap};
     for (int a = 0; a < n_asm; ++a) {
         const int64_t c0 = t->asm_first_ctg[a], nc = t->asm_first_ctg[a + 1] - c0;
@@ -183,6 +223,7 @@ extern "C" int64_t kp_format_paf(const kp_paf_tables *t, int32_t n_asm, const kp
             if (h.gene < 0 || h.gene >= t->n_genes || h.contig < 0 || h.contig >= nc) return KP_EINVAL;
             const int64_t c = c0 + h.contig;
             if (cigar_off[i + 1] < cigar_off[i] || (cigar_off[i + 1] > cigar_off[i] && !ops)) return KP_EINVAL;
+            if (flags && (cs_off[i + 1] < cs_off[i] || (cs_off[i + 1] > cs_off[i] && !cs))) return KP_EINVAL;
             o.put(t->gene_names + t->gene_name_off[h.gene], t->gene_name_off[h.gene + 1] - t->gene_name_off[h.gene]); o.put('\t');
             put_i(o, t->gene_len[h.gene]); o.put('\t');
             put_i(o, h.q_start); o.put('\t');
@@ -197,12 +238,29 @@ extern "C" int64_t kp_format_paf(const kp_paf_tables *t, int32_t n_asm, const kp
             put_u(o, h.mapq); o.lit("\tAS:i:");
             put_i(o, h.score); o.lit("\tNM:i:");
             put_i(o, (long long)h.block_len - h.matches); o.lit("\tcg:Z:");
-            for (int64_t z = cigar_off[i]; z < cigar_off[i + 1]; ++z) {
-                put_u(o, ops[z] >> 4);
-                o.put("MIDNSHP=XB??????"[ops[z] & 15u]);
-            }
+            const char *s = flags ? cs + cs_off[i] : nullptr;
+            const int64_t ns = flags ? cs_off[i + 1] - cs_off[i] : 0;
+            if (flags && !cs_check(s, ns, ops + cigar_off[i], cigar_off[i + 1] - cigar_off[i], (flags & KP_PAF_EQX) ? &o : nullptr)) return KP_EINVAL;
+            if (!(flags & KP_PAF_EQX))
+                for (int64_t z = cigar_off[i]; z < cigar_off[i + 1]; ++z) {
+                    put_u(o, ops[z] >> 4);
+                    o.put("MIDNSHP=XB??????"[ops[z] & 15u]);
+                }
+            if (flags & KP_PAF_CS) { o.lit("\tcs:Z:"); o.put(s, ns); }
             o.put('\n');
         }
     }
     return o.n;
+}
+
+}  // namespace
+
+extern "C" int64_t kp_format_paf(const kp_paf_tables *t, int32_t n_asm, const kp_hit *hits, const int64_t *hit_off, const uint32_t *ops,
+                                 const int64_t *cigar_off, char *out, int64_t cap) {
+    return format_paf(t, n_asm, hits, hit_off, ops, cigar_off, nullptr, nullptr, 0, out, cap);
+}
+
+extern "C" int64_t kp_format_paf_tags(const kp_paf_tables *t, int32_t n_asm, const kp_hit *hits, const int64_t *hit_off, const uint32_t *ops,
+                                      const int64_t *cigar_off, const char *cs, const int64_t *cs_off, int32_t flags, char *out, int64_t cap) {
+    return format_paf(t, n_asm, hits, hit_off, ops, cigar_off, cs, cs_off, flags, out, cap);
 }

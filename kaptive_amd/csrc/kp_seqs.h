@@ -67,3 +67,9 @@ struct KpQuerySeq {
     int len;
     KP_HD int code(int r) const { return (int)kp_nib(nib[r >> 3], r & 7); }
 };
+
+// the two sequences of a band task, a join or a finished hit: the gene's strand as aligned and the contig (kp_walk.h: kp_task_seqs)
+struct KpTaskSeqs {
+    KpQuerySeq q;
+    KpTargetSeq t;
+};

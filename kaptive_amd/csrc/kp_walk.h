@@ -22,10 +22,7 @@ struct KpNoVisit {
 };
 
 // ---- the two sequences of a band task or a join ------------------------------------------------------------------------------
-struct KpTaskSeqs {
-    KpQuerySeq q;
-    KpTargetSeq t;
-};
+// (KpTaskSeqs itself: kp_seqs.h)
 __device__ __forceinline__ KpTaskSeqs kp_task_seqs(const KpBatchView &b, const KpGenes &genes, int asm_id, int gs, int contig) {
     KpTaskSeqs s;
     const int gene = gs >> 1, c_abs = b.asm_first_ctg[asm_id] + contig, r0 = b.asm_first_nrun[asm_id];

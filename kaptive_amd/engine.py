@@ -30,20 +30,25 @@ class Engine:
     single-genome entry points (``align``, ``hits_to_alignments``) are those of a one-database engine."""
 
     def __init__(self, db: "Database | Sequence[Database]", device: int = 0, ctx: "_native.Context | None" = None,
-                 cigar: bool = False) -> None:
+                 cigar: bool = False, cs: bool = False) -> None:
         """``ctx``: a context of ``device`` the caller created ahead of time (the command line starts the runtime on a thread
         of its own while the database file is still being read); otherwise one is created here.  ``cigar``: alignment passes
         also leave the CIGAR of every hit (``Batch.cigars``; ``align`` then fills ``Alignments.cigars``) -- a second walk of
-        every path on the device, off by default because typing never reads them."""
+        every path on the device, off by default because typing never reads them.  ``cs``: they also leave the cs difference
+        string of every hit (``Batch.cs``; include/kp_spec.h, CS) and, since those are read off the ops, the CIGARs: ``align``
+        fills ``Alignments.cs`` and ``Alignments.cigars``."""
         dbs = list(db) if isinstance(db, (list, tuple)) else [db]
         self.dbs = dbs
         self.db = dbs[0]
         self.group = 0
         self.device = device
         self.ctx = ctx if ctx is not None else _native.Context(device)
-        self.cigar = bool(cigar)
+        self.cs = bool(cs)
+        self.cigar = bool(cigar) or self.cs
         if self.cigar:
             self.ctx.set_option("cigar", 1)
+        if self.cs:
+            self.ctx.set_option("cs", 1)
         for d in dbs:  # KP_MAX_GENE_LEN (include/kp_spec.h): query positions are 16-bit fields of the anchor and hit keys
             too_long = np.flatnonzero(np.asarray(d.genes.lengths) > _native.MAX_GENE_LEN)
             if len(too_long):
@@ -88,8 +93,10 @@ class Engine:
         finally:
             batch.close()
 
-    def hits_to_alignments(self, genome: GenomeAssembly, hits: np.ndarray, cigars: "Cigars | None" = None) -> Alignments:
-        """``cigars``: the CIGARs of ``hits``, row for row (``Cigars.from_offsets`` of a slice of ``Batch.cigars``)."""
+    def hits_to_alignments(self, genome: GenomeAssembly, hits: np.ndarray, cigars: "Cigars | None" = None,
+                           cs: "np.ndarray | None" = None) -> Alignments:
+        """``cigars``: the CIGARs of ``hits``, row for row (``Cigars.from_offsets`` of a slice of ``Batch.cigars``); ``cs``:
+        their cs strings, an object array of ``bytes``."""
         if len(hits) == 0:
             return Alignments.empty()
         db = self.db
@@ -98,7 +105,7 @@ class Engine:
             q_ids=hits["gene"], q_lengths=db.genes.lengths[hits["gene"]], q_starts=hits["q_start"],
             q_ends=hits["q_end"], t_ids=hits["contig"], t_lengths=genome.contigs.lengths[hits["contig"]],
             t_starts=hits["t_start"], t_ends=hits["t_end"], strands=hits["strand"], block_lens=hits["block_len"],
-            matches=hits["matches"], scores=hits["score"], mapqs=hits["mapq"], cigars=cigars,
+            matches=hits["matches"], scores=hits["score"], mapqs=hits["mapq"], cigars=cigars, cs=cs,
         )  # fmt: skip
 
     def align(self, genomes: Sequence[GenomeAssembly]) -> list[Alignments]:
@@ -108,10 +115,16 @@ class Engine:
         try:
             hits, off = batch.align()
             ops, coff = batch.cigars() if self.cigar else (None, None)
+            cs_data, cs_off = batch.cs() if self.cs else (None, None)
         finally:
             batch.close()
+        cs_rows = None
+        if self.cs:  # one bytes object per hit, as the reference's column holds them
+            blob, cs_rows = cs_data.tobytes(), np.empty(len(hits), dtype=object)
+            cs_rows[:] = [blob[cs_off[i] : cs_off[i + 1]] for i in range(len(hits))]
         return [self.hits_to_alignments(g, hits[off[i] : off[i + 1]],
-                                        Cigars.from_offsets(ops, coff[off[i] : off[i + 1] + 1]) if self.cigar else None)
+                                        Cigars.from_offsets(ops, coff[off[i] : off[i + 1] + 1]) if self.cigar else None,
+                                        cs_rows[off[i] : off[i + 1]] if self.cs else None)
                 for i, g in enumerate(genomes)]  # fmt: skip
 
     def protein_aligner(self, queries: Sequences, targets: Sequences) -> PairwiseAlignments:
