@@ -36,7 +36,7 @@ constexpr int BS_TILE = 1024;     // keys per LDS tile of the block-wide pass
 #define KP_BS_HUGE_LIST 64
 #endif
 constexpr int BS_BIG_LIST = KP_BS_BIG_LIST; // buckets of BS_RANK_MAX + 1 .. BS_STAGE keys remembered for the shared pass (more: sorted where they are met)
-constexpr int BS_HUGE_LIST = KP_BS_HUGE_LIST;  // buckets larger than BS_STAGE remembered for the block-wide pass (more: ranked in place, slowly)
+constexpr int BS_HUGE_LIST = KP_BS_HUGE_LIST;  // buckets larger than BS_STAGE remembered for the block-wide pass (more: that pass walks the buckets instead)
 
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -298,15 +298,7 @@ __global__ __launch_bounds__(BS_THREADS) void kp_anchor_bsort_kernel(const uint6
                 else bitonic_bucket<BS_STAGE / 64>(grp, dst, bs, bm, lane);
             } else if (lane == 0) {
                 const uint32_t slot = atomicAdd(&s_n_huge, 1u);
-                if (slot < BS_HUGE_LIST) { s_huge[slot][0] = bs; s_huge[slot][1] = bm; }
-                else {  // (practically never: more than BS_HUGE_LIST buckets beyond BS_STAGE keys in one assembly)
-                    for (uint32_t i = 0; i < bm; ++i) {
-                        const uint64_t key = grp[bs + i];
-                        uint32_t rank = 0;
-                        for (uint32_t j = 0; j < bm; ++j) rank += (grp[bs + j] < key || (grp[bs + j] == key && j < i)) ? 1u : 0u;
-                        dst[bs + rank] = key;
-                    }
-                }
+                if (slot < BS_HUGE_LIST) { s_huge[slot][0] = bs; s_huge[slot][1] = bm; }  // (a full list: counted only, see 3.)
             }
         }
     }
@@ -345,11 +337,19 @@ __global__ __launch_bounds__(BS_THREADS) void kp_anchor_bsort_kernel(const uint6
         }
     }
     // ---- 3. the few buckets beyond BS_STAGE keys: ranked by the whole block, tile by tile through LDS ---------------------
-    const uint32_t n_huge = min(s_n_huge, (uint32_t)BS_HUGE_LIST);
+    // More of them than the list holds (a database's own loci typed against it: every gene a few times over): the list is
+    // left aside and the block walks the buckets, whose bounds every thread reads alike, and ranks each one beyond BS_STAGE.
+    const bool walk = s_n_huge > (uint32_t)BS_HUGE_LIST;
+    const uint32_t n_huge = walk ? n_bins : s_n_huge;
     uint64_t *tile = s_tile;
     constexpr uint32_t TILE = BS_TILE;
     for (uint32_t h = 0; h < n_huge; ++h) {
-        const uint32_t bs = s_huge[h][0], bm = s_huge[h][1];
+        uint32_t bs, bm;
+        if (walk) {
+            bs = h ? s_bin[h - 1] : 0u;
+            bm = s_bin[h] - bs;
+            if (bm <= (uint32_t)BS_STAGE) continue;  // (uniform)
+        } else { bs = s_huge[h][0]; bm = s_huge[h][1]; }
         for (uint32_t i0 = 0; i0 < bm; i0 += BS_THREADS) {  // BS_THREADS keys are ranked per round
             const uint32_t i = i0 + tid;
             const uint64_t key = i < bm ? grp[bs + i] : 0ull;
