@@ -6,27 +6,24 @@ static const char *const NO_RESULTS = "this batch has no resident alignment resu
 
 // What a pass enqueues between its fork onto the join stream and the join back: chaining of the groups, joined fill and walk-back on `jstream`; the band
 // tasks' order, fill and traceback on `stream`.  The caller joins the streams whatever this returns: the next pass never starts beside kernels of this one.
-static int enqueue_forked(kp_ctx *ctx, kp_batch *b, KpWork *w, hipStream_t stream, const uint32_t *d_task_count) {
-    kp_launch_join_chain(b->view, ctx->genes, w->d_anchors_a.p, w->anchor_cap, w->key_bits, w->d_tasks.p, w->task_cap, w->d_groups.p,
-                         w->d_join_counts.p, w->group_cap, w->d_joins.p, w->d_join_counts.p + 1, w->join_cap, w->d_jscratch.p, w->jstream);
-    kp_launch_join_fill(b->view, ctx->genes, w->d_joins.p, w->d_join_counts.p + 1, w->join_cap, w->d_trace.p, w->d_trace_top.p, w->trace_cap, w->jstream);
-    kp_launch_join_trace(b->view, ctx->genes, w->d_joins.p, w->d_join_counts.p + 1, w->join_cap, w->task_cap, w->d_trace.p, w->d_task_drop.p, w->jstream);
-    kp_launch_task_order(b->view, ctx->genes, w->d_anchors_a.p, w->anchor_cap, w->key_bits, w->d_tasks.p, d_task_count, w->task_cap,
-                         w->d_results.p, w->d_task_order.p, w->d_task_order.p + KP_ORDER_HEAD, stream);
-    KP_HIP_CHECK(ctx, hipEventRecord(w->ev[3], stream));
-    // all four band classes in one fill launch, then the traceback (kp_sw.hip): ev[3]..ev[4] is the fill, ev[4]..ev[5]
-    // the traceback; the remaining event slots stay in the layout and read 0
-    kp_launch_sw(b->view, ctx->genes, w->d_tasks.p, w->d_task_order.p + KP_ORDER_COUNTS, w->task_cap, w->d_task_order.p + KP_ORDER_HEAD,
-                 w->d_ends.p, w->d_trace.p, w->d_trace_top.p, w->trace_cap, w->d_results.p, ctx->max_gene_len > KP_FILL16_MAX_GENE_LEN,
-                 stream, w->ev[4]);
-    // ev[5]..ev[6]: what is left of the join kernels once the band tasks are through (the "sw64" slot of kp_batch_profile; the
-    // last slot reads 0)
-    KP_HIP_CHECK(ctx, hipEventRecord(w->ev[5], stream));
+static int enqueue_forked(kp_ctx *ctx, kp_batch *b, KpWork *w, hipStream_t stream) {
+    const KpAnchors an = w->anchors();
+    const KpTasks tasks = w->tasks();
+    const KpJoins joins = w->joins();
+    const KpTrace trace = w->trace();
+    kp_launch_join_chain(an, tasks, w->groups(), joins, w->d_jscratch.p, ctx->opt.join, w->jstream);
+    kp_launch_join_fill(b->view, ctx->genes, joins, trace, ctx->opt.join, w->jstream);
+    kp_launch_join_trace(b->view, ctx->genes, joins, tasks, trace, ctx->opt.join, w->jstream);
+    kp_launch_task_order(b->view, ctx->genes, an, tasks, stream);
+    KP_HIP_CHECK(ctx, hipEventRecord(w->ev[KP_EV_ORDER], stream));
+    // all four band classes in one fill launch, then the traceback (kp_sw.hip)
+    kp_launch_sw(b->view, ctx->genes, tasks, trace, ctx->max_gene_len > KP_FILL16_MAX_GENE_LEN, stream, w->ev[KP_EV_FILL]);
+    KP_HIP_CHECK(ctx, hipEventRecord(w->ev[KP_EV_TRACEBACK], stream));
     return KP_OK;
 }
 
 static int enqueue_align(kp_ctx *ctx, kp_batch *b, KpWork *w) {
-    const size_t n_asm = (size_t)b->n_asm;
+    const size_t n_asm = w->n_asm;
     for (auto &e : w->ev)
         if (!e) KP_HIP_CHECK(ctx, hipEventCreate(&e.h));
     if (!w->astream) KP_HIP_CHECK(ctx, hipStreamCreateWithFlags(&w->astream.h, hipStreamNonBlocking));
@@ -43,13 +40,13 @@ static int enqueue_align(kp_ctx *ctx, kp_batch *b, KpWork *w) {
         return kp_fail(ctx, KP_EOVERFLOW, "a batch holds at most 2^33 bases (candidate positions); use smaller batches");
     KP_HIP_CHECK(ctx, w->d_anchors_a.reserve(n_asm * w->anchor_cap));
     KP_HIP_CHECK(ctx, w->d_anchors_b.reserve(n_asm * w->anchor_cap));
-    KP_HIP_CHECK(ctx, w->d_counts.reserve(2 * n_asm + KP_N_CLASSES));
+    KP_HIP_CHECK(ctx, w->d_counts.reserve(w->counts_len()));
     KP_HIP_CHECK(ctx, w->d_sub_counts.reserve(n_asm * KP_ANCHOR_SUBS));
-    KP_HIP_CHECK(ctx, w->d_seg.reserve(2 * n_asm));
+    KP_HIP_CHECK(ctx, w->d_seg.reserve(w->seg_len()));
     KP_HIP_CHECK(ctx, w->d_tasks.reserve(KP_N_CLASSES * (size_t)w->task_cap));
     KP_HIP_CHECK(ctx, w->d_results.reserve(KP_N_CLASSES * (size_t)w->task_cap));
     KP_HIP_CHECK(ctx, w->d_task_drop.reserve(KP_N_CLASSES * (size_t)w->task_cap));
-    KP_HIP_CHECK(ctx, w->d_jscratch.reserve(kp_join_chain_scratch_bytes()));
+    KP_HIP_CHECK(ctx, w->d_jscratch.reserve(kp_join_chain_scratch_bytes(ctx->opt.join)));
     {   // a table holds every distinct minimizer of the longest assembly (2 / 11 of its bases) at a load of at most a half
         uint32_t lg = 12;
         while (((uint64_t)1 << lg) < (uint64_t)b->max_asm_bases * 2 / 5 + 1 && lg < 31) ++lg;
@@ -58,57 +55,54 @@ static int enqueue_align(kp_ctx *ctx, kp_batch *b, KpWork *w) {
         KP_HIP_CHECK(ctx, w->d_occ_cnts.reserve((size_t)w->occ_slots << lg));
         KP_HIP_CHECK(ctx, w->d_occ_state.reserve(kp_occ_state_words(n_asm, w->occ_slots)));
     }
-    KP_HIP_CHECK(ctx, w->d_task_order.reserve(KP_ORDER_HEAD + KP_N_CLASSES * (size_t)w->task_cap));
+    KP_HIP_CHECK(ctx, w->d_task_order.reserve(w->order_len()));
     KP_HIP_CHECK(ctx, w->d_cand.reserve(w->cand_cap));
-    KP_HIP_CHECK(ctx, w->d_cand_count.reserve(2));  // [0] the streaming kernel's candidates (front), [1] the edge kernel's (back)
+    KP_HIP_CHECK(ctx, w->d_cand_count.reserve(KP_CAND_COUNTS));  // the streaming kernel's candidates (front), the edge kernel's (back)
     KP_HIP_CHECK(ctx, w->d_ends.reserve(KP_N_CLASSES * (size_t)w->task_cap));
-    KP_HIP_CHECK(ctx, w->d_trace_top.reserve(4));  // [0] trace units handed out, [1..2] the fill kernel's quad counters (four 32-bit words)
+    KP_HIP_CHECK(ctx, w->d_trace_top.reserve(KP_TOP_WORDS));
     KP_HIP_CHECK(ctx, w->d_trace.reserve(w->trace_cap));
     KP_HIP_CHECK(ctx, w->d_groups.reserve(w->group_cap));
     KP_HIP_CHECK(ctx, w->d_joins.reserve(KP_N_CLASSES * (size_t)w->join_cap));
-    KP_HIP_CHECK(ctx, w->d_join_counts.reserve(1 + KP_N_CLASSES));
+    KP_HIP_CHECK(ctx, w->d_join_counts.reserve(KP_JOIN_COUNTS));
     KP_HIP_CHECK(ctx, hipStreamWaitEvent(stream, b->in->ready, 0));  // the batch's H2D copies
     if (b->after && b->after->in) KP_HIP_CHECK(ctx, hipStreamWaitEvent(stream, b->after->in->ready, 0));
-    KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_counts.p, 0, (2 * n_asm + KP_N_CLASSES) * sizeof(uint32_t), stream));
+    KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_counts.p, 0, w->counts_len() * sizeof(uint32_t), stream));
     KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_sub_counts.p, 0, n_asm * KP_ANCHOR_SUBS * sizeof(uint32_t), stream));
-    KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_cand_count.p, 0, 2 * sizeof(unsigned long long), stream));
+    KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_cand_count.p, 0, KP_CAND_COUNTS * sizeof(unsigned long long), stream));
     KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_task_order.p, 0, KP_ORDER_HEAD * sizeof(uint32_t), stream));
-    KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_trace_top.p, 0, 4 * sizeof(unsigned long long), stream));
-    KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_join_counts.p, 0, (1 + KP_N_CLASSES) * sizeof(uint32_t), stream));
-    uint32_t *d_task_count = w->d_counts.p + n_asm;
-    const uint32_t sub_cap = w->anchor_cap / KP_ANCHOR_SUBS;
+    KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_trace_top.p, 0, KP_TOP_WORDS * sizeof(unsigned long long), stream));
+    KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_join_counts.p, 0, KP_JOIN_COUNTS * sizeof(uint32_t), stream));
     // compact anchor keys: as many bits per field as this batch and database can set
     auto bits_for = [](uint64_t max_value) { uint32_t n = 1; while (n < 63 && (max_value >> n)) ++n; return n; };
     w->key_bits.qb = std::min<uint32_t>(16, bits_for((uint64_t)std::max(ctx->max_gene_len, 1)));
     w->key_bits.db = std::min<uint32_t>(30, bits_for((uint64_t)b->max_asm_bases + KP_DIAG_BIAS));
-    KP_HIP_CHECK(ctx, hipEventRecord(ev[0], stream));
-    kp_launch_scan(b->view, ctx->index, w->d_cand.p, w->d_cand_count.p, w->cand_cap, w->d_anchors_a.p, w->d_sub_counts.p, sub_cap, w->key_bits, ctx->opt.scan_mode, b->n_ctg_total, stream, ev[1]);
+    const KpAnchors an = w->anchors();
+    KP_HIP_CHECK(ctx, hipEventRecord(ev[KP_EV_START], stream));
+    kp_launch_scan(b->view, ctx->index, w->d_cand.p, w->d_cand_count.p, w->cand_cap, an, ctx->opt.scan_mode, b->n_ctg_total, stream, ev[KP_EV_SCAN]);
     if (!ctx->opt.library_sort && kp_bsort_fits(2u * (uint32_t)ctx->n_genes)) {
         // buckets of the gene/strand field, each sorted on its own (kp_bsort.hip); sorted keys end up where the chaining reads them
-        kp_launch_anchor_bsort(b->view, w->d_anchors_a.p, w->d_sub_counts.p, sub_cap, w->d_anchors_b.p, w->d_anchors_a.p,
-                               w->d_counts.p, w->d_counts.p + n_asm + KP_N_CLASSES, 2u * (uint32_t)ctx->n_genes, w->key_bits, stream);
+        kp_launch_anchor_bsort(b->view, an, 2u * (uint32_t)ctx->n_genes, stream);
     } else {  // `library_sort`: compaction + the library's segmented radix sort (tests compare the two)
-        kp_launch_anchor_compact(b->view, w->d_anchors_a.p, w->d_sub_counts.p, sub_cap, w->d_anchors_b.p, w->d_counts.p, w->d_counts.p + n_asm + KP_N_CLASSES, stream);
-        int rc = kp_sort_anchors(ctx, w->d_anchors_b.p, w->d_anchors_a.p, w->d_counts.p, w->anchor_cap, b->n_asm, &w->sort_temp.p, &w->sort_temp.bytes, w->d_seg.p, w->d_seg.p + n_asm,
-                                 (int)(w->key_bits.qb + w->key_bits.db) + ctx->gs_bits,
-                                 stream);
+        kp_launch_anchor_compact(b->view, an, stream);
+        int rc = kp_sort_anchors(ctx, an, b->n_asm, &w->sort_temp.p, &w->sort_temp.bytes, w->seg_begin(), w->seg_end(),
+                                 (int)(w->key_bits.qb + w->key_bits.db) + ctx->gs_bits, stream);
         if (rc) return rc;
     }
-    KP_HIP_CHECK(ctx, hipEventRecord(ev[2], stream));
-    kp_launch_occ_cut(b->view, ctx->d_gene_len.p, w->d_anchors_a.p, w->d_counts.p, w->anchor_cap, w->key_bits, w->d_occ_keys.p, w->d_occ_cnts.p,
-                      w->d_occ_state.p, w->d_trace_top.p + 3, w->occ_slots, w->occ_log2, stream);  // (words 1-2 of trace_top are the fill kernel's quad counters)
-    kp_launch_chain(b->view, w->d_anchors_a.p, w->d_counts.p, w->anchor_cap, w->key_bits, w->d_tasks.p, d_task_count, w->task_cap, w->d_groups.p, w->d_join_counts.p, w->group_cap, stream);
+    KP_HIP_CHECK(ctx, hipEventRecord(ev[KP_EV_SORT], stream));
+    kp_launch_occ_cut(b->view, ctx->d_gene_len.p, an, w->d_occ_keys.p, w->d_occ_cnts.p, w->d_occ_state.p, w->occ_demand(), w->occ_slots, w->occ_log2, stream);
+    kp_launch_chain(b->view, an, w->tasks(), w->groups(), stream);
     // kp-align v5: the chains of a group's anchors, their joined fill and walk-back need the groups and the sorted anchors only:
     // they fork off here and run on the work set's second stream beside the band tasks' order, fill and traceback
     KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_task_drop.p, 0, KP_N_CLASSES * (size_t)w->task_cap, stream));
     KP_HIP_CHECK(ctx, hipEventRecord(w->ev_jfork, stream));
     KP_HIP_CHECK(ctx, hipStreamWaitEvent(w->jstream, w->ev_jfork, 0));
-    const int rc = enqueue_forked(ctx, b, w, stream, d_task_count);
+    const int rc = enqueue_forked(ctx, b, w, stream);
     const hipError_t e_done = hipEventRecord(w->ev_jdone, w->jstream), e_join = hipStreamWaitEvent(stream, w->ev_jdone, 0);
     if (rc) return rc;
     KP_HIP_CHECK(ctx, e_done);
     KP_HIP_CHECK(ctx, e_join);
-    for (int c = 2; c < KP_N_CLASSES; ++c) KP_HIP_CHECK(ctx, hipEventRecord(ev[4 + c], stream));
+    KP_HIP_CHECK(ctx, hipEventRecord(ev[KP_EV_JOINED], stream));
+    KP_HIP_CHECK(ctx, hipEventRecord(ev[KP_EV_END], stream));
     KP_HIP_CHECK(ctx, hipGetLastError());
     return KP_OK;
 }
@@ -142,7 +136,7 @@ int kp_batch_align(kp_ctx *ctx, kp_batch *b) {
             if (int rc = sync_runs(ctx, w)) return rc;  // its reductions may still be reading the hit tables
             w->owner->w = nullptr;
         }
-        w->owner = b;
+        w->owner = b; w->n_asm = (size_t)b->n_asm;
         b->w = w; b->last_w = w;
     }
     kp_caps_size(ctx->opt, ctx->learnt, b->n_asm, b->view.total_words, *w);
@@ -150,9 +144,8 @@ int kp_batch_align(kp_ctx *ctx, kp_batch *b) {
     w->cs_on = ctx->opt.cs != 0; w->cs_valid = false;
     w->cigar_on = ctx->opt.cigar != 0 || w->cs_on; w->cigar_valid = false;  // (cs reads the ops)
     for (auto &v : w->h_tasks) v.clear();
-    for (auto &r : w->runs)
-        if (r) { r->split = false; r->scored = false; r->reduced = false; r->sums_valid = false; }
-    w->stats[4] = 0;
+    w->reset_runs();
+    w->stats[KP_STAT_RERUNS] = 0;
     int rc = enqueue_align(ctx, b, w);
     if (rc) return rc;
     w->aligned = true;
@@ -162,33 +155,29 @@ int kp_batch_align(kp_ctx *ctx, kp_batch *b) {
 // hit-table finalisation on the device: compaction of the band-task results into per-assembly lists, emission order,
 // duplicates, mapq.  Grows hit_cap and repeats if an assembly produced more hits than its region holds.
 static int finalise_hits_on_device(kp_ctx *ctx, kp_batch *b, KpWork *w) {
-    const size_t n_asm = (size_t)b->n_asm;
+    const size_t n_asm = w->n_asm;
     for (int attempt = 0;; ++attempt) {
         KP_HIP_CHECK(ctx, w->d_hits_raw.reserve(n_asm * w->hit_cap));
         KP_HIP_CHECK(ctx, w->d_hits.reserve(n_asm * w->hit_cap));
         KP_HIP_CHECK(ctx, w->d_keys.reserve(n_asm * w->hit_cap * 3));
-        KP_HIP_CHECK(ctx, w->d_hit_counts.reserve(2 * n_asm));
+        KP_HIP_CHECK(ctx, w->d_hit_counts.reserve(w->hit_counts_len()));
         KP_HIP_CHECK(ctx, w->d_cells.reserve(1));
-        KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_hit_counts.p, 0, 2 * n_asm * sizeof(uint32_t), ctx->post));
+        KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_hit_counts.p, 0, w->hit_counts_len() * sizeof(uint32_t), ctx->post));
         KP_HIP_CHECK(ctx, hipMemsetAsync(w->d_cells.p, 0, sizeof(unsigned long long), ctx->post));
-        kp_launch_hit_finalise(b->view, ctx->d_gene_len.p, w->d_tasks.p, w->d_results.p, w->d_task_drop.p, w->d_counts.p + n_asm,
-                               w->task_cap, w->d_hits_raw.p, w->d_hit_counts.p, w->hit_cap, w->d_keys.p, w->d_hits.p,
-                               w->d_hit_counts.p + n_asm, w->d_cells.p, ctx->d_ln.p, ctx->d_ln.p + KP_MAPQ_LN_HALF_SIZE, w->d_joins.p,
-                               w->d_join_counts.p + 1, w->join_cap, ctx->post);
+        kp_launch_hit_finalise(b->view, ctx->d_gene_len.p, w->tasks(), w->joins(), w->raw_hits(), w->hits(), w->d_cells.p, ctx->ln_half(), ctx->ln_int(), ctx->post);
         KP_HIP_CHECK(ctx, hipGetLastError());
-        w->h_hit_counts.resize(2 * n_asm);
+        w->h_hit_counts.resize(w->hit_counts_len());
         unsigned long long cells = 0;
-        if (int frc = fetch_all(ctx, ctx->post, {{w->h_hit_counts.data(), w->d_hit_counts.p, 2 * n_asm * sizeof(uint32_t)}, {&cells, w->d_cells.p, sizeof cells}}))
+        if (int frc = fetch_all(ctx, ctx->post, {{w->h_hit_counts.data(), w->d_hit_counts.p, w->hit_counts_len() * sizeof(uint32_t)}, {&cells, w->d_cells.p, sizeof cells}}))
             return frc;
-        uint32_t max_raw = 0;
-        for (size_t a = 0; a < n_asm; ++a) max_raw = std::max(max_raw, w->h_hit_counts[a]);
-        if (max_raw <= w->hit_cap) { w->stats[2] = (int64_t)cells; break; }
+        const uint32_t max_raw = n_asm ? *std::max_element(w->h_raw_hit_count(), w->h_raw_hit_count() + n_asm) : 0;
+        if (max_raw <= w->hit_cap) { w->stats[KP_STAT_CELLS] = (int64_t)cells; break; }
         if (attempt >= 2) return kp_fail(ctx, KP_EOVERFLOW, "hit buffers overflowed repeatedly");
         kp_caps_grow_hits(ctx->learnt, *w, max_raw, true);
-        w->stats[4] += 1;
+        w->stats[KP_STAT_RERUNS] += 1;
     }
     w->hit_off.assign(n_asm + 1, 0);
-    for (size_t a = 0; a < n_asm; ++a) w->hit_off[a + 1] = w->hit_off[a] + (int64_t)w->h_hit_counts[n_asm + a];
+    for (size_t a = 0; a < n_asm; ++a) w->hit_off[a + 1] = w->hit_off[a] + (int64_t)w->h_hit_count()[a];
     return KP_OK;
 }
 
@@ -196,7 +185,7 @@ static int finalise_hits_on_device(kp_ctx *ctx, kp_batch *b, KpWork *w) {
 // buffer follows the policy of kp_caps.h; where it was too small only the writing kernel runs again -- the counts and offsets
 // are exact whatever the buffer held, and the direction bits of the pass are still in the work set's trace buffer.
 static int emit_cigars(kp_ctx *ctx, kp_batch *b, KpWork *w) {
-    const size_t n_asm = (size_t)b->n_asm;
+    const size_t n_asm = w->n_asm;
     const int64_t total = w->hit_off[n_asm];
     w->cigar_cap = kp_caps_cigar_size(ctx->opt, ctx->learnt, (uint64_t)total);
     KP_HIP_CHECK(ctx, w->d_cig_src.reserve(n_asm * w->hit_cap));
@@ -205,14 +194,10 @@ static int emit_cigars(kp_ctx *ctx, kp_batch *b, KpWork *w) {
     KP_HIP_CHECK(ctx, w->d_cig_hit_off.reserve(n_asm + 1));
     KP_HIP_CHECK(ctx, w->d_cig_ops.reserve(w->cigar_cap));
     KP_HIP_CHECK(ctx, hipMemcpyAsync(w->d_cig_hit_off.p, w->hit_off.data(), (n_asm + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->post));
-    const uint32_t *n_hits = w->d_hit_counts.p + n_asm;
-    kp_launch_cigar_locate(b->view, ctx->d_gene_len.p, w->d_tasks.p, w->d_results.p, w->d_task_drop.p, w->d_counts.p + n_asm, w->task_cap, w->d_joins.p,
-                           w->d_join_counts.p + 1, w->join_cap, w->d_hits.p, n_hits, w->hit_cap, w->d_cig_src.p, ctx->post);
-    kp_launch_cigar_count(b->view, ctx->genes, w->d_tasks.p, w->d_ends.p, w->task_cap, w->d_joins.p, w->join_cap, w->d_trace.p, n_hits, w->hit_cap,
-                          w->d_cig_hit_off.p, w->d_cig_src.p, w->d_cig_cnt.p, total, w->d_cig_off.p, ctx->post);
+    kp_launch_cigar_locate(b->view, ctx->d_gene_len.p, w->tasks(), w->joins(), w->hits(), w->d_cig_src.p, ctx->post);
+    kp_launch_cigar_walk(b->view, ctx->genes, w->tasks(), w->joins(), w->trace(), w->hits(), w->hit_rows(), w->d_cig_src.p, w->cigars(), false, ctx->post);
     for (int attempt = 0;; ++attempt) {
-        kp_launch_cigar_emit(b->view, ctx->genes, w->d_tasks.p, w->d_ends.p, w->task_cap, w->d_joins.p, w->join_cap, w->d_trace.p, n_hits, w->hit_cap,
-                             w->d_cig_hit_off.p, w->d_cig_src.p, w->d_cig_off.p, w->d_cig_ops.p, (int64_t)w->cigar_cap, ctx->post);
+        kp_launch_cigar_walk(b->view, ctx->genes, w->tasks(), w->joins(), w->trace(), w->hits(), w->hit_rows(), w->d_cig_src.p, w->cigars(), true, ctx->post);
         KP_HIP_CHECK(ctx, hipGetLastError());
         int64_t need = 0;
         if (int frc = fetch_all(ctx, ctx->post, {{&need, w->d_cig_off.p + total, sizeof need}})) return frc;
@@ -229,18 +214,14 @@ static int emit_cigars(kp_ctx *ctx, kp_batch *b, KpWork *w) {
 // rewritten buffer included.  Bytes counted, scanned and written; the byte buffer follows the policy of kp_caps.h, and where it was
 // too small only the writing kernel runs again: counts and offsets are exact whatever the buffer held.
 static int emit_cs(kp_ctx *ctx, kp_batch *b, KpWork *w) {
-    const size_t n_asm = (size_t)b->n_asm;
-    const int64_t total = w->hit_off[n_asm];
+    const int64_t total = w->hit_off[w->n_asm];
     w->cs_cap = kp_caps_cs_size(ctx->cs_caps, (uint64_t)total);
     KP_HIP_CHECK(ctx, w->d_cs_cnt.reserve((size_t)total));
     KP_HIP_CHECK(ctx, w->d_cs_off.reserve((size_t)total + 1));
     KP_HIP_CHECK(ctx, w->d_cs_bytes.reserve(w->cs_cap));
-    const uint32_t *n_hits = w->d_hit_counts.p + n_asm;
-    kp_launch_cs_count(b->view, ctx->genes, w->d_hits.p, n_hits, w->hit_cap, w->d_cig_hit_off.p, w->d_cig_ops.p, w->d_cig_off.p, (int64_t)w->cigar_cap,
-                       w->d_cs_cnt.p, total, w->d_cs_off.p, ctx->post);
+    kp_launch_cs_walk(b->view, ctx->genes, w->hits(), w->hit_rows(), w->cigars(), w->cs(), false, ctx->post);
     for (int attempt = 0;; ++attempt) {
-        kp_launch_cs_emit(b->view, ctx->genes, w->d_hits.p, n_hits, w->hit_cap, w->d_cig_hit_off.p, w->d_cig_ops.p, w->d_cig_off.p, (int64_t)w->cigar_cap,
-                          w->d_cs_off.p, w->d_cs_bytes.p, (int64_t)w->cs_cap, ctx->post);
+        kp_launch_cs_walk(b->view, ctx->genes, w->hits(), w->hit_rows(), w->cigars(), w->cs(), true, ctx->post);
         KP_HIP_CHECK(ctx, hipGetLastError());
         int64_t need = 0;
         if (int frc = fetch_all(ctx, ctx->post, {{&need, w->d_cs_off.p + total, sizeof need}})) return frc;
@@ -262,42 +243,43 @@ int kp_batch_wait(kp_ctx *ctx, kp_batch *b) {
     if (!w || !w->aligned) return kp_fail(ctx, KP_ESTATE, w ? "kp_batch_align has not been called" : NO_RESULTS);
     if (w->finalised) return KP_OK;
     KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const size_t n_asm = (size_t)b->n_asm;
+    const size_t n_asm = w->n_asm;
+    const uint32_t *const n_join = w->h_join_count();
     for (;;) {
         // the post stream picks up where this batch's alignment pass ends; later passes on ctx->stream are not waited for
-        KP_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->post, w->ev[3 + KP_N_CLASSES], 0));
-        w->h_counts.resize(2 * n_asm + KP_N_CLASSES);
-        unsigned long long n_cand2[2] = {0, 0}, trace_top2[4] = {0, 0, 0, 0};
-        if (int frc = fetch_all(ctx, ctx->post, {{w->h_counts.data(), w->d_counts.p, (2 * n_asm + KP_N_CLASSES) * sizeof(uint32_t)},
-                                                 {n_cand2, w->d_cand_count.p, sizeof n_cand2}, {trace_top2, w->d_trace_top.p, sizeof trace_top2},
+        KP_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->post, w->ev[KP_EV_END], 0));
+        w->h_counts.resize(w->counts_len());
+        unsigned long long n_cand[KP_CAND_COUNTS] = {}, top[KP_TOP_WORDS] = {};
+        if (int frc = fetch_all(ctx, ctx->post, {{w->h_counts.data(), w->d_counts.p, w->counts_len() * sizeof(uint32_t)},
+                                                 {n_cand, w->d_cand_count.p, sizeof n_cand}, {top, w->d_trace_top.p, sizeof top},
                                                  {w->h_join_counts, w->d_join_counts.p, sizeof w->h_join_counts}}))
             return frc;
         KpPassSeen seen;
-        seen.n_asm = n_asm; seen.total_words = b->view.total_words; seen.n_cand = n_cand2[0] + n_cand2[1];
-        seen.trace_need = trace_top2[0]; seen.occ_need = trace_top2[3];
-        seen.n_group = w->h_join_counts[0];
-        for (int c = 0; c < KP_N_CLASSES; ++c) seen.max_join = std::max(seen.max_join, w->h_join_counts[1 + c]);
-        for (size_t a = 0; a < n_asm; ++a) seen.max_slice = std::max(seen.max_slice, w->h_counts[n_asm + KP_N_CLASSES + a]);
-        for (int c = 0; c < KP_N_CLASSES; ++c) seen.max_task = std::max(seen.max_task, w->h_counts[n_asm + c]);
+        seen.n_asm = n_asm; seen.total_words = b->view.total_words; seen.n_cand = n_cand[KP_CAND_FRONT] + n_cand[KP_CAND_BACK];
+        seen.trace_need = top[KP_TOP_TRACE]; seen.occ_need = top[KP_TOP_OCC];
+        seen.n_group = w->h_group_count();
+        for (int c = 0; c < KP_N_CLASSES; ++c) seen.max_join = std::max(seen.max_join, n_join[c]);
+        for (size_t a = 0; a < n_asm; ++a) seen.max_slice = std::max(seen.max_slice, w->h_slice_need()[a]);
+        for (int c = 0; c < KP_N_CLASSES; ++c) seen.max_task = std::max(seen.max_task, w->h_task_count()[c]);
         if (ctx->opt.join_stats)
             std::fprintf(stderr, "[kp_batch_wait] %zu assemblies: %u groups, joins per band class %u %u %u %u, %llu assemblies needed their mid_occ (%u tables)\n", n_asm, seen.n_group,
-                         w->h_join_counts[1], w->h_join_counts[2], w->h_join_counts[3], w->h_join_counts[4], (unsigned long long)seen.occ_need, w->occ_slots);
+                         n_join[0], n_join[1], n_join[2], n_join[3], (unsigned long long)seen.occ_need, w->occ_slots);
         std::string err;
         const KpCapsVerdict verdict = kp_caps_after_pass(ctx->learnt, *w, seen, err);
         if (verdict == KP_CAPS_FITTED) break;
         if (verdict == KP_CAPS_OVERFLOW) return kp_fail(ctx, KP_EOVERFLOW, err);
-        w->stats[4] += 1;
+        w->stats[KP_STAT_RERUNS] += 1;
         int rc = enqueue_align(ctx, b, w);
         if (rc) return rc;
     }
     int64_t n_anchor = 0, n_task = 0;
-    for (size_t a = 0; a < n_asm; ++a) n_anchor += w->h_counts[a];
-    for (int c = 0; c < KP_N_CLASSES; ++c) n_task += w->h_counts[n_asm + c];
+    for (size_t a = 0; a < n_asm; ++a) n_anchor += w->h_anchor_count()[a];
+    for (int c = 0; c < KP_N_CLASSES; ++c) n_task += w->h_task_count()[c];
     for (auto &v : w->h_tasks) v.clear();
     w->h_joins.clear();
     int rc = finalise_hits_on_device(ctx, b, w);
     if (rc) return rc;
-    w->stats[0] = n_anchor; w->stats[1] = n_task; w->stats[3] = w->hit_off[n_asm];
+    w->stats[KP_STAT_ANCHORS] = n_anchor; w->stats[KP_STAT_TASKS] = n_task; w->stats[KP_STAT_HITS] = w->hit_off[n_asm];
     if (w->cigar_on)
         if (int crc = emit_cigars(ctx, b, w)) return crc;
     if (w->cs_on)
@@ -318,14 +300,14 @@ int kp_batch_hits(kp_ctx *ctx, kp_batch *b, kp_hit *out, int64_t cap) {
     if (!ctx || !b || b->ctx != ctx || (!out && cap > 0)) return kp_fail(ctx, KP_EINVAL, "bad arguments");
     KpWork *w = finalised_work(ctx, b);
     if (!w) return KP_ESTATE;
-    const size_t n_asm = (size_t)b->n_asm;
-    const int64_t total = w->hit_off[n_asm];
-    if (cap < total) return kp_fail(ctx, KP_EINVAL, "hit buffer too small");
+    const size_t n_asm = w->n_asm;
+    const KpHitTable hits = w->hits();
+    if (cap < w->hit_off[n_asm]) return kp_fail(ctx, KP_EINVAL, "hit buffer too small");
     KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     for (size_t a = 0; a < n_asm; ++a) {  // regions are contiguous per assembly; copy each used prefix
         const int64_t n = w->hit_off[a + 1] - w->hit_off[a];
         if (n > 0)
-            KP_HIP_CHECK(ctx, hipMemcpyAsync(out + w->hit_off[a], w->d_hits.p + a * (size_t)w->hit_cap, (size_t)n * sizeof(kp_hit), hipMemcpyDeviceToHost, ctx->post));
+            KP_HIP_CHECK(ctx, hipMemcpyAsync(out + w->hit_off[a], hits.of(a), (size_t)n * sizeof(kp_hit), hipMemcpyDeviceToHost, ctx->post));
     }
     KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->post));
     return KP_OK;
@@ -335,7 +317,7 @@ int kp_batch_set_hits(kp_ctx *ctx, kp_batch *b, const kp_hit *hits, const int64_
     if (!ctx || !b || b->ctx != ctx || !hit_off) return kp_fail(ctx, KP_EINVAL, "bad arguments");
     KpWork *w = finalised_work(ctx, b);
     if (!w) return KP_ESTATE;
-    const size_t n_asm = (size_t)b->n_asm;
+    const size_t n_asm = w->n_asm;
     int64_t max_n = 0;
     for (size_t a = 0; a < n_asm; ++a) {
         const int64_t n = hit_off[a + 1] - hit_off[a];
@@ -347,22 +329,22 @@ int kp_batch_set_hits(kp_ctx *ctx, kp_batch *b, const kp_hit *hits, const int64_
     if (int rc = sync_runs(ctx, w)) return rc;  // nothing may still be reading the table that is about to be replaced
     if ((uint64_t)max_n > w->hit_cap) kp_caps_grow_hits(ctx->learnt, *w, (uint32_t)max_n, false);
     KP_HIP_CHECK(ctx, w->d_hits.reserve(n_asm * w->hit_cap));
-    KP_HIP_CHECK(ctx, w->d_hit_counts.reserve(2 * n_asm));
-    w->h_hit_counts.resize(2 * n_asm);
+    KP_HIP_CHECK(ctx, w->d_hit_counts.reserve(w->hit_counts_len()));
+    w->h_hit_counts.resize(w->hit_counts_len());
+    const KpHitTable table = w->hits();
     w->hit_off.assign(n_asm + 1, 0);
     for (size_t a = 0; a < n_asm; ++a) {
         const int64_t n = hit_off[a + 1] - hit_off[a];
         if (n > 0)
-            KP_HIP_CHECK(ctx, hipMemcpy(w->d_hits.p + a * (size_t)w->hit_cap, hits + hit_off[a], (size_t)n * sizeof(kp_hit), hipMemcpyHostToDevice));
-        w->h_hit_counts[n_asm + a] = (uint32_t)n;
+            KP_HIP_CHECK(ctx, hipMemcpy(table.of(a), hits + hit_off[a], (size_t)n * sizeof(kp_hit), hipMemcpyHostToDevice));
+        w->h_hit_count()[a] = (uint32_t)n;
         w->hit_off[a + 1] = w->hit_off[a] + n;
     }
     if (n_asm)
-        KP_HIP_CHECK(ctx, hipMemcpy(w->d_hit_counts.p + n_asm, w->h_hit_counts.data() + n_asm, n_asm * sizeof(uint32_t), hipMemcpyHostToDevice));
-    w->stats[3] = w->hit_off[n_asm];
+        KP_HIP_CHECK(ctx, hipMemcpy(table.count, w->h_hit_count(), n_asm * sizeof(uint32_t), hipMemcpyHostToDevice));
+    w->stats[KP_STAT_HITS] = w->hit_off[n_asm];
     w->cigar_valid = false; w->cs_valid = false;  // (they described the table that has just been replaced)
-    for (auto &r : w->runs)
-        if (r) { r->split = false; r->scored = false; r->reduced = false; r->sums_valid = false; }
+    w->reset_runs();
     return KP_OK;
 }
 
@@ -429,9 +411,10 @@ int kp_batch_profile(kp_ctx *ctx, kp_batch *b, float *ms7, int64_t *bytes_scanne
     KpWork *w = finalised_work(ctx, b);
     if (!w) return KP_ESTATE;
     KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    for (int i = 0; i < 3 + KP_N_CLASSES; ++i)
-        if (hipEventElapsedTime(&ms7[i], w->ev[i], w->ev[i + 1]) != hipSuccess)
-            return kp_fail(ctx, KP_EHIP, "event timing failed");
+    for (int i = KP_EV_START; i < KP_EV_END; ++i) {  // seven consecutive intervals
+        const KpPassEvent next = KpPassEvent(i + 1);
+        if (hipEventElapsedTime(&ms7[i], w->ev[i], w->ev[next]) != hipSuccess) return kp_fail(ctx, KP_EHIP, "event timing failed");
+    }
     if (bytes_scanned) *bytes_scanned = 4 * b->view.total_words;
     return KP_OK;
 }
@@ -440,10 +423,10 @@ int64_t kp_batch_anchors(kp_ctx *ctx, kp_batch *b, int32_t a, uint64_t *out, int
     if (!ctx || !b || b->ctx != ctx || a < 0 || a >= b->n_asm) return kp_fail(ctx, KP_EINVAL, "bad arguments");
     KpWork *w = finalised_work(ctx, b);
     if (!w) return KP_ESTATE;
-    const int64_t n = w->h_counts[(size_t)a];
+    const int64_t n = w->h_anchor_count()[a];
     const int64_t m = std::min(n, cap);
     if (out && m > 0) {
-        if (hipMemcpy(out, w->d_anchors_a.p + (size_t)a * w->anchor_cap, (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
+        if (hipMemcpy(out, w->anchors().of((size_t)a), (size_t)m * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess)
             return kp_fail(ctx, KP_EHIP, "D2H anchors failed");
         for (int64_t i = 0; i < m; ++i) out[i] = kp_key_unpack(out[i], w->key_bits);  // callers see the spec's layout
     }
@@ -455,10 +438,10 @@ int64_t kp_batch_tasks(kp_ctx *ctx, kp_batch *b, int32_t a, int32_t *out8, int64
     KpWork *w = finalised_work(ctx, b);
     if (!w) return KP_ESTATE;
     for (int c = 0; c < KP_N_CLASSES; ++c) {  // fetched on first use: only the stage tests look at tasks
-        const size_t nt = w->h_counts[(size_t)b->n_asm + c];
+        const size_t nt = w->h_task_count()[c];
         if (w->h_tasks[c].size() == nt) continue;
         w->h_tasks[c].resize(nt);
-        if (nt && hipMemcpy(w->h_tasks[c].data(), w->d_tasks.p + (size_t)c * w->task_cap, nt * sizeof(KpTask), hipMemcpyDeviceToHost) != hipSuccess)
+        if (nt && hipMemcpy(w->h_tasks[c].data(), w->tasks().cls(c), nt * sizeof(KpTask), hipMemcpyDeviceToHost) != hipSuccess)
             return kp_fail(ctx, KP_EHIP, "D2H tasks failed");
     }
     int64_t n = 0;
@@ -485,7 +468,7 @@ int64_t kp_batch_task_results(kp_ctx *ctx, kp_batch *b, int32_t a, int32_t *out7
     for (int c = 0; c < KP_N_CLASSES; ++c) {
         const size_t nt = w->h_tasks[c].size();
         res.resize(nt);
-        if (nt && hipMemcpy(res.data(), w->d_results.p + (size_t)c * w->task_cap, nt * sizeof(KpSwResult), hipMemcpyDeviceToHost) != hipSuccess)
+        if (nt && hipMemcpy(res.data(), w->tasks().cls_results(c), nt * sizeof(KpSwResult), hipMemcpyDeviceToHost) != hipSuccess)
             return kp_fail(ctx, KP_EHIP, "D2H task results failed");
         for (size_t i = 0; i < nt; ++i) {
             if (w->h_tasks[c][i].asm_id != a || w->h_tasks[c][i].n_anchors == 0) continue;
@@ -505,13 +488,13 @@ int64_t kp_batch_joins(kp_ctx *ctx, kp_batch *b, int32_t a, int32_t *out, int64_
     KpWork *w = finalised_work(ctx, b);
     if (!w) return KP_ESTATE;
     size_t total = 0;
-    for (int c = 0; c < KP_N_CLASSES; ++c) total += w->h_join_counts[1 + c];
+    for (int c = 0; c < KP_N_CLASSES; ++c) total += w->h_join_count()[c];
     if (w->h_joins.size() != total) {  // fetched on first use: only the stage tests look at joins
         w->h_joins.resize(total);
         size_t at = 0;
         for (int c = 0; c < KP_N_CLASSES; ++c) {
-            const size_t nj = w->h_join_counts[1 + c];
-            if (nj && hipMemcpy(w->h_joins.data() + at, w->d_joins.p + (size_t)c * w->join_cap, nj * sizeof(KpJoin), hipMemcpyDeviceToHost) != hipSuccess)
+            const size_t nj = w->h_join_count()[c];
+            if (nj && hipMemcpy(w->h_joins.data() + at, w->joins().cls(c), nj * sizeof(KpJoin), hipMemcpyDeviceToHost) != hipSuccess)
                 return kp_fail(ctx, KP_EHIP, "D2H joins failed");
             at += nj;
         }

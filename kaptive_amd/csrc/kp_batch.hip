@@ -69,7 +69,7 @@ static int batch_tables(kp_ctx *ctx, kp_batch *b, int32_t n_asm, const int64_t *
 static void quiesce_batch(kp_batch *b) {
     KpWork *w = b->last_w;
     if (!w) return;
-    if (w->ev[3 + KP_N_CLASSES]) (void)hipEventSynchronize(w->ev[3 + KP_N_CLASSES]);  // end of the slot's most recent pass
+    if (w->ev[KP_EV_END]) (void)hipEventSynchronize(w->ev[KP_EV_END]);  // end of the slot's most recent pass
     if (b->ctx) (void)hipStreamSynchronize(b->ctx->post);
     for (auto &r : w->runs)
         if (r && r->stream) { (void)hipStreamSynchronize(r->stream); if (r->aux) (void)hipStreamSynchronize(r->aux); }

@@ -389,9 +389,7 @@ static uint32_t bucket_span_bits(uint32_t n_bins) {
 // KP_MAX_GENES; the library's radix sort stays behind the `library_sort` option)
 bool kp_bsort_fits(uint32_t n_bins) { return n_bins > 0; }
 
-void kp_launch_anchor_bsort(const KpBatchView &b, const uint64_t *sliced, const uint32_t *sub_count, uint32_t sub_cap,
-                            uint64_t *grouped, uint64_t *out, uint32_t *count, uint32_t *need, uint32_t n_bins,
-                            KpKeyBits kb, hipStream_t stream) {
+void kp_launch_anchor_bsort(const KpBatchView &b, const KpAnchors &an, uint32_t n_bins, hipStream_t stream) {
     if (b.n_asm == 0) return;
     // more than 64 KB of LDS per block has to be asked for, per device (the attribute belongs to the device's copy of the
     // kernel): once per device and process, whichever thread comes first
@@ -405,6 +403,6 @@ void kp_launch_anchor_bsort(const KpBatchView &b, const uint64_t *sliced, const 
         raised.fetch_or(bit, std::memory_order_release);
     }
     const uint32_t span = bucket_span_bits(n_bins), n_buckets = (n_bins + (1u << span) - 1) >> span;
-    hipLaunchKernelGGL(kp_anchor_bsort_kernel, dim3(b.n_asm), dim3(BS_THREADS), kp_bsort_lds_bytes(n_buckets), stream, sliced,
-                       sub_count, sub_cap, grouped, out, count, need, n_buckets, kb.qb + kb.db + span);
+    hipLaunchKernelGGL(kp_anchor_bsort_kernel, dim3(b.n_asm), dim3(BS_THREADS), kp_bsort_lds_bytes(n_buckets), stream, an.keys,
+                       an.sub_count, an.sub_cap, an.second, an.keys, an.count, an.need, n_buckets, an.kb.qb + an.kb.db + span);
 }

@@ -941,45 +941,38 @@ __global__ __launch_bounds__(256) void kp_task_scatter_kernel(KpBatchView b, KpG
 
 }  // namespace
 
-void kp_launch_task_order(const KpBatchView &b, const KpGenes &genes, const uint64_t *sorted_anchors, uint32_t cap, KpKeyBits key_bits,
-                          KpTask *tasks, const uint32_t *task_count, uint32_t task_cap, KpSwResult *results, uint32_t *hist,
-                          uint32_t *order, hipStream_t stream) {
+void kp_launch_task_order(const KpBatchView &b, const KpGenes &genes, const KpAnchors &an, const KpTasks &t, hipStream_t stream) {
     const dim3 grid(128, KP_N_CLASSES), block(256);
-    hipLaunchKernelGGL(kp_chain_score_kernel, dim3(2048, KP_N_CLASSES), dim3(CS_THREADS), 0, stream, sorted_anchors, cap, key_bits, tasks,
-                       task_count, task_cap, results);
-    hipLaunchKernelGGL(kp_task_hist_kernel, grid, block, 0, stream, b, genes, tasks, task_count, task_cap, hist);
-    hipLaunchKernelGGL(kp_task_scatter_kernel, grid, block, 0, stream, b, genes, tasks, task_count, task_cap, hist, order,
-                       hist + KP_ORDER_COUNTS);
+    hipLaunchKernelGGL(kp_chain_score_kernel, dim3(2048, KP_N_CLASSES), dim3(CS_THREADS), 0, stream, an.keys, an.cap, an.kb, t.tasks,
+                       t.count, t.cap, t.results);
+    hipLaunchKernelGGL(kp_task_hist_kernel, grid, block, 0, stream, b, genes, t.tasks, t.count, t.cap, t.order_head);
+    hipLaunchKernelGGL(kp_task_scatter_kernel, grid, block, 0, stream, b, genes, t.tasks, t.count, t.cap, t.order_head, t.order,
+                       t.order_count);
 }
 
-void kp_launch_segments(const uint32_t *count, uint32_t cap, int n_asm, uint32_t *seg_begin, uint32_t *seg_end,
-                        hipStream_t stream) {
+void kp_launch_segments(const KpAnchors &an, int n_asm, uint32_t *seg_begin, uint32_t *seg_end, hipStream_t stream) {
     if (n_asm == 0) return;
-    hipLaunchKernelGGL(kp_segments_kernel, dim3((n_asm + 255) / 256), dim3(256), 0, stream, count, cap, n_asm, seg_begin,
-                       seg_end);
+    hipLaunchKernelGGL(kp_segments_kernel, dim3((n_asm + 255) / 256), dim3(256), 0, stream, an.count, an.cap, n_asm, seg_begin, seg_end);
 }
 
 size_t kp_occ_state_words(size_t n_asm, uint32_t occ_slots) { return 2 * n_asm + occ_slots + (size_t)occ_slots * OCC_QWORDS; }
 
-void kp_launch_occ_cut(const KpBatchView &b, const int32_t *gene_len, uint64_t *sorted_anchors, uint32_t *anchor_count, uint32_t cap,
-                       KpKeyBits key_bits, uint32_t *occ_keys, uint32_t *occ_cnts, uint32_t *occ_state, unsigned long long *occ_demand,
-                       uint32_t occ_slots, uint32_t occ_log2_size, hipStream_t stream) {
+void kp_launch_occ_cut(const KpBatchView &b, const int32_t *gene_len, const KpAnchors &an, uint32_t *occ_keys, uint32_t *occ_cnts,
+                       uint32_t *occ_state, unsigned long long *occ_demand, uint32_t occ_slots, uint32_t occ_log2_size, hipStream_t stream) {
     if (b.n_asm == 0) return;
     OccScratch sc;
     sc.keys = occ_keys; sc.cnts = occ_cnts; sc.state = occ_state; sc.demand = occ_demand; sc.n_slots = occ_slots; sc.log2_size = occ_log2_size;
     sc.n_asm = b.n_asm;
-    hipLaunchKernelGGL(kp_occ_cut_kernel, dim3(b.n_asm), dim3(64 * OCC_WAVES), 0, stream, b, gene_len, sorted_anchors, anchor_count, cap, key_bits, sc, 0);
+    hipLaunchKernelGGL(kp_occ_cut_kernel, dim3(b.n_asm), dim3(64 * OCC_WAVES), 0, stream, b, gene_len, an.keys, an.count, an.cap, an.kb, sc, 0);
     hipLaunchKernelGGL(kp_occ_sketch_kernel, dim3(OCC_PARTS, occ_slots), dim3(256), 0, stream, b, sc);
     hipLaunchKernelGGL(kp_occ_quantile_kernel, dim3(OCC_QPARTS, occ_slots), dim3(1024), 0, stream, sc);
-    hipLaunchKernelGGL(kp_occ_cut_kernel, dim3(b.n_asm), dim3(64 * OCC_WAVES), 0, stream, b, gene_len, sorted_anchors, anchor_count, cap, key_bits, sc, 1);
+    hipLaunchKernelGGL(kp_occ_cut_kernel, dim3(b.n_asm), dim3(64 * OCC_WAVES), 0, stream, b, gene_len, an.keys, an.count, an.cap, an.kb, sc, 1);
 }
 
-void kp_launch_chain(const KpBatchView &b, const uint64_t *sorted_anchors, const uint32_t *anchor_count, uint32_t cap,
-                     KpKeyBits key_bits, KpTask *tasks, uint32_t *task_count, uint32_t task_cap, KpGroup *groups,
-                     uint32_t *group_count, uint32_t group_cap, hipStream_t stream) {
+void kp_launch_chain(const KpBatchView &b, const KpAnchors &an, const KpTasks &t, const KpGroups &groups, hipStream_t stream) {
     if (b.n_asm == 0) return;
     GroupOut go;
-    go.groups = groups; go.count = group_count; go.cap = group_cap;
-    hipLaunchKernelGGL(kp_chain_kernel, dim3(CHAIN_SLICES / CHAIN_WAVES, b.n_asm), dim3(64 * CHAIN_WAVES), 0, stream, b, sorted_anchors, anchor_count,
-                       cap, key_bits, tasks, task_count, task_cap, go);
+    go.groups = groups.list; go.count = groups.count; go.cap = groups.cap;
+    hipLaunchKernelGGL(kp_chain_kernel, dim3(CHAIN_SLICES / CHAIN_WAVES, b.n_asm), dim3(64 * CHAIN_WAVES), 0, stream, b, an.keys, an.count,
+                       an.cap, an.kb, t.tasks, t.count, t.cap, go);
 }

@@ -13,7 +13,7 @@
 //                       (kp_walk.h) with a visitor that merges columns of one kind into run-length ops; first to count the ops
 //                       of every hit, then -- after an exclusive scan of the counts -- to write them, last op first, since
 //                       the walk runs from the path's end to its start and ops are listed along the target
-//   kp_cigar_scan       the exclusive scan, one block (measured: 3.7 ms for 1.16 M hits -- DESIGN.md section 3; kp_cs.hip scans its byte counts with it)
+//   kp_cigar_scan       the exclusive scan, one block (measured: 3.1-3.8 ms for 1.16 M hits -- DESIGN.md section 3; kp_cs.hip scans its byte counts with it)
 //
 // The ops buffer is sized by the policy of kp_caps.h; the writing pass checks every store against its end, so a buffer that is
 // too small loses ops but nothing else, and the counts say how much room the repeat needs.
@@ -180,14 +180,13 @@ __global__ __launch_bounds__(SCAN_THREADS) void kp_cigar_scan_kernel(const uint3
 
 }  // namespace
 
-void kp_launch_cigar_locate(const KpBatchView &b, const int32_t *gene_len, const KpTask *tasks, const KpSwResult *results, const uint8_t *task_drop,
-                            const uint32_t *task_count, uint32_t task_cap, const KpJoin *joins, const uint32_t *join_count, uint32_t join_cap,
-                            const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap, unsigned long long *src, hipStream_t stream) {
-    (void)hipMemsetAsync(src, 0xFF, (size_t)b.n_asm * hit_cap * sizeof(unsigned long long), stream);
-    hipLaunchKernelGGL(kp_cigar_locate_tasks_kernel, dim3(256, KP_N_CLASSES), dim3(256), 0, stream, b, gene_len, tasks, results, task_drop, task_count,
-                       task_cap, hits, n_hits, hit_cap, src);
-    hipLaunchKernelGGL(kp_cigar_locate_joins_kernel, dim3(16, KP_N_CLASSES), dim3(64), 0, stream, b, gene_len, joins, join_count, join_cap, hits,
-                       n_hits, hit_cap, src);
+void kp_launch_cigar_locate(const KpBatchView &b, const int32_t *gene_len, const KpTasks &t, const KpJoins &j, const KpHitTable &hits,
+                            unsigned long long *src, hipStream_t stream) {
+    (void)hipMemsetAsync(src, 0xFF, (size_t)b.n_asm * hits.cap * sizeof(unsigned long long), stream);
+    hipLaunchKernelGGL(kp_cigar_locate_tasks_kernel, dim3(256, KP_N_CLASSES), dim3(256), 0, stream, b, gene_len, t.tasks, t.results, t.drop, t.count,
+                       t.cap, hits.rows, hits.count, hits.cap, src);
+    hipLaunchKernelGGL(kp_cigar_locate_joins_kernel, dim3(16, KP_N_CLASSES), dim3(64), 0, stream, b, gene_len, j.list, j.count, j.cap, hits.rows,
+                       hits.count, hits.cap, src);
 }
 
 // off[0 .. n] = exclusive scan of cnt[0 .. n): the scan above for any per-hit counts (kp_cs.hip: bytes of the cs strings)
@@ -195,20 +194,14 @@ void kp_launch_count_scan(const uint32_t *cnt, int64_t n, int64_t *off, hipStrea
     hipLaunchKernelGGL(kp_cigar_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, cnt, n, off);
 }
 
-static dim3 walk_grid(const KpBatchView &b) { return dim3((unsigned)std::min(std::max(b.n_asm, 1), 4096)); }
-
-void kp_launch_cigar_count(const KpBatchView &b, const KpGenes &genes, const KpTask *tasks, const KpSwEnd *ends, uint32_t task_cap, const KpJoin *joins,
-                           uint32_t join_cap, const void *trace, const uint32_t *n_hits, uint32_t hit_cap, const int64_t *hit_off,
-                           const unsigned long long *src, uint32_t *cnt, int64_t total_hits, int64_t *off, hipStream_t stream) {
-    hipLaunchKernelGGL(kp_cigar_walk_kernel<false>, walk_grid(b), dim3(WALK_THREADS), 0, stream, b, genes, tasks, ends, task_cap, joins, join_cap,
-                       reinterpret_cast<const uint4 *>(trace), n_hits, hit_cap, hit_off, src, cnt, (const int64_t *)nullptr, (uint32_t *)nullptr,
-                       (int64_t)0);
-    hipLaunchKernelGGL(kp_cigar_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, cnt, total_hits, off);
-}
-
-void kp_launch_cigar_emit(const KpBatchView &b, const KpGenes &genes, const KpTask *tasks, const KpSwEnd *ends, uint32_t task_cap, const KpJoin *joins,
-                          uint32_t join_cap, const void *trace, const uint32_t *n_hits, uint32_t hit_cap, const int64_t *hit_off,
-                          const unsigned long long *src, const int64_t *off, uint32_t *ops, int64_t ops_cap, hipStream_t stream) {
-    hipLaunchKernelGGL(kp_cigar_walk_kernel<true>, walk_grid(b), dim3(WALK_THREADS), 0, stream, b, genes, tasks, ends, task_cap, joins, join_cap,
-                       reinterpret_cast<const uint4 *>(trace), n_hits, hit_cap, hit_off, src, (uint32_t *)nullptr, off, ops, ops_cap);
+void kp_launch_cigar_walk(const KpBatchView &b, const KpGenes &genes, const KpTasks &t, const KpJoins &j, const KpTrace &trace, const KpHitTable &hits,
+                          const KpHitRows &rows, const unsigned long long *src, const KpPerHit<uint32_t> &cig, bool emit, hipStream_t stream) {
+    const dim3 grid((unsigned)std::min(std::max(b.n_asm, 1), 4096)), block(WALK_THREADS);
+    if (!emit) {
+        hipLaunchKernelGGL(kp_cigar_walk_kernel<false>, grid, block, 0, stream, b, genes, t.tasks, t.ends, t.cap, j.list, j.cap, trace.units, hits.count,
+                           hits.cap, rows.hit_off, src, cig.cnt, (const int64_t *)nullptr, (uint32_t *)nullptr, (int64_t)0);
+        return kp_launch_count_scan(cig.cnt, rows.total, cig.off, stream);
+    }
+    hipLaunchKernelGGL(kp_cigar_walk_kernel<true>, grid, block, 0, stream, b, genes, t.tasks, t.ends, t.cap, j.list, j.cap, trace.units, hits.count,
+                       hits.cap, rows.hit_off, src, (uint32_t *)nullptr, cig.off, cig.data, cig.cap);
 }

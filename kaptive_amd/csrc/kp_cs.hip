@@ -61,17 +61,13 @@ dim3 walk_grid(const KpBatchView &b) { return dim3((unsigned)std::min(std::max(b
 
 }  // namespace
 
-void kp_launch_cs_count(const KpBatchView &b, const KpGenes &genes, const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap,
-                        const int64_t *hit_off, const uint32_t *ops, const int64_t *cigar_off, int64_t ops_cap, uint32_t *cnt,
-                        int64_t total_hits, int64_t *off, hipStream_t stream) {
-    hipLaunchKernelGGL(kp_cs_walk_kernel<false>, walk_grid(b), dim3(WALK_THREADS), 0, stream, b, genes, hits, n_hits, hit_cap, hit_off, ops,
-                       cigar_off, ops_cap, cnt, (const int64_t *)nullptr, (char *)nullptr, (int64_t)0);
-    kp_launch_count_scan(cnt, total_hits, off, stream);
-}
-
-void kp_launch_cs_emit(const KpBatchView &b, const KpGenes &genes, const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap,
-                       const int64_t *hit_off, const uint32_t *ops, const int64_t *cigar_off, int64_t ops_cap, const int64_t *off,
-                       char *bytes, int64_t bytes_cap, hipStream_t stream) {
-    hipLaunchKernelGGL(kp_cs_walk_kernel<true>, walk_grid(b), dim3(WALK_THREADS), 0, stream, b, genes, hits, n_hits, hit_cap, hit_off, ops,
-                       cigar_off, ops_cap, (uint32_t *)nullptr, off, bytes, bytes_cap);
+void kp_launch_cs_walk(const KpBatchView &b, const KpGenes &genes, const KpHitTable &hits, const KpHitRows &rows, const KpPerHit<uint32_t> &cig,
+                       const KpPerHit<char> &cs, bool emit, hipStream_t stream) {
+    if (!emit) {
+        hipLaunchKernelGGL(kp_cs_walk_kernel<false>, walk_grid(b), dim3(WALK_THREADS), 0, stream, b, genes, hits.rows, hits.count, hits.cap, rows.hit_off,
+                           cig.data, cig.off, cig.cap, cs.cnt, (const int64_t *)nullptr, (char *)nullptr, (int64_t)0);
+        return kp_launch_count_scan(cs.cnt, rows.total, cs.off, stream);
+    }
+    hipLaunchKernelGGL(kp_cs_walk_kernel<true>, walk_grid(b), dim3(WALK_THREADS), 0, stream, b, genes, hits.rows, hits.count, hits.cap, rows.hit_off,
+                       cig.data, cig.off, cig.cap, (uint32_t *)nullptr, cs.off, cs.data, cs.cap);
 }

@@ -128,6 +128,9 @@ static void options_from_env(KpOptions &o) {
     { const char *rb = getenv("KAPTIVE_AMD_READBACK"); o.readback_copy_engine = rb && std::string(rb) == "copy"; }
     o.spin_wait = (int)env_u32("KAPTIVE_AMD_SPIN_WAIT", 0);
     o.join_stats = std::getenv("KAPTIVE_AMD_JOIN_STATS") != nullptr;
+    if (const char *e = std::getenv("KAPTIVE_AMD_JOIN_GRID")) std::sscanf(e, "%d,%d,%d,%d", &o.join.fill, &o.join.walk, &o.join.chain, &o.join.chain_large);
+    if (const char *e = std::getenv("KAPTIVE_AMD_JOIN_PRIO")) o.join.prio = std::atoi(e);
+    if (const char *e = std::getenv("KAPTIVE_AMD_SKIP_JOINS")) o.join.skip = std::atoi(e);
     g_debug_alloc = std::getenv("KAPTIVE_AMD_DEBUG_ALLOC") != nullptr;  // (process-wide: DevBuf knows no context)
 }
 

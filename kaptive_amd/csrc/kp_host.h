@@ -31,9 +31,8 @@ struct KpTypingRun {
     // from kp_ctx::group_streams, plain handles that the run does not destroy.  The two events are the run's own.
     hipStream_t stream = nullptr, aux = nullptr;
     Event ev_fork, ev_join;
-    bool split = false;  // hits / hit_n belong to the work set's most recent alignment pass
-    const kp_hit *hits = nullptr;    // the group's hit rows: d_hits, or the work set's table itself when the group
-    const uint32_t *hit_n = nullptr;  // spans every gene of the context (no copy)
+    bool split = false;  // `hits` belongs to the work set's most recent alignment pass
+    KpHitTable hits{};   // the group's hit rows: d_hits / d_hit_n, or the work set's table itself when the group spans every gene of the context (no copy)
     DevBuf<kp_hit> d_hits;
     DevBuf<uint32_t> d_hit_n;
     DevBuf<uint64_t> d_keys;   // cull keys
@@ -41,6 +40,7 @@ struct KpTypingRun {
     DevBuf<uint8_t> d_flag;
     DevBuf<int32_t> d_dp_scratch;
     int kept_cap = 0, piece_cap = 0, prot_cap = 0;
+    size_t n_asm = 0;  // assemblies of the most recent reduction: with kept_cap, the layout of d_pairs
     DevBuf<uint32_t> d_pack;  // kept / piece rows cut to the strides the caller asked for (kp_batch_typing)
     DevBuf<uint8_t> d_prot;
     DevBuf<double> d_scores;
@@ -53,6 +53,15 @@ struct KpTypingRun {
     bool sums_valid = false;  // h_sums / max_kept / max_pieces belong to the most recent reduction
     std::vector<KpAsmSummary> h_sums;
     int32_t max_kept = 1, max_pieces = 1;
+    // d_pairs: the pairs of the protein DP, one slot per kept row: q_off, q_len, t_off, t_len [slots each], then pair_base [n_asm], n_pairs [1]
+    size_t slots() const { return n_asm * (size_t)kept_cap; }
+    size_t pairs_len() const { return 4 * slots() + n_asm + 1; }
+    KpReduceTables tables() const {
+        int32_t *const q = d_pairs.p, *const base = q + 4 * slots();
+        return {.best = d_best.p, .keys = d_keys.p, .order = d_order.p, .kept_flag = d_flag.p, .kept = d_kept.p, .kept_cap = kept_cap,
+                .pieces = d_pieces.p, .piece_cap = piece_cap, .summary = d_summary.p, .prot = d_prot.p, .prot_cap = prot_cap,
+                .q_off = q, .q_len = q + slots(), .t_off = q + 2 * slots(), .t_len = q + 3 * slots(), .pair_base = base, .n_pairs = base + n_asm, .dp8 = d_dp.p};
+    }
 };
 
 struct kp_batch;
@@ -67,6 +76,7 @@ struct KpOptions : KpCapOptions {
     int cigar = 0;                  // CIGARs of the finished hits (kp_cigar.hip): off unless asked for; applies from the next kp_batch_align
     int cs = 0;                     // cs difference strings of the finished hits (kp_cs.hip); a pass with it computes the CIGARs too: cs reads them
     bool join_stats = false;        // KAPTIVE_AMD_JOIN_STATS: kp_batch_wait reports the pass's group / join / mid_occ counts on stderr
+    KpJoinLaunch join;              // KAPTIVE_AMD_JOIN_GRID / _JOIN_PRIO / _SKIP_JOINS: launch shape of the join kernels (kp_internal.h)
 };
 
 // Device copy of one batch's input (packed words + tables).  Recycled through the context (hipFree synchronises the
@@ -79,19 +89,41 @@ struct KpInput {
     Event ready;          // recorded on the copy stream after the last H2D copy of the batch
 };
 
+// Slots of KpWork::ev, each recorded after the stage named; kp_batch_profile returns the seven times between consecutive ones.
+// JOINED: after the join back, i.e. what is left of the join kernels once the band tasks are through (its "sw64" value); END: end
+// of the pass, recorded right behind it so that the layout stays (the last value reads 0).
+enum KpPassEvent { KP_EV_START, KP_EV_SCAN, KP_EV_SORT, KP_EV_ORDER, KP_EV_FILL, KP_EV_TRACEBACK, KP_EV_JOINED, KP_EV_END, KP_N_EVENTS };
+static_assert(KP_EV_END == 7, "kp_batch_profile returns seven stage times");
+enum KpStat { KP_STAT_ANCHORS, KP_STAT_TASKS, KP_STAT_CELLS, KP_STAT_HITS, KP_STAT_RERUNS, KP_N_STATS };  // KpWork::stats, kp_batch_stats
+enum KpTopWord { KP_TOP_TRACE = 0, KP_TOP_OCC = 3, KP_TOP_WORDS = 4 };  // d_trace_top: [0] trace units handed out, [1..2] the fill kernel's quad counters (four 32-bit words), [3] the occurrence cut's demand
+enum KpJoinCount { KP_JOIN_GROUPS = 0, KP_JOIN_CLASSES = 1, KP_JOIN_COUNTS = 1 + KP_N_CLASSES };  // d_join_counts: [0] groups, [1 + c] joins of band class c
+enum KpCandCount { KP_CAND_FRONT, KP_CAND_BACK, KP_CAND_COUNTS };  // d_cand_count: the streaming kernel's candidates (front of the list), the edge kernel's (back)
+
 // Work set: every device buffer an alignment pass and the reductions after it write, and the results they leave.  A
 // context owns KP_WORK_SLOTS of them and hands them to batches round-robin at kp_batch_align, so a stream of batches
 // allocates nothing after the first few and keeps what it learnt about buffer sizes (the caps live in the context).
-// Its base is what the buffers of the most recent pass were sized for.
+// Its base is what the buffers of the most recent pass were sized for.  The packed blocks (several tables behind one
+// allocation, one memset and one read-back) are laid out here and nowhere else: each has its length, an accessor per
+// region and, where the host keeps a mirror, the same for the mirror.
 struct KpWork : KpPassCaps {
     kp_batch *owner = nullptr;
+    size_t n_asm = 0;  // assemblies of `owner` (kp_batch_align): the blocks below are laid out by it
     KpKeyBits key_bits{16, 30};  // compact anchor keys of the most recent alignment pass
     DevBuf<uint64_t> d_anchors_a, d_anchors_b;
-    DevBuf<uint32_t> d_counts;  // [n_asm] anchor counts, [KP_N_CLASSES] task counts, [n_asm] largest sub-slice demand
+    DevBuf<uint32_t> d_counts;  // [n_asm] anchor counts, [KP_N_CLASSES] task counts, [n_asm] largest sub-slice demand; h_counts mirrors it
+    size_t task_count_at() const { return n_asm; }
+    size_t slice_need_at() const { return n_asm + KP_N_CLASSES; }
+    size_t counts_len() const { return slice_need_at() + n_asm; }
+    const uint32_t *h_anchor_count() const { return h_counts.data(); }
+    const uint32_t *h_task_count() const { return h_counts.data() + task_count_at(); }
+    const uint32_t *h_slice_need() const { return h_counts.data() + slice_need_at(); }
     DevBuf<uint32_t> d_sub_counts;  // [n_asm * KP_ANCHOR_SUBS]
     DevBuf<uint64_t> d_cand;        // candidates of the scan (kp_cand_pack); d_cand_count[0] = how many
     DevBuf<unsigned long long> d_cand_count;
-    DevBuf<uint32_t> d_seg;     // [2 * n_asm]
+    DevBuf<uint32_t> d_seg;     // the library sort's segments: [n_asm] begin, [n_asm] end
+    size_t seg_len() const { return 2 * n_asm; }
+    uint32_t *seg_begin() const { return d_seg.p; }
+    uint32_t *seg_end() const { return d_seg.p + n_asm; }
     DevBuf<KpTask> d_tasks;
     DevBuf<KpSwResult> d_results;
     // d_task_drop, per task slot: a chain consumed the cluster, its band task reports no hit (kp_join.hip)
@@ -100,7 +132,8 @@ struct KpWork : KpPassCaps {
     DevBuf<uint32_t> d_occ_keys, d_occ_cnts, d_occ_state;
     uint32_t occ_log2 = 0;
     DevBuf<KpSwEnd> d_ends;
-    DevBuf<unsigned long long> d_trace_top;
+    DevBuf<unsigned long long> d_trace_top;  // [KP_TOP_WORDS]
+    unsigned long long *occ_demand() const { return d_trace_top.p + KP_TOP_OCC; }
     // A work set's alignment pass runs on the set's own stream with its own trace buffer and sort scratch: the passes of
     // consecutive batches overlap on the device (the seed scan and the sort of one wait on the L2 and on HBM while the
     // fill kernel of the other keeps the vector ALUs busy)
@@ -111,16 +144,22 @@ struct KpWork : KpPassCaps {
     Event ev_jfork, ev_jdone;
     DevBuf<uint4> d_trace;  // direction bits of the banded Smith-Waterman: written by the fill kernel, read by the traceback
     DevBlock sort_temp;  // the library sort's scratch
-    DevBuf<uint32_t> d_task_order;  // [KP_ORDER_HEAD] histogram + cursors, then [KP_N_CLASSES * task_cap] permutation
-    // kp-align v4 (kp_join.hip): groups of provisional clusters, joins per band class, their counts ([0] groups, [1 + c] joins)
+    DevBuf<uint32_t> d_task_order;  // [KP_ORDER_HEAD] histogram + cursors (KP_ORDER_COUNTS inside), then [KP_N_CLASSES * task_cap] permutation
+    size_t order_len() const { return KP_ORDER_HEAD + KP_N_CLASSES * (size_t)task_cap; }
+    // kp-align v4 (kp_join.hip): groups of provisional clusters, joins per band class, their counts
     DevBuf<KpGroup> d_groups;
     DevBuf<KpJoin> d_joins;
     DevBuf<uint32_t> d_join_counts;
-    uint32_t h_join_counts[1 + KP_N_CLASSES] = {};
+    uint32_t h_join_counts[KP_JOIN_COUNTS] = {};
+    uint32_t h_group_count() const { return h_join_counts[KP_JOIN_GROUPS]; }
+    const uint32_t *h_join_count() const { return h_join_counts + KP_JOIN_CLASSES; }
     std::vector<KpJoin> h_joins;  // fetched on first use (kp_batch_joins: stage tests only)
     // device-side hit tables (per-assembly regions of hit_cap rows)
     DevBuf<kp_hit> d_hits_raw, d_hits;
-    DevBuf<uint32_t> d_hit_counts;  // [n_asm] raw, then [n_asm] final
+    DevBuf<uint32_t> d_hit_counts;  // [n_asm] raw, then [n_asm] final; h_hit_counts mirrors it
+    size_t hit_counts_len() const { return 2 * n_asm; }
+    uint32_t *h_raw_hit_count() { return h_hit_counts.data(); }
+    uint32_t *h_hit_count() { return h_hit_counts.data() + n_asm; }
     DevBuf<uint64_t> d_keys;        // 3 per hit row
     DevBuf<unsigned long long> d_cells;
     // CIGARs of the finished hits (kp_cigar.hip), only where the pass was enqueued with the `cigar` option: nothing below is
@@ -145,8 +184,26 @@ struct KpWork : KpPassCaps {
     std::vector<uint32_t> h_counts, h_hit_counts;
     std::vector<KpTask> h_tasks[KP_N_CLASSES];
     std::vector<int64_t> hit_off;
-    int64_t stats[5] = {0, 0, 0, 0, 0};
-    Event ev[4 + KP_N_CLASSES];  // stage boundaries of the most recent alignment pass; the last one marks its end
+    int64_t stats[KP_N_STATS] = {};
+    Event ev[KP_N_EVENTS];  // stage boundaries of the most recent alignment pass
+    // the views the launchers take (kp_internal.h), built here and nowhere else
+    KpAnchors anchors() const {
+        return {.keys = d_anchors_a.p, .count = d_counts.p, .cap = anchor_cap, .kb = key_bits, .sub_count = d_sub_counts.p,
+                .sub_cap = anchor_cap / KP_ANCHOR_SUBS, .second = d_anchors_b.p, .need = d_counts.p + slice_need_at()};
+    }
+    KpTasks tasks() const {
+        return {.tasks = d_tasks.p, .count = d_counts.p + task_count_at(), .cap = task_cap, .results = d_results.p, .ends = d_ends.p, .drop = d_task_drop.p,
+                .order_head = d_task_order.p, .order_count = d_task_order.p + KP_ORDER_COUNTS, .order = d_task_order.p + KP_ORDER_HEAD};
+    }
+    KpGroups groups() const { return {.list = d_groups.p, .count = d_join_counts.p + KP_JOIN_GROUPS, .cap = group_cap}; }
+    KpJoins joins() const { return {.list = d_joins.p, .count = d_join_counts.p + KP_JOIN_CLASSES, .cap = join_cap}; }
+    KpTrace trace() const { return {.units = d_trace.p, .top = d_trace_top.p + KP_TOP_TRACE, .cap = trace_cap}; }
+    KpHitTable raw_hits() const { return {.rows = d_hits_raw.p, .count = d_hit_counts.p, .cap = hit_cap, .keys = d_keys.p}; }
+    KpHitTable hits() const { return {.rows = d_hits.p, .count = d_hit_counts.p + n_asm, .cap = hit_cap, .keys = nullptr}; }
+    KpHitRows hit_rows() const { return {.hit_off = d_cig_hit_off.p, .total = hit_off[n_asm]}; }
+    KpPerHit<uint32_t> cigars() const { return {.cnt = d_cig_cnt.p, .off = d_cig_off.p, .data = d_cig_ops.p, .cap = (int64_t)cigar_cap}; }
+    KpPerHit<char> cs() const { return {.cnt = d_cs_cnt.p, .off = d_cs_off.p, .data = d_cs_bytes.p, .cap = (int64_t)cs_cap}; }
+    void reset_runs() { for (auto &r : runs) if (r) r->split = r->scored = r->reduced = r->sums_valid = false; }  // their hit table is about to be rewritten
 };
 
 #define KP_INPUT_POOL 16  /* recycled device copies of batch inputs: uploads run several shards ahead of the passes that read them */
@@ -182,6 +239,8 @@ struct kp_ctx {
     // protein stage
     DevBuf<int8_t> d_blosum;
     DevBuf<float> d_ln;  // logarithm tables of the mapping quality (kp_mapq.h): ln(i / 2), then ln(i), from kp_mapq_ln
+    const float *ln_half() const { return d_ln.p; }
+    const float *ln_int() const { return d_ln.p + KP_MAPQ_LN_HALF_SIZE; }
     DevBuf<uint8_t> d_pq, d_pt;
     DevBuf<int32_t> d_pmeta, d_pout, d_pscratch;
     // typing tables (kp_db_load_typing / kp_db_load_typing_group): one set per database whose genes are in the index

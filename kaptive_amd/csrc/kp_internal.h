@@ -213,42 +213,93 @@ struct KpJoin {
 struct kp_ctx;
 int kp_fail(kp_ctx *ctx, int code, const std::string &msg);
 
+// ---- host-side views of a pass's device tables ------------------------------------------------------------------
+// Plain structs of pointers with the cap that bounds them, built in one place from the work set (kp_host.h: KpWork::anchors(),
+// tasks(), ...; KpTypingRun::tables()) and taken by the launchers below.  A view never crosses into a kernel: a launcher spreads
+// it into the kernel's own `__restrict__` parameters.  That is measured, not taste: the compiler attaches `noalias` to kernel
+// pointer parameters only, so with loose parameters a uniform counter read inside a grid-stride loop stays one scalar load ahead
+// of the loop, while with a struct -- `__restrict__` members, plain members or members unpacked into local `__restrict__`
+// pointers alike -- it becomes a global_load_dword inside the loop (class-region kernel of this code base's shape, gfx950).
+// The kernels' parameter types carry the `const`; per-class and per-assembly regions are `cap` entries apart.
+struct KpAnchors {
+    uint64_t *keys;       // the scan's sub-slices (sub_cap * KP_ANCHOR_SUBS per assembly), then each assembly's sorted run
+    uint32_t *count;      // [n_asm]
+    uint32_t cap;
+    KpKeyBits kb;
+    uint32_t *sub_count;  // [n_asm * KP_ANCHOR_SUBS]: sub_count[a * KP_ANCHOR_SUBS + s] keeps counting past sub_cap = overflow
+    uint32_t sub_cap;
+    uint64_t *second;     // the sorts' other buffer
+    uint32_t *need;       // [n_asm] largest sub-slice demand
+    uint64_t *of(size_t a) const { return keys + a * cap; }
+};
+struct KpTasks {
+    KpTask *tasks;
+    uint32_t *count;  // [KP_N_CLASSES]
+    uint32_t cap;
+    KpSwResult *results;
+    KpSwEnd *ends;
+    uint8_t *drop;    // per task slot: a chain consumed the cluster, its band task reports no hit (kp_join.hip)
+    uint32_t *order_head, *order_count, *order;  // KP_ORDER_HEAD words, the KP_ORDER_COUNTS inside them, the permutation
+    KpTask *cls(int c) const { return tasks + (size_t)c * cap; }
+    KpSwResult *cls_results(int c) const { return results + (size_t)c * cap; }
+};
+struct KpGroups { KpGroup *list; uint32_t *count; uint32_t cap; };
+struct KpJoins { KpJoin *list; uint32_t *count /* [KP_N_CLASSES] */; uint32_t cap; KpJoin *cls(int c) const { return list + (size_t)c * cap; } };
+struct KpTrace { uint4 *units; unsigned long long *top; uint64_t cap; };  // 16-byte units; *top: units the pass needs
+struct KpHitTable {  // the finished table, the raw one with its sort keys, or a typing run's split table
+    kp_hit *rows;
+    uint32_t *count;  // [n_asm]
+    uint32_t cap;
+    uint64_t *keys;   // the raw table's sort keys, 3 per row; null in every other table
+    kp_hit *of(size_t a) const { return rows + a * cap; }
+};
+struct KpHitRows { const int64_t *hit_off; int64_t total; };  // rows as kp_batch_hits lists them: device hit_off[n_asm + 1]
+template <class T>
+struct KpPerHit { uint32_t *cnt; int64_t *off; T *data; int64_t cap; };  // per finished hit: items counted, scanned (off[total + 1]), written
+struct KpReduceTables {  // what the reduction, the protein DP of its kept hits and the gene states share (types: kp_reduce_core.h)
+    const int32_t *best;
+    uint64_t *keys;
+    uint32_t *order;
+    uint8_t *kept_flag;
+    kp_kept *kept; int kept_cap;
+    kp_piece *pieces; int piece_cap;
+    kp_asm_summary *summary;
+    uint8_t *prot; int prot_cap;
+    int32_t *q_off, *q_len, *t_off, *t_len, *pair_base, *n_pairs;  // the compact pair list; its length lives on the device
+    int32_t *dp8;
+};
+// grids and wave priority of the join kernels: options of the context (KAPTIVE_AMD_JOIN_GRID = "fill,walk,chain,chain_large" blocks
+// (per band class for the first two), KAPTIVE_AMD_JOIN_PRIO = 0 | 1: experiments; the defaults are what
+// tools/experiments/join_cost_ab.sh measured; KAPTIVE_AMD_SKIP_JOINS: debugging aid, bit 0 chaining, 1 fill, 2 walk-back)
+struct KpJoinLaunch { int fill = 2048, walk = 512, chain = 2560, chain_large = 512, prio = 1, skip = 0; };  // (blocks without work leave at once: a large grid costs nothing measurable)
+
 // ---- kernel launchers (one per .hip file) ------------------------------------------------------------------------
 // kp_scan.hip: pass 1 streams the packed contigs and records candidate positions (selected k-mers that pass the presence
 //   filters) at the front of `cand` (cand_cap words, kp_cand_pack; n_cand[0] counts them), the edge kernel the seeds next
 //   to contig ends and N runs at its back (n_cand[1]); n_cand[0] + n_cand[1] > cand_cap = overflow; pass 2 turns
-//   candidates into anchor keys.  Each
-//   assembly's anchor region of sub_cap * KP_ANCHOR_SUBS keys is cut into KP_ANCHOR_SUBS sub-slices with their own
-//   counters (sub_count[a * KP_ANCHOR_SUBS + s] keeps counting past sub_cap = overflow); kp_launch_anchor_compact then
-//   packs each assembly's slices into one run.  `after_scan` (optional) is recorded between the two passes.
+//   candidates into anchor keys.  Each assembly's anchor region is cut into KP_ANCHOR_SUBS sub-slices with their own counters
+//   (KpAnchors); kp_launch_anchor_compact then packs each assembly's slices into one run in `second`.  `after_scan`
+//   (optional) is recorded between the two passes.
 #define KP_ANCHOR_SUBS 64
-void kp_launch_scan(const KpBatchView &b, const KpSeedIndex &idx, uint64_t *cand, unsigned long long *n_cand,
-                    uint64_t cand_cap, uint64_t *anchors, uint32_t *sub_count, uint32_t sub_cap, KpKeyBits key_bits,
-                    int ablate_mode, int32_t n_ctg_total, hipStream_t stream, hipEvent_t after_scan);
-void kp_launch_anchor_compact(const KpBatchView &b, const uint64_t *sliced, const uint32_t *sub_count, uint32_t sub_cap,
-                              uint64_t *out, uint32_t *count, uint32_t *need, hipStream_t stream);
+void kp_launch_scan(const KpBatchView &b, const KpSeedIndex &idx, uint64_t *cand, unsigned long long *n_cand, uint64_t cand_cap,
+                    const KpAnchors &an, int ablate_mode, int32_t n_ctg_total, hipStream_t stream, hipEvent_t after_scan);
+void kp_launch_anchor_compact(const KpBatchView &b, const KpAnchors &an, hipStream_t stream);
 // kp_chain.hip: the occurrence cut on the sorted anchors (kp_spec.h, OCCURRENCE CUT): seeds with more anchors in an assembly than
-// minimap2's mid_occ of that assembly lose them; the lists are compacted in place and anchor_count updated.  occ_keys / occ_cnts:
+// minimap2's mid_occ of that assembly lose them; the lists are compacted in place and their counts updated.  occ_keys / occ_cnts:
 // `occ_slots` counting tables of 2^occ_log2_size entries for the assemblies that need their quantile worked out (a gene seed
 // beyond the floor of ten); occ_state: 2 * n_asm + occ_slots words of per-assembly state; *occ_demand (zeroed by the caller) ends
 // up as how many asked.
 size_t kp_occ_state_words(size_t n_asm, uint32_t occ_slots);  // 32-bit words of the occurrence cut's `occ_state`
-void kp_launch_occ_cut(const KpBatchView &b, const int32_t *gene_len, uint64_t *sorted_anchors, uint32_t *anchor_count, uint32_t cap,
-                       KpKeyBits key_bits, uint32_t *occ_keys, uint32_t *occ_cnts, uint32_t *occ_state, unsigned long long *occ_demand,
-                       uint32_t occ_slots, uint32_t occ_log2_size, hipStream_t stream);
-// kp_chain.hip: sorted anchors -> band tasks, appended per width class (class c region = tasks[c * cap ..)).
-void kp_launch_chain(const KpBatchView &b, const uint64_t *sorted_anchors, const uint32_t *anchor_count, uint32_t cap,
-                     KpKeyBits key_bits, KpTask *tasks, uint32_t *task_count /*[KP_N_CLASSES]*/, uint32_t task_cap,
-                     KpGroup *groups, uint32_t *group_count, uint32_t group_cap, hipStream_t stream);
+void kp_launch_occ_cut(const KpBatchView &b, const int32_t *gene_len, const KpAnchors &an, uint32_t *occ_keys, uint32_t *occ_cnts,
+                       uint32_t *occ_state, unsigned long long *occ_demand, uint32_t occ_slots, uint32_t occ_log2_size, hipStream_t stream);
+// kp_chain.hip: sorted anchors -> band tasks, appended per width class, and the groups of their clusters
+void kp_launch_chain(const KpBatchView &b, const KpAnchors &an, const KpTasks &tasks, const KpGroups &groups, hipStream_t stream);
 // kp_sw.hip: banded Smith-Waterman of every ORDERED task; class c (16/32/64/128 diagonals) has its tasks, order, ends and
-// results at c * task_cap and the length of its order at ordered_count[c]; one fill launch covers all four, one traceback launch follows.
-// `trace` holds trace_cap_units 16-byte units; *trace_top (zeroed by the caller) ends up as the units the pass needs.
-void kp_launch_sw(const KpBatchView &b, const KpGenes &genes, const KpTask *tasks, const uint32_t *ordered_count,
-                  uint32_t task_cap, const uint32_t *order, KpSwEnd *ends, void *trace, unsigned long long *trace_top,
-                  uint64_t trace_cap_units, KpSwResult *results, bool has_long_genes, hipStream_t stream,
-                  hipEvent_t after_fill);
+// results in its region and the length of its order at order_count[c]; one fill launch covers all four, one traceback launch follows.
+// *trace.top (zeroed by the caller) ends up as the units the pass needs.
+void kp_launch_sw(const KpBatchView &b, const KpGenes &genes, const KpTasks &tasks, const KpTrace &trace, bool has_long_genes, hipStream_t stream, hipEvent_t after_fill);
 // kp_chain.hip: settles the provisional tasks (chain score and anchor count of every cluster, or rejection: kp_spec.h), then
-// builds, per width class, a permutation of the surviving tasks ordered by query length (longest first).  `hist` is
+// builds, per width class, a permutation of the surviving tasks ordered by query length (longest first).  The order's head is
 // KP_ORDER_HEAD zeroed words: histogram, cursors and, at KP_ORDER_COUNTS, how many tasks each class's order holds.
 // (65 buckets per class: 64 by length for the packed fill kernel, the 65th holds the tasks of genes longer than
 // KP_FILL16_MAX_GENE_LEN, which come last in the order and are filled by kp_sw_long_kernel; counts: [KP_N_CLASSES] ordinary,
@@ -256,63 +307,39 @@ void kp_launch_sw(const KpBatchView &b, const KpGenes &genes, const KpTask *task
 #define KP_ORDER_BUCKETS 65
 #define KP_ORDER_COUNTS (2 * KP_N_CLASSES * KP_ORDER_BUCKETS)
 #define KP_ORDER_HEAD (KP_ORDER_COUNTS + 2 * KP_N_CLASSES)
-void kp_launch_task_order(const KpBatchView &b, const KpGenes &genes, const uint64_t *sorted_anchors, uint32_t cap, KpKeyBits key_bits,
-                          KpTask *tasks, const uint32_t *task_count, uint32_t task_cap, KpSwResult *results, uint32_t *hist,
-                          uint32_t *order, hipStream_t stream);
-// kp_join.hip (kp-align v5): groups -> joins (one list per band class: joins[c * join_cap ..), join_count[c]); the joined fill and
-// walk-back of every join (direction bytes and exports come out of the same trace buffer as the band tasks', in multiples of
-// 128 bytes); band tasks whose clusters a chain consumes get their flag in `task_drop` (one byte per task slot and class).
-void kp_launch_join_chain(const KpBatchView &b, const KpGenes &genes, const uint64_t *sorted_anchors, uint32_t anchor_cap, KpKeyBits kb,
-                          const KpTask *tasks, uint32_t task_cap, const KpGroup *groups, const uint32_t *group_count, uint32_t group_cap,
-                          KpJoin *joins, uint32_t *join_count, uint32_t join_cap, uint8_t *scratch, hipStream_t stream);
-size_t kp_join_chain_scratch_bytes();  // `scratch`: working arrays of the chaining instance for groups beyond 1024 anchors
-void kp_launch_join_fill(const KpBatchView &b, const KpGenes &genes, KpJoin *joins, const uint32_t *join_count, uint32_t join_cap,
-                         void *trace, unsigned long long *trace_top, uint64_t trace_cap_units, hipStream_t stream);
-void kp_launch_join_trace(const KpBatchView &b, const KpGenes &genes, KpJoin *joins, const uint32_t *join_count, uint32_t join_cap,
-                          uint32_t task_cap, const void *trace, uint8_t *task_drop, hipStream_t stream);
+void kp_launch_task_order(const KpBatchView &b, const KpGenes &genes, const KpAnchors &an, const KpTasks &tasks, hipStream_t stream);
+// kp_join.hip (kp-align v5): groups -> joins (one list per band class); the joined fill and walk-back of every join (direction
+// bytes and exports come out of the same trace buffer as the band tasks', in multiples of 128 bytes); band tasks whose clusters
+// a chain consumes get their flag in tasks.drop.  `scratch`: working arrays of the chaining instance for groups beyond 1024 anchors.
+void kp_launch_join_chain(const KpAnchors &an, const KpTasks &tasks, const KpGroups &groups, const KpJoins &joins, uint8_t *scratch,
+                          const KpJoinLaunch &L, hipStream_t stream);
+size_t kp_join_chain_scratch_bytes(const KpJoinLaunch &L);
+void kp_launch_join_fill(const KpBatchView &b, const KpGenes &genes, const KpJoins &joins, const KpTrace &trace, const KpJoinLaunch &L, hipStream_t stream);
+void kp_launch_join_trace(const KpBatchView &b, const KpGenes &genes, const KpJoins &joins, const KpTasks &tasks, const KpTrace &trace,
+                          const KpJoinLaunch &L, hipStream_t stream);
 // kp_cigar.hip (only with the `cigar` option; after kp_launch_hit_finalise, while `trace` still holds the pass): which band task or
-// joined path every finished hit came from (src: one key per row of the hit tables), the ops of every hit counted (cnt, rows as
-// kp_batch_hits lists them: hit_off[a] + i) and scanned (off[total_hits + 1]), and the ops written -- stores beyond ops_cap are dropped.
-void kp_launch_cigar_locate(const KpBatchView &b, const int32_t *gene_len, const KpTask *tasks, const KpSwResult *results, const uint8_t *task_drop,
-                            const uint32_t *task_count, uint32_t task_cap, const KpJoin *joins, const uint32_t *join_count, uint32_t join_cap,
-                            const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap, unsigned long long *src, hipStream_t stream);
-void kp_launch_cigar_count(const KpBatchView &b, const KpGenes &genes, const KpTask *tasks, const KpSwEnd *ends, uint32_t task_cap, const KpJoin *joins,
-                           uint32_t join_cap, const void *trace, const uint32_t *n_hits, uint32_t hit_cap, const int64_t *hit_off,
-                           const unsigned long long *src, uint32_t *cnt, int64_t total_hits, int64_t *off, hipStream_t stream);
-void kp_launch_cigar_emit(const KpBatchView &b, const KpGenes &genes, const KpTask *tasks, const KpSwEnd *ends, uint32_t task_cap, const KpJoin *joins,
-                          uint32_t join_cap, const void *trace, const uint32_t *n_hits, uint32_t hit_cap, const int64_t *hit_off,
-                          const unsigned long long *src, const int64_t *off, uint32_t *ops, int64_t ops_cap, hipStream_t stream);
+// joined path every finished hit came from (src: one key per row of the hit table), then the walk: the ops of every hit counted
+// (cig.cnt) and scanned (cig.off), or with `emit` the ops written -- stores beyond cig.cap are dropped.
+void kp_launch_cigar_locate(const KpBatchView &b, const int32_t *gene_len, const KpTasks &tasks, const KpJoins &joins, const KpHitTable &hits,
+                            unsigned long long *src, hipStream_t stream);
+void kp_launch_cigar_walk(const KpBatchView &b, const KpGenes &genes, const KpTasks &tasks, const KpJoins &joins, const KpTrace &trace, const KpHitTable &hits,
+                          const KpHitRows &rows, const unsigned long long *src, const KpPerHit<uint32_t> &cig, bool emit, hipStream_t stream);
 void kp_launch_count_scan(const uint32_t *cnt, int64_t n, int64_t *off, hipStream_t stream);  // kp_cigar.hip's scan, for any per-hit counts
 // kp_cs.hip (only with the `cs` option; after the CIGAR ops are final): the bytes of every hit's cs string (kp_spec.h, CS) counted
-// (cnt, rows as kp_batch_hits lists them) and scanned (off[total_hits + 1]), and the bytes written forward from off[row] -- stores
-// beyond bytes_cap are dropped.  ops / cigar_off: what kp_launch_cigar_emit left; nothing here reads the trace buffer.
-void kp_launch_cs_count(const KpBatchView &b, const KpGenes &genes, const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap,
-                        const int64_t *hit_off, const uint32_t *ops, const int64_t *cigar_off, int64_t ops_cap, uint32_t *cnt,
-                        int64_t total_hits, int64_t *off, hipStream_t stream);
-void kp_launch_cs_emit(const KpBatchView &b, const KpGenes &genes, const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap,
-                       const int64_t *hit_off, const uint32_t *ops, const int64_t *cigar_off, int64_t ops_cap, const int64_t *off,
-                       char *bytes, int64_t bytes_cap, hipStream_t stream);
-// kp_prot.hip
+// (cs.cnt) and scanned (cs.off), or with `emit` the bytes written forward from cs.off[row] -- stores beyond cs.cap are dropped.
+// cig: what kp_launch_cigar_walk left; nothing here reads the trace buffer.
+void kp_launch_cs_walk(const KpBatchView &b, const KpGenes &genes, const KpHitTable &hits, const KpHitRows &rows, const KpPerHit<uint32_t> &cig,
+                       const KpPerHit<char> &cs, bool emit, hipStream_t stream);
 // kp_reduce.hip: assembly a's hits with gene in [gene_lo, gene_hi) (one run: hits are sorted by gene) -> out rows, gene
-// indices relative to gene_lo; out_n[a] = how many
-void kp_launch_hit_split(const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap, int32_t gene_lo, int32_t gene_hi,
-                         kp_hit *out, uint32_t *out_n, int32_t n_asm, hipStream_t stream);
+// indices relative to gene_lo; out.count[a] = how many
+void kp_launch_hit_split(const KpHitTable &hits, int32_t gene_lo, int32_t gene_hi, const KpHitTable &out, int32_t n_asm, hipStream_t stream);
 // kp_reduce.hip: hit-table finalisation, locus scores, the typing reduction and its gene states (types: kp_reduce_core.h)
 struct KpTypingDb;
-void kp_launch_hit_finalise(const KpBatchView &b, const int32_t *gene_len, const KpTask *tasks, const KpSwResult *results, const uint8_t *task_drop,
-                            const uint32_t *task_count, uint32_t task_cap, kp_hit *raw, uint32_t *n_raw, uint32_t hit_cap,
-                            uint64_t *keys, kp_hit *hits, uint32_t *n_hits, unsigned long long *cells, const float *ln_half,
-                            const float *ln_int, const KpJoin *joins, const uint32_t *join_count, uint32_t join_cap, hipStream_t stream);
-void kp_launch_score(const KpBatchView &b, const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap,
-                     const KpTypingDb &db, double min_cov, double *scores, int32_t *counts, hipStream_t stream);
-void kp_launch_reduce(const KpBatchView &b, const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap,
-                      const KpTypingDb &db, const kp_typing_params &prm, const int32_t *best, uint64_t *keys,
-                      uint32_t *order, uint8_t *kept_flag, kp_kept *kept, int kept_cap, kp_piece *pieces, int piece_cap,
-                      kp_asm_summary *summary, uint8_t *prot, int prot_cap, int32_t *pair_q_off, int32_t *pair_q_len,
-                      int32_t *pair_t_off, int32_t *pair_t_len, int32_t *n_pairs, int32_t *pair_base,
-                      hipStream_t stream);
-void kp_launch_states(const KpBatchView &b, const KpTypingDb &db, const kp_typing_params &prm, kp_kept *kept, int kept_cap,
-                      kp_asm_summary *summary, const int32_t *dp8, const int32_t *pair_base, hipStream_t stream);
+void kp_launch_hit_finalise(const KpBatchView &b, const int32_t *gene_len, const KpTasks &tasks, const KpJoins &joins, const KpHitTable &raw,
+                            const KpHitTable &hits, unsigned long long *cells, const float *ln_half, const float *ln_int, hipStream_t stream);
+void kp_launch_score(const KpBatchView &b, const KpHitTable &hits, const KpTypingDb &db, double min_cov, double *scores, int32_t *counts, hipStream_t stream);
+void kp_launch_reduce(const KpBatchView &b, const KpHitTable &hits, const KpTypingDb &db, const kp_typing_params &prm, const KpReduceTables &t, hipStream_t stream);
+void kp_launch_states(const KpBatchView &b, const KpTypingDb &db, const kp_typing_params &prm, const KpReduceTables &t, hipStream_t stream);
 // kp_reduce.hip: `bytes` (a multiple of 4) of device memory into page-locked host memory, written by a kernel
 void kp_launch_read_back(const void *src, void *dst_pinned, size_t bytes, hipStream_t stream);
 void kp_launch_pack_rows(const uint32_t *src, size_t src_pitch, uint32_t *dst, size_t dst_pitch, size_t width, int rows,
@@ -323,13 +350,10 @@ void kp_launch_protein(const uint8_t *q, const int32_t *q_off, const int32_t *q_
                        int32_t *out8, int32_t *scratch, size_t scratch_ints_per_block, int n_blocks, hipStream_t stream,
                        hipStream_t aux, hipEvent_t fork, hipEvent_t join,  // aux != null: wide-band kernel runs beside the other
                        const int32_t *seed_off = nullptr, int seed_k = 0);  // seeded mode: one diagonal offset per pair, band k
-// kp_bsort.hip: sub-slices -> sorted run per assembly by buckets of the key's gene/strand field (one block per assembly);
-// count[a] / need[a] as kp_launch_anchor_compact leaves them.  n_bins = 2 * genes; kp_bsort_fits says whether it can run.
+// kp_bsort.hip: sub-slices -> sorted run per assembly (in `keys`, through `second`) by buckets of the key's gene/strand field (one
+// block per assembly); count[a] / need[a] as kp_launch_anchor_compact leaves them.  n_bins = 2 * genes; kp_bsort_fits says whether it can run.
 bool kp_bsort_fits(uint32_t n_bins);
-void kp_launch_anchor_bsort(const KpBatchView &b, const uint64_t *sliced, const uint32_t *sub_count, uint32_t sub_cap,
-                            uint64_t *grouped, uint64_t *out, uint32_t *count, uint32_t *need, uint32_t n_bins,
-                            KpKeyBits kb, hipStream_t stream);
-// kp_sort.hip: segmented sort of the anchor regions (wraps rocPRIM)
-int kp_sort_anchors(kp_ctx *ctx, uint64_t *keys_in, uint64_t *keys_out, const uint32_t *d_count, uint32_t cap,
-                    int32_t n_asm, void **temp, size_t *temp_bytes, uint32_t *d_seg_begin, uint32_t *d_seg_end,
-                    int end_bit, hipStream_t stream);
+void kp_launch_anchor_bsort(const KpBatchView &b, const KpAnchors &an, uint32_t n_bins, hipStream_t stream);
+// kp_sort.hip: segmented sort of the anchor regions, `second` -> `keys` (wraps rocPRIM)
+int kp_sort_anchors(kp_ctx *ctx, const KpAnchors &an, int32_t n_asm, void **temp, size_t *temp_bytes, uint32_t *d_seg_begin,
+                    uint32_t *d_seg_end, int end_bit, hipStream_t stream);

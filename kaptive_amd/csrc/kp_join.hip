@@ -23,8 +23,6 @@
 // some twenty joins per thousand assemblies on the headline workload, 55 per assembly on `bench.py --mix joins`.
 #include "kp_internal.h"
 #include "kp_walk.h"
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -552,49 +550,26 @@ __global__ __launch_bounds__(64) void kp_join_trace_kernel(KpBatchView b, KpGene
 
 }  // namespace
 
-// grids and wave priority of the join kernels (KAPTIVE_AMD_JOIN_GRID = "fill,walk,chain,chain_large" blocks (per band class for the
-// first two), KAPTIVE_AMD_JOIN_PRIO = 0 | 1: experiments; the defaults are what tools/experiments/join_cost_ab.sh measured)
-struct JoinLaunch { int fill = 2048, walk = 512, chain = 2560, chain_large = 512, prio = 1; };  // (blocks without work leave at once: a large grid costs nothing measurable)
-static const JoinLaunch &join_launch() {
-    static const JoinLaunch cfg = [] {
-        JoinLaunch c;
-        if (const char *e = std::getenv("KAPTIVE_AMD_JOIN_GRID")) std::sscanf(e, "%d,%d,%d,%d", &c.fill, &c.walk, &c.chain, &c.chain_large);
-        if (const char *e = std::getenv("KAPTIVE_AMD_JOIN_PRIO")) c.prio = std::atoi(e);
-        return c;
-    }();
-    return cfg;
+void kp_launch_join_chain(const KpAnchors &an, const KpTasks &t, const KpGroups &g, const KpJoins &j, uint8_t *scratch, const KpJoinLaunch &L, hipStream_t stream) {
+    if (L.skip & 1) return;
+    hipLaunchKernelGGL((kp_join_chain_kernel<JA_SMALL, 0>), dim3(L.chain), dim3(64), 0, stream, an.keys, an.cap, an.kb, t.tasks, t.cap, g.list,
+                       g.count, g.cap, j.list, j.count, j.cap, L.prio, (uint8_t *)nullptr);
+    hipLaunchKernelGGL((kp_join_chain_kernel<JA_MAX, JA_SMALL>), dim3(L.chain_large), dim3(64), 0, stream, an.keys, an.cap, an.kb, t.tasks, t.cap, g.list,
+                       g.count, g.cap, j.list, j.count, j.cap, L.prio, scratch);
 }
 
-void kp_launch_join_chain(const KpBatchView &b, const KpGenes &genes, const uint64_t *sorted_anchors, uint32_t anchor_cap, KpKeyBits kb,
-                          const KpTask *tasks, uint32_t task_cap, const KpGroup *groups, const uint32_t *group_count, uint32_t group_cap,
-                          KpJoin *joins, uint32_t *join_count, uint32_t join_cap, uint8_t *scratch, hipStream_t stream) {
-    (void)b; (void)genes;
-    if (const char *e = std::getenv("KAPTIVE_AMD_SKIP_JOINS")) if (std::atoi(e) & 1) return;  // (debugging aid: bit 0 chaining, 1 fill, 2 walk-back)
-    const JoinLaunch &L = join_launch();
-    hipLaunchKernelGGL((kp_join_chain_kernel<JA_SMALL, 0>), dim3(L.chain), dim3(64), 0, stream, sorted_anchors, anchor_cap, kb, tasks, task_cap, groups,
-                       group_count, group_cap, joins, join_count, join_cap, L.prio, (uint8_t *)nullptr);
-    hipLaunchKernelGGL((kp_join_chain_kernel<JA_MAX, JA_SMALL>), dim3(L.chain_large), dim3(64), 0, stream, sorted_anchors, anchor_cap, kb, tasks, task_cap, groups,
-                       group_count, group_cap, joins, join_count, join_cap, L.prio, scratch);
-}
-
-size_t kp_join_chain_scratch_bytes() { return (size_t)join_launch().chain_large * JOIN_CHAIN_SCRATCH; }
+size_t kp_join_chain_scratch_bytes(const KpJoinLaunch &L) { return (size_t)L.chain_large * JOIN_CHAIN_SCRATCH; }
 
 // The join kernels need nothing of the band tasks' fill and traceback: they run beside them, on a stream of their own
-// (kp_align.hip); the walk-back marks the band tasks whose hits a chain consumes (task_drop), which the hit compaction reads.
-void kp_launch_join_fill(const KpBatchView &b, const KpGenes &genes, KpJoin *joins, const uint32_t *join_count, uint32_t join_cap,
-                         void *trace, unsigned long long *trace_top, uint64_t trace_cap_units, hipStream_t stream) {
-    const char *skip_env = std::getenv("KAPTIVE_AMD_SKIP_JOINS");
-    if (skip_env && (std::atoi(skip_env) & 2)) return;
-    const JoinLaunch &L = join_launch();
-    hipLaunchKernelGGL(kp_join_fill_kernel, dim3(L.fill, KP_N_CLASSES), dim3(64), 0, stream, b, genes, joins, join_count, join_cap,
-                       reinterpret_cast<uint4 *>(trace), trace_top, trace_cap_units, L.prio);
+// (kp_align.hip); the walk-back marks the band tasks whose hits a chain consumes (tasks.drop), which the hit compaction reads.
+void kp_launch_join_fill(const KpBatchView &b, const KpGenes &genes, const KpJoins &j, const KpTrace &trace, const KpJoinLaunch &L, hipStream_t stream) {
+    if (L.skip & 2) return;
+    hipLaunchKernelGGL(kp_join_fill_kernel, dim3(L.fill, KP_N_CLASSES), dim3(64), 0, stream, b, genes, j.list, j.count, j.cap, trace.units, trace.top,
+                       trace.cap, L.prio);
 }
 
-void kp_launch_join_trace(const KpBatchView &b, const KpGenes &genes, KpJoin *joins, const uint32_t *join_count, uint32_t join_cap,
-                          uint32_t task_cap, const void *trace, uint8_t *task_drop, hipStream_t stream) {
-    const char *skip_env = std::getenv("KAPTIVE_AMD_SKIP_JOINS");
-    if (skip_env && (std::atoi(skip_env) & 4)) return;
-    const JoinLaunch &L = join_launch();
-    hipLaunchKernelGGL(kp_join_trace_kernel, dim3(L.walk, KP_N_CLASSES), dim3(64), 0, stream, b, genes, joins, join_count, join_cap, task_cap,
-                       reinterpret_cast<const uint4 *>(trace), task_drop, L.prio);
+void kp_launch_join_trace(const KpBatchView &b, const KpGenes &genes, const KpJoins &j, const KpTasks &t, const KpTrace &trace, const KpJoinLaunch &L, hipStream_t stream) {
+    if (L.skip & 4) return;
+    hipLaunchKernelGGL(kp_join_trace_kernel, dim3(L.walk, KP_N_CLASSES), dim3(64), 0, stream, b, genes, j.list, j.count, j.cap, t.cap, trace.units,
+                       t.drop, L.prio);
 }

@@ -548,11 +548,10 @@ void kp_launch_read_back(const void *src, void *dst_pinned, size_t bytes, hipStr
                        reinterpret_cast<uint32_t *>(dst_pinned), n);
 }
 
-void kp_launch_hit_split(const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap, int32_t gene_lo, int32_t gene_hi,
-                         kp_hit *out, uint32_t *out_n, int32_t n_asm, hipStream_t stream) {
+void kp_launch_hit_split(const KpHitTable &hits, int32_t gene_lo, int32_t gene_hi, const KpHitTable &out, int32_t n_asm, hipStream_t stream) {
     if (n_asm == 0) return;
-    hipLaunchKernelGGL(kp_hit_split_kernel, dim3(n_asm), dim3(256), 0, stream, hits, n_hits, hit_cap, gene_lo, gene_hi, out,
-                       out_n);
+    hipLaunchKernelGGL(kp_hit_split_kernel, dim3(n_asm), dim3(256), 0, stream, hits.rows, hits.count, hits.cap, gene_lo, gene_hi, out.rows,
+                       out.count);
 }
 
 void kp_launch_pack_rows(const uint32_t *src, size_t src_pitch, uint32_t *dst, size_t dst_pitch, size_t width, int rows,
@@ -561,41 +560,30 @@ void kp_launch_pack_rows(const uint32_t *src, size_t src_pitch, uint32_t *dst, s
     hipLaunchKernelGGL(kp_pack_rows_kernel, dim3(rows), dim3(256), 0, stream, src, src_pitch, dst, dst_pitch, width);
 }
 
-void kp_launch_hit_finalise(const KpBatchView &b, const int32_t *gene_len, const KpTask *tasks, const KpSwResult *results,
-                            const uint8_t *task_drop, const uint32_t *task_count, uint32_t task_cap, kp_hit *raw, uint32_t *n_raw, uint32_t hit_cap,
-                            uint64_t *keys, kp_hit *hits, uint32_t *n_hits, unsigned long long *cells,
-                            const float *ln_half, const float *ln_int, const KpJoin *joins, const uint32_t *join_count, uint32_t join_cap,
-                            hipStream_t stream) {
+void kp_launch_hit_finalise(const KpBatchView &b, const int32_t *gene_len, const KpTasks &t, const KpJoins &j, const KpHitTable &raw,
+                            const KpHitTable &hits, unsigned long long *cells, const float *ln_half, const float *ln_int, hipStream_t stream) {
     if (b.n_asm == 0) return;
-    hipLaunchKernelGGL(kp_hit_compact_kernel, dim3(512, KP_N_CLASSES), dim3(256), 0, stream, b, gene_len, tasks, results, task_drop, task_count,
-                       task_cap, raw, n_raw, hit_cap, cells);
-    hipLaunchKernelGGL(kp_join_hits_kernel, dim3(16, KP_N_CLASSES), dim3(64), 0, stream, b, gene_len, joins, join_count, join_cap, raw,
-                       n_raw, hit_cap, cells);
-    hipLaunchKernelGGL(kp_hit_sort_kernel, dim3(b.n_asm), dim3(SORT_THREADS), 0, stream, raw, n_raw, hit_cap, keys, hits,
-                       n_hits, ln_half, ln_int);
+    hipLaunchKernelGGL(kp_hit_compact_kernel, dim3(512, KP_N_CLASSES), dim3(256), 0, stream, b, gene_len, t.tasks, t.results, t.drop, t.count,
+                       t.cap, raw.rows, raw.count, raw.cap, cells);
+    hipLaunchKernelGGL(kp_join_hits_kernel, dim3(16, KP_N_CLASSES), dim3(64), 0, stream, b, gene_len, j.list, j.count, j.cap, raw.rows,
+                       raw.count, raw.cap, cells);
+    hipLaunchKernelGGL(kp_hit_sort_kernel, dim3(b.n_asm), dim3(SORT_THREADS), 0, stream, raw.rows, raw.count, raw.cap, raw.keys, hits.rows,
+                       hits.count, ln_half, ln_int);
 }
 
-void kp_launch_score(const KpBatchView &b, const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap,
-                     const KpTypingDb &db, double min_cov, double *scores, int32_t *counts, hipStream_t stream) {
+void kp_launch_score(const KpBatchView &b, const KpHitTable &hits, const KpTypingDb &db, double min_cov, double *scores, int32_t *counts, hipStream_t stream) {
     if (b.n_asm == 0) return;
-    hipLaunchKernelGGL(kp_score_kernel, dim3(b.n_asm), dim3(64), 0, stream, hits, n_hits, hit_cap, db, min_cov, scores, counts);
+    hipLaunchKernelGGL(kp_score_kernel, dim3(b.n_asm), dim3(64), 0, stream, hits.rows, hits.count, hits.cap, db, min_cov, scores, counts);
 }
 
-void kp_launch_reduce(const KpBatchView &b, const kp_hit *hits, const uint32_t *n_hits, uint32_t hit_cap,
-                      const KpTypingDb &db, const KpTypingParams &prm, const int32_t *best, uint64_t *keys,
-                      uint32_t *order, uint8_t *kept_flag, KpKept *kept, int kept_cap, KpPiece *pieces, int piece_cap,
-                      KpAsmSummary *summary, uint8_t *prot, int prot_cap, int32_t *pair_q_off, int32_t *pair_q_len,
-                      int32_t *pair_t_off, int32_t *pair_t_len, int32_t *n_pairs, int32_t *pair_base,
-                      hipStream_t stream) {
+void kp_launch_reduce(const KpBatchView &b, const KpHitTable &hits, const KpTypingDb &db, const KpTypingParams &prm, const KpReduceTables &t, hipStream_t stream) {
     if (b.n_asm == 0) return;
-    hipLaunchKernelGGL(kp_reduce_kernel, dim3(b.n_asm), dim3(64), 0, stream, b, hits, n_hits, hit_cap, db, prm, best, keys,
-                       order, kept_flag, kept, kept_cap, pieces, piece_cap, summary, prot, prot_cap, pair_q_off, pair_q_len,
-                       pair_t_off, pair_t_len, n_pairs, pair_base);
+    hipLaunchKernelGGL(kp_reduce_kernel, dim3(b.n_asm), dim3(64), 0, stream, b, hits.rows, hits.count, hits.cap, db, prm, t.best, t.keys,
+                       t.order, t.kept_flag, t.kept, t.kept_cap, t.pieces, t.piece_cap, t.summary, t.prot, t.prot_cap, t.q_off, t.q_len,
+                       t.t_off, t.t_len, t.n_pairs, t.pair_base);
 }
 
-void kp_launch_states(const KpBatchView &b, const KpTypingDb &db, const KpTypingParams &prm, KpKept *kept, int kept_cap,
-                      KpAsmSummary *summary, const int32_t *dp8, const int32_t *pair_base, hipStream_t stream) {
+void kp_launch_states(const KpBatchView &b, const KpTypingDb &db, const KpTypingParams &prm, const KpReduceTables &t, hipStream_t stream) {
     if (b.n_asm == 0) return;
-    hipLaunchKernelGGL(kp_state_kernel, dim3(b.n_asm), dim3(64), 0, stream, b, db, prm, kept, kept_cap, summary, dp8,
-                       pair_base);
+    hipLaunchKernelGGL(kp_state_kernel, dim3(b.n_asm), dim3(64), 0, stream, b, db, prm, t.kept, t.kept_cap, t.summary, t.dp8, t.pair_base);
 }

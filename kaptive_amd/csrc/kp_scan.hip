@@ -472,16 +472,14 @@ __global__ __launch_bounds__(256) void kp_anchor_compact_kernel(const uint64_t *
 
 }  // namespace
 
-void kp_launch_anchor_compact(const KpBatchView &b, const uint64_t *sliced, const uint32_t *sub_count, uint32_t sub_cap,
-                              uint64_t *out, uint32_t *count, uint32_t *need, hipStream_t stream) {
+void kp_launch_anchor_compact(const KpBatchView &b, const KpAnchors &an, hipStream_t stream) {
     if (b.n_asm == 0) return;
-    hipLaunchKernelGGL(kp_anchor_compact_kernel, dim3(b.n_asm), dim3(256), 0, stream, sliced, sub_count, sub_cap, out,
-                       count, need);
+    hipLaunchKernelGGL(kp_anchor_compact_kernel, dim3(b.n_asm), dim3(256), 0, stream, an.keys, an.sub_count, an.sub_cap, an.second,
+                       an.count, an.need);
 }
 
-void kp_launch_scan(const KpBatchView &b, const KpSeedIndex &idx, uint64_t *cand, unsigned long long *n_cand,
-                    uint64_t cand_cap, uint64_t *anchors, uint32_t *sub_count, uint32_t sub_cap, KpKeyBits key_bits,
-                    int mode, int32_t n_ctg_total, hipStream_t stream, hipEvent_t after_scan) {
+void kp_launch_scan(const KpBatchView &b, const KpSeedIndex &idx, uint64_t *cand, unsigned long long *n_cand, uint64_t cand_cap,
+                    const KpAnchors &an, int mode, int32_t n_ctg_total, hipStream_t stream, hipEvent_t after_scan) {
     if (b.total_words == 0) return;
     const int64_t n_units = b.total_words >> 2;
     int64_t blocks = ((n_units + SCAN_OWN - 1) / SCAN_OWN + DENSE_WAVES - 1) / DENSE_WAVES;
@@ -495,5 +493,5 @@ void kp_launch_scan(const KpBatchView &b, const KpSeedIndex &idx, uint64_t *cand
                            cand_cap, n_ctg_total);
     if (after_scan) (void)hipEventRecord(after_scan, stream);
     hipLaunchKernelGGL(kp_expand_kernel, dim3(256 * 8), dim3(256), 0, stream, b, idx, cand, n_cand, cand_cap,
-                       anchors, sub_count, sub_cap, key_bits);
+                       an.keys, an.sub_count, an.sub_cap, an.kb);
 }

@@ -19,17 +19,15 @@
 using SortConfig = rocprim::segmented_radix_sort_config<KP_SORT_RADIX_BITS, rocprim::kernel_config<KP_SORT_BLOCK, KP_SORT_ITEMS>,
                                                         rocprim::WarpSortConfig<32, 4, 256, 3000, 32, 4, 256>, true>;
 
-void kp_launch_segments(const uint32_t *count, uint32_t cap, int n_asm, uint32_t *seg_begin, uint32_t *seg_end,
-                        hipStream_t stream);
+void kp_launch_segments(const KpAnchors &an, int n_asm, uint32_t *seg_begin, uint32_t *seg_end, hipStream_t stream);  // kp_chain.hip
 
-int kp_sort_anchors(kp_ctx *ctx, uint64_t *keys_in, uint64_t *keys_out, const uint32_t *d_count, uint32_t cap,
-                    int32_t n_asm, void **temp, size_t *temp_bytes, uint32_t *d_seg_begin, uint32_t *d_seg_end,
-                    int end_bit, hipStream_t stream) {
+int kp_sort_anchors(kp_ctx *ctx, const KpAnchors &an, int32_t n_asm, void **temp, size_t *temp_bytes, uint32_t *d_seg_begin,
+                    uint32_t *d_seg_end, int end_bit, hipStream_t stream) {
     if (n_asm == 0) return KP_OK;
-    kp_launch_segments(d_count, cap, n_asm, d_seg_begin, d_seg_end, stream);
-    const unsigned int size = (unsigned int)((size_t)n_asm * cap);
+    kp_launch_segments(an, n_asm, d_seg_begin, d_seg_end, stream);
+    const unsigned int size = (unsigned int)((size_t)n_asm * an.cap);
     size_t need = 0;
-    KP_HIP_CHECK(ctx, rocprim::segmented_radix_sort_keys<SortConfig>(nullptr, need, keys_in, keys_out, size, (unsigned)n_asm,
+    KP_HIP_CHECK(ctx, rocprim::segmented_radix_sort_keys<SortConfig>(nullptr, need, an.second, an.keys, size, (unsigned)n_asm,
                                                          d_seg_begin, d_seg_end, 0, end_bit, stream));
     if (need > *temp_bytes) {
         if (*temp) KP_HIP_CHECK(ctx, hipFree(*temp));
@@ -37,7 +35,7 @@ int kp_sort_anchors(kp_ctx *ctx, uint64_t *keys_in, uint64_t *keys_out, const ui
         KP_HIP_CHECK(ctx, hipMalloc(temp, need));
         *temp_bytes = need;
     }
-    KP_HIP_CHECK(ctx, rocprim::segmented_radix_sort_keys<SortConfig>(*temp, need, keys_in, keys_out, size, (unsigned)n_asm,
+    KP_HIP_CHECK(ctx, rocprim::segmented_radix_sort_keys<SortConfig>(*temp, need, an.second, an.keys, size, (unsigned)n_asm,
                                                          d_seg_begin, d_seg_end, 0, end_bit, stream));
     return KP_OK;
 }

@@ -803,17 +803,13 @@ __global__ __launch_bounds__(TB_THREADS) void kp_sw_traceback_kernel(KpBatchView
 
 }  // namespace
 
-void kp_launch_sw(const KpBatchView &b, const KpGenes &genes, const KpTask *tasks, const uint32_t *task_count /* of each class's order */,
-                  uint32_t task_cap, const uint32_t *order, KpSwEnd *ends, void *trace, unsigned long long *trace_top,
-                  uint64_t trace_cap_units, KpSwResult *results, bool has_long_genes, hipStream_t stream,
-                  hipEvent_t after_fill) {
+void kp_launch_sw(const KpBatchView &b, const KpGenes &genes, const KpTasks &t, const KpTrace &trace, bool has_long_genes, hipStream_t stream, hipEvent_t after_fill) {
     const dim3 grid(3 * WIDE_BLOCKS + 256u * NARROW_BLOCKS_PER_CU + 3 * HELP_BLOCKS), block(64);
-    hipLaunchKernelGGL(kp_sw_kernel, grid, block, 0, stream, b, genes, tasks, task_count, task_cap, order, ends,
-                       reinterpret_cast<uint4 *>(trace), trace_top, trace_cap_units);
+    hipLaunchKernelGGL(kp_sw_kernel, grid, block, 0, stream, b, genes, t.tasks, t.order_count, t.cap, t.order, t.ends, trace.units, trace.top, trace.cap);
     if (has_long_genes)  // (a database property: the Kaptive-shaped ones have none and never launch it)
-        hipLaunchKernelGGL(kp_sw_long_kernel, dim3(256, KP_N_CLASSES), block, 0, stream, b, genes, tasks, task_count, task_cap, order, ends,
-                           reinterpret_cast<uint4 *>(trace), trace_top, trace_cap_units);
+        hipLaunchKernelGGL(kp_sw_long_kernel, dim3(256, KP_N_CLASSES), block, 0, stream, b, genes, t.tasks, t.order_count, t.cap, t.order, t.ends,
+                           trace.units, trace.top, trace.cap);
     if (after_fill) (void)hipEventRecord(after_fill, stream);
-    hipLaunchKernelGGL(kp_sw_traceback_kernel, dim3(2048, KP_N_CLASSES), dim3(TB_THREADS), 0, stream, b, genes, tasks, task_count,
-                       task_cap, order, ends, reinterpret_cast<const uint32_t *>(trace), results);
+    hipLaunchKernelGGL(kp_sw_traceback_kernel, dim3(2048, KP_N_CLASSES), dim3(TB_THREADS), 0, stream, b, genes, t.tasks, t.order_count,
+                       t.cap, t.order, t.ends, reinterpret_cast<const uint32_t *>(trace.units), t.results);  // (the walk reads words)
 }

@@ -47,17 +47,14 @@ int kp_batch_use_group(kp_ctx *ctx, kp_batch *b, int32_t group) {
 // indices made relative to the group's first gene.  A group that spans every gene of the context reads the table in place.
 static int split_hits(kp_ctx *ctx, kp_batch *b, KpWork *w, const KpTypingGroup &T, KpTypingRun &R) {
     if (R.split) return KP_OK;
-    const size_t n_asm = (size_t)b->n_asm;
     if (T.gene_lo == 0 && T.gene_hi == ctx->n_genes) {
-        R.hits = w->d_hits.p;
-        R.hit_n = w->d_hit_counts.p + n_asm;
+        R.hits = w->hits();
     } else {
-        KP_HIP_CHECK(ctx, R.d_hits.reserve(n_asm * w->hit_cap));
-        KP_HIP_CHECK(ctx, R.d_hit_n.reserve(n_asm));
-        kp_launch_hit_split(w->d_hits.p, w->d_hit_counts.p + n_asm, w->hit_cap, T.gene_lo, T.gene_hi, R.d_hits.p, R.d_hit_n.p, b->n_asm, R.stream);
+        KP_HIP_CHECK(ctx, R.d_hits.reserve(w->n_asm * w->hit_cap));
+        KP_HIP_CHECK(ctx, R.d_hit_n.reserve(w->n_asm));
+        R.hits = KpHitTable{.rows = R.d_hits.p, .count = R.d_hit_n.p, .cap = w->hit_cap, .keys = nullptr};
+        kp_launch_hit_split(w->hits(), T.gene_lo, T.gene_hi, R.hits, b->n_asm, R.stream);
         KP_HIP_CHECK(ctx, hipGetLastError());
-        R.hits = R.d_hits.p;
-        R.hit_n = R.d_hit_n.p;
     }
     R.split = true;
     return KP_OK;
@@ -77,7 +74,7 @@ int kp_batch_score(kp_ctx *ctx, kp_batch *b, double min_gene_coverage, double *l
     const size_t n = (size_t)b->n_asm * (size_t)T.typing.n_loci;
     KP_HIP_CHECK(ctx, R.d_scores.reserve(n));
     KP_HIP_CHECK(ctx, R.d_lcounts.reserve(n));
-    kp_launch_score(b->view, R.hits, R.hit_n, w->hit_cap, T.typing, min_gene_coverage, R.d_scores.p, R.d_lcounts.p, R.stream);
+    kp_launch_score(b->view, R.hits, T.typing, min_gene_coverage, R.d_scores.p, R.d_lcounts.p, R.stream);
     KP_HIP_CHECK(ctx, hipGetLastError());
     if (int frc = fetch_all(ctx, R.stream, {{locus_scores, R.d_scores.p, n * sizeof(double)}, {locus_counts, R.d_lcounts.p, n * sizeof(int32_t)}}))
         return frc;
@@ -91,10 +88,10 @@ static int enqueue_reduce(kp_ctx *ctx, kp_batch *b, KpWork *w) {
     KpTypingRun &R = typing_run(w, b->group);
     const KpRunCaps caps = run_caps(ctx, b->group);
     R.kept_cap = caps.kept_cap; R.piece_cap = caps.piece_cap; R.prot_cap = caps.prot_cap;
-    const size_t n_asm = (size_t)b->n_asm;
+    const size_t n_asm = R.n_asm = w->n_asm;
     if ((uint64_t)n_asm * (uint64_t)R.prot_cap > 0x7FFFFFFFull)
         return kp_fail(ctx, KP_EOVERFLOW, "protein buffer would exceed 2^31 bytes; use smaller batches");
-    const size_t slots = n_asm * (size_t)R.kept_cap;
+    const size_t slots = R.slots();
     KP_HIP_CHECK(ctx, R.d_keys.reserve(n_asm * w->hit_cap));
     KP_HIP_CHECK(ctx, R.d_order.reserve(n_asm * w->hit_cap));
     KP_HIP_CHECK(ctx, R.d_flag.reserve(n_asm * w->hit_cap));
@@ -102,23 +99,20 @@ static int enqueue_reduce(kp_ctx *ctx, kp_batch *b, KpWork *w) {
     KP_HIP_CHECK(ctx, R.d_pieces.reserve(n_asm * (size_t)R.piece_cap));
     KP_HIP_CHECK(ctx, R.d_summary.reserve(n_asm));
     KP_HIP_CHECK(ctx, R.d_prot.reserve(n_asm * (size_t)R.prot_cap));
-    KP_HIP_CHECK(ctx, R.d_pairs.reserve(4 * slots + n_asm + 1));
+    KP_HIP_CHECK(ctx, R.d_pairs.reserve(R.pairs_len()));
     KP_HIP_CHECK(ctx, R.d_dp.reserve(8 * slots));
-    int32_t *q_off = R.d_pairs.p, *q_len = q_off + slots, *t_off = q_len + slots, *t_len = t_off + slots;
-    int32_t *pair_base = t_len + slots, *n_pairs = pair_base + n_asm;
-    KP_HIP_CHECK(ctx, hipMemsetAsync(n_pairs, 0, sizeof(int32_t), R.stream));
-    kp_launch_reduce(b->view, R.hits, R.hit_n, w->hit_cap, T.typing, R.prm, R.d_best.p, R.d_keys.p, R.d_order.p, R.d_flag.p, R.d_kept.p, R.kept_cap, R.d_pieces.p, R.piece_cap,
-                     R.d_summary.p, R.d_prot.p, R.prot_cap, q_off, q_len, t_off, t_len, n_pairs, pair_base, R.stream);
+    const KpReduceTables t = R.tables();
+    KP_HIP_CHECK(ctx, hipMemsetAsync(t.n_pairs, 0, sizeof(int32_t), R.stream));
+    kp_launch_reduce(b->view, R.hits, T.typing, R.prm, t, R.stream);
     // protein DP of every kept hit against its database protein (pair list is compact; its length lives on the device)
     const int n_blocks = (int)std::min<size_t>(std::max<size_t>(slots, 1), 256 * 24);
     // row buffer of the strip kernel: KP_PROT_ROWBUF_FIELDS ints per column of the database protein, one region per
     // block, and 64 ints for its work counter (kp_prot.hip)
     const size_t scratch_per_block = (size_t)KP_PROT_ROWBUF_FIELDS * ((size_t)T.max_db_prot_len + 1);
     KP_HIP_CHECK(ctx, R.d_dp_scratch.reserve(scratch_per_block * (size_t)n_blocks + 64));
-    kp_launch_protein(R.d_prot.p, q_off, q_len, T.d_prot_db.p, t_off, t_len, (int32_t)slots, n_pairs, ctx->d_blosum.p,
-                      R.d_dp.p, R.d_dp_scratch.p, scratch_per_block, n_blocks, R.stream, R.aux, R.ev_fork,
-                      R.ev_join);
-    kp_launch_states(b->view, T.typing, R.prm, R.d_kept.p, R.kept_cap, R.d_summary.p, R.d_dp.p, pair_base, R.stream);
+    kp_launch_protein(t.prot, t.q_off, t.q_len, T.d_prot_db.p, t.t_off, t.t_len, (int32_t)slots, t.n_pairs, ctx->d_blosum.p,
+                      t.dp8, R.d_dp_scratch.p, scratch_per_block, n_blocks, R.stream, R.aux, R.ev_fork, R.ev_join);
+    kp_launch_states(b->view, T.typing, R.prm, t, R.stream);
     KP_HIP_CHECK(ctx, hipGetLastError());
     return KP_OK;
 }
@@ -172,7 +166,7 @@ static int fetch_summaries(kp_ctx *ctx, kp_batch *b, KpWork *w) {
         if (attempt >= 8) return kp_fail(ctx, KP_EOVERFLOW, "reduction buffers overflowed repeatedly");
         std::string err;
         if (!kp_caps_grow_run(run_caps(ctx, b->group), flags, err)) return kp_fail(ctx, KP_EOVERFLOW, err);
-        w->stats[4] += 1;
+        w->stats[KP_STAT_RERUNS] += 1;
         int rc = enqueue_reduce(ctx, b, w);
         if (rc) return rc;
     }

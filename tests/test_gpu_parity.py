@@ -709,6 +709,29 @@ def test_sw_raw_results_match_oracle(ctx, small_setup, small_db):
         batch.close()
 
 
+def test_profile_reports_the_stages_of_the_pass(ctx, small_setup, small_db):
+    """Batch.profile(): the seven times between the pass's stage events, and the bytes the scan read.  The events lie
+    between align_async() and the return of wait(), so their sum cannot exceed the host's wall time around the two."""
+    import math
+    import time
+
+    stages = ("scan", "sort", "chain", "sw16", "sw32", "sw64", "sw128")
+    asms = _assemblies(small_db)
+    for part in (asms[:3], asms[3:6]):  # the second batch takes the context's next work set
+        batch = ctx.batch([a.packed() for a in part])
+        t0 = time.perf_counter()
+        batch.align_async()
+        batch.wait()
+        wall_ms = (time.perf_counter() - t0) * 1e3
+        prof = batch.profile()
+        assert set(prof) == {*stages, "bytes_scanned"}
+        assert all(math.isfinite(prof[k]) and prof[k] >= 0.0 for k in stages), prof
+        assert all(prof[k] > 0.0 for k in ("scan", "sort", "chain", "sw16", "sw32")), prof
+        assert sum(prof[k] for k in stages) <= wall_ms, (prof, wall_ms)
+        assert prof["bytes_scanned"] == 4 * batch.total_words > 0
+        batch.close()
+
+
 def test_random_assembly_shapes_match_oracle(ctx, small_setup, small_db):
     """Fuzz over what shapes the chaining / SW / expansion kernels: divergence up to 25 %, indels, many tiny contigs,
     N runs, a second partial locus, no locus at all -- anchors, tasks and hits of one batch, all compared."""
