@@ -17,7 +17,7 @@ static int enqueue_forked(kp_ctx *ctx, kp_batch *b, KpWork *w, hipStream_t strea
     kp_launch_task_order(b->view, ctx->genes, an, tasks, stream);
     KP_HIP_CHECK(ctx, hipEventRecord(w->ev[KP_EV_ORDER], stream));
     // all four band classes in one fill launch, then the traceback (kp_sw.hip)
-    kp_launch_sw(b->view, ctx->genes, tasks, trace, ctx->max_gene_len > KP_FILL16_MAX_GENE_LEN, stream, w->ev[KP_EV_FILL]);
+    kp_launch_sw(b->view, ctx->genes, tasks, trace, ctx->max_gene_len > KP_FILL16_MAX_GENE_LEN, ctx->opt.trace_summary, stream, w->ev[KP_EV_FILL]);
     KP_HIP_CHECK(ctx, hipEventRecord(w->ev[KP_EV_TRACEBACK], stream));
     return KP_OK;
 }
@@ -195,9 +195,9 @@ static int emit_cigars(kp_ctx *ctx, kp_batch *b, KpWork *w) {
     KP_HIP_CHECK(ctx, w->d_cig_ops.reserve(w->cigar_cap));
     KP_HIP_CHECK(ctx, hipMemcpyAsync(w->d_cig_hit_off.p, w->hit_off.data(), (n_asm + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->post));
     kp_launch_cigar_locate(b->view, ctx->d_gene_len.p, w->tasks(), w->joins(), w->hits(), w->d_cig_src.p, ctx->post);
-    kp_launch_cigar_walk(b->view, ctx->genes, w->tasks(), w->joins(), w->trace(), w->hits(), w->hit_rows(), w->d_cig_src.p, w->cigars(), false, ctx->post);
+    kp_launch_cigar_walk(b->view, ctx->genes, w->tasks(), w->joins(), w->trace(), w->hits(), w->hit_rows(), w->d_cig_src.p, w->cigars(), false, ctx->opt.trace_summary, ctx->post);
     for (int attempt = 0;; ++attempt) {
-        kp_launch_cigar_walk(b->view, ctx->genes, w->tasks(), w->joins(), w->trace(), w->hits(), w->hit_rows(), w->d_cig_src.p, w->cigars(), true, ctx->post);
+        kp_launch_cigar_walk(b->view, ctx->genes, w->tasks(), w->joins(), w->trace(), w->hits(), w->hit_rows(), w->d_cig_src.p, w->cigars(), true, ctx->opt.trace_summary, ctx->post);
         KP_HIP_CHECK(ctx, hipGetLastError());
         int64_t need = 0;
         if (int frc = fetch_all(ctx, ctx->post, {{&need, w->d_cig_off.p + total, sizeof need}})) return frc;

@@ -116,7 +116,7 @@ template <bool EMIT>
 __global__ __launch_bounds__(WALK_THREADS) void kp_cigar_walk_kernel(KpBatchView b, KpGenes genes, const KpTask *__restrict__ tasks,
                                                                      const KpSwEnd *__restrict__ ends, uint32_t task_cap,
                                                                      const KpJoin *__restrict__ joins, uint32_t join_cap,
-                                                                     const uint4 *__restrict__ trace, const uint32_t *__restrict__ n_hits,
+                                                                     const uint4 *__restrict__ trace, bool summaries, const uint32_t *__restrict__ n_hits,
                                                                      uint32_t hit_cap, const int64_t *__restrict__ hit_off,
                                                                      const unsigned long long *__restrict__ src, uint32_t *__restrict__ cnt,
                                                                      const int64_t *__restrict__ off, uint32_t *__restrict__ ops, int64_t ops_cap) {
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(WALK_THREADS) void kp_cigar_walk_kernel(KpBatchView
             const int64_t row = hit_off[a] + i;
             OpRuns v;
             v.out = EMIT ? ops : nullptr; v.cap = ops_cap; v.pos = EMIT && have ? off[row + 1] : 0;
-            // a band task: its direction bits need no N test (matches are not counted here), so the fast path serves every task
+            // a band task: its direction bits need no N test (matches are not counted here), so the fast path -- plain pieces skipped by their summaries -- serves every task
             KpTask tk;
             tk.asm_id = a; tk.gs = 0; tk.contig = 0; tk.lo = 0;
             KpSwEnd e;
@@ -143,10 +143,10 @@ __global__ __launch_bounds__(WALK_THREADS) void kp_cigar_walk_kernel(KpBatchView
                 tk = tasks[at]; e = ends[at];
             }
             const KpTaskSeqs s = kp_task_seqs(b, genes, a, is_join ? J->gs : tk.gs, is_join ? J->contig : tk.contig);
-            int q0 = 0, r_hi;
+            int q0 = 0, r_hi = 0;
             if (is_task) kp_task_rows(tk.lo, 4 * P, s.t.cstart, s.t.cend, s.q.len, &q0, &r_hi);
             KpBandPath bp;
-            kp_band_walk(is_task, tk.lo, P, q0, e.er, e.eb & 255, false, trace + e.trace_off, s, bp, v);
+            kp_band_walk(is_task, summaries, tk.lo, P, q0, r_hi, e.er, e.eb & 255, false, trace + e.trace_off, s, bp, v);
             if (is_join) {  // (rare: a lane each, after the wave's band tasks)
                 KpJoinPath jp;
                 kp_join_walk(J, (int)(ref & 7u), P, s, trace, jp, v);
@@ -195,13 +195,13 @@ void kp_launch_count_scan(const uint32_t *cnt, int64_t n, int64_t *off, hipStrea
 }
 
 void kp_launch_cigar_walk(const KpBatchView &b, const KpGenes &genes, const KpTasks &t, const KpJoins &j, const KpTrace &trace, const KpHitTable &hits,
-                          const KpHitRows &rows, const unsigned long long *src, const KpPerHit<uint32_t> &cig, bool emit, hipStream_t stream) {
+                          const KpHitRows &rows, const unsigned long long *src, const KpPerHit<uint32_t> &cig, bool emit, bool walk_summaries, hipStream_t stream) {
     const dim3 grid((unsigned)std::min(std::max(b.n_asm, 1), 4096)), block(WALK_THREADS);
     if (!emit) {
-        hipLaunchKernelGGL(kp_cigar_walk_kernel<false>, grid, block, 0, stream, b, genes, t.tasks, t.ends, t.cap, j.list, j.cap, trace.units, hits.count,
+        hipLaunchKernelGGL(kp_cigar_walk_kernel<false>, grid, block, 0, stream, b, genes, t.tasks, t.ends, t.cap, j.list, j.cap, trace.units, walk_summaries, hits.count,
                            hits.cap, rows.hit_off, src, cig.cnt, (const int64_t *)nullptr, (uint32_t *)nullptr, (int64_t)0);
         return kp_launch_count_scan(cig.cnt, rows.total, cig.off, stream);
     }
-    hipLaunchKernelGGL(kp_cigar_walk_kernel<true>, grid, block, 0, stream, b, genes, t.tasks, t.ends, t.cap, j.list, j.cap, trace.units, hits.count,
+    hipLaunchKernelGGL(kp_cigar_walk_kernel<true>, grid, block, 0, stream, b, genes, t.tasks, t.ends, t.cap, j.list, j.cap, trace.units, walk_summaries, hits.count,
                        hits.cap, rows.hit_off, src, (uint32_t *)nullptr, cig.off, cig.data, cig.cap);
 }

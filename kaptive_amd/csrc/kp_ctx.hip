@@ -127,6 +127,7 @@ static void options_from_env(KpOptions &o) {
     o.upload_piece_mb = std::max<uint32_t>(1, env_u32("KAPTIVE_AMD_UPLOAD_PIECE_MB", 4096));
     { const char *rb = getenv("KAPTIVE_AMD_READBACK"); o.readback_copy_engine = rb && std::string(rb) == "copy"; }
     o.spin_wait = (int)env_u32("KAPTIVE_AMD_SPIN_WAIT", 0);
+    { const char *ts = std::getenv("KAPTIVE_AMD_TRACE_SUMMARY"); o.trace_summary = !(ts && std::string(ts) == "0"); }
     o.join_stats = std::getenv("KAPTIVE_AMD_JOIN_STATS") != nullptr;
     if (const char *e = std::getenv("KAPTIVE_AMD_JOIN_GRID")) std::sscanf(e, "%d,%d,%d,%d", &o.join.fill, &o.join.walk, &o.join.chain, &o.join.chain_large);
     if (const char *e = std::getenv("KAPTIVE_AMD_JOIN_PRIO")) o.join.prio = std::atoi(e);

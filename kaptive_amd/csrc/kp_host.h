@@ -75,6 +75,7 @@ struct KpOptions : KpCapOptions {
     int spin_wait = 0;              // host waits spin on the stream (the runtime's default) instead of blocking on an interrupt
     int cigar = 0;                  // CIGARs of the finished hits (kp_cigar.hip): off unless asked for; applies from the next kp_batch_align
     int cs = 0;                     // cs difference strings of the finished hits (kp_cs.hip); a pass with it computes the CIGARs too: cs reads them
+    bool trace_summary = true;      // KAPTIVE_AMD_TRACE_SUMMARY=0: the band walks ignore the fills' piece summaries and fetch every piece on a path (kp_walk.h; A/B switch)
     bool join_stats = false;        // KAPTIVE_AMD_JOIN_STATS: kp_batch_wait reports the pass's group / join / mid_occ counts on stderr
     KpJoinLaunch join;              // KAPTIVE_AMD_JOIN_GRID / _JOIN_PRIO / _SKIP_JOINS: launch shape of the join kernels (kp_internal.h)
 };

@@ -297,7 +297,7 @@ void kp_launch_chain(const KpBatchView &b, const KpAnchors &an, const KpTasks &t
 // kp_sw.hip: banded Smith-Waterman of every ORDERED task; class c (16/32/64/128 diagonals) has its tasks, order, ends and
 // results in its region and the length of its order at order_count[c]; one fill launch covers all four, one traceback launch follows.
 // *trace.top (zeroed by the caller) ends up as the units the pass needs.
-void kp_launch_sw(const KpBatchView &b, const KpGenes &genes, const KpTasks &tasks, const KpTrace &trace, bool has_long_genes, hipStream_t stream, hipEvent_t after_fill);
+void kp_launch_sw(const KpBatchView &b, const KpGenes &genes, const KpTasks &tasks, const KpTrace &trace, bool has_long_genes, bool walk_summaries, hipStream_t stream, hipEvent_t after_fill);
 // kp_chain.hip: settles the provisional tasks (chain score and anchor count of every cluster, or rejection: kp_spec.h), then
 // builds, per width class, a permutation of the surviving tasks ordered by query length (longest first).  The order's head is
 // KP_ORDER_HEAD zeroed words: histogram, cursors and, at KP_ORDER_COUNTS, how many tasks each class's order holds.
@@ -323,7 +323,7 @@ void kp_launch_join_trace(const KpBatchView &b, const KpGenes &genes, const KpJo
 void kp_launch_cigar_locate(const KpBatchView &b, const int32_t *gene_len, const KpTasks &tasks, const KpJoins &joins, const KpHitTable &hits,
                             unsigned long long *src, hipStream_t stream);
 void kp_launch_cigar_walk(const KpBatchView &b, const KpGenes &genes, const KpTasks &tasks, const KpJoins &joins, const KpTrace &trace, const KpHitTable &hits,
-                          const KpHitRows &rows, const unsigned long long *src, const KpPerHit<uint32_t> &cig, bool emit, hipStream_t stream);
+                          const KpHitRows &rows, const unsigned long long *src, const KpPerHit<uint32_t> &cig, bool emit, bool walk_summaries, hipStream_t stream);
 void kp_launch_count_scan(const uint32_t *cnt, int64_t n, int64_t *off, hipStream_t stream);  // kp_cigar.hip's scan, for any per-hit counts
 // kp_cs.hip (only with the `cs` option; after the CIGAR ops are final): the bytes of every hit's cs string (kp_spec.h, CS) counted
 // (cs.cnt) and scanned (cs.off), or with `emit` the bytes written forward from cs.off[row] -- stores beyond cs.cap are dropped.

@@ -21,7 +21,8 @@
 //     and 31 (the guard bit survives exactly when no borrow reaches it) -- no v_cmp, no lane mask, no carry push,
 //   * the four direction bits of a cell are gathered from those words byte-wise (v_perm_b32, one v_bfi),
 //   * every cross-lane move (DPP) and every band-edge select serves two cells.
-// 41.8 issue cycles per cell of a lane (2674 per 8 steps of 8 cells, tools/isa_cost.py; round 2: 52) instead of 82.
+// 42.6 issue cycles per cell of a lane (2725 per 8 steps of 8 cells, tools/isa_cost.py: 2674 for the cells and their direction
+// bits, 51 for the piece summaries; round 2: 52) instead of 82.
 //
 // Mapping (wavefront-parallel anti-diagonals, no MFMA -- this is dependent integer DP, not a contraction):
 //   * a task's band has W = 4P diagonals; P lanes own a PAIR of tasks of that width (neighbours in the length-ordered task
@@ -55,13 +56,15 @@
 //     first maximum in row order, then the first of the lane's cells that holds it.
 //   * direction bits, four steps per 16 bits, eight steps per 32-bit word and cell: the two tasks' halves are
 //     separated with v_perm_b32 every eight steps and each task's 16 bytes go to its own trace block.
+//   * piece summaries: per cell and 8 steps one bit per task, "this piece is not eight plain diagonal steps", formed before the
+//     halves are separated and stored as one word per lane, task and chunk behind the task's pieces (kp_walk.h: KpTraceBlock) --
+//     the traceback skips what they call plain without fetching it.
 #include "kp_internal.h"
 #include "kp_walk.h"
 
 namespace {
 
 constexpr int CH = 64;  // steps staged per chunk (multiple of 8)
-constexpr int TG = KP_TRACE_GROUP;  // consecutive 8-step trace pieces of a lane that are contiguous in memory (2 or 4)
 constexpr int OE = KP_GAP_OPEN + KP_GAP_EXT;
 constexpr int EX = KP_GAP_EXT;
 static_assert(KP_SC_MATCH == 2 && KP_SC_MISMATCH == -4 && KP_SC_N == -1 && OE == 6 && EX == 2,
@@ -172,6 +175,16 @@ __device__ __forceinline__ unsigned bfi(unsigned mask, unsigned a, unsigned b) {
 __device__ __forceinline__ unsigned bfi_v(unsigned mask, unsigned a, unsigned b) {
     unsigned r;
     asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(mask), "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ unsigned pk_min(unsigned a, unsigned b) {
+    unsigned r;
+    asm("v_pk_min_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ unsigned shl1_or(unsigned a, unsigned b) {  // (a << 1) | b
+    unsigned r;
+    asm("v_lshl_or_b32 %0, %1, 1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
 // a >= b for both halves: the answer in bits 15 and 31, the bits below are of no use to anyone
@@ -318,8 +331,8 @@ __device__ __forceinline__ void sw_class(const KpBatchView &b, const KpGenes &ge
     // statements becomes a branch)
     unsigned first_all = l == 0 ? ~0u : 0u, last_all = l == P - 1 ? ~0u : 0u;
     // (VGPR copies of constants that VOP3 / VOP3P instructions cannot take as literals)
-    unsigned twelve = CB * K1, fifteen = 15u * K1;  // twelve: a gap state of 0 on the biased scale
-    asm volatile("" : "+v"(twelve), "+v"(fifteen), "+v"(first_all), "+v"(last_all));
+    unsigned twelve = CB * K1, fifteen = 15u * K1, one = K1;  // twelve: a gap state of 0 on the biased scale
+    asm volatile("" : "+v"(twelve), "+v"(fifteen), "+v"(one), "+v"(first_all), "+v"(last_all));
 
     // The narrow class hands its quads out by a counter (longest tasks first) to a fixed number of single-wave blocks that
     // keep taking until it is exhausted: 32 per CU, twice what is resident, so the dispatcher always has a block to put
@@ -337,7 +350,8 @@ __device__ __forceinline__ void sw_class(const KpBatchView &b, const KpGenes &ge
         bool have[2];
         uint32_t ti[2];
         KpTask tk[2];
-        int qlen[2], lo[2], q0[2], n_runs[2], steps[2], n_chunks[2];  // lo: column of (row q0, band index 0); q0: first row filled
+        int qlen[2], lo[2], q0[2], n_runs[2], steps[2];  // lo: column of (row q0, band index 0); q0: first row filled
+        KpTraceBlock tb[2];  // the task's block of the trace buffer: pieces per lane, summary words per lane (kp_walk.h)
         int32_t cstart[2], cend[2];
         // (32-bit offsets from the batch's and the genes' arrays rather than pointers: registers)
         uint32_t asm_n_words[2], q_off[2], w_off[2], run_off[2];
@@ -367,14 +381,13 @@ __device__ __forceinline__ void sw_class(const KpBatchView &b, const KpGenes &ge
             kp_task_rows(tk[h].lo, 4 * P, cstart[h], cend[h], qlen[h], &q0[h], &r_hi);
             lo[h] = tk[h].lo + q0[h];
             steps[h] = have[h] ? (r_hi - q0[h]) + P - 1 : 0;  // steps the task needs
-            // 8-step trace pieces per lane, in whole groups of four
-            n_chunks[h] = (((steps[h] + 7) >> 3) + 3) & ~3;  // (a multiple of four whatever TG: task blocks start on 128-byte lines)
+            tb[h] = kp_trace_block(P, steps[h]);  // (nothing for a task that is not there)
         }
         int max_steps = max(steps[0], steps[1]);
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) max_steps = max(max_steps, __shfl_xor(max_steps, o));
-        // the pair's trace blocks, X's then Y's: P lane streams of n_chunks 16-byte pieces each
-        const unsigned long long want = (unsigned long long)P * (unsigned)((have[0] ? n_chunks[0] : 0) + (have[1] ? n_chunks[1] : 0));
+        // the pair's trace blocks, X's then Y's: each P lane streams of 16-byte pieces, then the summaries of those pieces
+        const unsigned long long want = (unsigned long long)tb[0].units() + tb[1].units();
         const unsigned long long toff = kp_trace_take(trace_top, have[0] && l == 0, want, g * P);
         const bool fits = have[0] && toff + want <= trace_cap;  // else: counted, host reruns
         // piece j of lane l at [j / TG][l][j % TG]: TG consecutive pieces of a lane are contiguous, so the traceback -- it
@@ -383,8 +396,11 @@ __device__ __forceinline__ void sw_class(const KpBatchView &b, const KpGenes &ge
         // piece) but keeps lines open for 32 steps, and the fill kernel pays more for the partial write-backs than the
         // traceback gains (11.9 ms against 11.0 ms); with a whole stream per lane a line stayed open for 64 steps, more open
         // lines than the L2 holds, and HBM saw three times the bytes (WRITE_SIZE, profiles/).
-        const unsigned long long toff_y = toff + (unsigned long long)P * (unsigned)n_chunks[0];
-        uint4 *trace_x = trace + toff + TG * l, *trace_y = trace + toff_y + TG * l;
+        const unsigned long long toff_y = toff + tb[0].units();
+        uint4 *trace_x = trace + toff + tb[0].piece_at(0, l), *trace_y = trace + toff_y + tb[1].piece_at(0, l);
+        // this lane's summary word of chunk 0, in bytes from trace_x / trace_y (a block is at most a few MB)
+        const uint32_t sum_dx = 16u * (tb[0].sum_off() - (uint32_t)tb[0].piece_at(0, l)) + 4u * (uint32_t)tb[0].sum_at(0, l);
+        const uint32_t sum_dy = 16u * (tb[1].sum_off() - (uint32_t)tb[1].piece_at(0, l)) + 4u * (uint32_t)tb[1].sum_at(0, l);
 
         State st;
         st.A.hmoe = GAP_EDGE; st.A.hg = GAP_EDGE | GUARD; st.A.emex = GAP_NONE; st.A.fmex = GAP_NONE;
@@ -394,6 +410,9 @@ __device__ __forceinline__ void sw_class(const KpBatchView &b, const KpGenes &ge
 #pragma unroll
         for (int k = 0; k < 4; ++k) st.s0[k] = st.s1[k] = GAP_EDGE;
         unsigned acc[4] = {0, 0, 0, 0}, held[4] = {0, 0, 0, 0};
+        // summaries of the pieces (kp_walk.h): per cell a shift register of "this piece is not plain", X's bits from bit 0 and
+        // Y's from bit 16 upwards, the latest piece lowest; emptied into a word per task at the end of every chunk
+        unsigned np[4] = {0, 0, 0, 0};
         // an N in the gene or in the target window: the traceback then compares bases itself
         bool saw_n[2] = {have[0] && genes.has_n[tk[0].gs >> 1] != 0, have[1] && genes.has_n[tk[1].gs >> 1] != 0};
 
@@ -518,12 +537,31 @@ __device__ __forceinline__ void sw_class(const KpBatchView &b, const KpGenes &ge
                 }
                 // eight steps of both tasks per cell: X = low halves, Y = high halves (steps 0-3 low, 4-7 high)
                 const int j = m >> 3;
-                if (fits && j < n_chunks[0])
-                    trace_x[(size_t)(j / TG) * (TG * P) + (j % TG)] = make_uint4(__builtin_amdgcn_perm(acc[0], held[0], 0x05040100u), __builtin_amdgcn_perm(acc[1], held[1], 0x05040100u),
+                // plain for X iff ((held | acc) & 0x0000AAAA) == 0, for Y the same of the high halves -- formed before the
+                // tasks are separated: four instructions per cell for both (13 issue cycles; 51 of the 2725 per 8 steps; alone the launch measured +3.4 %, profiles/trace_summary_ab.txt)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) np[c] = shl1_or(np[c], pk_min(and_k<KP_PLAIN_MASK>(or_v(held[c], acc[c])), one));
+                if (fits && j < tb[0].pieces)
+                    trace_x[tb[0].piece_at(j, 0)] = make_uint4(__builtin_amdgcn_perm(acc[0], held[0], 0x05040100u), __builtin_amdgcn_perm(acc[1], held[1], 0x05040100u),
                                                         __builtin_amdgcn_perm(acc[2], held[2], 0x05040100u), __builtin_amdgcn_perm(acc[3], held[3], 0x05040100u));
-                if (fits && have[1] && j < n_chunks[1])
-                    trace_y[(size_t)(j / TG) * (TG * P) + (j % TG)] = make_uint4(__builtin_amdgcn_perm(acc[0], held[0], 0x07060302u), __builtin_amdgcn_perm(acc[1], held[1], 0x07060302u),
+                if (fits && have[1] && j < tb[1].pieces)
+                    trace_y[tb[1].piece_at(j, 0)] = make_uint4(__builtin_amdgcn_perm(acc[0], held[0], 0x07060302u), __builtin_amdgcn_perm(acc[1], held[1], 0x07060302u),
                                                         __builtin_amdgcn_perm(acc[2], held[2], 0x07060302u), __builtin_amdgcn_perm(acc[3], held[3], 0x07060302u));
+            }
+            {   // the chunk's summary words: cell c in byte c, piece q of the chunk at bit 7 - q (a last chunk that ran fewer
+                // than eight pieces is moved up; a byte holds bits of its own pieces only, so nothing crosses into the next)
+                const int ch = m0 / CH, up = 8 - ((m_end - m0) >> 3);
+                // (v_perm_b32 selects: bytes 0-3 = second operand, 4-7 = first, 0x0c = zero; X's bits are byte 0 of a register, Y's byte 2)
+                const unsigned sx = (__builtin_amdgcn_perm(np[1], np[0], 0x0c0c0400u) | __builtin_amdgcn_perm(np[3], np[2], 0x04000c0cu)) << up;
+                const unsigned sy = (__builtin_amdgcn_perm(np[1], np[0], 0x0c0c0602u) | __builtin_amdgcn_perm(np[3], np[2], 0x06020c0cu)) << up;
+                const uint32_t at = (uint32_t)tb[0].sum_at(ch, 0) * 4u;  // (chunk ch has a word iff it has a piece: 8 ch < pieces)
+#ifdef KP_SW_NO_SUMMARY_STORE  // (A/B builds: the bits are formed, the words are not stored -- and the walks must not use them)
+                asm volatile("" ::"v"(sx), "v"(sy), "v"(at));
+#else
+                if (fits && 8 * ch < tb[0].pieces) *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(trace_x) + (sum_dx + at)) = sx;
+                if (fits && have[1] && 8 * ch < tb[1].pieces) *reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(trace_y) + (sum_dy + at)) = sy;
+#endif
+                np[0] = np[1] = np[2] = np[3] = 0;
             }
         }
 
@@ -636,7 +674,7 @@ __global__ __launch_bounds__(64, KP_SW_WAVES) void kp_sw_kernel(KpBatchView b, K
 // written out in plain 32-bit arithmetic, ONE task per lane group, sequences read straight from the packed words --
 // several times slower per cell, on a handful of tasks.  It leaves what kp_sw_kernel leaves: the best cell (KpSwEnd) and the
 // direction words in the same layout (a cell's word: eight steps, per four steps a byte of [not D, E opened] pairs above a
-// byte of [not L, F opened] pairs), so the traceback kernel does not know which kernel filled a task.
+// byte of [not L, F opened] pairs) and the same piece summaries, so the traceback kernel does not know which kernel filled a task.
 constexpr int LONG_NEG = -(1 << 29);
 
 template <int P>
@@ -657,14 +695,16 @@ __device__ __forceinline__ void sw_long_class(const KpBatchView &b, const KpGene
         int q0, r_hi;
         kp_task_rows(tk.lo, 4 * P, s.t.cstart, s.t.cend, have ? s.q.len : 0, &q0, &r_hi);
         const int steps = have ? (r_hi - q0) + P - 1 : 0;
-        const int n_chunks = (((steps + 7) >> 3) + 3) & ~3;
+        const KpTraceBlock tb = kp_trace_block(P, steps);
         int max_steps = steps;
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) max_steps = max(max_steps, __shfl_xor(max_steps, o));
-        const unsigned long long want = (unsigned long long)P * (unsigned)(have ? n_chunks : 0);
+        const unsigned long long want = tb.units();
         const unsigned long long toff = kp_trace_take(trace_top, have && l == 0, want, g * P);
         const bool fits = have && toff + want <= trace_cap;
-        uint4 *trace_x = trace + toff + TG * l;
+        uint4 *trace_x = trace + toff;
+        uint32_t *sum_x = reinterpret_cast<uint32_t *>(trace + toff + tb.sum_off());
+        uint32_t sum = 0;  // summary word of the chunk in hand (kp_walk.h): which of its pieces are not plain, per cell
         int H[4] = {0, 0, 0, 0}, E[4], F[4], tc[4];
         bool saw_n = have && genes.has_n[tk.gs >> 1] != 0;
 #pragma unroll
@@ -716,7 +756,13 @@ __device__ __forceinline__ void sw_long_class(const KpBatchView &b, const KpGene
             }
             if ((m & 7) == 7) {
                 const int j = m >> 3;
-                if (fits && j < n_chunks) trace_x[(size_t)(j / TG) * (TG * P) + (j % TG)] = make_uint4(word[0], word[1], word[2], word[3]);
+                if (fits && j < tb.pieces) trace_x[tb.piece_at(j, l)] = make_uint4(word[0], word[1], word[2], word[3]);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) sum |= (word[k] & KP_PLAIN_MASK) ? 1u << kp_sum_bit(k, j) : 0u;
+                if ((j & 7) == 7 || m + 1 == steps8) {
+                    if (fits && (j >> 3) < tb.sum_words) sum_x[tb.sum_at(j >> 3, l)] = sum;
+                    sum = 0;
+                }
                 word[0] = word[1] = word[2] = word[3] = 0;
             }
         }
@@ -761,7 +807,7 @@ __global__ __launch_bounds__(TB_THREADS) void kp_sw_traceback_kernel(KpBatchView
                                                               const uint32_t *__restrict__ task_count, uint32_t task_cap,
                                                               const uint32_t *__restrict__ order,
                                                               const KpSwEnd *__restrict__ ends,
-                                                              const uint32_t *__restrict__ trace,
+                                                              const uint32_t *__restrict__ trace, bool summaries,
                                                               KpSwResult *__restrict__ results) {
     const int cls = blockIdx.y;
     uint32_t n = task_count[cls] + task_count[KP_N_CLASSES + cls];  // the class's order: ordinary tasks, then those of long genes
@@ -784,12 +830,12 @@ __global__ __launch_bounds__(TB_THREADS) void kp_sw_traceback_kernel(KpBatchView
         const bool has_n = (e.eb & KP_SWEND_HAS_N) != 0;
         const int eb = e.eb & 255;
         const KpTaskSeqs s = kp_task_seqs(b, genes, tk.asm_id, tk.gs, tk.contig);
-        int q0 = 0, r_hi;  // q0: first row the fill kernel computed for the task: its steps count from there
+        int q0 = 0, r_hi = 0;  // q0: first row the fill kernel computed for the task: its steps count from there
         if (walking) kp_task_rows(tk.lo, 4 * P, s.t.cstart, s.t.cend, s.q.len, &q0, &r_hi);
-        const uint4 *tw = reinterpret_cast<const uint4 *>(trace) + e.trace_off;  // piece j of lane l at [(j / TG) * TG * P + TG * l + j % TG]
+        const uint4 *tw = reinterpret_cast<const uint4 *>(trace) + e.trace_off;  // the task's block (kp_walk.h: KpTraceBlock)
         KpBandPath path;
         KpNoVisit nobody;
-        kp_band_walk(walking, tk.lo, P, q0, e.er, eb, has_n, tw, s, path, nobody);
+        kp_band_walk(walking, summaries, tk.lo, P, q0, r_hi, e.er, eb, has_n, tw, s, path, nobody);
         if (!have) continue;
         if (e.score < KP_MIN_DP_SCORE) { results[at] = out; continue; }
         const int matches = has_n ? path.matches : (e.score + 4 * path.diag + path.gap_cost) / 6;
@@ -803,7 +849,7 @@ __global__ __launch_bounds__(TB_THREADS) void kp_sw_traceback_kernel(KpBatchView
 
 }  // namespace
 
-void kp_launch_sw(const KpBatchView &b, const KpGenes &genes, const KpTasks &t, const KpTrace &trace, bool has_long_genes, hipStream_t stream, hipEvent_t after_fill) {
+void kp_launch_sw(const KpBatchView &b, const KpGenes &genes, const KpTasks &t, const KpTrace &trace, bool has_long_genes, bool walk_summaries, hipStream_t stream, hipEvent_t after_fill) {
     const dim3 grid(3 * WIDE_BLOCKS + 256u * NARROW_BLOCKS_PER_CU + 3 * HELP_BLOCKS), block(64);
     hipLaunchKernelGGL(kp_sw_kernel, grid, block, 0, stream, b, genes, t.tasks, t.order_count, t.cap, t.order, t.ends, trace.units, trace.top, trace.cap);
     if (has_long_genes)  // (a database property: the Kaptive-shaped ones have none and never launch it)
@@ -811,5 +857,5 @@ void kp_launch_sw(const KpBatchView &b, const KpGenes &genes, const KpTasks &t, 
                            trace.units, trace.top, trace.cap);
     if (after_fill) (void)hipEventRecord(after_fill, stream);
     hipLaunchKernelGGL(kp_sw_traceback_kernel, dim3(2048, KP_N_CLASSES), dim3(TB_THREADS), 0, stream, b, genes, t.tasks, t.order_count,
-                       t.cap, t.order, t.ends, reinterpret_cast<const uint32_t *>(trace.units), t.results);  // (the walk reads words)
+                       t.cap, t.order, t.ends, reinterpret_cast<const uint32_t *>(trace.units), walk_summaries, t.results);  // (the walk reads words)
 }

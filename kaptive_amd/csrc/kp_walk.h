@@ -60,18 +60,51 @@ __device__ __forceinline__ uint32_t kp_piece_word(const uint4 &v, int k) {  // c
     return (k & 2) ? hi : lo;
 }
 
+// ---- a band task's block of the trace buffer: the one rule both fills and every walk take its sizes and offsets from ----------
+// P lane streams of `pieces` 16-byte pieces (8 steps x 4 cells; piece j of lane l at [j / TG][l][j % TG]: TG consecutive pieces
+// of a lane are contiguous bytes), then the SUMMARIES: per lane and chunk of 64 steps (8 pieces) one 32-bit word, laid out
+// [chunk][lane], that says of every cell and piece whether its word is "plain" -- eight diagonal steps, none the path's start:
+// exactly (word & KP_PLAIN_MASK) == 0, the test the walk makes -- so that the walk need not fetch a piece to learn that one
+// bit.  Cell k has byte k of the word; piece q of the chunk has bit 7 - q of that byte (set = NOT plain), so that the pieces a
+// walk meets, going backwards, follow each other from a bit upwards.  Both parts are whole 128-byte lines (pieces: a multiple of
+// four per lane and P >= 4; summaries: rounded up to eight units), so every block starts on one.
+constexpr uint32_t KP_PLAIN_MASK = 0xAAAAAAAAu;  // the (inverted) D and L bits of a cell's eight steps
+constexpr int KP_SUM_PIECES = 8;                 // pieces per summary word and lane
+
+struct KpTraceBlock {
+    int P;
+    int pieces;     // per lane stream
+    int sum_words;  // per lane stream
+    __host__ __device__ uint32_t sum_off() const { return (uint32_t)P * (uint32_t)pieces; }  // 16-byte units from the block's start
+    __host__ __device__ uint32_t units() const { return sum_off() + ((((uint32_t)P * (uint32_t)sum_words + 3u) / 4u + 7u) & ~7u); }
+    __host__ __device__ size_t piece_at(int j, int l) const { return (size_t)(j / KP_TRACE_GROUP) * (KP_TRACE_GROUP * P) + KP_TRACE_GROUP * l + j % KP_TRACE_GROUP; }
+    __host__ __device__ size_t sum_at(int chunk, int l) const { return (size_t)chunk * P + l; }  // 32-bit words from sum_off()
+};
+// steps = the steps the fill makes for the task: its rows (kp_task_rows) + P - 1, lane l works on row step - l; 0: no task
+__host__ __device__ inline KpTraceBlock kp_trace_block(int P, int steps) {
+    KpTraceBlock t;
+    t.P = P;
+    t.pieces = (((steps + 7) >> 3) + 3) & ~3;
+    t.sum_words = (t.pieces + KP_SUM_PIECES - 1) / KP_SUM_PIECES;
+    return t;
+}
+__host__ __device__ inline int kp_sum_bit(int cell, int piece) { return 8 * cell + 7 - (piece & 7); }
+
 // ---- band tasks: one lane per task, whole waves together ---------------------------------------------------------------------
 // Cell (row r, band index bi) sits on target position lo + r + bi; a diagonal step keeps bi, a step to the left (E, gap
 // in the query) lowers it, a step up (F, gap in the target) raises it.  The nibble of (r, bi) is in lane stream bi / 4,
-// step r + bi / 4: piece j = step / 8 (at [j / TG][lane][j % TG] of the task's block), word bi % 4 (the cell); bit layout of a word: below.
+// step r + bi / 4: piece j = step / 8 (KpTraceBlock::piece_at), word bi % 4 (the cell); bit layout of a word: below.
 //
-// A path runs along a diagonal most of the time: it stays in one lane stream and walks it backwards.  The walk therefore
-// works on whole 16-byte pieces (8 steps x 4 cells) held in registers: when it stands on the last step of a piece and
-// all eight nibbles of its cell say "diagonal, not the start", it takes the eight steps at once; everything else (gaps,
-// the first and last steps of a path, tasks with an N, whose matches are counted base by base) goes step by step from
-// the same registers.  Pieces are fetched TG at a time (contiguous bytes) and the group
-// after the current one is requested a whole group ahead, so the dependent fetches of a path overlap with other
-// waves' work; the direction bits are read about once (a quarter of what the fill wrote).
+// A path runs along a diagonal most of the time: it stays in one lane stream and cell and walks it backwards, through pieces
+// that are plain.  Standing on the last step of a piece, the walk therefore asks the lane's summary word (it keeps the chunk's
+// and the one below in registers) how many pieces from here down are plain and takes them all at once -- one bit scan, 8 n steps,
+// one run for the visitor -- without fetching any of them.  What is not plain (the path's end piece, gaps, lane changes, the
+// start) and tasks with an N, whose matches are counted base by base, goes step by step from 16-byte pieces held in registers.
+// Pieces are fetched TG at a time (contiguous bytes: one trip to memory) and the next group the walk will need on this lane and
+// cell -- the next one the summary calls not plain -- is requested as soon as the current one is, so the dependent fetches of a
+// path overlap with its steps and with other waves' work.  With summaries = false (KAPTIVE_AMD_TRACE_SUMMARY=0: the A/B switch)
+// the walk ignores them: it fetches every group on the path, the one before the current requested a group ahead, and learns
+// "plain" from the piece itself.
 // Matches: without an N in the gene or the window every diagonal step scores +2 or -4, so
 // score = 6 * matches - 4 * diagonal_steps - gap_costs gives the matches in closed form; tasks that saw an N (flagged by
 // the fill kernel) compare the bases of every diagonal step instead.
@@ -80,41 +113,91 @@ struct KpBandPath {
     int cols, matches /* counted base by base: has_n only */, diag, gap_cost, credit;
 };
 
-// Every lane of the wave calls it (walking = false: nothing to walk).  P = lanes of the task's band class, q0 = first row
+// Every lane of the wave calls it (walking = false: nothing to walk).  P = lanes of the task's band class, [q0, r_hi) = the rows
 // the fill computed for the task (kp_task_rows), (er, eb) = its best cell, tw = the task's trace block.
 template <class V>
-__device__ __forceinline__ void kp_band_walk(bool walking, int lo, int P, int q0, int er, int eb, bool has_n, const uint4 *tw,
-                                             const KpTaskSeqs &s, KpBandPath &out, V &v) {
+__device__ __forceinline__ void kp_band_walk(bool walking, bool summaries, int lo, int P, int q0, int r_hi, int er, int eb, bool has_n,
+                                             const uint4 *tw, const KpTaskSeqs &s, KpBandPath &out, V &v) {
     constexpr int TG = KP_TRACE_GROUP;
     constexpr int EX = KP_GAP_EXT;
+    static_assert(KP_SUM_PIECES % TG == 0, "a group of pieces lies in one summary word");
+    const KpTraceBlock blk = kp_trace_block(P, walking ? r_hi - q0 + P - 1 : 0);
+    const uint32_t *sum = reinterpret_cast<const uint32_t *>(tw + blk.sum_off());
     int r = er, bi = eb, state = 0, cols = 0, matches = 0, diag = 0, gap_cost = 0, gap = 0, credit = 0;
     int sr = r, sb = bi;
-    // curq = the TG pieces (contiguous bytes) of the lane stream the walk stands in, nxtq = the TG before them
-    // (requested a whole group ahead).  A group is fetched with loads in a row: one trip to memory --
+    // curq = the TG pieces (contiguous bytes) of the lane stream the walk stands in, nxtq = the group requested ahead.
+    // A group is fetched with loads in a row: one trip to memory --
     // with a load per piece the line had left the L2 by the time the walk came back for the next one (75 % misses,
     // one random 64-byte fetch per piece: the kernel ran at the rate HBM serves those, tools/microbench/l2_gather.hip)
     uint4 curq[TG], nxtq[TG];
 #pragma unroll
     for (int i = 0; i < TG; ++i) curq[i] = nxtq[i] = make_uint4(0, 0, 0, 0);
     int cur_tag = -1, nxt_tag = -1;  // (stream << 20) | group index
+    // the lane's summary words of the chunk the walk stands in and of the one below (all ones where there is none: nothing to skip)
+    uint32_t s_cur = ~0u, s_low = ~0u;
+    int s_tag = -1;  // (stream << 20) | chunk
+    // plain pieces of cell k from piece `pc` of chunk `ch` downwards, as far as the two words in hand tell (the walk stands in
+    // chunk ch or in the one above its first piece); `known` = false: all of them were plain, the run may go on below
+    auto plain_run = [&](int k, int pc, bool &known) -> int {
+        const int p = pc & 7;
+        const uint32_t hi = ((s_cur >> (8 * k)) & 255u) >> (7 - p);  // bits 0 .. p: pieces p .. 0
+        int n = __ffs((int)(hi | (1u << (p + 1)))) - 1;
+        known = n <= p;
+        if (!known) {
+            const int m = __ffs((int)(((s_low >> (8 * k)) & 255u) | 256u)) - 1;  // pieces 7 .. 0 of the chunk below
+            n += m;
+            known = m < 8;
+        }
+        return n;
+    };
     while (__any(walking)) {
         if (!walking) continue;
         const int l = bi >> 2, k = bi & 3, step = r - q0 + l;
         const int pc = step >> 3, grp = pc / TG, tag = (l << 20) | grp;
+        if (summaries) {
+            const int ch = pc / KP_SUM_PIECES, stag = (l << 20) | ch;
+            if (stag != s_tag) {  // (the word below was requested when the walk entered the chunk above: it is here by now)
+                s_cur = stag + 1 == s_tag && (s_tag & 0xFFFFF) != 0 ? s_low : sum[blk.sum_at(ch, l)];
+                s_low = ch > 0 ? sum[blk.sum_at(ch - 1, l)] : ~0u;
+                s_tag = stag;
+            }
+            if (state == 0 && !has_n && (step & 7) == 7) {
+                bool known;
+                // (a path's first piece is never plain -- above row q0 every H is 0, so its first step is a start or not diagonal --;
+                // the run is kept off piece 0 all the same, so that no trace content can take the walk above its first step)
+                const int n = min(plain_run(k, pc, known), pc);
+                if (n > 0) {  // 8 n plain diagonal steps (a diagonal step stays on its lane and cell)
+                    cols += 8 * n; diag += 8 * n; r -= 8 * n;
+                    v.run(KP_COL_M, 8 * n);
+                    continue;
+                }
+            }
+        }
         if (tag != cur_tag) {
-            const uint4 *stream = tw + TG * l;
             if (tag == nxt_tag) {
 #pragma unroll
                 for (int i = 0; i < TG; ++i) curq[i] = nxtq[i];
             } else {
 #pragma unroll
-                for (int i = 0; i < TG; ++i) curq[i] = stream[(size_t)grp * (TG * P) + i];
+                for (int i = 0; i < TG; ++i) curq[i] = tw[blk.piece_at(grp * TG, l) + i];
             }
             cur_tag = tag;
-            if (grp > 0) {
+            // ahead: the group before this one, or -- told by the summaries -- the next one below it that is not all plain
+            int ahead = grp - 1;
+            if (summaries && !has_n && grp > 0) {  // (a task with an N visits every piece: the group before)
+                // (the first piece of a group is never the first of a chunk's upper neighbour: KP_SUM_PIECES % TG == 0, so the
+                // pieces below the group start in this chunk or are the whole chunk below)
+                bool known;
+                const int first = grp * TG;  // the group's first piece
+                int n;
+                if (first & 7) n = plain_run(k, first - 1, known);
+                else { n = __ffs((int)(((s_low >> (8 * k)) & 255u) | 256u)) - 1; known = n < 8; }
+                ahead = known && first - 1 - n >= 0 ? (first - 1 - n) / TG : -1;
+            }
+            if (ahead >= 0) {
 #pragma unroll
-                for (int i = 0; i < TG; ++i) nxtq[i] = stream[(size_t)(grp - 1) * (TG * P) + i];
-                nxt_tag = tag - 1;
+                for (int i = 0; i < TG; ++i) nxtq[i] = tw[blk.piece_at(ahead * TG, l) + i];
+                nxt_tag = (l << 20) | ahead;
             }
         }
         uint4 cur = (pc & 1) ? curq[1] : curq[0];
@@ -123,15 +206,9 @@ __device__ __forceinline__ void kp_band_walk(bool walking, int lo, int P, int q0
             cur = (pc & 2) ? hi2 : cur;
         }
         const uint32_t word = kp_piece_word(cur, k);
-        if (state == 0 && !has_n && (step & 7) == 7 && (word & 0xAAAAAAAAu) == 0u) {  // eight plain diagonal steps (D and L are stored inverted)
-            // ... and the eight before them when they are the same cell's other piece of the group in hand (a diagonal step
-            // stays on its lane and cell): a wave goes round this loop as often as its slowest lane, and most paths are plain
-            int n = 8;
-#ifndef KP_TB_NO16
-            if (TG == 2 && (pc & 1) && (kp_piece_word(curq[0], k) & 0xAAAAAAAAu) == 0u) n = 16;
-#endif
-            cols += n; diag += n; r -= n;
-            v.run(KP_COL_M, n);
+        if (!summaries && state == 0 && !has_n && (step & 7) == 7 && (word & KP_PLAIN_MASK) == 0u) {  // eight plain diagonal steps (D and L are stored inverted)
+            cols += 8; diag += 8; r -= 8;
+            v.run(KP_COL_M, 8);
             continue;
         }
         // a cell's word: steps 0-3 in the low half, 4-7 in the high half; per half a byte of [L, F opened] pairs below
