@@ -67,7 +67,8 @@ KP_API void *kp_ctx_stream(kp_ctx *ctx);
  * cigar (0 | 1: CIGARs of the hits, kp_batch_cigars; from the next kp_batch_align) and cigar_ops_per_hit (first size of their
  * buffer; setting it forgets what the context has learnt for it), cs (0 | 1: cs difference strings of the hits, kp_batch_cs;
  * from the next kp_batch_align; such a pass computes the CIGARs as well) and cs_bytes_per_hit (first size of their buffer,
- * likewise). */
+ * likewise), variants (0 | 1: variant records of the kept hits, kp_batch_variants; from the next kp_batch_align; such a pass
+ * computes the CIGARs as well) and variants_per_kept (first size of their buffer, likewise). */
 KP_API int kp_ctx_set_option(kp_ctx *ctx, const char *name, int64_t value);
 #define KP_WORK_SLOTS 3
 
@@ -320,6 +321,22 @@ KP_API int kp_batch_typing(kp_ctx *ctx, kp_batch *batch, kp_asm_summary *summari
                            kp_piece *pieces, int32_t piece_stride);
 /* Translated proteins of one assembly (kp_kept.prot_off/prot_len index into it); returns bytes copied. */
 KP_API int kp_batch_proteins(kp_ctx *ctx, kp_batch *batch, int32_t asm_index, uint8_t *out, int64_t cap);
+/* Variant records of the kept hits (kp_spec.h, VARIANTS): for every record of the kept lists kp_batch_typing returns, which bases
+ * of the contig differ from the database's gene -- in the gene's forward coordinates -- and what a substituted base does to its
+ * codon.  The reference has no such output.  Only for a batch whose kp_batch_align ran with the option `variants` set (default 0:
+ * nothing is computed, allocated or launched for them; variants = 1 computes the CIGARs too, whatever `cigar` says), after
+ * kp_batch_reduce, for the group kp_batch_use_group chose.  Without ops for the current hit table -- the option was off, or
+ * kp_batch_set_hits replaced the table -- both calls return KP_EINVAL and kp_last_error names the cause; the context types its
+ * next batch as usual.  The records are made on the first of these calls after a reduction (three kernels on the reduction's
+ * stream) and kept until the next kp_batch_reduce of the group, the batch's next kp_batch_align or kp_batch_set_hits.
+ *   kp_batch_variant_offsets : var_off[n_asm + 1]: the records of assembly a are variants[var_off[a] .. var_off[a + 1])
+ *   kp_batch_variants        : the records, hits in kept-list order, ascending in q_pos within a hit; KP_EINVAL when
+ *                              cap < var_off[n_asm]
+ * The option `variants_per_kept` is the first guess for the size of the record buffer (default 8 per kept record); the context
+ * learns what its batches need, and a buffer that was too small is grown and the records stored again: no alignment pass and no
+ * reduction is rerun, and the retries kp_batch_stats counts stay as they were.  A second overflow is KP_EOVERFLOW. */
+KP_API int kp_batch_variant_offsets(kp_ctx *ctx, kp_batch *batch, int64_t *var_off);
+KP_API int kp_batch_variants(kp_ctx *ctx, kp_batch *batch, kp_variant *out, int64_t cap);
 
 /* ---- report rows (host only) -----------------------------------------------------------------------------------------------
  * Replaces KaptiveRow.from_result + bytes(row) per genome (src/kaptive/serotyping/io.py:191-296, 37-43): the TSV lines
@@ -379,6 +396,29 @@ KP_API int64_t kp_format_paf(const kp_paf_tables *tables, int32_t n_asm, const k
 KP_API int64_t kp_format_paf_tags(const kp_paf_tables *tables, int32_t n_asm, const kp_hit *hits, const int64_t *hit_off,
                                   const uint32_t *ops, const int64_t *cigar_off, const char *cs, const int64_t *cs_off, int32_t flags,
                                   char *out, int64_t cap);
+
+/* ---- variant table of a batch (host only) -------------------------------------------------------------------------------------
+ * One tab-separated line per variant record, in the records' order: Assembly, Contig, Position (1-based, contig forward strand),
+ * Strand (of the hit), Gene, Gene position (1-based, gene forward strand), Type (snv / ins / del), Length, Ref, Alt (gene-strand
+ * letters of an SNV, n for an ambiguous base; "." for ins and del), Codon (1-based), Ref aa, Alt aa ("." for ins and del) and
+ * Effect: for an SNV ambiguous (a side is n), synonymous (same amino acid), nonsense (alt is a stop, ref is not), stop_lost (ref is
+ * a stop, alt is not) or missense; for ins and del frameshift when Length % 3 != 0, else inframe.  No header line.  kept /
+ * kept_stride as kp_batch_typing filled them, variants / var_off as kp_batch_variants / kp_batch_variant_offsets did.  Names are
+ * byte blobs with n + 1 offsets, the contigs of all assemblies back to back as in kp_paf_tables.  Returns the number of bytes the
+ * lines need (written to `out` while they fit `cap`), or a negative error code (KP_EINVAL also for a record that names a kept
+ * record, gene or contig the tables do not have, or whose kind is unknown). */
+typedef struct kp_variant_tables {
+    const char *gene_names;
+    const int32_t *gene_name_off;
+    int32_t n_genes;
+    const char *asm_names;
+    const int64_t *asm_name_off;  /* n_asm + 1 */
+    const char *ctg_names;
+    const int64_t *ctg_name_off;
+    const int64_t *asm_first_ctg; /* n_asm + 1 */
+} kp_variant_tables;
+KP_API int64_t kp_format_variants(const kp_variant_tables *tables, int32_t n_asm, const kp_kept *kept, int32_t kept_stride,
+                                  const kp_variant *variants, const int64_t *var_off, char *out, int64_t cap);
 
 /* ---- JSON lines of a whole batch (host only) ----------------------------------------------------------------------------------
  * Replaces orjson.dumps(SerotypingResult.to_dict(), OPT_SERIALIZE_NUMPY | OPT_APPEND_NEWLINE) per genome

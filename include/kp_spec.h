@@ -437,4 +437,37 @@ typedef struct kp_typing_params {
     int32_t edge_tolerance;   /* Serotyper.partial_edge_tolerance */
 } kp_typing_params;
 
+/* ---- VARIANTS (optional, like the CIGAR and the cs string: no hit, no op, no kept record and no report byte depends on them) ------
+ * The variant records of a KEPT hit say, in the gene's own coordinates, where the contig differs from the database's gene and
+ * what a substituted base does to the codon it lies in.  They are listed for the records of the kept list only (kp_kept), never
+ * for hits the overlap cull dropped.
+ *
+ * ONE RECORD PER cs TOKEN.  Every * token of the hit's cs string (kp_spec.h, CS) is one SNV -- a column with an n on either side
+ * included: the rule `matches` and the cs string use --, every + token one DEL (the gene has bases the contig lacks, a CIGAR I
+ * op), every - token one INS (the contig has bases the gene lacks, a CIGAR D op); : runs give nothing.  Bases of inserted or
+ * deleted runs are not listed: the cs string has them.
+ * PURE FUNCTION.  The record list of a hit is a function of its CIGAR ops and its two sequences, nothing else.
+ * CODON CONSEQUENCES ARE PER VARIANT, IN ISOLATION.  ref_aa is the amino acid of codon q_pos / 3 of the gene's own forward
+ * sequence (the database's gene, frame 0), alt_aa that of the same codon with this ONE base replaced: two SNVs in one codon are
+ * each annotated against the unmodified reference codon.  The table is the product's (kp_fill_codon_table: NCBI 11, a codon with
+ * an ambiguous base is X); a last codon cut short by a gene length that is not a multiple of 3 is X on both sides.
+ * ORDER.  Within a hit the records ascend in q_pos (for strand -1 that is the reverse of the ops' order); hits come in the order
+ * of the kept list, assemblies in batch order; var_off[n_asm + 1] delimits the assemblies. */
+#define KP_VAR_SNV 0
+#define KP_VAR_INS 1
+#define KP_VAR_DEL 2
+typedef struct kp_variant {
+    int32_t kept;  /* index of the record in the assembly's kept list, as kp_batch_typing returns that list */
+    int32_t q_pos; /* 0-based, on the gene's FORWARD strand.  SNV: the base; DEL: the first gene base that is absent; INS: the gene
+                      base before which the extra bases lie on the gene's forward strand */
+    int32_t t_pos; /* 0-based, on the contig's forward strand.  SNV: the base; INS: the lowest coordinate of the extra bases; DEL: the
+                      first contig base above the gap in contig-forward order */
+    int32_t len;   /* 1 for an SNV, the op's length for INS and DEL */
+    uint8_t kind;  /* KP_VAR_SNV: one differing M column; KP_VAR_INS: a CIGAR D op; KP_VAR_DEL: a CIGAR I op */
+    uint8_t ref, alt;       /* SNV only: gene-strand codes 0..3, 4 = ambiguous; ref the gene's base, alt the contig's (complemented for
+                               strand -1).  0 for INS and DEL */
+    uint8_t ref_aa, alt_aa; /* SNV only, ASCII (above).  0 for INS and DEL */
+    uint8_t pad_[3];        /* zero */
+} kp_variant;
+
 #endif /* KP_SPEC_H */

@@ -142,7 +142,8 @@ int kp_batch_align(kp_ctx *ctx, kp_batch *b) {
     kp_caps_size(ctx->opt, ctx->learnt, b->n_asm, b->view.total_words, *w);
     w->aligned = false; w->finalised = false;
     w->cs_on = ctx->opt.cs != 0; w->cs_valid = false;
-    w->cigar_on = ctx->opt.cigar != 0 || w->cs_on; w->cigar_valid = false;  // (cs reads the ops)
+    w->var_on = ctx->opt.variants != 0;
+    w->cigar_on = ctx->opt.cigar != 0 || w->cs_on || w->var_on; w->cigar_valid = false;  // (cs and the variant records read the ops)
     for (auto &v : w->h_tasks) v.clear();
     w->reset_runs();
     w->stats[KP_STAT_RERUNS] = 0;

@@ -205,6 +205,38 @@ inline bool kp_caps_set_cs_option(KpCsCaps &c, const std::string &n, int64_t val
     return true;
 }
 
+// variant records of the kept hits (kp_variants.hip; only with the `variants` option): the same policy once more, per kept record.
+// The walk counts every kept hit's records before it writes them, so `need` is exact however small the buffer was.
+struct KpVarCaps {
+    // first guess for the records of a reduction, per kept record.  A guess, not a measurement: a kept gene of 1000 bases at 1 %
+    // divergence has about ten, a clean copy none, so 8 lies between them; a batch that needs more grows the buffer once
+    uint32_t per_kept = 8;
+    uint32_t learnt = 0;  // record buffer of a reduction = its kept records * this many (0: not yet sized); only grows
+};
+inline uint64_t kp_caps_variants_size(KpVarCaps &c, uint64_t total_kept) {
+    if (c.learnt == 0) c.learnt = std::max<uint32_t>(c.per_kept, 1u);
+    return std::max<uint64_t>(total_kept, 1) * c.learnt;
+}
+// true: the records fitted (what came close makes room for later batches); false: `cap` has grown -- write the records again, nothing else
+inline bool kp_caps_after_variants(KpVarCaps &c, uint64_t &cap, uint64_t total_kept, uint64_t need) {
+    const uint64_t kept = std::max<uint64_t>(total_kept, 1);
+    auto per_kept = [&](uint64_t records) { return (uint32_t)std::min<uint64_t>((records + kept - 1) / kept, 0xFFFFFFFFu); };
+    if (need <= cap) {
+        if (need + need / 8 > cap) c.learnt = std::max(c.learnt, per_kept(need + need / 4));
+        return true;
+    }
+    cap = need + need / 4;  // later batches differ a little
+    c.learnt = std::max(c.learnt, per_kept(cap));
+    return false;
+}
+// kp_ctx_set_option of `variants_per_kept` (false: `name` is something else): it also resets what the context has learnt
+inline bool kp_caps_set_variants_option(KpVarCaps &c, const std::string &n, int64_t value) {
+    if (n != "variants_per_kept") return false;
+    c.per_kept = (uint32_t)std::max<int64_t>(std::min<int64_t>(value, 0xFFFFFFFFll), 1);
+    c.learnt = 0;
+    return true;
+}
+
 // overflow flags of a reduction (KpAsmSummary::overflow: 1 kept hits, 2 pieces, 8 proteins); false: `err` says what cannot grow
 inline bool kp_caps_grow_run(KpRunCaps &c, int flags, std::string &err) {
     if (flags & 1) {

@@ -48,19 +48,11 @@ KP_HD void kp_cs_num(Sink &out, uint32_t v) {
 
 KP_HD char kp_cs_letter(unsigned code) { return code > 3u ? 'n' : (char)("acgt"[code]); }
 
-// the open run of identical columns and the cursor into the N runs, as the hit is walked along the target
-template <class Sink>
-struct KpCsWalk {
-    Sink &out;
+// the cursor into the assembly's N runs, as a hit is walked along the target (kp_variants.h walks with it too)
+struct KpRunCursor {
     const KpTargetSeq &t;
-    uint32_t same = 0;  // identical columns not yet written
-    int run;            // first N run whose end lies beyond the position last asked about
-    KP_HD KpCsWalk(Sink &o, const KpTargetSeq &tt, int t0) : out(o), t(tt), run(kp_first_run_after(tt.runs, tt.n_runs, t0)) {}
-    KP_HD void close_same() {
-        if (!same) return;
-        out.put(':'); kp_cs_num(out, same);
-        same = 0;
-    }
+    int run;  // first N run whose end lies beyond the position last asked about
+    KP_HD KpRunCursor(const KpTargetSeq &tt, int t0) : t(tt), run(kp_first_run_after(tt.runs, tt.n_runs, t0)) {}
     // positions are asked about in ascending order only
     KP_HD void seek(int pos) { while (run < t.n_runs && t.runs[2 * run + 1] <= pos) ++run; }
     KP_HD bool in_run(int pos) { seek(pos); return run < t.n_runs && t.runs[2 * run] <= pos; }
@@ -73,6 +65,19 @@ struct KpCsWalk {
             if (e > s) m |= ((1u << e) - 1u) & ~((1u << s) - 1u);
         }
         return m;
+    }
+};
+
+// the open run of identical columns on top of the cursor
+template <class Sink>
+struct KpCsWalk : KpRunCursor {
+    Sink &out;
+    uint32_t same = 0;  // identical columns not yet written
+    KP_HD KpCsWalk(Sink &o, const KpTargetSeq &tt, int t0) : KpRunCursor(tt, t0), out(o) {}
+    KP_HD void close_same() {
+        if (!same) return;
+        out.put(':'); kp_cs_num(out, same);
+        same = 0;
     }
 };
 
@@ -98,6 +103,23 @@ KP_HD int kp_cs_ctz8(uint32_t m) {  // lowest set bit of a non-zero 8-bit mask
 #endif
 }
 
+// Up to eight M columns whose rows r .. r + k lie in one word of the packed gene, against the contig from column t: the gene's
+// nibbles, the contig's codes spread to nibbles, the columns inside an N run and a bit per differing column (kp_spec.h, CS:
+// identical iff both codes are <= 3 and equal).  The cs walk below and the variant walk (kp_variants.h) compare with it.
+struct KpCsCols { uint32_t g, tn, nm, diff; };
+KP_HD KpCsCols kp_cs_columns(const KpTaskSeqs &s, KpRunCursor &w, int r, int t, int k) {
+    const uint32_t keep = k == 8 ? ~0u : (1u << (4 * k)) - 1u;
+    KpCsCols c;
+    c.g = (s.q.nib[r >> 3] >> (4 * (r & 7))) & keep;
+    const int sh = 2 * (t & 15);
+    uint32_t bits = s.t.words[t >> 4] >> sh;
+    if ((t & 15) + k > 16) bits |= s.t.words[(t >> 4) + 1] << (32 - sh);  // (sh > 0 here)
+    c.tn = kp_cs_spread(bits & 0xFFFFu) & keep;
+    c.nm = w.n_mask(t, k);
+    c.diff = kp_cs_any_nibble(c.g ^ c.tn) | c.nm;
+    return c;
+}
+
 // The hit's cs string into `out`.  ops: its n_ops CIGAR ops along the target; q0: first row of the path in the gene as aligned
 // (s.q is that strand's codes); t0: first column, in the assembly's padded space.
 template <class Sink>
@@ -110,14 +132,9 @@ KP_HD void kp_cs_hit(const uint32_t *ops, int64_t n_ops, const KpTaskSeqs &s, in
         if (kind == KP_CIGAR_M) {
             while (left > 0) {
                 const int in_word = 8 - (r & 7), k = left < in_word ? left : in_word;  // rows of one gene word
-                const uint32_t keep = k == 8 ? ~0u : (1u << (4 * k)) - 1u;
-                const uint32_t g = (s.q.nib[r >> 3] >> (4 * (r & 7))) & keep;
-                const int sh = 2 * (t & 15);
-                uint32_t bits = s.t.words[t >> 4] >> sh;
-                if ((t & 15) + k > 16) bits |= s.t.words[(t >> 4) + 1] << (32 - sh);  // (sh > 0 here)
-                const uint32_t tn = kp_cs_spread(bits & 0xFFFFu) & keep;
-                const uint32_t nm = w.n_mask(t, k);
-                uint32_t diff = kp_cs_any_nibble(g ^ tn) | nm;
+                const KpCsCols c = kp_cs_columns(s, w, r, t, k);
+                const uint32_t g = c.g, tn = c.tn, nm = c.nm;
+                uint32_t diff = c.diff;
                 if (!diff) w.same += (uint32_t)k;
                 else {
                     int at = 0;

@@ -257,10 +257,12 @@ int kp_ctx_set_option(kp_ctx *ctx, const char *name, int64_t value) {
     KpOptions &o = ctx->opt;
     if (kp_caps_set_option(o, ctx->learnt, ctx->run_caps, n, value)) return KP_OK;
     if (kp_caps_set_cs_option(ctx->cs_caps, n, value)) return KP_OK;
+    if (kp_caps_set_variants_option(ctx->var_caps, n, value)) return KP_OK;
     if (n == "scan_mode") o.scan_mode = (int)value;
     else if (n == "library_sort") o.library_sort = value != 0;
     else if (n == "cigar") o.cigar = value != 0;
     else if (n == "cs") o.cs = value != 0;
+    else if (n == "variants") o.variants = value != 0;
     else if (n == "upload_piece_mb") o.upload_piece_mb = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(value, 4096));
     else return kp_fail(ctx, KP_EINVAL, "unknown option: " + n);
     return KP_OK;

@@ -53,6 +53,20 @@ struct KpTypingRun {
     bool sums_valid = false;  // h_sums / max_kept / max_pieces belong to the most recent reduction
     std::vector<KpAsmSummary> h_sums;
     int32_t max_kept = 1, max_pieces = 1;
+    // variant records of the kept hits (kp_variants.hip), only where the pass ran with the `variants` option: nothing below is
+    // allocated otherwise.  Made on first request after a reduction; theirs until the next reduction or until the hit table goes.
+    bool var_valid = false;
+    uint64_t var_cap = 0;              // records d_var was sized for
+    int64_t var_total = 0;             // records of all kept hits
+    std::vector<int64_t> h_kept_off;   // [n_asm + 1] kept records before every assembly
+    std::vector<int64_t> h_var_off;    // [kept records + 1] first record of every kept hit
+    DevBuf<int64_t> d_kept_off, d_var_src, d_var_off;
+    DevBuf<uint32_t> d_var_cnt;
+    DevBuf<kp_variant> d_var;
+    KpKeptRows kept_rows(int32_t gene_lo) const {
+        return {.kept = d_kept.p, .kept_cap = kept_cap, .kept_off = d_kept_off.p, .total = h_kept_off.empty() ? 0 : h_kept_off.back(), .gene_lo = gene_lo};
+    }
+    KpPerHit<kp_variant> variants() const { return {.cnt = d_var_cnt.p, .off = d_var_off.p, .data = d_var.p, .cap = (int64_t)var_cap}; }
     // d_pairs: the pairs of the protein DP, one slot per kept row: q_off, q_len, t_off, t_len [slots each], then pair_base [n_asm], n_pairs [1]
     size_t slots() const { return n_asm * (size_t)kept_cap; }
     size_t pairs_len() const { return 4 * slots() + n_asm + 1; }
@@ -74,6 +88,7 @@ struct KpOptions : KpCapOptions {
     int readback_copy_engine = 0;   // results read back with hipMemcpyAsync instead of the read-back kernel (see Fetch)
     int spin_wait = 0;              // host waits spin on the stream (the runtime's default) instead of blocking on an interrupt
     int cigar = 0;                  // CIGARs of the finished hits (kp_cigar.hip): off unless asked for; applies from the next kp_batch_align
+    int variants = 0;               // variant records of the kept hits (kp_variants.hip); a pass with it computes the CIGARs too: the records are read off them
     int cs = 0;                     // cs difference strings of the finished hits (kp_cs.hip); a pass with it computes the CIGARs too: cs reads them
     bool trace_summary = true;      // KAPTIVE_AMD_TRACE_SUMMARY=0: the band walks ignore the fills' piece summaries and fetch every piece on a path (kp_walk.h; A/B switch)
     bool join_stats = false;        // KAPTIVE_AMD_JOIN_STATS: kp_batch_wait reports the pass's group / join / mid_occ counts on stderr
@@ -178,6 +193,7 @@ struct KpWork : KpPassCaps {
     DevBuf<uint32_t> d_cs_cnt;
     DevBuf<int64_t> d_cs_off;        // [total_hits + 1] first byte of every hit
     DevBuf<char> d_cs_bytes;
+    bool var_on = false;             // the pass was enqueued with the `variants` option (kp_variants.hip; the records live in the typing runs)
     // reduction: one run per typing group, created on first use
     std::vector<std::unique_ptr<KpTypingRun>> runs;
     // results
@@ -204,7 +220,7 @@ struct KpWork : KpPassCaps {
     KpHitRows hit_rows() const { return {.hit_off = d_cig_hit_off.p, .total = hit_off[n_asm]}; }
     KpPerHit<uint32_t> cigars() const { return {.cnt = d_cig_cnt.p, .off = d_cig_off.p, .data = d_cig_ops.p, .cap = (int64_t)cigar_cap}; }
     KpPerHit<char> cs() const { return {.cnt = d_cs_cnt.p, .off = d_cs_off.p, .data = d_cs_bytes.p, .cap = (int64_t)cs_cap}; }
-    void reset_runs() { for (auto &r : runs) if (r) r->split = r->scored = r->reduced = r->sums_valid = false; }  // their hit table is about to be rewritten
+    void reset_runs() { for (auto &r : runs) if (r) r->split = r->scored = r->reduced = r->sums_valid = r->var_valid = false; }  // their hit table is about to be rewritten
 };
 
 #define KP_INPUT_POOL 16  /* recycled device copies of batch inputs: uploads run several shards ahead of the passes that read them */
@@ -223,6 +239,7 @@ struct kp_ctx {
     KpOptions opt;
     KpLearnt learnt;
     KpCsCaps cs_caps;  // byte buffer of the cs strings: option and learnt size (kp_caps.h)
+    KpVarCaps var_caps;  // record buffer of the variant records, likewise
     // resident database
     bool has_db = false;
     int32_t n_genes = 0;

@@ -256,6 +256,11 @@ struct KpHitTable {  // the finished table, the raw one with its sort keys, or a
 struct KpHitRows { const int64_t *hit_off; int64_t total; };  // rows as kp_batch_hits lists them: device hit_off[n_asm + 1]
 template <class T>
 struct KpPerHit { uint32_t *cnt; int64_t *off; T *data; int64_t cap; };  // per finished hit: items counted, scanned (off[total + 1]), written
+struct KpKeptRows {  // the kept records of a finished reduction, row by row: device kept_off[n_asm + 1] counts them per assembly
+    const kp_kept *kept; int kept_cap;
+    const int64_t *kept_off; int64_t total;
+    int32_t gene_lo;  // first gene of the typing group: kept records index genes relative to it, the hit table does not
+};
 struct KpReduceTables {  // what the reduction, the protein DP of its kept hits and the gene states share (types: kp_reduce_core.h)
     const int32_t *best;
     uint64_t *keys;
@@ -330,6 +335,11 @@ void kp_launch_count_scan(const uint32_t *cnt, int64_t n, int64_t *off, hipStrea
 // cig: what kp_launch_cigar_walk left; nothing here reads the trace buffer.
 void kp_launch_cs_walk(const KpBatchView &b, const KpGenes &genes, const KpHitTable &hits, const KpHitRows &rows, const KpPerHit<uint32_t> &cig,
                        const KpPerHit<char> &cs, bool emit, hipStream_t stream);
+// kp_variants.hip (only with the `variants` option; after a reduction, while the ops of the pass are valid): the variant records
+// (kp_spec.h, VARIANTS) of every kept record -- the hit behind it located in the finished table (src: its row, -1 none), its records
+// counted (var.cnt) and scanned (var.off), or with `emit` stored from var.off[row] -- stores beyond var.cap are dropped.
+void kp_launch_variants_walk(const KpBatchView &b, const KpGenes &genes, const KpHitTable &hits, const KpHitRows &rows, const KpPerHit<uint32_t> &cig,
+                             const KpKeptRows &kept, int64_t *src, const KpPerHit<kp_variant> &var, bool emit, hipStream_t stream);
 // kp_reduce.hip: assembly a's hits with gene in [gene_lo, gene_hi) (one run: hits are sorted by gene) -> out rows, gene
 // indices relative to gene_lo; out.count[a] = how many
 void kp_launch_hit_split(const KpHitTable &hits, int32_t gene_lo, int32_t gene_hi, const KpHitTable &out, int32_t n_asm, hipStream_t stream);

@@ -264,3 +264,50 @@ extern "C" int64_t kp_format_paf_tags(const kp_paf_tables *t, int32_t n_asm, con
                                       const int64_t *cigar_off, const char *cs, const int64_t *cs_off, int32_t flags, char *out, int64_t cap) {
     return format_paf(t, n_asm, hits, hit_off, ops, cigar_off, cs, cs_off, flags, out, cap);
 }
+
+// ---- variant table (kp_spec.h, VARIANTS) -----------------------------------------------------------------------------------------
+// One line per record, straight from the records and the name tables: the streaming command line builds no object per assembly,
+// let alone per variant.
+extern "C" int64_t kp_format_variants(const kp_variant_tables *t, int32_t n_asm, const kp_kept *kept, int32_t kept_stride, const kp_variant *variants,
+                                      const int64_t *var_off, char *out, int64_t cap) {
+    if (!t || n_asm < 0 || cap < 0 || (cap > 0 && !out) || (n_asm > 0 && (!var_off || !t->asm_name_off || !t->asm_first_ctg))) return KP_EINVAL;
+    if (n_asm > 0 && (var_off[n_asm] < var_off[0] || (var_off[n_asm] > var_off[0] && (!variants || !kept)))) return KP_EINVAL;
+    static const char letters[] = "acgtn";
+    Out o{out, cap};
+    for (int a = 0; a < n_asm; ++a) {
+        const int64_t c0 = t->asm_first_ctg[a], nc = t->asm_first_ctg[a + 1] - c0;
+        if (var_off[a + 1] < var_off[a]) return KP_EINVAL;
+        for (int64_t i = var_off[a]; i < var_off[a + 1]; ++i) {
+            const kp_variant &v = variants[i];
+            if (v.kept < 0 || v.kept >= kept_stride || v.kind > KP_VAR_DEL) return KP_EINVAL;
+            const kp_kept &k = kept[(size_t)a * (size_t)kept_stride + (size_t)v.kept];
+            if (k.gene < 0 || k.gene >= t->n_genes || k.contig < 0 || k.contig >= nc) return KP_EINVAL;
+            const int64_t c = c0 + k.contig;
+            o.put(t->asm_names + t->asm_name_off[a], t->asm_name_off[a + 1] - t->asm_name_off[a]); o.put('\t');
+            o.put(t->ctg_names + t->ctg_name_off[c], t->ctg_name_off[c + 1] - t->ctg_name_off[c]); o.put('\t');
+            put_i(o, (long long)v.t_pos + 1); o.put('\t');
+            o.put(k.strand < 0 ? '-' : '+'); o.put('\t');
+            o.put(t->gene_names + t->gene_name_off[k.gene], t->gene_name_off[k.gene + 1] - t->gene_name_off[k.gene]); o.put('\t');
+            put_i(o, (long long)v.q_pos + 1); o.put('\t');
+            o.lit(v.kind == KP_VAR_SNV ? "snv" : (v.kind == KP_VAR_INS ? "ins" : "del")); o.put('\t');
+            put_i(o, v.len); o.put('\t');
+            if (v.kind == KP_VAR_SNV) {
+                o.put(letters[v.ref > 4 ? 4 : v.ref]); o.put('\t');
+                o.put(letters[v.alt > 4 ? 4 : v.alt]); o.put('\t');
+                put_i(o, (long long)v.q_pos / 3 + 1); o.put('\t');
+                o.put((char)v.ref_aa); o.put('\t');
+                o.put((char)v.alt_aa); o.put('\t');
+                if (v.ref > 3 || v.alt > 3) o.lit("ambiguous");
+                else if (v.ref_aa == v.alt_aa) o.lit("synonymous");
+                else if (v.alt_aa == '*') o.lit("nonsense");
+                else if (v.ref_aa == '*') o.lit("stop_lost");
+                else o.lit("missense");
+            } else {
+                o.lit(".\t.\t.\t.\t.\t");
+                o.lit(v.len % 3 != 0 ? "frameshift" : "inframe");
+            }
+            o.put('\n');
+        }
+    }
+    return o.n;
+}

@@ -1,4 +1,5 @@
-// kp_typing.hip -- batched typing (locus scores, the reduction of a batch's hits, gene states; per typing group), stand-alone protein aligner.
+// kp_typing.hip -- batched typing (locus scores, the reduction of a batch's hits, gene states, the variant records of the kept hits; per
+// typing group), stand-alone protein aligner.
 #include "kp_host.h"
 
 // the typing group a batch currently addresses and the run of the batch's work set for it (created on first use)
@@ -148,6 +149,7 @@ int kp_batch_reduce(kp_ctx *ctx, kp_batch *b, const int32_t *best_locus, const k
     if (rc) return rc;
     R.reduced = true;
     R.sums_valid = false;
+    R.var_valid = false;  // (the variant records describe a kept list: the one that is about to be replaced)
     return KP_OK;
 }
 
@@ -231,6 +233,71 @@ int kp_batch_typing(kp_ctx *ctx, kp_batch *b, kp_asm_summary *summaries, kp_kept
         summaries[a].n_normal = (int32_t)vals.size();
         summaries[a].ident_sum = kp_np_sum_f32(vals.data(), (int)vals.size());
     }
+    return KP_OK;
+}
+
+// ---- variant records of the kept hits (kp_variants.hip; kp_spec.h, VARIANTS) ------------------------------------------------------
+static const char *const NO_VARIANTS = "this batch has no variant records (aligned without the variants option, or its hit table was replaced)";
+
+// The records of the batch's current group, made on first request after its reduction: the hit behind every kept record located and
+// its records counted, the counts scanned, the records stored -- on the reduction's stream, behind the kernels that finalised the
+// kept list.  The buffer follows the policy of kp_caps.h; where it was too small only the storing kernel runs again: counts and
+// offsets are exact whatever the buffer held.  No alignment pass, no reduction and no kp_batch_stats counter is touched.
+static int ensure_variants(kp_ctx *ctx, kp_batch *b, KpTypingRun **R_out) {
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    if (!w->var_on || !w->cigar_valid) return kp_fail(ctx, KP_EINVAL, NO_VARIANTS);
+    KpTypingRun *Rp = reduced_run(ctx, b, &w);
+    if (!Rp) return KP_ESTATE;
+    KpTypingRun &R = *Rp;
+    *R_out = Rp;
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (int rc = fetch_summaries(ctx, b, w)) return rc;
+    if (R.var_valid) return KP_OK;
+    const size_t n_asm = (size_t)b->n_asm;
+    R.h_kept_off.assign(n_asm + 1, 0);
+    for (size_t a = 0; a < n_asm; ++a) R.h_kept_off[a + 1] = R.h_kept_off[a] + std::min(std::max(R.h_sums[a].n_kept, 0), R.kept_cap);
+    const int64_t total = R.h_kept_off[n_asm];
+    R.h_var_off.assign((size_t)total + 1, 0);
+    R.var_total = 0;
+    if (total > 0) {
+        R.var_cap = kp_caps_variants_size(ctx->var_caps, (uint64_t)total);
+        KP_HIP_CHECK(ctx, R.d_var_src.reserve((size_t)total));
+        KP_HIP_CHECK(ctx, R.d_var_cnt.reserve((size_t)total));
+        KP_HIP_CHECK(ctx, R.d_var_off.reserve((size_t)total + 1));
+        KP_HIP_CHECK(ctx, R.d_var.reserve(R.var_cap));
+        if (int rc = upload(ctx, R.d_kept_off, R.h_kept_off.data(), n_asm + 1, R.stream)) return rc;
+        const KpTypingGroup &T = *typing_group(ctx, b);
+        kp_launch_variants_walk(b->view, ctx->genes, w->hits(), w->hit_rows(), w->cigars(), R.kept_rows(T.gene_lo), R.d_var_src.p, R.variants(), false, R.stream);
+        for (int attempt = 0;; ++attempt) {
+            kp_launch_variants_walk(b->view, ctx->genes, w->hits(), w->hit_rows(), w->cigars(), R.kept_rows(T.gene_lo), R.d_var_src.p, R.variants(), true, R.stream);
+            KP_HIP_CHECK(ctx, hipGetLastError());
+            if (int frc = fetch_all(ctx, R.stream, {{R.h_var_off.data(), R.d_var_off.p, ((size_t)total + 1) * sizeof(int64_t)}})) return frc;
+            R.var_total = R.h_var_off[(size_t)total];
+            if (kp_caps_after_variants(ctx->var_caps, R.var_cap, (uint64_t)total, (uint64_t)R.var_total)) break;
+            if (attempt >= 1) return kp_fail(ctx, KP_EOVERFLOW, "variant buffer overflowed repeatedly");
+            KP_HIP_CHECK(ctx, R.d_var.reserve(R.var_cap));
+        }
+    }
+    R.var_valid = true;
+    return KP_OK;
+}
+
+int kp_batch_variant_offsets(kp_ctx *ctx, kp_batch *b, int64_t *var_off) {
+    if (!ctx || !b || b->ctx != ctx || !var_off) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpTypingRun *R = nullptr;
+    if (int rc = ensure_variants(ctx, b, &R)) return rc;
+    for (size_t a = 0; a < R->h_kept_off.size(); ++a) var_off[a] = R->h_var_off[(size_t)R->h_kept_off[a]];
+    return KP_OK;
+}
+
+int kp_batch_variants(kp_ctx *ctx, kp_batch *b, kp_variant *out, int64_t cap) {
+    if (!ctx || !b || b->ctx != ctx || (!out && cap > 0)) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpTypingRun *R = nullptr;
+    if (int rc = ensure_variants(ctx, b, &R)) return rc;
+    if (cap < R->var_total) return kp_fail(ctx, KP_EINVAL, "variant buffer too small");
+    if (R->var_total > 0)
+        if (int frc = fetch_all(ctx, R->stream, {{out, R->d_var.p, (size_t)R->var_total * sizeof(kp_variant)}})) return frc;
     return KP_OK;
 }
 

@@ -3,7 +3,8 @@
 Field names and dtypes are the reference's (src/kaptive/db/core.py:82-98). What differs is how one is made: the
 reference compiles GenBank + TOML with the ``gb-io`` Rust wheel and caches a pickle; here a database is assembled
 from already-parsed parts (``from_parts``) and stored as a versioned ``.npz`` blob (``save``/``load``) that holds only
-arrays and JSON -- no pickled code objects. GenBank compilation is SURVEY.md section 8 row (f2), not built yet.
+arrays and JSON -- no pickled code objects. GenBank + TOML files are compiled by ``kaptive_amd.db.genbank.database_from_genbank``
+(SURVEY.md section 8 row f2), which the command line calls for a ``.gbk`` database argument.
 """
 
 from __future__ import annotations
@@ -178,7 +179,7 @@ class Database:
         if not (file.is_file() and file.stat().st_size > 0):
             raise FileNotFoundError(file)
         if file.suffix == ".gbk":
-            raise DatabaseError("GenBank compilation is not built yet (SURVEY.md section 8 row f2); load a .npz blob")
+            raise DatabaseError("Database.load reads .npz blobs; compile a GenBank file with kaptive_amd.db.genbank.database_from_genbank")
         if file.suffix != ".npz":
             raise DatabaseError(f"File {file} not supported")
         with np.load(file, allow_pickle=False) as z:

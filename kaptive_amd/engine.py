@@ -30,13 +30,15 @@ class Engine:
     single-genome entry points (``align``, ``hits_to_alignments``) are those of a one-database engine."""
 
     def __init__(self, db: "Database | Sequence[Database]", device: int = 0, ctx: "_native.Context | None" = None,
-                 cigar: bool = False, cs: bool = False) -> None:
+                 cigar: bool = False, cs: bool = False, variants: bool = False) -> None:
         """``ctx``: a context of ``device`` the caller created ahead of time (the command line starts the runtime on a thread
         of its own while the database file is still being read); otherwise one is created here.  ``cigar``: alignment passes
         also leave the CIGAR of every hit (``Batch.cigars``; ``align`` then fills ``Alignments.cigars``) -- a second walk of
         every path on the device, off by default because typing never reads them.  ``cs``: they also leave the cs difference
         string of every hit (``Batch.cs``; include/kp_spec.h, CS) and, since those are read off the ops, the CIGARs: ``align``
-        fills ``Alignments.cs`` and ``Alignments.cigars``."""
+        fills ``Alignments.cs`` and ``Alignments.cigars``.  ``variants``: every typing path also fetches the variant records of
+        the kept hits (``Batch.variants``; include/kp_spec.h, VARIANTS): ``BatchTyping.variants()`` / ``.variants_tsv()``.  They are
+        read off the ops, so such passes compute the CIGARs as well."""
         dbs = list(db) if isinstance(db, (list, tuple)) else [db]
         self.dbs = dbs
         self.db = dbs[0]
@@ -44,11 +46,14 @@ class Engine:
         self.device = device
         self.ctx = ctx if ctx is not None else _native.Context(device)
         self.cs = bool(cs)
-        self.cigar = bool(cigar) or self.cs
+        self.variants = bool(variants)
+        self.cigar = bool(cigar) or self.cs or self.variants
         if self.cigar:
             self.ctx.set_option("cigar", 1)
         if self.cs:
             self.ctx.set_option("cs", 1)
+        if self.variants:
+            self.ctx.set_option("variants", 1)
         for d in dbs:  # KP_MAX_GENE_LEN (include/kp_spec.h): query positions are 16-bit fields of the anchor and hit keys
             too_long = np.flatnonzero(np.asarray(d.genes.lengths) > _native.MAX_GENE_LEN)
             if len(too_long):
@@ -144,6 +149,14 @@ class Engine:
             typer.partial_edge_tolerance,
         )
 
+    def _collect(self, typer, batch, ids, scores, best, genomes=None, group: "int | None" = None):
+        """The records of a batch's finished reduction as a ``BatchTyping`` -- with the ``variants`` option, its variant records too."""
+        from kaptive_amd.serotyping import batch as B
+
+        group = self.group if group is None else group
+        sums, kept, pieces = batch.typing(group)
+        return B.BatchTyping(typer, ids, sums, kept, pieces, scores, best, genomes, variants=batch.variants(group) if self.variants else None)
+
     def type_batch(self, typer, batch, ids: Sequence[str], genomes: Sequence[GenomeAssembly] | None = None,
                    aligned: bool = False):
         """Whole typing of a resident batch: alignment and reduction on the device, the numpy float steps, and the
@@ -157,8 +170,7 @@ class Engine:
         scores, counts = batch.score(typer.min_gene_coverage, self.group)
         best, _, _ = B.choose_best_loci(scores, counts, typer._expected_genes_per_locus)
         batch.reduce_async(best, self.typing_params(typer), self.group)
-        sums, kept, pieces = batch.typing(self.group)
-        return B.BatchTyping(typer, ids, sums, kept, pieces, scores, best, genomes)
+        return self._collect(typer, batch, ids, scores, best, genomes)
 
     def type_batches(self, typer, batches: Sequence, ids: Sequence[Sequence[str]], aligned: bool = False) -> list:
         """Any number of resident batches through the same context, software-pipelined as a sliding window.
@@ -181,8 +193,7 @@ class Engine:
 
         def collect(item) -> None:
             i, scores, best = item
-            sums, kept, pieces = batches[i].typing(self.group)
-            out.append(B.BatchTyping(typer, ids[i], sums, kept, pieces, scores, best))
+            out.append(self._collect(typer, batches[i], ids[i], scores, best))
 
         for i in range(n):
             first_live = pending[0] if pending is not None else i
@@ -218,8 +229,7 @@ class Engine:
 
         def collect(item):
             batch, ids, genomes, scores, best = item
-            sums, kept, pieces = batch.typing(self.group)
-            return B.BatchTyping(typer, ids, sums, kept, pieces, scores, best, genomes), batch
+            return self._collect(typer, batch, ids, scores, best, genomes), batch
 
         # A source may say whether its next item can be had without waiting (``ready()``: the CLI's reader pipeline): the
         # window is then only topped up with what is there, and the driver waits for the source only when it has nothing
@@ -288,8 +298,7 @@ class Engine:
             batch, ids, genomes, staged = item
             out = []
             for g, (typer, (scores, best)) in enumerate(zip(typers, staged)):
-                sums, kept, pieces = batch.typing(g)
-                out.append(B.BatchTyping(typer, ids, sums, kept, pieces, scores, best, genomes))
+                out.append(self._collect(typer, batch, ids, scores, best, genomes, g))
             return tuple(out), batch
 
         can_pull = getattr(source, "ready", None)
@@ -367,12 +376,9 @@ class Engine:
 
     def collect_batches(self, typer, batches: Sequence, ids: Sequence[Sequence[str]], staged: list) -> list:
         """Second half: fetch the reduction records and finish them column-wise (``BatchTyping``)."""
-        from kaptive_amd.serotyping import batch as B
-
         out = []
         for b, i, (scores, best) in zip(batches, ids, staged):
-            sums, kept, pieces = b.typing(self.group)
-            out.append(B.BatchTyping(typer, i, sums, kept, pieces, scores, best))
+            out.append(self._collect(typer, b, i, scores, best))
         return out
 
     def type_many(self, typer, genomes: Sequence[GenomeAssembly]) -> list:

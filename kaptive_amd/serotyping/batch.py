@@ -102,8 +102,10 @@ class BatchTyping:
     phenotype, n_pieces, n_hits (hits kept in the result).
     """
 
-    def __init__(self, typer, ids, sums, kept, pieces, scores, best, genomes=None) -> None:
+    def __init__(self, typer, ids, sums, kept, pieces, scores, best, genomes=None, variants=None) -> None:
+        """``variants``: ``(records, var_off)`` of ``Batch.variants`` where the engine was made with ``variants=True``."""
         self.typer, self.ids, self.genomes = typer, list(ids), genomes
+        self._variants = variants
         self.sums, self.kept, self.pieces = sums, kept, pieces
         db = typer._db
         n = len(sums)
@@ -216,6 +218,26 @@ class BatchTyping:
         return fmt.format(self.ids, self.phenotype, self.sums, self.kept, self.best_locus, self.typeable, self.problems,
                           self.percent_identity, self.percent_coverage, self.length_discrepancy)  # fmt: skip
 
+
+    def variants(self):
+        """``(records, var_off)``: the variant records (``_native.VARIANT_DTYPE``; include/kp_spec.h, VARIANTS) of the batch's kept
+        hits -- ``records[var_off[i]:var_off[i + 1]]`` are assembly i's, ``records["kept"]`` indexes ``self.kept[i]``.  Only where
+        the engine was made with ``variants=True``."""
+        if self._variants is None:
+            raise ValueError("this batch was typed without variant records: Engine(db, variants=True) / Serotyper(db, variants=True)")
+        return self._variants
+
+    def variants_tsv(self) -> bytes:
+        """The lines of the variant table (``--variants``; no header: ``_native.VARIANTS_HEADER``), formatted by the native library
+        from the records (kp_format_variants).  Contig names come from the genomes: ``genomes`` must have been given."""
+        from kaptive_amd import _native
+
+        records, var_off = self.variants()
+        if self.genomes is None:
+            raise ValueError("the variant table names contigs: the batch needs its genomes")
+        first = np.concatenate([[0], np.cumsum([len(g.contigs.ids) for g in self.genomes])]).astype(np.int64)
+        names = [n for g in self.genomes for n in g.contigs.ids]
+        return _native.format_variants(self.typer._db.genes.ids, self.ids, names, first, self.kept, records, var_off)
 
     def jsonl(self) -> bytes:
         """The JSON lines of the whole batch (``-j``), from the batch's columns and the genomes' text (``genomes`` must have
