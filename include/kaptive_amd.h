@@ -337,6 +337,19 @@ KP_API int kp_batch_proteins(kp_ctx *ctx, kp_batch *batch, int32_t asm_index, ui
  * reduction is rerun, and the retries kp_batch_stats counts stay as they were.  A second overflow is KP_EOVERFLOW. */
 KP_API int kp_batch_variant_offsets(kp_ctx *ctx, kp_batch *batch, int64_t *var_off);
 KP_API int kp_batch_variants(kp_ctx *ctx, kp_batch *batch, kp_variant *out, int64_t cap);
+/* Breakpoint records of the kept lists (kp_spec.h, BREAKPOINTS): which two records of a kept list are fragments of one gene -- cut by
+ * an insertion longer than the aligner joins across, a deletion, an inversion or a contig end --, the gaps between them on the gene
+ * and on the contig, the distances of the junction to the contig ends and the inverted repeat at the ends of an inserted stretch.
+ * The reference has no such output.  For the group kp_batch_use_group chose, after kp_batch_reduce; they need no option and no ops,
+ * so a hit table that kp_batch_set_hits put in place serves as well.  Without a reduction of the group's current hit table both calls
+ * return KP_EINVAL and kp_last_error names the cause; the context types its next batch as usual.  The records are made on the first
+ * of these calls after a reduction (three kernels on the reduction's stream; nothing is allocated or launched if nobody asks) and
+ * kept until the next kp_batch_reduce of the group, the batch's next kp_batch_align or kp_batch_set_hits.  A record per kept record
+ * is an upper bound, so there is no buffer option and nothing is retried.
+ *   kp_batch_breakpoint_offsets : bp_off[n_asm + 1]: the records of assembly a are breakpoints[bp_off[a] .. bp_off[a + 1])
+ *   kp_batch_breakpoints        : the records, ascending in kept_b within an assembly; KP_EINVAL when cap < bp_off[n_asm] */
+KP_API int kp_batch_breakpoint_offsets(kp_ctx *ctx, kp_batch *batch, int64_t *bp_off);
+KP_API int kp_batch_breakpoints(kp_ctx *ctx, kp_batch *batch, kp_breakpoint *out, int64_t cap);
 
 /* ---- report rows (host only) -----------------------------------------------------------------------------------------------
  * Replaces KaptiveRow.from_result + bytes(row) per genome (src/kaptive/serotyping/io.py:191-296, 37-43): the TSV lines
@@ -419,6 +432,17 @@ typedef struct kp_variant_tables {
 } kp_variant_tables;
 KP_API int64_t kp_format_variants(const kp_variant_tables *tables, int32_t n_asm, const kp_kept *kept, int32_t kept_stride,
                                   const kp_variant *variants, const int64_t *var_off, char *out, int64_t cap);
+
+/* ---- breakpoint table of a batch (host only) -----------------------------------------------------------------------------------
+ * One tab-separated line per breakpoint record, in the records' order: Assembly, Gene, Event, Gene position (q_end of fragment a:
+ * its last gene base, 1-based), Gene gap (q_gap), Contig A, Position A (1-based), Strand A, Contig B, Position B, Strand B, Length
+ * (t_gap; "." unless COLLINEAR), Duplication (max(0, -q_gap)), Edge A, Edge B and Inverted repeat (matches/cols; "." when ir_cols is
+ * 0).  Event: for COLLINEAR insertion (q_gap <= 0 < t_gap), deletion (t_gap <= 0 < q_gap), replacement (both > 0) or overlap (both
+ * <= 0); inversion for INVERTED; rearrangement for DISORDERED; for CONTIGS contig_break when both edges are <= edge_tolerance, else
+ * translocation.  No header line.  Tables, kept / kept_stride and the return value as kp_format_variants has them (KP_EINVAL also
+ * for a record that names a kept record, gene or contig the tables do not have, or whose kind is unknown). */
+KP_API int64_t kp_format_breakpoints(const kp_variant_tables *tables, int32_t n_asm, const kp_kept *kept, int32_t kept_stride,
+                                     const kp_breakpoint *breakpoints, const int64_t *bp_off, int32_t edge_tolerance, char *out, int64_t cap);
 
 /* ---- JSON lines of a whole batch (host only) ----------------------------------------------------------------------------------
  * Replaces orjson.dumps(SerotypingResult.to_dict(), OPT_SERIALIZE_NUMPY | OPT_APPEND_NEWLINE) per genome

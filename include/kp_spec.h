@@ -470,4 +470,44 @@ typedef struct kp_variant {
     uint8_t pad_[3];        /* zero */
 } kp_variant;
 
+/* ---- BREAKPOINTS (optional, like the variant records: no hit, no kept record and no report byte depends on them) ------------------
+ * kp-align joins pieces across diagonal jumps of at most KP_JOIN_BW only, so a gene cut by a larger event -- an insertion
+ * sequence, a long deletion, an inversion, a contig end -- is reported as two clean hits, both of which survive the overlap cull
+ * (it is by target) and sit in the kept list as two records of one gene.  A breakpoint record links two such records.
+ *
+ * ELIGIBLE RECORDS.  The records of an assembly's kept list (kp_kept) without KP_F_SPURIOUS.
+ * FRAGMENT PAIR (a, b).  a != b, same gene, q_start_a < q_start_b and q_end_a < q_end_b (a precedes b along the gene; two full
+ * copies are no pair) and q_end_a - q_start_b <= KP_BP_MAX_OVERLAP.
+ * DERIVED VALUES.  q_gap = q_start_b - q_end_a (negative: the fragments overlap on the gene -- a target-site duplication).  pos_a
+ * is a's junction-side base, 0-based on its contig: t_end_a - 1 for strand +1, t_start_a for strand -1; pos_b is b's: t_start_b for
+ * strand +1, t_end_b - 1 for strand -1.  edge_a is the number of bases from pos_a to the contig end it faces: ctg_len - t_end_a for
+ * strand +1, t_start_a for strand -1; edge_b likewise: t_start_b for strand +1, ctg_len - t_end_b for strand -1.
+ * KIND.  COLLINEAR: same contig, same strand and t_gap >= -KP_BP_MAX_OVERLAP, where t_gap = t_start_b - t_end_a for strand +1 and
+ * t_start_a - t_end_b for strand -1.  INVERTED: same contig, strands differ.  DISORDERED: same contig, same strand, not collinear.
+ * CONTIGS: different contigs.
+ * ONE RECORD PER b.  Every eligible b has at most one record; its a is the candidate with the smallest key (rank, dist, kept index
+ * of a): rank 0 for COLLINEAR with dist = t_gap + KP_BP_MAX_OVERLAP, rank 1 for INVERTED and DISORDERED with dist =
+ * |pos_a - pos_b|, rank 2 for CONTIGS with dist = edge_a + edge_b (64 bits).  A b without a candidate has no record; one a may
+ * serve several b.
+ * INVERTED REPEAT.  For COLLINEAR records with t_gap >= 2 only (else both fields are 0): S is the t_gap contig bases between the
+ * fragments on the contig's forward strand, ir_cols = min(KP_BP_IR_COLS, t_gap / 2), ir_matches the number of i < ir_cols for which
+ * S[i] and S[t_gap - 1 - i] are both unambiguous (a base inside an N run is ambiguous) and complementary.  Chance gives about a
+ * quarter of the columns, the terminal repeats of an insertion sequence most of them.
+ * ORDER.  Records ascend in kept_b within an assembly; assemblies come in batch order; bp_off[n_asm + 1] delimits them.
+ * PURE FUNCTION of the kept list, the contig lengths and the contig bases: no CIGAR, no option and no trace is read. */
+#define KP_BP_MAX_OVERLAP 64
+#define KP_BP_IR_COLS 32
+#define KP_BP_COLLINEAR 0
+#define KP_BP_INVERTED 1
+#define KP_BP_DISORDERED 2
+#define KP_BP_CONTIGS 3
+typedef struct kp_breakpoint {
+    int32_t kept_a, kept_b; /* indices in the assembly's kept list, as kp_batch_typing returns it */
+    int32_t q_gap;
+    int32_t t_gap;          /* COLLINEAR only, else 0 */
+    int32_t t_lo;           /* COLLINEAR with t_gap > 0: lowest contig coordinate of S, else 0 */
+    int32_t edge_a, edge_b; /* always filled */
+    uint8_t kind, ir_cols, ir_matches, pad_; /* pad_ zero */
+} kp_breakpoint;
+
 #endif /* KP_SPEC_H */

@@ -35,6 +35,13 @@ VARIANT_DTYPE = np.dtype(
 VARIANTS_HEADER = (b"Assembly\tContig\tPosition\tStrand\tGene\tGene position\tType\tLength\tRef\tAlt\tCodon\tRef aa\tAlt aa\t"
                    b"Effect\n")  # the columns of kp_format_variants
 
+BREAKPOINT_DTYPE = np.dtype(
+    [("kept_a", "<i4"), ("kept_b", "<i4"), ("q_gap", "<i4"), ("t_gap", "<i4"), ("t_lo", "<i4"), ("edge_a", "<i4"), ("edge_b", "<i4"),
+     ("kind", "u1"), ("ir_cols", "u1"), ("ir_matches", "u1"), ("pad", "u1")]
+)  # fmt: skip (kp_breakpoint of include/kp_spec.h, BREAKPOINTS: 32 bytes; kind 0 = collinear, 1 = inverted, 2 = disordered, 3 = contigs)
+BREAKPOINTS_HEADER = (b"Assembly\tGene\tEvent\tGene position\tGene gap\tContig A\tPosition A\tStrand A\tContig B\tPosition B\tStrand B\t"
+                      b"Length\tDuplication\tEdge A\tEdge B\tInverted repeat\n")  # the columns of kp_format_breakpoints
+
 JOIN_MAX_PIECES = 8  # KP_JOIN_MAX_PIECES
 JOIN_DTYPE = np.dtype(
     [("gs", "<i4"), ("contig", "<i4"), ("n_pieces", "<i4"), ("n_anchors", "<i4"), ("chain_score", "<i4"), ("width", "<i4"),
@@ -45,7 +52,7 @@ EXPORTS = (
     "kp_ctx_create", "kp_ctx_destroy", "kp_last_error", "kp_ctx_stream", "kp_ctx_set_option", "kp_host_alloc",
     "kp_host_free", "kp_host_reserve", "kp_host_lock", "kp_host_pinned_bytes", "kp_device_allocations", "kp_db_load", "kp_db_n_postings", "kp_batch_create", "kp_batch_create_async",
     "kp_batch_upload_wait", "kp_batch_depends_on", "kp_batch_create_device", "kp_batch_device_words", "kp_batch_destroy", "kp_batch_align", "kp_batch_wait",
-    "kp_batch_hit_offsets", "kp_batch_hits", "kp_batch_set_hits", "kp_batch_cigar_offsets", "kp_batch_cigars", "kp_batch_cs_offsets", "kp_batch_cs", "kp_batch_variant_offsets", "kp_batch_variants", "kp_format_variants", "kp_format_paf", "kp_format_paf_tags", "kp_batch_stats", "kp_batch_profile", "kp_batch_anchors",
+    "kp_batch_hit_offsets", "kp_batch_hits", "kp_batch_set_hits", "kp_batch_cigar_offsets", "kp_batch_cigars", "kp_batch_cs_offsets", "kp_batch_cs", "kp_batch_variant_offsets", "kp_batch_variants", "kp_format_variants", "kp_batch_breakpoint_offsets", "kp_batch_breakpoints", "kp_format_breakpoints", "kp_format_paf", "kp_format_paf_tags", "kp_batch_stats", "kp_batch_profile", "kp_batch_anchors",
     "kp_batch_tasks", "kp_batch_task_results", "kp_batch_joins", "kp_db_load_typing", "kp_db_load_typing_group", "kp_batch_use_group", "kp_batch_score", "kp_batch_reduce", "kp_batch_typing_caps",
     "kp_device_count", "kp_device_numa_node", "kp_batch_typing", "kp_batch_proteins", "kp_protein_align", "kp_fasta_pack", "kp_fasta_ingest", "kp_fasta_ingest_many", "kp_fasta_ingest_file", "kp_fasta_ingest_shard", "kp_shard_words_into", "kp_shard_free", "kp_fasta_simd", "kp_pack_contigs",
     "kp_fasta_free", "kp_format_rows", "kp_format_json", "kp_format_fasta", "kp_protein_align_seeded", "kp_randstrobes", "kp_randstrobe_top_hits",
@@ -500,6 +507,39 @@ def format_variants(gene_names, asm_names, contig_names, asm_first_ctg, kept, va
             return out[:need].tobytes()
         out = np.empty(int(need), np.uint8)
     raise NativeError("kp_format_variants: size kept changing")
+
+
+def format_breakpoints(gene_names, asm_names, contig_names, asm_first_ctg, kept, breakpoints, bp_off, edge_tolerance: int) -> bytes:
+    """The lines of the breakpoint table (kp_format_breakpoints; host only; no header: ``BREAKPOINTS_HEADER``): one per record of
+    ``breakpoints`` (BREAKPOINT_DTYPE), assembly a's being ``bp_off[a]:bp_off[a + 1]``.  The name tables and ``kept`` are those of
+    ``format_variants``; ``edge_tolerance`` (the typer's ``partial_edge_tolerance``) decides between contig_break and translocation."""
+    gn_b, gn_o = _blob(gene_names)
+    an_b, an_o = _blob64(asm_names)
+    cn_b, cn_o = _blob64(contig_names)
+    first, bp_off = _c(asm_first_ctg, np.int64), _c(bp_off, np.int64)
+    kept = np.ascontiguousarray(kept)
+    breakpoints = np.ascontiguousarray(breakpoints, dtype=BREAKPOINT_DTYPE)
+    n_asm = len(bp_off) - 1
+    if kept.itemsize != 84 or (n_asm and (kept.ndim != 2 or kept.shape[0] != n_asm)):
+        raise ValueError("kept must be the [n_asm, stride] table of Batch.typing")
+    if len(first) != n_asm + 1 or len(an_o) != n_asm + 1 or (n_asm and int(first[-1]) > len(cn_o) - 1):
+        raise ValueError("name tables do not describe the batch")
+    if n_asm and (int(bp_off[0]) < 0 or int(bp_off[-1]) > len(breakpoints)):
+        raise ValueError("offsets run past the records")
+    t = VariantTables(gene_names=_p(gn_b).value, gene_name_off=_p(gn_o).value, n_genes=len(gn_o) - 1, asm_names=_p(an_b).value,
+                      asm_name_off=_p(an_o).value, ctg_names=_p(cn_b).value, ctg_name_off=_p(cn_o).value, asm_first_ctg=_p(first).value)  # fmt: skip
+    h = lib()
+    h.kp_format_breakpoints.restype = C.c_int64
+    out = np.empty(max(4096, 256 * len(breakpoints)), np.uint8)
+    for _ in range(2):
+        need = h.kp_format_breakpoints(C.byref(t), C.c_int32(n_asm), _p(kept), C.c_int32(kept.shape[1] if kept.ndim == 2 else 0), _p(breakpoints),
+                                       _p(bp_off), C.c_int32(int(edge_tolerance)), _p(out), C.c_int64(len(out)))
+        if need < 0:
+            raise ValueError(f"kp_format_breakpoints failed ({need})")
+        if need <= len(out):
+            return out[:need].tobytes()
+        out = np.empty(int(need), np.uint8)
+    raise NativeError("kp_format_breakpoints: size kept changing")
 
 
 class JsonTables(C.Structure):  # kp_json_tables
@@ -1005,6 +1045,17 @@ class Batch:
         self.ctx._check(lib().kp_batch_variant_offsets(self.ctx._h, self._h, _p(off)), "kp_batch_variant_offsets")
         out = np.zeros(int(off[-1]), VARIANT_DTYPE)
         self.ctx._check(lib().kp_batch_variants(self.ctx._h, self._h, _p(out), C.c_int64(len(out))), "kp_batch_variants")
+        return out, off
+
+    def breakpoints(self, group: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """(records BREAKPOINT_DTYPE, bp_off int64 [n_asm + 1]): the breakpoint records of the kept lists of ``typing(group)``,
+        assembly a's being ``records[bp_off[a]:bp_off[a + 1]]`` (kp_batch_breakpoints; include/kp_spec.h, BREAKPOINTS).  After
+        ``reduce_async``; no option is needed, and a hit table that ``set_hits`` put in place serves as well."""
+        self.use_group(group)
+        off = np.zeros(self.n_asm + 1, np.int64)
+        self.ctx._check(lib().kp_batch_breakpoint_offsets(self.ctx._h, self._h, _p(off)), "kp_batch_breakpoint_offsets")
+        out = np.zeros(int(off[-1]), BREAKPOINT_DTYPE)
+        self.ctx._check(lib().kp_batch_breakpoints(self.ctx._h, self._h, _p(out), C.c_int64(len(out))), "kp_batch_breakpoints")
         return out, off
 
     def proteins(self, asm_index: int, nbytes: int, group: int = 0) -> np.ndarray:

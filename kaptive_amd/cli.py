@@ -116,6 +116,9 @@ def _add_outputs(p: argparse.ArgumentParser, tsv_flags, include_json: bool) -> N
         g.add_argument("--variants", metavar="FILE", default=argparse.SUPPRESS,
                        help="Write the variants of the reported gene hits -- substitutions with their codon consequence, insertions and "
                             "deletions, in gene coordinates -- as a TSV table to a file")
+        g.add_argument("--breakpoints", metavar="FILE", default=argparse.SUPPRESS,
+                       help="Write the genes that are split across two reported hits -- by an insertion sequence, a long deletion, an "
+                            "inversion or a contig end -- with what lies between the fragments, as a TSV table to a file")
     g.add_argument("--pha4ge", metavar="FILE", nargs="?", const="kaptive_results.pha4ge", type=Path,
                    help="Write PHA4GE-compliant serotyping report to a TSV file (default: %(const)s)")
 
@@ -201,7 +204,8 @@ class _TypingPipeline:
         self.want_paf = bool(getattr(args, "paf", None))  # every hit with its CIGAR: the alignment passes of this run leave them
         self.paf_cs, self.paf_eqx = bool(getattr(args, "cs", False)), bool(getattr(args, "eqx", False))  # ... and its cs string
         self.want_variants = bool(getattr(args, "variants", None))  # the variant table of the kept hits: the reductions of this run leave the records
-        self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins", "paf", "variants"))  # the files' text (and contig names) are kept
+        self.want_breakpoints = bool(getattr(args, "breakpoints", None))  # the breakpoint table of the kept lists, likewise
+        self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins", "paf", "variants", "breakpoints"))  # the files' text (and contig names) are kept
         self.fasta_outputs = any(getattr(args, f, None) for f in ("loci", "genes", "proteins"))  # ... and result objects are built
         self.threads = max(1, args.threads or usable_cpus())  # (the cgroup's quota, not the 256 CPUs a container may see)
         # PREFETCH + 1 chunks are being parsed at any time, each by one native call: the thread budget is shared out among them
@@ -261,11 +265,11 @@ class _TypingPipeline:
                 if more:  # one pass for all of them; duplicate keywords and too many genes are refused here, before any typing
                     typer = MultiSerotyper([self.db, *more], max_other_genes=args.max_other_genes, min_completeness=args.min_completeness,
                                            allow_below_threshold=args.below_threshold, partial_edge_tolerance=args.partial_edge_tolerance,
-                                           device=device, variants=self.want_variants)  # fmt: skip
+                                           device=device, variants=self.want_variants, breakpoints=self.want_breakpoints)  # fmt: skip
                 else:
                     typer = Serotyper(self.db, max_other_genes=args.max_other_genes, min_completeness=args.min_completeness,
                                       allow_below_threshold=args.below_threshold, partial_edge_tolerance=args.partial_edge_tolerance,
-                                      device=device, variants=self.want_variants)  # fmt: skip
+                                      device=device, variants=self.want_variants, breakpoints=self.want_breakpoints)  # fmt: skip
                 typer._ctx_early = early_ctx
             self.typer = typer
             self.engine = self.typer.engine  # the context is created here, on the thread that will drive it
@@ -453,6 +457,8 @@ class _TypingPipeline:
                 out["paf"] = hits_to_paf(self.engine.view(group), bt.genomes, *aligned, cs_tag=self.paf_cs, eqx=self.paf_eqx)
             if self.want_variants:
                 out["variants"] = bt.variants_tsv()
+            if self.want_breakpoints:
+                out["breakpoints"] = bt.breakpoints_tsv()
             if self.want_tsv:
                 out["tsv"] = bt.tsv()
             if getattr(args, "pha4ge", None):
@@ -690,7 +696,7 @@ class _PerDatabaseOutputs:
     genome by genome (``interleave_lines``).  The files are opened with the first chunk's outputs, which carry the
     databases' keywords."""
 
-    KINDS = (("tsv", "out"), ("pha4ge", "pha4ge"), ("json", "json"), ("paf", "paf"), ("variants", "variants"))
+    KINDS = (("tsv", "out"), ("pha4ge", "pha4ge"), ("json", "json"), ("paf", "paf"), ("variants", "variants"), ("breakpoints", "breakpoints"))
 
     def __init__(self, args: argparse.Namespace) -> None:
         self.wanted = [(key, path) for key, attr in self.KINDS if (path := getattr(args, attr, None))]
@@ -700,9 +706,10 @@ class _PerDatabaseOutputs:
     def _open(self, keywords) -> None:
         from kaptive_amd.serotyping.io import KaptiveRow, Pha4geRow
 
-        from kaptive_amd._native import VARIANTS_HEADER
+        from kaptive_amd._native import BREAKPOINTS_HEADER, VARIANTS_HEADER
 
-        headers = {"tsv": KaptiveRow.header(), "pha4ge": Pha4geRow.header(), "json": b"", "paf": b"", "variants": VARIANTS_HEADER}
+        headers = {"tsv": KaptiveRow.header(), "pha4ge": Pha4geRow.header(), "json": b"", "paf": b"", "variants": VARIANTS_HEADER,
+                   "breakpoints": BREAKPOINTS_HEADER}
         self.streams = {}
         for key, path in self.wanted:
             if _is_stdout(path):
@@ -768,6 +775,8 @@ def run_type(args: argparse.Namespace) -> int:
 
     if getattr(args, "db", None) and (v := getattr(args, "variants", None)) and _is_stdout(v):
         raise ValueError("--variants with --db writes a table per database: it needs a file name, not stdout")
+    if getattr(args, "db", None) and (v := getattr(args, "breakpoints", None)) and _is_stdout(v):
+        raise ValueError("--breakpoints with --db writes a table per database: it needs a file name, not stdout")
     handles = {}
     per_db = _PerDatabaseOutputs(args) if getattr(args, "db", None) else None  # several databases: reports per database
 
@@ -790,6 +799,11 @@ def run_type(args: argparse.Namespace) -> int:
 
             handles["variants"] = stream(f)
             handles["variants"].write(VARIANTS_HEADER)
+        if f := getattr(args, "breakpoints", None):
+            from kaptive_amd._native import BREAKPOINTS_HEADER
+
+            handles["breakpoints"] = stream(f)
+            handles["breakpoints"].write(BREAKPOINTS_HEADER)
     done = 0
     timing_path = os.environ.get("KAPTIVE_AMD_CLI_TIMING")  # bench.py: when each chunk's rows were written
     t_start, chunk_times, phases = time.perf_counter(), [], {}

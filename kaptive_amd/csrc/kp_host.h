@@ -67,6 +67,14 @@ struct KpTypingRun {
         return {.kept = d_kept.p, .kept_cap = kept_cap, .kept_off = d_kept_off.p, .total = h_kept_off.empty() ? 0 : h_kept_off.back(), .gene_lo = gene_lo};
     }
     KpPerHit<kp_variant> variants() const { return {.cnt = d_var_cnt.p, .off = d_var_off.p, .data = d_var.p, .cap = (int64_t)var_cap}; }
+    // breakpoint records of the kept list (kp_breakpoints.hip): made on first request after a reduction, theirs until the next
+    // reduction or until the hit table goes; nothing below is allocated before somebody asks.
+    bool bp_valid = false;
+    std::vector<int64_t> h_bp_kept_off;  // [n_asm + 1] kept records before every assembly
+    std::vector<int64_t> h_bp_off;       // [n_asm + 1] breakpoint records before every assembly
+    DevBuf<int64_t> d_bp_kept_off, d_bp_off;
+    DevBuf<uint32_t> d_bp_cnt;           // [n_asm]
+    DevBuf<kp_breakpoint> d_bp_tmp, d_bp;  // one record per kept row each: per assembly from its first row, then back to back
     // d_pairs: the pairs of the protein DP, one slot per kept row: q_off, q_len, t_off, t_len [slots each], then pair_base [n_asm], n_pairs [1]
     size_t slots() const { return n_asm * (size_t)kept_cap; }
     size_t pairs_len() const { return 4 * slots() + n_asm + 1; }
@@ -220,7 +228,7 @@ struct KpWork : KpPassCaps {
     KpHitRows hit_rows() const { return {.hit_off = d_cig_hit_off.p, .total = hit_off[n_asm]}; }
     KpPerHit<uint32_t> cigars() const { return {.cnt = d_cig_cnt.p, .off = d_cig_off.p, .data = d_cig_ops.p, .cap = (int64_t)cigar_cap}; }
     KpPerHit<char> cs() const { return {.cnt = d_cs_cnt.p, .off = d_cs_off.p, .data = d_cs_bytes.p, .cap = (int64_t)cs_cap}; }
-    void reset_runs() { for (auto &r : runs) if (r) r->split = r->scored = r->reduced = r->sums_valid = r->var_valid = false; }  // their hit table is about to be rewritten
+    void reset_runs() { for (auto &r : runs) if (r) r->split = r->scored = r->reduced = r->sums_valid = r->var_valid = r->bp_valid = false; }  // their hit table is about to be rewritten
 };
 
 #define KP_INPUT_POOL 16  /* recycled device copies of batch inputs: uploads run several shards ahead of the passes that read them */

@@ -340,6 +340,12 @@ void kp_launch_cs_walk(const KpBatchView &b, const KpGenes &genes, const KpHitTa
 // counted (var.cnt) and scanned (var.off), or with `emit` stored from var.off[row] -- stores beyond var.cap are dropped.
 void kp_launch_variants_walk(const KpBatchView &b, const KpGenes &genes, const KpHitTable &hits, const KpHitRows &rows, const KpPerHit<uint32_t> &cig,
                              const KpKeptRows &kept, int64_t *src, const KpPerHit<kp_variant> &var, bool emit, hipStream_t stream);
+// kp_breakpoints.hip (after a reduction, when its breakpoint records are first asked for): the records (kp_spec.h, BREAKPOINTS) of
+// every assembly's kept list -- a wave per assembly leaves them in kept_b order from tmp[kept.kept_off[a]] on and their number in cnt[a];
+// bp_off[n_asm + 1] is the scan of the numbers and out holds the records back to back.  tmp and out: kept.total records each;
+// max_kept: the longest list (sizes the LDS tile).
+void kp_launch_breakpoints(const KpBatchView &b, const KpKeptRows &kept, int max_kept, kp_breakpoint *tmp, uint32_t *cnt, int64_t *bp_off,
+                           kp_breakpoint *out, hipStream_t stream);
 // kp_reduce.hip: assembly a's hits with gene in [gene_lo, gene_hi) (one run: hits are sorted by gene) -> out rows, gene
 // indices relative to gene_lo; out.count[a] = how many
 void kp_launch_hit_split(const KpHitTable &hits, int32_t gene_lo, int32_t gene_hi, const KpHitTable &out, int32_t n_asm, hipStream_t stream);

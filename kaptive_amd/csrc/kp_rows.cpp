@@ -311,3 +311,48 @@ extern "C" int64_t kp_format_variants(const kp_variant_tables *t, int32_t n_asm,
     }
     return o.n;
 }
+
+// ---- breakpoint table (kp_spec.h, BREAKPOINTS) -------------------------------------------------------------------------------------
+// One line per record; the event's name is derived here, from the record's kind, its two gaps and its two edges.
+extern "C" int64_t kp_format_breakpoints(const kp_variant_tables *t, int32_t n_asm, const kp_kept *kept, int32_t kept_stride, const kp_breakpoint *bps,
+                                         const int64_t *bp_off, int32_t edge_tolerance, char *out, int64_t cap) {
+    if (!t || n_asm < 0 || cap < 0 || (cap > 0 && !out) || (n_asm > 0 && (!bp_off || !t->asm_name_off || !t->asm_first_ctg))) return KP_EINVAL;
+    if (n_asm > 0 && (bp_off[n_asm] < bp_off[0] || (bp_off[n_asm] > bp_off[0] && (!bps || !kept)))) return KP_EINVAL;
+    Out o{out, cap};
+    for (int a = 0; a < n_asm; ++a) {
+        const int64_t c0 = t->asm_first_ctg[a], nc = t->asm_first_ctg[a + 1] - c0;
+        if (bp_off[a + 1] < bp_off[a]) return KP_EINVAL;
+        for (int64_t i = bp_off[a]; i < bp_off[a + 1]; ++i) {
+            const kp_breakpoint &r = bps[i];
+            if (r.kept_a < 0 || r.kept_a >= kept_stride || r.kept_b < 0 || r.kept_b >= kept_stride || r.kind > KP_BP_CONTIGS) return KP_EINVAL;
+            const kp_kept &ka = kept[(size_t)a * (size_t)kept_stride + (size_t)r.kept_a], &kb = kept[(size_t)a * (size_t)kept_stride + (size_t)r.kept_b];
+            if (ka.gene < 0 || ka.gene >= t->n_genes || ka.contig < 0 || ka.contig >= nc || kb.contig < 0 || kb.contig >= nc) return KP_EINVAL;
+            const char *event;
+            if (r.kind == KP_BP_COLLINEAR) event = r.t_gap > 0 ? (r.q_gap > 0 ? "replacement" : "insertion") : (r.q_gap > 0 ? "deletion" : "overlap");
+            else if (r.kind == KP_BP_INVERTED) event = "inversion";
+            else if (r.kind == KP_BP_DISORDERED) event = "rearrangement";
+            else event = (r.edge_a <= edge_tolerance && r.edge_b <= edge_tolerance) ? "contig_break" : "translocation";
+            const bool fa = ka.strand >= 0, fb = kb.strand >= 0;
+            const int64_t ca = c0 + ka.contig, cb = c0 + kb.contig;
+            o.put(t->asm_names + t->asm_name_off[a], t->asm_name_off[a + 1] - t->asm_name_off[a]); o.put('\t');
+            o.put(t->gene_names + t->gene_name_off[ka.gene], t->gene_name_off[ka.gene + 1] - t->gene_name_off[ka.gene]); o.put('\t');
+            o.lit(event); o.put('\t');
+            put_i(o, ka.q_end); o.put('\t');
+            put_i(o, r.q_gap); o.put('\t');
+            o.put(t->ctg_names + t->ctg_name_off[ca], t->ctg_name_off[ca + 1] - t->ctg_name_off[ca]); o.put('\t');
+            put_i(o, fa ? (long long)ka.t_end : (long long)ka.t_start + 1); o.put('\t');  // pos_a + 1
+            o.put(fa ? '+' : '-'); o.put('\t');
+            o.put(t->ctg_names + t->ctg_name_off[cb], t->ctg_name_off[cb + 1] - t->ctg_name_off[cb]); o.put('\t');
+            put_i(o, fb ? (long long)kb.t_start + 1 : (long long)kb.t_end); o.put('\t');  // pos_b + 1
+            o.put(fb ? '+' : '-'); o.put('\t');
+            if (r.kind == KP_BP_COLLINEAR) put_i(o, r.t_gap); else o.put('.');
+            o.put('\t');
+            put_i(o, r.q_gap < 0 ? -(long long)r.q_gap : 0); o.put('\t');
+            put_i(o, r.edge_a); o.put('\t');
+            put_i(o, r.edge_b); o.put('\t');
+            if (r.ir_cols) { put_i(o, r.ir_matches); o.put('/'); put_i(o, r.ir_cols); } else o.put('.');
+            o.put('\n');
+        }
+    }
+    return o.n;
+}

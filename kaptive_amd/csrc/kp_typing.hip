@@ -1,5 +1,5 @@
-// kp_typing.hip -- batched typing (locus scores, the reduction of a batch's hits, gene states, the variant records of the kept hits; per
-// typing group), stand-alone protein aligner.
+// kp_typing.hip -- batched typing (locus scores, the reduction of a batch's hits, gene states, the variant and breakpoint records of the kept hits;
+// per typing group), stand-alone protein aligner.
 #include "kp_host.h"
 
 // the typing group a batch currently addresses and the run of the batch's work set for it (created on first use)
@@ -150,6 +150,7 @@ int kp_batch_reduce(kp_ctx *ctx, kp_batch *b, const int32_t *best_locus, const k
     R.reduced = true;
     R.sums_valid = false;
     R.var_valid = false;  // (the variant records describe a kept list: the one that is about to be replaced)
+    R.bp_valid = false;   // (the breakpoint records likewise)
     return KP_OK;
 }
 
@@ -298,6 +299,61 @@ int kp_batch_variants(kp_ctx *ctx, kp_batch *b, kp_variant *out, int64_t cap) {
     if (cap < R->var_total) return kp_fail(ctx, KP_EINVAL, "variant buffer too small");
     if (R->var_total > 0)
         if (int frc = fetch_all(ctx, R->stream, {{out, R->d_var.p, (size_t)R->var_total * sizeof(kp_variant)}})) return frc;
+    return KP_OK;
+}
+
+// ---- breakpoint records of the kept lists (kp_breakpoints.hip; kp_spec.h, BREAKPOINTS) --------------------------------------------
+static const char *const NO_BREAKPOINTS = "this batch has no breakpoint records: kp_batch_reduce has not run for this group since its hit table was made";
+
+// The records of the batch's current group, made on first request after its reduction (three kernels on the reduction's stream,
+// behind the ones that finalised the kept list) once the summaries show that no reduction buffer overflowed.  They need the kept
+// list and the batch's contigs only: no option, no ops -- a table that kp_batch_set_hits put in place serves as well.  The buffers
+// hold a record per kept record, which is an upper bound: nothing can overflow, nothing is retried.
+static int ensure_breakpoints(kp_ctx *ctx, kp_batch *b, KpTypingRun **R_out) {
+    KpWork *w = work_of(b);
+    if (!w || !w->finalised || !typing_group(ctx, b)) return kp_fail(ctx, KP_EINVAL, NO_BREAKPOINTS);
+    KpTypingRun &R = typing_run(w, b->group);
+    if (!R.reduced) return kp_fail(ctx, KP_EINVAL, NO_BREAKPOINTS);
+    *R_out = &R;
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (int rc = fetch_summaries(ctx, b, w)) return rc;
+    if (R.bp_valid) return KP_OK;
+    const size_t n_asm = (size_t)b->n_asm;
+    R.h_bp_kept_off.assign(n_asm + 1, 0);
+    for (size_t a = 0; a < n_asm; ++a) R.h_bp_kept_off[a + 1] = R.h_bp_kept_off[a] + std::min(std::max(R.h_sums[a].n_kept, 0), R.kept_cap);
+    const int64_t total = R.h_bp_kept_off[n_asm];
+    R.h_bp_off.assign(n_asm + 1, 0);
+    if (total > 0) {
+        KP_HIP_CHECK(ctx, R.d_bp_cnt.reserve(n_asm));
+        KP_HIP_CHECK(ctx, R.d_bp_off.reserve(n_asm + 1));
+        KP_HIP_CHECK(ctx, R.d_bp_tmp.reserve((size_t)total));
+        KP_HIP_CHECK(ctx, R.d_bp.reserve((size_t)total));
+        if (int rc = upload(ctx, R.d_bp_kept_off, R.h_bp_kept_off.data(), n_asm + 1, R.stream)) return rc;
+        const KpKeptRows rows{.kept = R.d_kept.p, .kept_cap = R.kept_cap, .kept_off = R.d_bp_kept_off.p, .total = total, .gene_lo = typing_group(ctx, b)->gene_lo};
+        kp_launch_breakpoints(b->view, rows, R.max_kept, R.d_bp_tmp.p, R.d_bp_cnt.p, R.d_bp_off.p, R.d_bp.p, R.stream);
+        KP_HIP_CHECK(ctx, hipGetLastError());
+        if (int frc = fetch_all(ctx, R.stream, {{R.h_bp_off.data(), R.d_bp_off.p, (n_asm + 1) * sizeof(int64_t)}})) return frc;
+    }
+    R.bp_valid = true;
+    return KP_OK;
+}
+
+int kp_batch_breakpoint_offsets(kp_ctx *ctx, kp_batch *b, int64_t *bp_off) {
+    if (!ctx || !b || b->ctx != ctx || !bp_off) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpTypingRun *R = nullptr;
+    if (int rc = ensure_breakpoints(ctx, b, &R)) return rc;
+    std::copy(R->h_bp_off.begin(), R->h_bp_off.end(), bp_off);
+    return KP_OK;
+}
+
+int kp_batch_breakpoints(kp_ctx *ctx, kp_batch *b, kp_breakpoint *out, int64_t cap) {
+    if (!ctx || !b || b->ctx != ctx || (!out && cap > 0)) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpTypingRun *R = nullptr;
+    if (int rc = ensure_breakpoints(ctx, b, &R)) return rc;
+    const int64_t total = R->h_bp_off.back();
+    if (cap < total) return kp_fail(ctx, KP_EINVAL, "breakpoint buffer too small");
+    if (total > 0)
+        if (int frc = fetch_all(ctx, R->stream, {{out, R->d_bp.p, (size_t)total * sizeof(kp_breakpoint)}})) return frc;
     return KP_OK;
 }
 

@@ -30,7 +30,7 @@ class Engine:
     single-genome entry points (``align``, ``hits_to_alignments``) are those of a one-database engine."""
 
     def __init__(self, db: "Database | Sequence[Database]", device: int = 0, ctx: "_native.Context | None" = None,
-                 cigar: bool = False, cs: bool = False, variants: bool = False) -> None:
+                 cigar: bool = False, cs: bool = False, variants: bool = False, breakpoints: bool = False) -> None:
         """``ctx``: a context of ``device`` the caller created ahead of time (the command line starts the runtime on a thread
         of its own while the database file is still being read); otherwise one is created here.  ``cigar``: alignment passes
         also leave the CIGAR of every hit (``Batch.cigars``; ``align`` then fills ``Alignments.cigars``) -- a second walk of
@@ -38,7 +38,9 @@ class Engine:
         string of every hit (``Batch.cs``; include/kp_spec.h, CS) and, since those are read off the ops, the CIGARs: ``align``
         fills ``Alignments.cs`` and ``Alignments.cigars``.  ``variants``: every typing path also fetches the variant records of
         the kept hits (``Batch.variants``; include/kp_spec.h, VARIANTS): ``BatchTyping.variants()`` / ``.variants_tsv()``.  They are
-        read off the ops, so such passes compute the CIGARs as well."""
+        read off the ops, so such passes compute the CIGARs as well.  ``breakpoints``: every typing path also fetches the breakpoint
+        records of the kept lists (``Batch.breakpoints``; include/kp_spec.h, BREAKPOINTS): ``BatchTyping.breakpoints()`` /
+        ``.breakpoints_tsv()``.  They are read off the kept lists and the contigs; the alignment passes do nothing more for them."""
         dbs = list(db) if isinstance(db, (list, tuple)) else [db]
         self.dbs = dbs
         self.db = dbs[0]
@@ -47,6 +49,7 @@ class Engine:
         self.ctx = ctx if ctx is not None else _native.Context(device)
         self.cs = bool(cs)
         self.variants = bool(variants)
+        self.breakpoints = bool(breakpoints)
         self.cigar = bool(cigar) or self.cs or self.variants
         if self.cigar:
             self.ctx.set_option("cigar", 1)
@@ -150,12 +153,14 @@ class Engine:
         )
 
     def _collect(self, typer, batch, ids, scores, best, genomes=None, group: "int | None" = None):
-        """The records of a batch's finished reduction as a ``BatchTyping`` -- with the ``variants`` option, its variant records too."""
+        """The records of a batch's finished reduction as a ``BatchTyping`` -- with the ``variants`` / ``breakpoints`` option, its
+        variant / breakpoint records too."""
         from kaptive_amd.serotyping import batch as B
 
         group = self.group if group is None else group
         sums, kept, pieces = batch.typing(group)
-        return B.BatchTyping(typer, ids, sums, kept, pieces, scores, best, genomes, variants=batch.variants(group) if self.variants else None)
+        return B.BatchTyping(typer, ids, sums, kept, pieces, scores, best, genomes, variants=batch.variants(group) if self.variants else None,
+                             breakpoints=batch.breakpoints(group) if self.breakpoints else None)
 
     def type_batch(self, typer, batch, ids: Sequence[str], genomes: Sequence[GenomeAssembly] | None = None,
                    aligned: bool = False):

@@ -102,10 +102,12 @@ class BatchTyping:
     phenotype, n_pieces, n_hits (hits kept in the result).
     """
 
-    def __init__(self, typer, ids, sums, kept, pieces, scores, best, genomes=None, variants=None) -> None:
-        """``variants``: ``(records, var_off)`` of ``Batch.variants`` where the engine was made with ``variants=True``."""
+    def __init__(self, typer, ids, sums, kept, pieces, scores, best, genomes=None, variants=None, breakpoints=None) -> None:
+        """``variants``: ``(records, var_off)`` of ``Batch.variants`` where the engine was made with ``variants=True``;
+        ``breakpoints``: ``(records, bp_off)`` of ``Batch.breakpoints`` where it was made with ``breakpoints=True``."""
         self.typer, self.ids, self.genomes = typer, list(ids), genomes
         self._variants = variants
+        self._breakpoints = breakpoints
         self.sums, self.kept, self.pieces = sums, kept, pieces
         db = typer._db
         n = len(sums)
@@ -238,6 +240,28 @@ class BatchTyping:
         first = np.concatenate([[0], np.cumsum([len(g.contigs.ids) for g in self.genomes])]).astype(np.int64)
         names = [n for g in self.genomes for n in g.contigs.ids]
         return _native.format_variants(self.typer._db.genes.ids, self.ids, names, first, self.kept, records, var_off)
+
+    def breakpoints(self):
+        """``(records, bp_off)``: the breakpoint records (``_native.BREAKPOINT_DTYPE``; include/kp_spec.h, BREAKPOINTS) of the batch's
+        kept lists -- ``records[bp_off[i]:bp_off[i + 1]]`` are assembly i's, ``records["kept_a"]`` and ``records["kept_b"]`` index
+        ``self.kept[i]``.  Only where the engine was made with ``breakpoints=True``."""
+        if self._breakpoints is None:
+            raise ValueError("this batch was typed without breakpoint records: Engine(db, breakpoints=True) / Serotyper(db, breakpoints=True)")
+        return self._breakpoints
+
+    def breakpoints_tsv(self) -> bytes:
+        """The lines of the breakpoint table (``--breakpoints``; no header: ``_native.BREAKPOINTS_HEADER``), formatted by the native
+        library from the records (kp_format_breakpoints) with the typer's ``partial_edge_tolerance``.  Contig names come from the
+        genomes: ``genomes`` must have been given."""
+        from kaptive_amd import _native
+
+        records, bp_off = self.breakpoints()
+        if self.genomes is None:
+            raise ValueError("the breakpoint table names contigs: the batch needs its genomes")
+        first = np.concatenate([[0], np.cumsum([len(g.contigs.ids) for g in self.genomes])]).astype(np.int64)
+        names = [n for g in self.genomes for n in g.contigs.ids]
+        return _native.format_breakpoints(self.typer._db.genes.ids, self.ids, names, first, self.kept, records, bp_off,
+                                          self.typer.partial_edge_tolerance)
 
     def jsonl(self) -> bytes:
         """The JSON lines of the whole batch (``-j``), from the batch's columns and the genomes' text (``genomes`` must have
