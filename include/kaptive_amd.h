@@ -350,6 +350,17 @@ KP_API int kp_batch_variants(kp_ctx *ctx, kp_batch *batch, kp_variant *out, int6
  *   kp_batch_breakpoints        : the records, ascending in kept_b within an assembly; KP_EINVAL when cap < bp_off[n_asm] */
 KP_API int kp_batch_breakpoint_offsets(kp_ctx *ctx, kp_batch *batch, int64_t *bp_off);
 KP_API int kp_batch_breakpoints(kp_ctx *ctx, kp_batch *batch, kp_breakpoint *out, int64_t cap);
+/* Allele digests of the kept records and the locus pieces (kp_spec.h, ALLELES): a stable 64-bit digest of every kept record's
+ * strand-corrected bases and of its protein bytes, and of every locus piece's bases -- what tells whether two isolates carry the
+ * same allele of a gene, the same protein or the same locus.  The reference has no such output.  Laid out like kp_batch_typing:
+ * out[a * kept_stride + i] belongs to kept record i of assembly a, piece_out[a * piece_stride + p] to its piece p; rows beyond the
+ * counts are zero; strides smaller than the counts give KP_EINVAL (kp_batch_typing_caps).  Lifetime and refusals are those of
+ * kp_batch_breakpoints: for the group kp_batch_use_group chose, after kp_batch_reduce, no option and no ops needed, a table that
+ * kp_batch_set_hits put in place serves; made on the first call after a reduction (one kernel on the reduction's stream; nothing is
+ * allocated or launched if nobody asks) and kept until the group's next kp_batch_reduce, the batch's next kp_batch_align or
+ * kp_batch_set_hits; without a current reduction KP_EINVAL, and kp_last_error names the cause.  One record per kept row and per
+ * piece row: nothing overflows, nothing is retried.  The locus digest of an assembly is kp_format_alleles' to combine. */
+KP_API int kp_batch_alleles(kp_ctx *ctx, kp_batch *batch, kp_allele *out, int32_t kept_stride, uint64_t *piece_out, int32_t piece_stride);
 
 /* ---- report rows (host only) -----------------------------------------------------------------------------------------------
  * Replaces KaptiveRow.from_result + bytes(row) per genome (src/kaptive/serotyping/io.py:191-296, 37-43): the TSV lines
@@ -443,6 +454,29 @@ KP_API int64_t kp_format_variants(const kp_variant_tables *tables, int32_t n_asm
  * for a record that names a kept record, gene or contig the tables do not have, or whose kind is unknown). */
 KP_API int64_t kp_format_breakpoints(const kp_variant_tables *tables, int32_t n_asm, const kp_kept *kept, int32_t kept_stride,
                                      const kp_breakpoint *breakpoints, const int64_t *bp_off, int32_t edge_tolerance, char *out, int64_t cap);
+
+/* ---- allele table of a batch (host only) ----------------------------------------------------------------------------------------
+ * One tab-separated line per kept record without KP_F_SPURIOUS, in kept-list order, assemblies in batch order: Assembly, Locus (the
+ * best-match locus's name), Locus allele, Gene, Set (expected / other / extra from KP_F_EXPECTED / KP_F_EXTRA, then _in / _out from
+ * KP_F_INSIDE), Contig, Start, End (1-based and closed, contig forward strand), Strand, State (normal / partial / truncated /
+ * below_id_threshold), Length (t_end - t_start), Allele, Protein length, Protein allele.  Digests are 16 lower-case hex digits;
+ * Locus allele is "." for an assembly without a piece, Protein allele "." for a record with prot_len == 0 (kp_spec.h, ALLELES).  No
+ * header line.  Tables are kp_variant_tables plus the locus names; n_kept / n_pieces / best_locus per assembly as the summaries and
+ * the host's choice have them; kept / alleles with kept_stride and piece_digests / piece_order with piece_stride as
+ * kp_batch_typing and kp_batch_alleles filled them, piece_order as kp_format_json takes it (numpy's argsort of mean_pos per
+ * assembly).  Return value as kp_format_variants has it; KP_EINVAL also for a count beyond its stride, a best locus, gene or contig
+ * the tables do not have, an order entry outside the assembly's pieces or an unknown state.
+ * kp_allele_locus_digest: the locus digest of n pieces listed in `order` (0 for n <= 0) -- the one the table prints. */
+typedef struct kp_allele_tables {
+    kp_variant_tables names;
+    const char *locus_names;
+    const int32_t *locus_name_off; /* n_loci + 1 */
+    int32_t n_loci;
+} kp_allele_tables;
+KP_API int64_t kp_format_alleles(const kp_allele_tables *tables, int32_t n_asm, const int32_t *n_kept, const int32_t *n_pieces, const int32_t *best_locus,
+                                 const kp_kept *kept, const kp_allele *alleles, int32_t kept_stride, const uint64_t *piece_digests,
+                                 const int32_t *piece_order, int32_t piece_stride, char *out, int64_t cap);
+KP_API uint64_t kp_allele_locus_digest(const uint64_t *piece_digests, const int32_t *order, int32_t n);
 
 /* ---- JSON lines of a whole batch (host only) ----------------------------------------------------------------------------------
  * Replaces orjson.dumps(SerotypingResult.to_dict(), OPT_SERIALIZE_NUMPY | OPT_APPEND_NEWLINE) per genome

@@ -510,4 +510,36 @@ typedef struct kp_breakpoint {
     uint8_t kind, ir_cols, ir_matches, pad_; /* pad_ zero */
 } kp_breakpoint;
 
+/* ---- ALLELES (optional, like the variant and breakpoint records: no hit, no kept record and no report byte depends on them) -------
+ * A stable 64-bit digest of every kept record's bases, of its protein and of the assembly's locus: two isolates carry the same
+ * allele of a gene exactly when the digests agree (up to the collision odds below), across runs and machines.
+ *
+ * SEQUENCE OF AN INTERVAL.  An interval (contig, start, end, strand) has L = end - start codes x_0 .. x_{L-1}.  For strand >= 0,
+ * x_p = kp_code_at(start + p); for strand < 0, x_p is the complement of kp_code_at(end - 1 - p): 3 - v for v <= 3, 4 stays 4.
+ * Codes are 0..3, or 4 inside an N run.  This is the strand-corrected sequence the extraction of kp_reduce_core.h translates and
+ * the one gene_seqs / locus_seqs hold on the host.
+ * MIXER.  MIX(z): z ^= z >> 30; z *= 0xbf58476d1ce4e5b9; z ^= z >> 27; z *= 0x94d049bb133111eb; z ^= z >> 31 (64-bit wrap-around).
+ * DIGEST of a block list v_0 .. v_{B-1}, a length L and a tag: S = sum over i of MIX(MIX(i + 1) ^ v_i) mod 2^64;
+ * DIGEST = MIX(S ^ MIX((tag << 56) | L)).  S is a plain sum: the blocks are independent, any lane may take any block.
+ * NUCLEOTIDE DIGEST (tag 1).  Block i covers columns 16i .. 16i + 15: w_i = sum of (x < 4 ? x : 0) << 2j, m_i = sum of (x == 4) << j
+ * over its columns j (columns >= L contribute nothing), v_i = w_i | (uint64)m_i << 32.
+ * PROTEIN DIGEST (tag 2).  Over the record's prot_len protein bytes -- the bytes kp_batch_proteins returns for it, so a protein cut
+ * at a stop is digested as cut --, eight bytes per block, little-endian, zero-padded.  A record with prot_len == 0 has protein
+ * digest 0 and prints ".".
+ * LOCUS DIGEST (tag 3).  Its blocks are the nucleotide digests of the assembly's locus pieces in the order the product lists them
+ * (numpy's argsort of mean_pos, as kp_format_json is given it); L is the number of pieces.  An assembly without a piece has locus
+ * digest 0 and prints ".".
+ * PURE FUNCTION of the kept list, the pieces, the protein buffer and the contig bases: no CIGAR, no option and no trace is read.
+ * Every kept record has digests, KP_F_SPURIOUS ones included; the table lists the others, as the report does.
+ * NOT CRYPTOGRAPHIC.  64 bits: among n distinct alleles of a gene two collide with odds of about n^2 / 2^65, and anyone can
+ * construct a collision.  The digests tell alleles apart; they authenticate nothing.
+ * KNOWN ANSWERS.  Bases "" 332e6d2b1a14193e, "a" c8754b03323395a8, "acgt" 5eeccfc7d63eed1e, "acgtnacgt" 90dd01a6934ea7e4; protein
+ * "M" 137859f1719b82ad, "MKLVAAAAW" 973b1ff3dad4bcac; the pieces "acgt", "tgca" eef6d079d9303a4a (more in tests/test_alleles_cpu.py).
+ * OUT OF SCOPE.  Digests of the database's own genes (a "matches the reference allele" column), allele numbering within a run and
+ * any change to the TSV / JSON / PHA4GE bytes. */
+typedef struct kp_allele {
+    uint64_t nt; /* nucleotide digest of (contig, t_start, t_end, strand) */
+    uint64_t aa; /* protein digest; 0 when prot_len == 0 */
+} kp_allele;
+
 #endif /* KP_SPEC_H */

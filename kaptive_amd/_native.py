@@ -42,6 +42,10 @@ BREAKPOINT_DTYPE = np.dtype(
 BREAKPOINTS_HEADER = (b"Assembly\tGene\tEvent\tGene position\tGene gap\tContig A\tPosition A\tStrand A\tContig B\tPosition B\tStrand B\t"
                       b"Length\tDuplication\tEdge A\tEdge B\tInverted repeat\n")  # the columns of kp_format_breakpoints
 
+ALLELE_DTYPE = np.dtype([("nt", "<u8"), ("aa", "<u8")])  # kp_allele of include/kp_spec.h, ALLELES: 16 bytes; aa is 0 where prot_len is 0
+ALLELES_HEADER = (b"Assembly\tLocus\tLocus allele\tGene\tSet\tContig\tStart\tEnd\tStrand\tState\tLength\tAllele\tProtein length\t"
+                  b"Protein allele\n")  # the columns of kp_format_alleles
+
 JOIN_MAX_PIECES = 8  # KP_JOIN_MAX_PIECES
 JOIN_DTYPE = np.dtype(
     [("gs", "<i4"), ("contig", "<i4"), ("n_pieces", "<i4"), ("n_anchors", "<i4"), ("chain_score", "<i4"), ("width", "<i4"),
@@ -52,7 +56,7 @@ EXPORTS = (
     "kp_ctx_create", "kp_ctx_destroy", "kp_last_error", "kp_ctx_stream", "kp_ctx_set_option", "kp_host_alloc",
     "kp_host_free", "kp_host_reserve", "kp_host_lock", "kp_host_pinned_bytes", "kp_device_allocations", "kp_db_load", "kp_db_n_postings", "kp_batch_create", "kp_batch_create_async",
     "kp_batch_upload_wait", "kp_batch_depends_on", "kp_batch_create_device", "kp_batch_device_words", "kp_batch_destroy", "kp_batch_align", "kp_batch_wait",
-    "kp_batch_hit_offsets", "kp_batch_hits", "kp_batch_set_hits", "kp_batch_cigar_offsets", "kp_batch_cigars", "kp_batch_cs_offsets", "kp_batch_cs", "kp_batch_variant_offsets", "kp_batch_variants", "kp_format_variants", "kp_batch_breakpoint_offsets", "kp_batch_breakpoints", "kp_format_breakpoints", "kp_format_paf", "kp_format_paf_tags", "kp_batch_stats", "kp_batch_profile", "kp_batch_anchors",
+    "kp_batch_hit_offsets", "kp_batch_hits", "kp_batch_set_hits", "kp_batch_cigar_offsets", "kp_batch_cigars", "kp_batch_cs_offsets", "kp_batch_cs", "kp_batch_variant_offsets", "kp_batch_variants", "kp_format_variants", "kp_batch_breakpoint_offsets", "kp_batch_breakpoints", "kp_format_breakpoints", "kp_batch_alleles", "kp_format_alleles", "kp_allele_locus_digest", "kp_format_paf", "kp_format_paf_tags", "kp_batch_stats", "kp_batch_profile", "kp_batch_anchors",
     "kp_batch_tasks", "kp_batch_task_results", "kp_batch_joins", "kp_db_load_typing", "kp_db_load_typing_group", "kp_batch_use_group", "kp_batch_score", "kp_batch_reduce", "kp_batch_typing_caps",
     "kp_device_count", "kp_device_numa_node", "kp_batch_typing", "kp_batch_proteins", "kp_protein_align", "kp_fasta_pack", "kp_fasta_ingest", "kp_fasta_ingest_many", "kp_fasta_ingest_file", "kp_fasta_ingest_shard", "kp_shard_words_into", "kp_shard_free", "kp_fasta_simd", "kp_pack_contigs",
     "kp_fasta_free", "kp_format_rows", "kp_format_json", "kp_format_fasta", "kp_protein_align_seeded", "kp_randstrobes", "kp_randstrobe_top_hits",
@@ -540,6 +544,80 @@ def format_breakpoints(gene_names, asm_names, contig_names, asm_first_ctg, kept,
             return out[:need].tobytes()
         out = np.empty(int(need), np.uint8)
     raise NativeError("kp_format_breakpoints: size kept changing")
+
+
+class AlleleTables(C.Structure):  # kp_allele_tables
+    _fields_ = [("names", VariantTables), ("locus_names", C.c_void_p), ("locus_name_off", C.c_void_p), ("n_loci", C.c_int32)]
+
+
+def piece_order(pieces, n_pieces) -> np.ndarray:
+    """int32 [n_asm, stride]: the order in which the product lists every assembly's locus pieces -- numpy's argsort of their mean
+    positions (core.py:281), as ``kp_format_json`` is given it; entries beyond an assembly's pieces are their own index."""
+    pieces = np.ascontiguousarray(pieces)
+    n, stride = len(n_pieces), (pieces.shape[1] if pieces.ndim == 2 else 0)
+    order = np.zeros((n, max(stride, 1)), np.int32)
+    order[:] = np.arange(max(stride, 1), dtype=np.int32)[None, :]
+    for a in np.flatnonzero(np.asarray(n_pieces) > 1):
+        m = int(n_pieces[a])
+        order[a, :m] = np.argsort(np.ascontiguousarray(pieces["mean_pos"][a, :m]))
+    return order
+
+
+def locus_alleles(piece_digests, order, n_pieces) -> np.ndarray:
+    """uint64 [n_asm]: the locus digest of every assembly (kp_allele_locus_digest; include/kp_spec.h, ALLELES) from its pieces'
+    digests ``piece_digests[a]`` taken in ``order[a]`` (``piece_order``); 0 for an assembly without a piece."""
+    piece_digests, order = np.ascontiguousarray(piece_digests, np.uint64), np.ascontiguousarray(order, np.int32)
+    h = lib()
+    h.kp_allele_locus_digest.restype = C.c_uint64
+    out = np.zeros(len(n_pieces), np.uint64)
+    for a in np.flatnonzero(np.asarray(n_pieces) > 0):
+        m = int(n_pieces[a])
+        if m > piece_digests.shape[1] or m > order.shape[1]:
+            raise ValueError("a summary counts more locus pieces than the digest table holds")
+        out[a] = h.kp_allele_locus_digest(_p(piece_digests[a]), _p(order[a]), C.c_int32(m))
+    return out
+
+
+def format_alleles(gene_names, locus_names, asm_names, contig_names, asm_first_ctg, n_kept, n_pieces, best_locus, kept, alleles, piece_digests,
+                   order) -> bytes:
+    """The lines of the allele table (kp_format_alleles; host only; no header: ``ALLELES_HEADER``): one per kept record that is not
+    spurious.  The name tables and ``kept`` are those of ``format_variants`` plus the loci's names; ``alleles`` (ALLELE_DTYPE, the
+    shape of ``kept``) and ``piece_digests`` as ``Batch.alleles`` returns them, ``order`` as ``piece_order`` gives it."""
+    gn_b, gn_o = _blob(gene_names)
+    ln_b, ln_o = _blob(locus_names)
+    an_b, an_o = _blob64(asm_names)
+    cn_b, cn_o = _blob64(contig_names)
+    first = _c(asm_first_ctg, np.int64)
+    n_kept, n_pieces, best_locus = _c(n_kept, np.int32), _c(n_pieces, np.int32), _c(best_locus, np.int32)
+    kept = np.ascontiguousarray(kept)
+    alleles = np.ascontiguousarray(alleles, dtype=ALLELE_DTYPE)
+    piece_digests, order = np.ascontiguousarray(piece_digests, np.uint64), np.ascontiguousarray(order, np.int32)
+    n_asm = len(n_kept)
+    if kept.itemsize != 84 or (n_asm and (kept.ndim != 2 or kept.shape[0] != n_asm)) or alleles.shape != kept.shape:
+        raise ValueError("kept must be the [n_asm, stride] table of Batch.typing and alleles the records of Batch.alleles for it")
+    if len(first) != n_asm + 1 or len(an_o) != n_asm + 1 or len(n_pieces) != n_asm or len(best_locus) != n_asm or (n_asm and int(first[-1]) > len(cn_o) - 1):
+        raise ValueError("name tables do not describe the batch")
+    pstride = piece_digests.shape[1] if piece_digests.ndim == 2 else 0
+    if n_asm and (piece_digests.ndim != 2 or piece_digests.shape[0] != n_asm or order.ndim != 2 or order.shape[0] != n_asm or order.shape[1] < pstride):
+        raise ValueError("piece digests and piece order must be [n_asm, stride] tables")
+    if n_asm and order.shape[1] != pstride:
+        order = np.ascontiguousarray(order[:, :pstride])
+    names = VariantTables(gene_names=_p(gn_b).value, gene_name_off=_p(gn_o).value, n_genes=len(gn_o) - 1, asm_names=_p(an_b).value,
+                          asm_name_off=_p(an_o).value, ctg_names=_p(cn_b).value, ctg_name_off=_p(cn_o).value, asm_first_ctg=_p(first).value)  # fmt: skip
+    t = AlleleTables(names=names, locus_names=_p(ln_b).value, locus_name_off=_p(ln_o).value, n_loci=len(ln_o) - 1)
+    h = lib()
+    h.kp_format_alleles.restype = C.c_int64
+    out = np.empty(max(4096, 256 * int(n_kept.sum()) if n_asm else 0), np.uint8)
+    for _ in range(2):
+        need = h.kp_format_alleles(C.byref(t), C.c_int32(n_asm), _p(n_kept), _p(n_pieces), _p(best_locus), _p(kept), _p(alleles),
+                                   C.c_int32(kept.shape[1] if kept.ndim == 2 else 0), _p(piece_digests), _p(order), C.c_int32(pstride), _p(out),
+                                   C.c_int64(len(out)))  # fmt: skip
+        if need < 0:
+            raise ValueError(f"kp_format_alleles failed ({need})")
+        if need <= len(out):
+            return out[:need].tobytes()
+        out = np.empty(int(need), np.uint8)
+    raise NativeError("kp_format_alleles: size kept changing")
 
 
 class JsonTables(C.Structure):  # kp_json_tables
@@ -1057,6 +1135,24 @@ class Batch:
         out = np.zeros(int(off[-1]), BREAKPOINT_DTYPE)
         self.ctx._check(lib().kp_batch_breakpoints(self.ctx._h, self._h, _p(out), C.c_int64(len(out))), "kp_batch_breakpoints")
         return out, off
+
+    def alleles(self, group: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """(records ALLELE_DTYPE [n_asm, kept_stride], piece digests uint64 [n_asm, piece_stride]): the allele digests of the kept
+        records and the locus pieces of ``typing(group)``, laid out as its tables are (kp_batch_alleles; include/kp_spec.h, ALLELES);
+        rows beyond the counts are zero.  After ``reduce_async``; no option is needed, and a hit table that ``set_hits`` put in
+        place serves as well."""
+        self.use_group(group)
+        h = lib()
+        # the first call makes the digests (or says why there are none); strides of zero serve a batch without a kept record only
+        rc = h.kp_batch_alleles(self.ctx._h, self._h, None, C.c_int32(0), None, C.c_int32(0))
+        if not (rc == -1 and b"strides too small" in h.kp_last_error(self.ctx._h)):
+            self.ctx._check(rc, "kp_batch_alleles")
+        kc, pc = C.c_int32(0), C.c_int32(0)
+        self.ctx._check(h.kp_batch_typing_caps(self.ctx._h, self._h, C.byref(kc), C.byref(pc)), "typing_caps")
+        out = np.zeros((self.n_asm, kc.value), ALLELE_DTYPE)
+        pieces = np.zeros((self.n_asm, pc.value), np.uint64)
+        self.ctx._check(h.kp_batch_alleles(self.ctx._h, self._h, _p(out), kc, _p(pieces), pc), "kp_batch_alleles")
+        return out, pieces
 
     def proteins(self, asm_index: int, nbytes: int, group: int = 0) -> np.ndarray:
         self.use_group(group)

@@ -119,6 +119,9 @@ def _add_outputs(p: argparse.ArgumentParser, tsv_flags, include_json: bool) -> N
         g.add_argument("--breakpoints", metavar="FILE", default=argparse.SUPPRESS,
                        help="Write the genes that are split across two reported hits -- by an insertion sequence, a long deletion, an "
                             "inversion or a contig end -- with what lies between the fragments, as a TSV table to a file")
+        g.add_argument("--alleles", metavar="FILE", default=argparse.SUPPRESS,
+                       help="Write a stable 64-bit digest of every reported gene's bases and protein and of the whole locus -- equal "
+                            "digests, equal alleles, across runs -- as a TSV table to a file")
     g.add_argument("--pha4ge", metavar="FILE", nargs="?", const="kaptive_results.pha4ge", type=Path,
                    help="Write PHA4GE-compliant serotyping report to a TSV file (default: %(const)s)")
 
@@ -205,7 +208,8 @@ class _TypingPipeline:
         self.paf_cs, self.paf_eqx = bool(getattr(args, "cs", False)), bool(getattr(args, "eqx", False))  # ... and its cs string
         self.want_variants = bool(getattr(args, "variants", None))  # the variant table of the kept hits: the reductions of this run leave the records
         self.want_breakpoints = bool(getattr(args, "breakpoints", None))  # the breakpoint table of the kept lists, likewise
-        self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins", "paf", "variants", "breakpoints"))  # the files' text (and contig names) are kept
+        self.want_alleles = bool(getattr(args, "alleles", None))  # the allele table of the kept records and the locus pieces, likewise
+        self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins", "paf", "variants", "breakpoints", "alleles"))  # the files' text (and contig names) are kept
         self.fasta_outputs = any(getattr(args, f, None) for f in ("loci", "genes", "proteins"))  # ... and result objects are built
         self.threads = max(1, args.threads or usable_cpus())  # (the cgroup's quota, not the 256 CPUs a container may see)
         # PREFETCH + 1 chunks are being parsed at any time, each by one native call: the thread budget is shared out among them
@@ -265,11 +269,13 @@ class _TypingPipeline:
                 if more:  # one pass for all of them; duplicate keywords and too many genes are refused here, before any typing
                     typer = MultiSerotyper([self.db, *more], max_other_genes=args.max_other_genes, min_completeness=args.min_completeness,
                                            allow_below_threshold=args.below_threshold, partial_edge_tolerance=args.partial_edge_tolerance,
-                                           device=device, variants=self.want_variants, breakpoints=self.want_breakpoints)  # fmt: skip
+                                           device=device, variants=self.want_variants, breakpoints=self.want_breakpoints,
+                                           alleles=self.want_alleles)  # fmt: skip
                 else:
                     typer = Serotyper(self.db, max_other_genes=args.max_other_genes, min_completeness=args.min_completeness,
                                       allow_below_threshold=args.below_threshold, partial_edge_tolerance=args.partial_edge_tolerance,
-                                      device=device, variants=self.want_variants, breakpoints=self.want_breakpoints)  # fmt: skip
+                                      device=device, variants=self.want_variants, breakpoints=self.want_breakpoints,
+                                      alleles=self.want_alleles)  # fmt: skip
                 typer._ctx_early = early_ctx
             self.typer = typer
             self.engine = self.typer.engine  # the context is created here, on the thread that will drive it
@@ -459,6 +465,8 @@ class _TypingPipeline:
                 out["variants"] = bt.variants_tsv()
             if self.want_breakpoints:
                 out["breakpoints"] = bt.breakpoints_tsv()
+            if self.want_alleles:
+                out["alleles"] = bt.alleles_tsv()
             if self.want_tsv:
                 out["tsv"] = bt.tsv()
             if getattr(args, "pha4ge", None):
@@ -696,7 +704,8 @@ class _PerDatabaseOutputs:
     genome by genome (``interleave_lines``).  The files are opened with the first chunk's outputs, which carry the
     databases' keywords."""
 
-    KINDS = (("tsv", "out"), ("pha4ge", "pha4ge"), ("json", "json"), ("paf", "paf"), ("variants", "variants"), ("breakpoints", "breakpoints"))
+    KINDS = (("tsv", "out"), ("pha4ge", "pha4ge"), ("json", "json"), ("paf", "paf"), ("variants", "variants"), ("breakpoints", "breakpoints"),
+             ("alleles", "alleles"))
 
     def __init__(self, args: argparse.Namespace) -> None:
         self.wanted = [(key, path) for key, attr in self.KINDS if (path := getattr(args, attr, None))]
@@ -706,10 +715,10 @@ class _PerDatabaseOutputs:
     def _open(self, keywords) -> None:
         from kaptive_amd.serotyping.io import KaptiveRow, Pha4geRow
 
-        from kaptive_amd._native import BREAKPOINTS_HEADER, VARIANTS_HEADER
+        from kaptive_amd._native import ALLELES_HEADER, BREAKPOINTS_HEADER, VARIANTS_HEADER
 
         headers = {"tsv": KaptiveRow.header(), "pha4ge": Pha4geRow.header(), "json": b"", "paf": b"", "variants": VARIANTS_HEADER,
-                   "breakpoints": BREAKPOINTS_HEADER}
+                   "breakpoints": BREAKPOINTS_HEADER, "alleles": ALLELES_HEADER}
         self.streams = {}
         for key, path in self.wanted:
             if _is_stdout(path):
@@ -777,6 +786,8 @@ def run_type(args: argparse.Namespace) -> int:
         raise ValueError("--variants with --db writes a table per database: it needs a file name, not stdout")
     if getattr(args, "db", None) and (v := getattr(args, "breakpoints", None)) and _is_stdout(v):
         raise ValueError("--breakpoints with --db writes a table per database: it needs a file name, not stdout")
+    if getattr(args, "db", None) and (v := getattr(args, "alleles", None)) and _is_stdout(v):
+        raise ValueError("--alleles with --db writes a table per database: it needs a file name, not stdout")
     handles = {}
     per_db = _PerDatabaseOutputs(args) if getattr(args, "db", None) else None  # several databases: reports per database
 
@@ -804,6 +815,11 @@ def run_type(args: argparse.Namespace) -> int:
 
             handles["breakpoints"] = stream(f)
             handles["breakpoints"].write(BREAKPOINTS_HEADER)
+        if f := getattr(args, "alleles", None):
+            from kaptive_amd._native import ALLELES_HEADER
+
+            handles["alleles"] = stream(f)
+            handles["alleles"].write(ALLELES_HEADER)
     done = 0
     timing_path = os.environ.get("KAPTIVE_AMD_CLI_TIMING")  # bench.py: when each chunk's rows were written
     t_start, chunk_times, phases = time.perf_counter(), [], {}

@@ -75,6 +75,15 @@ struct KpTypingRun {
     DevBuf<int64_t> d_bp_kept_off, d_bp_off;
     DevBuf<uint32_t> d_bp_cnt;           // [n_asm]
     DevBuf<kp_breakpoint> d_bp_tmp, d_bp;  // one record per kept row each: per assembly from its first row, then back to back
+    // allele digests of the kept records and the pieces (kp_alleles.hip): made on first request after a reduction, theirs until the
+    // next reduction or until the hit table goes; nothing below is allocated before somebody asks.
+    bool al_valid = false;
+    std::vector<int64_t> h_al_off;        // kept_off[n_asm + 1], then piece_off[n_asm + 1]: rows before every assembly
+    std::vector<kp_allele> h_al;          // one per kept row, back to back
+    std::vector<uint64_t> h_al_piece;     // one per piece row, back to back
+    DevBuf<int64_t> d_al_off;
+    DevBuf<kp_allele> d_al;
+    DevBuf<uint64_t> d_al_piece;
     // d_pairs: the pairs of the protein DP, one slot per kept row: q_off, q_len, t_off, t_len [slots each], then pair_base [n_asm], n_pairs [1]
     size_t slots() const { return n_asm * (size_t)kept_cap; }
     size_t pairs_len() const { return 4 * slots() + n_asm + 1; }
@@ -228,7 +237,7 @@ struct KpWork : KpPassCaps {
     KpHitRows hit_rows() const { return {.hit_off = d_cig_hit_off.p, .total = hit_off[n_asm]}; }
     KpPerHit<uint32_t> cigars() const { return {.cnt = d_cig_cnt.p, .off = d_cig_off.p, .data = d_cig_ops.p, .cap = (int64_t)cigar_cap}; }
     KpPerHit<char> cs() const { return {.cnt = d_cs_cnt.p, .off = d_cs_off.p, .data = d_cs_bytes.p, .cap = (int64_t)cs_cap}; }
-    void reset_runs() { for (auto &r : runs) if (r) r->split = r->scored = r->reduced = r->sums_valid = r->var_valid = r->bp_valid = false; }  // their hit table is about to be rewritten
+    void reset_runs() { for (auto &r : runs) if (r) r->split = r->scored = r->reduced = r->sums_valid = r->var_valid = r->bp_valid = r->al_valid = false; }  // their hit table is about to be rewritten
 };
 
 #define KP_INPUT_POOL 16  /* recycled device copies of batch inputs: uploads run several shards ahead of the passes that read them */

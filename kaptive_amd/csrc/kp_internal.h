@@ -346,6 +346,11 @@ void kp_launch_variants_walk(const KpBatchView &b, const KpGenes &genes, const K
 // max_kept: the longest list (sizes the LDS tile).
 void kp_launch_breakpoints(const KpBatchView &b, const KpKeptRows &kept, int max_kept, kp_breakpoint *tmp, uint32_t *cnt, int64_t *bp_off,
                            kp_breakpoint *out, hipStream_t stream);
+// kp_alleles.hip (after a reduction, when its allele digests are first asked for): the digests (kp_spec.h, ALLELES) of every kept row
+// (out[kept.total], rows as kept.kept_off lists them) and of every piece row (piece_out[total_pieces], rows as piece_off[n_asm + 1]
+// lists them) -- a wave per row; prot: the reduction's protein buffers, prot_cap bytes per assembly.
+void kp_launch_alleles(const KpBatchView &b, const KpKeptRows &kept, const kp_piece *pieces, int piece_cap, const int64_t *piece_off, int64_t total_pieces,
+                       const uint8_t *prot, int prot_cap, kp_allele *out, uint64_t *piece_out, hipStream_t stream);
 // kp_reduce.hip: assembly a's hits with gene in [gene_lo, gene_hi) (one run: hits are sorted by gene) -> out rows, gene
 // indices relative to gene_lo; out.count[a] = how many
 void kp_launch_hit_split(const KpHitTable &hits, int32_t gene_lo, int32_t gene_hi, const KpHitTable &out, int32_t n_asm, hipStream_t stream);

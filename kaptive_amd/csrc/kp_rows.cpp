@@ -12,6 +12,7 @@
 #include <string>
 
 #include "../../include/kaptive_amd.h"
+#include "kp_alleles.h"
 
 namespace {
 
@@ -351,6 +352,71 @@ extern "C" int64_t kp_format_breakpoints(const kp_variant_tables *t, int32_t n_a
             put_i(o, r.edge_a); o.put('\t');
             put_i(o, r.edge_b); o.put('\t');
             if (r.ir_cols) { put_i(o, r.ir_matches); o.put('/'); put_i(o, r.ir_cols); } else o.put('.');
+            o.put('\n');
+        }
+    }
+    return o.n;
+}
+
+// ---- allele table (kp_spec.h, ALLELES) -------------------------------------------------------------------------------------------
+// One line per kept record the report lists; the locus digest of an assembly is combined here, by kp_alleles.h's one function, from
+// the piece digests in the product's order.
+
+namespace {
+
+inline void put_hex(Out &o, uint64_t v) {
+    char buf[16];
+    for (int i = 15; i >= 0; --i, v >>= 4) buf[i] = "0123456789abcdef"[v & 15u];
+    o.put(buf, 16);
+}
+
+}  // namespace
+
+extern "C" uint64_t kp_allele_locus_digest(const uint64_t *piece_digests, const int32_t *order, int32_t n) {
+    if (n <= 0 || !piece_digests || !order) return 0;
+    return kp_al_locus_digest(piece_digests, order, n);
+}
+
+extern "C" int64_t kp_format_alleles(const kp_allele_tables *t, int32_t n_asm, const int32_t *n_kept, const int32_t *n_pieces, const int32_t *best_locus,
+                                     const kp_kept *kept, const kp_allele *alleles, int32_t kept_stride, const uint64_t *piece_digests,
+                                     const int32_t *piece_order, int32_t piece_stride, char *out, int64_t cap) {
+    if (!t || n_asm < 0 || cap < 0 || (cap > 0 && !out) || kept_stride < 0 || piece_stride < 0) return KP_EINVAL;
+    if (n_asm > 0 && (!n_kept || !n_pieces || !best_locus || !t->names.asm_name_off || !t->names.asm_first_ctg || !t->locus_name_off)) return KP_EINVAL;
+    Out o{out, cap};
+    for (int a = 0; a < n_asm; ++a) {
+        const int nk = n_kept[a], np = n_pieces[a], best = best_locus[a];
+        if (nk < 0 || nk > kept_stride || np < 0 || np > piece_stride || (nk > 0 && (!kept || !alleles)) || (np > 0 && (!piece_digests || !piece_order)))
+            return KP_EINVAL;
+        if (nk == 0) continue;
+        if (best < 0 || best >= t->n_loci) return KP_EINVAL;
+        const int64_t c0 = t->names.asm_first_ctg[a], nc = t->names.asm_first_ctg[a + 1] - c0;
+        const int32_t *order = np ? piece_order + (size_t)a * (size_t)piece_stride : nullptr;
+        for (int p = 0; p < np; ++p)
+            if (order[p] < 0 || order[p] >= np) return KP_EINVAL;
+        const uint64_t locus = np ? kp_al_locus_digest(piece_digests + (size_t)a * (size_t)piece_stride, order, np) : 0;
+        for (int i = 0; i < nk; ++i) {
+            const kp_kept &k = kept[(size_t)a * (size_t)kept_stride + (size_t)i];
+            const kp_allele &d = alleles[(size_t)a * (size_t)kept_stride + (size_t)i];
+            if (!alive(k)) continue;
+            if (k.gene < 0 || k.gene >= t->names.n_genes || k.contig < 0 || k.contig >= nc || k.state < KP_STATE_NORMAL || k.state > KP_STATE_NOVEL) return KP_EINVAL;
+            const int64_t c = c0 + k.contig;
+            o.put(t->names.asm_names + t->names.asm_name_off[a], t->names.asm_name_off[a + 1] - t->names.asm_name_off[a]); o.put('\t');
+            o.put(t->locus_names + t->locus_name_off[best], t->locus_name_off[best + 1] - t->locus_name_off[best]); o.put('\t');
+            if (np) put_hex(o, locus); else o.put('.');
+            o.put('\t');
+            o.put(t->names.gene_names + t->names.gene_name_off[k.gene], t->names.gene_name_off[k.gene + 1] - t->names.gene_name_off[k.gene]); o.put('\t');
+            o.lit((k.flags & KP_F_EXPECTED) ? "expected" : ((k.flags & KP_F_EXTRA) ? "extra" : "other"));
+            o.lit((k.flags & KP_F_INSIDE) ? "_in" : "_out"); o.put('\t');
+            o.put(t->names.ctg_names + t->names.ctg_name_off[c], t->names.ctg_name_off[c + 1] - t->names.ctg_name_off[c]); o.put('\t');
+            put_i(o, (long long)k.t_start + 1); o.put('\t');
+            put_i(o, k.t_end); o.put('\t');
+            o.put(k.strand < 0 ? '-' : '+'); o.put('\t');
+            o.lit(k.state == KP_STATE_PARTIAL ? "partial" : (k.state == KP_STATE_TRUNCATED ? "truncated" : (k.state == KP_STATE_NOVEL ? "below_id_threshold" : "normal")));
+            o.put('\t');
+            put_i(o, (long long)k.t_end - k.t_start); o.put('\t');
+            put_hex(o, d.nt); o.put('\t');
+            put_i(o, k.prot_len); o.put('\t');
+            if (k.prot_len > 0) put_hex(o, d.aa); else o.put('.');
             o.put('\n');
         }
     }

@@ -1,5 +1,5 @@
-// kp_typing.hip -- batched typing (locus scores, the reduction of a batch's hits, gene states, the variant and breakpoint records of the kept hits;
-// per typing group), stand-alone protein aligner.
+// kp_typing.hip -- batched typing (locus scores, the reduction of a batch's hits, gene states, the variant and breakpoint records and the allele
+// digests of the kept hits; per typing group), stand-alone protein aligner.
 #include "kp_host.h"
 
 // the typing group a batch currently addresses and the run of the batch's work set for it (created on first use)
@@ -151,6 +151,7 @@ int kp_batch_reduce(kp_ctx *ctx, kp_batch *b, const int32_t *best_locus, const k
     R.sums_valid = false;
     R.var_valid = false;  // (the variant records describe a kept list: the one that is about to be replaced)
     R.bp_valid = false;   // (the breakpoint records likewise)
+    R.al_valid = false;   // (... and the allele digests)
     return KP_OK;
 }
 
@@ -354,6 +355,66 @@ int kp_batch_breakpoints(kp_ctx *ctx, kp_batch *b, kp_breakpoint *out, int64_t c
     if (cap < total) return kp_fail(ctx, KP_EINVAL, "breakpoint buffer too small");
     if (total > 0)
         if (int frc = fetch_all(ctx, R->stream, {{out, R->d_bp.p, (size_t)total * sizeof(kp_breakpoint)}})) return frc;
+    return KP_OK;
+}
+
+// ---- allele digests of the kept records and the pieces (kp_alleles.hip; kp_spec.h, ALLELES) ---------------------------------------
+static const char *const NO_ALLELES = "this batch has no allele digests: kp_batch_reduce has not run for this group since its hit table was made";
+
+// The digests of the batch's current group, made on first request after its reduction (one kernel on the reduction's stream, behind
+// the ones that finalised the kept list) once the summaries show that no reduction buffer overflowed, and fetched: a record per kept
+// row and per piece row, back to back.  They need the kept list, the pieces, the proteins and the batch's contigs only: no option,
+// no ops -- a table that kp_batch_set_hits put in place serves as well.
+static int ensure_alleles(kp_ctx *ctx, kp_batch *b, KpTypingRun **R_out) {
+    KpWork *w = work_of(b);
+    if (!w || !w->finalised || !typing_group(ctx, b)) return kp_fail(ctx, KP_EINVAL, NO_ALLELES);
+    KpTypingRun &R = typing_run(w, b->group);
+    if (!R.reduced) return kp_fail(ctx, KP_EINVAL, NO_ALLELES);
+    *R_out = &R;
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (int rc = fetch_summaries(ctx, b, w)) return rc;
+    if (R.al_valid) return KP_OK;
+    const size_t n_asm = (size_t)b->n_asm;
+    R.h_al_off.assign(2 * (n_asm + 1), 0);
+    int64_t *const kept_off = R.h_al_off.data(), *const piece_off = kept_off + n_asm + 1;
+    for (size_t a = 0; a < n_asm; ++a) {
+        kept_off[a + 1] = kept_off[a] + std::min(std::max(R.h_sums[a].n_kept, 0), R.kept_cap);
+        piece_off[a + 1] = piece_off[a] + std::min(std::max(R.h_sums[a].n_pieces, 0), R.piece_cap);
+    }
+    const int64_t total = kept_off[n_asm], total_pieces = piece_off[n_asm];
+    R.h_al.assign((size_t)total, kp_allele{0, 0});
+    R.h_al_piece.assign((size_t)total_pieces, 0);
+    if (total + total_pieces > 0) {
+        KP_HIP_CHECK(ctx, R.d_al.reserve((size_t)std::max<int64_t>(total, 1)));
+        KP_HIP_CHECK(ctx, R.d_al_piece.reserve((size_t)std::max<int64_t>(total_pieces, 1)));
+        if (int rc = upload(ctx, R.d_al_off, R.h_al_off.data(), 2 * (n_asm + 1), R.stream)) return rc;
+        const KpKeptRows rows{.kept = R.d_kept.p, .kept_cap = R.kept_cap, .kept_off = R.d_al_off.p, .total = total, .gene_lo = typing_group(ctx, b)->gene_lo};
+        kp_launch_alleles(b->view, rows, R.d_pieces.p, R.piece_cap, R.d_al_off.p + n_asm + 1, total_pieces, R.d_prot.p, R.prot_cap, R.d_al.p, R.d_al_piece.p,
+                          R.stream);
+        KP_HIP_CHECK(ctx, hipGetLastError());
+        if (int frc = fetch_all(ctx, R.stream, {{R.h_al.data(), R.d_al.p, (size_t)total * sizeof(kp_allele)},
+                                                {R.h_al_piece.data(), R.d_al_piece.p, (size_t)total_pieces * sizeof(uint64_t)}})) return frc;
+    }
+    R.al_valid = true;
+    return KP_OK;
+}
+
+int kp_batch_alleles(kp_ctx *ctx, kp_batch *b, kp_allele *out, int32_t kept_stride, uint64_t *piece_out, int32_t piece_stride) {
+    if (!ctx || !b || b->ctx != ctx || kept_stride < 0 || piece_stride < 0 || (b->n_asm > 0 && ((!out && kept_stride > 0) || (!piece_out && piece_stride > 0))))
+        return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpTypingRun *R = nullptr;
+    if (int rc = ensure_alleles(ctx, b, &R)) return rc;
+    const size_t n_asm = (size_t)b->n_asm;
+    const int64_t *const kept_off = R->h_al_off.data(), *const piece_off = kept_off + n_asm + 1;
+    for (size_t a = 0; a < n_asm; ++a)
+        if (kept_off[a + 1] - kept_off[a] > kept_stride || piece_off[a + 1] - piece_off[a] > piece_stride)
+            return kp_fail(ctx, KP_EINVAL, "output strides too small (see kp_batch_typing_caps)");
+    if (kept_stride > 0) std::memset(out, 0, n_asm * (size_t)kept_stride * sizeof(kp_allele));
+    if (piece_stride > 0) std::memset(piece_out, 0, n_asm * (size_t)piece_stride * sizeof(uint64_t));
+    for (size_t a = 0; a < n_asm; ++a) {
+        std::copy(R->h_al.begin() + kept_off[a], R->h_al.begin() + kept_off[a + 1], out + a * (size_t)kept_stride);
+        std::copy(R->h_al_piece.begin() + piece_off[a], R->h_al_piece.begin() + piece_off[a + 1], piece_out + a * (size_t)piece_stride);
+    }
     return KP_OK;
 }
 

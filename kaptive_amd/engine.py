@@ -30,7 +30,7 @@ class Engine:
     single-genome entry points (``align``, ``hits_to_alignments``) are those of a one-database engine."""
 
     def __init__(self, db: "Database | Sequence[Database]", device: int = 0, ctx: "_native.Context | None" = None,
-                 cigar: bool = False, cs: bool = False, variants: bool = False, breakpoints: bool = False) -> None:
+                 cigar: bool = False, cs: bool = False, variants: bool = False, breakpoints: bool = False, alleles: bool = False) -> None:
         """``ctx``: a context of ``device`` the caller created ahead of time (the command line starts the runtime on a thread
         of its own while the database file is still being read); otherwise one is created here.  ``cigar``: alignment passes
         also leave the CIGAR of every hit (``Batch.cigars``; ``align`` then fills ``Alignments.cigars``) -- a second walk of
@@ -40,7 +40,10 @@ class Engine:
         the kept hits (``Batch.variants``; include/kp_spec.h, VARIANTS): ``BatchTyping.variants()`` / ``.variants_tsv()``.  They are
         read off the ops, so such passes compute the CIGARs as well.  ``breakpoints``: every typing path also fetches the breakpoint
         records of the kept lists (``Batch.breakpoints``; include/kp_spec.h, BREAKPOINTS): ``BatchTyping.breakpoints()`` /
-        ``.breakpoints_tsv()``.  They are read off the kept lists and the contigs; the alignment passes do nothing more for them."""
+        ``.breakpoints_tsv()``.  They are read off the kept lists and the contigs; the alignment passes do nothing more for them.
+        ``alleles``: every typing path also fetches the allele digests of the kept records and the locus pieces (``Batch.alleles``;
+        include/kp_spec.h, ALLELES): ``BatchTyping.alleles()`` / ``.locus_alleles()`` / ``.alleles_tsv()``.  One kernel behind the
+        reduction; the alignment passes do nothing more for them either."""
         dbs = list(db) if isinstance(db, (list, tuple)) else [db]
         self.dbs = dbs
         self.db = dbs[0]
@@ -50,6 +53,7 @@ class Engine:
         self.cs = bool(cs)
         self.variants = bool(variants)
         self.breakpoints = bool(breakpoints)
+        self.alleles = bool(alleles)
         self.cigar = bool(cigar) or self.cs or self.variants
         if self.cigar:
             self.ctx.set_option("cigar", 1)
@@ -153,14 +157,15 @@ class Engine:
         )
 
     def _collect(self, typer, batch, ids, scores, best, genomes=None, group: "int | None" = None):
-        """The records of a batch's finished reduction as a ``BatchTyping`` -- with the ``variants`` / ``breakpoints`` option, its
-        variant / breakpoint records too."""
+        """The records of a batch's finished reduction as a ``BatchTyping`` -- with the ``variants`` / ``breakpoints`` / ``alleles``
+        option, its variant / breakpoint records / allele digests too."""
         from kaptive_amd.serotyping import batch as B
 
         group = self.group if group is None else group
         sums, kept, pieces = batch.typing(group)
         return B.BatchTyping(typer, ids, sums, kept, pieces, scores, best, genomes, variants=batch.variants(group) if self.variants else None,
-                             breakpoints=batch.breakpoints(group) if self.breakpoints else None)
+                             breakpoints=batch.breakpoints(group) if self.breakpoints else None,
+                             alleles=batch.alleles(group) if self.alleles else None)
 
     def type_batch(self, typer, batch, ids: Sequence[str], genomes: Sequence[GenomeAssembly] | None = None,
                    aligned: bool = False):

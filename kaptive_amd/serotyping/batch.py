@@ -102,12 +102,14 @@ class BatchTyping:
     phenotype, n_pieces, n_hits (hits kept in the result).
     """
 
-    def __init__(self, typer, ids, sums, kept, pieces, scores, best, genomes=None, variants=None, breakpoints=None) -> None:
+    def __init__(self, typer, ids, sums, kept, pieces, scores, best, genomes=None, variants=None, breakpoints=None, alleles=None) -> None:
         """``variants``: ``(records, var_off)`` of ``Batch.variants`` where the engine was made with ``variants=True``;
-        ``breakpoints``: ``(records, bp_off)`` of ``Batch.breakpoints`` where it was made with ``breakpoints=True``."""
+        ``breakpoints``: ``(records, bp_off)`` of ``Batch.breakpoints`` where it was made with ``breakpoints=True``; ``alleles``:
+        ``(records, piece digests)`` of ``Batch.alleles`` where it was made with ``alleles=True``."""
         self.typer, self.ids, self.genomes = typer, list(ids), genomes
         self._variants = variants
         self._breakpoints = breakpoints
+        self._alleles = alleles
         self.sums, self.kept, self.pieces = sums, kept, pieces
         db = typer._db
         n = len(sums)
@@ -262,6 +264,36 @@ class BatchTyping:
         names = [n for g in self.genomes for n in g.contigs.ids]
         return _native.format_breakpoints(self.typer._db.genes.ids, self.ids, names, first, self.kept, records, bp_off,
                                           self.typer.partial_edge_tolerance)
+
+    def alleles(self):
+        """``(records, piece_digests)``: the allele digests (``_native.ALLELE_DTYPE``; include/kp_spec.h, ALLELES) of the batch's kept
+        records -- ``records[i, j]`` belongs to ``self.kept[i, j]`` -- and of its locus pieces -- ``piece_digests[i, p]`` to
+        ``self.pieces[i, p]``.  Only where the engine was made with ``alleles=True``."""
+        if self._alleles is None:
+            raise ValueError("this batch was typed without allele digests: Engine(db, alleles=True) / Serotyper(db, alleles=True)")
+        return self._alleles
+
+    def locus_alleles(self) -> np.ndarray:
+        """uint64 [n_asm]: the locus digest of every assembly -- its pieces' digests combined in the order the product lists the
+        pieces; 0 for an assembly without a piece."""
+        from kaptive_amd import _native
+
+        _, piece_digests = self.alleles()
+        return _native.locus_alleles(piece_digests, _native.piece_order(self.pieces, self.sums["n_pieces"]), self.sums["n_pieces"])
+
+    def alleles_tsv(self) -> bytes:
+        """The lines of the allele table (``--alleles``; no header: ``_native.ALLELES_HEADER``), formatted by the native library from
+        the digests (kp_format_alleles).  Contig names come from the genomes: ``genomes`` must have been given."""
+        from kaptive_amd import _native
+
+        records, piece_digests = self.alleles()
+        if self.genomes is None:
+            raise ValueError("the allele table names contigs: the batch needs its genomes")
+        first = np.concatenate([[0], np.cumsum([len(g.contigs.ids) for g in self.genomes])]).astype(np.int64)
+        names = [n for g in self.genomes for n in g.contigs.ids]
+        db = self.typer._db
+        return _native.format_alleles(db.genes.ids, db.loci.ids, self.ids, names, first, self.sums["n_kept"], self.sums["n_pieces"], self.best_locus,
+                                      self.kept, records, piece_digests, _native.piece_order(self.pieces, self.sums["n_pieces"]))
 
     def jsonl(self) -> bytes:
         """The JSON lines of the whole batch (``-j``), from the batch's columns and the genomes' text (``genomes`` must have
