@@ -361,6 +361,22 @@ KP_API int kp_batch_breakpoints(kp_ctx *ctx, kp_batch *batch, kp_breakpoint *out
  * kp_batch_set_hits; without a current reduction KP_EINVAL, and kp_last_error names the cause.  One record per kept row and per
  * piece row: nothing overflows, nothing is retried.  The locus digest of an assembly is kp_format_alleles' to combine. */
 KP_API int kp_batch_alleles(kp_ctx *ctx, kp_batch *batch, kp_allele *out, int32_t kept_stride, uint64_t *piece_out, int32_t piece_stride);
+/* Aligned rows of the kept hits (kp_spec.h, ALIGNED ROWS; option "aligned"): every kept record's contig bases projected through its
+ * CIGAR onto the coordinates of the database's gene -- gene_len columns, sixteen to a 64-bit block --, so that the rows of one gene
+ * from any number of batches stack into a multiple alignment.  The reference has no such output.  Option "aligned" (0 | 1) takes
+ * effect from the next kp_batch_align; such a pass computes the CIGARs too, whatever "cigar" says, exactly as "variants" does.
+ * Lifetime and refusals are those of kp_batch_variants: for the group kp_batch_use_group chose, after kp_batch_reduce; made on the
+ * first call after a reduction (kernels on the reduction's stream; with the option off nothing is computed, allocated or launched)
+ * and kept until the group's next kp_batch_reduce, the batch's next kp_batch_align or kp_batch_set_hits.  Without ops for the current
+ * hit table -- the option was off, or kp_batch_set_hits replaced the table -- KP_EINVAL, and kp_last_error names the cause; the
+ * context types its next batch as usual.  Sizes are exact: one record per kept row, (gene_len + 15) / 16 blocks per row.
+ *   kp_batch_aligned_size   : the blocks of all rows
+ *   kp_batch_aligned_rows   : the row of record i of assembly a at rows[a * kept_stride + i] (laid out like kp_batch_typing; rows
+ *                             beyond the counts are zero; a stride smaller than a count gives KP_EINVAL)
+ *   kp_batch_aligned_blocks : the blocks, rows back to back in kept-list order; KP_EINVAL when cap < n_blocks */
+KP_API int kp_batch_aligned_size(kp_ctx *ctx, kp_batch *batch, int64_t *n_blocks);
+KP_API int kp_batch_aligned_rows(kp_ctx *ctx, kp_batch *batch, kp_aligned_row *rows, int32_t kept_stride);
+KP_API int kp_batch_aligned_blocks(kp_ctx *ctx, kp_batch *batch, uint64_t *out, int64_t cap);
 
 /* ---- report rows (host only) -----------------------------------------------------------------------------------------------
  * Replaces KaptiveRow.from_result + bytes(row) per genome (src/kaptive/serotyping/io.py:191-296, 37-43): the TSV lines
@@ -477,6 +493,17 @@ KP_API int64_t kp_format_alleles(const kp_allele_tables *tables, int32_t n_asm, 
                                  const kp_kept *kept, const kp_allele *alleles, int32_t kept_stride, const uint64_t *piece_digests,
                                  const int32_t *piece_order, int32_t piece_stride, char *out, int64_t cap);
 KP_API uint64_t kp_allele_locus_digest(const uint64_t *piece_digests, const int32_t *order, int32_t n);
+
+/* ---- aligned table of a batch (host only) ---------------------------------------------------------------------------------------
+ * One tab-separated line per kept record without KP_F_SPURIOUS, in kept-list order, assemblies in batch order: Assembly, Gene, Contig,
+ * Start, End (1-based and closed, contig forward strand), Strand, Gene length, Gene start, Gene end (1-based and closed, on the
+ * gene), Covered, Inserted, Insertions, Aligned -- the row (kp_spec.h, ALIGNED ROWS) as acgt, n and -, exactly Gene length
+ * characters.  No header line.  Tables as kp_format_variants takes them; n_kept per assembly as the summaries have it; kept and rows
+ * with kept_stride and blocks / n_blocks as kp_batch_typing and kp_batch_aligned_rows / _blocks / _size filled them.  Return value as
+ * kp_format_variants has it; KP_EINVAL also for a count beyond the stride, a row whose off or gene_len runs outside `blocks`, or a
+ * gene or contig the tables do not have. */
+KP_API int64_t kp_format_aligned(const kp_variant_tables *tables, int32_t n_asm, const int32_t *n_kept, const kp_kept *kept, int32_t kept_stride,
+                                 const kp_aligned_row *rows, const uint64_t *blocks, int64_t n_blocks, char *out, int64_t cap);
 
 /* ---- JSON lines of a whole batch (host only) ----------------------------------------------------------------------------------
  * Replaces orjson.dumps(SerotypingResult.to_dict(), OPT_SERIALIZE_NUMPY | OPT_APPEND_NEWLINE) per genome

@@ -542,4 +542,42 @@ typedef struct kp_allele {
     uint64_t aa; /* protein digest; 0 when prot_len == 0 */
 } kp_allele;
 
+/* ---- ALIGNED ROWS (optional, like the variant records: no hit, no op, no kept record and no report byte depends on them) ----------
+ * The reference-anchored alignment row of a KEPT hit: the contig's bases projected through the hit's CIGAR onto the coordinates of
+ * the database's gene.  Rows of one gene from any run on any machine have the same columns and stack into a multiple alignment
+ * with no further work.  Rows are made for the records of the kept list only (kp_kept), never for hits the overlap cull dropped.
+ *
+ * COLUMNS.  The row of a record whose gene has Lq bases has Lq columns; column j is position j of the gene's FORWARD strand.
+ * VALUE OF COLUMN j.  A code 0..3: the contig base that an M column of the hit's CIGAR aligns to gene base j, on the gene's strand
+ * -- complemented, 3 - v, for strand -1 --; 4: that contig position lies inside an N run; GAP: j lies outside [q_start, q_end), or
+ * inside an I op (the gene has bases the contig lacks).  The contig bases of D ops (bases the gene lacks) have no column: they are
+ * dropped and only counted -- `inserted` is the sum of the D lengths, `n_ins` the number of D ops.  `covered` is the number of
+ * columns that are not GAP; it equals the sum of the M lengths.
+ * ORIENTATION is the CIGAR's and the cs string's: for strand +1 the ops run along the gene from row q_start; for strand -1 along
+ * the reverse-complemented gene from row Lq - q_end, and row r of that walk is column Lq - 1 - r of the gene's forward strand.  The
+ * contig is walked forward from t_start either way.  An op of a kind other than M, I and D moves nothing.
+ * PACKED FORM.  Sixteen columns make a block; block b holds columns 16 b .. 16 b + 15.  It is the ALLELES block plus a gap mask:
+ * v = w | (uint64)m << 32 | (uint64)g << 48, where w holds the 2-bit codes (column c in bits 2c, 2c + 1; 0 where m or g is set),
+ * m has bit c set for code 4 and g has bit c set for GAP.  Columns at or beyond Lq contribute nothing to any of the three.  A row
+ * has (Lq + 15) / 16 blocks.
+ * PURE FUNCTION of the record's span and strand, the ops of the hit behind it and the contig's bases.  The gene's own bases are
+ * not read: a column says what the contig holds, not whether it agrees with the gene.
+ * INVALID WALK.  A record whose hit is not found in the finished hit table, or whose ops would leave the gene or the contig -- with
+ * R the sum of the M and I lengths and C that of the M and D lengths: q0 < 0, q0 + R > Lq, t_start < 0 or t_start + C beyond the
+ * contig's end, q0 being the walk's first row; the check the variant records make -- has a row of all GAP, and covered = inserted
+ * = n_ins = 0.
+ * WHICH RECORDS.  Every kept record has a row, KP_F_SPURIOUS ones included; the table lists the others, as the report does.
+ * ORDER.  Rows follow the kept list, assemblies the batch; `off` is the row's first block in the batch's block array, and the
+ * rows lie in it back to back in that order.
+ * KNOWN ANSWERS.  Contig "ttacgtnacgga", gene of 20 bases, record q_start 2, q_end 12, t_start 2, ops 4M 2I 3M 1D 1M.  Strand +1:
+ * "--acgt--nacg--------", blocks f0c3010000900e40 000f000000000000, covered 8, inserted 1, n_ins 1.  Strand -1 (the same ops, now
+ * along the reverse complement from row 8): "--cgtn--acgt--------", blocks f0c3002000e40390 000f000000000000, the same counts.
+ * OUT OF SCOPE.  Merging two fragments of one gene into one row; the dropped insertion bases (the cs string has them); codon or
+ * protein alignments; per-gene output files; any change to the TSV / JSON / PHA4GE bytes. */
+typedef struct kp_aligned_row {
+    int64_t off;      /* first block of the row in the batch's block array */
+    int32_t gene_len; /* Lq */
+    int32_t covered, inserted, n_ins;
+} kp_aligned_row;
+
 #endif /* KP_SPEC_H */

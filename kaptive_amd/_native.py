@@ -46,6 +46,11 @@ ALLELE_DTYPE = np.dtype([("nt", "<u8"), ("aa", "<u8")])  # kp_allele of include/
 ALLELES_HEADER = (b"Assembly\tLocus\tLocus allele\tGene\tSet\tContig\tStart\tEnd\tStrand\tState\tLength\tAllele\tProtein length\t"
                   b"Protein allele\n")  # the columns of kp_format_alleles
 
+ALIGNED_ROW_DTYPE = np.dtype([("off", "<i8"), ("gene_len", "<i4"), ("covered", "<i4"), ("inserted", "<i4"), ("n_ins", "<i4")])  # kp_aligned_row of include/kp_spec.h, ALIGNED ROWS: 24 bytes
+ALIGNED_HEADER = (b"Assembly\tGene\tContig\tStart\tEnd\tStrand\tGene length\tGene start\tGene end\tCovered\tInserted\tInsertions\t"
+                  b"Aligned\n")  # the columns of kp_format_aligned
+ALIGNED_GAP = 5  # the code ``aligned_codes`` gives a GAP column (0..3 bases, 4 inside an N run)
+
 JOIN_MAX_PIECES = 8  # KP_JOIN_MAX_PIECES
 JOIN_DTYPE = np.dtype(
     [("gs", "<i4"), ("contig", "<i4"), ("n_pieces", "<i4"), ("n_anchors", "<i4"), ("chain_score", "<i4"), ("width", "<i4"),
@@ -56,7 +61,7 @@ EXPORTS = (
     "kp_ctx_create", "kp_ctx_destroy", "kp_last_error", "kp_ctx_stream", "kp_ctx_set_option", "kp_host_alloc",
     "kp_host_free", "kp_host_reserve", "kp_host_lock", "kp_host_pinned_bytes", "kp_device_allocations", "kp_db_load", "kp_db_n_postings", "kp_batch_create", "kp_batch_create_async",
     "kp_batch_upload_wait", "kp_batch_depends_on", "kp_batch_create_device", "kp_batch_device_words", "kp_batch_destroy", "kp_batch_align", "kp_batch_wait",
-    "kp_batch_hit_offsets", "kp_batch_hits", "kp_batch_set_hits", "kp_batch_cigar_offsets", "kp_batch_cigars", "kp_batch_cs_offsets", "kp_batch_cs", "kp_batch_variant_offsets", "kp_batch_variants", "kp_format_variants", "kp_batch_breakpoint_offsets", "kp_batch_breakpoints", "kp_format_breakpoints", "kp_batch_alleles", "kp_format_alleles", "kp_allele_locus_digest", "kp_format_paf", "kp_format_paf_tags", "kp_batch_stats", "kp_batch_profile", "kp_batch_anchors",
+    "kp_batch_hit_offsets", "kp_batch_hits", "kp_batch_set_hits", "kp_batch_cigar_offsets", "kp_batch_cigars", "kp_batch_cs_offsets", "kp_batch_cs", "kp_batch_variant_offsets", "kp_batch_variants", "kp_format_variants", "kp_batch_breakpoint_offsets", "kp_batch_breakpoints", "kp_format_breakpoints", "kp_batch_alleles", "kp_format_alleles", "kp_allele_locus_digest", "kp_batch_aligned_size", "kp_batch_aligned_rows", "kp_batch_aligned_blocks", "kp_format_aligned", "kp_format_paf", "kp_format_paf_tags", "kp_batch_stats", "kp_batch_profile", "kp_batch_anchors",
     "kp_batch_tasks", "kp_batch_task_results", "kp_batch_joins", "kp_db_load_typing", "kp_db_load_typing_group", "kp_batch_use_group", "kp_batch_score", "kp_batch_reduce", "kp_batch_typing_caps",
     "kp_device_count", "kp_device_numa_node", "kp_batch_typing", "kp_batch_proteins", "kp_protein_align", "kp_fasta_pack", "kp_fasta_ingest", "kp_fasta_ingest_many", "kp_fasta_ingest_file", "kp_fasta_ingest_shard", "kp_shard_words_into", "kp_shard_free", "kp_fasta_simd", "kp_pack_contigs",
     "kp_fasta_free", "kp_format_rows", "kp_format_json", "kp_format_fasta", "kp_protein_align_seeded", "kp_randstrobes", "kp_randstrobe_top_hits",
@@ -620,6 +625,53 @@ def format_alleles(gene_names, locus_names, asm_names, contig_names, asm_first_c
     raise NativeError("kp_format_alleles: size kept changing")
 
 
+def aligned_codes(row, blocks) -> np.ndarray:
+    """uint8 [gene_len]: the columns of one aligned row (``row``: an ALIGNED_ROW_DTYPE record, ``blocks``: the batch's block array) as
+    codes 0..3, 4 inside an N run and ``ALIGNED_GAP`` for GAP (include/kp_spec.h, ALIGNED ROWS)."""
+    L, off = int(row["gene_len"]), int(row["off"])
+    nb = (L + 15) // 16
+    if L < 0 or off < 0 or off + nb > len(blocks):
+        raise ValueError("the row runs outside the block array")
+    v = np.ascontiguousarray(blocks[off:off + nb], np.uint64)[:, None]
+    c = np.arange(16, dtype=np.uint64)[None, :]
+    code = ((v >> (2 * c)) & np.uint64(3)).astype(np.uint8)
+    code[((v >> (c + np.uint64(32))) & np.uint64(1)) != 0] = 4
+    code[((v >> (c + np.uint64(48))) & np.uint64(1)) != 0] = ALIGNED_GAP
+    return code.reshape(-1)[:L]
+
+
+def format_aligned(gene_names, asm_names, contig_names, asm_first_ctg, n_kept, kept, rows, blocks) -> bytes:
+    """The lines of the aligned table (kp_format_aligned; host only; no header: ``ALIGNED_HEADER``): one per kept record that is not
+    spurious.  The name tables and ``kept`` are those of ``format_variants``; ``rows`` (ALIGNED_ROW_DTYPE, the shape of ``kept``) and
+    ``blocks`` as ``Batch.aligned`` returns them."""
+    gn_b, gn_o = _blob(gene_names)
+    an_b, an_o = _blob64(asm_names)
+    cn_b, cn_o = _blob64(contig_names)
+    first, n_kept = _c(asm_first_ctg, np.int64), _c(n_kept, np.int32)
+    kept = np.ascontiguousarray(kept)
+    rows = np.ascontiguousarray(rows, dtype=ALIGNED_ROW_DTYPE)
+    blocks = np.ascontiguousarray(blocks, np.uint64)
+    n_asm = len(n_kept)
+    if kept.itemsize != 84 or (n_asm and (kept.ndim != 2 or kept.shape[0] != n_asm)) or rows.shape != kept.shape:
+        raise ValueError("kept must be the [n_asm, stride] table of Batch.typing and rows the records of Batch.aligned for it")
+    if len(first) != n_asm + 1 or len(an_o) != n_asm + 1 or (n_asm and int(first[-1]) > len(cn_o) - 1):
+        raise ValueError("name tables do not describe the batch")
+    t = VariantTables(gene_names=_p(gn_b).value, gene_name_off=_p(gn_o).value, n_genes=len(gn_o) - 1, asm_names=_p(an_b).value,
+                      asm_name_off=_p(an_o).value, ctg_names=_p(cn_b).value, ctg_name_off=_p(cn_o).value, asm_first_ctg=_p(first).value)  # fmt: skip
+    h = lib()
+    h.kp_format_aligned.restype = C.c_int64
+    out = np.empty(max(4096, 16 * len(blocks) + 256 * int(n_kept.sum()) if n_asm else 0), np.uint8)
+    for _ in range(2):
+        need = h.kp_format_aligned(C.byref(t), C.c_int32(n_asm), _p(n_kept), _p(kept), C.c_int32(kept.shape[1] if kept.ndim == 2 else 0), _p(rows),
+                                   _p(blocks), C.c_int64(len(blocks)), _p(out), C.c_int64(len(out)))
+        if need < 0:
+            raise ValueError(f"kp_format_aligned failed ({need})")
+        if need <= len(out):
+            return out[:need].tobytes()
+        out = np.empty(int(need), np.uint8)
+    raise NativeError("kp_format_aligned: size kept changing")
+
+
 class JsonTables(C.Structure):  # kp_json_tables
     _fields_ = [("head", C.c_char_p), ("head_len", C.c_int32), ("gene_names", C.c_void_p), ("gene_name_off", C.c_void_p),
                 ("gene_ids", C.c_void_p), ("cluster_names", C.c_void_p), ("products", C.c_void_p), ("gene_id_off", C.c_void_p),
@@ -1153,6 +1205,23 @@ class Batch:
         pieces = np.zeros((self.n_asm, pc.value), np.uint64)
         self.ctx._check(h.kp_batch_alleles(self.ctx._h, self._h, _p(out), kc, _p(pieces), pc), "kp_batch_alleles")
         return out, pieces
+
+    def aligned(self, group: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """(rows ALIGNED_ROW_DTYPE [n_asm, kept_stride], blocks uint64 [n_blocks]): the aligned rows of the kept hits of
+        ``typing(group)`` (kp_batch_aligned_rows / _blocks; include/kp_spec.h, ALIGNED ROWS): ``rows[a, i]`` belongs to kept record i
+        of assembly a, its ``(gene_len + 15) // 16`` blocks start at ``blocks[rows[a, i]["off"]]``; rows beyond the counts are zero.
+        Only after ``reduce_async`` of a batch aligned with the context's ``aligned`` option set."""
+        self.use_group(group)
+        h = lib()
+        n = C.c_int64(0)
+        self.ctx._check(h.kp_batch_aligned_size(self.ctx._h, self._h, C.byref(n)), "kp_batch_aligned_size")
+        kc, pc = C.c_int32(0), C.c_int32(0)
+        self.ctx._check(h.kp_batch_typing_caps(self.ctx._h, self._h, C.byref(kc), C.byref(pc)), "typing_caps")
+        rows = np.zeros((self.n_asm, kc.value), ALIGNED_ROW_DTYPE)
+        blocks = np.zeros(n.value, np.uint64)
+        self.ctx._check(h.kp_batch_aligned_rows(self.ctx._h, self._h, _p(rows), kc), "kp_batch_aligned_rows")
+        self.ctx._check(h.kp_batch_aligned_blocks(self.ctx._h, self._h, _p(blocks), C.c_int64(len(blocks))), "kp_batch_aligned_blocks")
+        return rows, blocks
 
     def proteins(self, asm_index: int, nbytes: int, group: int = 0) -> np.ndarray:
         self.use_group(group)

@@ -122,6 +122,9 @@ def _add_outputs(p: argparse.ArgumentParser, tsv_flags, include_json: bool) -> N
         g.add_argument("--alleles", metavar="FILE", default=argparse.SUPPRESS,
                        help="Write a stable 64-bit digest of every reported gene's bases and protein and of the whole locus -- equal "
                             "digests, equal alleles, across runs -- as a TSV table to a file")
+        g.add_argument("--aligned", metavar="FILE", default=argparse.SUPPRESS,
+                       help="Write every reported gene's contig bases in the coordinates of the database's gene -- one row of exactly "
+                            "gene-length columns per hit, ready to stack into an alignment -- as a TSV table to a file")
     g.add_argument("--pha4ge", metavar="FILE", nargs="?", const="kaptive_results.pha4ge", type=Path,
                    help="Write PHA4GE-compliant serotyping report to a TSV file (default: %(const)s)")
 
@@ -209,7 +212,8 @@ class _TypingPipeline:
         self.want_variants = bool(getattr(args, "variants", None))  # the variant table of the kept hits: the reductions of this run leave the records
         self.want_breakpoints = bool(getattr(args, "breakpoints", None))  # the breakpoint table of the kept lists, likewise
         self.want_alleles = bool(getattr(args, "alleles", None))  # the allele table of the kept records and the locus pieces, likewise
-        self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins", "paf", "variants", "breakpoints", "alleles"))  # the files' text (and contig names) are kept
+        self.want_aligned = bool(getattr(args, "aligned", None))  # the aligned rows of the kept hits, likewise
+        self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins", "paf", "variants", "breakpoints", "alleles", "aligned"))  # the files' text (and contig names) are kept
         self.fasta_outputs = any(getattr(args, f, None) for f in ("loci", "genes", "proteins"))  # ... and result objects are built
         self.threads = max(1, args.threads or usable_cpus())  # (the cgroup's quota, not the 256 CPUs a container may see)
         # PREFETCH + 1 chunks are being parsed at any time, each by one native call: the thread budget is shared out among them
@@ -270,12 +274,12 @@ class _TypingPipeline:
                     typer = MultiSerotyper([self.db, *more], max_other_genes=args.max_other_genes, min_completeness=args.min_completeness,
                                            allow_below_threshold=args.below_threshold, partial_edge_tolerance=args.partial_edge_tolerance,
                                            device=device, variants=self.want_variants, breakpoints=self.want_breakpoints,
-                                           alleles=self.want_alleles)  # fmt: skip
+                                           alleles=self.want_alleles, aligned=self.want_aligned)  # fmt: skip
                 else:
                     typer = Serotyper(self.db, max_other_genes=args.max_other_genes, min_completeness=args.min_completeness,
                                       allow_below_threshold=args.below_threshold, partial_edge_tolerance=args.partial_edge_tolerance,
                                       device=device, variants=self.want_variants, breakpoints=self.want_breakpoints,
-                                      alleles=self.want_alleles)  # fmt: skip
+                                      alleles=self.want_alleles, aligned=self.want_aligned)  # fmt: skip
                 typer._ctx_early = early_ctx
             self.typer = typer
             self.engine = self.typer.engine  # the context is created here, on the thread that will drive it
@@ -467,6 +471,8 @@ class _TypingPipeline:
                 out["breakpoints"] = bt.breakpoints_tsv()
             if self.want_alleles:
                 out["alleles"] = bt.alleles_tsv()
+            if self.want_aligned:
+                out["aligned"] = bt.aligned_tsv()
             if self.want_tsv:
                 out["tsv"] = bt.tsv()
             if getattr(args, "pha4ge", None):
@@ -705,7 +711,7 @@ class _PerDatabaseOutputs:
     databases' keywords."""
 
     KINDS = (("tsv", "out"), ("pha4ge", "pha4ge"), ("json", "json"), ("paf", "paf"), ("variants", "variants"), ("breakpoints", "breakpoints"),
-             ("alleles", "alleles"))
+             ("alleles", "alleles"), ("aligned", "aligned"))
 
     def __init__(self, args: argparse.Namespace) -> None:
         self.wanted = [(key, path) for key, attr in self.KINDS if (path := getattr(args, attr, None))]
@@ -715,10 +721,10 @@ class _PerDatabaseOutputs:
     def _open(self, keywords) -> None:
         from kaptive_amd.serotyping.io import KaptiveRow, Pha4geRow
 
-        from kaptive_amd._native import ALLELES_HEADER, BREAKPOINTS_HEADER, VARIANTS_HEADER
+        from kaptive_amd._native import ALIGNED_HEADER, ALLELES_HEADER, BREAKPOINTS_HEADER, VARIANTS_HEADER
 
         headers = {"tsv": KaptiveRow.header(), "pha4ge": Pha4geRow.header(), "json": b"", "paf": b"", "variants": VARIANTS_HEADER,
-                   "breakpoints": BREAKPOINTS_HEADER, "alleles": ALLELES_HEADER}
+                   "breakpoints": BREAKPOINTS_HEADER, "alleles": ALLELES_HEADER, "aligned": ALIGNED_HEADER}
         self.streams = {}
         for key, path in self.wanted:
             if _is_stdout(path):
@@ -788,6 +794,8 @@ def run_type(args: argparse.Namespace) -> int:
         raise ValueError("--breakpoints with --db writes a table per database: it needs a file name, not stdout")
     if getattr(args, "db", None) and (v := getattr(args, "alleles", None)) and _is_stdout(v):
         raise ValueError("--alleles with --db writes a table per database: it needs a file name, not stdout")
+    if getattr(args, "db", None) and (v := getattr(args, "aligned", None)) and _is_stdout(v):
+        raise ValueError("--aligned with --db writes a table per database: it needs a file name, not stdout")
     handles = {}
     per_db = _PerDatabaseOutputs(args) if getattr(args, "db", None) else None  # several databases: reports per database
 
@@ -820,6 +828,11 @@ def run_type(args: argparse.Namespace) -> int:
 
             handles["alleles"] = stream(f)
             handles["alleles"].write(ALLELES_HEADER)
+        if f := getattr(args, "aligned", None):
+            from kaptive_amd._native import ALIGNED_HEADER
+
+            handles["aligned"] = stream(f)
+            handles["aligned"].write(ALIGNED_HEADER)
     done = 0
     timing_path = os.environ.get("KAPTIVE_AMD_CLI_TIMING")  # bench.py: when each chunk's rows were written
     t_start, chunk_times, phases = time.perf_counter(), [], {}

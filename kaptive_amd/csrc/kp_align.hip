@@ -143,7 +143,8 @@ int kp_batch_align(kp_ctx *ctx, kp_batch *b) {
     w->aligned = false; w->finalised = false;
     w->cs_on = ctx->opt.cs != 0; w->cs_valid = false;
     w->var_on = ctx->opt.variants != 0;
-    w->cigar_on = ctx->opt.cigar != 0 || w->cs_on || w->var_on; w->cigar_valid = false;  // (cs and the variant records read the ops)
+    w->aln_on = ctx->opt.aligned != 0;
+    w->cigar_on = ctx->opt.cigar != 0 || w->cs_on || w->var_on || w->aln_on; w->cigar_valid = false;  // (cs, the variant records and the aligned rows read the ops)
     for (auto &v : w->h_tasks) v.clear();
     w->reset_runs();
     w->stats[KP_STAT_RERUNS] = 0;

@@ -75,14 +75,11 @@ KP_HD bool kp_al_clear_of_runs(const KpTargetSeq &t, int32_t s, int32_t e) {
     return a >= t.n_runs || t.runs[2 * a] >= e;
 }
 
-// v_i of the interval [s, e) (assembly coordinates, checked by kp_al_interval) on `strand`: w_i | m_i << 32.  i < kp_al_nt_blocks.
-// The block's n live columns are assembly positions p0 .. p0 + n - 1; they sit in one packed word or in two neighbouring ones, and
-// the second is read only where a live column lies in it -- never a word beyond the assembly's last.
-KP_HD uint64_t kp_al_nt_block(const KpTargetSeq &t, int32_t s, int32_t e, int strand, int64_t i, bool clear_of_runs) {
-    const int64_t L = (int64_t)e - s, c0 = i * KP_AL_COLS;
-    const int n = (int)(L - c0 < KP_AL_COLS ? L - c0 : KP_AL_COLS);
-    const bool fwd = strand >= 0;
-    const int32_t p0 = fwd ? (int32_t)(s + c0) : (int32_t)(e - c0 - n);
+// 1 <= n <= 16 strand-corrected columns of the assembly positions p0 .. p0 + n - 1 (inside the assembly's packed words), with their
+// N mask: w | m << 32, column j in bits 2j / bit j, nothing above column n - 1.  Forward, column j is position p0 + j; otherwise it
+// is position p0 + n - 1 - j, complemented.  The positions sit in one packed word or in two neighbouring ones, and the second is
+// read only where one of them lies in it -- never a word beyond the assembly's last.
+KP_HD uint64_t kp_al_cols(const KpTargetSeq &t, int32_t p0, int n, bool fwd, bool clear_of_runs) {
     const int wi = p0 >> 4, sh = 2 * (p0 & 15);
     uint32_t w = t.words[wi] >> sh;
     if (((p0 + n - 1) >> 4) != wi) w |= t.words[wi + 1] << (32 - sh);  // (sh > 0 here)
@@ -94,6 +91,15 @@ KP_HD uint64_t kp_al_nt_block(const KpTargetSeq &t, int32_t s, int32_t e, int st
     }
     w &= live & ~kp_al_pair_mask(m);
     return (uint64_t)w | ((uint64_t)m << 32);
+}
+
+// v_i of the interval [s, e) (assembly coordinates, checked by kp_al_interval) on `strand`: w_i | m_i << 32.  i < kp_al_nt_blocks.
+// The block's n live columns are assembly positions p0 .. p0 + n - 1.
+KP_HD uint64_t kp_al_nt_block(const KpTargetSeq &t, int32_t s, int32_t e, int strand, int64_t i, bool clear_of_runs) {
+    const int64_t L = (int64_t)e - s, c0 = i * KP_AL_COLS;
+    const int n = (int)(L - c0 < KP_AL_COLS ? L - c0 : KP_AL_COLS);
+    const bool fwd = strand >= 0;
+    return kp_al_cols(t, fwd ? (int32_t)(s + c0) : (int32_t)(e - c0 - n), n, fwd, clear_of_runs);
 }
 
 // v_i of n protein bytes: eight per block, little-endian, zero-padded

@@ -263,6 +263,7 @@ int kp_ctx_set_option(kp_ctx *ctx, const char *name, int64_t value) {
     else if (n == "cigar") o.cigar = value != 0;
     else if (n == "cs") o.cs = value != 0;
     else if (n == "variants") o.variants = value != 0;
+    else if (n == "aligned") o.aligned = value != 0;
     else if (n == "upload_piece_mb") o.upload_piece_mb = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(value, 4096));
     else return kp_fail(ctx, KP_EINVAL, "unknown option: " + n);
     return KP_OK;

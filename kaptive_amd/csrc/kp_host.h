@@ -56,6 +56,8 @@ struct KpTypingRun {
     // variant records of the kept hits (kp_variants.hip), only where the pass ran with the `variants` option: nothing below is
     // allocated otherwise.  Made on first request after a reduction; theirs until the next reduction or until the hit table goes.
     bool var_valid = false;
+    bool src_valid = false;            // h_kept_off / d_kept_off / d_var_src belong to the most recent reduction (kp_launch_kept_locate): the
+                                       // variant records and the aligned rows both read them, whichever is asked for first makes them
     uint64_t var_cap = 0;              // records d_var was sized for
     int64_t var_total = 0;             // records of all kept hits
     std::vector<int64_t> h_kept_off;   // [n_asm + 1] kept records before every assembly
@@ -84,6 +86,15 @@ struct KpTypingRun {
     DevBuf<int64_t> d_al_off;
     DevBuf<kp_allele> d_al;
     DevBuf<uint64_t> d_al_piece;
+    // aligned rows of the kept hits (kp_aligned.hip), only where the pass ran with the `aligned` option: nothing below is allocated
+    // otherwise.  Made on first request after a reduction; theirs until the next reduction or until the hit table goes.
+    bool aln_valid = false;
+    int64_t aln_blocks = 0;                  // blocks of all rows: what d_aln_blocks holds, exactly
+    std::vector<kp_aligned_row> h_aln_rows;  // one per kept row, back to back
+    DevBuf<uint32_t> d_aln_cnt;
+    DevBuf<int64_t> d_aln_off;               // [kept rows + 1] first block of every row
+    DevBuf<uint64_t> d_aln_blocks;
+    DevBuf<kp_aligned_row> d_aln_rows;
     // d_pairs: the pairs of the protein DP, one slot per kept row: q_off, q_len, t_off, t_len [slots each], then pair_base [n_asm], n_pairs [1]
     size_t slots() const { return n_asm * (size_t)kept_cap; }
     size_t pairs_len() const { return 4 * slots() + n_asm + 1; }
@@ -106,6 +117,7 @@ struct KpOptions : KpCapOptions {
     int spin_wait = 0;              // host waits spin on the stream (the runtime's default) instead of blocking on an interrupt
     int cigar = 0;                  // CIGARs of the finished hits (kp_cigar.hip): off unless asked for; applies from the next kp_batch_align
     int variants = 0;               // variant records of the kept hits (kp_variants.hip); a pass with it computes the CIGARs too: the records are read off them
+    int aligned = 0;                // aligned rows of the kept hits (kp_aligned.hip); a pass with it computes the CIGARs too: the rows are read off them
     int cs = 0;                     // cs difference strings of the finished hits (kp_cs.hip); a pass with it computes the CIGARs too: cs reads them
     bool trace_summary = true;      // KAPTIVE_AMD_TRACE_SUMMARY=0: the band walks ignore the fills' piece summaries and fetch every piece on a path (kp_walk.h; A/B switch)
     bool join_stats = false;        // KAPTIVE_AMD_JOIN_STATS: kp_batch_wait reports the pass's group / join / mid_occ counts on stderr
@@ -211,6 +223,7 @@ struct KpWork : KpPassCaps {
     DevBuf<int64_t> d_cs_off;        // [total_hits + 1] first byte of every hit
     DevBuf<char> d_cs_bytes;
     bool var_on = false;             // the pass was enqueued with the `variants` option (kp_variants.hip; the records live in the typing runs)
+    bool aln_on = false;             // the pass was enqueued with the `aligned` option (kp_aligned.hip; the rows live in the typing runs)
     // reduction: one run per typing group, created on first use
     std::vector<std::unique_ptr<KpTypingRun>> runs;
     // results
@@ -237,7 +250,7 @@ struct KpWork : KpPassCaps {
     KpHitRows hit_rows() const { return {.hit_off = d_cig_hit_off.p, .total = hit_off[n_asm]}; }
     KpPerHit<uint32_t> cigars() const { return {.cnt = d_cig_cnt.p, .off = d_cig_off.p, .data = d_cig_ops.p, .cap = (int64_t)cigar_cap}; }
     KpPerHit<char> cs() const { return {.cnt = d_cs_cnt.p, .off = d_cs_off.p, .data = d_cs_bytes.p, .cap = (int64_t)cs_cap}; }
-    void reset_runs() { for (auto &r : runs) if (r) r->split = r->scored = r->reduced = r->sums_valid = r->var_valid = r->bp_valid = r->al_valid = false; }  // their hit table is about to be rewritten
+    void reset_runs() { for (auto &r : runs) if (r) r->split = r->scored = r->reduced = r->sums_valid = r->var_valid = r->src_valid = r->aln_valid = r->bp_valid = r->al_valid = false; }  // their hit table is about to be rewritten
 };
 
 #define KP_INPUT_POOL 16  /* recycled device copies of batch inputs: uploads run several shards ahead of the passes that read them */

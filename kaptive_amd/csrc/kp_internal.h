@@ -335,11 +335,22 @@ void kp_launch_count_scan(const uint32_t *cnt, int64_t n, int64_t *off, hipStrea
 // cig: what kp_launch_cigar_walk left; nothing here reads the trace buffer.
 void kp_launch_cs_walk(const KpBatchView &b, const KpGenes &genes, const KpHitTable &hits, const KpHitRows &rows, const KpPerHit<uint32_t> &cig,
                        const KpPerHit<char> &cs, bool emit, hipStream_t stream);
+// kp_variants.hip (after a reduction, for the passes that read the ops of the kept hits -- variant records, aligned rows; once per
+// reduction, whichever asks first): the hit behind every kept record located in the finished table: src[kept.total], its row as
+// kp_batch_hits lists the rows, -1 none.
+void kp_launch_kept_locate(const KpBatchView &b, const KpHitTable &hits, const KpHitRows &rows, const KpKeptRows &kept, int64_t *src, hipStream_t stream);
 // kp_variants.hip (only with the `variants` option; after a reduction, while the ops of the pass are valid): the variant records
-// (kp_spec.h, VARIANTS) of every kept record -- the hit behind it located in the finished table (src: its row, -1 none), its records
-// counted (var.cnt) and scanned (var.off), or with `emit` stored from var.off[row] -- stores beyond var.cap are dropped.
-void kp_launch_variants_walk(const KpBatchView &b, const KpGenes &genes, const KpHitTable &hits, const KpHitRows &rows, const KpPerHit<uint32_t> &cig,
-                             const KpKeptRows &kept, int64_t *src, const KpPerHit<kp_variant> &var, bool emit, hipStream_t stream);
+// (kp_spec.h, VARIANTS) of every kept record -- src: kp_launch_kept_locate's --, its records counted (var.cnt) and scanned (var.off),
+// or with `emit` stored from var.off[row] -- stores beyond var.cap are dropped.
+void kp_launch_variants_walk(const KpBatchView &b, const KpGenes &genes, const KpPerHit<uint32_t> &cig, const KpKeptRows &kept, const int64_t *src,
+                             const KpPerHit<kp_variant> &var, bool emit, hipStream_t stream);
+// kp_aligned.hip (only with the `aligned` option; after a reduction, while the ops of the pass are valid): the aligned rows
+// (kp_spec.h, ALIGNED ROWS) of every kept record.  count: the blocks of every row (cnt[kept.total]) and their scan (off[kept.total + 1]);
+// emit: the blocks from off[row] on (`blocks` holds off[kept.total] of them) and the row records (out[kept.total]); src:
+// kp_launch_kept_locate's, rows: the hit rows it indexes.
+void kp_launch_aligned_count(const KpBatchView &b, const KpGenes &genes, const KpKeptRows &kept, uint32_t *cnt, int64_t *off, hipStream_t stream);
+void kp_launch_aligned_emit(const KpBatchView &b, const KpGenes &genes, const KpHitRows &rows, const KpPerHit<uint32_t> &cig, const KpKeptRows &kept,
+                            const int64_t *src, const int64_t *off, uint64_t *blocks, kp_aligned_row *out, hipStream_t stream);
 // kp_breakpoints.hip (after a reduction, when its breakpoint records are first asked for): the records (kp_spec.h, BREAKPOINTS) of
 // every assembly's kept list -- a wave per assembly leaves them in kept_b order from tmp[kept.kept_off[a]] on and their number in cnt[a];
 // bp_off[n_asm + 1] is the scan of the numbers and out holds the records back to back.  tmp and out: kept.total records each;

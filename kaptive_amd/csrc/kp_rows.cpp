@@ -422,3 +422,48 @@ extern "C" int64_t kp_format_alleles(const kp_allele_tables *t, int32_t n_asm, c
     }
     return o.n;
 }
+
+// ---- aligned table (kp_spec.h, ALIGNED ROWS) --------------------------------------------------------------------------------------
+// One line per kept record the report lists; the row is unpacked here, sixteen columns a block: a gap bit gives '-', an N bit 'n',
+// anything else the letter of its 2-bit code.
+extern "C" int64_t kp_format_aligned(const kp_variant_tables *t, int32_t n_asm, const int32_t *n_kept, const kp_kept *kept, int32_t kept_stride,
+                                     const kp_aligned_row *rows, const uint64_t *blocks, int64_t n_blocks, char *out, int64_t cap) {
+    if (!t || n_asm < 0 || cap < 0 || (cap > 0 && !out) || kept_stride < 0 || n_blocks < 0 || (n_blocks > 0 && !blocks)) return KP_EINVAL;
+    if (n_asm > 0 && (!n_kept || !t->asm_name_off || !t->asm_first_ctg)) return KP_EINVAL;
+    Out o{out, cap};
+    for (int a = 0; a < n_asm; ++a) {
+        const int nk = n_kept[a];
+        if (nk < 0 || nk > kept_stride || (nk > 0 && (!kept || !rows))) return KP_EINVAL;
+        const int64_t c0 = t->asm_first_ctg[a], nc = t->asm_first_ctg[a + 1] - c0;
+        for (int i = 0; i < nk; ++i) {
+            const kp_kept &k = kept[(size_t)a * (size_t)kept_stride + (size_t)i];
+            const kp_aligned_row &r = rows[(size_t)a * (size_t)kept_stride + (size_t)i];
+            if (!alive(k)) continue;
+            if (k.gene < 0 || k.gene >= t->n_genes || k.contig < 0 || k.contig >= nc) return KP_EINVAL;
+            const int64_t nb = r.gene_len < 0 ? -1 : ((int64_t)r.gene_len + 15) / 16;
+            if (nb < 0 || r.off < 0 || r.off > n_blocks || nb > n_blocks - r.off) return KP_EINVAL;
+            const int64_t c = c0 + k.contig;
+            o.put(t->asm_names + t->asm_name_off[a], t->asm_name_off[a + 1] - t->asm_name_off[a]); o.put('\t');
+            o.put(t->gene_names + t->gene_name_off[k.gene], t->gene_name_off[k.gene + 1] - t->gene_name_off[k.gene]); o.put('\t');
+            o.put(t->ctg_names + t->ctg_name_off[c], t->ctg_name_off[c + 1] - t->ctg_name_off[c]); o.put('\t');
+            put_i(o, (long long)k.t_start + 1); o.put('\t');
+            put_i(o, k.t_end); o.put('\t');
+            o.put(k.strand < 0 ? '-' : '+'); o.put('\t');
+            put_i(o, r.gene_len); o.put('\t');
+            put_i(o, (long long)k.q_start + 1); o.put('\t');
+            put_i(o, k.q_end); o.put('\t');
+            put_i(o, r.covered); o.put('\t');
+            put_i(o, r.inserted); o.put('\t');
+            put_i(o, r.n_ins); o.put('\t');
+            for (int64_t j = 0; j < nb; ++j) {
+                const uint64_t v = blocks[r.off + j];
+                const int n = (int)std::min<int64_t>(16, (int64_t)r.gene_len - 16 * j);
+                char buf[16];
+                for (int x = 0; x < n; ++x) buf[x] = ((v >> (48 + x)) & 1u) ? '-' : (((v >> (32 + x)) & 1u) ? 'n' : "acgt"[(v >> (2 * x)) & 3u]);
+                o.put(buf, n);
+            }
+            o.put('\n');
+        }
+    }
+    return o.n;
+}

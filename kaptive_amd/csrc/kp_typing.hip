@@ -1,5 +1,5 @@
-// kp_typing.hip -- batched typing (locus scores, the reduction of a batch's hits, gene states, the variant and breakpoint records and the allele
-// digests of the kept hits; per typing group), stand-alone protein aligner.
+// kp_typing.hip -- batched typing (locus scores, the reduction of a batch's hits, gene states, the variant and breakpoint records, the allele
+// digests and the aligned rows of the kept hits; per typing group), stand-alone protein aligner.
 #include "kp_host.h"
 
 // the typing group a batch currently addresses and the run of the batch's work set for it (created on first use)
@@ -32,6 +32,17 @@ static int ensure_run_streams(kp_ctx *ctx, KpTypingRun &R, int32_t group) {
     KP_HIP_CHECK(ctx, hipEventCreateWithFlags(&R.ev_fork.h, hipEventDisableTiming));
     KP_HIP_CHECK(ctx, hipEventCreateWithFlags(&R.ev_join.h, hipEventDisableTiming));
     return KP_OK;
+}
+
+// A buffer whose rows are read back beyond what the kernels wrote (the kept and piece rows behind an assembly's counts): zeroed
+// whenever it is (re)allocated, so that those bytes never depend on what the device memory held before -- a settled context
+// allocates nothing and pays nothing.
+template <class T>
+static hipError_t reserve_zeroed(DevBuf<T> &buf, size_t want, hipStream_t stream) {
+    const size_t had = buf.n;
+    hipError_t e = buf.reserve(want);
+    if (e == hipSuccess && buf.n != had) e = hipMemsetAsync(buf.p, 0, buf.n * sizeof(T), stream);
+    return e;
 }
 
 extern "C" {
@@ -96,8 +107,8 @@ static int enqueue_reduce(kp_ctx *ctx, kp_batch *b, KpWork *w) {
     KP_HIP_CHECK(ctx, R.d_keys.reserve(n_asm * w->hit_cap));
     KP_HIP_CHECK(ctx, R.d_order.reserve(n_asm * w->hit_cap));
     KP_HIP_CHECK(ctx, R.d_flag.reserve(n_asm * w->hit_cap));
-    KP_HIP_CHECK(ctx, R.d_kept.reserve(slots));
-    KP_HIP_CHECK(ctx, R.d_pieces.reserve(n_asm * (size_t)R.piece_cap));
+    KP_HIP_CHECK(ctx, reserve_zeroed(R.d_kept, slots, R.stream));
+    KP_HIP_CHECK(ctx, reserve_zeroed(R.d_pieces, n_asm * (size_t)R.piece_cap, R.stream));
     KP_HIP_CHECK(ctx, R.d_summary.reserve(n_asm));
     KP_HIP_CHECK(ctx, R.d_prot.reserve(n_asm * (size_t)R.prot_cap));
     KP_HIP_CHECK(ctx, R.d_pairs.reserve(R.pairs_len()));
@@ -150,6 +161,8 @@ int kp_batch_reduce(kp_ctx *ctx, kp_batch *b, const int32_t *best_locus, const k
     R.reduced = true;
     R.sums_valid = false;
     R.var_valid = false;  // (the variant records describe a kept list: the one that is about to be replaced)
+    R.src_valid = false;  // (... and so do the hit rows behind its records
+    R.aln_valid = false;  //  and the aligned rows)
     R.bp_valid = false;   // (the breakpoint records likewise)
     R.al_valid = false;   // (... and the allele digests)
     return KP_OK;
@@ -218,7 +231,7 @@ int kp_batch_typing(kp_ctx *ctx, kp_batch *b, kp_asm_summary *summaries, kp_kept
         size_t &hw = run_caps(ctx, b->group).pack_items;
         const size_t need = n_asm * ((size_t)kept_stride * sizeof(KpKept) + (size_t)piece_stride * sizeof(KpPiece)) / 4;
         if (need > hw) hw = need + need / 4;
-        KP_HIP_CHECK(ctx, R.d_pack.reserve(hw));
+        KP_HIP_CHECK(ctx, reserve_zeroed(R.d_pack, hw, R.stream));
     }
     uint32_t *pk = R.d_pack.p, *pp = pk + n_asm * (size_t)kept_stride * sizeof(KpKept) / 4;
     kp_launch_pack_rows(reinterpret_cast<const uint32_t *>(R.d_kept.p), (size_t)R.kept_cap * sizeof(KpKept) / 4, pk, (size_t)kept_stride * sizeof(KpKept) / 4, kw, (int)n_asm, R.stream);
@@ -235,6 +248,26 @@ int kp_batch_typing(kp_ctx *ctx, kp_batch *b, kp_asm_summary *summaries, kp_kept
         summaries[a].n_normal = (int32_t)vals.size();
         summaries[a].ident_sum = kp_np_sum_f32(vals.data(), (int)vals.size());
     }
+    return KP_OK;
+}
+
+// ---- the hit behind every kept record (kp_variants.hip: kp_launch_kept_locate) ----------------------------------------------------
+// What the variant records and the aligned rows both start from: the kept rows laid out back to back (h_kept_off / d_kept_off) and,
+// in d_var_src, the row of the finished hit table behind each -- enqueued once per reduction, by whichever of the two is asked for
+// first, on the reduction's stream behind the kernels that finalised the kept list.  The caller has fetched the summaries.
+static int ensure_kept_src(kp_ctx *ctx, kp_batch *b, KpWork *w, KpTypingRun &R) {
+    if (R.src_valid) return KP_OK;
+    const size_t n_asm = (size_t)b->n_asm;
+    R.h_kept_off.assign(n_asm + 1, 0);
+    for (size_t a = 0; a < n_asm; ++a) R.h_kept_off[a + 1] = R.h_kept_off[a] + std::min(std::max(R.h_sums[a].n_kept, 0), R.kept_cap);
+    const int64_t total = R.h_kept_off[n_asm];
+    if (total > 0) {
+        KP_HIP_CHECK(ctx, R.d_var_src.reserve((size_t)total));
+        if (int rc = upload(ctx, R.d_kept_off, R.h_kept_off.data(), n_asm + 1, R.stream)) return rc;
+        kp_launch_kept_locate(b->view, w->hits(), w->hit_rows(), R.kept_rows(typing_group(ctx, b)->gene_lo), R.d_var_src.p, R.stream);
+        KP_HIP_CHECK(ctx, hipGetLastError());
+    }
+    R.src_valid = true;
     return KP_OK;
 }
 
@@ -256,23 +289,19 @@ static int ensure_variants(kp_ctx *ctx, kp_batch *b, KpTypingRun **R_out) {
     KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     if (int rc = fetch_summaries(ctx, b, w)) return rc;
     if (R.var_valid) return KP_OK;
-    const size_t n_asm = (size_t)b->n_asm;
-    R.h_kept_off.assign(n_asm + 1, 0);
-    for (size_t a = 0; a < n_asm; ++a) R.h_kept_off[a + 1] = R.h_kept_off[a] + std::min(std::max(R.h_sums[a].n_kept, 0), R.kept_cap);
-    const int64_t total = R.h_kept_off[n_asm];
+    if (int rc = ensure_kept_src(ctx, b, w, R)) return rc;
+    const int64_t total = R.h_kept_off.back();
     R.h_var_off.assign((size_t)total + 1, 0);
     R.var_total = 0;
     if (total > 0) {
         R.var_cap = kp_caps_variants_size(ctx->var_caps, (uint64_t)total);
-        KP_HIP_CHECK(ctx, R.d_var_src.reserve((size_t)total));
         KP_HIP_CHECK(ctx, R.d_var_cnt.reserve((size_t)total));
         KP_HIP_CHECK(ctx, R.d_var_off.reserve((size_t)total + 1));
         KP_HIP_CHECK(ctx, R.d_var.reserve(R.var_cap));
-        if (int rc = upload(ctx, R.d_kept_off, R.h_kept_off.data(), n_asm + 1, R.stream)) return rc;
         const KpTypingGroup &T = *typing_group(ctx, b);
-        kp_launch_variants_walk(b->view, ctx->genes, w->hits(), w->hit_rows(), w->cigars(), R.kept_rows(T.gene_lo), R.d_var_src.p, R.variants(), false, R.stream);
+        kp_launch_variants_walk(b->view, ctx->genes, w->cigars(), R.kept_rows(T.gene_lo), R.d_var_src.p, R.variants(), false, R.stream);
         for (int attempt = 0;; ++attempt) {
-            kp_launch_variants_walk(b->view, ctx->genes, w->hits(), w->hit_rows(), w->cigars(), R.kept_rows(T.gene_lo), R.d_var_src.p, R.variants(), true, R.stream);
+            kp_launch_variants_walk(b->view, ctx->genes, w->cigars(), R.kept_rows(T.gene_lo), R.d_var_src.p, R.variants(), true, R.stream);
             KP_HIP_CHECK(ctx, hipGetLastError());
             if (int frc = fetch_all(ctx, R.stream, {{R.h_var_off.data(), R.d_var_off.p, ((size_t)total + 1) * sizeof(int64_t)}})) return frc;
             R.var_total = R.h_var_off[(size_t)total];
@@ -300,6 +329,77 @@ int kp_batch_variants(kp_ctx *ctx, kp_batch *b, kp_variant *out, int64_t cap) {
     if (cap < R->var_total) return kp_fail(ctx, KP_EINVAL, "variant buffer too small");
     if (R->var_total > 0)
         if (int frc = fetch_all(ctx, R->stream, {{out, R->d_var.p, (size_t)R->var_total * sizeof(kp_variant)}})) return frc;
+    return KP_OK;
+}
+
+// ---- aligned rows of the kept hits (kp_aligned.hip; kp_spec.h, ALIGNED ROWS) -------------------------------------------------------
+static const char *const NO_ALIGNED = "this batch has no aligned rows (aligned without the aligned option, or its hit table was replaced)";
+
+// The rows of the batch's current group, made on first request after its reduction: the hit behind every kept record located (unless
+// the variant records already did), the blocks of every row counted and scanned, the total fetched and exactly that reserved, the
+// rows stored and their records fetched -- on the reduction's stream, behind the kernels that finalised the kept list.  Sizes are
+// exact before anything is stored: no guessed capacity, no overflow, no retry.
+static int ensure_aligned(kp_ctx *ctx, kp_batch *b, KpTypingRun **R_out) {
+    KpWork *w = work_of(b);
+    if (!w || !w->finalised || !w->aln_on || !w->cigar_valid || !typing_group(ctx, b)) return kp_fail(ctx, KP_EINVAL, NO_ALIGNED);
+    KpTypingRun &R = typing_run(w, b->group);
+    if (!R.reduced) return kp_fail(ctx, KP_EINVAL, "this batch has no aligned rows: kp_batch_reduce has not run for this group since its hit table was made");
+    *R_out = &R;
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    if (int rc = fetch_summaries(ctx, b, w)) return rc;
+    if (R.aln_valid) return KP_OK;
+    if (int rc = ensure_kept_src(ctx, b, w, R)) return rc;
+    const int64_t total = R.h_kept_off.back();
+    R.h_aln_rows.assign((size_t)total, kp_aligned_row{0, 0, 0, 0, 0});
+    R.aln_blocks = 0;
+    if (total > 0) {
+        KP_HIP_CHECK(ctx, R.d_aln_cnt.reserve((size_t)total));
+        KP_HIP_CHECK(ctx, R.d_aln_off.reserve((size_t)total + 1));
+        KP_HIP_CHECK(ctx, R.d_aln_rows.reserve((size_t)total));
+        const KpKeptRows rows = R.kept_rows(typing_group(ctx, b)->gene_lo);
+        kp_launch_aligned_count(b->view, ctx->genes, rows, R.d_aln_cnt.p, R.d_aln_off.p, R.stream);
+        KP_HIP_CHECK(ctx, hipGetLastError());
+        int64_t n_blocks = 0;
+        if (int frc = fetch_all(ctx, R.stream, {{&n_blocks, R.d_aln_off.p + total, sizeof(int64_t)}})) return frc;
+        if (n_blocks < 0) return kp_fail(ctx, KP_EHIP, "aligned rows: bad block count");
+        KP_HIP_CHECK(ctx, R.d_aln_blocks.reserve((size_t)std::max<int64_t>(n_blocks, 1)));
+        kp_launch_aligned_emit(b->view, ctx->genes, w->hit_rows(), w->cigars(), rows, R.d_var_src.p, R.d_aln_off.p, R.d_aln_blocks.p, R.d_aln_rows.p, R.stream);
+        KP_HIP_CHECK(ctx, hipGetLastError());
+        if (int frc = fetch_all(ctx, R.stream, {{R.h_aln_rows.data(), R.d_aln_rows.p, (size_t)total * sizeof(kp_aligned_row)}})) return frc;
+        R.aln_blocks = n_blocks;
+    }
+    R.aln_valid = true;
+    return KP_OK;
+}
+
+int kp_batch_aligned_size(kp_ctx *ctx, kp_batch *b, int64_t *n_blocks) {
+    if (!ctx || !b || b->ctx != ctx || !n_blocks) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpTypingRun *R = nullptr;
+    if (int rc = ensure_aligned(ctx, b, &R)) return rc;
+    *n_blocks = R->aln_blocks;
+    return KP_OK;
+}
+
+int kp_batch_aligned_rows(kp_ctx *ctx, kp_batch *b, kp_aligned_row *rows, int32_t kept_stride) {
+    if (!ctx || !b || b->ctx != ctx || kept_stride < 0 || (b->n_asm > 0 && !rows && kept_stride > 0)) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpTypingRun *R = nullptr;
+    if (int rc = ensure_aligned(ctx, b, &R)) return rc;
+    const size_t n_asm = (size_t)b->n_asm;
+    const std::vector<int64_t> &kept_off = R->h_kept_off;
+    for (size_t a = 0; a < n_asm; ++a)
+        if (kept_off[a + 1] - kept_off[a] > kept_stride) return kp_fail(ctx, KP_EINVAL, "output strides too small (see kp_batch_typing_caps)");
+    if (kept_stride > 0) std::memset(rows, 0, n_asm * (size_t)kept_stride * sizeof(kp_aligned_row));
+    for (size_t a = 0; a < n_asm; ++a) std::copy(R->h_aln_rows.begin() + kept_off[a], R->h_aln_rows.begin() + kept_off[a + 1], rows + a * (size_t)kept_stride);
+    return KP_OK;
+}
+
+int kp_batch_aligned_blocks(kp_ctx *ctx, kp_batch *b, uint64_t *out, int64_t cap) {
+    if (!ctx || !b || b->ctx != ctx || (!out && cap > 0)) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpTypingRun *R = nullptr;
+    if (int rc = ensure_aligned(ctx, b, &R)) return rc;
+    if (cap < R->aln_blocks) return kp_fail(ctx, KP_EINVAL, "aligned block buffer too small");
+    if (R->aln_blocks > 0)
+        if (int frc = fetch_all(ctx, R->stream, {{out, R->d_aln_blocks.p, (size_t)R->aln_blocks * sizeof(uint64_t)}})) return frc;
     return KP_OK;
 }
 

@@ -30,7 +30,8 @@ class Engine:
     single-genome entry points (``align``, ``hits_to_alignments``) are those of a one-database engine."""
 
     def __init__(self, db: "Database | Sequence[Database]", device: int = 0, ctx: "_native.Context | None" = None,
-                 cigar: bool = False, cs: bool = False, variants: bool = False, breakpoints: bool = False, alleles: bool = False) -> None:
+                 cigar: bool = False, cs: bool = False, variants: bool = False, breakpoints: bool = False, alleles: bool = False,
+                 aligned: bool = False) -> None:
         """``ctx``: a context of ``device`` the caller created ahead of time (the command line starts the runtime on a thread
         of its own while the database file is still being read); otherwise one is created here.  ``cigar``: alignment passes
         also leave the CIGAR of every hit (``Batch.cigars``; ``align`` then fills ``Alignments.cigars``) -- a second walk of
@@ -43,7 +44,9 @@ class Engine:
         ``.breakpoints_tsv()``.  They are read off the kept lists and the contigs; the alignment passes do nothing more for them.
         ``alleles``: every typing path also fetches the allele digests of the kept records and the locus pieces (``Batch.alleles``;
         include/kp_spec.h, ALLELES): ``BatchTyping.alleles()`` / ``.locus_alleles()`` / ``.alleles_tsv()``.  One kernel behind the
-        reduction; the alignment passes do nothing more for them either."""
+        reduction; the alignment passes do nothing more for them either.  ``aligned``: every typing path also fetches the aligned rows
+        of the kept hits (``Batch.aligned``; include/kp_spec.h, ALIGNED ROWS): ``BatchTyping.aligned()`` / ``.aligned_codes()`` /
+        ``.aligned_tsv()``.  They are read off the ops, so such passes compute the CIGARs as well."""
         dbs = list(db) if isinstance(db, (list, tuple)) else [db]
         self.dbs = dbs
         self.db = dbs[0]
@@ -54,13 +57,16 @@ class Engine:
         self.variants = bool(variants)
         self.breakpoints = bool(breakpoints)
         self.alleles = bool(alleles)
-        self.cigar = bool(cigar) or self.cs or self.variants
+        self.aligned = bool(aligned)
+        self.cigar = bool(cigar) or self.cs or self.variants or self.aligned
         if self.cigar:
             self.ctx.set_option("cigar", 1)
         if self.cs:
             self.ctx.set_option("cs", 1)
         if self.variants:
             self.ctx.set_option("variants", 1)
+        if self.aligned:
+            self.ctx.set_option("aligned", 1)
         for d in dbs:  # KP_MAX_GENE_LEN (include/kp_spec.h): query positions are 16-bit fields of the anchor and hit keys
             too_long = np.flatnonzero(np.asarray(d.genes.lengths) > _native.MAX_GENE_LEN)
             if len(too_long):
@@ -165,7 +171,8 @@ class Engine:
         sums, kept, pieces = batch.typing(group)
         return B.BatchTyping(typer, ids, sums, kept, pieces, scores, best, genomes, variants=batch.variants(group) if self.variants else None,
                              breakpoints=batch.breakpoints(group) if self.breakpoints else None,
-                             alleles=batch.alleles(group) if self.alleles else None)
+                             alleles=batch.alleles(group) if self.alleles else None,
+                             aligned=batch.aligned(group) if self.aligned else None)
 
     def type_batch(self, typer, batch, ids: Sequence[str], genomes: Sequence[GenomeAssembly] | None = None,
                    aligned: bool = False):

@@ -102,14 +102,16 @@ class BatchTyping:
     phenotype, n_pieces, n_hits (hits kept in the result).
     """
 
-    def __init__(self, typer, ids, sums, kept, pieces, scores, best, genomes=None, variants=None, breakpoints=None, alleles=None) -> None:
+    def __init__(self, typer, ids, sums, kept, pieces, scores, best, genomes=None, variants=None, breakpoints=None, alleles=None, aligned=None) -> None:
         """``variants``: ``(records, var_off)`` of ``Batch.variants`` where the engine was made with ``variants=True``;
         ``breakpoints``: ``(records, bp_off)`` of ``Batch.breakpoints`` where it was made with ``breakpoints=True``; ``alleles``:
-        ``(records, piece digests)`` of ``Batch.alleles`` where it was made with ``alleles=True``."""
+        ``(records, piece digests)`` of ``Batch.alleles`` where it was made with ``alleles=True``; ``aligned``: ``(rows, blocks)`` of
+        ``Batch.aligned`` where it was made with ``aligned=True``."""
         self.typer, self.ids, self.genomes = typer, list(ids), genomes
         self._variants = variants
         self._breakpoints = breakpoints
         self._alleles = alleles
+        self._aligned = aligned
         self.sums, self.kept, self.pieces = sums, kept, pieces
         db = typer._db
         n = len(sums)
@@ -294,6 +296,36 @@ class BatchTyping:
         db = self.typer._db
         return _native.format_alleles(db.genes.ids, db.loci.ids, self.ids, names, first, self.sums["n_kept"], self.sums["n_pieces"], self.best_locus,
                                       self.kept, records, piece_digests, _native.piece_order(self.pieces, self.sums["n_pieces"]))
+
+    def aligned(self):
+        """``(rows, blocks)``: the aligned rows (``_native.ALIGNED_ROW_DTYPE``; include/kp_spec.h, ALIGNED ROWS) of the batch's kept
+        records -- ``rows[i, j]`` belongs to ``self.kept[i, j]`` and its blocks start at ``blocks[rows[i, j]["off"]]``.  Only where the
+        engine was made with ``aligned=True``."""
+        if self._aligned is None:
+            raise ValueError("this batch was typed without aligned rows: Engine(db, aligned=True) / Serotyper(db, aligned=True)")
+        return self._aligned
+
+    def aligned_codes(self, a: int, i: int) -> np.ndarray:
+        """uint8 [gene length]: the row of kept record ``i`` of assembly ``a`` as codes 0..3 (acgt on the gene's strand), 4 (inside
+        an N run) and 5 (GAP), one per base of the database's gene."""
+        from kaptive_amd import _native
+
+        rows, blocks = self.aligned()
+        if not (0 <= a < len(self.sums)) or not (0 <= i < int(self.sums["n_kept"][a])):
+            raise IndexError("no such kept record")
+        return _native.aligned_codes(rows[a, i], blocks)
+
+    def aligned_tsv(self) -> bytes:
+        """The lines of the aligned table (``--aligned``; no header: ``_native.ALIGNED_HEADER``), formatted by the native library from
+        the rows (kp_format_aligned).  Contig names come from the genomes: ``genomes`` must have been given."""
+        from kaptive_amd import _native
+
+        rows, blocks = self.aligned()
+        if self.genomes is None:
+            raise ValueError("the aligned table names contigs: the batch needs its genomes")
+        first = np.concatenate([[0], np.cumsum([len(g.contigs.ids) for g in self.genomes])]).astype(np.int64)
+        names = [n for g in self.genomes for n in g.contigs.ids]
+        return _native.format_aligned(self.typer._db.genes.ids, self.ids, names, first, self.sums["n_kept"], self.kept, rows, blocks)
 
     def jsonl(self) -> bytes:
         """The JSON lines of the whole batch (``-j``), from the batch's columns and the genomes' text (``genomes`` must have

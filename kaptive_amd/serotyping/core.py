@@ -46,16 +46,19 @@ class Serotyper:
         variants: bool = False,
         breakpoints: bool = False,
         alleles: bool = False,
+        aligned: bool = False,
     ) -> None:
         """``preset`` and ``scoring_metric`` are accepted and ignored, as in the reference.
         ``aligner`` / ``protein_aligner`` replace the HIP stages; tests use them to feed recorded hits.  ``variants``: the engine
         this typer creates also leaves the variant records of the kept hits (``Engine(db, variants=True)``); ``breakpoints``: it leaves
         the breakpoint records of the kept lists (``Engine(db, breakpoints=True)``); ``alleles``: it leaves the allele digests of the
-        kept records and the locus pieces (``Engine(db, alleles=True)``)."""
+        kept records and the locus pieces (``Engine(db, alleles=True)``); ``aligned``: it leaves the aligned rows of the kept hits
+        (``Engine(db, aligned=True)``)."""
         self._db = db
         self._variants = bool(variants)
         self._breakpoints = bool(breakpoints)
         self._alleles = bool(alleles)
+        self._aligned = bool(aligned)
         self.max_other_genes = max_other_genes
         self.min_completeness = min_completeness
         self.allow_below_threshold = allow_below_threshold
@@ -93,7 +96,7 @@ class Serotyper:
             early = getattr(self, "_ctx_early", None)  # (a future of _native.Context: kaptive_amd/cli.py starts the runtime early)
             self._ctx_early = None
             self._engine = Engine(self._db, device=self._device, ctx=early.result() if early is not None else None, variants=self._variants,
-                                  breakpoints=self._breakpoints, alleles=self._alleles)
+                                  breakpoints=self._breakpoints, alleles=self._alleles, aligned=self._aligned)
         return self._engine
 
     def align(self, genome: GenomeAssembly) -> Alignments:
@@ -416,6 +419,7 @@ class MultiSerotyper:
         variants: bool = False,
         breakpoints: bool = False,
         alleles: bool = False,
+        aligned: bool = False,
     ) -> None:
         self.dbs = list(dbs)
         check_databases(self.dbs)
@@ -423,10 +427,11 @@ class MultiSerotyper:
         self._variants = bool(variants)
         self._breakpoints = bool(breakpoints)
         self._alleles = bool(alleles)
+        self._aligned = bool(aligned)
         self._engine = None
         self.serotypers = tuple(
             Serotyper(db, max_other_genes, min_completeness, allow_below_threshold, partial_edge_tolerance=partial_edge_tolerance,
-                      device=device, variants=variants, breakpoints=breakpoints, alleles=alleles) for db in self.dbs
+                      device=device, variants=variants, breakpoints=breakpoints, alleles=alleles, aligned=aligned) for db in self.dbs
         )  # fmt: skip
 
     @property
@@ -438,7 +443,7 @@ class MultiSerotyper:
             early = getattr(self, "_ctx_early", None)  # (as Serotyper.engine: a context the command line started early)
             self._ctx_early = None
             self._engine = Engine(self.dbs, device=self._device, ctx=early.result() if early is not None else None, variants=self._variants,
-                                  breakpoints=self._breakpoints, alleles=self._alleles)
+                                  breakpoints=self._breakpoints, alleles=self._alleles, aligned=self._aligned)
             for i, s in enumerate(self.serotypers):
                 s._engine = self._engine.view(i)
         return self._engine
