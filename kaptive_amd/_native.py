@@ -8,6 +8,7 @@ import ctypes as C
 import os
 import threading
 import weakref
+from collections import namedtuple
 from pathlib import Path
 
 import numpy as np
@@ -50,6 +51,18 @@ ALIGNED_ROW_DTYPE = np.dtype([("off", "<i8"), ("gene_len", "<i4"), ("covered", "
 ALIGNED_HEADER = (b"Assembly\tGene\tContig\tStart\tEnd\tStrand\tGene length\tGene start\tGene end\tCovered\tInserted\tInsertions\t"
                   b"Aligned\n")  # the columns of kp_format_aligned
 ALIGNED_GAP = 5  # the code ``aligned_codes`` gives a GAP column (0..3 bases, 4 inside an N run)
+
+# The reports derived from a reduction's kept list ("Reports derived from the kept list"), one row each: `name` (the command
+# line's option, the keyword of Engine / Serotyper / BatchTyping, the key of a chunk's outputs), the `header` line of its table, the Batch
+# method that fetches its records, the BatchTyping method that formats its lines (`tsv`), and the `noun` BatchTyping says a batch was
+# typed without (its first word names the table).
+Report = namedtuple("Report", "name header fetch tsv noun")
+REPORTS = (
+    Report("variants", VARIANTS_HEADER, "variants", "variants_tsv", "variant records"),
+    Report("breakpoints", BREAKPOINTS_HEADER, "breakpoints", "breakpoints_tsv", "breakpoint records"),
+    Report("alleles", ALLELES_HEADER, "alleles", "alleles_tsv", "allele digests"),
+    Report("aligned", ALIGNED_HEADER, "aligned", "aligned_tsv", "aligned rows"),
+)
 
 JOIN_MAX_PIECES = 8  # KP_JOIN_MAX_PIECES
 JOIN_DTYPE = np.dtype(

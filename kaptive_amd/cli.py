@@ -27,6 +27,8 @@ from pathlib import Path
 
 import numpy as np
 
+from kaptive_amd._native import REPORTS  # the tables derived from the kept lists: one row per report, every loop below goes over it
+
 FILE_SUFFIX = "kaptive_results"
 _KEEP: list = []  # FAST_EXIT: what must not be finalised one object at a time on the way out
 FAST_EXIT = False  # set by __main__: the process ends right after main() returns, so nothing needs to be torn down in order
@@ -209,11 +211,8 @@ class _TypingPipeline:
         self.marks = {"pipeline_start": time.perf_counter()}  # (KAPTIVE_AMD_CLI_TIMING: where the time before the first rows goes)
         self.want_paf = bool(getattr(args, "paf", None))  # every hit with its CIGAR: the alignment passes of this run leave them
         self.paf_cs, self.paf_eqx = bool(getattr(args, "cs", False)), bool(getattr(args, "eqx", False))  # ... and its cs string
-        self.want_variants = bool(getattr(args, "variants", None))  # the variant table of the kept hits: the reductions of this run leave the records
-        self.want_breakpoints = bool(getattr(args, "breakpoints", None))  # the breakpoint table of the kept lists, likewise
-        self.want_alleles = bool(getattr(args, "alleles", None))  # the allele table of the kept records and the locus pieces, likewise
-        self.want_aligned = bool(getattr(args, "aligned", None))  # the aligned rows of the kept hits, likewise
-        self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins", "paf", "variants", "breakpoints", "alleles", "aligned"))  # the files' text (and contig names) are kept
+        self.want = {r.name: bool(getattr(args, r.name, None)) for r in REPORTS}  # the tables of the kept lists: the reductions of this run leave their records
+        self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins", "paf", *self.want))  # the files' text (and contig names) are kept
         self.fasta_outputs = any(getattr(args, f, None) for f in ("loci", "genes", "proteins"))  # ... and result objects are built
         self.threads = max(1, args.threads or usable_cpus())  # (the cgroup's quota, not the 256 CPUs a container may see)
         # PREFETCH + 1 chunks are being parsed at any time, each by one native call: the thread budget is shared out among them
@@ -273,13 +272,11 @@ class _TypingPipeline:
                 if more:  # one pass for all of them; duplicate keywords and too many genes are refused here, before any typing
                     typer = MultiSerotyper([self.db, *more], max_other_genes=args.max_other_genes, min_completeness=args.min_completeness,
                                            allow_below_threshold=args.below_threshold, partial_edge_tolerance=args.partial_edge_tolerance,
-                                           device=device, variants=self.want_variants, breakpoints=self.want_breakpoints,
-                                           alleles=self.want_alleles, aligned=self.want_aligned)  # fmt: skip
+                                           device=device, **self.want)  # fmt: skip
                 else:
                     typer = Serotyper(self.db, max_other_genes=args.max_other_genes, min_completeness=args.min_completeness,
                                       allow_below_threshold=args.below_threshold, partial_edge_tolerance=args.partial_edge_tolerance,
-                                      device=device, variants=self.want_variants, breakpoints=self.want_breakpoints,
-                                      alleles=self.want_alleles, aligned=self.want_aligned)  # fmt: skip
+                                      device=device, **self.want)  # fmt: skip
                 typer._ctx_early = early_ctx
             self.typer = typer
             self.engine = self.typer.engine  # the context is created here, on the thread that will drive it
@@ -465,14 +462,9 @@ class _TypingPipeline:
             out = {}
             if aligned is not None:
                 out["paf"] = hits_to_paf(self.engine.view(group), bt.genomes, *aligned, cs_tag=self.paf_cs, eqx=self.paf_eqx)
-            if self.want_variants:
-                out["variants"] = bt.variants_tsv()
-            if self.want_breakpoints:
-                out["breakpoints"] = bt.breakpoints_tsv()
-            if self.want_alleles:
-                out["alleles"] = bt.alleles_tsv()
-            if self.want_aligned:
-                out["aligned"] = bt.aligned_tsv()
+            for r in REPORTS:
+                if self.want[r.name]:
+                    out[r.name] = getattr(bt, r.tsv)()
             if self.want_tsv:
                 out["tsv"] = bt.tsv()
             if getattr(args, "pha4ge", None):
@@ -710,8 +702,7 @@ class _PerDatabaseOutputs:
     genome by genome (``interleave_lines``).  The files are opened with the first chunk's outputs, which carry the
     databases' keywords."""
 
-    KINDS = (("tsv", "out"), ("pha4ge", "pha4ge"), ("json", "json"), ("paf", "paf"), ("variants", "variants"), ("breakpoints", "breakpoints"),
-             ("alleles", "alleles"), ("aligned", "aligned"))
+    KINDS = (("tsv", "out"), ("pha4ge", "pha4ge"), ("json", "json"), ("paf", "paf"), *((r.name, r.name) for r in REPORTS))
 
     def __init__(self, args: argparse.Namespace) -> None:
         self.wanted = [(key, path) for key, attr in self.KINDS if (path := getattr(args, attr, None))]
@@ -721,10 +712,7 @@ class _PerDatabaseOutputs:
     def _open(self, keywords) -> None:
         from kaptive_amd.serotyping.io import KaptiveRow, Pha4geRow
 
-        from kaptive_amd._native import ALIGNED_HEADER, ALLELES_HEADER, BREAKPOINTS_HEADER, VARIANTS_HEADER
-
-        headers = {"tsv": KaptiveRow.header(), "pha4ge": Pha4geRow.header(), "json": b"", "paf": b"", "variants": VARIANTS_HEADER,
-                   "breakpoints": BREAKPOINTS_HEADER, "alleles": ALLELES_HEADER, "aligned": ALIGNED_HEADER}
+        headers = {"tsv": KaptiveRow.header(), "pha4ge": Pha4geRow.header(), "json": b"", "paf": b"", **{r.name: r.header for r in REPORTS}}
         self.streams = {}
         for key, path in self.wanted:
             if _is_stdout(path):
@@ -788,14 +776,9 @@ def run_type(args: argparse.Namespace) -> int:
     t_check = time.perf_counter() - t_check
     from kaptive_amd.serotyping.io import KaptiveRow, Pha4geRow
 
-    if getattr(args, "db", None) and (v := getattr(args, "variants", None)) and _is_stdout(v):
-        raise ValueError("--variants with --db writes a table per database: it needs a file name, not stdout")
-    if getattr(args, "db", None) and (v := getattr(args, "breakpoints", None)) and _is_stdout(v):
-        raise ValueError("--breakpoints with --db writes a table per database: it needs a file name, not stdout")
-    if getattr(args, "db", None) and (v := getattr(args, "alleles", None)) and _is_stdout(v):
-        raise ValueError("--alleles with --db writes a table per database: it needs a file name, not stdout")
-    if getattr(args, "db", None) and (v := getattr(args, "aligned", None)) and _is_stdout(v):
-        raise ValueError("--aligned with --db writes a table per database: it needs a file name, not stdout")
+    for r in REPORTS:
+        if getattr(args, "db", None) and (v := getattr(args, r.name, None)) and _is_stdout(v):
+            raise ValueError(f"--{r.name} with --db writes a table per database: it needs a file name, not stdout")
     handles = {}
     per_db = _PerDatabaseOutputs(args) if getattr(args, "db", None) else None  # several databases: reports per database
 
@@ -813,26 +796,10 @@ def run_type(args: argparse.Namespace) -> int:
             handles["json"] = stream(j)
         if f := getattr(args, "paf", None):
             handles["paf"] = stream(f)
-        if f := getattr(args, "variants", None):
-            from kaptive_amd._native import VARIANTS_HEADER
-
-            handles["variants"] = stream(f)
-            handles["variants"].write(VARIANTS_HEADER)
-        if f := getattr(args, "breakpoints", None):
-            from kaptive_amd._native import BREAKPOINTS_HEADER
-
-            handles["breakpoints"] = stream(f)
-            handles["breakpoints"].write(BREAKPOINTS_HEADER)
-        if f := getattr(args, "alleles", None):
-            from kaptive_amd._native import ALLELES_HEADER
-
-            handles["alleles"] = stream(f)
-            handles["alleles"].write(ALLELES_HEADER)
-        if f := getattr(args, "aligned", None):
-            from kaptive_amd._native import ALIGNED_HEADER
-
-            handles["aligned"] = stream(f)
-            handles["aligned"].write(ALIGNED_HEADER)
+        for r in REPORTS:
+            if f := getattr(args, r.name, None):
+                handles[r.name] = stream(f)
+                handles[r.name].write(r.header)
     done = 0
     timing_path = os.environ.get("KAPTIVE_AMD_CLI_TIMING")  # bench.py: when each chunk's rows were written
     t_start, chunk_times, phases = time.perf_counter(), [], {}

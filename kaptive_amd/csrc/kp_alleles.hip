@@ -111,12 +111,12 @@ __global__ __launch_bounds__(AL_THREADS) void kp_alleles_kernel(KpBatchView b, c
 
 }  // namespace
 
-void kp_launch_alleles(const KpBatchView &b, const KpKeptRows &kept, const kp_piece *pieces, int piece_cap, const int64_t *piece_off, int64_t total_pieces,
-                       const uint8_t *prot, int prot_cap, kp_allele *out, uint64_t *piece_out, hipStream_t stream) {
-    const int64_t total = kept.total + total_pieces;
+void kp_launch_alleles(const KpBatchView &b, const KpKeptRows &kept, const KpPieceRows &pieces, const uint8_t *prot, int prot_cap, kp_allele *out,
+                       uint64_t *piece_out, hipStream_t stream) {
+    const int64_t total = kept.total + pieces.total;
     if (b.n_asm <= 0 || total <= 0) return;
     constexpr int per_block = AL_THREADS / AL_WAVE;
     const unsigned blocks = (unsigned)std::min<int64_t>((total + per_block - 1) / per_block, 2048);
-    hipLaunchKernelGGL(kp_alleles_kernel, dim3(blocks), dim3(AL_THREADS), 0, stream, b, kept.kept, kept.kept_cap, kept.kept_off, kept.total, pieces, piece_cap,
-                       piece_off, total_pieces, prot, prot_cap, out, piece_out);
+    hipLaunchKernelGGL(kp_alleles_kernel, dim3(blocks), dim3(AL_THREADS), 0, stream, b, kept.kept, kept.kept_cap, kept.kept_off, kept.total, pieces.pieces,
+                       pieces.piece_cap, pieces.piece_off, pieces.total, prot, prot_cap, out, piece_out);
 }

@@ -22,6 +22,58 @@ struct KpTypingGroup {
     int max_db_prot_len = 0;
 };
 
+// Reports derived from a finished reduction's kept list ("Reports derived from the kept list"): each is made on first
+// request after the reduction and is the run's until the next kp_batch_reduce or until the hit table is rewritten
+// (KpTypingRun::invalidate_derived); nothing of a report is allocated before somebody asks for it.
+struct KpRowLayout {  // the kept rows and the piece rows of every assembly back to back: min(max(count, 0), cap) of each
+    bool valid = false;
+    size_t n_asm = 0;
+    std::vector<int64_t> h_off;  // kept_off[n_asm + 1], then piece_off[n_asm + 1]: rows before every assembly
+    DevBuf<int64_t> d_off;       // the same, uploaded once per reduction
+    const int64_t *kept_off() const { return h_off.data(); }
+    const int64_t *piece_off() const { return h_off.data() + n_asm + 1; }
+    int64_t kept_total() const { return h_off.empty() ? 0 : h_off[n_asm]; }
+    int64_t piece_total() const { return h_off.empty() ? 0 : h_off.back(); }
+};
+struct KpKeptSrcState {  // kp_launch_kept_locate: the variant records and the aligned rows both read it, whichever is asked for first makes it
+    bool valid = false;
+    DevBuf<int64_t> d_src;  // [kept rows] the row of the finished hit table behind every kept row
+};
+struct KpVariantsState {  // kp_variants.hip; only where the pass ran with the `variants` option
+    bool valid = false;
+    uint64_t cap = 0;            // records d_rec was sized for
+    int64_t total = 0;           // records of all kept hits
+    std::vector<int64_t> h_off;  // [kept rows + 1] first record of every kept hit
+    DevBuf<int64_t> d_off;
+    DevBuf<uint32_t> d_cnt;
+    DevBuf<kp_variant> d_rec;
+    KpPerHit<kp_variant> view() const { return {.cnt = d_cnt.p, .off = d_off.p, .data = d_rec.p, .cap = (int64_t)cap}; }
+};
+struct KpAlignedState {  // kp_aligned.hip; only where the pass ran with the `aligned` option
+    bool valid = false;
+    int64_t n_blocks = 0;                // blocks of all rows: what d_blocks holds, exactly
+    std::vector<kp_aligned_row> h_rows;  // one per kept row, back to back
+    DevBuf<uint32_t> d_cnt;
+    DevBuf<int64_t> d_off;               // [kept rows + 1] first block of every row
+    DevBuf<uint64_t> d_blocks;
+    DevBuf<kp_aligned_row> d_rows;
+};
+struct KpBreakpointsState {  // kp_breakpoints.hip
+    bool valid = false;
+    std::vector<int64_t> h_off;          // [n_asm + 1] breakpoint records before every assembly
+    DevBuf<int64_t> d_off;
+    DevBuf<uint32_t> d_cnt;              // [n_asm]
+    DevBuf<kp_breakpoint> d_tmp, d_rec;  // one record per kept row each: per assembly from its first row, then back to back
+};
+struct KpAllelesState {  // kp_alleles.hip
+    bool valid = false;
+    std::vector<kp_allele> h_rec;   // one per kept row, back to back
+    std::vector<uint64_t> h_piece;  // one per piece row, back to back
+    DevBuf<kp_allele> d_rec;
+    DevBuf<uint64_t> d_piece;
+};
+struct KpDerived { KpRowLayout layout; KpKeptSrcState src; KpVariantsState var; KpAlignedState aln; KpBreakpointsState bp; KpAllelesState al; };
+
 // Reduction state of one (batch, typing group): the group's hits (copied out of the batch's hit table with gene indices
 // rebased) and everything score / reduce / typing produce for it.
 struct KpTypingRun {
@@ -53,48 +105,17 @@ struct KpTypingRun {
     bool sums_valid = false;  // h_sums / max_kept / max_pieces belong to the most recent reduction
     std::vector<KpAsmSummary> h_sums;
     int32_t max_kept = 1, max_pieces = 1;
-    // variant records of the kept hits (kp_variants.hip), only where the pass ran with the `variants` option: nothing below is
-    // allocated otherwise.  Made on first request after a reduction; theirs until the next reduction or until the hit table goes.
-    bool var_valid = false;
-    bool src_valid = false;            // h_kept_off / d_kept_off / d_var_src belong to the most recent reduction (kp_launch_kept_locate): the
-                                       // variant records and the aligned rows both read them, whichever is asked for first makes them
-    uint64_t var_cap = 0;              // records d_var was sized for
-    int64_t var_total = 0;             // records of all kept hits
-    std::vector<int64_t> h_kept_off;   // [n_asm + 1] kept records before every assembly
-    std::vector<int64_t> h_var_off;    // [kept records + 1] first record of every kept hit
-    DevBuf<int64_t> d_kept_off, d_var_src, d_var_off;
-    DevBuf<uint32_t> d_var_cnt;
-    DevBuf<kp_variant> d_var;
-    KpKeptRows kept_rows(int32_t gene_lo) const {
-        return {.kept = d_kept.p, .kept_cap = kept_cap, .kept_off = d_kept_off.p, .total = h_kept_off.empty() ? 0 : h_kept_off.back(), .gene_lo = gene_lo};
+    KpDerived derived;  // the reports made from the kept list, on request (above)
+    void invalidate_derived() {  // the kept list they describe is about to be replaced: flags only, every buffer stays (a settled context allocates nothing)
+        derived.layout.valid = derived.src.valid = derived.var.valid = derived.aln.valid = derived.bp.valid = derived.al.valid = false;
     }
-    KpPerHit<kp_variant> variants() const { return {.cnt = d_var_cnt.p, .off = d_var_off.p, .data = d_var.p, .cap = (int64_t)var_cap}; }
-    // breakpoint records of the kept list (kp_breakpoints.hip): made on first request after a reduction, theirs until the next
-    // reduction or until the hit table goes; nothing below is allocated before somebody asks.
-    bool bp_valid = false;
-    std::vector<int64_t> h_bp_kept_off;  // [n_asm + 1] kept records before every assembly
-    std::vector<int64_t> h_bp_off;       // [n_asm + 1] breakpoint records before every assembly
-    DevBuf<int64_t> d_bp_kept_off, d_bp_off;
-    DevBuf<uint32_t> d_bp_cnt;           // [n_asm]
-    DevBuf<kp_breakpoint> d_bp_tmp, d_bp;  // one record per kept row each: per assembly from its first row, then back to back
-    // allele digests of the kept records and the pieces (kp_alleles.hip): made on first request after a reduction, theirs until the
-    // next reduction or until the hit table goes; nothing below is allocated before somebody asks.
-    bool al_valid = false;
-    std::vector<int64_t> h_al_off;        // kept_off[n_asm + 1], then piece_off[n_asm + 1]: rows before every assembly
-    std::vector<kp_allele> h_al;          // one per kept row, back to back
-    std::vector<uint64_t> h_al_piece;     // one per piece row, back to back
-    DevBuf<int64_t> d_al_off;
-    DevBuf<kp_allele> d_al;
-    DevBuf<uint64_t> d_al_piece;
-    // aligned rows of the kept hits (kp_aligned.hip), only where the pass ran with the `aligned` option: nothing below is allocated
-    // otherwise.  Made on first request after a reduction; theirs until the next reduction or until the hit table goes.
-    bool aln_valid = false;
-    int64_t aln_blocks = 0;                  // blocks of all rows: what d_aln_blocks holds, exactly
-    std::vector<kp_aligned_row> h_aln_rows;  // one per kept row, back to back
-    DevBuf<uint32_t> d_aln_cnt;
-    DevBuf<int64_t> d_aln_off;               // [kept rows + 1] first block of every row
-    DevBuf<uint64_t> d_aln_blocks;
-    DevBuf<kp_aligned_row> d_aln_rows;
+    // the only places the views of the kept and the piece rows are built (valid once derived.layout is)
+    KpKeptRows kept_rows(int32_t gene_lo) const {
+        return {.kept = d_kept.p, .kept_cap = kept_cap, .kept_off = derived.layout.d_off.p, .total = derived.layout.kept_total(), .gene_lo = gene_lo};
+    }
+    KpPieceRows piece_rows() const {
+        return {.pieces = d_pieces.p, .piece_cap = piece_cap, .piece_off = derived.layout.d_off.p + derived.layout.n_asm + 1, .total = derived.layout.piece_total()};
+    }
     // d_pairs: the pairs of the protein DP, one slot per kept row: q_off, q_len, t_off, t_len [slots each], then pair_base [n_asm], n_pairs [1]
     size_t slots() const { return n_asm * (size_t)kept_cap; }
     size_t pairs_len() const { return 4 * slots() + n_asm + 1; }
@@ -250,7 +271,7 @@ struct KpWork : KpPassCaps {
     KpHitRows hit_rows() const { return {.hit_off = d_cig_hit_off.p, .total = hit_off[n_asm]}; }
     KpPerHit<uint32_t> cigars() const { return {.cnt = d_cig_cnt.p, .off = d_cig_off.p, .data = d_cig_ops.p, .cap = (int64_t)cigar_cap}; }
     KpPerHit<char> cs() const { return {.cnt = d_cs_cnt.p, .off = d_cs_off.p, .data = d_cs_bytes.p, .cap = (int64_t)cs_cap}; }
-    void reset_runs() { for (auto &r : runs) if (r) r->split = r->scored = r->reduced = r->sums_valid = r->var_valid = r->src_valid = r->aln_valid = r->bp_valid = r->al_valid = false; }  // their hit table is about to be rewritten
+    void reset_runs() { for (auto &r : runs) if (r) { r->split = r->scored = r->reduced = r->sums_valid = false; r->invalidate_derived(); } }  // their hit table is about to be rewritten
 };
 
 #define KP_INPUT_POOL 16  /* recycled device copies of batch inputs: uploads run several shards ahead of the passes that read them */

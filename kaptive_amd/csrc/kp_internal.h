@@ -261,6 +261,7 @@ struct KpKeptRows {  // the kept records of a finished reduction, row by row: de
     const int64_t *kept_off; int64_t total;
     int32_t gene_lo;  // first gene of the typing group: kept records index genes relative to it, the hit table does not
 };
+struct KpPieceRows { const kp_piece *pieces; int piece_cap; const int64_t *piece_off; int64_t total; };  // its locus pieces likewise: device piece_off[n_asm + 1]
 struct KpReduceTables {  // what the reduction, the protein DP of its kept hits and the gene states share (types: kp_reduce_core.h)
     const int32_t *best;
     uint64_t *keys;
@@ -358,10 +359,10 @@ void kp_launch_aligned_emit(const KpBatchView &b, const KpGenes &genes, const Kp
 void kp_launch_breakpoints(const KpBatchView &b, const KpKeptRows &kept, int max_kept, kp_breakpoint *tmp, uint32_t *cnt, int64_t *bp_off,
                            kp_breakpoint *out, hipStream_t stream);
 // kp_alleles.hip (after a reduction, when its allele digests are first asked for): the digests (kp_spec.h, ALLELES) of every kept row
-// (out[kept.total], rows as kept.kept_off lists them) and of every piece row (piece_out[total_pieces], rows as piece_off[n_asm + 1]
+// (out[kept.total], rows as kept.kept_off lists them) and of every piece row (piece_out[pieces.total], rows as pieces.piece_off
 // lists them) -- a wave per row; prot: the reduction's protein buffers, prot_cap bytes per assembly.
-void kp_launch_alleles(const KpBatchView &b, const KpKeptRows &kept, const kp_piece *pieces, int piece_cap, const int64_t *piece_off, int64_t total_pieces,
-                       const uint8_t *prot, int prot_cap, kp_allele *out, uint64_t *piece_out, hipStream_t stream);
+void kp_launch_alleles(const KpBatchView &b, const KpKeptRows &kept, const KpPieceRows &pieces, const uint8_t *prot, int prot_cap, kp_allele *out,
+                       uint64_t *piece_out, hipStream_t stream);
 // kp_reduce.hip: assembly a's hits with gene in [gene_lo, gene_hi) (one run: hits are sorted by gene) -> out rows, gene
 // indices relative to gene_lo; out.count[a] = how many
 void kp_launch_hit_split(const KpHitTable &hits, int32_t gene_lo, int32_t gene_hi, const KpHitTable &out, int32_t n_asm, hipStream_t stream);

@@ -55,6 +55,11 @@ struct Out {
 };
 
 inline bool alive(const kp_kept &k) { return (k.flags & KP_F_SPURIOUS) == 0; }
+template <class Off>  // (the name tables of the rows have 32-bit offsets, the others 64-bit ones)
+inline void put_name(Out &o, const char *names, const Off *off, int64_t i) { o.put(names + off[i], off[i + 1] - off[i]); }
+// a record's gene is one of the database's and its contig one of the `nc` contigs of its assembly
+template <class Rec>
+inline bool gene_contig_ok(const Rec &r, int32_t n_genes, int64_t nc) { return r.gene >= 0 && r.gene < n_genes && r.contig >= 0 && r.contig < nc; }
 
 // how many distinct genes the selected hits have (np.unique(gene_indices[mask]) in the reference)
 template <class Pred>
@@ -77,7 +82,7 @@ void details(Out &o, const kp_row_tables *t, const kp_kept *k, int n, Pred pred)
         if (!alive(k[i]) || !pred(k[i])) continue;
         if (!first) o.put(';');
         first = false;
-        o.put(t->gene_ids + t->gene_id_off[k[i].gene], t->gene_id_off[k[i].gene + 1] - t->gene_id_off[k[i].gene]);
+        put_name(o, t->gene_ids, t->gene_id_off, k[i].gene);
         o.put(',');
         o.pct_f32(k[i].pident);
         o.put(',');
@@ -107,9 +112,9 @@ extern "C" int64_t kp_format_rows(const kp_row_tables *t, int32_t n_asm, const k
         const int n = s.n_kept;
         const int best = c->best_locus[a];
         o.put(t->prefix, t->prefix_len);  // Kaptive version, database name, database version (tab-terminated)
-        o.put(c->asm_ids + c->asm_id_off[a], c->asm_id_off[a + 1] - c->asm_id_off[a]); o.put('\t');
-        o.put(t->locus_names + t->locus_name_off[best], t->locus_name_off[best + 1] - t->locus_name_off[best]); o.put('\t');
-        o.put(c->phenotypes + c->phenotype_off[a], c->phenotype_off[a + 1] - c->phenotype_off[a]); o.put('\t');
+        put_name(o, c->asm_ids, c->asm_id_off, a); o.put('\t');
+        put_name(o, t->locus_names, t->locus_name_off, best); o.put('\t');
+        put_name(o, c->phenotypes, c->phenotype_off, a); o.put('\t');
         o.lit(c->typeable[a] ? "Typeable" : "Untypeable"); o.put('\t');
         static const char symbols[] = "?+-*!";  // SerotypingProblem.to_symbols (models.py:82-92)
         for (int bit = 0; bit < 5; ++bit)
@@ -135,7 +140,7 @@ extern "C" int64_t kp_format_rows(const kp_row_tables *t, int32_t n_asm, const k
                 if (!((s.missing_mask[j >> 6] >> (j & 63)) & 1ull)) continue;
                 if (!first) o.put(';');
                 first = false;
-                o.put(t->gene_ids + t->gene_id_off[g0 + j], t->gene_id_off[g0 + j + 1] - t->gene_id_off[g0 + j]);
+                put_name(o, t->gene_ids, t->gene_id_off, g0 + j);
             }
         }
         o.put('\t');
@@ -221,16 +226,16 @@ int64_t format_paf(const kp_paf_tables *t, int32_t n_asm, const kp_hit *hits, co
         const int64_t c0 = t->asm_first_ctg[a], nc = t->asm_first_ctg[a + 1] - c0;
         for (int64_t i = hit_off[a]; i < hit_off[a + 1]; ++i) {
             const kp_hit &h = hits[i];
-            if (h.gene < 0 || h.gene >= t->n_genes || h.contig < 0 || h.contig >= nc) return KP_EINVAL;
+            if (!gene_contig_ok(h, t->n_genes, nc)) return KP_EINVAL;
             const int64_t c = c0 + h.contig;
             if (cigar_off[i + 1] < cigar_off[i] || (cigar_off[i + 1] > cigar_off[i] && !ops)) return KP_EINVAL;
             if (flags && (cs_off[i + 1] < cs_off[i] || (cs_off[i + 1] > cs_off[i] && !cs))) return KP_EINVAL;
-            o.put(t->gene_names + t->gene_name_off[h.gene], t->gene_name_off[h.gene + 1] - t->gene_name_off[h.gene]); o.put('\t');
+            put_name(o, t->gene_names, t->gene_name_off, h.gene); o.put('\t');
             put_i(o, t->gene_len[h.gene]); o.put('\t');
             put_i(o, h.q_start); o.put('\t');
             put_i(o, h.q_end); o.put('\t');
             o.put(h.strand < 0 ? '-' : '+'); o.put('\t');
-            o.put(t->ctg_names + t->ctg_name_off[c], t->ctg_name_off[c + 1] - t->ctg_name_off[c]); o.put('\t');
+            put_name(o, t->ctg_names, t->ctg_name_off, c); o.put('\t');
             put_i(o, t->ctg_len[c]); o.put('\t');
             put_i(o, h.t_start); o.put('\t');
             put_i(o, h.t_end); o.put('\t');
@@ -282,13 +287,13 @@ extern "C" int64_t kp_format_variants(const kp_variant_tables *t, int32_t n_asm,
             const kp_variant &v = variants[i];
             if (v.kept < 0 || v.kept >= kept_stride || v.kind > KP_VAR_DEL) return KP_EINVAL;
             const kp_kept &k = kept[(size_t)a * (size_t)kept_stride + (size_t)v.kept];
-            if (k.gene < 0 || k.gene >= t->n_genes || k.contig < 0 || k.contig >= nc) return KP_EINVAL;
+            if (!gene_contig_ok(k, t->n_genes, nc)) return KP_EINVAL;
             const int64_t c = c0 + k.contig;
-            o.put(t->asm_names + t->asm_name_off[a], t->asm_name_off[a + 1] - t->asm_name_off[a]); o.put('\t');
-            o.put(t->ctg_names + t->ctg_name_off[c], t->ctg_name_off[c + 1] - t->ctg_name_off[c]); o.put('\t');
+            put_name(o, t->asm_names, t->asm_name_off, a); o.put('\t');
+            put_name(o, t->ctg_names, t->ctg_name_off, c); o.put('\t');
             put_i(o, (long long)v.t_pos + 1); o.put('\t');
             o.put(k.strand < 0 ? '-' : '+'); o.put('\t');
-            o.put(t->gene_names + t->gene_name_off[k.gene], t->gene_name_off[k.gene + 1] - t->gene_name_off[k.gene]); o.put('\t');
+            put_name(o, t->gene_names, t->gene_name_off, k.gene); o.put('\t');
             put_i(o, (long long)v.q_pos + 1); o.put('\t');
             o.lit(v.kind == KP_VAR_SNV ? "snv" : (v.kind == KP_VAR_INS ? "ins" : "del")); o.put('\t');
             put_i(o, v.len); o.put('\t');
@@ -327,7 +332,7 @@ extern "C" int64_t kp_format_breakpoints(const kp_variant_tables *t, int32_t n_a
             const kp_breakpoint &r = bps[i];
             if (r.kept_a < 0 || r.kept_a >= kept_stride || r.kept_b < 0 || r.kept_b >= kept_stride || r.kind > KP_BP_CONTIGS) return KP_EINVAL;
             const kp_kept &ka = kept[(size_t)a * (size_t)kept_stride + (size_t)r.kept_a], &kb = kept[(size_t)a * (size_t)kept_stride + (size_t)r.kept_b];
-            if (ka.gene < 0 || ka.gene >= t->n_genes || ka.contig < 0 || ka.contig >= nc || kb.contig < 0 || kb.contig >= nc) return KP_EINVAL;
+            if (!gene_contig_ok(ka, t->n_genes, nc) || kb.contig < 0 || kb.contig >= nc) return KP_EINVAL;
             const char *event;
             if (r.kind == KP_BP_COLLINEAR) event = r.t_gap > 0 ? (r.q_gap > 0 ? "replacement" : "insertion") : (r.q_gap > 0 ? "deletion" : "overlap");
             else if (r.kind == KP_BP_INVERTED) event = "inversion";
@@ -335,15 +340,15 @@ extern "C" int64_t kp_format_breakpoints(const kp_variant_tables *t, int32_t n_a
             else event = (r.edge_a <= edge_tolerance && r.edge_b <= edge_tolerance) ? "contig_break" : "translocation";
             const bool fa = ka.strand >= 0, fb = kb.strand >= 0;
             const int64_t ca = c0 + ka.contig, cb = c0 + kb.contig;
-            o.put(t->asm_names + t->asm_name_off[a], t->asm_name_off[a + 1] - t->asm_name_off[a]); o.put('\t');
-            o.put(t->gene_names + t->gene_name_off[ka.gene], t->gene_name_off[ka.gene + 1] - t->gene_name_off[ka.gene]); o.put('\t');
+            put_name(o, t->asm_names, t->asm_name_off, a); o.put('\t');
+            put_name(o, t->gene_names, t->gene_name_off, ka.gene); o.put('\t');
             o.lit(event); o.put('\t');
             put_i(o, ka.q_end); o.put('\t');
             put_i(o, r.q_gap); o.put('\t');
-            o.put(t->ctg_names + t->ctg_name_off[ca], t->ctg_name_off[ca + 1] - t->ctg_name_off[ca]); o.put('\t');
+            put_name(o, t->ctg_names, t->ctg_name_off, ca); o.put('\t');
             put_i(o, fa ? (long long)ka.t_end : (long long)ka.t_start + 1); o.put('\t');  // pos_a + 1
             o.put(fa ? '+' : '-'); o.put('\t');
-            o.put(t->ctg_names + t->ctg_name_off[cb], t->ctg_name_off[cb + 1] - t->ctg_name_off[cb]); o.put('\t');
+            put_name(o, t->ctg_names, t->ctg_name_off, cb); o.put('\t');
             put_i(o, fb ? (long long)kb.t_start + 1 : (long long)kb.t_end); o.put('\t');  // pos_b + 1
             o.put(fb ? '+' : '-'); o.put('\t');
             if (r.kind == KP_BP_COLLINEAR) put_i(o, r.t_gap); else o.put('.');
@@ -398,16 +403,16 @@ extern "C" int64_t kp_format_alleles(const kp_allele_tables *t, int32_t n_asm, c
             const kp_kept &k = kept[(size_t)a * (size_t)kept_stride + (size_t)i];
             const kp_allele &d = alleles[(size_t)a * (size_t)kept_stride + (size_t)i];
             if (!alive(k)) continue;
-            if (k.gene < 0 || k.gene >= t->names.n_genes || k.contig < 0 || k.contig >= nc || k.state < KP_STATE_NORMAL || k.state > KP_STATE_NOVEL) return KP_EINVAL;
+            if (!gene_contig_ok(k, t->names.n_genes, nc) || k.state < KP_STATE_NORMAL || k.state > KP_STATE_NOVEL) return KP_EINVAL;
             const int64_t c = c0 + k.contig;
-            o.put(t->names.asm_names + t->names.asm_name_off[a], t->names.asm_name_off[a + 1] - t->names.asm_name_off[a]); o.put('\t');
-            o.put(t->locus_names + t->locus_name_off[best], t->locus_name_off[best + 1] - t->locus_name_off[best]); o.put('\t');
+            put_name(o, t->names.asm_names, t->names.asm_name_off, a); o.put('\t');
+            put_name(o, t->locus_names, t->locus_name_off, best); o.put('\t');
             if (np) put_hex(o, locus); else o.put('.');
             o.put('\t');
-            o.put(t->names.gene_names + t->names.gene_name_off[k.gene], t->names.gene_name_off[k.gene + 1] - t->names.gene_name_off[k.gene]); o.put('\t');
+            put_name(o, t->names.gene_names, t->names.gene_name_off, k.gene); o.put('\t');
             o.lit((k.flags & KP_F_EXPECTED) ? "expected" : ((k.flags & KP_F_EXTRA) ? "extra" : "other"));
             o.lit((k.flags & KP_F_INSIDE) ? "_in" : "_out"); o.put('\t');
-            o.put(t->names.ctg_names + t->names.ctg_name_off[c], t->names.ctg_name_off[c + 1] - t->names.ctg_name_off[c]); o.put('\t');
+            put_name(o, t->names.ctg_names, t->names.ctg_name_off, c); o.put('\t');
             put_i(o, (long long)k.t_start + 1); o.put('\t');
             put_i(o, k.t_end); o.put('\t');
             o.put(k.strand < 0 ? '-' : '+'); o.put('\t');
@@ -439,13 +444,13 @@ extern "C" int64_t kp_format_aligned(const kp_variant_tables *t, int32_t n_asm, 
             const kp_kept &k = kept[(size_t)a * (size_t)kept_stride + (size_t)i];
             const kp_aligned_row &r = rows[(size_t)a * (size_t)kept_stride + (size_t)i];
             if (!alive(k)) continue;
-            if (k.gene < 0 || k.gene >= t->n_genes || k.contig < 0 || k.contig >= nc) return KP_EINVAL;
+            if (!gene_contig_ok(k, t->n_genes, nc)) return KP_EINVAL;
             const int64_t nb = r.gene_len < 0 ? -1 : ((int64_t)r.gene_len + 15) / 16;
             if (nb < 0 || r.off < 0 || r.off > n_blocks || nb > n_blocks - r.off) return KP_EINVAL;
             const int64_t c = c0 + k.contig;
-            o.put(t->asm_names + t->asm_name_off[a], t->asm_name_off[a + 1] - t->asm_name_off[a]); o.put('\t');
-            o.put(t->gene_names + t->gene_name_off[k.gene], t->gene_name_off[k.gene + 1] - t->gene_name_off[k.gene]); o.put('\t');
-            o.put(t->ctg_names + t->ctg_name_off[c], t->ctg_name_off[c + 1] - t->ctg_name_off[c]); o.put('\t');
+            put_name(o, t->asm_names, t->asm_name_off, a); o.put('\t');
+            put_name(o, t->gene_names, t->gene_name_off, k.gene); o.put('\t');
+            put_name(o, t->ctg_names, t->ctg_name_off, c); o.put('\t');
             put_i(o, (long long)k.t_start + 1); o.put('\t');
             put_i(o, k.t_end); o.put('\t');
             o.put(k.strand < 0 ? '-' : '+'); o.put('\t');

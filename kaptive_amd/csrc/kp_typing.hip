@@ -160,11 +160,7 @@ int kp_batch_reduce(kp_ctx *ctx, kp_batch *b, const int32_t *best_locus, const k
     if (rc) return rc;
     R.reduced = true;
     R.sums_valid = false;
-    R.var_valid = false;  // (the variant records describe a kept list: the one that is about to be replaced)
-    R.src_valid = false;  // (... and so do the hit rows behind its records
-    R.aln_valid = false;  //  and the aligned rows)
-    R.bp_valid = false;   // (the breakpoint records likewise)
-    R.al_valid = false;   // (... and the allele digests)
+    R.invalidate_derived();  // (every report describes a kept list: the one that is about to be replaced)
     return KP_OK;
 }
 
@@ -251,66 +247,106 @@ int kp_batch_typing(kp_ctx *ctx, kp_batch *b, kp_asm_summary *summaries, kp_kept
     return KP_OK;
 }
 
-// ---- the hit behind every kept record (kp_variants.hip: kp_launch_kept_locate) ----------------------------------------------------
-// What the variant records and the aligned rows both start from: the kept rows laid out back to back (h_kept_off / d_kept_off) and,
-// in d_var_src, the row of the finished hit table behind each -- enqueued once per reduction, by whichever of the two is asked for
-// first, on the reduction's stream behind the kernels that finalised the kept list.  The caller has fetched the summaries.
+// ---- reports derived from the kept list ("Reports derived from the kept list"; state: KpDerived, kp_host.h) ----------------
+// What every entry point of a report answers once its own arguments have passed ("bad arguments", KP_EINVAL), checked in this order:
+//                                        variants (_variant_offsets, _variants)  aligned (_size, _rows, _blocks)  breakpoints (_offsets, _breakpoints)  alleles
+//   1 no work set (never aligned, or     KP_ESTATE, finalised_work's text        KP_EINVAL, NO_ALIGNED            KP_EINVAL, NO_BREAKPOINTS              KP_EINVAL, NO_ALLELES
+//     displaced) / pass not waited for   (kp_align.hip), one per case
+//   2 pass without the report's option   KP_EINVAL, NO_VARIANTS                  KP_EINVAL, NO_ALIGNED            (needs no option: a table that kp_batch_set_hits
+//     (w->var_on / w->aln_on), or ops                                                                             put in place serves as well)
+//     gone (!w->cigar_valid)
+//   3 no typing group                    as 4 (such a run is never reduced)      KP_EINVAL, NO_ALIGNED            KP_EINVAL, NO_BREAKPOINTS              KP_EINVAL, NO_ALLELES
+//   4 group's run not reduced since the  KP_ESTATE, "kp_batch_reduce has not     KP_EINVAL, ALIGNED_NOT_REDUCED   KP_EINVAL, NO_BREAKPOINTS              KP_EINVAL, NO_ALLELES
+//     hit table was made                 been called"
+// The variant records answer KP_ESTATE where a call is missing, as kp_batch_typing does; the later reports KP_EINVAL with their own text
+// throughout.  kp_batch_set_hits clears cigar_valid and resets the runs: 2 for variants and aligned, 4 for the others.  Then the device is
+// made current and the summaries are fetched (the reduction run again where a buffer overflowed): their errors pass through.  `code`: that
+// of 1 and 4; `no_records`: the text of 1-3 under KP_EINVAL; `not_reduced`: the text of 4; `option`: the flag of 2, or null.  The run: *R_out.
+static const char *const NO_VARIANTS = "this batch has no variant records (aligned without the variants option, or its hit table was replaced)";
+static const char *const NO_ALIGNED = "this batch has no aligned rows (aligned without the aligned option, or its hit table was replaced)";
+static const char *const ALIGNED_NOT_REDUCED = "this batch has no aligned rows: kp_batch_reduce has not run for this group since its hit table was made";
+static const char *const NO_BREAKPOINTS = "this batch has no breakpoint records: kp_batch_reduce has not run for this group since its hit table was made";
+static const char *const NO_ALLELES = "this batch has no allele digests: kp_batch_reduce has not run for this group since its hit table was made";
+
+static int report_run(kp_ctx *ctx, kp_batch *b, int code, const char *no_records, const char *not_reduced, bool KpWork::*option, KpWork **w_out, KpTypingRun **R_out) {
+    if (!ctx || !b || b->ctx != ctx) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpWork *w = code == KP_ESTATE ? finalised_work(ctx, b) : work_of(b);
+    if (!w) return code == KP_ESTATE ? KP_ESTATE : kp_fail(ctx, KP_EINVAL, no_records);
+    if (!w->finalised || (option && (!(w->*option) || !w->cigar_valid))) return kp_fail(ctx, KP_EINVAL, no_records);
+    if (code == KP_EINVAL && !typing_group(ctx, b)) return kp_fail(ctx, KP_EINVAL, no_records);
+    KpTypingRun &R = typing_run(w, b->group);
+    if (!R.reduced) return kp_fail(ctx, code, not_reduced);
+    *w_out = w; *R_out = &R;
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    return fetch_summaries(ctx, b, w);
+}
+
+// The rows of the reduction laid out back to back, from the summaries the caller has fetched and the caps of the reduction's last run: made
+// and -- where there is a row -- uploaded once per reduction, for the report that asks first, on the reduction's stream.
+static int ensure_layout(kp_ctx *ctx, KpTypingRun &R, size_t n_asm) {
+    KpRowLayout &L = R.derived.layout;
+    if (L.valid) return KP_OK;
+    L.n_asm = n_asm;
+    L.h_off.assign(2 * (n_asm + 1), 0);
+    int64_t *const kept_off = L.h_off.data(), *const piece_off = kept_off + n_asm + 1;
+    for (size_t a = 0; a < n_asm; ++a) {
+        kept_off[a + 1] = kept_off[a] + std::min(std::max(R.h_sums[a].n_kept, 0), R.kept_cap);
+        piece_off[a + 1] = piece_off[a] + std::min(std::max(R.h_sums[a].n_pieces, 0), R.piece_cap);
+    }
+    if (L.kept_total() + L.piece_total() > 0)
+        if (int rc = upload(ctx, L.d_off, L.h_off.data(), L.h_off.size(), R.stream)) return rc;
+    L.valid = true;
+    return KP_OK;
+}
+
+// the hit behind every kept record (kp_variants.hip: kp_launch_kept_locate): what the variant records and the aligned rows both start
+// from, enqueued once per reduction by whichever of the two is asked for first
 static int ensure_kept_src(kp_ctx *ctx, kp_batch *b, KpWork *w, KpTypingRun &R) {
-    if (R.src_valid) return KP_OK;
-    const size_t n_asm = (size_t)b->n_asm;
-    R.h_kept_off.assign(n_asm + 1, 0);
-    for (size_t a = 0; a < n_asm; ++a) R.h_kept_off[a + 1] = R.h_kept_off[a] + std::min(std::max(R.h_sums[a].n_kept, 0), R.kept_cap);
-    const int64_t total = R.h_kept_off[n_asm];
+    if (int rc = ensure_layout(ctx, R, (size_t)b->n_asm)) return rc;
+    KpKeptSrcState &S = R.derived.src;
+    if (S.valid) return KP_OK;
+    const int64_t total = R.derived.layout.kept_total();
     if (total > 0) {
-        KP_HIP_CHECK(ctx, R.d_var_src.reserve((size_t)total));
-        if (int rc = upload(ctx, R.d_kept_off, R.h_kept_off.data(), n_asm + 1, R.stream)) return rc;
-        kp_launch_kept_locate(b->view, w->hits(), w->hit_rows(), R.kept_rows(typing_group(ctx, b)->gene_lo), R.d_var_src.p, R.stream);
+        KP_HIP_CHECK(ctx, S.d_src.reserve((size_t)total));
+        kp_launch_kept_locate(b->view, w->hits(), w->hit_rows(), R.kept_rows(typing_group(ctx, b)->gene_lo), S.d_src.p, R.stream);
         KP_HIP_CHECK(ctx, hipGetLastError());
     }
-    R.src_valid = true;
+    S.valid = true;
     return KP_OK;
 }
 
 // ---- variant records of the kept hits (kp_variants.hip; kp_spec.h, VARIANTS) ------------------------------------------------------
-static const char *const NO_VARIANTS = "this batch has no variant records (aligned without the variants option, or its hit table was replaced)";
-
-// The records of the batch's current group, made on first request after its reduction: the hit behind every kept record located and
-// its records counted, the counts scanned, the records stored -- on the reduction's stream, behind the kernels that finalised the
-// kept list.  The buffer follows the policy of kp_caps.h; where it was too small only the storing kernel runs again: counts and
+// The records of the batch's current group: the hit behind every kept record located and its records counted, the counts scanned, the
+// records stored.  The buffer follows the policy of kp_caps.h; where it was too small only the storing kernel runs again: counts and
 // offsets are exact whatever the buffer held.  No alignment pass, no reduction and no kp_batch_stats counter is touched.
 static int ensure_variants(kp_ctx *ctx, kp_batch *b, KpTypingRun **R_out) {
-    KpWork *w = finalised_work(ctx, b);
-    if (!w) return KP_ESTATE;
-    if (!w->var_on || !w->cigar_valid) return kp_fail(ctx, KP_EINVAL, NO_VARIANTS);
-    KpTypingRun *Rp = reduced_run(ctx, b, &w);
-    if (!Rp) return KP_ESTATE;
-    KpTypingRun &R = *Rp;
-    *R_out = Rp;
-    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (int rc = fetch_summaries(ctx, b, w)) return rc;
-    if (R.var_valid) return KP_OK;
+    KpWork *w = nullptr;
+    if (int rc = report_run(ctx, b, KP_ESTATE, NO_VARIANTS, "kp_batch_reduce has not been called", &KpWork::var_on, &w, R_out)) return rc;
+    KpTypingRun &R = **R_out;
+    KpVariantsState &V = R.derived.var;
+    if (V.valid) return KP_OK;
     if (int rc = ensure_kept_src(ctx, b, w, R)) return rc;
-    const int64_t total = R.h_kept_off.back();
-    R.h_var_off.assign((size_t)total + 1, 0);
-    R.var_total = 0;
+    const int64_t total = R.derived.layout.kept_total();
+    V.h_off.assign((size_t)total + 1, 0);
+    V.total = 0;
     if (total > 0) {
-        R.var_cap = kp_caps_variants_size(ctx->var_caps, (uint64_t)total);
-        KP_HIP_CHECK(ctx, R.d_var_cnt.reserve((size_t)total));
-        KP_HIP_CHECK(ctx, R.d_var_off.reserve((size_t)total + 1));
-        KP_HIP_CHECK(ctx, R.d_var.reserve(R.var_cap));
-        const KpTypingGroup &T = *typing_group(ctx, b);
-        kp_launch_variants_walk(b->view, ctx->genes, w->cigars(), R.kept_rows(T.gene_lo), R.d_var_src.p, R.variants(), false, R.stream);
+        V.cap = kp_caps_variants_size(ctx->var_caps, (uint64_t)total);
+        KP_HIP_CHECK(ctx, V.d_cnt.reserve((size_t)total));
+        KP_HIP_CHECK(ctx, V.d_off.reserve((size_t)total + 1));
+        KP_HIP_CHECK(ctx, V.d_rec.reserve(V.cap));
+        const KpKeptRows rows = R.kept_rows(typing_group(ctx, b)->gene_lo);
+        kp_launch_variants_walk(b->view, ctx->genes, w->cigars(), rows, R.derived.src.d_src.p, V.view(), false, R.stream);
         for (int attempt = 0;; ++attempt) {
-            kp_launch_variants_walk(b->view, ctx->genes, w->cigars(), R.kept_rows(T.gene_lo), R.d_var_src.p, R.variants(), true, R.stream);
+            kp_launch_variants_walk(b->view, ctx->genes, w->cigars(), rows, R.derived.src.d_src.p, V.view(), true, R.stream);
             KP_HIP_CHECK(ctx, hipGetLastError());
-            if (int frc = fetch_all(ctx, R.stream, {{R.h_var_off.data(), R.d_var_off.p, ((size_t)total + 1) * sizeof(int64_t)}})) return frc;
-            R.var_total = R.h_var_off[(size_t)total];
-            if (kp_caps_after_variants(ctx->var_caps, R.var_cap, (uint64_t)total, (uint64_t)R.var_total)) break;
+            if (int frc = fetch_all(ctx, R.stream, {{V.h_off.data(), V.d_off.p, ((size_t)total + 1) * sizeof(int64_t)}})) return frc;
+            V.total = V.h_off[(size_t)total];
+            if (kp_caps_after_variants(ctx->var_caps, V.cap, (uint64_t)total, (uint64_t)V.total)) break;
             if (attempt >= 1) return kp_fail(ctx, KP_EOVERFLOW, "variant buffer overflowed repeatedly");
-            KP_HIP_CHECK(ctx, R.d_var.reserve(R.var_cap));
+            KP_HIP_CHECK(ctx, V.d_rec.reserve(V.cap));
         }
     }
-    R.var_valid = true;
+    V.valid = true;
     return KP_OK;
 }
 
@@ -318,7 +354,8 @@ int kp_batch_variant_offsets(kp_ctx *ctx, kp_batch *b, int64_t *var_off) {
     if (!ctx || !b || b->ctx != ctx || !var_off) return kp_fail(ctx, KP_EINVAL, "bad arguments");
     KpTypingRun *R = nullptr;
     if (int rc = ensure_variants(ctx, b, &R)) return rc;
-    for (size_t a = 0; a < R->h_kept_off.size(); ++a) var_off[a] = R->h_var_off[(size_t)R->h_kept_off[a]];
+    const int64_t *const kept_off = R->derived.layout.kept_off();
+    for (int a = 0; a <= b->n_asm; ++a) var_off[a] = R->derived.var.h_off[(size_t)kept_off[a]];
     return KP_OK;
 }
 
@@ -326,49 +363,44 @@ int kp_batch_variants(kp_ctx *ctx, kp_batch *b, kp_variant *out, int64_t cap) {
     if (!ctx || !b || b->ctx != ctx || (!out && cap > 0)) return kp_fail(ctx, KP_EINVAL, "bad arguments");
     KpTypingRun *R = nullptr;
     if (int rc = ensure_variants(ctx, b, &R)) return rc;
-    if (cap < R->var_total) return kp_fail(ctx, KP_EINVAL, "variant buffer too small");
-    if (R->var_total > 0)
-        if (int frc = fetch_all(ctx, R->stream, {{out, R->d_var.p, (size_t)R->var_total * sizeof(kp_variant)}})) return frc;
+    const KpVariantsState &V = R->derived.var;
+    if (cap < V.total) return kp_fail(ctx, KP_EINVAL, "variant buffer too small");
+    if (V.total > 0)
+        if (int frc = fetch_all(ctx, R->stream, {{out, V.d_rec.p, (size_t)V.total * sizeof(kp_variant)}})) return frc;
     return KP_OK;
 }
 
 // ---- aligned rows of the kept hits (kp_aligned.hip; kp_spec.h, ALIGNED ROWS) -------------------------------------------------------
-static const char *const NO_ALIGNED = "this batch has no aligned rows (aligned without the aligned option, or its hit table was replaced)";
-
-// The rows of the batch's current group, made on first request after its reduction: the hit behind every kept record located (unless
-// the variant records already did), the blocks of every row counted and scanned, the total fetched and exactly that reserved, the
-// rows stored and their records fetched -- on the reduction's stream, behind the kernels that finalised the kept list.  Sizes are
-// exact before anything is stored: no guessed capacity, no overflow, no retry.
+// The rows of the batch's current group: the hit behind every kept record located (unless the variant records already did), the
+// blocks of every row counted and scanned, the total fetched and exactly that reserved, the rows stored and their records fetched.
+// Sizes are exact before anything is stored: no guessed capacity, no overflow, no retry.
 static int ensure_aligned(kp_ctx *ctx, kp_batch *b, KpTypingRun **R_out) {
-    KpWork *w = work_of(b);
-    if (!w || !w->finalised || !w->aln_on || !w->cigar_valid || !typing_group(ctx, b)) return kp_fail(ctx, KP_EINVAL, NO_ALIGNED);
-    KpTypingRun &R = typing_run(w, b->group);
-    if (!R.reduced) return kp_fail(ctx, KP_EINVAL, "this batch has no aligned rows: kp_batch_reduce has not run for this group since its hit table was made");
-    *R_out = &R;
-    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (int rc = fetch_summaries(ctx, b, w)) return rc;
-    if (R.aln_valid) return KP_OK;
+    KpWork *w = nullptr;
+    if (int rc = report_run(ctx, b, KP_EINVAL, NO_ALIGNED, ALIGNED_NOT_REDUCED, &KpWork::aln_on, &w, R_out)) return rc;
+    KpTypingRun &R = **R_out;
+    KpAlignedState &A = R.derived.aln;
+    if (A.valid) return KP_OK;
     if (int rc = ensure_kept_src(ctx, b, w, R)) return rc;
-    const int64_t total = R.h_kept_off.back();
-    R.h_aln_rows.assign((size_t)total, kp_aligned_row{0, 0, 0, 0, 0});
-    R.aln_blocks = 0;
+    const int64_t total = R.derived.layout.kept_total();
+    A.h_rows.assign((size_t)total, kp_aligned_row{0, 0, 0, 0, 0});
+    A.n_blocks = 0;
     if (total > 0) {
-        KP_HIP_CHECK(ctx, R.d_aln_cnt.reserve((size_t)total));
-        KP_HIP_CHECK(ctx, R.d_aln_off.reserve((size_t)total + 1));
-        KP_HIP_CHECK(ctx, R.d_aln_rows.reserve((size_t)total));
+        KP_HIP_CHECK(ctx, A.d_cnt.reserve((size_t)total));
+        KP_HIP_CHECK(ctx, A.d_off.reserve((size_t)total + 1));
+        KP_HIP_CHECK(ctx, A.d_rows.reserve((size_t)total));
         const KpKeptRows rows = R.kept_rows(typing_group(ctx, b)->gene_lo);
-        kp_launch_aligned_count(b->view, ctx->genes, rows, R.d_aln_cnt.p, R.d_aln_off.p, R.stream);
+        kp_launch_aligned_count(b->view, ctx->genes, rows, A.d_cnt.p, A.d_off.p, R.stream);
         KP_HIP_CHECK(ctx, hipGetLastError());
         int64_t n_blocks = 0;
-        if (int frc = fetch_all(ctx, R.stream, {{&n_blocks, R.d_aln_off.p + total, sizeof(int64_t)}})) return frc;
+        if (int frc = fetch_all(ctx, R.stream, {{&n_blocks, A.d_off.p + total, sizeof(int64_t)}})) return frc;
         if (n_blocks < 0) return kp_fail(ctx, KP_EHIP, "aligned rows: bad block count");
-        KP_HIP_CHECK(ctx, R.d_aln_blocks.reserve((size_t)std::max<int64_t>(n_blocks, 1)));
-        kp_launch_aligned_emit(b->view, ctx->genes, w->hit_rows(), w->cigars(), rows, R.d_var_src.p, R.d_aln_off.p, R.d_aln_blocks.p, R.d_aln_rows.p, R.stream);
+        KP_HIP_CHECK(ctx, A.d_blocks.reserve((size_t)std::max<int64_t>(n_blocks, 1)));
+        kp_launch_aligned_emit(b->view, ctx->genes, w->hit_rows(), w->cigars(), rows, R.derived.src.d_src.p, A.d_off.p, A.d_blocks.p, A.d_rows.p, R.stream);
         KP_HIP_CHECK(ctx, hipGetLastError());
-        if (int frc = fetch_all(ctx, R.stream, {{R.h_aln_rows.data(), R.d_aln_rows.p, (size_t)total * sizeof(kp_aligned_row)}})) return frc;
-        R.aln_blocks = n_blocks;
+        if (int frc = fetch_all(ctx, R.stream, {{A.h_rows.data(), A.d_rows.p, (size_t)total * sizeof(kp_aligned_row)}})) return frc;
+        A.n_blocks = n_blocks;
     }
-    R.aln_valid = true;
+    A.valid = true;
     return KP_OK;
 }
 
@@ -376,7 +408,7 @@ int kp_batch_aligned_size(kp_ctx *ctx, kp_batch *b, int64_t *n_blocks) {
     if (!ctx || !b || b->ctx != ctx || !n_blocks) return kp_fail(ctx, KP_EINVAL, "bad arguments");
     KpTypingRun *R = nullptr;
     if (int rc = ensure_aligned(ctx, b, &R)) return rc;
-    *n_blocks = R->aln_blocks;
+    *n_blocks = R->derived.aln.n_blocks;
     return KP_OK;
 }
 
@@ -385,11 +417,12 @@ int kp_batch_aligned_rows(kp_ctx *ctx, kp_batch *b, kp_aligned_row *rows, int32_
     KpTypingRun *R = nullptr;
     if (int rc = ensure_aligned(ctx, b, &R)) return rc;
     const size_t n_asm = (size_t)b->n_asm;
-    const std::vector<int64_t> &kept_off = R->h_kept_off;
+    const int64_t *const kept_off = R->derived.layout.kept_off();
+    const std::vector<kp_aligned_row> &h_rows = R->derived.aln.h_rows;
     for (size_t a = 0; a < n_asm; ++a)
         if (kept_off[a + 1] - kept_off[a] > kept_stride) return kp_fail(ctx, KP_EINVAL, "output strides too small (see kp_batch_typing_caps)");
     if (kept_stride > 0) std::memset(rows, 0, n_asm * (size_t)kept_stride * sizeof(kp_aligned_row));
-    for (size_t a = 0; a < n_asm; ++a) std::copy(R->h_aln_rows.begin() + kept_off[a], R->h_aln_rows.begin() + kept_off[a + 1], rows + a * (size_t)kept_stride);
+    for (size_t a = 0; a < n_asm; ++a) std::copy(h_rows.begin() + kept_off[a], h_rows.begin() + kept_off[a + 1], rows + a * (size_t)kept_stride);
     return KP_OK;
 }
 
@@ -397,45 +430,36 @@ int kp_batch_aligned_blocks(kp_ctx *ctx, kp_batch *b, uint64_t *out, int64_t cap
     if (!ctx || !b || b->ctx != ctx || (!out && cap > 0)) return kp_fail(ctx, KP_EINVAL, "bad arguments");
     KpTypingRun *R = nullptr;
     if (int rc = ensure_aligned(ctx, b, &R)) return rc;
-    if (cap < R->aln_blocks) return kp_fail(ctx, KP_EINVAL, "aligned block buffer too small");
-    if (R->aln_blocks > 0)
-        if (int frc = fetch_all(ctx, R->stream, {{out, R->d_aln_blocks.p, (size_t)R->aln_blocks * sizeof(uint64_t)}})) return frc;
+    const KpAlignedState &A = R->derived.aln;
+    if (cap < A.n_blocks) return kp_fail(ctx, KP_EINVAL, "aligned block buffer too small");
+    if (A.n_blocks > 0)
+        if (int frc = fetch_all(ctx, R->stream, {{out, A.d_blocks.p, (size_t)A.n_blocks * sizeof(uint64_t)}})) return frc;
     return KP_OK;
 }
 
 // ---- breakpoint records of the kept lists (kp_breakpoints.hip; kp_spec.h, BREAKPOINTS) --------------------------------------------
-static const char *const NO_BREAKPOINTS = "this batch has no breakpoint records: kp_batch_reduce has not run for this group since its hit table was made";
-
-// The records of the batch's current group, made on first request after its reduction (three kernels on the reduction's stream,
-// behind the ones that finalised the kept list) once the summaries show that no reduction buffer overflowed.  They need the kept
-// list and the batch's contigs only: no option, no ops -- a table that kp_batch_set_hits put in place serves as well.  The buffers
-// hold a record per kept record, which is an upper bound: nothing can overflow, nothing is retried.
+// The records of the batch's current group: three kernels.  They need the kept list and the batch's contigs only.  The buffers hold a
+// record per kept record, which is an upper bound: nothing can overflow, nothing is retried.
 static int ensure_breakpoints(kp_ctx *ctx, kp_batch *b, KpTypingRun **R_out) {
-    KpWork *w = work_of(b);
-    if (!w || !w->finalised || !typing_group(ctx, b)) return kp_fail(ctx, KP_EINVAL, NO_BREAKPOINTS);
-    KpTypingRun &R = typing_run(w, b->group);
-    if (!R.reduced) return kp_fail(ctx, KP_EINVAL, NO_BREAKPOINTS);
-    *R_out = &R;
-    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (int rc = fetch_summaries(ctx, b, w)) return rc;
-    if (R.bp_valid) return KP_OK;
+    KpWork *w = nullptr;
+    if (int rc = report_run(ctx, b, KP_EINVAL, NO_BREAKPOINTS, NO_BREAKPOINTS, nullptr, &w, R_out)) return rc;
+    KpTypingRun &R = **R_out;
+    KpBreakpointsState &B = R.derived.bp;
+    if (B.valid) return KP_OK;
     const size_t n_asm = (size_t)b->n_asm;
-    R.h_bp_kept_off.assign(n_asm + 1, 0);
-    for (size_t a = 0; a < n_asm; ++a) R.h_bp_kept_off[a + 1] = R.h_bp_kept_off[a] + std::min(std::max(R.h_sums[a].n_kept, 0), R.kept_cap);
-    const int64_t total = R.h_bp_kept_off[n_asm];
-    R.h_bp_off.assign(n_asm + 1, 0);
+    if (int rc = ensure_layout(ctx, R, n_asm)) return rc;
+    const int64_t total = R.derived.layout.kept_total();
+    B.h_off.assign(n_asm + 1, 0);
     if (total > 0) {
-        KP_HIP_CHECK(ctx, R.d_bp_cnt.reserve(n_asm));
-        KP_HIP_CHECK(ctx, R.d_bp_off.reserve(n_asm + 1));
-        KP_HIP_CHECK(ctx, R.d_bp_tmp.reserve((size_t)total));
-        KP_HIP_CHECK(ctx, R.d_bp.reserve((size_t)total));
-        if (int rc = upload(ctx, R.d_bp_kept_off, R.h_bp_kept_off.data(), n_asm + 1, R.stream)) return rc;
-        const KpKeptRows rows{.kept = R.d_kept.p, .kept_cap = R.kept_cap, .kept_off = R.d_bp_kept_off.p, .total = total, .gene_lo = typing_group(ctx, b)->gene_lo};
-        kp_launch_breakpoints(b->view, rows, R.max_kept, R.d_bp_tmp.p, R.d_bp_cnt.p, R.d_bp_off.p, R.d_bp.p, R.stream);
+        KP_HIP_CHECK(ctx, B.d_cnt.reserve(n_asm));
+        KP_HIP_CHECK(ctx, B.d_off.reserve(n_asm + 1));
+        KP_HIP_CHECK(ctx, B.d_tmp.reserve((size_t)total));
+        KP_HIP_CHECK(ctx, B.d_rec.reserve((size_t)total));
+        kp_launch_breakpoints(b->view, R.kept_rows(typing_group(ctx, b)->gene_lo), R.max_kept, B.d_tmp.p, B.d_cnt.p, B.d_off.p, B.d_rec.p, R.stream);
         KP_HIP_CHECK(ctx, hipGetLastError());
-        if (int frc = fetch_all(ctx, R.stream, {{R.h_bp_off.data(), R.d_bp_off.p, (n_asm + 1) * sizeof(int64_t)}})) return frc;
+        if (int frc = fetch_all(ctx, R.stream, {{B.h_off.data(), B.d_off.p, (n_asm + 1) * sizeof(int64_t)}})) return frc;
     }
-    R.bp_valid = true;
+    B.valid = true;
     return KP_OK;
 }
 
@@ -443,7 +467,7 @@ int kp_batch_breakpoint_offsets(kp_ctx *ctx, kp_batch *b, int64_t *bp_off) {
     if (!ctx || !b || b->ctx != ctx || !bp_off) return kp_fail(ctx, KP_EINVAL, "bad arguments");
     KpTypingRun *R = nullptr;
     if (int rc = ensure_breakpoints(ctx, b, &R)) return rc;
-    std::copy(R->h_bp_off.begin(), R->h_bp_off.end(), bp_off);
+    std::copy(R->derived.bp.h_off.begin(), R->derived.bp.h_off.end(), bp_off);
     return KP_OK;
 }
 
@@ -451,51 +475,35 @@ int kp_batch_breakpoints(kp_ctx *ctx, kp_batch *b, kp_breakpoint *out, int64_t c
     if (!ctx || !b || b->ctx != ctx || (!out && cap > 0)) return kp_fail(ctx, KP_EINVAL, "bad arguments");
     KpTypingRun *R = nullptr;
     if (int rc = ensure_breakpoints(ctx, b, &R)) return rc;
-    const int64_t total = R->h_bp_off.back();
+    const int64_t total = R->derived.bp.h_off.back();
     if (cap < total) return kp_fail(ctx, KP_EINVAL, "breakpoint buffer too small");
     if (total > 0)
-        if (int frc = fetch_all(ctx, R->stream, {{out, R->d_bp.p, (size_t)total * sizeof(kp_breakpoint)}})) return frc;
+        if (int frc = fetch_all(ctx, R->stream, {{out, R->derived.bp.d_rec.p, (size_t)total * sizeof(kp_breakpoint)}})) return frc;
     return KP_OK;
 }
 
 // ---- allele digests of the kept records and the pieces (kp_alleles.hip; kp_spec.h, ALLELES) ---------------------------------------
-static const char *const NO_ALLELES = "this batch has no allele digests: kp_batch_reduce has not run for this group since its hit table was made";
-
-// The digests of the batch's current group, made on first request after its reduction (one kernel on the reduction's stream, behind
-// the ones that finalised the kept list) once the summaries show that no reduction buffer overflowed, and fetched: a record per kept
-// row and per piece row, back to back.  They need the kept list, the pieces, the proteins and the batch's contigs only: no option,
-// no ops -- a table that kp_batch_set_hits put in place serves as well.
+// The digests of the batch's current group, one kernel, and fetched: a record per kept row and per piece row, back to back.  They need
+// the kept list, the pieces, the proteins and the batch's contigs only.
 static int ensure_alleles(kp_ctx *ctx, kp_batch *b, KpTypingRun **R_out) {
-    KpWork *w = work_of(b);
-    if (!w || !w->finalised || !typing_group(ctx, b)) return kp_fail(ctx, KP_EINVAL, NO_ALLELES);
-    KpTypingRun &R = typing_run(w, b->group);
-    if (!R.reduced) return kp_fail(ctx, KP_EINVAL, NO_ALLELES);
-    *R_out = &R;
-    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if (int rc = fetch_summaries(ctx, b, w)) return rc;
-    if (R.al_valid) return KP_OK;
-    const size_t n_asm = (size_t)b->n_asm;
-    R.h_al_off.assign(2 * (n_asm + 1), 0);
-    int64_t *const kept_off = R.h_al_off.data(), *const piece_off = kept_off + n_asm + 1;
-    for (size_t a = 0; a < n_asm; ++a) {
-        kept_off[a + 1] = kept_off[a] + std::min(std::max(R.h_sums[a].n_kept, 0), R.kept_cap);
-        piece_off[a + 1] = piece_off[a] + std::min(std::max(R.h_sums[a].n_pieces, 0), R.piece_cap);
-    }
-    const int64_t total = kept_off[n_asm], total_pieces = piece_off[n_asm];
-    R.h_al.assign((size_t)total, kp_allele{0, 0});
-    R.h_al_piece.assign((size_t)total_pieces, 0);
+    KpWork *w = nullptr;
+    if (int rc = report_run(ctx, b, KP_EINVAL, NO_ALLELES, NO_ALLELES, nullptr, &w, R_out)) return rc;
+    KpTypingRun &R = **R_out;
+    KpAllelesState &A = R.derived.al;
+    if (A.valid) return KP_OK;
+    if (int rc = ensure_layout(ctx, R, (size_t)b->n_asm)) return rc;
+    const int64_t total = R.derived.layout.kept_total(), total_pieces = R.derived.layout.piece_total();
+    A.h_rec.assign((size_t)total, kp_allele{0, 0});
+    A.h_piece.assign((size_t)total_pieces, 0);
     if (total + total_pieces > 0) {
-        KP_HIP_CHECK(ctx, R.d_al.reserve((size_t)std::max<int64_t>(total, 1)));
-        KP_HIP_CHECK(ctx, R.d_al_piece.reserve((size_t)std::max<int64_t>(total_pieces, 1)));
-        if (int rc = upload(ctx, R.d_al_off, R.h_al_off.data(), 2 * (n_asm + 1), R.stream)) return rc;
-        const KpKeptRows rows{.kept = R.d_kept.p, .kept_cap = R.kept_cap, .kept_off = R.d_al_off.p, .total = total, .gene_lo = typing_group(ctx, b)->gene_lo};
-        kp_launch_alleles(b->view, rows, R.d_pieces.p, R.piece_cap, R.d_al_off.p + n_asm + 1, total_pieces, R.d_prot.p, R.prot_cap, R.d_al.p, R.d_al_piece.p,
-                          R.stream);
+        KP_HIP_CHECK(ctx, A.d_rec.reserve((size_t)std::max<int64_t>(total, 1)));
+        KP_HIP_CHECK(ctx, A.d_piece.reserve((size_t)std::max<int64_t>(total_pieces, 1)));
+        kp_launch_alleles(b->view, R.kept_rows(typing_group(ctx, b)->gene_lo), R.piece_rows(), R.d_prot.p, R.prot_cap, A.d_rec.p, A.d_piece.p, R.stream);
         KP_HIP_CHECK(ctx, hipGetLastError());
-        if (int frc = fetch_all(ctx, R.stream, {{R.h_al.data(), R.d_al.p, (size_t)total * sizeof(kp_allele)},
-                                                {R.h_al_piece.data(), R.d_al_piece.p, (size_t)total_pieces * sizeof(uint64_t)}})) return frc;
+        if (int frc = fetch_all(ctx, R.stream, {{A.h_rec.data(), A.d_rec.p, (size_t)total * sizeof(kp_allele)},
+                                                {A.h_piece.data(), A.d_piece.p, (size_t)total_pieces * sizeof(uint64_t)}})) return frc;
     }
-    R.al_valid = true;
+    A.valid = true;
     return KP_OK;
 }
 
@@ -505,15 +513,16 @@ int kp_batch_alleles(kp_ctx *ctx, kp_batch *b, kp_allele *out, int32_t kept_stri
     KpTypingRun *R = nullptr;
     if (int rc = ensure_alleles(ctx, b, &R)) return rc;
     const size_t n_asm = (size_t)b->n_asm;
-    const int64_t *const kept_off = R->h_al_off.data(), *const piece_off = kept_off + n_asm + 1;
+    const int64_t *const kept_off = R->derived.layout.kept_off(), *const piece_off = R->derived.layout.piece_off();
+    const KpAllelesState &A = R->derived.al;
     for (size_t a = 0; a < n_asm; ++a)
         if (kept_off[a + 1] - kept_off[a] > kept_stride || piece_off[a + 1] - piece_off[a] > piece_stride)
             return kp_fail(ctx, KP_EINVAL, "output strides too small (see kp_batch_typing_caps)");
     if (kept_stride > 0) std::memset(out, 0, n_asm * (size_t)kept_stride * sizeof(kp_allele));
     if (piece_stride > 0) std::memset(piece_out, 0, n_asm * (size_t)piece_stride * sizeof(uint64_t));
     for (size_t a = 0; a < n_asm; ++a) {
-        std::copy(R->h_al.begin() + kept_off[a], R->h_al.begin() + kept_off[a + 1], out + a * (size_t)kept_stride);
-        std::copy(R->h_al_piece.begin() + piece_off[a], R->h_al_piece.begin() + piece_off[a + 1], piece_out + a * (size_t)piece_stride);
+        std::copy(A.h_rec.begin() + kept_off[a], A.h_rec.begin() + kept_off[a + 1], out + a * (size_t)kept_stride);
+        std::copy(A.h_piece.begin() + piece_off[a], A.h_piece.begin() + piece_off[a + 1], piece_out + a * (size_t)piece_stride);
     }
     return KP_OK;
 }

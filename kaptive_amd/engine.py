@@ -163,16 +163,14 @@ class Engine:
         )
 
     def _collect(self, typer, batch, ids, scores, best, genomes=None, group: "int | None" = None):
-        """The records of a batch's finished reduction as a ``BatchTyping`` -- with the ``variants`` / ``breakpoints`` / ``alleles``
-        option, its variant / breakpoint records / allele digests too."""
+        """The records of a batch's finished reduction as a ``BatchTyping`` -- with those of every report (``_native.REPORTS``) the
+        engine was made for."""
         from kaptive_amd.serotyping import batch as B
 
         group = self.group if group is None else group
         sums, kept, pieces = batch.typing(group)
-        return B.BatchTyping(typer, ids, sums, kept, pieces, scores, best, genomes, variants=batch.variants(group) if self.variants else None,
-                             breakpoints=batch.breakpoints(group) if self.breakpoints else None,
-                             alleles=batch.alleles(group) if self.alleles else None,
-                             aligned=batch.aligned(group) if self.aligned else None)
+        reports = {r.name: getattr(batch, r.fetch)(group) if getattr(self, r.name) else None for r in _native.REPORTS}
+        return B.BatchTyping(typer, ids, sums, kept, pieces, scores, best, genomes, **reports)
 
     def type_batch(self, typer, batch, ids: Sequence[str], genomes: Sequence[GenomeAssembly] | None = None,
                    aligned: bool = False):

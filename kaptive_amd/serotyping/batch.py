@@ -103,15 +103,10 @@ class BatchTyping:
     """
 
     def __init__(self, typer, ids, sums, kept, pieces, scores, best, genomes=None, variants=None, breakpoints=None, alleles=None, aligned=None) -> None:
-        """``variants``: ``(records, var_off)`` of ``Batch.variants`` where the engine was made with ``variants=True``;
-        ``breakpoints``: ``(records, bp_off)`` of ``Batch.breakpoints`` where it was made with ``breakpoints=True``; ``alleles``:
-        ``(records, piece digests)`` of ``Batch.alleles`` where it was made with ``alleles=True``; ``aligned``: ``(rows, blocks)`` of
-        ``Batch.aligned`` where it was made with ``aligned=True``."""
+        """``variants`` / ``breakpoints`` / ``alleles`` / ``aligned``: what the ``Batch`` method of that name gave (one row of
+        ``_native.REPORTS`` each), where the engine was made with that option."""
         self.typer, self.ids, self.genomes = typer, list(ids), genomes
-        self._variants = variants
-        self._breakpoints = breakpoints
-        self._alleles = alleles
-        self._aligned = aligned
+        self._variants, self._breakpoints, self._alleles, self._aligned = variants, breakpoints, alleles, aligned
         self.sums, self.kept, self.pieces = sums, kept, pieces
         db = typer._db
         n = len(sums)
@@ -224,34 +219,39 @@ class BatchTyping:
         return fmt.format(self.ids, self.phenotype, self.sums, self.kept, self.best_locus, self.typeable, self.problems,
                           self.percent_identity, self.percent_coverage, self.length_discrepancy)  # fmt: skip
 
+    def _report(self, name: str, tables: bool = False):
+        """The payload of report ``name`` (``_native.REPORTS``); with ``tables`` also the contigs' names and every assembly's first contig."""
+        from kaptive_amd import _native
+
+        noun, payload = next(r.noun for r in _native.REPORTS if r.name == name), getattr(self, "_" + name)
+        if payload is None:
+            raise ValueError(f"this batch was typed without {noun}: Engine(db, {name}=True) / Serotyper(db, {name}=True)")
+        if not tables:
+            return payload
+        if self.genomes is None:
+            raise ValueError(f"the {noun.split()[0]} table names contigs: the batch needs its genomes")
+        first = np.concatenate([[0], np.cumsum([len(g.contigs.ids) for g in self.genomes])]).astype(np.int64)
+        return (*payload, [n for g in self.genomes for n in g.contigs.ids], first)
 
     def variants(self):
         """``(records, var_off)``: the variant records (``_native.VARIANT_DTYPE``; include/kp_spec.h, VARIANTS) of the batch's kept
         hits -- ``records[var_off[i]:var_off[i + 1]]`` are assembly i's, ``records["kept"]`` indexes ``self.kept[i]``.  Only where
         the engine was made with ``variants=True``."""
-        if self._variants is None:
-            raise ValueError("this batch was typed without variant records: Engine(db, variants=True) / Serotyper(db, variants=True)")
-        return self._variants
+        return self._report("variants")
 
     def variants_tsv(self) -> bytes:
         """The lines of the variant table (``--variants``; no header: ``_native.VARIANTS_HEADER``), formatted by the native library
         from the records (kp_format_variants).  Contig names come from the genomes: ``genomes`` must have been given."""
         from kaptive_amd import _native
 
-        records, var_off = self.variants()
-        if self.genomes is None:
-            raise ValueError("the variant table names contigs: the batch needs its genomes")
-        first = np.concatenate([[0], np.cumsum([len(g.contigs.ids) for g in self.genomes])]).astype(np.int64)
-        names = [n for g in self.genomes for n in g.contigs.ids]
+        records, var_off, names, first = self._report("variants", tables=True)
         return _native.format_variants(self.typer._db.genes.ids, self.ids, names, first, self.kept, records, var_off)
 
     def breakpoints(self):
         """``(records, bp_off)``: the breakpoint records (``_native.BREAKPOINT_DTYPE``; include/kp_spec.h, BREAKPOINTS) of the batch's
         kept lists -- ``records[bp_off[i]:bp_off[i + 1]]`` are assembly i's, ``records["kept_a"]`` and ``records["kept_b"]`` index
         ``self.kept[i]``.  Only where the engine was made with ``breakpoints=True``."""
-        if self._breakpoints is None:
-            raise ValueError("this batch was typed without breakpoint records: Engine(db, breakpoints=True) / Serotyper(db, breakpoints=True)")
-        return self._breakpoints
+        return self._report("breakpoints")
 
     def breakpoints_tsv(self) -> bytes:
         """The lines of the breakpoint table (``--breakpoints``; no header: ``_native.BREAKPOINTS_HEADER``), formatted by the native
@@ -259,11 +259,7 @@ class BatchTyping:
         genomes: ``genomes`` must have been given."""
         from kaptive_amd import _native
 
-        records, bp_off = self.breakpoints()
-        if self.genomes is None:
-            raise ValueError("the breakpoint table names contigs: the batch needs its genomes")
-        first = np.concatenate([[0], np.cumsum([len(g.contigs.ids) for g in self.genomes])]).astype(np.int64)
-        names = [n for g in self.genomes for n in g.contigs.ids]
+        records, bp_off, names, first = self._report("breakpoints", tables=True)
         return _native.format_breakpoints(self.typer._db.genes.ids, self.ids, names, first, self.kept, records, bp_off,
                                           self.typer.partial_edge_tolerance)
 
@@ -271,9 +267,7 @@ class BatchTyping:
         """``(records, piece_digests)``: the allele digests (``_native.ALLELE_DTYPE``; include/kp_spec.h, ALLELES) of the batch's kept
         records -- ``records[i, j]`` belongs to ``self.kept[i, j]`` -- and of its locus pieces -- ``piece_digests[i, p]`` to
         ``self.pieces[i, p]``.  Only where the engine was made with ``alleles=True``."""
-        if self._alleles is None:
-            raise ValueError("this batch was typed without allele digests: Engine(db, alleles=True) / Serotyper(db, alleles=True)")
-        return self._alleles
+        return self._report("alleles")
 
     def locus_alleles(self) -> np.ndarray:
         """uint64 [n_asm]: the locus digest of every assembly -- its pieces' digests combined in the order the product lists the
@@ -288,11 +282,7 @@ class BatchTyping:
         the digests (kp_format_alleles).  Contig names come from the genomes: ``genomes`` must have been given."""
         from kaptive_amd import _native
 
-        records, piece_digests = self.alleles()
-        if self.genomes is None:
-            raise ValueError("the allele table names contigs: the batch needs its genomes")
-        first = np.concatenate([[0], np.cumsum([len(g.contigs.ids) for g in self.genomes])]).astype(np.int64)
-        names = [n for g in self.genomes for n in g.contigs.ids]
+        records, piece_digests, names, first = self._report("alleles", tables=True)
         db = self.typer._db
         return _native.format_alleles(db.genes.ids, db.loci.ids, self.ids, names, first, self.sums["n_kept"], self.sums["n_pieces"], self.best_locus,
                                       self.kept, records, piece_digests, _native.piece_order(self.pieces, self.sums["n_pieces"]))
@@ -301,9 +291,7 @@ class BatchTyping:
         """``(rows, blocks)``: the aligned rows (``_native.ALIGNED_ROW_DTYPE``; include/kp_spec.h, ALIGNED ROWS) of the batch's kept
         records -- ``rows[i, j]`` belongs to ``self.kept[i, j]`` and its blocks start at ``blocks[rows[i, j]["off"]]``.  Only where the
         engine was made with ``aligned=True``."""
-        if self._aligned is None:
-            raise ValueError("this batch was typed without aligned rows: Engine(db, aligned=True) / Serotyper(db, aligned=True)")
-        return self._aligned
+        return self._report("aligned")
 
     def aligned_codes(self, a: int, i: int) -> np.ndarray:
         """uint8 [gene length]: the row of kept record ``i`` of assembly ``a`` as codes 0..3 (acgt on the gene's strand), 4 (inside
@@ -320,11 +308,7 @@ class BatchTyping:
         the rows (kp_format_aligned).  Contig names come from the genomes: ``genomes`` must have been given."""
         from kaptive_amd import _native
 
-        rows, blocks = self.aligned()
-        if self.genomes is None:
-            raise ValueError("the aligned table names contigs: the batch needs its genomes")
-        first = np.concatenate([[0], np.cumsum([len(g.contigs.ids) for g in self.genomes])]).astype(np.int64)
-        names = [n for g in self.genomes for n in g.contigs.ids]
+        rows, blocks, names, first = self._report("aligned", tables=True)
         return _native.format_aligned(self.typer._db.genes.ids, self.ids, names, first, self.sums["n_kept"], self.kept, rows, blocks)
 
     def jsonl(self) -> bytes:
