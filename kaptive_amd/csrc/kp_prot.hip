@@ -31,6 +31,8 @@ namespace {
 constexpr int NEGP = KP_PROT_NEG_INF;
 constexpr int GO = KP_PROT_GAP_OPEN + KP_PROT_GAP_EXT;
 constexpr int GE = KP_PROT_GAP_EXT;
+// (REG_MAX_LEN, QP, S2_CAP, WAVE_NC_MAX and KP_PROT_K choose a pair's path below; tests/protein_paths_util.py restates them and
+// that choice as path_of(), and its case tables hold both sides of every threshold: change them together.)
 constexpr int REG_MAX_LEN = 768;  // residues per sequence the register kernel stages (four pairs per block: 12 KB of LDS)
 
 // Path statistics a DP state carries: a = matches << 16 | mismatches, g = gaps that consumed a query row << 16 | gaps that

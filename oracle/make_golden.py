@@ -6,6 +6,7 @@ Inputs come from kaptive_amd.synth (fixed seeds below) and, for the typing cases
 Every expected value in the fixtures is an output of reference code:
 
   protein_dp.npz   kaptive.core.pairwise.PairwiseAligner            (src/kaptive/core/pairwise.py:255-584)
+  protein_dp_seeded.npz  the same aligner with seeds given and k set (pairwise.py:277-279, 449-451)
   intervals.npz    kaptive.core.interval.Intervals.cull_overlaps / cluster_spatial (interval.py:435-493)
   seqs.npz         kaptive.core.seq.Sequences.extract / translate    (src/kaptive/core/seq.py:327-408)
   typing_*.npz     kaptive.serotyping.core.Serotyper.__call__ + KaptiveRow/Pha4geRow (core.py:124-486, io.py)
@@ -123,6 +124,40 @@ def gen_protein_dp(rng: np.random.Generator) -> None:
         q_seqs=q.seqs, q_offsets=q.offsets, q_lengths=q.lengths, t_seqs=t.seqs, t_offsets=t.offsets,
         t_lengths=t.lengths, scores=r.scores, matches=r.matches, mismatches=r.mismatches, gaps=r.gaps,
         q_starts=r.q_starts, q_ends=r.q_ends, t_starts=r.t_starts, t_ends=r.t_ends, pidents=r.pidents,
+    )  # fmt: skip
+
+
+def gen_protein_dp_seeded() -> None:
+    """tests/golden/protein_dp_seeded.npz: the REFERENCE's PairwiseAligner in its seeded mode (pairwise.py:277-279,
+    449-451) at bands the comparator never asks for -- k in {0, 1, 2, 3, 5, 8, 20} -- on the small end of the seeded case
+    table of tests/protein_paths_util.py (at most 60 residues a side): offsets 0 and +-1, the planted homology's own
+    diagonal, that diagonal on the band's edge and one outside, bands that hold one corner cell of the matrix or none,
+    identical sequences, empty ones and bytes outside the alphabet.  The offsets reach the reference the way
+    align_seeds hands them on: as the ``offsets`` column of its ``seeds`` argument."""
+    from types import SimpleNamespace
+
+    from tests.protein_paths_util import COLS, by_k, golden_seeded_table
+
+    cases = golden_seeded_table()
+    assert max(max(len(c[1]), len(c[2])) for c in cases) <= 60
+    q = RefSequences.from_bytes([c[1] for c in cases])
+    t = RefSequences.from_bytes([c[2] for c in cases])
+    offsets = np.array([c[3] for c in cases], np.int32)
+    ks = np.array([c[4] for c in cases], np.int32)
+    out = np.zeros((len(cases), 8), np.int32)
+    t0 = time.time()
+    for k in by_k(cases):
+        sel = np.flatnonzero(ks == k)
+        qs = RefSequences.from_bytes([cases[i][1] for i in sel])
+        ts = RefSequences.from_bytes([cases[i][2] for i in sel])
+        r = RefPairwiseAligner(k=int(k))(qs, ts, SimpleNamespace(offsets=offsets[sel]))
+        out[sel] = np.stack([getattr(r, c) for c in COLS], axis=1)
+    print(f"protein_dp_seeded: {len(cases)} pairs through the reference in {time.time() - t0:.1f}s, "
+          f"{int((out[:, 0] > 0).sum())} with a positive score")
+    np.savez_compressed(
+        OUT / "protein_dp_seeded.npz",
+        names=np.array([c[0] for c in cases]), q_seqs=q.seqs, q_offsets=q.offsets, q_lengths=q.lengths, t_seqs=t.seqs,
+        t_offsets=t.offsets, t_lengths=t.lengths, offsets=offsets, k=ks, **{c: out[:, i] for i, c in enumerate(COLS)},
     )  # fmt: skip
 
 
@@ -493,9 +528,11 @@ def gen_compare() -> None:
 
 def main() -> None:
     OUT.mkdir(parents=True, exist_ok=True)
-    what = set(sys.argv[1:]) or {"protein", "intervals", "seqs", "typing", "genbank", "compare"}
+    what = set(sys.argv[1:]) or {"protein", "protein_seeded", "intervals", "seqs", "typing", "genbank", "compare"}
     if "compare" in what:
         gen_compare()
+    if "protein_seeded" in what:
+        gen_protein_dp_seeded()
     if "genbank" in what:
         gen_genbank()
     if "protein" in what:
