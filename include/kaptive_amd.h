@@ -270,6 +270,11 @@ KP_API int64_t kp_batch_task_results(kp_ctx *ctx, kp_batch *batch, int32_t asm_i
  * score, order-score bonus. */
 #define KP_JOIN_ROW_INTS (6 + KP_JOIN_MAX_PIECES + 11 * KP_JOIN_MAX_PIECES)
 KP_API int64_t kp_batch_joins(kp_ctx *ctx, kp_batch *batch, int32_t asm_index, int32_t *out, int64_t cap);
+/* ... and what the OCCURRENCE CUT (kp_spec.h) left for one assembly, as uint32 words: [0] its state (bit 0: a gene seed with
+ * more than KP_MID_OCC anchors, bit 1: the assembly's own mid_occ decides: it claimed a counting table), [1] the mid_occ
+ * it was cut at (KP_MID_OCC without a table), then, with a table, the table's non-empty entries as (seed value, count)
+ * pairs in table order: the assembly's distinct minimizers and how often each occurs.  Returns the number of words. */
+KP_API int64_t kp_batch_occ(kp_ctx *ctx, kp_batch *batch, int32_t asm_index, uint32_t *out, int64_t cap);
 
 /* ---- batched typing: hit table -> per-assembly records -----------------------------------------------------------------
  * Replaces, for a whole batch, the reduction Serotyper.__call__ runs per genome after the aligner returns

@@ -520,4 +520,41 @@ int64_t kp_batch_joins(kp_ctx *ctx, kp_batch *b, int32_t a, int32_t *out, int64_
     return n;
 }
 
+int64_t kp_batch_occ(kp_ctx *ctx, kp_batch *b, int32_t a, uint32_t *out, int64_t cap) {
+    if (!ctx || !b || b->ctx != ctx || a < 0 || a >= b->n_asm) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    // what the pass left (kp_chain.hip, OccScratch): [n_asm] state, [n_asm] mid_occ, [occ_slots] the tables' assemblies
+    const size_t n_asm = w->n_asm;
+    uint32_t head[2] = {0, (uint32_t)KP_MID_OCC};
+    unsigned long long demand = 0;
+    if (hipMemcpy(&head[0], w->d_occ_state.p + a, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(&demand, w->occ_demand(), sizeof demand, hipMemcpyDeviceToHost) != hipSuccess)
+        return kp_fail(ctx, KP_EHIP, "D2H occurrence-cut state failed");
+    int64_t n = 2;
+    if (head[0] & 2u) {  // the assembly claimed a table: its mid_occ, and the table among those the pass handed out
+        if (hipMemcpy(&head[1], w->d_occ_state.p + n_asm + a, sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+            return kp_fail(ctx, KP_EHIP, "D2H occurrence-cut state failed");
+        const size_t n_slots = (size_t)std::min<unsigned long long>(demand, w->occ_slots), size = (size_t)1 << w->occ_log2;
+        // (a stage test's accessor: the size query and the call that fills `out` each fetch the whole table, 2 x 4 x 2^occ_log2 bytes;
+        // nothing is kept on the host between them, unlike h_tasks / h_joins, which every assembly of a batch shares)
+        std::vector<uint32_t> owner(n_slots), keys(size), cnts(size);
+        if (n_slots && hipMemcpy(owner.data(), w->d_occ_state.p + 2 * n_asm, n_slots * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+            return kp_fail(ctx, KP_EHIP, "D2H occurrence-cut state failed");
+        size_t slot = 0;
+        while (slot < n_slots && owner[slot] != (uint32_t)a) ++slot;
+        if (slot == n_slots) return kp_fail(ctx, KP_ESTATE, "the occurrence cut's state names no counting table for this assembly");
+        if (hipMemcpy(keys.data(), w->d_occ_keys.p + slot * size, size * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(cnts.data(), w->d_occ_cnts.p + slot * size, size * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+            return kp_fail(ctx, KP_EHIP, "D2H occurrence-cut table failed");
+        for (size_t i = 0; i < size; ++i) {
+            if (keys[i] == 0xFFFFFFFFu && cnts[i] == 0) continue;  // (an empty entry; a key without a count, or the reverse, is reported)
+            if (out && n + 2 <= cap) { out[n] = keys[i]; out[n + 1] = cnts[i]; }
+            n += 2;
+        }
+    }
+    if (out && cap >= 2) { out[0] = head[0]; out[1] = head[1]; }
+    return n;
+}
+
 }  // extern "C"

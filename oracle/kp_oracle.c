@@ -459,8 +459,10 @@ static int asm_mid_occ(const kpo_asm *a) {
     return mid;
 }
 
-/* all anchors of one assembly, sorted by key; returns count (caller frees *out) */
-static int64_t collect_anchors(const kpo_db *db, const kpo_asm *a, uint64_t **out) {
+/* all anchors of one assembly, sorted by key; returns count (caller frees *out).  Test hooks: without `cut` the list is left as
+ * sorted, before the occurrence cut; occ3, if given, receives the largest number of seeds beyond the floor that one gene has,
+ * the mid_occ the assembly is cut at, and whether the assembly's own mid_occ was worked out for that. */
+static int64_t collect_anchors_x(const kpo_db *db, const kpo_asm *a, uint64_t **out, int cut, int32_t *occ3) {
     kpo_collect k = {db, 0, NULL, 0, 1 << 16, 0};
     k.keys = malloc((size_t)k.cap * sizeof(uint64_t));
     for (int c = 0; c < a->n_ctg; c++) {
@@ -475,7 +477,7 @@ static int64_t collect_anchors(const kpo_db *db, const kpo_asm *a, uint64_t **ou
     int64_t kept = 0;
     /* the assembly's cut (kp_spec.h, OCCURRENCE CUT): minimap2's mid_occ when some gene has KP_MIN_ANCHORS seeds beyond the floor,
      * the floor otherwise */
-    int mid_occ = KP_MID_OCC;
+    int mid_occ = KP_MID_OCC, n_over_max = 0;
     for (int64_t i = 0; i < k.n;) {
         const uint32_t gene = KP_KEY_GS(k.keys[i]) >> 1;
         int64_t j = i;
@@ -489,10 +491,15 @@ static int64_t collect_anchors(const kpo_db *db, const kpo_asm *a, uint64_t **ou
                 if (++occ[(KP_KEY_GS(k.keys[u]) & 1) ? glen - KP_K - q : q] == KP_MID_OCC + 1) n_over++;
             }
             free(occ);
-            if (n_over >= KP_MIN_ANCHORS) { mid_occ = asm_mid_occ(a); break; }
+            if (n_over > n_over_max) n_over_max = n_over;
+            if (n_over >= KP_MIN_ANCHORS && !occ3) break;  /* (the hook goes on: it reports the largest) */
         }
         i = j;
     }
+    const int needs_quantile = n_over_max >= KP_MIN_ANCHORS;
+    if (needs_quantile) mid_occ = asm_mid_occ(a);
+    if (occ3) { occ3[0] = n_over_max; occ3[1] = mid_occ; occ3[2] = needs_quantile; }
+    if (!cut) { *out = k.keys; return k.n; }
     for (int64_t i = 0; i < k.n;) {
         const uint32_t gene = KP_KEY_GS(k.keys[i]) >> 1;
         int64_t j = i;
@@ -519,6 +526,7 @@ static int64_t collect_anchors(const kpo_db *db, const kpo_asm *a, uint64_t **ou
     *out = k.keys;
     return k.n;
 }
+static int64_t collect_anchors(const kpo_db *db, const kpo_asm *a, uint64_t **out) { return collect_anchors_x(db, a, out, 1, NULL); }
 
 /* test hook: the seeds of one sequence of codes, in emission order; returns the count (writes at most cap) */
 typedef struct { int32_t *start; uint8_t *z; uint32_t *x; int64_t n, cap; } kpo_seedbuf;
@@ -1180,6 +1188,26 @@ KPO_API int64_t kpo_anchors(const kpo_db *db, const uint32_t *words, int64_t pad
     kpo_asm a; asm_init(&a, words, padded_len, ctg_start, ctg_len, n_ctg, n_runs, n_nruns);
     uint64_t *keys; int64_t n = n_ctg ? collect_anchors(db, &a, &keys) : (keys = NULL, 0);
     if (out) memcpy(out, keys, (size_t)(n < cap ? n : cap) * sizeof(uint64_t));
+    free(keys); free(a.codes);
+    return n;
+}
+
+/* test hooks of the occurrence cut: the sorted anchors BEFORE the cut, and (n_over_max, mid_occ, needs_quantile) of collect_anchors_x */
+KPO_API int64_t kpo_anchors_uncut(const kpo_db *db, const uint32_t *words, int64_t padded_len, const int32_t *ctg_start,
+                                  const int32_t *ctg_len, int n_ctg, const int32_t *n_runs, int n_nruns, uint64_t *out,
+                                  int64_t cap) {
+    kpo_asm a; asm_init(&a, words, padded_len, ctg_start, ctg_len, n_ctg, n_runs, n_nruns);
+    uint64_t *keys; int64_t n = n_ctg ? collect_anchors_x(db, &a, &keys, 0, NULL) : (keys = NULL, 0);
+    if (out) memcpy(out, keys, (size_t)(n < cap ? n : cap) * sizeof(uint64_t));
+    free(keys); free(a.codes);
+    return n;
+}
+
+KPO_API int64_t kpo_occ(const kpo_db *db, const uint32_t *words, int64_t padded_len, const int32_t *ctg_start,
+                        const int32_t *ctg_len, int n_ctg, const int32_t *n_runs, int n_nruns, int32_t *occ3) {
+    kpo_asm a; asm_init(&a, words, padded_len, ctg_start, ctg_len, n_ctg, n_runs, n_nruns);
+    occ3[0] = 0; occ3[1] = KP_MID_OCC; occ3[2] = 0;
+    uint64_t *keys; int64_t n = n_ctg ? collect_anchors_x(db, &a, &keys, 1, occ3) : (keys = NULL, 0);
     free(keys); free(a.codes);
     return n;
 }

@@ -73,7 +73,7 @@ def _load(path: Path) -> None:
     _LIB = C.CDLL(str(path))
     _LIB.kpo_db_create.restype = C.c_void_p
     _LIB.kpo_db_n_postings.restype = C.c_int64
-    for f in ("kpo_anchors", "kpo_tasks", "kpo_sw", "kpo_align", "kpo_translate", "kpo_extract", "kpo_seeds", "kpo_joins"):
+    for f in ("kpo_anchors", "kpo_tasks", "kpo_sw", "kpo_align", "kpo_translate", "kpo_extract", "kpo_seeds", "kpo_joins", "kpo_anchors_uncut", "kpo_occ"):
         getattr(_LIB, f).restype = C.c_int64
 
 
@@ -196,12 +196,22 @@ class OracleDB:
         return keep, (self._h, _p(words), C.c_int64(pa.padded_len), _p(cs), _p(cl), C.c_int(len(cs)), _p(nr),
                       C.c_int(len(nr) // 2))  # fmt: skip
 
-    def anchors(self, pa) -> np.ndarray:
+    def anchors(self, pa, cut: bool = True) -> np.ndarray:
+        """Sorted anchor keys of the assembly; ``cut=False``: before the occurrence cut (kp_spec.h)."""
         keep, args = self._asm_args(pa)
-        n = lib().kpo_anchors(*args, None, C.c_int64(0))
+        fn = lib().kpo_anchors if cut else lib().kpo_anchors_uncut
+        n = fn(*args, None, C.c_int64(0))
         out = np.zeros(n, np.uint64)
-        lib().kpo_anchors(*args, _p(out), C.c_int64(n))
+        fn(*args, _p(out), C.c_int64(n))
         return out
+
+    def occ(self, pa) -> tuple[int, int, bool]:
+        """(n_over_max, mid_occ, needs_quantile) of the occurrence cut: the largest number of seeds with more than KP_MID_OCC
+        anchors that one gene has, the mid_occ the assembly is cut at, and whether its own quantile was worked out for it."""
+        keep, args = self._asm_args(pa)
+        out = np.zeros(3, np.int32)
+        lib().kpo_occ(*args, _p(out))
+        return int(out[0]), int(out[1]), bool(out[2])
 
     def tasks(self, pa) -> np.ndarray:
         keep, args = self._asm_args(pa)

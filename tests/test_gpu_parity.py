@@ -334,9 +334,10 @@ def test_occurrence_cut_matches_oracle(oracle):
     """minimap2 drops a query seed that occurs more than mid_occ (>= 10) times among the target's minimizers
     (src/kaptive/core/genome.py:177-191 builds that index per assembly); kp_spec.h's KP_MID_OCC restates the floor: a gene
     seed with more than ten anchors in an assembly loses them all (kp_occ_cut_kernel).  A stretch of a gene repeated 9, 10,
-    11, 12, 30 and 150 times on both strands, a whole gene in 14 copies, a repeat that lies beyond position 4096 of a 9 kb
-    gene and one that straddles it (the second / both counting windows), next to assemblies without any repeat: anchors
-    (after the cut), band tasks and hits equal the oracle's, and the cut removed what it should."""
+    11, 12, 30 and 150 times on both strands, a whole gene in 14 copies, two repeats in later counting windows of a 9 kb gene
+    (windows of OCC_BINS = 1024 positions of the forward strand: bases 5000-5300 across the edge at 5120, bases 3950-4250
+    across the edge at 4096; tests/test_gpu_occ_cut.py holds the edges themselves), next to assemblies without any repeat:
+    anchors (after the cut), band tasks and hits equal the oracle's, and the cut removed what it should."""
     rng = np.random.default_rng(4242)
     db = make_db("kpsc_k", seed=7, n_loci=4)
     long_gene = random_dna(rng, 9_000, 0.5)
