@@ -148,6 +148,7 @@ __host__ __device__ inline void kp_piece_rows(int lo, int width, int cstart, int
     if (*r_hi > r1) *r_hi = r1;
     if (*r_hi < *r_lo) *r_hi = *r_lo;
 }
+// (restated in Python by task_rows of tests/band_tasks_util.py, which pins the row counts its cases claim: change both)
 __host__ __device__ inline void kp_task_rows(int lo, int width, int cstart, int cend, int qlen, int *r_lo, int *r_hi) {
     int a = cstart - lo - (width - 1);
     if (a < 0) a = 0;
