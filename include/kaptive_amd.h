@@ -275,6 +275,13 @@ KP_API int64_t kp_batch_joins(kp_ctx *ctx, kp_batch *batch, int32_t asm_index, i
  * it was cut at (KP_MID_OCC without a table), then, with a table, the table's non-empty entries as (seed value, count)
  * pairs in table order: the assembly's distinct minimizers and how often each occurs.  Returns the number of words. */
 KP_API int64_t kp_batch_occ(kp_ctx *ctx, kp_batch *batch, int32_t asm_index, uint32_t *out, int64_t cap);
+/* ... and the seed scan's own output, the CANDIDATE LIST of the batch's last pass, as uint64 words: [0] how many the streaming
+ * kernel listed (the front of the list), [1] how many the edge kernel listed (its back), then the front words in list order and
+ * the back words in the order they were appended.  A word is (batch-wide base position << 31) | (strand bit << 30) | seed value.
+ * The order of either part depends on the order in which waves and threads finished: compare them as sets.  A null `out` returns
+ * the number of words; a buffer of fewer words is refused with nothing written; a pass whose list overflowed is never a batch's
+ * last one, and is refused, not returned cut short. */
+KP_API int64_t kp_batch_candidates(kp_ctx *ctx, kp_batch *batch, uint64_t *out, int64_t cap);
 
 /* ---- batched typing: hit table -> per-assembly records -----------------------------------------------------------------
  * Replaces, for a whole batch, the reduction Serotyper.__call__ runs per genome after the aligner returns

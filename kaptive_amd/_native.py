@@ -75,7 +75,7 @@ EXPORTS = (
     "kp_host_free", "kp_host_reserve", "kp_host_lock", "kp_host_pinned_bytes", "kp_device_allocations", "kp_db_load", "kp_db_n_postings", "kp_batch_create", "kp_batch_create_async",
     "kp_batch_upload_wait", "kp_batch_depends_on", "kp_batch_create_device", "kp_batch_device_words", "kp_batch_destroy", "kp_batch_align", "kp_batch_wait",
     "kp_batch_hit_offsets", "kp_batch_hits", "kp_batch_set_hits", "kp_batch_cigar_offsets", "kp_batch_cigars", "kp_batch_cs_offsets", "kp_batch_cs", "kp_batch_variant_offsets", "kp_batch_variants", "kp_format_variants", "kp_batch_breakpoint_offsets", "kp_batch_breakpoints", "kp_format_breakpoints", "kp_batch_alleles", "kp_format_alleles", "kp_allele_locus_digest", "kp_batch_aligned_size", "kp_batch_aligned_rows", "kp_batch_aligned_blocks", "kp_format_aligned", "kp_format_paf", "kp_format_paf_tags", "kp_batch_stats", "kp_batch_profile", "kp_batch_anchors",
-    "kp_batch_tasks", "kp_batch_task_results", "kp_batch_joins", "kp_batch_occ", "kp_db_load_typing", "kp_db_load_typing_group", "kp_batch_use_group", "kp_batch_score", "kp_batch_reduce", "kp_batch_typing_caps",
+    "kp_batch_tasks", "kp_batch_task_results", "kp_batch_joins", "kp_batch_occ", "kp_batch_candidates", "kp_db_load_typing", "kp_db_load_typing_group", "kp_batch_use_group", "kp_batch_score", "kp_batch_reduce", "kp_batch_typing_caps",
     "kp_device_count", "kp_device_numa_node", "kp_batch_typing", "kp_batch_proteins", "kp_protein_align", "kp_fasta_pack", "kp_fasta_ingest", "kp_fasta_ingest_many", "kp_fasta_ingest_file", "kp_fasta_ingest_shard", "kp_shard_words_into", "kp_shard_free", "kp_fasta_simd", "kp_pack_contigs",
     "kp_fasta_free", "kp_format_rows", "kp_format_json", "kp_format_fasta", "kp_protein_align_seeded", "kp_randstrobes", "kp_randstrobe_top_hits",
 )  # fmt: skip
@@ -896,7 +896,7 @@ def lib() -> C.CDLL:
                 h = C.CDLL(str(LIB_PATH))
                 h.kp_last_error.restype = C.c_char_p
                 h.kp_ctx_stream.restype = C.c_void_p
-                for f in ("kp_db_n_postings", "kp_batch_anchors", "kp_batch_tasks", "kp_batch_task_results", "kp_batch_joins", "kp_batch_occ"):
+                for f in ("kp_db_n_postings", "kp_batch_anchors", "kp_batch_tasks", "kp_batch_task_results", "kp_batch_joins", "kp_batch_occ", "kp_batch_candidates"):
                     getattr(h, f).restype = C.c_int64
                 h.kp_ctx_destroy.restype = None
                 h.kp_batch_destroy.restype = None
@@ -1294,6 +1294,17 @@ class Batch:
         out = np.zeros(n, np.uint32)
         lib().kp_batch_occ(self.ctx._h, self._h, C.c_int32(asm_index), _p(out), C.c_int64(n))
         return int(out[0]), int(out[1]), out[2:].reshape(-1, 2)
+
+    def candidates(self) -> tuple[np.ndarray, np.ndarray]:
+        """The seed scan's candidate list of the batch's last pass (kp_batch_candidates) as two uint64 arrays: the streaming
+        kernel's words (front) and the edge kernel's (back), each (batch-wide position << 31) | (strand bit << 30) | seed value.
+        The order within either array is that of the device's appends: compare them sorted."""
+        n = lib().kp_batch_candidates(self.ctx._h, self._h, None, C.c_int64(0))
+        self.ctx._check(n, "kp_batch_candidates")
+        out = np.zeros(n, np.uint64)
+        self.ctx._check(lib().kp_batch_candidates(self.ctx._h, self._h, _p(out), C.c_int64(n)), "kp_batch_candidates")
+        n_front, n_back = int(out[0]), int(out[1])
+        return out[2 : 2 + n_front].copy(), out[2 + n_front : 2 + n_front + n_back].copy()
 
 
 RANDSTROBE_DTYPE = np.dtype([("hash", "<u8"), ("seq_idx", "<u4"), ("pos1", "<u4"), ("pos2", "<u4")])

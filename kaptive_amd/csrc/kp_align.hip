@@ -2,6 +2,8 @@
 // pass again (sizes: kp_caps.h), finalisation of the hit table and the accessors of every stage's results.
 #include "kp_host.h"
 
+#include <algorithm>
+
 static const char *const NO_RESULTS = "this batch has no resident alignment results (not aligned yet, or displaced: a context keeps the results of its KP_WORK_SLOTS most recently aligned batches)";
 
 // What a pass enqueues between its fork onto the join stream and the join back: chaining of the groups, joined fill and walk-back on `jstream`; the band
@@ -554,6 +556,28 @@ int64_t kp_batch_occ(kp_ctx *ctx, kp_batch *b, int32_t a, uint32_t *out, int64_t
         }
     }
     if (out && cap >= 2) { out[0] = head[0]; out[1] = head[1]; }
+    return n;
+}
+
+int64_t kp_batch_candidates(kp_ctx *ctx, kp_batch *b, uint64_t *out, int64_t cap) {
+    if (!ctx || !b || b->ctx != ctx || (out && cap < 0)) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpWork *w = finalised_work(ctx, b);
+    if (!w) return KP_ESTATE;
+    // what the last pass's scan left (kp_scan.hip): the streaming kernel's words from the list's front, the edge kernel's from its back
+    unsigned long long n_cand[KP_CAND_COUNTS] = {};
+    if (hipMemcpy(n_cand, w->d_cand_count.p, sizeof n_cand, hipMemcpyDeviceToHost) != hipSuccess)
+        return kp_fail(ctx, KP_EHIP, "D2H candidate counts failed");
+    const uint64_t n_front = n_cand[KP_CAND_FRONT], n_back = n_cand[KP_CAND_BACK];
+    if (n_front + n_back > w->cand_cap) return kp_fail(ctx, KP_ESTATE, "the last pass's candidate list overflowed: it holds no whole list");
+    const int64_t n = KP_CAND_COUNTS + (int64_t)(n_front + n_back);
+    if (!out) return n;
+    if (cap < n) return kp_fail(ctx, KP_EINVAL, "candidate buffer too small");
+    out[KP_CAND_FRONT] = n_front; out[KP_CAND_BACK] = n_back;
+    uint64_t *front = out + KP_CAND_COUNTS, *back = front + n_front;
+    if ((n_front && hipMemcpy(front, w->d_cand.p, n_front * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) ||
+        (n_back && hipMemcpy(back, w->d_cand.p + (w->cand_cap - n_back), n_back * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess))
+        return kp_fail(ctx, KP_EHIP, "D2H candidates failed");
+    std::reverse(back, back + n_back);  // entry k of the back list lies at cand[cand_cap - 1 - k]
     return n;
 }
 
