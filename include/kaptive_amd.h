@@ -68,7 +68,8 @@ KP_API void *kp_ctx_stream(kp_ctx *ctx);
  * buffer; setting it forgets what the context has learnt for it), cs (0 | 1: cs difference strings of the hits, kp_batch_cs;
  * from the next kp_batch_align; such a pass computes the CIGARs as well) and cs_bytes_per_hit (first size of their buffer,
  * likewise), variants (0 | 1: variant records of the kept hits, kp_batch_variants; from the next kp_batch_align; such a pass
- * computes the CIGARs as well) and variants_per_kept (first size of their buffer, likewise). */
+ * computes the CIGARs as well) and variants_per_kept (first size of their buffer, likewise), rescue (0 | 1) and rescue_flank (0 .. 65535:
+ * the rescue records of the missing genes, kp_batch_rescue; read when the records are asked for). */
 KP_API int kp_ctx_set_option(kp_ctx *ctx, const char *name, int64_t value);
 #define KP_WORK_SLOTS 3
 
@@ -389,6 +390,19 @@ KP_API int kp_batch_alleles(kp_ctx *ctx, kp_batch *batch, kp_allele *out, int32_
 KP_API int kp_batch_aligned_size(kp_ctx *ctx, kp_batch *batch, int64_t *n_blocks);
 KP_API int kp_batch_aligned_rows(kp_ctx *ctx, kp_batch *batch, kp_aligned_row *rows, int32_t kept_stride);
 KP_API int kp_batch_aligned_blocks(kp_ctx *ctx, kp_batch *batch, uint64_t *out, int64_t cap);
+/* Rescue records of the missing genes (kp_spec.h, RESCUE; options "rescue" (0 | 1) and "rescue_flank" (0 .. KP_RESCUE_FLANK_MAX, default
+ * KP_RESCUE_FLANK)): every gene the reduction lists as missing is looked for by aligning its database protein against the six-frame
+ * translation of the contig around every locus piece -- Kaptive 2 searched genes with tblastn; a nucleotide seed does not land in a
+ * gene below 75-80 % identity.  One record per missing gene, in ascending gene order.  For the group kp_batch_use_group chose, after
+ * kp_batch_reduce; made on the first call after a reduction (kernels on the reduction's stream) and kept until the group's next
+ * kp_batch_reduce, the batch's next kp_batch_align or kp_batch_set_hits, or a call with another rescue_flank.  The options are read
+ * when the records are asked for: no alignment pass and no reduction does anything for them, and with "rescue" off nothing is
+ * computed, allocated or launched -- both calls then return KP_EINVAL, as they do without a current reduction, and kp_last_error
+ * names the cause.  Sizes are exact: nothing overflows, nothing is retried.
+ *   kp_batch_rescue_offsets : rescue_off[n_asm + 1]: the records of assembly a are out[rescue_off[a] .. rescue_off[a + 1])
+ *   kp_batch_rescue         : the records; KP_EINVAL when cap < rescue_off[n_asm] */
+KP_API int kp_batch_rescue_offsets(kp_ctx *ctx, kp_batch *batch, int64_t *rescue_off);
+KP_API int kp_batch_rescue(kp_ctx *ctx, kp_batch *batch, kp_rescue *out, int64_t cap);
 
 /* ---- report rows (host only) -----------------------------------------------------------------------------------------------
  * Replaces KaptiveRow.from_result + bytes(row) per genome (src/kaptive/serotyping/io.py:191-296, 37-43): the TSV lines
@@ -516,6 +530,20 @@ KP_API uint64_t kp_allele_locus_digest(const uint64_t *piece_digests, const int3
  * gene or contig the tables do not have. */
 KP_API int64_t kp_format_aligned(const kp_variant_tables *tables, int32_t n_asm, const int32_t *n_kept, const kp_kept *kept, int32_t kept_stride,
                                  const kp_aligned_row *rows, const uint64_t *blocks, int64_t n_blocks, char *out, int64_t cap);
+
+/* ---- rescue table of a batch (host only) ----------------------------------------------------------------------------------------
+ * One tab-separated line per rescue record, in the records' order: Assembly, Locus (the best-match locus's name), Gene, Protein length
+ * (of the database's protein, its trailing * included), Call, Score, Contig, Start, End (1-based and closed, contig forward strand),
+ * Strand, Frame (1..3), Protein start (1-based), Protein end, Matches, Mismatches, Gaps, Identity (matches * 100 / (matches +
+ * mismatches + gaps), %.2f), Coverage ((p_end - p_start) * 100 / protein length, %.2f), Stops and Edge (start / end / both / .).  A
+ * record with score 0 has "." in every column from Contig to Protein end.  Call is the first that applies of: absent (score <
+ * min_score), interrupted (a stop inside the aligned stretch: stops > 0, not counting the gene's own stop where the alignment reaches the
+ * protein's trailing *), partial (edge != 0 and coverage < 90), fragment (coverage < 90), diverged; the 90 is the
+ * reference's TRUNCATED rule (prot_cov < 0.90).  No header line.  Tables are kp_allele_tables; prot_len the database's protein lengths
+ * by gene; best_locus per assembly as the host chose it; records / rescue_off as kp_batch_rescue / kp_batch_rescue_offsets filled
+ * them.  Return value as kp_format_variants has it; KP_EINVAL also for a best locus, gene or contig the tables do not have. */
+KP_API int64_t kp_format_rescue(const kp_allele_tables *tables, int32_t n_asm, const int32_t *prot_len, const int32_t *best_locus, const kp_rescue *records,
+                                const int64_t *rescue_off, int32_t min_score, char *out, int64_t cap);
 
 /* ---- JSON lines of a whole batch (host only) ----------------------------------------------------------------------------------
  * Replaces orjson.dumps(SerotypingResult.to_dict(), OPT_SERIALIZE_NUMPY | OPT_APPEND_NEWLINE) per genome

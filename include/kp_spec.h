@@ -580,4 +580,62 @@ typedef struct kp_aligned_row {
     int32_t covered, inserted, n_ins;
 } kp_aligned_row;
 
+/* ---- RESCUE (optional, like the reports above: no hit, no kept record and no report byte depends on it) ---------------------------
+ * A gene of the best-match locus is listed as missing when no nucleotide seed landed in it -- because it is absent, or because it
+ * has drifted below the 75-80 % nucleotide identity a (10, 15) minimizer needs.  The rescue records tell the two apart: every
+ * missing gene's database protein is aligned against the six-frame translation of the contig windows around the locus pieces.
+ *
+ * SUBJECTS.  The genes of an assembly whose bit is set in kp_asm_summary.missing_mask after a finished reduction (bit j: gene
+ * locus_gene_off[best_locus] + j), in ascending gene order: one record each.  An assembly whose summary has overflow bit 2 (locus
+ * wider than the mask) has none.  rescue_off[n_asm + 1] delimits the assemblies.
+ * WINDOWS.  Every piece p of the assembly (kp_piece, in the order kp_batch_typing returns them) gives one window on the piece's
+ * contig: ws = max(0, start - F), we = min(ctg_len, end + F), F the option rescue_flank (default KP_RESCUE_FLANK: a design constant,
+ * longer than nearly every gene, so that a gene just outside the bounding box of the primary hits still lies in the window).  An
+ * assembly without a piece has no window.
+ * FRAME TEXT.  For strand s in (+, -) and frame f in (0, 1, 2) the frame text has A = max(0, (we - ws - f) / 3) residues.  Forward,
+ * residue a is the codon of contig bases ws + f + 3a .. + 2; reverse, the codon of the complements of bases we - 1 - f - 3a,
+ * we - 2 - f - 3a, we - 3 - f - 3a.  The table is the product's (kp_fill_codon_table: NCBI 11); a codon with a base inside an N run
+ * is X, stops are *, nothing is cut at a stop.  Byte for byte the reference's translate(extract(window, strand), frame f,
+ * to_stop = False) (src/kaptive/core/seq.py:612-741).
+ * ALIGNMENT.  Rows i run over the frame text (the reference's query: the assembly side), columns j over the database protein as
+ * stored, its trailing * included.  The arithmetic is the reference's _batched_banded_gotoh (src/kaptive/core/pairwise.py:395-584)
+ * with a band that covers the whole rectangle -- seeded mode, offset 0, k >= A + protein length --: BLOSUM62 through the 256 x 256
+ * lookup, gap open KP_PROT_GAP_OPEN, extend KP_PROT_GAP_EXT, opening a gap beats extending one, the diagonal beats D beats I, a cell
+ * with best <= 0 restarts the path, the reported cell is the first maximum in row-major order and the path counts are those of the
+ * reference's traceback.  Scores are int32.  The eight values: score, matches, mismatches, gaps, a0, a1 (frame text, half-open),
+ * p0, p1 (protein, half-open).
+ * BEST OF A SUBJECT.  The maximum score over its tasks; task index = (piece * 2 + (strand < 0)) * 3 + f; ties go to the lowest
+ * task index.  Score 0 means nothing: the record then has piece = -1 and every other field 0 except gene.
+ * DERIVED FIELDS.  Forward: t_start = ws + f + 3 a0, t_end = ws + f + 3 a1; reverse: t_start = we - f - 3 a1, t_end = we - f - 3 a0;
+ * both 0-based and half-open on the contig's forward strand.  stops = number of * in the frame text at [a0, a1) -- the gene's own
+ * stop included where the alignment reaches the protein's trailing * (its last column is then * against *: nothing else scores
+ * positive against *); the table does not count that one as an interruption.  edge bit 0:
+ * t_start <= tol; bit 1: t_end >= ctg_len - tol; tol = kp_typing_params.edge_tolerance of the reduction.
+ * PURE FUNCTION of the summaries, the pieces, the contig lengths, the packed contigs, the database proteins and the two options
+ * (rescue_flank, edge_tolerance): no hit, no CIGAR and no trace is read.
+ * NOT DONE.  A gene on a contig that holds no piece of the locus is not looked for.  A frameshifted gene is two alignments in two
+ * frames: the better one is reported, as a fragment.  Completeness, confidence and every other column of the reports stay as they are.
+ *
+ * KP_RESCUE_MIN_SCORE, the table's default threshold between `absent` and a call, is a default, not a measurement: with BLAST's
+ * published gapped parameters for BLOSUM62 11/1 (lambda 0.267, K 0.041), a 330-residue protein against six frames of a 43 kb window
+ * is m n = 330 x 6 x 14 300 = 2.8e7 cell pairs, and E = K m n exp(-lambda S) = 0.041 x 2.8e7 x exp(-0.267 x 80) = 6e-4 at S = 80.  The
+ * raw score is always in the table. */
+#define KP_RESCUE_FLANK 4096
+#define KP_RESCUE_FLANK_MAX 65535
+#define KP_RESCUE_MIN_SCORE 80
+typedef struct kp_rescue {
+    int32_t gene;             /* index of the subject, as kp_kept.gene counts genes */
+    int32_t piece;            /* index of the winning window's piece, as kp_batch_typing returns the pieces; -1: nothing found */
+    int32_t contig;           /* contig index within the assembly */
+    int32_t t_start, t_end;   /* on the contig's forward strand, 0-based half-open */
+    int32_t score, matches, mismatches, gaps;
+    int32_t p_start, p_end;   /* on the database protein, 0-based half-open */
+    int32_t stops;            /* stop codons inside the aligned stretch of the frame text */
+    int32_t a_len;            /* A: residues of the winning frame text */
+    int8_t strand;            /* +1 / -1; 0 when nothing was found */
+    uint8_t frame;            /* 0..2 */
+    uint8_t edge;             /* bit 0: the alignment starts at the contig's start, bit 1: it ends at the contig's end */
+    uint8_t pad_;             /* zero */
+} kp_rescue;
+
 #endif /* KP_SPEC_H */

@@ -52,6 +52,16 @@ ALIGNED_HEADER = (b"Assembly\tGene\tContig\tStart\tEnd\tStrand\tGene length\tGen
                   b"Aligned\n")  # the columns of kp_format_aligned
 ALIGNED_GAP = 5  # the code ``aligned_codes`` gives a GAP column (0..3 bases, 4 inside an N run)
 
+RESCUE_DTYPE = np.dtype(
+    [("gene", "<i4"), ("piece", "<i4"), ("contig", "<i4"), ("t_start", "<i4"), ("t_end", "<i4"), ("score", "<i4"), ("matches", "<i4"),
+     ("mismatches", "<i4"), ("gaps", "<i4"), ("p_start", "<i4"), ("p_end", "<i4"), ("stops", "<i4"), ("a_len", "<i4"), ("strand", "i1"),
+     ("frame", "u1"), ("edge", "u1"), ("pad", "u1")]
+)  # fmt: skip (kp_rescue of include/kp_spec.h, RESCUE: 56 bytes; piece -1 = nothing found)
+RESCUE_HEADER = (b"Assembly\tLocus\tGene\tProtein length\tCall\tScore\tContig\tStart\tEnd\tStrand\tFrame\tProtein start\tProtein end\t"
+                 b"Matches\tMismatches\tGaps\tIdentity\tCoverage\tStops\tEdge\n")  # the columns of kp_format_rescue
+RESCUE_FLANK = 4096  # KP_RESCUE_FLANK of include/kp_spec.h (tests/test_native_abi.py's neighbours compare such pairs)
+RESCUE_MIN_SCORE = 80  # KP_RESCUE_MIN_SCORE
+
 # The reports derived from a reduction's kept list ("Reports derived from the kept list"), one row each: `name` (the command
 # line's option, the keyword of Engine / Serotyper / BatchTyping, the key of a chunk's outputs), the `header` line of its table, the Batch
 # method that fetches its records, the BatchTyping method that formats its lines (`tsv`), and the `noun` BatchTyping says a batch was
@@ -62,6 +72,7 @@ REPORTS = (
     Report("breakpoints", BREAKPOINTS_HEADER, "breakpoints", "breakpoints_tsv", "breakpoint records"),
     Report("alleles", ALLELES_HEADER, "alleles", "alleles_tsv", "allele digests"),
     Report("aligned", ALIGNED_HEADER, "aligned", "aligned_tsv", "aligned rows"),
+    Report("rescue", RESCUE_HEADER, "rescue", "rescue_tsv", "rescue records"),
 )
 
 JOIN_MAX_PIECES = 8  # KP_JOIN_MAX_PIECES
@@ -74,7 +85,7 @@ EXPORTS = (
     "kp_ctx_create", "kp_ctx_destroy", "kp_last_error", "kp_ctx_stream", "kp_ctx_set_option", "kp_host_alloc",
     "kp_host_free", "kp_host_reserve", "kp_host_lock", "kp_host_pinned_bytes", "kp_device_allocations", "kp_db_load", "kp_db_n_postings", "kp_batch_create", "kp_batch_create_async",
     "kp_batch_upload_wait", "kp_batch_depends_on", "kp_batch_create_device", "kp_batch_device_words", "kp_batch_destroy", "kp_batch_align", "kp_batch_wait",
-    "kp_batch_hit_offsets", "kp_batch_hits", "kp_batch_set_hits", "kp_batch_cigar_offsets", "kp_batch_cigars", "kp_batch_cs_offsets", "kp_batch_cs", "kp_batch_variant_offsets", "kp_batch_variants", "kp_format_variants", "kp_batch_breakpoint_offsets", "kp_batch_breakpoints", "kp_format_breakpoints", "kp_batch_alleles", "kp_format_alleles", "kp_allele_locus_digest", "kp_batch_aligned_size", "kp_batch_aligned_rows", "kp_batch_aligned_blocks", "kp_format_aligned", "kp_format_paf", "kp_format_paf_tags", "kp_batch_stats", "kp_batch_profile", "kp_batch_anchors",
+    "kp_batch_hit_offsets", "kp_batch_hits", "kp_batch_set_hits", "kp_batch_cigar_offsets", "kp_batch_cigars", "kp_batch_cs_offsets", "kp_batch_cs", "kp_batch_variant_offsets", "kp_batch_variants", "kp_format_variants", "kp_batch_breakpoint_offsets", "kp_batch_breakpoints", "kp_format_breakpoints", "kp_batch_alleles", "kp_format_alleles", "kp_allele_locus_digest", "kp_batch_aligned_size", "kp_batch_aligned_rows", "kp_batch_aligned_blocks", "kp_format_aligned", "kp_batch_rescue_offsets", "kp_batch_rescue", "kp_format_rescue", "kp_format_paf", "kp_format_paf_tags", "kp_batch_stats", "kp_batch_profile", "kp_batch_anchors",
     "kp_batch_tasks", "kp_batch_task_results", "kp_batch_joins", "kp_batch_occ", "kp_batch_candidates", "kp_db_load_typing", "kp_db_load_typing_group", "kp_batch_use_group", "kp_batch_score", "kp_batch_reduce", "kp_batch_typing_caps",
     "kp_device_count", "kp_device_numa_node", "kp_batch_typing", "kp_batch_proteins", "kp_protein_align", "kp_fasta_pack", "kp_fasta_ingest", "kp_fasta_ingest_many", "kp_fasta_ingest_file", "kp_fasta_ingest_shard", "kp_shard_words_into", "kp_shard_free", "kp_fasta_simd", "kp_pack_contigs",
     "kp_fasta_free", "kp_format_rows", "kp_format_json", "kp_format_fasta", "kp_protein_align_seeded", "kp_randstrobes", "kp_randstrobe_top_hits",
@@ -562,6 +573,41 @@ def format_breakpoints(gene_names, asm_names, contig_names, asm_first_ctg, kept,
             return out[:need].tobytes()
         out = np.empty(int(need), np.uint8)
     raise NativeError("kp_format_breakpoints: size kept changing")
+
+
+def format_rescue(gene_names, locus_names, asm_names, contig_names, asm_first_ctg, prot_len, best_locus, records, rescue_off,
+                  min_score: int = RESCUE_MIN_SCORE) -> bytes:
+    """The lines of the rescue table (kp_format_rescue; host only; no header: ``RESCUE_HEADER``): one per record of ``records``
+    (RESCUE_DTYPE), assembly a's being ``rescue_off[a]:rescue_off[a + 1]``.  The name tables are those of ``format_alleles``;
+    ``prot_len`` the database's protein lengths by gene (``Database.translations.lengths``); ``min_score`` decides between ``absent``
+    and a call."""
+    gn_b, gn_o = _blob(gene_names)
+    ln_b, ln_o = _blob(locus_names)
+    an_b, an_o = _blob64(asm_names)
+    cn_b, cn_o = _blob64(contig_names)
+    first, rescue_off = _c(asm_first_ctg, np.int64), _c(rescue_off, np.int64)
+    prot_len, best_locus = _c(prot_len, np.int32), _c(best_locus, np.int32)
+    records = np.ascontiguousarray(records, dtype=RESCUE_DTYPE)
+    n_asm = len(rescue_off) - 1
+    if len(first) != n_asm + 1 or len(an_o) != n_asm + 1 or len(best_locus) != n_asm or len(prot_len) != len(gn_o) - 1 or (n_asm and int(first[-1]) > len(cn_o) - 1):
+        raise ValueError("name tables do not describe the batch")
+    if n_asm and (int(rescue_off[0]) < 0 or int(rescue_off[-1]) > len(records)):
+        raise ValueError("offsets run past the records")
+    names = VariantTables(gene_names=_p(gn_b).value, gene_name_off=_p(gn_o).value, n_genes=len(gn_o) - 1, asm_names=_p(an_b).value,
+                          asm_name_off=_p(an_o).value, ctg_names=_p(cn_b).value, ctg_name_off=_p(cn_o).value, asm_first_ctg=_p(first).value)  # fmt: skip
+    t = AlleleTables(names=names, locus_names=_p(ln_b).value, locus_name_off=_p(ln_o).value, n_loci=len(ln_o) - 1)
+    h = lib()
+    h.kp_format_rescue.restype = C.c_int64
+    out = np.empty(max(4096, 320 * len(records)), np.uint8)
+    for _ in range(2):
+        need = h.kp_format_rescue(C.byref(t), C.c_int32(n_asm), _p(prot_len), _p(best_locus), _p(records), _p(rescue_off), C.c_int32(int(min_score)),
+                                  _p(out), C.c_int64(len(out)))
+        if need < 0:
+            raise ValueError(f"kp_format_rescue failed ({need})")
+        if need <= len(out):
+            return out[:need].tobytes()
+        out = np.empty(int(need), np.uint8)
+    raise NativeError("kp_format_rescue: size kept changing")
 
 
 class AlleleTables(C.Structure):  # kp_allele_tables
@@ -1235,6 +1281,17 @@ class Batch:
         self.ctx._check(h.kp_batch_aligned_rows(self.ctx._h, self._h, _p(rows), kc), "kp_batch_aligned_rows")
         self.ctx._check(h.kp_batch_aligned_blocks(self.ctx._h, self._h, _p(blocks), C.c_int64(len(blocks))), "kp_batch_aligned_blocks")
         return rows, blocks
+
+    def rescue(self, group: int = 0) -> tuple[np.ndarray, np.ndarray]:
+        """(records RESCUE_DTYPE, rescue_off int64 [n_asm + 1]): the rescue records of the genes ``typing(group)`` lists as missing,
+        assembly a's being ``records[rescue_off[a]:rescue_off[a + 1]]`` (kp_batch_rescue; include/kp_spec.h, RESCUE).  After
+        ``reduce_async``, on a context whose ``rescue`` option is set; a hit table that ``set_hits`` put in place serves as well."""
+        self.use_group(group)
+        off = np.zeros(self.n_asm + 1, np.int64)
+        self.ctx._check(lib().kp_batch_rescue_offsets(self.ctx._h, self._h, _p(off)), "kp_batch_rescue_offsets")
+        out = np.zeros(int(off[-1]), RESCUE_DTYPE)
+        self.ctx._check(lib().kp_batch_rescue(self.ctx._h, self._h, _p(out), C.c_int64(len(out))), "kp_batch_rescue")
+        return out, off
 
     def proteins(self, asm_index: int, nbytes: int, group: int = 0) -> np.ndarray:
         self.use_group(group)

@@ -127,6 +127,14 @@ def _add_outputs(p: argparse.ArgumentParser, tsv_flags, include_json: bool) -> N
         g.add_argument("--aligned", metavar="FILE", default=argparse.SUPPRESS,
                        help="Write every reported gene's contig bases in the coordinates of the database's gene -- one row of exactly "
                             "gene-length columns per hit, ready to stack into an alignment -- as a TSV table to a file")
+        g.add_argument("--rescue", metavar="FILE", default=argparse.SUPPRESS,
+                       help="Look for every gene reported as missing by aligning its protein against the six-frame translation of the "
+                            "contig around the locus -- absent, or present but too diverged for a nucleotide seed -- and write one line "
+                            "per missing gene as a TSV table to a file")
+        g.add_argument("--rescue-flank", type=int, metavar="N", default=argparse.SUPPRESS,
+                       help="With --rescue: bases either side of every locus piece that are searched (0 .. 65535; default: 4096)")
+        g.add_argument("--rescue-min-score", type=int, metavar="N", default=argparse.SUPPRESS,
+                       help="With --rescue: alignment score below which a gene is called absent (default: 80)")
     g.add_argument("--pha4ge", metavar="FILE", nargs="?", const="kaptive_results.pha4ge", type=Path,
                    help="Write PHA4GE-compliant serotyping report to a TSV file (default: %(const)s)")
 
@@ -139,6 +147,12 @@ class _Parser(argparse.ArgumentParser):
         for flag in ("cs", "eqx"):
             if getattr(ns, flag, False) and not getattr(ns, "paf", None):
                 self.error(f"--{flag} requires --paf FILE")
+        for flag in ("rescue_flank", "rescue_min_score"):
+            if getattr(ns, flag, None) is not None:
+                if not getattr(ns, "rescue", None):
+                    self.error(f"--{flag.replace('_', '-')} requires --rescue FILE")
+                if getattr(ns, flag) < 0 or (flag == "rescue_flank" and ns.rescue_flank > 65535):
+                    self.error(f"--{flag.replace('_', '-')} is out of range")
         return ns, rest
 
 
@@ -212,6 +226,7 @@ class _TypingPipeline:
         self.want_paf = bool(getattr(args, "paf", None))  # every hit with its CIGAR: the alignment passes of this run leave them
         self.paf_cs, self.paf_eqx = bool(getattr(args, "cs", False)), bool(getattr(args, "eqx", False))  # ... and its cs string
         self.want = {r.name: bool(getattr(args, r.name, None)) for r in REPORTS}  # the tables of the kept lists: the reductions of this run leave their records
+        self.typer_options = {**self.want, **{k: getattr(args, k) for k in ("rescue_flank", "rescue_min_score") if getattr(args, k, None) is not None}}
         self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins", "paf", *self.want))  # the files' text (and contig names) are kept
         self.fasta_outputs = any(getattr(args, f, None) for f in ("loci", "genes", "proteins"))  # ... and result objects are built
         self.threads = max(1, args.threads or usable_cpus())  # (the cgroup's quota, not the 256 CPUs a container may see)
@@ -272,11 +287,11 @@ class _TypingPipeline:
                 if more:  # one pass for all of them; duplicate keywords and too many genes are refused here, before any typing
                     typer = MultiSerotyper([self.db, *more], max_other_genes=args.max_other_genes, min_completeness=args.min_completeness,
                                            allow_below_threshold=args.below_threshold, partial_edge_tolerance=args.partial_edge_tolerance,
-                                           device=device, **self.want)  # fmt: skip
+                                           device=device, **self.typer_options)  # fmt: skip
                 else:
                     typer = Serotyper(self.db, max_other_genes=args.max_other_genes, min_completeness=args.min_completeness,
                                       allow_below_threshold=args.below_threshold, partial_edge_tolerance=args.partial_edge_tolerance,
-                                      device=device, **self.want)  # fmt: skip
+                                      device=device, **self.typer_options)  # fmt: skip
                 typer._ctx_early = early_ctx
             self.typer = typer
             self.engine = self.typer.engine  # the context is created here, on the thread that will drive it

@@ -264,6 +264,11 @@ int kp_ctx_set_option(kp_ctx *ctx, const char *name, int64_t value) {
     else if (n == "cs") o.cs = value != 0;
     else if (n == "variants") o.variants = value != 0;
     else if (n == "aligned") o.aligned = value != 0;
+    else if (n == "rescue") o.rescue = value != 0;
+    else if (n == "rescue_flank") {
+        if (value > KP_RESCUE_FLANK_MAX) return kp_fail(ctx, KP_EINVAL, "rescue_flank must be within [0, 65535]");
+        o.rescue_flank = (int)value;
+    }
     else if (n == "upload_piece_mb") o.upload_piece_mb = (uint32_t)std::max<int64_t>(1, std::min<int64_t>(value, 4096));
     else return kp_fail(ctx, KP_EINVAL, "unknown option: " + n);
     return KP_OK;

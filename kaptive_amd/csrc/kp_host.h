@@ -72,7 +72,17 @@ struct KpAllelesState {  // kp_alleles.hip
     DevBuf<kp_allele> d_rec;
     DevBuf<uint64_t> d_piece;
 };
-struct KpDerived { KpRowLayout layout; KpKeptSrcState src; KpVariantsState var; KpAlignedState aln; KpBreakpointsState bp; KpAllelesState al; };
+struct KpRescueState {  // kp_rescue.hip; only where the context has the `rescue` option
+    bool valid = false;
+    int32_t flank = 0;           // the rescue_flank the records were made with (another one makes them again)
+    std::vector<int64_t> h_off;  // rec_off[n_asm + 1], then unit_off[n_asm + 1]: records / (subject, piece) units before every assembly
+    std::vector<kp_rescue> h_rec;
+    DevBuf<int64_t> d_off;
+    DevBuf<KpRescueUnit> d_units;
+    DevBuf<int32_t> d_cell, d_sub, d_ctl, d_scratch;
+    DevBuf<kp_rescue> d_rec;
+};
+struct KpDerived { KpRowLayout layout; KpKeptSrcState src; KpVariantsState var; KpAlignedState aln; KpBreakpointsState bp; KpAllelesState al; KpRescueState rs; };
 
 // Reduction state of one (batch, typing group): the group's hits (copied out of the batch's hit table with gene indices
 // rebased) and everything score / reduce / typing produce for it.
@@ -107,7 +117,7 @@ struct KpTypingRun {
     int32_t max_kept = 1, max_pieces = 1;
     KpDerived derived;  // the reports made from the kept list, on request (above)
     void invalidate_derived() {  // the kept list they describe is about to be replaced: flags only, every buffer stays (a settled context allocates nothing)
-        derived.layout.valid = derived.src.valid = derived.var.valid = derived.aln.valid = derived.bp.valid = derived.al.valid = false;
+        derived.layout.valid = derived.src.valid = derived.var.valid = derived.aln.valid = derived.bp.valid = derived.al.valid = derived.rs.valid = false;
     }
     // the only places the views of the kept and the piece rows are built (valid once derived.layout is)
     KpKeptRows kept_rows(int32_t gene_lo) const {
@@ -140,6 +150,8 @@ struct KpOptions : KpCapOptions {
     int variants = 0;               // variant records of the kept hits (kp_variants.hip); a pass with it computes the CIGARs too: the records are read off them
     int aligned = 0;                // aligned rows of the kept hits (kp_aligned.hip); a pass with it computes the CIGARs too: the rows are read off them
     int cs = 0;                     // cs difference strings of the finished hits (kp_cs.hip); a pass with it computes the CIGARs too: cs reads them
+    int rescue = 0;                 // rescue records of the missing genes (kp_rescue.hip); read when the records are asked for: no pass does anything for them
+    int rescue_flank = KP_RESCUE_FLANK;  // bases either side of a locus piece the translated search looks at (0 .. KP_RESCUE_FLANK_MAX)
     bool trace_summary = true;      // KAPTIVE_AMD_TRACE_SUMMARY=0: the band walks ignore the fills' piece summaries and fetch every piece on a path (kp_walk.h; A/B switch)
     bool join_stats = false;        // KAPTIVE_AMD_JOIN_STATS: kp_batch_wait reports the pass's group / join / mid_occ counts on stderr
     KpJoinLaunch join;              // KAPTIVE_AMD_JOIN_GRID / _JOIN_PRIO / _SKIP_JOINS: launch shape of the join kernels (kp_internal.h)

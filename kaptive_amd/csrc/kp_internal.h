@@ -364,6 +364,30 @@ void kp_launch_breakpoints(const KpBatchView &b, const KpKeptRows &kept, int max
 // lists them) -- a wave per row; prot: the reduction's protein buffers, prot_cap bytes per assembly.
 void kp_launch_alleles(const KpBatchView &b, const KpKeptRows &kept, const KpPieceRows &pieces, const uint8_t *prot, int prot_cap, kp_allele *out,
                        uint64_t *piece_out, hipStream_t stream);
+// kp_rescue.hip (after a reduction, when its rescue records are first asked for; only with the `rescue` option): the translated search
+// of every missing gene (kp_spec.h, RESCUE).  A unit is one (subject, piece): its window and six tasks, unit * KP_RS_FRAMES + the task
+// index's strand-and-frame part.  The host lays records and units out from the summaries (rec_off / unit_off [n_asm + 1] on the device:
+// assembly a has rec_off[a + 1] - rec_off[a] subjects with the same number of units each); the plan fills the units and every record
+// with "nothing found"; the fill leaves score and best cell per task in `cell` (four words), picks every subject's best task (sub:
+// four words per record -- first unit, units, winning task or -1, spare) and stores the winners' records.  ctl: KP_RS_CTL_WORDS zeroed
+// words -- the two fills' task counters and the longest frame text of a subject whose protein needs strips, from which the host sizes
+// `scratch` (KP_RS_SCRATCH_FIELDS x (that + 1) ints per block; null where no protein needs strips).
+struct KpTypingDb;
+struct KpRescueUnit { int32_t asm_id, rec, gene, piece, contig, ws, we, ctg_len; };  // ws == we: no window (the piece lies outside its contig)
+enum KpRescueCtl { KP_RS_CTL_QUEUE, KP_RS_CTL_QUEUE2, KP_RS_CTL_ROWS, KP_RS_CTL_WORDS = 4 };
+#define KP_RS_SCRATCH_FIELDS 6
+struct KpRescueTables {
+    const int64_t *rec_off, *unit_off;
+    int64_t n_rec, n_units;
+    KpRescueUnit *units;
+    int32_t *cell, *sub, *ctl;
+    kp_rescue *rec;
+    int32_t *scratch; size_t scratch_per_block;
+};
+void kp_launch_rescue_plan(const KpBatchView &b, const KpTypingDb &db, const kp_asm_summary *summary, const kp_piece *pieces, int piece_cap, int flank,
+                           const KpRescueTables &t, hipStream_t stream);
+void kp_launch_rescue_fill(const KpBatchView &b, const KpTypingDb &db, const int8_t *blosum, int edge_tolerance, const KpRescueTables &t, int n_blocks,
+                           hipStream_t stream);
 // kp_reduce.hip: assembly a's hits with gene in [gene_lo, gene_hi) (one run: hits are sorted by gene) -> out rows, gene
 // indices relative to gene_lo; out.count[a] = how many
 void kp_launch_hit_split(const KpHitTable &hits, int32_t gene_lo, int32_t gene_hi, const KpHitTable &out, int32_t n_asm, hipStream_t stream);

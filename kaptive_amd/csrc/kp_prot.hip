@@ -25,38 +25,13 @@
 #include <algorithm>
 
 #include "kp_internal.h"
+#include "kp_prot_cell.h"  // the cell update, its path statistics (Pay), the wave shifts and the BLOSUM62 staging: shared with kp_rescue.hip
 
 namespace {
 
-constexpr int NEGP = KP_PROT_NEG_INF;
-constexpr int GO = KP_PROT_GAP_OPEN + KP_PROT_GAP_EXT;
-constexpr int GE = KP_PROT_GAP_EXT;
 // (REG_MAX_LEN, QP, S2_CAP, WAVE_NC_MAX and KP_PROT_K choose a pair's path below; tests/protein_paths_util.py restates them and
 // that choice as path_of(), and its case tables hold both sides of every threshold: change them together.)
 constexpr int REG_MAX_LEN = 768;  // residues per sequence the register kernel stages (four pairs per block: 12 KB of LDS)
-
-// Path statistics a DP state carries: a = matches << 16 | mismatches, g = gaps that consumed a query row << 16 | gaps that
-// consumed a target column.  The start of the path is not carried (round 2 did: a third register through every select):
-// a path that ends in (bi, bj) has consumed matches + mismatches + row gaps rows and matches + mismatches + column gaps
-// columns, so start_i = bi - (m + mm + g_row) and start_j = bj - (m + mm + g_col) -- exactly what the reference's traceback
-// would reach (it stops at the first cell whose M is 0, which is where the counts were reset here).
-struct Pay {
-    unsigned a, g;
-};
-constexpr unsigned GAP_ROW = 0x10000u, GAP_COL = 1u;
-
-// one-lane wave shifts; the edge lane reads 0 (bound_ctrl) and is overridden by the caller where that matters
-__device__ __forceinline__ int from_lower(int v) {  // lane b <- lane b-1
-    return __builtin_amdgcn_mov_dpp(v, 0x138 /*wave_shr:1*/, 0xf, 0xf, true);
-}
-__device__ __forceinline__ int from_upper(int v) {  // lane b <- lane b+1
-    return __builtin_amdgcn_mov_dpp(v, 0x130 /*wave_shl:1*/, 0xf, 0xf, true);
-}
-
-struct Result {
-    int best, bi, bj;
-    Pay bp;
-};
 
 // ---- register path ------------------------------------------------------------------------------------------------------
 // Band of up to 64 diagonals on 16 lanes: lane l owns the four adjacent diagonals b = 4l .. 4l+3 (cells c = 0..3) and
@@ -77,55 +52,6 @@ __device__ __forceinline__ Pay row_lower(Pay p) {
 }
 __device__ __forceinline__ Pay row_upper(Pay p) {
     return Pay{(unsigned)row_upper((int)p.a), (unsigned)row_upper((int)p.g)};
-}
-
-struct PCell {
-    int m, dv, iv;
-    Pay pm, pd, pi;
-};
-
-__device__ __forceinline__ Pay pick(bool c, const Pay &x, const Pay &y) {
-    return Pay{c ? x.a : y.a, c ? x.g : y.g};
-}
-
-// one cell (i, j); `left` = (i, j-1): its M, I and their payloads; `up` = (i-1, j): its M, D and their payloads; the
-// diagonal neighbour (i-1, j-1) comes in as c.m / c.pm.  Same statements as the reference's kernel (see top), written
-// as selects: every lane executes the same instructions whatever its cell decides.
-template <bool ROW_MAJOR = true>  // false: the lane does not visit its cells in row-major order and ties are settled by (i, j)
-__device__ __forceinline__ void prot_cell(PCell &c, Result &r, bool in, int i, int j, unsigned c1, unsigned c2,
-                                          const int8_t *s_mat, int lm, int li, Pay lpm, Pay lpi, int um, int ud, Pay upm,
-                                          Pay upd) {
-    // D: gap arriving from above.  (A path starts at a cell whose M is 0: such a cell keeps the payload of its M state at
-    // zero -- the last statement below --, so none of its three readers has to ask.)
-    const int d_open = um - GO, d_ext = ud - GE;
-    int ndv = max(d_open, d_ext);
-    Pay npd = pick(d_open >= d_ext, upm, upd);
-    npd.g += GAP_ROW;
-    // I: gap arriving from the left
-    const int i_open = lm - GO, i_ext = li - GE;
-    int niv = max(i_open, i_ext);
-    Pay npi = pick(i_open >= i_ext, lpm, lpi);
-    npi.g += GAP_COL;
-    // M: diagonal first, then D, then I, each only if strictly better
-    Pay npm = c.pm;
-    const unsigned x1 = c1 & 255u, x2 = c2 & 255u;
-    const int sc = (int)s_mat[x1 * 32 + x2];  // (index 31 = a byte outside the alphabet: its row and column hold KP_PROT_FILL)
-    int bv = c.m + sc;
-    npm.a += ((c1 >> 8) == (c2 >> 8)) ? 0x10000u : 1u;
-    const bool take_d = ndv > bv;
-    bv = max(bv, ndv);
-    npm = pick(take_d, npd, npm);
-    const bool take_i = niv > bv;
-    bv = max(bv, niv);
-    npm = pick(take_i, npi, npm);
-    // cells outside the matrix or the band take boundary values, exactly as the reference's band array holds them
-    const int nm = in ? max(bv, 0) : 0;
-    // the first maximum in row-major order: a lane's cells come in that order (strict rise), or the tie is looked at
-    if (nm > r.best || (!ROW_MAJOR && nm == r.best && nm > 0 && (i < r.bi || (i == r.bi && j < r.bj)))) {
-        r.best = nm; r.bi = i; r.bj = j; r.bp = npm;
-    }
-    c.m = nm; c.dv = in ? ndv : NEGP; c.iv = in ? niv : NEGP;
-    c.pm = pick(nm == 0, Pay{0, 0}, npm); c.pd = npd; c.pi = npi;
 }
 
 // NC adjacent diagonals per lane: 4 covers any band of up to 64 diagonals; 3 covers 48, which is enough for the default band
@@ -392,22 +318,6 @@ __device__ __forceinline__ void store_result(Result r, int lane_in_group, int32_
             for (int x = 0; x < 8; ++x) o[x] = 0;
         }
     }
-}
-
-// compact substitution table in LDS: s_idx = index of each byte in ARNDCQEGHILKMFPSTWYVBJZX* (31 for everything else),
-// s_mat = the 32 x 32 corner of the reference's 256 x 256 lookup those indices address
-__device__ __forceinline__ void stage_blosum(const int8_t *__restrict__ blosum, int8_t *s_mat, uint8_t *s_idx, int lane) {
-    for (int c = lane; c < 256; c += 64) s_idx[c] = 31;
-    __syncthreads();
-    if (lane < 25) s_idx[(uint8_t)"ARNDCQEGHILKMFPSTWYVBJZX*"[lane]] = (uint8_t)lane;
-    __syncthreads();
-    for (int x = lane; x < 32 * 32; x += 64) {
-        const int a = x >> 5, c = x & 31;
-        s_mat[x] = (a < 25 && c < 25) ? blosum[(int)(uint8_t)"ARNDCQEGHILKMFPSTWYVBJZX*"[a] * 256 +
-                                               (int)(uint8_t)"ARNDCQEGHILKMFPSTWYVBJZX*"[c]]
-                                      : (int8_t)KP_PROT_FILL;
-    }
-    __syncthreads();
 }
 
 // ---- exact prefix: no DP needed ------------------------------------------------------------------------------------------------

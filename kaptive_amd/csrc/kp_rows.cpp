@@ -472,3 +472,61 @@ extern "C" int64_t kp_format_aligned(const kp_variant_tables *t, int32_t n_asm, 
     }
     return o.n;
 }
+
+// ---- rescue table (kp_spec.h, RESCUE) ---------------------------------------------------------------------------------------------
+// One line per record; the call is derived here, from the record's score, stops, edge and the share of the protein it covers.
+extern "C" int64_t kp_format_rescue(const kp_allele_tables *t, int32_t n_asm, const int32_t *prot_len, const int32_t *best_locus, const kp_rescue *recs,
+                                    const int64_t *rescue_off, int32_t min_score, char *out, int64_t cap) {
+    if (!t || n_asm < 0 || cap < 0 || (cap > 0 && !out)) return KP_EINVAL;
+    if (n_asm > 0 && (!rescue_off || !best_locus || !prot_len || !t->names.asm_name_off || !t->names.asm_first_ctg || !t->locus_name_off)) return KP_EINVAL;
+    if (n_asm > 0 && (rescue_off[n_asm] < rescue_off[0] || (rescue_off[n_asm] > rescue_off[0] && !recs))) return KP_EINVAL;
+    Out o{out, cap};
+    auto fixed2 = [&o](long long num, long long den) {  // "%.2f" of num / den (0 where den is 0)
+        char buf[64];
+        o.put(buf, std::snprintf(buf, sizeof buf, "%.2f", den > 0 ? (double)num / (double)den : 0.0));
+    };
+    for (int a = 0; a < n_asm; ++a) {
+        if (rescue_off[a + 1] < rescue_off[a]) return KP_EINVAL;
+        if (rescue_off[a + 1] == rescue_off[a]) continue;
+        const int best = best_locus[a];
+        if (best < 0 || best >= t->n_loci) return KP_EINVAL;
+        const int64_t c0 = t->names.asm_first_ctg[a], nc = t->names.asm_first_ctg[a + 1] - c0;
+        for (int64_t i = rescue_off[a]; i < rescue_off[a + 1]; ++i) {
+            const kp_rescue &r = recs[i];
+            const bool found = r.score > 0;
+            if (r.gene < 0 || r.gene >= t->names.n_genes || (found && (r.contig < 0 || r.contig >= nc || r.frame > 2))) return KP_EINVAL;
+            const long long plen = prot_len[r.gene], span = (long long)r.p_end - r.p_start, cols = (long long)r.matches + r.mismatches + r.gaps;
+            const bool short_cov = span * 100 < 90 * plen;
+            // (an alignment that reaches the protein's trailing * ends on the gene's own stop: a local path ends on a positive column, and * scores
+            // positive against * only.  That stop interrupts nothing.)
+            const long long inner_stops = (long long)r.stops - (found && plen > 0 && r.p_end == plen ? 1 : 0);
+            const char *call = r.score < min_score ? "absent" : (inner_stops > 0 ? "interrupted" : (short_cov ? (r.edge ? "partial" : "fragment") : "diverged"));
+            put_name(o, t->names.asm_names, t->names.asm_name_off, a); o.put('\t');
+            put_name(o, t->locus_names, t->locus_name_off, best); o.put('\t');
+            put_name(o, t->names.gene_names, t->names.gene_name_off, r.gene); o.put('\t');
+            put_i(o, plen); o.put('\t');
+            o.lit(call); o.put('\t');
+            put_i(o, r.score); o.put('\t');
+            if (found) {
+                put_name(o, t->names.ctg_names, t->names.ctg_name_off, c0 + r.contig); o.put('\t');
+                put_i(o, (long long)r.t_start + 1); o.put('\t');
+                put_i(o, r.t_end); o.put('\t');
+                o.put(r.strand < 0 ? '-' : '+'); o.put('\t');
+                put_i(o, (long long)r.frame + 1); o.put('\t');
+                put_i(o, (long long)r.p_start + 1); o.put('\t');
+                put_i(o, r.p_end); o.put('\t');
+            } else {
+                o.lit(".\t.\t.\t.\t.\t.\t.\t");
+            }
+            put_i(o, r.matches); o.put('\t');
+            put_i(o, r.mismatches); o.put('\t');
+            put_i(o, r.gaps); o.put('\t');
+            fixed2((long long)r.matches * 100, cols); o.put('\t');
+            fixed2(span * 100, plen); o.put('\t');
+            put_i(o, r.stops); o.put('\t');
+            o.lit(!found || !r.edge ? "." : (r.edge == 3 ? "both" : (r.edge == 1 ? "start" : "end")));
+            o.put('\n');
+        }
+    }
+    return o.n;
+}

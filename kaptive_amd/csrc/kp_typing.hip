@@ -1,6 +1,7 @@
 // kp_typing.hip -- batched typing (locus scores, the reduction of a batch's hits, gene states, the variant and breakpoint records, the allele
-// digests and the aligned rows of the kept hits; per typing group), stand-alone protein aligner.
+// digests and the aligned rows of the kept hits, the rescue records of the missing genes; per typing group), stand-alone protein aligner.
 #include "kp_host.h"
+#include "kp_rescue.h"
 
 // the typing group a batch currently addresses and the run of the batch's work set for it (created on first use)
 static KpTypingGroup *typing_group(kp_ctx *ctx, const kp_batch *b) {
@@ -259,7 +260,9 @@ int kp_batch_typing(kp_ctx *ctx, kp_batch *b, kp_asm_summary *summaries, kp_kept
 //   4 group's run not reduced since the  KP_ESTATE, "kp_batch_reduce has not     KP_EINVAL, ALIGNED_NOT_REDUCED   KP_EINVAL, NO_BREAKPOINTS              KP_EINVAL, NO_ALLELES
 //     hit table was made                 been called"
 // The variant records answer KP_ESTATE where a call is missing, as kp_batch_typing does; the later reports KP_EINVAL with their own text
-// throughout.  kp_batch_set_hits clears cigar_valid and resets the runs: 2 for variants and aligned, 4 for the others.  Then the device is
+// throughout.  kp_batch_set_hits clears cigar_valid and resets the runs: 2 for variants and aligned, 4 for the others.  The rescue
+// records (further down) answer like the allele digests, with NO_RESCUE, and before anything else KP_EINVAL with the same text where the
+// context's `rescue` option is off.  Then the device is
 // made current and the summaries are fetched (the reduction run again where a buffer overflowed): their errors pass through.  `code`: that
 // of 1 and 4; `no_records`: the text of 1-3 under KP_EINVAL; `not_reduced`: the text of 4; `option`: the flag of 2, or null.  The run: *R_out.
 static const char *const NO_VARIANTS = "this batch has no variant records (aligned without the variants option, or its hit table was replaced)";
@@ -524,6 +527,90 @@ int kp_batch_alleles(kp_ctx *ctx, kp_batch *b, kp_allele *out, int32_t kept_stri
         std::copy(A.h_rec.begin() + kept_off[a], A.h_rec.begin() + kept_off[a + 1], out + a * (size_t)kept_stride);
         std::copy(A.h_piece.begin() + piece_off[a], A.h_piece.begin() + piece_off[a + 1], piece_out + a * (size_t)piece_stride);
     }
+    return KP_OK;
+}
+
+// ---- rescue records of the missing genes (kp_rescue.hip; kp_spec.h, RESCUE) ---------------------------------------------------------
+// The records of the batch's current group: one per set bit of the summaries' missing masks, laid out here from the summaries the
+// report has fetched; the plan, the score-only fill over every frame, the pick and the winners' fill with path statistics follow on
+// the reduction's stream.  They need the summaries, the pieces, the batch's contigs and the database's proteins only.  The one
+// buffer whose size the host cannot know -- the strips' boundary column, for proteins beyond 384 residues -- is sized from the
+// longest such frame text, which the plan leaves and one read-back fetches (only where the database has such a protein).
+static const char *const NO_RESCUE = "this batch has no rescue records: the rescue option is off, or kp_batch_reduce has not run for this group since its hit table was made";
+
+static int ensure_rescue(kp_ctx *ctx, kp_batch *b, KpTypingRun **R_out) {
+    if (!ctx || !b || b->ctx != ctx) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    if (!ctx->opt.rescue) return kp_fail(ctx, KP_EINVAL, NO_RESCUE);
+    KpWork *w = nullptr;
+    if (int rc = report_run(ctx, b, KP_EINVAL, NO_RESCUE, NO_RESCUE, nullptr, &w, R_out)) return rc;
+    KpTypingRun &R = **R_out;
+    KpRescueState &S = R.derived.rs;
+    const int32_t flank = ctx->opt.rescue_flank;
+    if (S.valid && S.flank == flank) return KP_OK;
+    const size_t n_asm = (size_t)b->n_asm;
+    if (int rc = ensure_layout(ctx, R, n_asm)) return rc;
+    const KpTypingGroup &T = *typing_group(ctx, b);
+    S.valid = false;
+    S.h_off.assign(2 * (n_asm + 1), 0);
+    int64_t *const rec_off = S.h_off.data(), *const unit_off = rec_off + n_asm + 1;
+    const int64_t *const piece_off = R.derived.layout.piece_off();
+    for (size_t a = 0; a < n_asm; ++a) {
+        int n = 0;
+        if (!(R.h_sums[a].overflow & 4))
+            for (int x = 0; x < KP_MAX_LOCUS_GENES / 64; ++x) n += __builtin_popcountll(R.h_sums[a].missing_mask[x]);
+        rec_off[a + 1] = rec_off[a] + n;
+        unit_off[a + 1] = unit_off[a] + (int64_t)n * (piece_off[a + 1] - piece_off[a]);
+    }
+    const int64_t n_rec = rec_off[n_asm], n_units = unit_off[n_asm];
+    if (n_units > 0x7FFFFFFFll / (4 * KP_RS_FRAMES)) return kp_fail(ctx, KP_EOVERFLOW, "too many missing genes and locus pieces for one rescue pass; use smaller batches");
+    S.h_rec.assign((size_t)n_rec, kp_rescue{});
+    if (n_rec > 0) {
+        if (int rc = upload(ctx, S.d_off, S.h_off.data(), S.h_off.size(), R.stream)) return rc;
+        KP_HIP_CHECK(ctx, S.d_rec.reserve((size_t)n_rec));
+        KP_HIP_CHECK(ctx, S.d_sub.reserve(4 * (size_t)n_rec));
+        KP_HIP_CHECK(ctx, S.d_units.reserve((size_t)std::max<int64_t>(n_units, 1)));
+        KP_HIP_CHECK(ctx, S.d_cell.reserve(4 * (size_t)KP_RS_FRAMES * (size_t)std::max<int64_t>(n_units, 1)));
+        KP_HIP_CHECK(ctx, S.d_ctl.reserve(KP_RS_CTL_WORDS));
+        KP_HIP_CHECK(ctx, hipMemsetAsync(S.d_ctl.p, 0, KP_RS_CTL_WORDS * sizeof(int32_t), R.stream));
+        KpRescueTables t{.rec_off = S.d_off.p, .unit_off = S.d_off.p + n_asm + 1, .n_rec = n_rec, .n_units = n_units, .units = S.d_units.p,
+                         .cell = S.d_cell.p, .sub = S.d_sub.p, .ctl = S.d_ctl.p, .rec = S.d_rec.p, .scratch = nullptr, .scratch_per_block = 0};
+        kp_launch_rescue_plan(b->view, T.typing, R.d_summary.p, R.d_pieces.p, R.piece_cap, flank, t, R.stream);
+        KP_HIP_CHECK(ctx, hipGetLastError());
+        int n_blocks = 4096;  // one wave each; the waves take the tasks off a counter
+        if (n_units > 0 && kp_rs_needs_strips(T.max_db_prot_len)) {
+            int32_t rows = 0;
+            if (int frc = fetch_all(ctx, R.stream, {{&rows, S.d_ctl.p + KP_RS_CTL_ROWS, sizeof(int32_t)}})) return frc;
+            if (rows > 0) {
+                n_blocks = 512;  // (a boundary column per block: 24 bytes a row)
+                t.scratch_per_block = (size_t)KP_RS_SCRATCH_FIELDS * ((size_t)rows + 1);
+                KP_HIP_CHECK(ctx, S.d_scratch.reserve(t.scratch_per_block * (size_t)n_blocks));
+                t.scratch = S.d_scratch.p;
+            }
+        }
+        kp_launch_rescue_fill(b->view, T.typing, ctx->d_blosum.p, R.prm.edge_tolerance, t, n_blocks, R.stream);
+        KP_HIP_CHECK(ctx, hipGetLastError());
+        if (int frc = fetch_all(ctx, R.stream, {{S.h_rec.data(), S.d_rec.p, (size_t)n_rec * sizeof(kp_rescue)}})) return frc;
+    }
+    S.flank = flank;
+    S.valid = true;
+    return KP_OK;
+}
+
+int kp_batch_rescue_offsets(kp_ctx *ctx, kp_batch *b, int64_t *rescue_off) {
+    if (!ctx || !b || b->ctx != ctx || !rescue_off) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpTypingRun *R = nullptr;
+    if (int rc = ensure_rescue(ctx, b, &R)) return rc;
+    std::copy(R->derived.rs.h_off.begin(), R->derived.rs.h_off.begin() + b->n_asm + 1, rescue_off);
+    return KP_OK;
+}
+
+int kp_batch_rescue(kp_ctx *ctx, kp_batch *b, kp_rescue *out, int64_t cap) {
+    if (!ctx || !b || b->ctx != ctx || (!out && cap > 0)) return kp_fail(ctx, KP_EINVAL, "bad arguments");
+    KpTypingRun *R = nullptr;
+    if (int rc = ensure_rescue(ctx, b, &R)) return rc;
+    const std::vector<kp_rescue> &rec = R->derived.rs.h_rec;
+    if (cap < (int64_t)rec.size()) return kp_fail(ctx, KP_EINVAL, "rescue buffer too small");
+    std::copy(rec.begin(), rec.end(), out);
     return KP_OK;
 }
 

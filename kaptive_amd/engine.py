@@ -31,7 +31,7 @@ class Engine:
 
     def __init__(self, db: "Database | Sequence[Database]", device: int = 0, ctx: "_native.Context | None" = None,
                  cigar: bool = False, cs: bool = False, variants: bool = False, breakpoints: bool = False, alleles: bool = False,
-                 aligned: bool = False) -> None:
+                 aligned: bool = False, rescue: bool = False, rescue_flank: "int | None" = None) -> None:
         """``ctx``: a context of ``device`` the caller created ahead of time (the command line starts the runtime on a thread
         of its own while the database file is still being read); otherwise one is created here.  ``cigar``: alignment passes
         also leave the CIGAR of every hit (``Batch.cigars``; ``align`` then fills ``Alignments.cigars``) -- a second walk of
@@ -46,7 +46,11 @@ class Engine:
         include/kp_spec.h, ALLELES): ``BatchTyping.alleles()`` / ``.locus_alleles()`` / ``.alleles_tsv()``.  One kernel behind the
         reduction; the alignment passes do nothing more for them either.  ``aligned``: every typing path also fetches the aligned rows
         of the kept hits (``Batch.aligned``; include/kp_spec.h, ALIGNED ROWS): ``BatchTyping.aligned()`` / ``.aligned_codes()`` /
-        ``.aligned_tsv()``.  They are read off the ops, so such passes compute the CIGARs as well."""
+        ``.aligned_tsv()``.  They are read off the ops, so such passes compute the CIGARs as well.  ``rescue``: every typing path
+        also fetches the rescue records of the genes the reduction lists as missing (``Batch.rescue``; include/kp_spec.h, RESCUE):
+        ``BatchTyping.rescue()`` / ``.rescue_tsv()`` -- every such gene's protein aligned against the six-frame translation of the contig
+        around the locus pieces, ``rescue_flank`` bases either side (default ``_native.RESCUE_FLANK``).  Kernels behind the reduction;
+        the alignment passes do nothing more for them."""
         dbs = list(db) if isinstance(db, (list, tuple)) else [db]
         self.dbs = dbs
         self.db = dbs[0]
@@ -58,6 +62,9 @@ class Engine:
         self.breakpoints = bool(breakpoints)
         self.alleles = bool(alleles)
         self.aligned = bool(aligned)
+        self.rescue = bool(rescue)
+        if rescue_flank is not None and not self.rescue:
+            raise ValueError("rescue_flank needs rescue=True")
         self.cigar = bool(cigar) or self.cs or self.variants or self.aligned
         if self.cigar:
             self.ctx.set_option("cigar", 1)
@@ -67,6 +74,10 @@ class Engine:
             self.ctx.set_option("variants", 1)
         if self.aligned:
             self.ctx.set_option("aligned", 1)
+        if self.rescue:
+            self.ctx.set_option("rescue", 1)
+            if rescue_flank is not None:
+                self.ctx.set_option("rescue_flank", int(rescue_flank))
         for d in dbs:  # KP_MAX_GENE_LEN (include/kp_spec.h): query positions are 16-bit fields of the anchor and hit keys
             too_long = np.flatnonzero(np.asarray(d.genes.lengths) > _native.MAX_GENE_LEN)
             if len(too_long):

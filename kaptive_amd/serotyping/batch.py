@@ -102,11 +102,11 @@ class BatchTyping:
     phenotype, n_pieces, n_hits (hits kept in the result).
     """
 
-    def __init__(self, typer, ids, sums, kept, pieces, scores, best, genomes=None, variants=None, breakpoints=None, alleles=None, aligned=None) -> None:
-        """``variants`` / ``breakpoints`` / ``alleles`` / ``aligned``: what the ``Batch`` method of that name gave (one row of
+    def __init__(self, typer, ids, sums, kept, pieces, scores, best, genomes=None, variants=None, breakpoints=None, alleles=None, aligned=None, rescue=None) -> None:
+        """``variants`` / ``breakpoints`` / ``alleles`` / ``aligned`` / ``rescue``: what the ``Batch`` method of that name gave (one row of
         ``_native.REPORTS`` each), where the engine was made with that option."""
         self.typer, self.ids, self.genomes = typer, list(ids), genomes
-        self._variants, self._breakpoints, self._alleles, self._aligned = variants, breakpoints, alleles, aligned
+        self._variants, self._breakpoints, self._alleles, self._aligned, self._rescue = variants, breakpoints, alleles, aligned, rescue
         self.sums, self.kept, self.pieces = sums, kept, pieces
         db = typer._db
         n = len(sums)
@@ -310,6 +310,26 @@ class BatchTyping:
 
         rows, blocks, names, first = self._report("aligned", tables=True)
         return _native.format_aligned(self.typer._db.genes.ids, self.ids, names, first, self.sums["n_kept"], self.kept, rows, blocks)
+
+    def rescue(self):
+        """``(records, rescue_off)``: the rescue records (``_native.RESCUE_DTYPE``; include/kp_spec.h, RESCUE) of the genes the batch's
+        summaries list as missing -- ``records[rescue_off[i]:rescue_off[i + 1]]`` are assembly i's, one per missing gene in ascending
+        gene order; ``records["piece"]`` indexes ``self.pieces[i]``, -1 where nothing was found.  Only where the engine was made with
+        ``rescue=True``."""
+        return self._report("rescue")
+
+    def rescue_tsv(self, min_score: "int | None" = None) -> bytes:
+        """The lines of the rescue table (``--rescue``; no header: ``_native.RESCUE_HEADER``), formatted by the native library from
+        the records (kp_format_rescue); ``min_score``: the score below which a gene is called ``absent`` (default: the typer's
+        ``rescue_min_score``).  Contig names come from the genomes: ``genomes`` must have been given."""
+        from kaptive_amd import _native
+
+        records, rescue_off, names, first = self._report("rescue", tables=True)
+        db = self.typer._db
+        if min_score is None:
+            min_score = getattr(self.typer, "rescue_min_score", _native.RESCUE_MIN_SCORE)
+        return _native.format_rescue(db.genes.ids, db.loci.ids, self.ids, names, first, db.translations.lengths, self.best_locus, records, rescue_off,
+                                     min_score)
 
     def jsonl(self) -> bytes:
         """The JSON lines of the whole batch (``-j``), from the batch's columns and the genomes' text (``genomes`` must have

@@ -47,18 +47,27 @@ class Serotyper:
         breakpoints: bool = False,
         alleles: bool = False,
         aligned: bool = False,
+        rescue: bool = False,
+        rescue_flank: "int | None" = None,
+        rescue_min_score: "int | None" = None,
     ) -> None:
         """``preset`` and ``scoring_metric`` are accepted and ignored, as in the reference.
         ``aligner`` / ``protein_aligner`` replace the HIP stages; tests use them to feed recorded hits.  ``variants``: the engine
         this typer creates also leaves the variant records of the kept hits (``Engine(db, variants=True)``); ``breakpoints``: it leaves
         the breakpoint records of the kept lists (``Engine(db, breakpoints=True)``); ``alleles``: it leaves the allele digests of the
         kept records and the locus pieces (``Engine(db, alleles=True)``); ``aligned``: it leaves the aligned rows of the kept hits
-        (``Engine(db, aligned=True)``)."""
+        (``Engine(db, aligned=True)``); ``rescue``: it leaves the rescue records of the missing genes (``Engine(db, rescue=True,
+        rescue_flank=...)``), and ``rescue_min_score`` is the score below which their table calls a gene ``absent`` (default
+        ``_native.RESCUE_MIN_SCORE``)."""
         self._db = db
         self._variants = bool(variants)
         self._breakpoints = bool(breakpoints)
         self._alleles = bool(alleles)
         self._aligned = bool(aligned)
+        self._rescue, self._rescue_flank = bool(rescue), rescue_flank
+        if (rescue_flank is not None or rescue_min_score is not None) and not rescue:
+            raise ValueError("rescue_flank and rescue_min_score need rescue=True")
+        self.rescue_min_score = 80 if rescue_min_score is None else int(rescue_min_score)  # _native.RESCUE_MIN_SCORE (KP_RESCUE_MIN_SCORE)
         self.max_other_genes = max_other_genes
         self.min_completeness = min_completeness
         self.allow_below_threshold = allow_below_threshold
@@ -96,7 +105,8 @@ class Serotyper:
             early = getattr(self, "_ctx_early", None)  # (a future of _native.Context: kaptive_amd/cli.py starts the runtime early)
             self._ctx_early = None
             self._engine = Engine(self._db, device=self._device, ctx=early.result() if early is not None else None, variants=self._variants,
-                                  breakpoints=self._breakpoints, alleles=self._alleles, aligned=self._aligned)
+                                  breakpoints=self._breakpoints, alleles=self._alleles, aligned=self._aligned, rescue=self._rescue,
+                                  rescue_flank=self._rescue_flank)
         return self._engine
 
     def align(self, genome: GenomeAssembly) -> Alignments:
@@ -420,6 +430,9 @@ class MultiSerotyper:
         breakpoints: bool = False,
         alleles: bool = False,
         aligned: bool = False,
+        rescue: bool = False,
+        rescue_flank: "int | None" = None,
+        rescue_min_score: "int | None" = None,
     ) -> None:
         self.dbs = list(dbs)
         check_databases(self.dbs)
@@ -428,10 +441,12 @@ class MultiSerotyper:
         self._breakpoints = bool(breakpoints)
         self._alleles = bool(alleles)
         self._aligned = bool(aligned)
+        self._rescue, self._rescue_flank = bool(rescue), rescue_flank
         self._engine = None
         self.serotypers = tuple(
             Serotyper(db, max_other_genes, min_completeness, allow_below_threshold, partial_edge_tolerance=partial_edge_tolerance,
-                      device=device, variants=variants, breakpoints=breakpoints, alleles=alleles, aligned=aligned) for db in self.dbs
+                      device=device, variants=variants, breakpoints=breakpoints, alleles=alleles, aligned=aligned, rescue=rescue, rescue_flank=rescue_flank,
+                      rescue_min_score=rescue_min_score) for db in self.dbs
         )  # fmt: skip
 
     @property
@@ -443,7 +458,8 @@ class MultiSerotyper:
             early = getattr(self, "_ctx_early", None)  # (as Serotyper.engine: a context the command line started early)
             self._ctx_early = None
             self._engine = Engine(self.dbs, device=self._device, ctx=early.result() if early is not None else None, variants=self._variants,
-                                  breakpoints=self._breakpoints, alleles=self._alleles, aligned=self._aligned)
+                                  breakpoints=self._breakpoints, alleles=self._alleles, aligned=self._aligned, rescue=self._rescue,
+                                  rescue_flank=self._rescue_flank)
             for i, s in enumerate(self.serotypers):
                 s._engine = self._engine.view(i)
         return self._engine

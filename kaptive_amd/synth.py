@@ -102,6 +102,33 @@ def revcomp(seq: np.ndarray) -> np.ndarray:
     return COMP_MAP[seq[::-1]]
 
 
+_AA = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"  # NCBI 11, codons in TCAG order
+CODONS = {a + b + c: aa for (a, b, c), aa in zip(((a, b, c) for a in "TCAG" for b in "TCAG" for c in "TCAG"), _AA)}
+_BY_AA: dict = {}
+for _codon, _aa in CODONS.items():
+    _BY_AA.setdefault(_aa, []).append(_codon)
+_RESIDUES = sorted(a for a in _BY_AA if a != "*")
+
+
+def recode_orf(rng: np.random.Generator, orf: np.ndarray, substituted: float = 0.25) -> np.ndarray:
+    """The ORF codon by codon: another codon of the same amino acid wherever there is one, and about ``substituted`` of the residues
+    replaced by another amino acid; the start codon stays, the stop becomes another stop.  Such a gene shares no 15-mer with its
+    original (every codon but ATG / TGG changes) and still encodes a protein about three quarters identical to it: what a
+    nucleotide seed misses and a translated search finds."""
+    text = bytes(orf).decode()
+    if len(text) % 3:
+        raise ValueError("an ORF has whole codons")
+    out = [text[:3]]
+    for i in range(3, len(text), 3):
+        cod = text[i : i + 3]
+        aa = CODONS[cod]
+        if aa != "*" and rng.random() < substituted:
+            aa = _RESIDUES[int(rng.integers(len(_RESIDUES)))]
+        alt = [c for c in _BY_AA[aa] if c != cod] or [cod]
+        out.append(alt[int(rng.integers(len(alt)))])
+    return np.frombuffer("".join(out).encode(), np.uint8).copy()
+
+
 def make_db(kind: str = "kpsc_k", seed: int = 100, n_loci: int | None = None, id_threshold: float = 82.5) -> Database:
     shape = DB_SHAPES[kind]
     rng = np.random.default_rng(seed)
