@@ -10,6 +10,7 @@ Every expected value in the fixtures is an output of reference code:
   intervals.npz    kaptive.core.interval.Intervals.cull_overlaps / cluster_spatial (interval.py:435-493)
   seqs.npz         kaptive.core.seq.Sequences.extract / translate    (src/kaptive/core/seq.py:327-408)
   typing_*.npz     kaptive.serotyping.core.Serotyper.__call__ + KaptiveRow/Pha4geRow (core.py:124-486, io.py)
+  typing_rules_*.npz  the same, on the constructed tables of tests/reduction_rules_util.py (gen_typing_rules)
 """
 
 from __future__ import annotations
@@ -526,9 +527,44 @@ def gen_compare() -> None:
     print(f"compare: {len(e)} edges between {n_loci} loci ({time.time() - t0:.0f} s)")
 
 
+def gen_typing_rules() -> None:
+    """tests/golden/typing_rules_<key>.npz: every case of tests/reduction_rules_util.py -- hit tables that sit on the rules and
+    round edges of the typing reduction, over a planted "rules assembly" per golden database -- through the REFERENCE's
+    Serotyper (core.py:124-486), the tables replayed by the rammappy stand-in.  Per database one file (all groups fit under the size of the largest older fixture, so none is split off): the assembly once,
+    then the cases' groups, tables, Serotyper keywords and everything run_reference_typing records, a field of
+    all cases as one array (reduction_rules_util.pack_records; the two large sequence blobs as digests).  Reads
+    db_k.npz / db_o.npz and writes nothing else."""
+    from tests import reduction_rules_util as U
+    from tests.golden_util import load_db
+
+    t0, n = time.time(), 0
+    for key in ("k", "o"):
+        db, R = load_db(key), U.rules_assembly(key)
+        ref_db = to_ref_db(db)
+        c = R.genome.contigs
+        cases, records = U.cases(key), []
+        for case in cases:
+            exp = run_reference_typing(ref_db, RefSerotyper(ref_db, **case.kwargs), R.genome, case.hits)
+            exp["typer_kwargs_json"] = np.frombuffer(json.dumps(case.kwargs).encode(), np.uint8)
+            for f in U.DIGESTED:
+                exp[f] = U.digest(exp[f])
+            records.append(exp)
+        sizes = np.array([len(x.hits) for x in cases], np.int64)
+        np.savez_compressed(
+            U.fixture_path(key),
+            db_key=np.array(key), genome_id=np.array(R.genome.id), contig_ids=np.array(list(c.ids), dtype="U"), contig_seqs=c.seqs,
+            contig_lengths=c.lengths, names=np.array([x.name for x in cases], dtype="U"), groups=np.array([x.group for x in cases], dtype="U"),
+            hits=np.concatenate([x.hits for x in cases]), hit_off=np.concatenate([[0], np.cumsum(sizes)]),
+            **{f"exp.{k}": v for k, v in U.pack_records(records).items()},
+        )  # fmt: skip
+        n += len(cases)
+        print(f"typing_rules_{key}: {len(cases)} cases, {U.fixture_path(key).stat().st_size >> 10} KB")
+    print(f"typing rules: {n} cases through the reference in {time.time() - t0:.1f}s")
+
+
 def main() -> None:
     OUT.mkdir(parents=True, exist_ok=True)
-    what = set(sys.argv[1:]) or {"protein", "protein_seeded", "intervals", "seqs", "typing", "genbank", "compare"}
+    what = set(sys.argv[1:]) or {"protein", "protein_seeded", "intervals", "seqs", "typing", "genbank", "compare", "typing_rules"}
     if "compare" in what:
         gen_compare()
     if "protein_seeded" in what:
@@ -543,6 +579,8 @@ def main() -> None:
         gen_seqs(np.random.default_rng(3))
     if "typing" in what:
         gen_typing()
+    if "typing_rules" in what:
+        gen_typing_rules()
     if "typing_full" in what:  # only the full-size cases that are not there yet (the index gains their names)
         gen_typing_full_missing()
 
