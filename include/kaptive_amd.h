@@ -545,6 +545,31 @@ KP_API int64_t kp_format_aligned(const kp_variant_tables *tables, int32_t n_asm,
 KP_API int64_t kp_format_rescue(const kp_allele_tables *tables, int32_t n_asm, const int32_t *prot_len, const int32_t *best_locus, const kp_rescue *records,
                                 const int64_t *rescue_off, int32_t min_score, char *out, int64_t cap);
 
+/* ---- pairwise locus distances (kp_spec.h, DISTANCES) -----------------------------------------------------------------------------
+ * The one result that spans batches: the caller collects the locus rows of every assembly of a run that carries one locus and hands
+ * them over as a matrix.  The handle holds the matrix's bit planes on the device and nothing else of the context's; it needs no
+ * database and no batch, and a run that never creates one allocates and launches nothing for it.
+ *   kp_dist_create : blocks is the [n_rows, n_blocks] matrix of locus rows, row-major, padding flagged; it is uploaded and turned
+ *                    into planes.  KP_EINVAL for null pointers, n_rows < 0, n_blocks <= 0 with n_rows > 0, 16 * n_blocks >= 2^31
+ *                    and n_rows > KP_DIST_MAX_ROWS (kp_caps.h).  n_rows of 0 or 1 is valid and gives 0 pairs.
+ *   kp_dist_count  : counts the listed pairs for (max_diff, min_compared) into *n_pairs.
+ *   kp_dist_pairs  : the pairs of the last kp_dist_count, ascending (a, b); KP_ESTATE without one, KP_EINVAL if cap is short.
+ *   kp_dist_destroy: frees the handle's device memory (while its context lives; a null handle is ignored).
+ * kp_device_allocations does not count what a handle does: it shows whether a stream of batches has settled, and a handle works
+ * outside that stream.  Its planes and tables are allocated once, in kp_dist_create; only the record buffer is replaced -- freed
+ * and allocated anew, which waits for the device like any allocation -- when a listing is longer than every one before it. */
+typedef struct kp_dist kp_dist;
+KP_API int kp_dist_create(kp_ctx *ctx, const uint64_t *blocks, int32_t n_rows, int64_t n_blocks, kp_dist **out);
+KP_API int kp_dist_count(kp_ctx *ctx, kp_dist *d, int32_t max_diff, int32_t min_compared, int64_t *n_pairs);
+KP_API int kp_dist_pairs(kp_ctx *ctx, kp_dist *d, kp_dist_pair *out, int64_t cap);
+KP_API void kp_dist_destroy(kp_dist *d);
+/* The distance table of one locus (host only): one tab-separated line per pair, in the pairs' order: Locus, Assembly A, Assembly B,
+ * Columns (the locus's total gene length), Compared, Differences, Unshared.  No header line.  names / name_off [n_names + 1]: the
+ * assemblies' names by row of the matrix.  Return value as kp_format_variants has it; KP_EINVAL also for a pair that names a row
+ * outside [0, n_names). */
+KP_API int64_t kp_format_distances(const char *locus_name, int32_t locus_name_len, int64_t columns, const char *names, const int64_t *name_off,
+                                   int32_t n_names, const kp_dist_pair *pairs, int64_t n_pairs, char *out, int64_t cap);
+
 /* ---- JSON lines of a whole batch (host only) ----------------------------------------------------------------------------------
  * Replaces orjson.dumps(SerotypingResult.to_dict(), OPT_SERIALIZE_NUMPY | OPT_APPEND_NEWLINE) per genome
  * (src/kaptive/serotyping/cli.py:67-76, src/kaptive/serotyping/models.py:629-654) together with the construction of the

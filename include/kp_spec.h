@@ -638,4 +638,41 @@ typedef struct kp_rescue {
     uint8_t pad_;             /* zero */
 } kp_rescue;
 
+/* ---- DISTANCES (optional; the first report about PAIRS of assemblies: no hit, no kept record and no report byte depends on it) -----
+ * How many bases apart are the loci of two isolates that carry the same locus?  The aligned rows already put every isolate's genes
+ * on the database's coordinates; a LOCUS ROW strings the rows of one locus's genes together, and a pair of locus rows reduces to
+ * three counts.
+ *
+ * LOCUS ROW.  One per assembly and database.  It covers the genes of the assembly's best locus, locus_gene_off[best] .. +
+ * locus_gene_len[best], in database order; gene g contributes (Lq + 15) / 16 blocks in the ALIGNED ROWS packed form, back to back.
+ * Its blocks are those of the aligned row of the gene's kept record that carries KP_F_PRIMARY -- there is at most one per expected
+ * gene --; without such a record the gene's blocks are all GAP.  Other kept records of the gene (fragments, copies outside the
+ * locus) contribute nothing.
+ * PADDING.  The columns at or beyond Lq in a gene's last block have their GAP bit set in a locus row.  This is the one difference
+ * from the ALIGNED ROWS block format, where those columns carry no bit at all -- left that way they would read as base a on both
+ * sides of a pair.  All locus rows of one locus have the same number of blocks, NB.
+ * COUNTS of a pair (a, b), a < b, rows of the same locus, over all 16 NB columns.  compared: columns where both rows hold a code
+ * 0..3 (neither GAP nor N).  differences: compared columns whose codes differ.  unshared: columns where exactly one row is GAP --
+ * gene content present in one isolate and absent, or not aligned, in the other.  N against anything is neither compared nor
+ * unshared; GAP against GAP (padding against padding included) is neither.  All three are int32: a locus of 16 NB >= 2^31 columns
+ * is refused.
+ * LISTED PAIRS.  A pair is listed iff differences <= max_diff and compared >= min_compared; max_diff = INT32_MAX with
+ * min_compared = 0 lists every pair.  Listed pairs ascend in (a, b); the order depends on nothing else -- not on the tile shape,
+ * not on scheduling.
+ * KNOWN ANSWERS, on the two known-answer rows of ALIGNED ROWS (a gene of 20 bases).  "--acgt--nacg--------" against
+ * "--cgtn--acgt--------": compared 6, differences 6, unshared 0.  Either against the all-GAP row: compared 0, differences 0,
+ * unshared 8.  With the padding flagged the second block's gap mask is ffff, not 000f.
+ * KP_DIST_MAX_DIFF and KP_DIST_MIN_COMPARED, the command line's defaults, are design constants like KP_RESCUE_FLANK, not
+ * measurements: ten differences in a 25 kb locus is 0.04 %, well inside one outbreak and well below two variants of a locus; one
+ * compared column keeps pairs of empty rows out of the table.
+ * OUT OF SCOPE.  Merging fragments of one gene; distances between isolates of different loci or different databases; indel events
+ * as events (an inserted run counts through `unshared` only); clustering and trees; any change to an existing report byte. */
+#define KP_DIST_MAX_DIFF 10
+#define KP_DIST_MIN_COMPARED 1
+typedef struct kp_dist_pair {
+    int32_t a, b; /* rows of the matrix, a < b */
+    int32_t compared, differences, unshared;
+    int32_t pad_; /* zero */
+} kp_dist_pair;
+
 #endif /* KP_SPEC_H */

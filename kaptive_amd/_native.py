@@ -75,6 +75,16 @@ REPORTS = (
     Report("rescue", RESCUE_HEADER, "rescue", "rescue_tsv", "rescue records"),
 )
 
+# Pairwise locus distances (include/kp_spec.h, DISTANCES): a layer beside the per-batch reports above, not one of them -- it spans the
+# batches of a run (kaptive_amd/distances.py).
+DIST_PAIR_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("compared", "<i4"), ("differences", "<i4"), ("unshared", "<i4"), ("pad", "<i4")])  # kp_dist_pair: 24 bytes
+DISTANCES_HEADER = b"Locus\tAssembly A\tAssembly B\tColumns\tCompared\tDifferences\tUnshared\n"  # the columns of kp_format_distances
+DIST_TILE = 64  # KP_DIST_TILE of kaptive_amd/csrc/kp_dist.h: pairs along either side of a workgroup's tile (tests/test_distances_cpu.py compares the mirrors)
+DIST_CHUNK = 8  # KP_DIST_CHUNK: plane words (of 64 columns: four blocks) of a row strip that lie in LDS at a time
+DIST_MAX_ROWS = 1 << 18  # KP_DIST_MAX_ROWS of kaptive_amd/csrc/kp_caps.h
+DIST_MAX_DIFF = 10  # KP_DIST_MAX_DIFF of include/kp_spec.h: the command line's --max-distance
+DIST_MIN_COMPARED = 1  # KP_DIST_MIN_COMPARED: its --min-compared
+
 JOIN_MAX_PIECES = 8  # KP_JOIN_MAX_PIECES
 JOIN_DTYPE = np.dtype(
     [("gs", "<i4"), ("contig", "<i4"), ("n_pieces", "<i4"), ("n_anchors", "<i4"), ("chain_score", "<i4"), ("width", "<i4"),
@@ -89,6 +99,7 @@ EXPORTS = (
     "kp_batch_tasks", "kp_batch_task_results", "kp_batch_joins", "kp_batch_occ", "kp_batch_candidates", "kp_db_load_typing", "kp_db_load_typing_group", "kp_batch_use_group", "kp_batch_score", "kp_batch_reduce", "kp_batch_typing_caps",
     "kp_device_count", "kp_device_numa_node", "kp_batch_typing", "kp_batch_proteins", "kp_protein_align", "kp_fasta_pack", "kp_fasta_ingest", "kp_fasta_ingest_many", "kp_fasta_ingest_file", "kp_fasta_ingest_shard", "kp_shard_words_into", "kp_shard_free", "kp_fasta_simd", "kp_pack_contigs",
     "kp_fasta_free", "kp_format_rows", "kp_format_json", "kp_format_fasta", "kp_protein_align_seeded", "kp_randstrobes", "kp_randstrobe_top_hits",
+    "kp_dist_create", "kp_dist_count", "kp_dist_pairs", "kp_dist_destroy", "kp_format_distances",
 )  # fmt: skip
 
 
@@ -731,6 +742,26 @@ def format_aligned(gene_names, asm_names, contig_names, asm_first_ctg, n_kept, k
     raise NativeError("kp_format_aligned: size kept changing")
 
 
+def format_distances(locus_name: str, columns: int, names, pairs) -> bytes:
+    """The lines of one locus's distance table (kp_format_distances; host only; no header: ``DISTANCES_HEADER``): one per record of
+    ``pairs`` (DIST_PAIR_DTYPE), whose ``a`` and ``b`` index ``names``, the assemblies' names by row of the locus's matrix."""
+    nm_b, nm_o = _blob64(names)
+    pairs = np.ascontiguousarray(pairs, dtype=DIST_PAIR_DTYPE)
+    locus = locus_name.encode("utf-8")
+    h = lib()
+    h.kp_format_distances.restype = C.c_int64
+    out = np.empty(max(4096, 96 * len(pairs)), np.uint8)
+    for _ in range(2):
+        need = h.kp_format_distances(C.c_char_p(locus), C.c_int32(len(locus)), C.c_int64(int(columns)), _p(nm_b), _p(nm_o), C.c_int32(len(nm_o) - 1),
+                                     _p(pairs), C.c_int64(len(pairs)), _p(out), C.c_int64(len(out)))
+        if need < 0:
+            raise ValueError(f"kp_format_distances failed ({need})")
+        if need <= len(out):
+            return out[:need].tobytes()
+        out = np.empty(int(need), np.uint8)
+    raise NativeError("kp_format_distances: size kept changing")
+
+
 class JsonTables(C.Structure):  # kp_json_tables
     _fields_ = [("head", C.c_char_p), ("head_len", C.c_int32), ("gene_names", C.c_void_p), ("gene_name_off", C.c_void_p),
                 ("gene_ids", C.c_void_p), ("cluster_names", C.c_void_p), ("products", C.c_void_p), ("gene_id_off", C.c_void_p),
@@ -1362,6 +1393,52 @@ class Batch:
         self.ctx._check(lib().kp_batch_candidates(self.ctx._h, self._h, _p(out), C.c_int64(n)), "kp_batch_candidates")
         n_front, n_back = int(out[0]), int(out[1])
         return out[2 : 2 + n_front].copy(), out[2 + n_front : 2 + n_front + n_back].copy()
+
+
+class Distances:
+    """The locus rows of one locus on the device, ready to be compared all against all (kp_dist; include/kp_spec.h, DISTANCES).
+    ``rows_matrix``: uint64 [n_rows, n_blocks], one locus row per assembly, padding flagged.  A context manager; closing the context
+    closes it too."""
+
+    def __init__(self, ctx: Context, rows_matrix) -> None:
+        m = np.ascontiguousarray(rows_matrix, np.uint64)
+        if m.ndim != 2:
+            raise ValueError("the locus rows come as a [n_rows, n_blocks] matrix")
+        self.ctx, self.n_rows, self.n_blocks = ctx, int(m.shape[0]), int(m.shape[1])
+        self._h = C.c_void_p()
+        ctx._check(lib().kp_dist_create(ctx._h, _p(m), C.c_int32(self.n_rows), C.c_int64(self.n_blocks), C.byref(self._h)), "kp_dist_create")
+        ctx._batches.add(self)
+        _live.add(self)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            if getattr(self.ctx, "_h", None):  # (as a batch: without its context there is nothing left to free)
+                h = lib()
+                h.kp_dist_destroy.restype = None
+                h.kp_dist_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self) -> "Distances":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def count(self, max_diff: "int | None" = None, min_compared: int = 0) -> int:
+        """How many pairs ``pairs`` would list (kp_dist_count)."""
+        n = C.c_int64(0)
+        md = np.iinfo(np.int32).max if max_diff is None else int(max_diff)
+        self.ctx._check(lib().kp_dist_count(self.ctx._h, self._h, C.c_int32(md), C.c_int32(int(min_compared)), C.byref(n)), "kp_dist_count")
+        return n.value
+
+    def pairs(self, max_diff: "int | None" = None, min_compared: int = 0) -> np.ndarray:
+        """DIST_PAIR_DTYPE records of the pairs (a, b), a < b, with ``differences <= max_diff`` (None: no limit) and ``compared >=
+        min_compared``, ascending in (a, b)."""
+        out = np.zeros(self.count(max_diff, min_compared), DIST_PAIR_DTYPE)
+        self.ctx._check(lib().kp_dist_pairs(self.ctx._h, self._h, _p(out), C.c_int64(len(out))), "kp_dist_pairs")
+        return out
 
 
 RANDSTROBE_DTYPE = np.dtype([("hash", "<u8"), ("seq_idx", "<u4"), ("pos1", "<u4"), ("pos2", "<u4")])

@@ -135,6 +135,14 @@ def _add_outputs(p: argparse.ArgumentParser, tsv_flags, include_json: bool) -> N
                        help="With --rescue: bases either side of every locus piece that are searched (0 .. 65535; default: 4096)")
         g.add_argument("--rescue-min-score", type=int, metavar="N", default=argparse.SUPPRESS,
                        help="With --rescue: alignment score below which a gene is called absent (default: 80)")
+    if include_json:
+        g.add_argument("--distances", metavar="FILE", default=argparse.SUPPRESS,
+                       help="Compare the loci of all assemblies that carry the same locus, all against all, and write the pairs that lie "
+                            "within --max-distance differing bases of each other as a TSV table to a file")
+        g.add_argument("--max-distance", type=int, metavar="N", default=argparse.SUPPRESS,
+                       help="With --distances: most differing bases a listed pair may have (default: 10)")
+        g.add_argument("--min-compared", type=int, metavar="N", default=argparse.SUPPRESS,
+                       help="With --distances: fewest columns both assemblies must hold a base in (default: 1)")
     g.add_argument("--pha4ge", metavar="FILE", nargs="?", const="kaptive_results.pha4ge", type=Path,
                    help="Write PHA4GE-compliant serotyping report to a TSV file (default: %(const)s)")
 
@@ -152,6 +160,12 @@ class _Parser(argparse.ArgumentParser):
                 if not getattr(ns, "rescue", None):
                     self.error(f"--{flag.replace('_', '-')} requires --rescue FILE")
                 if getattr(ns, flag) < 0 or (flag == "rescue_flank" and ns.rescue_flank > 65535):
+                    self.error(f"--{flag.replace('_', '-')} is out of range")
+        for flag in ("max_distance", "min_compared"):
+            if getattr(ns, flag, None) is not None:
+                if not getattr(ns, "distances", None):
+                    self.error(f"--{flag.replace('_', '-')} requires --distances FILE")
+                if not 0 <= getattr(ns, flag) <= 2**31 - 1:
                     self.error(f"--{flag.replace('_', '-')} is out of range")
         return ns, rest
 
@@ -226,7 +240,8 @@ class _TypingPipeline:
         self.want_paf = bool(getattr(args, "paf", None))  # every hit with its CIGAR: the alignment passes of this run leave them
         self.paf_cs, self.paf_eqx = bool(getattr(args, "cs", False)), bool(getattr(args, "eqx", False))  # ... and its cs string
         self.want = {r.name: bool(getattr(args, r.name, None)) for r in REPORTS}  # the tables of the kept lists: the reductions of this run leave their records
-        self.typer_options = {**self.want, **{k: getattr(args, k) for k in ("rescue_flank", "rescue_min_score") if getattr(args, k, None) is not None}}
+        self.want_distances = bool(getattr(args, "distances", None))  # the run's locus rows: every chunk's go with its outputs (LOCUS_ROWS_KEY)
+        self.typer_options = {**self.want, "aligned": self.want["aligned"] or self.want_distances, **{k: getattr(args, k) for k in ("rescue_flank", "rescue_min_score") if getattr(args, k, None) is not None}}
         self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins", "paf", *self.want))  # the files' text (and contig names) are kept
         self.fasta_outputs = any(getattr(args, f, None) for f in ("loci", "genes", "proteins"))  # ... and result objects are built
         self.threads = max(1, args.threads or usable_cpus())  # (the cgroup's quota, not the 256 CPUs a container may see)
@@ -480,6 +495,12 @@ class _TypingPipeline:
             for r in REPORTS:
                 if self.want[r.name]:
                     out[r.name] = getattr(bt, r.tsv)()
+            if self.want_distances:  # (a payload for the parent to merge, not bytes for a file; no --aligned table is made of the rows)
+                from kaptive_amd.distances import LocusRows
+
+                chunk_rows = LocusRows(bt.typer._db)
+                chunk_rows.add(bt)
+                out[LOCUS_ROWS_KEY] = chunk_rows.state()
             if self.want_tsv:
                 out["tsv"] = bt.tsv()
             if getattr(args, "pha4ge", None):
@@ -613,6 +634,52 @@ def hits_to_paf(engine, genomes, hits, hit_off, ops, cigar_off, cs=None, cs_off=
         return _native.format_paf_tags(engine.db.genes.ids, engine.db.genes.lengths, names, lengths, first, hits, hit_off, ops, cigar_off,
                                        cs, cs_off, (_native.PAF_CS if cs_tag else 0) | (_native.PAF_EQX if eqx else 0))
     return _native.format_paf(engine.db.genes.ids, engine.db.genes.lengths, names, lengths, first, hits, hit_off, ops, cigar_off)
+
+
+LOCUS_ROWS_KEY = "locus_rows"  # a chunk's outputs: the ``LocusRows.state()`` of its assemblies (--distances); never written to a file
+
+
+class _RunDistances:
+    """``--distances``: the locus rows of the whole run, merged chunk by chunk in input order -- one ``LocusRows`` per database -- and,
+    after the last chunk, compared on a device and written: one table, or with ``--db`` one per database (``per_database_path``)."""
+
+    def __init__(self, args: argparse.Namespace) -> None:
+        self.path = args.distances
+        self.max_diff = getattr(args, "max_distance", None)
+        self.min_compared = getattr(args, "min_compared", None)
+        self.rows: "list | None" = None  # [(keyword or None, LocusRows)]
+        self.args = args
+
+    def _start(self, dbs) -> None:
+        from kaptive_amd.distances import LocusRows
+
+        several = bool(getattr(self.args, "db", None))
+        self.rows = [(db.metadata.keyword if several else None, LocusRows(db)) for db in dbs]
+
+    def take(self, out, dbs=None) -> None:
+        """Removes the payload(s) from one chunk's outputs and merges them.  ``dbs``: the run's databases, where somebody has them
+        loaded already (the single-device pipeline); otherwise they are read from the command line's paths on first use."""
+        if self.rows is None:
+            self._start(dbs if dbs is not None else [load_database(p) for p in (self.args.database, *(getattr(self.args, "db", None) or []))])
+        if isinstance(out, dict):
+            self.rows[0][1].merge(out.pop(LOCUS_ROWS_KEY))
+        else:
+            for (_, rows), (_, o) in zip(self.rows, out):
+                rows.merge(o.pop(LOCUS_ROWS_KEY))
+
+    def write(self, ctx) -> None:
+        from kaptive_amd import _native
+
+        md = _native.DIST_MAX_DIFF if self.max_diff is None else self.max_diff
+        mc = _native.DIST_MIN_COMPARED if self.min_compared is None else self.min_compared
+        for kw, rows in self.rows or []:
+            body = rows.tsv(ctx, md, mc)
+            if kw is None and _is_stdout(self.path):
+                sys.stdout.buffer.write(_native.DISTANCES_HEADER + body)
+                sys.stdout.buffer.flush()
+            else:
+                with open(self.path if kw is None else per_database_path(self.path, kw), "wb") as h:
+                    h.write(_native.DISTANCES_HEADER + body)
 
 
 def _read_ahead_bytes() -> int:
@@ -794,6 +861,10 @@ def run_type(args: argparse.Namespace) -> int:
     for r in REPORTS:
         if getattr(args, "db", None) and (v := getattr(args, r.name, None)) and _is_stdout(v):
             raise ValueError(f"--{r.name} with --db writes a table per database: it needs a file name, not stdout")
+    if getattr(args, "db", None) and (v := getattr(args, "distances", None)) and _is_stdout(v):
+        raise ValueError("--distances with --db writes a table per database: it needs a file name, not stdout")
+    dist = _RunDistances(args) if getattr(args, "distances", None) else None
+    run_dbs = None  # the databases of the run, where this process has loaded them (one device)
     handles = {}
     per_db = _PerDatabaseOutputs(args) if getattr(args, "db", None) else None  # several databases: reports per database
 
@@ -821,6 +892,8 @@ def run_type(args: argparse.Namespace) -> int:
 
     def write(out, n):
         nonlocal done
+        if dist is not None:
+            dist.take(out, run_dbs)
         if per_db is not None:
             per_db.write(out)
         else:
@@ -835,8 +908,13 @@ def run_type(args: argparse.Namespace) -> int:
         if len(devices) == 1:
             pipe = _TypingPipeline(args, devices[0], chunks=chunks)
             try:
+                run_dbs = [t._db for t in pipe.typer.serotypers] if pipe.keywords is not None else [pipe.typer._db]
                 for k, out in pipe.run(chunks):
                     write(out, len(chunks[k][1]))
+                if dist is not None:  # after the last chunk, on the pipeline's own context
+                    if dist.rows is None:
+                        dist._start(run_dbs)
+                    dist.write(pipe.engine.ctx)
             finally:
                 phases = {name: round(t - t_start, 3) for name, t in pipe.marks.items()}
                 pipe.close(fast=FAST_EXIT)
@@ -888,6 +966,17 @@ def run_type(args: argparse.Namespace) -> int:
                     proc.join(timeout=30 if ok else 5)
                     if proc.is_alive():
                         proc.terminate()
+            if dist is not None:
+                # the workers have ended and this process has not touched a device yet: a context on the first listed one, for this step
+                from kaptive_amd import _native
+
+                if dist.rows is None:
+                    dist.take(())
+                dctx = _native.Context(devices[0])
+                try:
+                    dist.write(dctx)
+                finally:
+                    dctx.close()
     finally:
         for h in handles.values():
             if h is not sys.stdout.buffer:

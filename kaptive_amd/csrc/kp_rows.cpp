@@ -530,3 +530,26 @@ extern "C" int64_t kp_format_rescue(const kp_allele_tables *t, int32_t n_asm, co
     }
     return o.n;
 }
+
+// ---- distance table (kp_spec.h, DISTANCES) ----------------------------------------------------------------------------------------
+// One line per listed pair of one locus; the rows of the matrix are named by the caller, in the order it stacked them.
+extern "C" int64_t kp_format_distances(const char *locus_name, int32_t locus_name_len, int64_t columns, const char *names, const int64_t *name_off,
+                                       int32_t n_names, const kp_dist_pair *pairs, int64_t n_pairs, char *out, int64_t cap) {
+    if (locus_name_len < 0 || (locus_name_len > 0 && !locus_name) || columns < 0 || n_names < 0 || n_pairs < 0 || cap < 0 || (cap > 0 && !out)) return KP_EINVAL;
+    if (n_pairs > 0 && (!pairs || !name_off || n_names == 0)) return KP_EINVAL;
+    Out o{out, cap};
+    for (int64_t i = 0; i < n_pairs; ++i) {
+        const kp_dist_pair &r = pairs[i];
+        if (r.a < 0 || r.a >= n_names || r.b < 0 || r.b >= n_names) return KP_EINVAL;
+        if (name_off[r.a + 1] < name_off[r.a] || name_off[r.b + 1] < name_off[r.b] || ((name_off[r.a + 1] > name_off[r.a] || name_off[r.b + 1] > name_off[r.b]) && !names)) return KP_EINVAL;
+        o.put(locus_name, locus_name_len); o.put('\t');
+        put_name(o, names, name_off, r.a); o.put('\t');
+        put_name(o, names, name_off, r.b); o.put('\t');
+        put_i(o, columns); o.put('\t');
+        put_i(o, r.compared); o.put('\t');
+        put_i(o, r.differences); o.put('\t');
+        put_i(o, r.unshared);
+        o.put('\n');
+    }
+    return o.n;
+}

@@ -1,0 +1,171 @@
+"""Pairwise locus distances between the isolates of a run (include/kp_spec.h, DISTANCES).
+
+Every other report answers a question about one assembly; this one is about pairs: which isolates carry the same or nearly the same
+locus, and how many bases apart they are.  ``LocusRows`` collects, batch after batch, one LOCUS ROW per assembly -- the aligned rows of
+the primary kept records of its best locus's genes, strung together in database order, padding flagged -- and, when the run is over,
+hands the rows of every locus to the device as one matrix (``_native.Distances``: kp_dist.hip compares them all against all).
+
+It spans batches and, on a multi-GPU run, processes: ``state()`` is a picklable payload of what was added, ``merge()`` absorbs one.
+"""
+
+from __future__ import annotations
+
+import numpy as np
+
+from kaptive_amd import _native
+from kaptive_amd.serotyping.batch import F_PRIMARY
+
+GAP_BLOCK = np.uint64(0xFFFF << 48)  # sixteen GAP columns: a gene without a primary record, and what padding adds to a last block
+DIST_RECORD_DTYPE = np.dtype([("locus", "<i4"), ("a", "<i4"), ("b", "<i4"), ("compared", "<i4"), ("differences", "<i4"), ("unshared", "<i4")])
+
+
+def pad_masks(gene_lengths) -> np.ndarray:
+    """uint64 per gene: the GAP bits of the columns at or beyond the gene's length in its last block (kp_dist_pad_mask)."""
+    n = np.asarray(gene_lengths, np.int64) & 15
+    return np.where(n > 0, ((0xFFFF << n) & 0xFFFF).astype(np.uint64) << np.uint64(48), np.uint64(0))
+
+
+class LocusRows:
+    """The locus rows of a run, for one database.
+
+    ``add(bt)`` takes a ``BatchTyping`` of an engine made with ``aligned=True``; ``distances(ctx)`` / ``tsv(ctx)`` / ``matrix(ctx,
+    locus)`` compare them on the device of ``ctx`` (a ``_native.Context``; no database needs to be resident in it).  Assemblies are
+    numbered in the order they were added."""
+
+    def __init__(self, db) -> None:
+        self.db = db
+        self.ids: list = []
+        self.best = np.zeros(0, np.int32)
+        self._parts: dict = {}  # locus -> [(assembly numbers int64 [k], matrix uint64 [k, NB])]
+        lengths = np.asarray(db.genes.lengths, np.int64)
+        self._gene_blocks = (lengths + 15) // 16
+        self._gene_pad = pad_masks(lengths)
+        self._gene_lengths = lengths
+
+    def __len__(self) -> int:
+        return len(self.ids)
+
+    # -- geometry of a locus -----------------------------------------------------------------------------------------------------
+    def locus_genes(self, locus: int) -> tuple[int, int]:
+        g0 = int(self.db.locus_gene_offsets[locus])
+        return g0, g0 + int(self.db.locus_gene_lengths[locus])
+
+    def n_blocks(self, locus: int) -> int:
+        g0, g1 = self.locus_genes(locus)
+        return int(self._gene_blocks[g0:g1].sum())
+
+    def columns(self, locus: int) -> int:
+        """The locus's total gene length: the table's ``Columns``."""
+        g0, g1 = self.locus_genes(locus)
+        return int(self._gene_lengths[g0:g1].sum())
+
+    # -- building --------------------------------------------------------------------------------------------------------------------
+    def rows_of(self, locus: int, members, n_kept, kept, rows, blocks) -> np.ndarray:
+        """uint64 [len(members), NB]: the locus rows of assemblies ``members`` (indices into the batch's tables) for ``locus``."""
+        members = np.asarray(members, np.int64)
+        g0, g1 = self.locus_genes(locus)
+        nbg = self._gene_blocks[g0:g1]
+        first = np.concatenate([[0], np.cumsum(nbg)]).astype(np.int64)  # first block of every gene in the row
+        nb = int(first[-1])
+        mat = np.full((len(members), nb), GAP_BLOCK, np.uint64)
+        if len(members) == 0 or nb == 0:
+            return mat
+        k = kept[members]
+        live = (np.arange(kept.shape[1])[None, :] < np.asarray(n_kept)[members, None]) & ((k["flags"] & F_PRIMARY) != 0)
+        live &= (k["gene"] >= g0) & (k["gene"] < g1)
+        m, i = np.nonzero(live)  # member, kept index of every contributing record
+        if len(m):
+            gene = k["gene"][m, i].astype(np.int64) - g0
+            r = rows[members[m], i]
+            n = nbg[gene]
+            ok = (r["gene_len"] == self._gene_lengths[g0 + gene]) & (r["off"] >= 0) & (r["off"] + n <= len(blocks))
+            if not ok.all():
+                raise ValueError("an aligned row does not have its gene's length, or lies outside the block array")
+            # every block of every record: one gather, one scatter
+            rec = np.repeat(np.arange(len(m)), n)
+            within = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+            mat[m[rec], first[gene][rec] + within] = np.asarray(blocks, np.uint64)[r["off"][rec] + within]
+        has = nbg > 0
+        mat[:, (first[1:] - 1)[has]] |= self._gene_pad[g0:g1][has][None, :]
+        return mat
+
+    def add(self, bt) -> None:
+        """The assemblies of one typed batch (``BatchTyping``; its engine must have been made with ``aligned=True``)."""
+        rows, blocks = bt.aligned()
+        n = len(bt.sums)
+        base = len(self.ids)
+        best = np.asarray(bt.best_locus, np.int32)
+        for locus in np.unique(best):
+            members = np.flatnonzero(best == locus)
+            self._parts.setdefault(int(locus), []).append((members + base, self.rows_of(int(locus), members, bt.sums["n_kept"], bt.kept, rows, blocks)))
+        self.ids.extend(bt.ids[:n])
+        self.best = np.concatenate([self.best, best])
+
+    def locus_matrix(self, locus: int) -> tuple[np.ndarray, np.ndarray]:
+        """(assembly numbers int64 [R], matrix uint64 [R, NB]) of ``locus``, ascending in assembly number."""
+        parts = self._parts.get(int(locus), [])
+        if not parts:
+            return np.zeros(0, np.int64), np.zeros((0, self.n_blocks(locus)), np.uint64)
+        idx, mat = np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+        order = np.argsort(idx, kind="stable")
+        self._parts[int(locus)] = [(idx[order], mat[order])]
+        return self._parts[int(locus)][0]
+
+    def loci(self) -> list:
+        """The loci that have a row, in database order."""
+        return sorted(self._parts)
+
+    # -- across processes ------------------------------------------------------------------------------------------------------------
+    def state(self) -> dict:
+        """What was added, as plain picklable data (ids, best loci, per locus the assembly numbers and the matrix)."""
+        return {"ids": list(self.ids), "best": self.best.copy(), "loci": {L: self.locus_matrix(L) for L in self.loci()}}
+
+    def merge(self, state: dict) -> None:
+        """Absorbs the ``state()`` of another accumulator of the same database: its assemblies follow the ones already here."""
+        base = len(self.ids)
+        for L, (idx, mat) in state["loci"].items():
+            if mat.shape[1] != self.n_blocks(L):
+                raise ValueError(f"locus {L}: rows of {mat.shape[1]} blocks, the database gives {self.n_blocks(L)}")
+            self._parts.setdefault(int(L), []).append((np.asarray(idx, np.int64) + base, np.ascontiguousarray(mat, np.uint64)))
+        self.ids.extend(state["ids"])
+        self.best = np.concatenate([self.best, np.asarray(state["best"], np.int32)])
+
+    # -- comparing -------------------------------------------------------------------------------------------------------------------
+    def _locus_pairs(self, ctx, locus: int, max_diff, min_compared):
+        idx, mat = self.locus_matrix(locus)
+        if len(idx) < 2:
+            return idx, np.zeros(0, _native.DIST_PAIR_DTYPE)
+        with _native.Distances(ctx, mat) as d:
+            return idx, d.pairs(max_diff, min_compared)
+
+    def distances(self, ctx, max_diff: "int | None" = _native.DIST_MAX_DIFF, min_compared: int = _native.DIST_MIN_COMPARED) -> np.ndarray:
+        """DIST_RECORD_DTYPE records ``(locus, a, b, compared, differences, unshared)`` of the listed pairs: loci in database order, one
+        ``Distances`` handle each; a and b number the assemblies in the order they were added, a < b, ascending within a locus."""
+        out = []
+        for L in self.loci():
+            idx, p = self._locus_pairs(ctx, L, max_diff, min_compared)
+            rec = np.zeros(len(p), DIST_RECORD_DTYPE)
+            rec["locus"] = L
+            rec["a"], rec["b"] = idx[p["a"]], idx[p["b"]]
+            for f in ("compared", "differences", "unshared"):
+                rec[f] = p[f]
+            out.append(rec)
+        return np.concatenate(out) if out else np.zeros(0, DIST_RECORD_DTYPE)
+
+    def tsv(self, ctx, max_diff: "int | None" = _native.DIST_MAX_DIFF, min_compared: int = _native.DIST_MIN_COMPARED) -> bytes:
+        """The lines of the distance table (``--distances``; no header: ``_native.DISTANCES_HEADER``), formatted by the native library
+        (kp_format_distances): loci in database order, pairs in input order with A before B."""
+        out = []
+        for L in self.loci():
+            idx, p = self._locus_pairs(ctx, L, max_diff, min_compared)
+            out.append(_native.format_distances(self.db.loci.ids[L], self.columns(L), [self.ids[i] for i in idx], p))
+        return b"".join(out)
+
+    def matrix(self, ctx, locus: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(assembly numbers [R], differences int32 [R, R], compared int32 [R, R]) of one locus, dense and symmetric, for small R."""
+        idx, p = self._locus_pairs(ctx, locus, None, 0)
+        R = len(idx)
+        diff, comp = np.zeros((R, R), np.int32), np.zeros((R, R), np.int32)
+        diff[p["a"], p["b"]] = diff[p["b"], p["a"]] = p["differences"]
+        comp[p["a"], p["b"]] = comp[p["b"], p["a"]] = p["compared"]
+        return idx, diff, comp

@@ -181,7 +181,10 @@ class Engine:
         group = self.group if group is None else group
         sums, kept, pieces = batch.typing(group)
         reports = {r.name: getattr(batch, r.fetch)(group) if getattr(self, r.name) else None for r in _native.REPORTS}
-        return B.BatchTyping(typer, ids, sums, kept, pieces, scores, best, genomes, **reports)
+        bt = B.BatchTyping(typer, ids, sums, kept, pieces, scores, best, genomes, **reports)
+        if getattr(typer, "locus_rows", None) is not None:  # Serotyper(db, distances=True): the run's locus rows grow batch by batch
+            typer.locus_rows.add(bt)
+        return bt
 
     def type_batch(self, typer, batch, ids: Sequence[str], genomes: Sequence[GenomeAssembly] | None = None,
                    aligned: bool = False):

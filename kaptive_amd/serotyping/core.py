@@ -50,6 +50,7 @@ class Serotyper:
         rescue: bool = False,
         rescue_flank: "int | None" = None,
         rescue_min_score: "int | None" = None,
+        distances: bool = False,
     ) -> None:
         """``preset`` and ``scoring_metric`` are accepted and ignored, as in the reference.
         ``aligner`` / ``protein_aligner`` replace the HIP stages; tests use them to feed recorded hits.  ``variants``: the engine
@@ -58,12 +59,18 @@ class Serotyper:
         kept records and the locus pieces (``Engine(db, alleles=True)``); ``aligned``: it leaves the aligned rows of the kept hits
         (``Engine(db, aligned=True)``); ``rescue``: it leaves the rescue records of the missing genes (``Engine(db, rescue=True,
         rescue_flank=...)``), and ``rescue_min_score`` is the score below which their table calls a gene ``absent`` (default
-        ``_native.RESCUE_MIN_SCORE``)."""
+        ``_native.RESCUE_MIN_SCORE``); ``distances``: every batch this typer types also feeds ``locus_rows``, the run's
+        ``distances.LocusRows`` of this database (include/kp_spec.h, DISTANCES) -- it implies ``aligned``."""
         self._db = db
         self._variants = bool(variants)
         self._breakpoints = bool(breakpoints)
         self._alleles = bool(alleles)
-        self._aligned = bool(aligned)
+        self._aligned = bool(aligned) or bool(distances)
+        self.locus_rows = None  # distances=True: the locus rows of every assembly typed so far (Engine._collect feeds it)
+        if distances:
+            from kaptive_amd.distances import LocusRows
+
+            self.locus_rows = LocusRows(db)
         self._rescue, self._rescue_flank = bool(rescue), rescue_flank
         if (rescue_flank is not None or rescue_min_score is not None) and not rescue:
             raise ValueError("rescue_flank and rescue_min_score need rescue=True")
@@ -433,20 +440,22 @@ class MultiSerotyper:
         rescue: bool = False,
         rescue_flank: "int | None" = None,
         rescue_min_score: "int | None" = None,
+        distances: bool = False,
     ) -> None:
+        """``distances``: every one of ``.serotypers`` keeps the ``locus_rows`` of its database (it implies ``aligned``)."""
         self.dbs = list(dbs)
         check_databases(self.dbs)
         self._device = device
         self._variants = bool(variants)
         self._breakpoints = bool(breakpoints)
         self._alleles = bool(alleles)
-        self._aligned = bool(aligned)
+        self._aligned = bool(aligned) or bool(distances)
         self._rescue, self._rescue_flank = bool(rescue), rescue_flank
         self._engine = None
         self.serotypers = tuple(
             Serotyper(db, max_other_genes, min_completeness, allow_below_threshold, partial_edge_tolerance=partial_edge_tolerance,
                       device=device, variants=variants, breakpoints=breakpoints, alleles=alleles, aligned=aligned, rescue=rescue, rescue_flank=rescue_flank,
-                      rescue_min_score=rescue_min_score) for db in self.dbs
+                      rescue_min_score=rescue_min_score, distances=distances) for db in self.dbs
         )  # fmt: skip
 
     @property
