@@ -569,6 +569,27 @@ KP_API void kp_dist_destroy(kp_dist *d);
  * outside [0, n_names). */
 KP_API int64_t kp_format_distances(const char *locus_name, int32_t locus_name_len, int64_t columns, const char *names, const int64_t *name_off,
                                    int32_t n_names, const kp_dist_pair *pairs, int64_t n_pairs, char *out, int64_t cap);
+/* Clusters and nearest neighbours of a handle's rows (kp_spec.h, CLUSTERS): one pass over the same tiles, no pair stored.
+ *   labels [n_levels][n_rows]: every row's label at every level; may be null when n_levels == 0.
+ *   nearest [n_rows]: every row's nearest record; may be null, then the nearest pass stores nothing.
+ * KP_EINVAL for a null context or handle, a handle of another device, n_levels outside [0, KP_CLUST_MAX_LEVELS], levels that are
+ * negative or do not strictly ascend, null levels with n_levels > 0, and null labels with n_levels > 0 and n_rows > 0.  n_rows of 0
+ * and 1 are valid; one row has label 0 and no neighbour.  The call leaves the handle's listing state alone: a kp_dist_pairs that
+ * follows a kp_dist_count works with a kp_dist_clusters between them.  Its tables are the handle's own, allocated once, on the
+ * first call; like everything a handle does, kp_device_allocations does not count them. */
+KP_API int kp_dist_clusters(kp_ctx *ctx, kp_dist *d, const int32_t *levels, int32_t n_levels, int32_t min_compared,
+                            int32_t *labels /* [n_levels][n_rows], may be null when n_levels == 0 */,
+                            kp_dist_nearest *nearest /* [n_rows], may be null: then no nearest pass output */);
+/* The cluster table of one locus (host only): one tab-separated line per row, in row order: Locus, Assembly, one cluster number
+ * per level (the 1-based rank of the row's label among its level's labels), Nearest (the neighbour's name, "." for none),
+ * Differences, Compared, Unshared ("." for none).  No header line.  names / name_off [n_names + 1]: the assemblies' names; row i of
+ * the matrix is named names[rows[i]], or names[i] when rows is null; labels [n_levels][n_names] and nearest [n_names] as
+ * kp_dist_clusters filled them.  Return value as kp_format_variants has it; KP_EINVAL also for a label, a neighbour or an entry of
+ * rows outside [0, n_names), a label larger than its row or one that is not its own label, and n_levels outside [0,
+ * KP_CLUST_MAX_LEVELS]. */
+KP_API int64_t kp_format_clusters(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off,
+                                  int32_t n_names, const int32_t *rows /* [n_names] or null */, int32_t n_levels,
+                                  const int32_t *labels, const kp_dist_nearest *nearest, char *out, int64_t cap);
 
 /* ---- JSON lines of a whole batch (host only) ----------------------------------------------------------------------------------
  * Replaces orjson.dumps(SerotypingResult.to_dict(), OPT_SERIALIZE_NUMPY | OPT_APPEND_NEWLINE) per genome

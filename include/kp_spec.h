@@ -666,7 +666,7 @@ typedef struct kp_rescue {
  * measurements: ten differences in a 25 kb locus is 0.04 %, well inside one outbreak and well below two variants of a locus; one
  * compared column keeps pairs of empty rows out of the table.
  * OUT OF SCOPE.  Merging fragments of one gene; distances between isolates of different loci or different databases; indel events
- * as events (an inserted run counts through `unshared` only); clustering and trees; any change to an existing report byte. */
+ * as events (an inserted run counts through `unshared` only); trees (clusters: CLUSTERS, below); any change to an existing report byte. */
 #define KP_DIST_MAX_DIFF 10
 #define KP_DIST_MIN_COMPARED 1
 typedef struct kp_dist_pair {
@@ -674,5 +674,33 @@ typedef struct kp_dist_pair {
     int32_t compared, differences, unshared;
     int32_t pad_; /* zero */
 } kp_dist_pair;
+
+/* ---- CLUSTERS (optional; two reductions over the pairs of DISTANCES: no pair record, no report byte depends on them) --------------
+ * Which isolates belong together at a threshold, and which isolate is closest to each?  Both are reductions over all pairs of one
+ * matrix of locus rows; no pair is ever listed for them, so they work where the listing cannot be held.
+ *
+ * LEVELS.  K thresholds T_0 < T_1 < ... < T_{K-1}, all >= 0, 0 <= K <= KP_CLUST_MAX_LEVELS.  The command line's default is
+ * 0, 1, 2, 5, 10: design constants, as KP_DIST_MAX_DIFF is.
+ * EDGE.  A pair (a, b) of rows of one matrix is an edge at level k iff compared >= min_compared and differences <= T_k -- the
+ * DISTANCES counts, and the DISTANCES listing predicate with max_diff = T_k.
+ * CLUSTER.  The clusters at level k are the connected components of the rows under the level's edges (single linkage).  The LABEL
+ * of a row at level k is the smallest row index of its component.  Levels nest: rows with equal labels at level k have equal
+ * labels at every level above it.
+ * NEAREST.  For row r, among all rows s != r with compared(r, s) >= min_compared the one with the smallest key (differences, s).
+ * The record holds s and the three counts of the pair; a row without such an s has s = -1 and counts 0.  Nearest does not depend
+ * on the levels: it also sees pairs far beyond every threshold.
+ * PURE FUNCTION of the matrix, the levels and min_compared.  Neither labels nor nearest depend on the tile shape, on scheduling or
+ * on the order in which edges are met.
+ * CLUSTER NUMBER, in the table: the 1-based rank of a row's label among the labels of its level, ascending.  Numbers are ranks
+ * within the run.
+ * KNOWN ANSWERS, on the three rows of the DISTANCES known answers: A "--acgt--nacg--------" is row 0, B "--cgtn--acgt--------"
+ * row 1, C, all GAP, row 2; levels (0, 6).  min_compared = 1: labels 0, 1, 2 at level 0 and 0, 0, 2 at level 6; nearest A -> (1;
+ * compared 6, differences 6, unshared 0), B -> (0; 6, 6, 0), C -> none.  min_compared = 0: labels 0, 0, 0 at both levels; nearest
+ * A -> 2, B -> 2, C -> 0, each with counts (0, 0, 8) -- the empty row is 0 differences from everything and links A to B, which is
+ * the reason for the default of 1.
+ * OUT OF SCOPE.  Any linkage other than single; trees, a minimum spanning tree included; cluster names that are stable across
+ * runs; a threshold on `unshared`; merging fragments of a split gene; any change to an existing report byte. */
+#define KP_CLUST_MAX_LEVELS 8
+typedef struct kp_dist_nearest { int32_t row, compared, differences, unshared; } kp_dist_nearest;  /* 16 bytes */
 
 #endif /* KP_SPEC_H */

@@ -84,6 +84,23 @@ DIST_CHUNK = 8  # KP_DIST_CHUNK: plane words (of 64 columns: four blocks) of a r
 DIST_MAX_ROWS = 1 << 18  # KP_DIST_MAX_ROWS of kaptive_amd/csrc/kp_caps.h
 DIST_MAX_DIFF = 10  # KP_DIST_MAX_DIFF of include/kp_spec.h: the command line's --max-distance
 DIST_MIN_COMPARED = 1  # KP_DIST_MIN_COMPARED: its --min-compared
+# Clusters and nearest neighbours of the same rows (include/kp_spec.h, CLUSTERS)
+DIST_NEAREST_DTYPE = np.dtype([("row", "<i4"), ("compared", "<i4"), ("differences", "<i4"), ("unshared", "<i4")])  # kp_dist_nearest: 16 bytes
+CLUST_MAX_LEVELS = 8  # KP_CLUST_MAX_LEVELS of include/kp_spec.h
+CLUSTER_LEVELS = (0, 1, 2, 5, 10)  # the command line's --cluster-levels
+
+
+def check_cluster_levels(levels) -> tuple:
+    """``levels`` as a tuple of ints, or ValueError: at most CLUST_MAX_LEVELS, none negative, strictly ascending (kp_dist_clusters)."""
+    lv = tuple(int(t) for t in levels)
+    if len(lv) > CLUST_MAX_LEVELS or any(t < 0 or t > 2**31 - 1 for t in lv) or any(b <= a for a, b in zip(lv, lv[1:])):
+        raise ValueError(f"cluster levels must be at most {CLUST_MAX_LEVELS} non-negative, strictly ascending numbers")
+    return lv
+
+
+def clusters_header(levels) -> bytes:
+    """The header line of the cluster table for ``levels`` (the columns of kp_format_clusters)."""
+    return ("\t".join(["Locus", "Assembly", *(f"HC{t}" for t in check_cluster_levels(levels)), "Nearest", "Differences", "Compared", "Unshared"]) + "\n").encode()
 
 JOIN_MAX_PIECES = 8  # KP_JOIN_MAX_PIECES
 JOIN_DTYPE = np.dtype(
@@ -99,7 +116,7 @@ EXPORTS = (
     "kp_batch_tasks", "kp_batch_task_results", "kp_batch_joins", "kp_batch_occ", "kp_batch_candidates", "kp_db_load_typing", "kp_db_load_typing_group", "kp_batch_use_group", "kp_batch_score", "kp_batch_reduce", "kp_batch_typing_caps",
     "kp_device_count", "kp_device_numa_node", "kp_batch_typing", "kp_batch_proteins", "kp_protein_align", "kp_fasta_pack", "kp_fasta_ingest", "kp_fasta_ingest_many", "kp_fasta_ingest_file", "kp_fasta_ingest_shard", "kp_shard_words_into", "kp_shard_free", "kp_fasta_simd", "kp_pack_contigs",
     "kp_fasta_free", "kp_format_rows", "kp_format_json", "kp_format_fasta", "kp_protein_align_seeded", "kp_randstrobes", "kp_randstrobe_top_hits",
-    "kp_dist_create", "kp_dist_count", "kp_dist_pairs", "kp_dist_destroy", "kp_format_distances",
+    "kp_dist_create", "kp_dist_count", "kp_dist_pairs", "kp_dist_destroy", "kp_format_distances", "kp_dist_clusters", "kp_format_clusters",
 )  # fmt: skip
 
 
@@ -760,6 +777,32 @@ def format_distances(locus_name: str, columns: int, names, pairs) -> bytes:
             return out[:need].tobytes()
         out = np.empty(int(need), np.uint8)
     raise NativeError("kp_format_distances: size kept changing")
+
+
+def format_clusters(locus_name: str, names, labels, nearest, rows=None) -> bytes:
+    """The lines of one locus's cluster table (kp_format_clusters; host only; no header: ``clusters_header``): one per row of the
+    locus's matrix.  ``labels`` int32 [K, R] and ``nearest`` (DIST_NEAREST_DTYPE [R]) as ``Distances.clusters`` returns them;
+    ``names`` the R assemblies' names, by row -- or, with ``rows`` (int32 [R]), row i is ``names[rows[i]]``."""
+    nm_b, nm_o = _blob64(names)
+    nearest = np.ascontiguousarray(nearest, dtype=DIST_NEAREST_DTYPE)
+    R = len(nearest)
+    labels = np.ascontiguousarray(labels, np.int32).reshape(-1, R) if R else np.zeros((len(labels), 0), np.int32)
+    if len(nm_o) - 1 != R or (rows is not None and len(rows) != R):
+        raise ValueError("a name, a nearest record and a label per level for every row")
+    rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+    locus = locus_name.encode("utf-8")
+    h = lib()
+    h.kp_format_clusters.restype = C.c_int64
+    out = np.empty(max(4096, 96 * R), np.uint8)
+    for _ in range(2):
+        need = h.kp_format_clusters(C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows),
+                                    C.c_int32(labels.shape[0]), _p(labels), _p(nearest), _p(out), C.c_int64(len(out)))
+        if need < 0:
+            raise ValueError(f"kp_format_clusters failed ({need})")
+        if need <= len(out):
+            return out[:need].tobytes()
+        out = np.empty(int(need), np.uint8)
+    raise NativeError("kp_format_clusters: size kept changing")
 
 
 class JsonTables(C.Structure):  # kp_json_tables
@@ -1439,6 +1482,21 @@ class Distances:
         out = np.zeros(self.count(max_diff, min_compared), DIST_PAIR_DTYPE)
         self.ctx._check(lib().kp_dist_pairs(self.ctx._h, self._h, _p(out), C.c_int64(len(out))), "kp_dist_pairs")
         return out
+
+    def clusters(self, levels=CLUSTER_LEVELS, min_compared: int = DIST_MIN_COMPARED, nearest: bool = True):
+        """(labels int32 [K, R], nearest DIST_NEAREST_DTYPE [R]) of the rows (kp_dist_clusters; include/kp_spec.h, CLUSTERS):
+        ``labels[k, r]`` is the smallest row of r's single-linkage cluster at ``differences <= levels[k]``, ``nearest[r]`` the row
+        with the fewest differences from r (then the smaller row) among those with ``compared >= min_compared``, with the pair's
+        three counts; row -1 where there is none.  With ``nearest=False`` the second item is None.  No pair is listed for it, and
+        the listing state of ``count`` / ``pairs`` is left alone."""
+        lv = np.array(check_cluster_levels(levels), np.int32)
+        labels = np.zeros((len(lv), self.n_rows), np.int32)
+        near = np.zeros(self.n_rows, DIST_NEAREST_DTYPE) if nearest else None
+        if nearest:
+            near["row"] = -1
+        self.ctx._check(lib().kp_dist_clusters(self.ctx._h, self._h, _p(lv) if len(lv) else None, C.c_int32(len(lv)), C.c_int32(int(min_compared)),
+                                               _p(labels) if labels.size else None, _p(near) if nearest else None), "kp_dist_clusters")
+        return labels, near
 
 
 RANDSTROBE_DTYPE = np.dtype([("hash", "<u8"), ("seq_idx", "<u4"), ("pos1", "<u4"), ("pos2", "<u4")])

@@ -142,7 +142,13 @@ def _add_outputs(p: argparse.ArgumentParser, tsv_flags, include_json: bool) -> N
         g.add_argument("--max-distance", type=int, metavar="N", default=argparse.SUPPRESS,
                        help="With --distances: most differing bases a listed pair may have (default: 10)")
         g.add_argument("--min-compared", type=int, metavar="N", default=argparse.SUPPRESS,
-                       help="With --distances: fewest columns both assemblies must hold a base in (default: 1)")
+                       help="With --distances or --clusters: fewest columns both assemblies must hold a base in (default: 1)")
+        g.add_argument("--clusters", metavar="FILE", default=argparse.SUPPRESS,
+                       help="Group the assemblies that carry the same locus by single linkage at every one of --cluster-levels "
+                            "differing bases, name every assembly's nearest neighbour, and write one line per assembly as a TSV "
+                            "table to a file; no pair is listed for it")
+        g.add_argument("--cluster-levels", metavar="T0,T1,...", default=argparse.SUPPRESS,
+                       help="With --clusters: the thresholds, comma-separated, strictly ascending, at most 8 (default: 0,1,2,5,10)")
     g.add_argument("--pha4ge", metavar="FILE", nargs="?", const="kaptive_results.pha4ge", type=Path,
                    help="Write PHA4GE-compliant serotyping report to a TSV file (default: %(const)s)")
 
@@ -161,12 +167,22 @@ class _Parser(argparse.ArgumentParser):
                     self.error(f"--{flag.replace('_', '-')} requires --rescue FILE")
                 if getattr(ns, flag) < 0 or (flag == "rescue_flank" and ns.rescue_flank > 65535):
                     self.error(f"--{flag.replace('_', '-')} is out of range")
-        for flag in ("max_distance", "min_compared"):
+        for flag, beside in (("max_distance", ("distances",)), ("min_compared", ("distances", "clusters"))):
             if getattr(ns, flag, None) is not None:
-                if not getattr(ns, "distances", None):
-                    self.error(f"--{flag.replace('_', '-')} requires --distances FILE")
+                if not any(getattr(ns, b, None) for b in beside):
+                    self.error(f"--{flag.replace('_', '-')} requires " + " or ".join(f"--{b} FILE" for b in beside))
                 if not 0 <= getattr(ns, flag) <= 2**31 - 1:
                     self.error(f"--{flag.replace('_', '-')} is out of range")
+        if getattr(ns, "cluster_levels", None) is not None:
+            if not getattr(ns, "clusters", None):
+                self.error("--cluster-levels requires --clusters FILE")
+            try:
+                from kaptive_amd._native import check_cluster_levels
+
+                v = ns.cluster_levels  # (the sub-command's parser has been here before its parent: then it is a tuple already)
+                ns.cluster_levels = check_cluster_levels(v if isinstance(v, tuple) else [int(t) for t in str(v).split(",")])
+            except ValueError:
+                self.error("--cluster-levels takes at most 8 comma-separated numbers, none negative, strictly ascending")
         return ns, rest
 
 
@@ -240,7 +256,7 @@ class _TypingPipeline:
         self.want_paf = bool(getattr(args, "paf", None))  # every hit with its CIGAR: the alignment passes of this run leave them
         self.paf_cs, self.paf_eqx = bool(getattr(args, "cs", False)), bool(getattr(args, "eqx", False))  # ... and its cs string
         self.want = {r.name: bool(getattr(args, r.name, None)) for r in REPORTS}  # the tables of the kept lists: the reductions of this run leave their records
-        self.want_distances = bool(getattr(args, "distances", None))  # the run's locus rows: every chunk's go with its outputs (LOCUS_ROWS_KEY)
+        self.want_distances = bool(getattr(args, "distances", None) or getattr(args, "clusters", None))  # the run's locus rows: every chunk's go with its outputs (LOCUS_ROWS_KEY)
         self.typer_options = {**self.want, "aligned": self.want["aligned"] or self.want_distances, **{k: getattr(args, k) for k in ("rescue_flank", "rescue_min_score") if getattr(args, k, None) is not None}}
         self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins", "paf", *self.want))  # the files' text (and contig names) are kept
         self.fasta_outputs = any(getattr(args, f, None) for f in ("loci", "genes", "proteins"))  # ... and result objects are built
@@ -636,15 +652,18 @@ def hits_to_paf(engine, genomes, hits, hit_off, ops, cigar_off, cs=None, cs_off=
     return _native.format_paf(engine.db.genes.ids, engine.db.genes.lengths, names, lengths, first, hits, hit_off, ops, cigar_off)
 
 
-LOCUS_ROWS_KEY = "locus_rows"  # a chunk's outputs: the ``LocusRows.state()`` of its assemblies (--distances); never written to a file
+LOCUS_ROWS_KEY = "locus_rows"  # a chunk's outputs: the ``LocusRows.state()`` of its assemblies (--distances, --clusters); never written to a file
 
 
 class _RunDistances:
-    """``--distances``: the locus rows of the whole run, merged chunk by chunk in input order -- one ``LocusRows`` per database -- and,
-    after the last chunk, compared on a device and written: one table, or with ``--db`` one per database (``per_database_path``)."""
+    """``--distances`` and ``--clusters``: the locus rows of the whole run, collected once for both, merged chunk by chunk in input
+    order -- one ``LocusRows`` per database -- and, after the last chunk, compared on a device and written: one table each, or with
+    ``--db`` one per database (``per_database_path``).  Both tables of a locus come from one device handle."""
 
     def __init__(self, args: argparse.Namespace) -> None:
-        self.path = args.distances
+        self.path = getattr(args, "distances", None)
+        self.clusters_path = getattr(args, "clusters", None)
+        self.levels = getattr(args, "cluster_levels", None)
         self.max_diff = getattr(args, "max_distance", None)
         self.min_compared = getattr(args, "min_compared", None)
         self.rows: "list | None" = None  # [(keyword or None, LocusRows)]
@@ -672,14 +691,21 @@ class _RunDistances:
 
         md = _native.DIST_MAX_DIFF if self.max_diff is None else self.max_diff
         mc = _native.DIST_MIN_COMPARED if self.min_compared is None else self.min_compared
+        levels = _native.CLUSTER_LEVELS if self.levels is None else self.levels
         for kw, rows in self.rows or []:
-            body = rows.tsv(ctx, md, mc)
-            if kw is None and _is_stdout(self.path):
-                sys.stdout.buffer.write(_native.DISTANCES_HEADER + body)
-                sys.stdout.buffer.flush()
-            else:
-                with open(self.path if kw is None else per_database_path(self.path, kw), "wb") as h:
-                    h.write(_native.DISTANCES_HEADER + body)
+            tables = []
+            if self.path:
+                tables.append((self.path, _native.DISTANCES_HEADER + rows.tsv(ctx, md, mc)))
+            if self.clusters_path:
+                tables.append((self.clusters_path, _native.clusters_header(levels) + rows.clusters_tsv(ctx, levels, mc)))
+            rows.close()  # (the handles of this database's loci: both tables have been made of them)
+            for path, text in tables:
+                if kw is None and _is_stdout(path):
+                    sys.stdout.buffer.write(text)
+                    sys.stdout.buffer.flush()
+                else:
+                    with open(path if kw is None else per_database_path(path, kw), "wb") as h:
+                        h.write(text)
 
 
 def _read_ahead_bytes() -> int:
@@ -861,9 +887,10 @@ def run_type(args: argparse.Namespace) -> int:
     for r in REPORTS:
         if getattr(args, "db", None) and (v := getattr(args, r.name, None)) and _is_stdout(v):
             raise ValueError(f"--{r.name} with --db writes a table per database: it needs a file name, not stdout")
-    if getattr(args, "db", None) and (v := getattr(args, "distances", None)) and _is_stdout(v):
-        raise ValueError("--distances with --db writes a table per database: it needs a file name, not stdout")
-    dist = _RunDistances(args) if getattr(args, "distances", None) else None
+    for flag in ("distances", "clusters"):
+        if getattr(args, "db", None) and (v := getattr(args, flag, None)) and _is_stdout(v):
+            raise ValueError(f"--{flag} with --db writes a table per database: it needs a file name, not stdout")
+    dist = _RunDistances(args) if getattr(args, "distances", None) or getattr(args, "clusters", None) else None
     run_dbs = None  # the databases of the run, where this process has loaded them (one device)
     handles = {}
     per_db = _PerDatabaseOutputs(args) if getattr(args, "db", None) else None  # several databases: reports per database

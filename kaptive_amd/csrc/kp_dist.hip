@@ -20,6 +20,12 @@
 //                          records: for a fixed (i, j) the sixteen pairs of a row are sixteen neighbouring lanes of one wave -- a
 //                          ballot, restricted to those sixteen bits, and mbcnt rank them in ascending b.
 //
+//   kp_dist_clust_kernel   the same tiles and counts with another epilogue (kp_spec.h, CLUSTERS; kp_clust.h): every valid pair is united
+//                          into the parent arrays of its levels by a lock-free union-find and offered to both of its rows as
+//                          nearest partner -- reduced inside the tile, then one 64-bit atomic minimum per row and tile.  Around
+//                          it kp_clust_init_kernel (identity parents, no partner), kp_clust_flatten_kernel (label = root) and
+//                          kp_dist_nearest_kernel (the partner's three counts, recomputed).  No pair is stored.
+//
 // Bounds: a lane reads planes only for r < R and w < NW, stores cnt only for a < R and tj < nt, and a record only below the total
 // the count pass found (the fill recomputes the same flags, so it is the same total).
 #include <algorithm>
@@ -28,6 +34,7 @@
 
 #include "kp_host.h"
 #include "kp_dist.h"
+#include "kp_clust.h"
 
 struct kp_dist {
     int device = 0;
@@ -43,6 +50,11 @@ struct kp_dist {
     bool counted = false;
     int32_t max_diff = 0, min_compared = 0;
     int64_t n_pairs = 0;
+    // clusters and nearest neighbours (kp_dist_clusters): allocated on its first call, at their largest size
+    DevBuf<int32_t> d_parent;             // [KP_CLUST_MAX_LEVELS][n_rows]
+    DevBuf<int32_t> d_label;              // [KP_CLUST_MAX_LEVELS][n_rows]
+    DevBuf<unsigned long long> d_best;    // [n_rows] nearest keys
+    DevBuf<kp_dist_nearest> d_nearest;    // [n_rows]
 };
 
 namespace {
@@ -66,15 +78,12 @@ __global__ __launch_bounds__(DIST_THREADS) void kp_dist_plane_kernel(const uint6
     }
 }
 
-template <bool FILL>
-__global__ __launch_bounds__(DIST_THREADS) void kp_dist_pair_kernel(const uint64_t *__restrict__ planes, int32_t R, int64_t NW, int32_t nt,
-                                                                    int32_t max_diff, int32_t min_compared, uint32_t *__restrict__ cnt,
-                                                                    const int64_t *__restrict__ off, kp_dist_pair *__restrict__ out, int64_t n_out) {
-    __shared__ uint64_t s[2][KP_DIST_PLANES][CH][T];
-    int32_t ti, tj;
-    kp_dist_tile_of((int64_t)blockIdx.x, nt, &ti, &tj);
+// The three counts of a lane's 4 x 4 pairs of tile (ti, tj), over all NW plane words: the chunk loop every pair kernel shares.  Ends
+// behind a __syncthreads: the strips in `s` are free for the caller.
+__device__ __forceinline__ void dist_tile_counts(const uint64_t *__restrict__ planes, int32_t R, int64_t NW, int32_t ti, int32_t tj,
+                                                 uint64_t (&s)[2][KP_DIST_PLANES][CH][T], int32_t (&cmp)[RG][RG], int32_t (&dif)[RG][RG],
+                                                 int32_t (&uns)[RG][RG]) {
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    int32_t cmp[RG][RG], dif[RG][RG], uns[RG][RG];
 #pragma unroll
     for (int i = 0; i < RG; ++i)
 #pragma unroll
@@ -105,6 +114,18 @@ __global__ __launch_bounds__(DIST_THREADS) void kp_dist_pair_kernel(const uint64
         }
         __syncthreads();  // (the next chunk overwrites the strips)
     }
+}
+
+template <bool FILL>
+__global__ __launch_bounds__(DIST_THREADS) void kp_dist_pair_kernel(const uint64_t *__restrict__ planes, int32_t R, int64_t NW, int32_t nt,
+                                                                    int32_t max_diff, int32_t min_compared, uint32_t *__restrict__ cnt,
+                                                                    const int64_t *__restrict__ off, kp_dist_pair *__restrict__ out, int64_t n_out) {
+    __shared__ uint64_t s[2][KP_DIST_PLANES][CH][T];
+    int32_t ti, tj;
+    kp_dist_tile_of((int64_t)blockIdx.x, nt, &ti, &tj);
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    int32_t cmp[RG][RG], dif[RG][RG], uns[RG][RG];
+    dist_tile_counts(planes, R, NW, ti, tj, s, cmp, dif, uns);
     // ---- listing: row a = ty + 16 i of the tile; its pairs with b = tx + 16 j ascend in (j, tx)
     const int lane = tid & 63, group = lane >> 4;  // the sixteen lanes of this lane's ty within its wave
     const unsigned long long group_bits = 0xffffull << (16 * group);
@@ -162,6 +183,100 @@ __global__ __launch_bounds__(DIST_THREADS) void kp_dist_row_scan_kernel(const ui
             if (t < nt) off[a * nt + t] = carry + (int64_t)(incl - c);
             carry += (int64_t)__shfl(incl, 63);
         }
+    }
+}
+
+// ---- clusters and nearest neighbours (kp_spec.h, CLUSTERS; the arithmetic: kp_clust.h) ----------------------------------------------
+// parent[k][r] = r, best[r] = none
+__global__ __launch_bounds__(DIST_THREADS) void kp_clust_init_kernel(int32_t R, int32_t K, int32_t *__restrict__ parent, unsigned long long *__restrict__ best) {
+    const int64_t n = (int64_t)R * K;
+    for (int64_t e = (int64_t)blockIdx.x * DIST_THREADS + threadIdx.x; e < std::max<int64_t>(n, R); e += (int64_t)gridDim.x * DIST_THREADS) {
+        if (e < n) parent[e] = (int32_t)(e % R);
+        if (e < R) best[e] = KP_CLUST_KEY_NONE;
+    }
+}
+
+// The pair kernel's tiles and counts with another epilogue.  A valid pair (a < b < R, compared >= min_compared)
+//   * is an edge from its first level on: it is united into parent[k][..] of those levels (kp_clust_edge; lock-free, no lane waits
+//     for another), and
+//   * offers b to a and a to b as nearest partner.  Row a's sixteen partners of one j are the sixteen tx of ty's lanes in one wave: the
+//     lane's minimum over j goes through four xor-shuffles, and tx 0 sends the row's minimum of this tile to best[a] -- one 64-bit
+//     atomic minimum per row and tile.  Column b's partners are spread over all ty: a lane's minimum over i, two xor-shuffles over
+//     the four ty of its wave, then the four waves through LDS (the strips are free behind the last __syncthreads of the chunk
+//     loop), and the first 64 lanes send one atomic minimum per column.  A diagonal tile holds the same rows on both sides; a < b keeps
+//     each pair once, and it still offers both ways.
+// Bounds: parent is read and written at rows a, b < R of levels < K and at values read from it, which are row indices (the init
+// kernel stored r, a hook stores a root, halving a grandparent); best at a, b < R; col_best at [wave < 4][column < 64].
+__global__ __launch_bounds__(DIST_THREADS) void kp_dist_clust_kernel(const uint64_t *__restrict__ planes, int32_t R, int64_t NW, int32_t nt,
+                                                                     KpClustLevels levels, int32_t min_compared, int32_t *__restrict__ parent,
+                                                                     unsigned long long *__restrict__ best) {
+    __shared__ uint64_t s[2][KP_DIST_PLANES][CH][T];
+    int32_t ti, tj;
+    kp_dist_tile_of((int64_t)blockIdx.x, nt, &ti, &tj);
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    int32_t cmp[RG][RG], dif[RG][RG], uns[RG][RG];
+    dist_tile_counts(planes, R, NW, ti, tj, s, cmp, dif, uns);
+    const int32_t K = levels.n;
+    uint64_t col_key[RG];
+#pragma unroll
+    for (int j = 0; j < RG; ++j) col_key[j] = KP_CLUST_KEY_NONE;
+#pragma unroll
+    for (int i = 0; i < RG; ++i) {
+        const int64_t a = (int64_t)ti * T + ty + 16 * i;
+        uint64_t row_key = KP_CLUST_KEY_NONE;
+#pragma unroll
+        for (int j = 0; j < RG; ++j) {
+            const int64_t b = (int64_t)tj * T + tx + 16 * j;
+            if (a < b && b < R && cmp[i][j] >= min_compared) {
+                row_key = std::min(row_key, kp_clust_key(dif[i][j], (int32_t)b));
+                col_key[j] = std::min(col_key[j], kp_clust_key(dif[i][j], (int32_t)a));
+                kp_clust_edge(parent, R, K, kp_clust_first_level(levels, dif[i][j]), (int32_t)a, (int32_t)b);
+            }
+        }
+#pragma unroll
+        for (int o = 8; o >= 1; o >>= 1) row_key = std::min(row_key, (uint64_t)__shfl_xor((unsigned long long)row_key, o));
+        if (tx == 0 && a < R && row_key != KP_CLUST_KEY_NONE) atomicMin(best + a, (unsigned long long)row_key);
+    }
+    uint64_t (*col_best)[T] = reinterpret_cast<uint64_t (*)[T]>(&s[0][0][0][0]);  // [wave][column of the tile]
+    const int wave = tid >> 6;
+#pragma unroll
+    for (int j = 0; j < RG; ++j) {
+        uint64_t k = col_key[j];
+        k = std::min(k, (uint64_t)__shfl_xor((unsigned long long)k, 16));
+        k = std::min(k, (uint64_t)__shfl_xor((unsigned long long)k, 32));
+        if ((tid & 63) < 16) col_best[wave][tx + 16 * j] = k;
+    }
+    __syncthreads();
+    if (tid < T) {
+        const uint64_t k = std::min(std::min(col_best[0][tid], col_best[1][tid]), std::min(col_best[2][tid], col_best[3][tid]));
+        const int64_t b = (int64_t)tj * T + tid;
+        if (b < R && k != KP_CLUST_KEY_NONE) atomicMin(best + b, (unsigned long long)k);
+    }
+}
+
+// label[k][r] = the root of r at level k.  A launch of its own: the kernel boundary is what orders it behind every hook.
+__global__ __launch_bounds__(DIST_THREADS) void kp_clust_flatten_kernel(int32_t R, int32_t K, int32_t *__restrict__ parent, int32_t *__restrict__ label) {
+    const int64_t n = (int64_t)R * K;
+    for (int64_t e = (int64_t)blockIdx.x * DIST_THREADS + threadIdx.x; e < n; e += (int64_t)gridDim.x * DIST_THREADS) {
+        const int64_t k = e / R;
+        label[e] = kp_clust_find(parent + k * R, (int32_t)(e - k * R));
+    }
+}
+
+// The nearest record of every row: the partner of best[r] and the pair's three counts, recomputed from the planes.
+__global__ __launch_bounds__(DIST_THREADS) void kp_dist_nearest_kernel(const uint64_t *__restrict__ planes, int32_t R, int64_t NW,
+                                                                       const unsigned long long *__restrict__ best, kp_dist_nearest *__restrict__ out) {
+    const size_t plane = (size_t)NW * (size_t)R;
+    for (int64_t r = (int64_t)blockIdx.x * DIST_THREADS + threadIdx.x; r < R; r += (int64_t)gridDim.x * DIST_THREADS) {
+        const int32_t partner = kp_clust_key_row(best[r]);
+        int32_t c = 0, d = 0, u = 0;
+        if (partner >= 0 && partner < R)
+            for (int64_t w = 0; w < NW; ++w) {
+                const uint64_t *at = planes + (size_t)w * (size_t)R;
+                kp_dist_word_counts(at[r], at[plane + r], at[2 * plane + r], at[3 * plane + r], at[partner], at[plane + partner], at[2 * plane + partner],
+                                    at[3 * plane + partner], &c, &d, &u);
+            }
+        kp_dist_nearest_store(out + r, partner >= 0 && partner < R ? partner : -1, c, d, u);
     }
 }
 
@@ -267,6 +382,47 @@ int kp_dist_pairs(kp_ctx *ctx, kp_dist *d, kp_dist_pair *out, int64_t cap) {
     int rc;
     if ((rc = dist_launch_pairs(ctx, d, true))) return rc;
     KP_HIP_CHECK(ctx, hipMemcpyAsync(out, d->d_rec.p, (size_t)d->n_pairs * sizeof(kp_dist_pair), hipMemcpyDeviceToHost, ctx->stream));
+    KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return KP_OK;
+}
+
+int kp_dist_clusters(kp_ctx *ctx, kp_dist *d, const int32_t *levels, int32_t n_levels, int32_t min_compared, int32_t *labels, kp_dist_nearest *nearest) {
+    if (!ctx) return kp_fail(nullptr, KP_EINVAL, "null context");
+    if (!d) return kp_fail(ctx, KP_EINVAL, "null distance handle");
+    if (d->device != ctx->device) return kp_fail(ctx, KP_EINVAL, "the distance handle belongs to another device");
+    if (n_levels < 0 || n_levels > KP_CLUST_MAX_LEVELS) return kp_fail(ctx, KP_EINVAL, "number of cluster levels outside 0 .. KP_CLUST_MAX_LEVELS");
+    if (n_levels > 0 && !levels) return kp_fail(ctx, KP_EINVAL, "null cluster levels");
+    if (!kp_clust_levels_valid(levels, n_levels)) return kp_fail(ctx, KP_EINVAL, "cluster levels must be non-negative and strictly ascending");
+    if (n_levels > 0 && d->n_rows > 0 && !labels) return kp_fail(ctx, KP_EINVAL, "null label table");
+    const int32_t R = d->n_rows, K = n_levels;
+    if (R == 0 || (K == 0 && !nearest)) return KP_OK;
+    const int64_t tiles = kp_dist_tiles(d->nt);
+    if (tiles * DIST_THREADS >= (1ll << 32)) return kp_fail(ctx, KP_EINVAL, "too many tiles for one grid (KP_DIST_MAX_ROWS)");  // (kp_dist_create refused it)
+    KpClustLevels lv{};
+    for (int32_t k = 0; k < KP_CLUST_MAX_LEVELS; ++k) lv.t[k] = k < K ? levels[k] : INT32_MAX;
+    lv.n = K;
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipError_t e = d->d_parent.reserve((size_t)KP_CLUST_MAX_LEVELS * (size_t)R);
+    if (e == hipSuccess) e = d->d_label.reserve((size_t)KP_CLUST_MAX_LEVELS * (size_t)R);
+    if (e == hipSuccess) e = d->d_best.reserve((size_t)R);
+    if (e == hipSuccess) e = d->d_nearest.reserve((size_t)R);
+    if (e != hipSuccess) return kp_fail(ctx, e == hipErrorOutOfMemory ? KP_ENOMEM : KP_EHIP, std::string("cluster tables: ") + hipGetErrorString(e));
+    const auto grid_of = [](int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + DIST_THREADS - 1) / DIST_THREADS, 1 << 16)); };
+    hipLaunchKernelGGL(kp_clust_init_kernel, dim3(grid_of((int64_t)R * std::max(K, 1))), dim3(DIST_THREADS), 0, ctx->stream, R, K, d->d_parent.p, d->d_best.p);
+    if (R > 1)  // (one row: no pair; label 0 and no neighbour come from the init kernel's tables)
+        hipLaunchKernelGGL(kp_dist_clust_kernel, dim3((unsigned)tiles), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, R, d->n_words, d->nt, lv, min_compared,
+                           d->d_parent.p, d->d_best.p);
+    if (K > 0) {
+        hipLaunchKernelGGL(kp_clust_flatten_kernel, dim3(grid_of((int64_t)R * K)), dim3(DIST_THREADS), 0, ctx->stream, R, K, d->d_parent.p, d->d_label.p);
+        KP_HIP_CHECK(ctx, hipGetLastError());
+        KP_HIP_CHECK(ctx, hipMemcpyAsync(labels, d->d_label.p, (size_t)K * (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (nearest) {
+        hipLaunchKernelGGL(kp_dist_nearest_kernel, dim3(grid_of(R)), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, R, d->n_words, d->d_best.p, d->d_nearest.p);
+        KP_HIP_CHECK(ctx, hipGetLastError());
+        KP_HIP_CHECK(ctx, hipMemcpyAsync(nearest, d->d_nearest.p, (size_t)R * sizeof(kp_dist_nearest), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    KP_HIP_CHECK(ctx, hipGetLastError());
     KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return KP_OK;
 }

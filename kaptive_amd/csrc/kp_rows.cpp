@@ -10,9 +10,11 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/kaptive_amd.h"
 #include "kp_alleles.h"
+#include "kp_clust.h"
 
 namespace {
 
@@ -549,6 +551,41 @@ extern "C" int64_t kp_format_distances(const char *locus_name, int32_t locus_nam
         put_i(o, r.compared); o.put('\t');
         put_i(o, r.differences); o.put('\t');
         put_i(o, r.unshared);
+        o.put('\n');
+    }
+    return o.n;
+}
+
+// ---- cluster table (kp_spec.h, CLUSTERS) --------------------------------------------------------------------------------------------
+// One line per row of one locus's matrix, in row order: its cluster number at every level (kp_clust_numbers), then its nearest row.
+extern "C" int64_t kp_format_clusters(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
+                                      const int32_t *rows, int32_t n_levels, const int32_t *labels, const kp_dist_nearest *nearest, char *out, int64_t cap) {
+    if (locus_name_len < 0 || (locus_name_len > 0 && !locus_name) || n_names < 0 || n_levels < 0 || n_levels > KP_CLUST_MAX_LEVELS || cap < 0 || (cap > 0 && !out)) return KP_EINVAL;
+    if (n_names > 0 && (!name_off || !nearest || (n_levels > 0 && !labels))) return KP_EINVAL;
+    const auto name_of = [&](int32_t r) { return rows ? rows[r] : r; };
+    for (int32_t r = 0; r < n_names; ++r) {
+        const int32_t at = name_of(r);
+        if (at < 0 || at >= n_names || name_off[at + 1] < name_off[at] || (name_off[at + 1] > name_off[at] && !names)) return KP_EINVAL;
+        if (nearest[r].row < -1 || nearest[r].row >= n_names) return KP_EINVAL;
+    }
+    std::vector<int32_t> number((size_t)n_levels * (size_t)n_names), rank((size_t)n_names);
+    for (int32_t k = 0; k < n_levels; ++k)
+        if (!kp_clust_numbers(labels + (size_t)k * (size_t)n_names, n_names, rank.data(), number.data() + (size_t)k * (size_t)n_names)) return KP_EINVAL;
+    Out o{out, cap};
+    for (int32_t r = 0; r < n_names; ++r) {
+        const kp_dist_nearest &nr = nearest[r];
+        if (locus_name_len > 0) o.put(locus_name, locus_name_len);  // (an empty name may come as a null pointer)
+        o.put('\t');
+        put_name(o, names, name_off, name_of(r)); o.put('\t');
+        for (int32_t k = 0; k < n_levels; ++k) { put_i(o, number[(size_t)k * (size_t)n_names + (size_t)r]); o.put('\t'); }
+        if (nr.row >= 0) {
+            put_name(o, names, name_off, name_of(nr.row)); o.put('\t');
+            put_i(o, nr.differences); o.put('\t');
+            put_i(o, nr.compared); o.put('\t');
+            put_i(o, nr.unshared);
+        } else {
+            o.lit(".\t.\t.\t.");
+        }
         o.put('\n');
     }
     return o.n;

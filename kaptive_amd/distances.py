@@ -3,7 +3,10 @@
 Every other report answers a question about one assembly; this one is about pairs: which isolates carry the same or nearly the same
 locus, and how many bases apart they are.  ``LocusRows`` collects, batch after batch, one LOCUS ROW per assembly -- the aligned rows of
 the primary kept records of its best locus's genes, strung together in database order, padding flagged -- and, when the run is over,
-hands the rows of every locus to the device as one matrix (``_native.Distances``: kp_dist.hip compares them all against all).
+hands the rows of every locus to the device as one matrix (``_native.Distances``: kp_dist.hip compares them all against all).  Two
+tables come of a matrix: the listed pairs (``distances`` / ``tsv``) and, with no pair listed, every row's single-linkage cluster at a
+few thresholds and its nearest neighbour (``clusters`` / ``clusters_tsv``; include/kp_spec.h, CLUSTERS).  One device handle per locus
+serves both: it is kept until the rows change or ``close()``.
 
 It spans batches and, on a multi-GPU run, processes: ``state()`` is a picklable payload of what was added, ``merge()`` absorbs one.
 """
@@ -19,6 +22,12 @@ GAP_BLOCK = np.uint64(0xFFFF << 48)  # sixteen GAP columns: a gene without a pri
 DIST_RECORD_DTYPE = np.dtype([("locus", "<i4"), ("a", "<i4"), ("b", "<i4"), ("compared", "<i4"), ("differences", "<i4"), ("unshared", "<i4")])
 
 
+def clust_record_dtype(n_levels: int) -> np.dtype:
+    """The records of ``LocusRows.clusters`` for ``n_levels`` levels: assembly numbers throughout, ``nearest`` -1 for none."""
+    return np.dtype([("locus", "<i4"), ("assembly", "<i4"), ("labels", "<i4", (int(n_levels),)), ("nearest", "<i4"), ("compared", "<i4"),
+                     ("differences", "<i4"), ("unshared", "<i4")])  # fmt: skip
+
+
 def pad_masks(gene_lengths) -> np.ndarray:
     """uint64 per gene: the GAP bits of the columns at or beyond the gene's length in its last block (kp_dist_pad_mask)."""
     n = np.asarray(gene_lengths, np.int64) & 15
@@ -29,14 +38,16 @@ class LocusRows:
     """The locus rows of a run, for one database.
 
     ``add(bt)`` takes a ``BatchTyping`` of an engine made with ``aligned=True``; ``distances(ctx)`` / ``tsv(ctx)`` / ``matrix(ctx,
-    locus)`` compare them on the device of ``ctx`` (a ``_native.Context``; no database needs to be resident in it).  Assemblies are
-    numbered in the order they were added."""
+    locus)`` and ``clusters(ctx)`` / ``clusters_tsv(ctx)`` compare them on the device of ``ctx`` (a ``_native.Context``; no database
+    needs to be resident in it).  Assemblies are numbered in the order they were added.  A locus's matrix is uploaded once, by the
+    first of these calls that needs it; ``close()`` -- or another ``add`` / ``merge`` -- frees the handles."""
 
     def __init__(self, db) -> None:
         self.db = db
         self.ids: list = []
         self.best = np.zeros(0, np.int32)
         self._parts: dict = {}  # locus -> [(assembly numbers int64 [k], matrix uint64 [k, NB])]
+        self._handles: dict = {}  # locus -> _native.Distances of its matrix as it stands
         lengths = np.asarray(db.genes.lengths, np.int64)
         self._gene_blocks = (lengths + 15) // 16
         self._gene_pad = pad_masks(lengths)
@@ -91,6 +102,7 @@ class LocusRows:
 
     def add(self, bt) -> None:
         """The assemblies of one typed batch (``BatchTyping``; its engine must have been made with ``aligned=True``)."""
+        self.close()
         rows, blocks = bt.aligned()
         n = len(bt.sums)
         base = len(self.ids)
@@ -122,6 +134,7 @@ class LocusRows:
 
     def merge(self, state: dict) -> None:
         """Absorbs the ``state()`` of another accumulator of the same database: its assemblies follow the ones already here."""
+        self.close()
         base = len(self.ids)
         for L, (idx, mat) in state["loci"].items():
             if mat.shape[1] != self.n_blocks(L):
@@ -131,12 +144,35 @@ class LocusRows:
         self.best = np.concatenate([self.best, np.asarray(state["best"], np.int32)])
 
     # -- comparing -------------------------------------------------------------------------------------------------------------------
+    def _handle(self, ctx, locus: int):
+        """The device handle of ``locus``'s matrix on ``ctx``: made on first use, then shared by every table."""
+        h = self._handles.get(int(locus))
+        if h is None or h.ctx is not ctx or not h._h:
+            if h is not None:
+                h.close()
+            h = self._handles[int(locus)] = _native.Distances(ctx, self.locus_matrix(locus)[1])
+        return h
+
+    def close(self) -> None:
+        """Frees the device handles (the rows stay: a later call uploads them again)."""
+        for h in self._handles.values():
+            h.close()
+        self._handles.clear()
+
     def _locus_pairs(self, ctx, locus: int, max_diff, min_compared):
         idx, mat = self.locus_matrix(locus)
         if len(idx) < 2:
             return idx, np.zeros(0, _native.DIST_PAIR_DTYPE)
-        with _native.Distances(ctx, mat) as d:
-            return idx, d.pairs(max_diff, min_compared)
+        return idx, self._handle(ctx, locus).pairs(max_diff, min_compared)
+
+    def _locus_clusters(self, ctx, locus: int, levels, min_compared):
+        """(assembly numbers [R], labels int32 [K, R] as rows of the matrix, nearest records [R]) of one locus."""
+        idx, mat = self.locus_matrix(locus)
+        if len(idx) < 2:  # one row: its own cluster at every level, no neighbour
+            near = np.zeros(len(idx), _native.DIST_NEAREST_DTYPE)
+            near["row"] = -1
+            return idx, np.zeros((len(_native.check_cluster_levels(levels)), len(idx)), np.int32), near
+        return (idx, *self._handle(ctx, locus).clusters(levels, min_compared))
 
     def distances(self, ctx, max_diff: "int | None" = _native.DIST_MAX_DIFF, min_compared: int = _native.DIST_MIN_COMPARED) -> np.ndarray:
         """DIST_RECORD_DTYPE records ``(locus, a, b, compared, differences, unshared)`` of the listed pairs: loci in database order, one
@@ -159,6 +195,32 @@ class LocusRows:
         for L in self.loci():
             idx, p = self._locus_pairs(ctx, L, max_diff, min_compared)
             out.append(_native.format_distances(self.db.loci.ids[L], self.columns(L), [self.ids[i] for i in idx], p))
+        return b"".join(out)
+
+    def clusters(self, ctx, levels=_native.CLUSTER_LEVELS, min_compared: int = _native.DIST_MIN_COMPARED) -> np.ndarray:
+        """``clust_record_dtype(len(levels))`` records, one per assembly: loci in database order, assemblies in input order within a
+        locus; ``labels[k]`` is the smallest assembly number of the assembly's cluster at ``levels[k]``, ``nearest`` the number of
+        its nearest assembly (-1: none) with the pair's three counts."""
+        dt = clust_record_dtype(len(_native.check_cluster_levels(levels)))
+        out = []
+        for L in self.loci():
+            idx, labels, near = self._locus_clusters(ctx, L, levels, min_compared)
+            rec = np.zeros(len(idx), dt)
+            rec["locus"], rec["assembly"] = L, idx
+            rec["labels"] = idx[labels].T
+            rec["nearest"] = np.where(near["row"] >= 0, idx[np.maximum(near["row"], 0)], -1)
+            for f in ("compared", "differences", "unshared"):
+                rec[f] = near[f]
+            out.append(rec)
+        return np.concatenate(out) if out else np.zeros(0, dt)
+
+    def clusters_tsv(self, ctx, levels=_native.CLUSTER_LEVELS, min_compared: int = _native.DIST_MIN_COMPARED) -> bytes:
+        """The lines of the cluster table (``--clusters``; no header: ``_native.clusters_header(levels)``), formatted by the native
+        library (kp_format_clusters): loci in database order, a line per assembly in input order."""
+        out = []
+        for L in self.loci():
+            idx, labels, near = self._locus_clusters(ctx, L, levels, min_compared)
+            out.append(_native.format_clusters(self.db.loci.ids[L], [self.ids[i] for i in idx], labels, near))
         return b"".join(out)
 
     def matrix(self, ctx, locus: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:

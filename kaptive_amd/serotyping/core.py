@@ -60,7 +60,9 @@ class Serotyper:
         (``Engine(db, aligned=True)``); ``rescue``: it leaves the rescue records of the missing genes (``Engine(db, rescue=True,
         rescue_flank=...)``), and ``rescue_min_score`` is the score below which their table calls a gene ``absent`` (default
         ``_native.RESCUE_MIN_SCORE``); ``distances``: every batch this typer types also feeds ``locus_rows``, the run's
-        ``distances.LocusRows`` of this database (include/kp_spec.h, DISTANCES) -- it implies ``aligned``."""
+        ``distances.LocusRows`` of this database (include/kp_spec.h, DISTANCES) -- it implies ``aligned``.  The one keyword feeds both
+        tables of the rows: the listed pairs (``locus_rows.distances`` / ``tsv``) and the clusters and nearest neighbours
+        (``locus_rows.clusters`` / ``clusters_tsv``; CLUSTERS)."""
         self._db = db
         self._variants = bool(variants)
         self._breakpoints = bool(breakpoints)
@@ -442,7 +444,8 @@ class MultiSerotyper:
         rescue_min_score: "int | None" = None,
         distances: bool = False,
     ) -> None:
-        """``distances``: every one of ``.serotypers`` keeps the ``locus_rows`` of its database (it implies ``aligned``)."""
+        """``distances``: every one of ``.serotypers`` keeps the ``locus_rows`` of its database (it implies ``aligned``); they feed the
+        distance table and the cluster table alike."""
         self.dbs = list(dbs)
         check_databases(self.dbs)
         self._device = device
