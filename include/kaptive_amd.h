@@ -590,6 +590,29 @@ KP_API int kp_dist_clusters(kp_ctx *ctx, kp_dist *d, const int32_t *levels, int3
 KP_API int64_t kp_format_clusters(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off,
                                   int32_t n_names, const int32_t *rows /* [n_names] or null */, int32_t n_levels,
                                   const int32_t *labels, const kp_dist_nearest *nearest, char *out, int64_t cap);
+/* The minimum spanning forest of a handle's rows (kp_spec.h, TREE): Boruvka's rounds over the same tiles, no pair stored.
+ *   edges [cap]: the forest's *n_edges = n_rows - (number of trees) records, ascending by (differences, a, b).
+ *   component [n_rows]: the smallest row of every row's tree; may be null.
+ * KP_EINVAL for a null context, handle or n_edges, a handle of another device, cap < n_rows - 1 with n_rows > 1, null edges with
+ * cap > 0, and a matrix of 16 * n_blocks >= 2^28 columns, which does not fit the packed edge key (KP_TREE_MAX_COLUMNS, kp_caps.h;
+ * the other calls of the handle keep their own limit).  min_compared as kp_dist_clusters takes it.  n_rows of 0 and 1 are valid:
+ * no edge, and one row is its own component.  KP_ESTATE if the rounds reach their bound (ceil(log2 n_rows) + 1) with edges still
+ * arriving; no matrix does that.  The call leaves the handle's listing state and its cluster tables alone.  Its tables are the
+ * handle's own, allocated once, on the first call; like everything a handle does, kp_device_allocations does not count them.
+ *   kp_dist_tree_rounds: the rounds the handle's last kp_dist_tree ran, the empty last one included (0: none ran). */
+KP_API int kp_dist_tree(kp_ctx *ctx, kp_dist *d, int32_t min_compared, kp_dist_pair *edges, int64_t cap, int64_t *n_edges,
+                        int32_t *component /* [n_rows], may be null */);
+KP_API int32_t kp_dist_tree_rounds(const kp_dist *d);
+/* The Newick table of one locus (host only): one tab-separated line per tree of the forest, ascending in the tree's smallest row:
+ * Locus, Tree (the 1-based rank of the component's label), Assemblies (its rows), Newick (kp_spec.h, TREE, NEWICK).  No header
+ * line.  names / name_off [n_names + 1]: the assemblies' names; row i of the matrix is named names[rows[i]], or names[i] when rows
+ * is null; edges and component [n_names] as kp_dist_tree filled them.  Written without recursion.  Return value as
+ * kp_format_variants has it; KP_EINVAL also for an edge or an entry of rows outside [0, n_names), an edge with a >= b, edges that
+ * close a cycle or join rows of different components, and a component label that is not the smallest row of its tree.  The edge
+ * table needs no formatter of its own: kp_format_distances writes kp_dist_pair records. */
+KP_API int64_t kp_format_newick(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
+                                const int32_t *rows /* [n_names] or null */, const kp_dist_pair *edges, int64_t n_edges, const int32_t *component,
+                                char *out, int64_t cap);
 
 /* ---- JSON lines of a whole batch (host only) ----------------------------------------------------------------------------------
  * Replaces orjson.dumps(SerotypingResult.to_dict(), OPT_SERIALIZE_NUMPY | OPT_APPEND_NEWLINE) per genome

@@ -666,7 +666,8 @@ typedef struct kp_rescue {
  * measurements: ten differences in a 25 kb locus is 0.04 %, well inside one outbreak and well below two variants of a locus; one
  * compared column keeps pairs of empty rows out of the table.
  * OUT OF SCOPE.  Merging fragments of one gene; distances between isolates of different loci or different databases; indel events
- * as events (an inserted run counts through `unshared` only); trees (clusters: CLUSTERS, below); any change to an existing report byte. */
+ * as events (an inserted run counts through `unshared` only); neighbour-joining or any tree with inferred inner nodes (clusters:
+ * CLUSTERS, a minimum spanning tree: TREE, below); any change to an existing report byte. */
 #define KP_DIST_MAX_DIFF 10
 #define KP_DIST_MIN_COMPARED 1
 typedef struct kp_dist_pair {
@@ -698,9 +699,40 @@ typedef struct kp_dist_pair {
  * compared 6, differences 6, unshared 0), B -> (0; 6, 6, 0), C -> none.  min_compared = 0: labels 0, 0, 0 at both levels; nearest
  * A -> 2, B -> 2, C -> 0, each with counts (0, 0, 8) -- the empty row is 0 differences from everything and links A to B, which is
  * the reason for the default of 1.
- * OUT OF SCOPE.  Any linkage other than single; trees, a minimum spanning tree included; cluster names that are stable across
- * runs; a threshold on `unshared`; merging fragments of a split gene; any change to an existing report byte. */
+ * OUT OF SCOPE.  Any linkage other than single; neighbour-joining or any tree with inferred inner nodes (the minimum spanning tree
+ * of the same edges: TREE, below); cluster names that are stable across runs; a threshold on `unshared`; merging fragments of a
+ * split gene; any change to an existing report byte. */
 #define KP_CLUST_MAX_LEVELS 8
 typedef struct kp_dist_nearest { int32_t row, compared, differences, unshared; } kp_dist_nearest;  /* 16 bytes */
+
+/* ---- TREE (optional; a third reduction over the pairs of DISTANCES: no pair record, no report byte depends on it) ------------------
+ * Who links to whom inside a cluster, and in what order do the links form?  The minimum spanning forest of one matrix of locus rows
+ * answers both, and it is the single-linkage dendrogram at every threshold at once.
+ *
+ * GRAPH.  The vertices are the rows of one matrix of locus rows.  A pair (a, b), a < b, is an edge iff compared >= min_compared --
+ * the CLUSTERS edge rule without a threshold.
+ * KEY.  An edge's key is (differences, a, b), compared lexicographically.  The key is a strict total order, so the minimum spanning
+ * forest under it is unique: a PURE FUNCTION of the matrix and min_compared, which depends neither on the tile shape, nor on
+ * scheduling, nor on the order in which edges are met.
+ * FOREST.  Its edges are n_rows - n_components records of kp_dist_pair -- a, b and the pair's three counts --, ascending by key.
+ * component[r] is the smallest row of r's tree.
+ * PROPERTIES.  (1) For every T, the connected components of the forest's edges with differences <= T are the CLUSTERS labels at
+ * level T with the same min_compared.  (2) Every row's NEAREST pair is an edge of the forest: among partners at equal differences
+ * the smaller row wins under both keys.
+ * PACKED KEY.  differences << 36 | a << 18 | b in 64 bits, ordered as the tuple: rows are below KP_DIST_MAX_ROWS = 2^18, and the
+ * differences fit 28 bits when 16 * n_blocks < 2^28 (KP_TREE_MAX_COLUMNS, kp_caps.h).  A matrix beyond that is refused by the tree
+ * alone.  All ones is "no edge": a < b keeps every key below it.
+ * ROUNDS.  The forest is built by Boruvka's rounds: every component takes its lightest outgoing edge.  The components that still
+ * have one at least halve each round, so ceil(log2(max(n_rows, 2))) + 1 rounds, the last of them empty, always suffice.
+ * KNOWN ANSWERS, on the three rows of the DISTANCES known answers (A is row 0, B row 1, C, all GAP, row 2).  min_compared = 1: one
+ * edge (0, 1; compared 6, differences 6, unshared 0), components 0, 0, 2.  min_compared = 0: edges (0, 2; 0, 0, 8) and (1, 2; 0, 0,
+ * 8) in that order, components 0, 0, 0.
+ * NEWICK (host only).  One tree per component, rooted at the component's smallest row.  Every node, inner ones included, is
+ * labelled with its assembly's name; a node's children are its tree neighbours away from the root, ascending by (differences,
+ * row); the branch length is the integer `differences`.  A node with children is written (child:len,child:len)name, a leaf name,
+ * and the tree ends in ;.  A name is written bare when every byte is in A-Za-z0-9_.- and otherwise in single quotes with every '
+ * doubled.  The known answers: (B:6)A; and C; with min_compared = 1, ((B:0)C:0)A; with 0.
+ * OUT OF SCOPE.  Any linkage other than single; neighbour-joining or any tree with inferred inner nodes; names that are stable
+ * across runs; any change to an existing report byte. */
 
 #endif /* KP_SPEC_H */

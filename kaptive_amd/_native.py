@@ -102,6 +102,18 @@ def clusters_header(levels) -> bytes:
     """The header line of the cluster table for ``levels`` (the columns of kp_format_clusters)."""
     return ("\t".join(["Locus", "Assembly", *(f"HC{t}" for t in check_cluster_levels(levels)), "Nearest", "Differences", "Compared", "Unshared"]) + "\n").encode()
 
+
+# Minimum spanning forest of the same rows (include/kp_spec.h, TREE): its edges are DIST_PAIR_DTYPE records, its edge table has the
+# columns of DISTANCES_HEADER
+TREE_MAX_COLUMNS = 1 << 28  # KP_TREE_MAX_COLUMNS of kaptive_amd/csrc/kp_caps.h: a locus of as many columns does not fit the packed edge key
+NEWICK_HEADER = b"Locus\tTree\tAssemblies\tNewick\n"  # the columns of kp_format_newick
+
+
+def newick_header() -> bytes:
+    """The header line of the Newick table (the columns of kp_format_newick)."""
+    return NEWICK_HEADER
+
+
 JOIN_MAX_PIECES = 8  # KP_JOIN_MAX_PIECES
 JOIN_DTYPE = np.dtype(
     [("gs", "<i4"), ("contig", "<i4"), ("n_pieces", "<i4"), ("n_anchors", "<i4"), ("chain_score", "<i4"), ("width", "<i4"),
@@ -117,6 +129,7 @@ EXPORTS = (
     "kp_device_count", "kp_device_numa_node", "kp_batch_typing", "kp_batch_proteins", "kp_protein_align", "kp_fasta_pack", "kp_fasta_ingest", "kp_fasta_ingest_many", "kp_fasta_ingest_file", "kp_fasta_ingest_shard", "kp_shard_words_into", "kp_shard_free", "kp_fasta_simd", "kp_pack_contigs",
     "kp_fasta_free", "kp_format_rows", "kp_format_json", "kp_format_fasta", "kp_protein_align_seeded", "kp_randstrobes", "kp_randstrobe_top_hits",
     "kp_dist_create", "kp_dist_count", "kp_dist_pairs", "kp_dist_destroy", "kp_format_distances", "kp_dist_clusters", "kp_format_clusters",
+    "kp_dist_tree", "kp_dist_tree_rounds", "kp_format_newick",
 )  # fmt: skip
 
 
@@ -803,6 +816,32 @@ def format_clusters(locus_name: str, names, labels, nearest, rows=None) -> bytes
             return out[:need].tobytes()
         out = np.empty(int(need), np.uint8)
     raise NativeError("kp_format_clusters: size kept changing")
+
+
+def format_newick(locus_name: str, names, edges, component, rows=None) -> bytes:
+    """The lines of one locus's Newick table (kp_format_newick; host only; no header: ``newick_header``): one per tree of the forest,
+    ascending in the tree's smallest row.  ``edges`` (DIST_PAIR_DTYPE [E]) and ``component`` (int32 [R]) as ``Distances.tree``
+    returns them; ``names`` the R assemblies' names, by row -- or, with ``rows`` (int32 [R]), row i is ``names[rows[i]]``."""
+    nm_b, nm_o = _blob64(names)
+    edges = np.ascontiguousarray(edges, dtype=DIST_PAIR_DTYPE)
+    component = np.ascontiguousarray(component, np.int32)
+    R = len(component)
+    if len(nm_o) - 1 != R or (rows is not None and len(rows) != R):
+        raise ValueError("a name and a component for every row")
+    rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+    locus = locus_name.encode("utf-8")
+    h = lib()
+    h.kp_format_newick.restype = C.c_int64
+    out = np.empty(max(4096, 64 * R + len(nm_b) + 64), np.uint8)
+    for _ in range(2):
+        need = h.kp_format_newick(C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows),
+                                  _p(edges), C.c_int64(len(edges)), _p(component), _p(out), C.c_int64(len(out)))
+        if need < 0:
+            raise ValueError(f"kp_format_newick failed ({need})")
+        if need <= len(out):
+            return out[:need].tobytes()
+        out = np.empty(int(need), np.uint8)
+    raise NativeError("kp_format_newick: size kept changing")
 
 
 class JsonTables(C.Structure):  # kp_json_tables
@@ -1497,6 +1536,24 @@ class Distances:
         self.ctx._check(lib().kp_dist_clusters(self.ctx._h, self._h, _p(lv) if len(lv) else None, C.c_int32(len(lv)), C.c_int32(int(min_compared)),
                                                _p(labels) if labels.size else None, _p(near) if nearest else None), "kp_dist_clusters")
         return labels, near
+
+    def tree(self, min_compared: int = DIST_MIN_COMPARED):
+        """(edges DIST_PAIR_DTYPE [E], component int32 [R]) of the rows' minimum spanning forest (kp_dist_tree; include/kp_spec.h,
+        TREE): the graph's edges are the pairs with ``compared >= min_compared``, an edge's key is (differences, a, b); the forest's
+        edges ascend by key, ``component[r]`` is the smallest row of r's tree and ``E == R - number of trees``.  No pair is listed
+        for it; the listing state and the cluster tables are left alone."""
+        edges = np.zeros(max(self.n_rows - 1, 0), DIST_PAIR_DTYPE)
+        component = np.zeros(self.n_rows, np.int32)
+        n = C.c_int64(0)
+        self.ctx._check(lib().kp_dist_tree(self.ctx._h, self._h, C.c_int32(int(min_compared)), _p(edges) if len(edges) else None, C.c_int64(len(edges)),
+                                           C.byref(n), _p(component) if self.n_rows else None), "kp_dist_tree")
+        return edges[: n.value].copy(), component
+
+    def tree_rounds(self) -> int:
+        """The rounds the last ``tree`` ran on the device, the empty last one included (kp_dist_tree_rounds)."""
+        h = lib()
+        h.kp_dist_tree_rounds.restype = C.c_int32
+        return int(h.kp_dist_tree_rounds(self._h))
 
 
 RANDSTROBE_DTYPE = np.dtype([("hash", "<u8"), ("seq_idx", "<u4"), ("pos1", "<u4"), ("pos2", "<u4")])

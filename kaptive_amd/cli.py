@@ -142,13 +142,18 @@ def _add_outputs(p: argparse.ArgumentParser, tsv_flags, include_json: bool) -> N
         g.add_argument("--max-distance", type=int, metavar="N", default=argparse.SUPPRESS,
                        help="With --distances: most differing bases a listed pair may have (default: 10)")
         g.add_argument("--min-compared", type=int, metavar="N", default=argparse.SUPPRESS,
-                       help="With --distances or --clusters: fewest columns both assemblies must hold a base in (default: 1)")
+                       help="With --distances, --clusters, --mst or --newick: fewest columns both assemblies must hold a base in (default: 1)")
         g.add_argument("--clusters", metavar="FILE", default=argparse.SUPPRESS,
                        help="Group the assemblies that carry the same locus by single linkage at every one of --cluster-levels "
                             "differing bases, name every assembly's nearest neighbour, and write one line per assembly as a TSV "
                             "table to a file; no pair is listed for it")
         g.add_argument("--cluster-levels", metavar="T0,T1,...", default=argparse.SUPPRESS,
                        help="With --clusters: the thresholds, comma-separated, strictly ascending, at most 8 (default: 0,1,2,5,10)")
+        g.add_argument("--mst", metavar="FILE", default=argparse.SUPPRESS,
+                       help="Build the minimum spanning tree of the assemblies that carry the same locus, by differing bases, and "
+                            "write its edges as a TSV table with the columns of --distances to a file; no pair is listed for it")
+        g.add_argument("--newick", metavar="FILE", default=argparse.SUPPRESS,
+                       help="The same trees as Newick text, one line per tree, as a TSV table to a file")
     g.add_argument("--pha4ge", metavar="FILE", nargs="?", const="kaptive_results.pha4ge", type=Path,
                    help="Write PHA4GE-compliant serotyping report to a TSV file (default: %(const)s)")
 
@@ -167,7 +172,7 @@ class _Parser(argparse.ArgumentParser):
                     self.error(f"--{flag.replace('_', '-')} requires --rescue FILE")
                 if getattr(ns, flag) < 0 or (flag == "rescue_flank" and ns.rescue_flank > 65535):
                     self.error(f"--{flag.replace('_', '-')} is out of range")
-        for flag, beside in (("max_distance", ("distances",)), ("min_compared", ("distances", "clusters"))):
+        for flag, beside in (("max_distance", ("distances",)), ("min_compared", ("distances", "clusters", "mst", "newick"))):
             if getattr(ns, flag, None) is not None:
                 if not any(getattr(ns, b, None) for b in beside):
                     self.error(f"--{flag.replace('_', '-')} requires " + " or ".join(f"--{b} FILE" for b in beside))
@@ -256,7 +261,7 @@ class _TypingPipeline:
         self.want_paf = bool(getattr(args, "paf", None))  # every hit with its CIGAR: the alignment passes of this run leave them
         self.paf_cs, self.paf_eqx = bool(getattr(args, "cs", False)), bool(getattr(args, "eqx", False))  # ... and its cs string
         self.want = {r.name: bool(getattr(args, r.name, None)) for r in REPORTS}  # the tables of the kept lists: the reductions of this run leave their records
-        self.want_distances = bool(getattr(args, "distances", None) or getattr(args, "clusters", None))  # the run's locus rows: every chunk's go with its outputs (LOCUS_ROWS_KEY)
+        self.want_distances = any(getattr(args, f, None) for f in PAIR_TABLES)  # the run's locus rows: every chunk's go with its outputs (LOCUS_ROWS_KEY)
         self.typer_options = {**self.want, "aligned": self.want["aligned"] or self.want_distances, **{k: getattr(args, k) for k in ("rescue_flank", "rescue_min_score") if getattr(args, k, None) is not None}}
         self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins", "paf", *self.want))  # the files' text (and contig names) are kept
         self.fasta_outputs = any(getattr(args, f, None) for f in ("loci", "genes", "proteins"))  # ... and result objects are built
@@ -652,17 +657,21 @@ def hits_to_paf(engine, genomes, hits, hit_off, ops, cigar_off, cs=None, cs_off=
     return _native.format_paf(engine.db.genes.ids, engine.db.genes.lengths, names, lengths, first, hits, hit_off, ops, cigar_off)
 
 
-LOCUS_ROWS_KEY = "locus_rows"  # a chunk's outputs: the ``LocusRows.state()`` of its assemblies (--distances, --clusters); never written to a file
+LOCUS_ROWS_KEY = "locus_rows"  # a chunk's outputs: the ``LocusRows.state()`` of its assemblies (PAIR_TABLES); never written to a file
+PAIR_TABLES = ("distances", "clusters", "mst", "newick")  # the flags whose tables are made of the run's locus rows
 
 
 class _RunDistances:
-    """``--distances`` and ``--clusters``: the locus rows of the whole run, collected once for both, merged chunk by chunk in input
-    order -- one ``LocusRows`` per database -- and, after the last chunk, compared on a device and written: one table each, or with
-    ``--db`` one per database (``per_database_path``).  Both tables of a locus come from one device handle."""
+    """``--distances``, ``--clusters``, ``--mst`` and ``--newick``: the locus rows of the whole run, collected once for all of them,
+    merged chunk by chunk in input order -- one ``LocusRows`` per database -- and, after the last chunk, compared on a device and
+    written: one table each, or with ``--db`` one per database (``per_database_path``).  All tables of a locus come from one device
+    handle."""
 
     def __init__(self, args: argparse.Namespace) -> None:
         self.path = getattr(args, "distances", None)
         self.clusters_path = getattr(args, "clusters", None)
+        self.mst_path = getattr(args, "mst", None)
+        self.newick_path = getattr(args, "newick", None)
         self.levels = getattr(args, "cluster_levels", None)
         self.max_diff = getattr(args, "max_distance", None)
         self.min_compared = getattr(args, "min_compared", None)
@@ -698,7 +707,11 @@ class _RunDistances:
                 tables.append((self.path, _native.DISTANCES_HEADER + rows.tsv(ctx, md, mc)))
             if self.clusters_path:
                 tables.append((self.clusters_path, _native.clusters_header(levels) + rows.clusters_tsv(ctx, levels, mc)))
-            rows.close()  # (the handles of this database's loci: both tables have been made of them)
+            if self.mst_path:
+                tables.append((self.mst_path, _native.DISTANCES_HEADER + rows.tree_tsv(ctx, mc)))
+            if self.newick_path:
+                tables.append((self.newick_path, _native.newick_header() + rows.newick_tsv(ctx, mc)))
+            rows.close()  # (the handles of this database's loci: every table has been made of them)
             for path, text in tables:
                 if kw is None and _is_stdout(path):
                     sys.stdout.buffer.write(text)
@@ -887,10 +900,10 @@ def run_type(args: argparse.Namespace) -> int:
     for r in REPORTS:
         if getattr(args, "db", None) and (v := getattr(args, r.name, None)) and _is_stdout(v):
             raise ValueError(f"--{r.name} with --db writes a table per database: it needs a file name, not stdout")
-    for flag in ("distances", "clusters"):
+    for flag in PAIR_TABLES:
         if getattr(args, "db", None) and (v := getattr(args, flag, None)) and _is_stdout(v):
             raise ValueError(f"--{flag} with --db writes a table per database: it needs a file name, not stdout")
-    dist = _RunDistances(args) if getattr(args, "distances", None) or getattr(args, "clusters", None) else None
+    dist = _RunDistances(args) if any(getattr(args, f, None) for f in PAIR_TABLES) else None
     run_dbs = None  # the databases of the run, where this process has loaded them (one device)
     handles = {}
     per_db = _PerDatabaseOutputs(args) if getattr(args, "db", None) else None  # several databases: reports per database

@@ -274,3 +274,12 @@ inline bool kp_caps_set_option(KpCapOptions &o, KpLearnt &L, std::vector<KpRunCa
 // 2^18 rows are nt = 4096 and 8 390 656 blocks, 2 148 007 936 work items -- half the limit (kp_dist.hip asserts it) --; the
 // listing's count table then has rows * nt = 2^30 entries, indexed in 64 bits, and every tile index fits an int32.
 constexpr int32_t KP_DIST_MAX_ROWS = 1 << 18;
+
+// the packed edge key of a tree (kp_tree.h; kp_spec.h, TREE): differences << 36 | a << 18 | b, one 64-bit word that a single
+// atomic minimum orders as the tuple.  Rows take KP_TREE_ROW_BITS each -- all of KP_DIST_MAX_ROWS fit --, which leaves
+// KP_TREE_DIFF_BITS for the differences: a matrix of 16 * n_blocks >= KP_TREE_MAX_COLUMNS columns is refused by kp_dist_tree, and by
+// it alone (the other calls of a handle keep kp_dist_create's limit of 2^31 columns).
+constexpr int KP_TREE_ROW_BITS = 18, KP_TREE_DIFF_BITS = 28;
+constexpr int64_t KP_TREE_MAX_COLUMNS = 1ll << KP_TREE_DIFF_BITS;
+static_assert(KP_TREE_DIFF_BITS + KP_TREE_ROW_BITS + KP_TREE_ROW_BITS == 64, "28 + 18 + 18: the key fills one 64-bit word");
+static_assert(KP_DIST_MAX_ROWS <= (1 << KP_TREE_ROW_BITS), "every row of the largest matrix must fit the key's row fields");

@@ -26,15 +26,28 @@
 //                          it kp_clust_init_kernel (identity parents, no partner), kp_clust_flatten_kernel (label = root) and
 //                          kp_dist_nearest_kernel (the partner's three counts, recomputed).  No pair is stored.
 //
+//   kp_dist_tree_kernel    the same tiles and counts with a third epilogue (kp_spec.h, TREE; kp_tree.h): one round of Boruvka.  Every valid
+//                          pair whose rows carry different labels offers its packed key to both components -- reduced inside the
+//                          tile as the nearest keys are, then one 64-bit atomic minimum per row and tile.  Around it
+//                          kp_tree_round_kernel (no edge yet), kp_tree_hook_kernel (one union per component and round; the root
+//                          that moved keeps the edge), kp_clust_flatten_kernel (next round's labels) and, after the last round,
+//                          kp_tree_edge_kernel (the edges' three counts, recomputed).  No pair is stored.
+//
 // Bounds: a lane reads planes only for r < R and w < NW, stores cnt only for a < R and tj < nt, and a record only below the total
 // the count pass found (the fill recomputes the same flags, so it is the same total).
 #include <algorithm>
 #include <climits>
 #include <new>
+#include <vector>
 
 #include "kp_host.h"
 #include "kp_dist.h"
 #include "kp_clust.h"
+#include "kp_tree.h"
+
+#ifndef KP_TREE_SKIP
+#define KP_TREE_SKIP 1 /* a tile whose rows all carry one label returns before the chunk loop: it holds no outgoing edge */
+#endif
 
 struct kp_dist {
     int device = 0;
@@ -55,6 +68,14 @@ struct kp_dist {
     DevBuf<int32_t> d_label;              // [KP_CLUST_MAX_LEVELS][n_rows]
     DevBuf<unsigned long long> d_best;    // [n_rows] nearest keys
     DevBuf<kp_dist_nearest> d_nearest;    // [n_rows]
+    // minimum spanning forest (kp_dist_tree): allocated on its first call
+    DevBuf<int32_t> d_tree_parent;            // [n_rows]
+    DevBuf<int32_t> d_tree_label;             // [n_rows] the smallest row of every row's component, as of the last round
+    DevBuf<unsigned long long> d_tree_best;   // [n_rows] by label: the component's lightest outgoing edge of this round
+    DevBuf<unsigned long long> d_tree_slot;   // [n_rows] by the root an edge's union moved: the edge's key
+    DevBuf<kp_dist_pair> d_tree_rec;          // [n_rows] the slots as records
+    DevBuf<uint32_t> d_tree_new;              // [1] edges of the round
+    int32_t tree_rounds = 0;                  // rounds of the last kp_dist_tree, the empty one included
 };
 
 namespace {
@@ -280,6 +301,124 @@ __global__ __launch_bounds__(DIST_THREADS) void kp_dist_nearest_kernel(const uin
     }
 }
 
+// ---- minimum spanning forest (kp_spec.h, TREE; the arithmetic: kp_tree.h) -------------------------------------------------------------
+// a round begins: no component has an edge, the round has none
+__global__ __launch_bounds__(DIST_THREADS) void kp_tree_round_kernel(int32_t R, unsigned long long *__restrict__ cbest, uint32_t *__restrict__ n_new) {
+    for (int64_t r = (int64_t)blockIdx.x * DIST_THREADS + threadIdx.x; r < R; r += (int64_t)gridDim.x * DIST_THREADS) cbest[r] = KP_TREE_KEY_NONE;
+    if (blockIdx.x == 0 && threadIdx.x == 0) *n_new = 0u;
+}
+
+// The pair kernel's tiles and counts with a third epilogue.  A valid pair (a < b < R, compared >= min_compared) whose rows carry
+// different labels offers its packed key to label[a]'s and to label[b]'s component: the key is canonical, both sides send the same
+// value.  The reductions are those of the cluster kernel's nearest keys: row a's minimum over its sixteen tx by four xor-shuffles,
+// column b's over the wave's four ty and across the four waves through the free strips, then one 64-bit atomic minimum per row and
+// tile and one per column and tile.
+// KP_TREE_SKIP: the labels of the tile's 128 rows are compared with the first one's before any plane word is read; where none
+// differs the tile holds no outgoing edge and the whole block returns -- __syncthreads_or makes the branch uniform.
+// Bounds: label is read at rows < R; its values are roots, rows < R (kp_clust_flatten_kernel stored them), and index cbest.
+__global__ __launch_bounds__(DIST_THREADS) void kp_dist_tree_kernel(const uint64_t *__restrict__ planes, int32_t R, int64_t NW, int32_t nt, int32_t min_compared,
+                                                                    const int32_t *__restrict__ label, unsigned long long *__restrict__ cbest) {
+    __shared__ uint64_t s[2][KP_DIST_PLANES][CH][T];
+    int32_t ti, tj;
+    kp_dist_tile_of((int64_t)blockIdx.x, nt, &ti, &tj);
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+#if KP_TREE_SKIP
+    {
+        const int32_t first = label[(int64_t)ti * T];  // (a launched tile has a first row: ti * T < R)
+        int differs = 0;
+        if (tid < 2 * T) {
+            const int64_t r = (int64_t)(tid < T ? ti : tj) * T + (tid & (T - 1));
+            if (r < R) differs = label[r] != first;
+        }
+        if (!__syncthreads_or(differs)) return;
+    }
+#endif
+    int32_t cmp[RG][RG], dif[RG][RG], uns[RG][RG];
+    dist_tile_counts(planes, R, NW, ti, tj, s, cmp, dif, uns);
+    int32_t lb[RG];
+    uint64_t col_key[RG];
+#pragma unroll
+    for (int j = 0; j < RG; ++j) {
+        const int64_t b = (int64_t)tj * T + tx + 16 * j;
+        lb[j] = b < R ? label[b] : -1;
+        col_key[j] = KP_TREE_KEY_NONE;
+    }
+#pragma unroll
+    for (int i = 0; i < RG; ++i) {
+        const int64_t a = (int64_t)ti * T + ty + 16 * i;
+        const int32_t la = a < R ? label[a] : -1;
+        uint64_t row_key = KP_TREE_KEY_NONE;
+#pragma unroll
+        for (int j = 0; j < RG; ++j) {
+            const int64_t b = (int64_t)tj * T + tx + 16 * j;
+            if (a < b && b < R && cmp[i][j] >= min_compared && la != lb[j]) {
+                const uint64_t k = kp_tree_key(dif[i][j], (int32_t)a, (int32_t)b);
+                row_key = std::min(row_key, k);
+                col_key[j] = std::min(col_key[j], k);
+            }
+        }
+#pragma unroll
+        for (int o = 8; o >= 1; o >>= 1) row_key = std::min(row_key, (uint64_t)__shfl_xor((unsigned long long)row_key, o));
+        if (tx == 0 && a < R && row_key != KP_TREE_KEY_NONE) atomicMin(cbest + la, (unsigned long long)row_key);
+    }
+    uint64_t (*col_best)[T] = reinterpret_cast<uint64_t (*)[T]>(&s[0][0][0][0]);  // [wave][column of the tile]
+    const int wave = tid >> 6;
+#pragma unroll
+    for (int j = 0; j < RG; ++j) {
+        uint64_t k = col_key[j];
+        k = std::min(k, (uint64_t)__shfl_xor((unsigned long long)k, 16));
+        k = std::min(k, (uint64_t)__shfl_xor((unsigned long long)k, 32));
+        if ((tid & 63) < 16) col_best[wave][tx + 16 * j] = k;
+    }
+    __syncthreads();
+    if (tid < T) {
+        const uint64_t k = std::min(std::min(col_best[0][tid], col_best[1][tid]), std::min(col_best[2][tid], col_best[3][tid]));
+        const int64_t b = (int64_t)tj * T + tid;
+        if (b < R && k != KP_TREE_KEY_NONE) atomicMin(cbest + label[b], (unsigned long long)k);
+    }
+}
+
+// One lane per component that has an edge: the union of the edge's rows.  Under a strict total order the chosen edges close no
+// cycle; an edge chosen from both sides is united once -- the second union finds one root -- and is kept iff the union moved a
+// root, in that root's slot: a root moves at most once in its life, so no two lanes of any round share a slot.
+// Bounds: a and b come out of a key the tree kernel packed from rows < R; the moved root is a row < R.
+__global__ __launch_bounds__(DIST_THREADS) void kp_tree_hook_kernel(int32_t R, const int32_t *__restrict__ label, const unsigned long long *__restrict__ cbest,
+                                                                    int32_t *__restrict__ parent, unsigned long long *__restrict__ slot, uint32_t *__restrict__ n_new) {
+    for (int64_t r = (int64_t)blockIdx.x * DIST_THREADS + threadIdx.x; r < R; r += (int64_t)gridDim.x * DIST_THREADS) {
+        if (label[r] != (int32_t)r) continue;
+        const uint64_t key = cbest[r];
+        if (key == KP_TREE_KEY_NONE) continue;
+        const int32_t a = kp_tree_key_a(key), b = kp_tree_key_b(key);
+        if (a >= b || b >= R) continue;  // (no key the tree kernel packs)
+        const int32_t moved = kp_tree_unite(parent, a, b);
+        if (moved >= 0) {
+            slot[moved] = key;
+            atomicAdd(n_new, 1u);
+        }
+    }
+}
+
+// The slots as records: a row whose slot holds an edge gets the edge's rows and its three counts, recomputed from the planes; every
+// other row a record with a = -1.
+__global__ __launch_bounds__(DIST_THREADS) void kp_tree_edge_kernel(const uint64_t *__restrict__ planes, int32_t R, int64_t NW,
+                                                                    const unsigned long long *__restrict__ slot, kp_dist_pair *__restrict__ out) {
+    const size_t plane = (size_t)NW * (size_t)R;
+    for (int64_t r = (int64_t)blockIdx.x * DIST_THREADS + threadIdx.x; r < R; r += (int64_t)gridDim.x * DIST_THREADS) {
+        const uint64_t key = slot[r];
+        const int32_t a = kp_tree_key_a(key), b = kp_tree_key_b(key);
+        if (key == KP_TREE_KEY_NONE || a >= b || b >= R) {
+            kp_dist_pair_store(out + r, -1, -1, 0, 0, 0);
+            continue;
+        }
+        int32_t c = 0, d = 0, u = 0;
+        for (int64_t w = 0; w < NW; ++w) {
+            const uint64_t *at = planes + (size_t)w * (size_t)R;
+            kp_dist_word_counts(at[a], at[plane + a], at[2 * plane + a], at[3 * plane + a], at[b], at[plane + b], at[2 * plane + b], at[3 * plane + b], &c, &d, &u);
+        }
+        kp_dist_pair_store(out + r, a, b, c, d, u);
+    }
+}
+
 int dist_launch_pairs(kp_ctx *ctx, kp_dist *d, bool fill) {
     const int64_t tiles = kp_dist_tiles(d->nt);
     if (tiles <= 0) return KP_OK;
@@ -426,6 +565,76 @@ int kp_dist_clusters(kp_ctx *ctx, kp_dist *d, const int32_t *levels, int32_t n_l
     KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return KP_OK;
 }
+
+int kp_dist_tree(kp_ctx *ctx, kp_dist *d, int32_t min_compared, kp_dist_pair *edges, int64_t cap, int64_t *n_edges, int32_t *component) {
+    if (!ctx) return kp_fail(nullptr, KP_EINVAL, "null context");
+    if (!d || !n_edges) return kp_fail(ctx, KP_EINVAL, "null distance handle or edge count pointer");
+    *n_edges = 0;
+    if (d->device != ctx->device) return kp_fail(ctx, KP_EINVAL, "the distance handle belongs to another device");
+    if (!kp_tree_fits(d->n_blocks)) return kp_fail(ctx, KP_EINVAL, "a locus of 2^28 columns or more does not fit the tree's edge key (KP_TREE_MAX_COLUMNS)");
+    const int32_t R = d->n_rows;
+    if (R > 1 && cap < (int64_t)R - 1) return kp_fail(ctx, KP_EINVAL, "room for fewer edges than a tree of the rows may have (n_rows - 1)");
+    if (cap > 0 && !edges) return kp_fail(ctx, KP_EINVAL, "null edge table");
+    d->tree_rounds = 0;
+    if (R == 0) return KP_OK;
+    if (R == 1) {  // one row: its own tree, no edge, no launch
+        if (component) component[0] = 0;
+        return KP_OK;
+    }
+    const int64_t tiles = kp_dist_tiles(d->nt);
+    if (tiles * DIST_THREADS >= (1ll << 32)) return kp_fail(ctx, KP_EINVAL, "too many tiles for one grid (KP_DIST_MAX_ROWS)");  // (kp_dist_create refused it)
+    KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+    hipError_t e = d->d_tree_parent.reserve((size_t)R);
+    if (e == hipSuccess) e = d->d_tree_label.reserve((size_t)R);
+    if (e == hipSuccess) e = d->d_tree_best.reserve((size_t)R);
+    if (e == hipSuccess) e = d->d_tree_slot.reserve((size_t)R);
+    if (e == hipSuccess) e = d->d_tree_rec.reserve((size_t)R);
+    if (e == hipSuccess) e = d->d_tree_new.reserve(1);
+    if (e != hipSuccess) return kp_fail(ctx, e == hipErrorOutOfMemory ? KP_ENOMEM : KP_EHIP, std::string("tree tables: ") + hipGetErrorString(e));
+    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)R + DIST_THREADS - 1) / DIST_THREADS, 1 << 16));
+    // identity parents and empty slots; the first round's labels are the rows themselves
+    hipLaunchKernelGGL(kp_clust_init_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, R, 1, d->d_tree_parent.p, d->d_tree_slot.p);
+    hipLaunchKernelGGL(kp_clust_flatten_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, R, 1, d->d_tree_parent.p, d->d_tree_label.p);
+    KP_HIP_CHECK(ctx, hipGetLastError());
+    const int32_t bound = kp_tree_max_rounds(R);
+    uint32_t fresh = 1;
+    int64_t total = 0;
+    for (int32_t round = 0; round < bound && fresh != 0; ++round) {
+        hipLaunchKernelGGL(kp_tree_round_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, R, d->d_tree_best.p, d->d_tree_new.p);
+        hipLaunchKernelGGL(kp_dist_tree_kernel, dim3((unsigned)tiles), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, R, d->n_words, d->nt, min_compared,
+                           d->d_tree_label.p, d->d_tree_best.p);
+        hipLaunchKernelGGL(kp_tree_hook_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, R, d->d_tree_label.p, d->d_tree_best.p, d->d_tree_parent.p,
+                           d->d_tree_slot.p, d->d_tree_new.p);
+        hipLaunchKernelGGL(kp_clust_flatten_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, R, 1, d->d_tree_parent.p, d->d_tree_label.p);
+        KP_HIP_CHECK(ctx, hipGetLastError());
+        int rc;
+        if ((rc = fetch_all(ctx, ctx->stream, {{&fresh, d->d_tree_new.p, sizeof(uint32_t)}}))) return rc;
+        d->tree_rounds = round + 1;
+        total += fresh;
+    }
+    // the bound holds for every matrix (kp_tree_max_rounds); past it the loop does not go round again
+    if (fresh != 0) return kp_fail(ctx, KP_ESTATE, "the tree's rounds reached their bound with edges still arriving");
+    if (total > (int64_t)R - 1) return kp_fail(ctx, KP_ESTATE, "more tree edges than rows");
+    hipLaunchKernelGGL(kp_tree_edge_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, R, d->n_words, d->d_tree_slot.p, d->d_tree_rec.p);
+    KP_HIP_CHECK(ctx, hipGetLastError());
+    std::vector<kp_dist_pair> rec((size_t)R);
+    KP_HIP_CHECK(ctx, hipMemcpyAsync(rec.data(), d->d_tree_rec.p, (size_t)R * sizeof(kp_dist_pair), hipMemcpyDeviceToHost, ctx->stream));
+    if (component) KP_HIP_CHECK(ctx, hipMemcpyAsync(component, d->d_tree_label.p, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    // compact the slots and sort them by key (at most 2^18 records)
+    int64_t n = 0;
+    for (int32_t r = 0; r < R; ++r)
+        if (rec[(size_t)r].a >= 0) rec[(size_t)n++] = rec[(size_t)r];
+    if (n != total) return kp_fail(ctx, KP_ESTATE, "the tree's slots do not hold the edges its rounds counted");
+    std::sort(rec.begin(), rec.begin() + n, [](const kp_dist_pair &x, const kp_dist_pair &y) {
+        return kp_tree_key(x.differences, x.a, x.b) < kp_tree_key(y.differences, y.a, y.b);
+    });
+    std::copy(rec.begin(), rec.begin() + n, edges);
+    *n_edges = n;
+    return KP_OK;
+}
+
+int32_t kp_dist_tree_rounds(const kp_dist *d) { return d ? d->tree_rounds : 0; }
 
 void kp_dist_destroy(kp_dist *d) {
     if (!d) return;

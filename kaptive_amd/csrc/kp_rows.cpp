@@ -6,6 +6,7 @@
 // returned plus the per-assembly decisions the host finished column-wise (kaptive_amd/serotyping/batch.py).  Number
 // formatting is C's "%.2f" on the same doubles Python's "%.2f" gets (float32 identities / coverages widen exactly), so
 // the bytes are identical; tests compare them with the reference's golden rows.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -587,6 +588,101 @@ extern "C" int64_t kp_format_clusters(const char *locus_name, int32_t locus_name
             o.lit(".\t.\t.\t.");
         }
         o.put('\n');
+    }
+    return o.n;
+}
+
+// ---- Newick table (kp_spec.h, TREE) ---------------------------------------------------------------------------------------------------
+// A Newick label: bare when every byte is one of A-Za-z0-9_.- ; otherwise in single quotes with every ' doubled.
+static void put_newick_name(Out &o, const char *s, int64_t n) {
+    bool bare = true;
+    for (int64_t i = 0; i < n && bare; ++i) {
+        const unsigned char c = (unsigned char)s[i];
+        bare = (c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z') || (c >= '0' && c <= '9') || c == '_' || c == '.' || c == '-';
+    }
+    if (bare) { o.put(s, n); return; }
+    o.put('\'');
+    for (int64_t i = 0; i < n; ++i) {
+        if (s[i] == '\'') o.put('\'');
+        o.put(s[i]);
+    }
+    o.put('\'');
+}
+
+// One line per tree of one locus's forest, ascending in the component's label: every tree rooted at its smallest row, a node's
+// children ascending by (differences, row), written with a stack of its own -- a chain of 2^18 rows is a legal tree.
+extern "C" int64_t kp_format_newick(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
+                                    const int32_t *rows, const kp_dist_pair *edges, int64_t n_edges, const int32_t *component, char *out, int64_t cap) {
+    if (locus_name_len < 0 || (locus_name_len > 0 && !locus_name) || n_names < 0 || n_edges < 0 || cap < 0 || (cap > 0 && !out)) return KP_EINVAL;
+    if (n_names > 0 && (!name_off || !component)) return KP_EINVAL;
+    if (n_edges > 0 && !edges) return KP_EINVAL;
+    const int32_t R = n_names;
+    const auto name_of = [&](int32_t r) { return rows ? rows[r] : r; };
+    for (int32_t r = 0; r < R; ++r) {
+        const int32_t at = name_of(r);
+        if (at < 0 || at >= R || name_off[at + 1] < name_off[at] || (name_off[at + 1] > name_off[at] && !names)) return KP_EINVAL;
+    }
+    // the edges must be a forest over the rows, and component[] the smallest row of every row's tree
+    std::vector<int32_t> parent((size_t)R);
+    for (int32_t r = 0; r < R; ++r) parent[(size_t)r] = r;
+    std::vector<int64_t> first((size_t)R + 1, 0);
+    for (int64_t e = 0; e < n_edges; ++e) {
+        const kp_dist_pair &p = edges[e];
+        if (p.a < 0 || p.b >= R || p.a >= p.b) return KP_EINVAL;
+        if (!kp_clust_unite(parent.data(), p.a, p.b)) return KP_EINVAL;  // (closes a cycle)
+        ++first[(size_t)p.a + 1]; ++first[(size_t)p.b + 1];
+    }
+    std::vector<int32_t> size((size_t)R, 0);
+    for (int32_t r = 0; r < R; ++r) {
+        if (component[r] != kp_clust_find(parent.data(), r)) return KP_EINVAL;  // (the larger root went under the smaller: a root is its tree's smallest row)
+        ++size[(size_t)component[r]];
+    }
+    // neighbours of every row, ascending by (differences, row)
+    struct Nb { int32_t differences, row; };
+    for (int32_t r = 0; r < R; ++r) first[(size_t)r + 1] += first[(size_t)r];
+    std::vector<Nb> nb((size_t)(2 * n_edges));
+    {
+        std::vector<int64_t> at(first.begin(), first.end() - 1);
+        for (int64_t e = 0; e < n_edges; ++e) {
+            const kp_dist_pair &p = edges[e];
+            nb[(size_t)at[(size_t)p.a]++] = Nb{p.differences, p.b};
+            nb[(size_t)at[(size_t)p.b]++] = Nb{p.differences, p.a};
+        }
+    }
+    for (int32_t r = 0; r < R; ++r)
+        std::sort(nb.begin() + first[(size_t)r], nb.begin() + first[(size_t)r + 1],
+                  [](const Nb &x, const Nb &y) { return x.differences != y.differences ? x.differences < y.differences : x.row < y.row; });
+    Out o{out, cap};
+    struct Frame { int32_t row, from, length; int64_t next; bool open; };  // from: the row it was reached from; length: that edge's differences
+    std::vector<Frame> stack;
+    long long tree = 0;
+    for (int32_t root = 0; root < R; ++root) {
+        if (component[root] != root) continue;
+        if (locus_name_len > 0) o.put(locus_name, locus_name_len);
+        o.put('\t');
+        put_i(o, ++tree); o.put('\t');
+        put_i(o, size[(size_t)root]); o.put('\t');
+        stack.push_back(Frame{root, -1, 0, first[(size_t)root], false});
+        while (!stack.empty()) {
+            Frame &f = stack.back();
+            if (f.next < first[(size_t)f.row + 1] && nb[(size_t)f.next].row == f.from) ++f.next;  // (a forest: the way back is one neighbour)
+            if (f.next < first[(size_t)f.row + 1]) {
+                const Nb child = nb[(size_t)f.next++];
+                o.put(f.open ? ',' : '(');
+                f.open = true;
+                const int32_t here = f.row;
+                stack.push_back(Frame{child.row, here, child.differences, first[(size_t)child.row], false});  // (f is dead from here on)
+                continue;
+            }
+            if (f.open) o.put(')');
+            const int32_t at = name_of(f.row);
+            put_newick_name(o, names + name_off[at], name_off[at + 1] - name_off[at]);
+            const bool is_root = f.from < 0;
+            const int32_t length = f.length;
+            stack.pop_back();
+            if (!is_root) { o.put(':'); put_i(o, length); }
+        }
+        o.lit(";\n");
     }
     return o.n;
 }

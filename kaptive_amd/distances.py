@@ -5,8 +5,9 @@ locus, and how many bases apart they are.  ``LocusRows`` collects, batch after b
 the primary kept records of its best locus's genes, strung together in database order, padding flagged -- and, when the run is over,
 hands the rows of every locus to the device as one matrix (``_native.Distances``: kp_dist.hip compares them all against all).  Two
 tables come of a matrix: the listed pairs (``distances`` / ``tsv``) and, with no pair listed, every row's single-linkage cluster at a
-few thresholds and its nearest neighbour (``clusters`` / ``clusters_tsv``; include/kp_spec.h, CLUSTERS).  One device handle per locus
-serves both: it is kept until the rows change or ``close()``.
+few thresholds and its nearest neighbour (``clusters`` / ``clusters_tsv``; include/kp_spec.h, CLUSTERS), and the minimum spanning forest
+of the rows as an edge table and as Newick text (``tree`` / ``tree_tsv`` / ``newick_tsv``; include/kp_spec.h, TREE).  One device handle
+per locus serves them all: it is kept until the rows change or ``close()``.
 
 It spans batches and, on a multi-GPU run, processes: ``state()`` is a picklable payload of what was added, ``merge()`` absorbs one.
 """
@@ -38,7 +39,7 @@ class LocusRows:
     """The locus rows of a run, for one database.
 
     ``add(bt)`` takes a ``BatchTyping`` of an engine made with ``aligned=True``; ``distances(ctx)`` / ``tsv(ctx)`` / ``matrix(ctx,
-    locus)`` and ``clusters(ctx)`` / ``clusters_tsv(ctx)`` compare them on the device of ``ctx`` (a ``_native.Context``; no database
+    locus)``, ``clusters(ctx)`` / ``clusters_tsv(ctx)`` and ``tree(ctx)`` / ``tree_tsv(ctx)`` / ``newick_tsv(ctx)`` compare them on the device of ``ctx`` (a ``_native.Context``; no database
     needs to be resident in it).  Assemblies are numbered in the order they were added.  A locus's matrix is uploaded once, by the
     first of these calls that needs it; ``close()`` -- or another ``add`` / ``merge`` -- frees the handles."""
 
@@ -221,6 +222,46 @@ class LocusRows:
         for L in self.loci():
             idx, labels, near = self._locus_clusters(ctx, L, levels, min_compared)
             out.append(_native.format_clusters(self.db.loci.ids[L], [self.ids[i] for i in idx], labels, near))
+        return b"".join(out)
+
+    def _locus_tree(self, ctx, locus: int, min_compared):
+        """(assembly numbers [R], edges as rows of the matrix, component int32 [R]) of one locus."""
+        idx, mat = self.locus_matrix(locus)
+        if len(idx) < 2:  # one row: its own tree, no edge
+            return idx, np.zeros(0, _native.DIST_PAIR_DTYPE), np.zeros(len(idx), np.int32)
+        return (idx, *self._handle(ctx, locus).tree(min_compared))
+
+    def tree(self, ctx, min_compared: int = _native.DIST_MIN_COMPARED) -> np.ndarray:
+        """DIST_RECORD_DTYPE records ``(locus, a, b, compared, differences, unshared)`` of the edges of every locus's minimum spanning
+        forest (include/kp_spec.h, TREE): loci in database order, a and b assembly numbers, a < b, ascending by (differences, a, b)
+        within a locus."""
+        out = []
+        for L in self.loci():
+            idx, p, _ = self._locus_tree(ctx, L, min_compared)
+            rec = np.zeros(len(p), DIST_RECORD_DTYPE)
+            rec["locus"] = L
+            rec["a"], rec["b"] = idx[p["a"]], idx[p["b"]]
+            for f in ("compared", "differences", "unshared"):
+                rec[f] = p[f]
+            out.append(rec)
+        return np.concatenate(out) if out else np.zeros(0, DIST_RECORD_DTYPE)
+
+    def tree_tsv(self, ctx, min_compared: int = _native.DIST_MIN_COMPARED) -> bytes:
+        """The lines of the edge table (``--mst``; no header: ``_native.DISTANCES_HEADER``, the columns of the distance table),
+        formatted by the native library (kp_format_distances): loci in database order, edges in key order within a locus."""
+        out = []
+        for L in self.loci():
+            idx, p, _ = self._locus_tree(ctx, L, min_compared)
+            out.append(_native.format_distances(self.db.loci.ids[L], self.columns(L), [self.ids[i] for i in idx], p))
+        return b"".join(out)
+
+    def newick_tsv(self, ctx, min_compared: int = _native.DIST_MIN_COMPARED) -> bytes:
+        """The lines of the Newick table (``--newick``; no header: ``_native.newick_header()``), formatted by the native library
+        (kp_format_newick): loci in database order, a line per tree, ascending in the tree's first assembly."""
+        out = []
+        for L in self.loci():
+            idx, p, comp = self._locus_tree(ctx, L, min_compared)
+            out.append(_native.format_newick(self.db.loci.ids[L], [self.ids[i] for i in idx], p, comp))
         return b"".join(out)
 
     def matrix(self, ctx, locus: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:

@@ -60,9 +60,10 @@ class Serotyper:
         (``Engine(db, aligned=True)``); ``rescue``: it leaves the rescue records of the missing genes (``Engine(db, rescue=True,
         rescue_flank=...)``), and ``rescue_min_score`` is the score below which their table calls a gene ``absent`` (default
         ``_native.RESCUE_MIN_SCORE``); ``distances``: every batch this typer types also feeds ``locus_rows``, the run's
-        ``distances.LocusRows`` of this database (include/kp_spec.h, DISTANCES) -- it implies ``aligned``.  The one keyword feeds both
-        tables of the rows: the listed pairs (``locus_rows.distances`` / ``tsv``) and the clusters and nearest neighbours
-        (``locus_rows.clusters`` / ``clusters_tsv``; CLUSTERS)."""
+        ``distances.LocusRows`` of this database (include/kp_spec.h, DISTANCES) -- it implies ``aligned``.  The one keyword feeds every
+        table of the rows: the listed pairs (``locus_rows.distances`` / ``tsv``), the clusters and nearest neighbours
+        (``locus_rows.clusters`` / ``clusters_tsv``; CLUSTERS) and the minimum spanning trees (``locus_rows.tree`` / ``tree_tsv`` /
+        ``newick_tsv``; TREE)."""
         self._db = db
         self._variants = bool(variants)
         self._breakpoints = bool(breakpoints)
