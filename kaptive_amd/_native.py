@@ -772,6 +772,20 @@ def format_aligned(gene_names, asm_names, contig_names, asm_first_ctg, n_kept, k
     raise NativeError("kp_format_aligned: size kept changing")
 
 
+def _sized(name: str, room: int, call) -> bytes:
+    """The bytes of one of the pair formatters below: ``call(out, cap)`` formats into ``out`` and returns the room the table needs --
+    so a first buffer of ``room`` bytes is tried, and one of exactly the size asked for if that was too small."""
+    out = np.empty(max(4096, room), np.uint8)
+    for _ in range(2):
+        need = call(_p(out), C.c_int64(len(out)))
+        if need < 0:
+            raise ValueError(f"{name} failed ({need})")
+        if need <= len(out):
+            return out[:need].tobytes()
+        out = np.empty(int(need), np.uint8)
+    raise NativeError(f"{name}: size kept changing")
+
+
 def format_distances(locus_name: str, columns: int, names, pairs) -> bytes:
     """The lines of one locus's distance table (kp_format_distances; host only; no header: ``DISTANCES_HEADER``): one per record of
     ``pairs`` (DIST_PAIR_DTYPE), whose ``a`` and ``b`` index ``names``, the assemblies' names by row of the locus's matrix."""
@@ -780,16 +794,8 @@ def format_distances(locus_name: str, columns: int, names, pairs) -> bytes:
     locus = locus_name.encode("utf-8")
     h = lib()
     h.kp_format_distances.restype = C.c_int64
-    out = np.empty(max(4096, 96 * len(pairs)), np.uint8)
-    for _ in range(2):
-        need = h.kp_format_distances(C.c_char_p(locus), C.c_int32(len(locus)), C.c_int64(int(columns)), _p(nm_b), _p(nm_o), C.c_int32(len(nm_o) - 1),
-                                     _p(pairs), C.c_int64(len(pairs)), _p(out), C.c_int64(len(out)))
-        if need < 0:
-            raise ValueError(f"kp_format_distances failed ({need})")
-        if need <= len(out):
-            return out[:need].tobytes()
-        out = np.empty(int(need), np.uint8)
-    raise NativeError("kp_format_distances: size kept changing")
+    return _sized("kp_format_distances", 96 * len(pairs), lambda out, cap: h.kp_format_distances(
+        C.c_char_p(locus), C.c_int32(len(locus)), C.c_int64(int(columns)), _p(nm_b), _p(nm_o), C.c_int32(len(nm_o) - 1), _p(pairs), C.c_int64(len(pairs)), out, cap))  # fmt: skip
 
 
 def format_clusters(locus_name: str, names, labels, nearest, rows=None) -> bytes:
@@ -806,16 +812,9 @@ def format_clusters(locus_name: str, names, labels, nearest, rows=None) -> bytes
     locus = locus_name.encode("utf-8")
     h = lib()
     h.kp_format_clusters.restype = C.c_int64
-    out = np.empty(max(4096, 96 * R), np.uint8)
-    for _ in range(2):
-        need = h.kp_format_clusters(C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows),
-                                    C.c_int32(labels.shape[0]), _p(labels), _p(nearest), _p(out), C.c_int64(len(out)))
-        if need < 0:
-            raise ValueError(f"kp_format_clusters failed ({need})")
-        if need <= len(out):
-            return out[:need].tobytes()
-        out = np.empty(int(need), np.uint8)
-    raise NativeError("kp_format_clusters: size kept changing")
+    return _sized("kp_format_clusters", 96 * R, lambda out, cap: h.kp_format_clusters(
+        C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows), C.c_int32(labels.shape[0]), _p(labels),
+        _p(nearest), out, cap))  # fmt: skip
 
 
 def format_newick(locus_name: str, names, edges, component, rows=None) -> bytes:
@@ -832,16 +831,9 @@ def format_newick(locus_name: str, names, edges, component, rows=None) -> bytes:
     locus = locus_name.encode("utf-8")
     h = lib()
     h.kp_format_newick.restype = C.c_int64
-    out = np.empty(max(4096, 64 * R + len(nm_b) + 64), np.uint8)
-    for _ in range(2):
-        need = h.kp_format_newick(C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows),
-                                  _p(edges), C.c_int64(len(edges)), _p(component), _p(out), C.c_int64(len(out)))
-        if need < 0:
-            raise ValueError(f"kp_format_newick failed ({need})")
-        if need <= len(out):
-            return out[:need].tobytes()
-        out = np.empty(int(need), np.uint8)
-    raise NativeError("kp_format_newick: size kept changing")
+    return _sized("kp_format_newick", 64 * R + len(nm_b) + 64, lambda out, cap: h.kp_format_newick(
+        C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows), _p(edges), C.c_int64(len(edges)),
+        _p(component), out, cap))  # fmt: skip
 
 
 class JsonTables(C.Structure):  # kp_json_tables

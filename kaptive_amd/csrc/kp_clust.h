@@ -27,7 +27,7 @@ KP_HD int32_t kp_clust_first_level(const KpClustLevels &L, int32_t differences) 
 }
 
 // NEAREST KEY of a partner s at `differences`: a smaller key is a better partner -- fewer differences, then the smaller row.
-#define KP_CLUST_KEY_NONE 0xffffffffffffffffull /* no partner: loses to every key */
+#define KP_CLUST_KEY_NONE KP_DIST_KEY_NONE /* no partner: loses to every key */
 KP_HD uint64_t kp_clust_key(int32_t differences, int32_t s) { return ((uint64_t)(uint32_t)differences << 32) | (uint64_t)(uint32_t)s; }
 KP_HD int32_t kp_clust_key_row(uint64_t key) { return key == KP_CLUST_KEY_NONE ? -1 : (int32_t)(uint32_t)key; }
 KP_HD int32_t kp_clust_key_differences(uint64_t key) { return key == KP_CLUST_KEY_NONE ? 0 : (int32_t)(uint32_t)(key >> 32); }
@@ -82,17 +82,21 @@ KP_HD int32_t kp_clust_find(int32_t *parent, int32_t x) {
     }
 }
 
-// Joins the components of a and b: the larger root goes under the smaller one.  False when they were one component already.
-// The loop runs again only when the hook lost to another union -- another lane has made progress; nothing waits for a lane.
-KP_HD bool kp_clust_unite(int32_t *parent, int32_t a, int32_t b) {
+// Joins the components of a and b: the larger root goes under the smaller one and is returned; -1 when they were one component
+// already.  The loop runs again only when the hook lost to another union -- another lane has made progress; nothing waits for a
+// lane.  A root is moved at most once in its life -- a cell that has left its root state never returns to it --, so the returned
+// row is a slot no other union of the run is given (the tree's hook kernel keeps its edge there).
+KP_HD int32_t kp_clust_unite_root(int32_t *parent, int32_t a, int32_t b) {
     for (;;) {
         a = kp_clust_find(parent, a);
         b = kp_clust_find(parent, b);
-        if (a == b) return false;
+        if (a == b) return -1;
         const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        if (kp_clust_hook(parent + hi, hi, lo)) return true;
+        if (kp_clust_hook(parent + hi, hi, lo)) return hi;
     }
 }
+// False when a and b were one component already.
+KP_HD bool kp_clust_unite(int32_t *parent, int32_t a, int32_t b) { return kp_clust_unite_root(parent, a, b) >= 0; }
 
 // An edge of first level k into the parent arrays parent[K][R] of levels k .. K - 1.  Levels nest, and every edge walks its levels
 // upwards: where the two rows are one component at a level already, the edges that joined them there go on to join them at every

@@ -1,9 +1,10 @@
 // kp_dist.h -- pairwise distances between locus rows (kp_spec.h, DISTANCES), written once as plain functions: the padding mask of a
 // gene's last block, the bit planes of a block and of four blocks (one plane word: 64 columns), the three counts of one plane word
-// of a pair, the listing predicate, and the tile geometry the pair kernel (kp_dist.hip) and its host share.  No HIP header:
-// tests/native_harness compiles it with g++.
+// of a pair and of a whole pair (from planes; from two block rows), the key that loses every minimum, the listing predicate, and the
+// tile geometry the pair kernel (kp_dist.hip) and its host share.  No HIP header: tests/native_harness compiles it with g++.
 #pragma once
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "kp_seqs.h"  // KP_HD
@@ -71,6 +72,32 @@ KP_HD void kp_dist_word_counts(uint64_t la, uint64_t ha, uint64_t va, uint64_t p
     *differences += __builtin_popcountll(d);
     *unshared += __builtin_popcountll(u);
 }
+
+// The three counts of rows (a, b) of a matrix of R rows, from its plane-major planes -- planes[(p * NW + w) * R + r]: what a kernel
+// recounts for the one pair a row's key names.
+struct KpDistCounts { int32_t compared, differences, unshared; };
+KP_HD KpDistCounts kp_dist_plane_counts(const uint64_t *planes, int64_t R, int64_t NW, int64_t a, int64_t b) {
+    const size_t plane = (size_t)NW * (size_t)R;
+    KpDistCounts n{0, 0, 0};
+    for (int64_t w = 0; w < NW; ++w) {
+        const uint64_t *at = planes + (size_t)w * (size_t)R;
+        kp_dist_word_counts(at[a], at[plane + a], at[2 * plane + a], at[3 * plane + a], at[b], at[plane + b], at[2 * plane + b], at[3 * plane + b], &n.compared,
+                            &n.differences, &n.unshared);
+    }
+    return n;
+}
+// The same of two rows of nb blocks each, for the host restatements.
+inline KpDistCounts kp_dist_row_counts(const uint64_t *a, const uint64_t *b, int64_t nb) {
+    KpDistCounts n{0, 0, 0};
+    for (int64_t w = 0; w < kp_dist_words(nb); ++w) {
+        const KpDistWord x = kp_dist_word_planes(a, nb, w), y = kp_dist_word_planes(b, nb, w);
+        kp_dist_word_counts(x.lo, x.hi, x.valid, x.present, y.lo, y.hi, y.valid, y.present, &n.compared, &n.differences, &n.unshared);
+    }
+    return n;
+}
+
+// A packed 64-bit key (kp_clust.h: nearest partner; kp_tree.h: edge) that loses every minimum: no partner, no edge.
+#define KP_DIST_KEY_NONE 0xffffffffffffffffull
 
 // LISTED PAIRS
 KP_HD bool kp_dist_listed(int32_t compared, int32_t differences, int32_t max_diff, int32_t min_compared) {

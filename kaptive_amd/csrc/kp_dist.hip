@@ -33,6 +33,10 @@
 //                          that moved keeps the edge), kp_clust_flatten_kernel (next round's labels) and, after the last round,
 //                          kp_tree_edge_kernel (the edges' three counts, recomputed).  No pair is stored.
 //
+// A report over pairs is an epilogue and a formatter; the rest is written once: dist_tile_counts (the chunk loop), dist_row_min /
+// dist_col_min (a key's minimum per row and column of the tile), kp_dist_plane_counts (kp_dist.h: one pair recounted), and on the host
+// dist_enter (a call's first checks), dist_grid, DistReserve (all tables or the call's refusal) and dist_launch_tiles (the tile grid).
+//
 // Bounds: a lane reads planes only for r < R and w < NW, stores cnt only for a < R and tj < nt, and a record only below the total
 // the count pass found (the fill recomputes the same flags, so it is the same total).
 #include <algorithm>
@@ -55,27 +59,31 @@ struct kp_dist {
     int64_t n_blocks = 0, n_words = 0;
     int32_t nt = 0;  // tile rows
     DevBuf<uint64_t> d_planes;  // [KP_DIST_PLANES][n_words][n_rows]
-    DevBuf<uint32_t> d_cnt;     // [n_rows * nt]
-    DevBuf<int64_t> d_off;      // [n_rows * nt] first record of every entry
-    DevBuf<uint32_t> d_row_cnt; // [n_rows] listed pairs of every row
-    DevBuf<int64_t> d_row_off;  // [n_rows + 1] their scan
-    DevBuf<kp_dist_pair> d_rec;
-    bool counted = false;
-    int32_t max_diff = 0, min_compared = 0;
-    int64_t n_pairs = 0;
-    // clusters and nearest neighbours (kp_dist_clusters): allocated on its first call, at their largest size
-    DevBuf<int32_t> d_parent;             // [KP_CLUST_MAX_LEVELS][n_rows]
-    DevBuf<int32_t> d_label;              // [KP_CLUST_MAX_LEVELS][n_rows]
-    DevBuf<unsigned long long> d_best;    // [n_rows] nearest keys
-    DevBuf<kp_dist_nearest> d_nearest;    // [n_rows]
-    // minimum spanning forest (kp_dist_tree): allocated on its first call
-    DevBuf<int32_t> d_tree_parent;            // [n_rows]
-    DevBuf<int32_t> d_tree_label;             // [n_rows] the smallest row of every row's component, as of the last round
-    DevBuf<unsigned long long> d_tree_best;   // [n_rows] by label: the component's lightest outgoing edge of this round
-    DevBuf<unsigned long long> d_tree_slot;   // [n_rows] by the root an edge's union moved: the edge's key
-    DevBuf<kp_dist_pair> d_tree_rec;          // [n_rows] the slots as records
-    DevBuf<uint32_t> d_tree_new;              // [1] edges of the round
-    int32_t tree_rounds = 0;                  // rounds of the last kp_dist_tree, the empty one included
+    struct Listing {  // kp_dist_count / kp_dist_pairs: allocated with the handle, but for the records
+        DevBuf<uint32_t> cnt;      // [n_rows * nt]
+        DevBuf<int64_t> off;       // [n_rows * nt] first record of every entry
+        DevBuf<uint32_t> row_cnt;  // [n_rows] listed pairs of every row
+        DevBuf<int64_t> row_off;   // [n_rows + 1] their scan
+        DevBuf<kp_dist_pair> rec;
+        bool counted = false;
+        int32_t max_diff = 0, min_compared = 0;
+        int64_t n_pairs = 0;
+    } list;
+    struct Clusters {  // kp_dist_clusters: allocated on its first call, at their largest size
+        DevBuf<int32_t> parent;            // [KP_CLUST_MAX_LEVELS][n_rows]
+        DevBuf<int32_t> label;             // [KP_CLUST_MAX_LEVELS][n_rows]
+        DevBuf<unsigned long long> best;   // [n_rows] nearest keys
+        DevBuf<kp_dist_nearest> nearest;   // [n_rows]
+    } clust;
+    struct Tree {  // kp_dist_tree: allocated on its first call
+        DevBuf<int32_t> parent;            // [n_rows]
+        DevBuf<int32_t> label;             // [n_rows] the smallest row of every row's component, as of the last round
+        DevBuf<unsigned long long> best;   // [n_rows] by label: the component's lightest outgoing edge of this round
+        DevBuf<unsigned long long> slot;   // [n_rows] by the root an edge's union moved: the edge's key
+        DevBuf<kp_dist_pair> rec;          // [n_rows] the slots as records
+        DevBuf<uint32_t> fresh;            // [1] edges of the round
+        int32_t rounds = 0;                // rounds of the last kp_dist_tree, the empty one included
+    } tree;
 };
 
 namespace {
@@ -135,6 +143,34 @@ __device__ __forceinline__ void dist_tile_counts(const uint64_t *__restrict__ pl
         }
         __syncthreads();  // (the next chunk overwrites the strips)
     }
+}
+
+// A 64-bit key's minimum over the tile, for the epilogues that send one atomic minimum per row and per column of it.
+// Row a = ty + 16 i of the tile: its sixteen pairs of one j are the sixteen tx of ty's lanes in one wave, so the lane's minimum over j
+// goes through four xor-shuffles and every tx holds the row's.
+__device__ __forceinline__ uint64_t dist_row_min(uint64_t key) {
+#pragma unroll
+    for (int o = 8; o >= 1; o >>= 1) key = std::min(key, (uint64_t)__shfl_xor((unsigned long long)key, o));
+    return key;
+}
+// Column b = tx + 16 j of the tile is spread over all ty: col_key[j] is the lane's minimum over i; two xor-shuffles take it over the
+// four ty of its wave, then the four waves meet in LDS (the strips are free behind the last __syncthreads of the chunk loop), and
+// lane tid < T returns the minimum of column tid.  The other lanes return KP_DIST_KEY_NONE.
+// Bounds: LDS is written and read at [wave < 4][column < 64] of the strips' first 2 KiB.
+__device__ __forceinline__ uint64_t dist_col_min(const uint64_t (&col_key)[RG], uint64_t (&s)[2][KP_DIST_PLANES][CH][T]) {
+    const int tid = threadIdx.x, tx = tid & 15;
+    uint64_t (*col_best)[T] = reinterpret_cast<uint64_t (*)[T]>(&s[0][0][0][0]);  // [wave][column of the tile]
+    const int wave = tid >> 6;
+#pragma unroll
+    for (int j = 0; j < RG; ++j) {
+        uint64_t k = col_key[j];
+        k = std::min(k, (uint64_t)__shfl_xor((unsigned long long)k, 16));
+        k = std::min(k, (uint64_t)__shfl_xor((unsigned long long)k, 32));
+        if ((tid & 63) < 16) col_best[wave][tx + 16 * j] = k;
+    }
+    __syncthreads();
+    if (tid >= T) return KP_DIST_KEY_NONE;
+    return std::min(std::min(col_best[0][tid], col_best[1][tid]), std::min(col_best[2][tid], col_best[3][tid]));
 }
 
 template <bool FILL>
@@ -213,21 +249,18 @@ __global__ __launch_bounds__(DIST_THREADS) void kp_clust_init_kernel(int32_t R, 
     const int64_t n = (int64_t)R * K;
     for (int64_t e = (int64_t)blockIdx.x * DIST_THREADS + threadIdx.x; e < std::max<int64_t>(n, R); e += (int64_t)gridDim.x * DIST_THREADS) {
         if (e < n) parent[e] = (int32_t)(e % R);
-        if (e < R) best[e] = KP_CLUST_KEY_NONE;
+        if (e < R) best[e] = KP_DIST_KEY_NONE;
     }
 }
 
 // The pair kernel's tiles and counts with another epilogue.  A valid pair (a < b < R, compared >= min_compared)
 //   * is an edge from its first level on: it is united into parent[k][..] of those levels (kp_clust_edge; lock-free, no lane waits
 //     for another), and
-//   * offers b to a and a to b as nearest partner.  Row a's sixteen partners of one j are the sixteen tx of ty's lanes in one wave: the
-//     lane's minimum over j goes through four xor-shuffles, and tx 0 sends the row's minimum of this tile to best[a] -- one 64-bit
-//     atomic minimum per row and tile.  Column b's partners are spread over all ty: a lane's minimum over i, two xor-shuffles over
-//     the four ty of its wave, then the four waves through LDS (the strips are free behind the last __syncthreads of the chunk
-//     loop), and the first 64 lanes send one atomic minimum per column.  A diagonal tile holds the same rows on both sides; a < b keeps
-//     each pair once, and it still offers both ways.
+//   * offers b to a and a to b as nearest partner.  tx 0 sends row a's minimum of this tile (dist_row_min) to best[a], the first 64
+//     lanes column b's (dist_col_min) to best[b] -- one 64-bit atomic minimum per row and tile and one per column and tile.  A
+//     diagonal tile holds the same rows on both sides; a < b keeps each pair once, and it still offers both ways.
 // Bounds: parent is read and written at rows a, b < R of levels < K and at values read from it, which are row indices (the init
-// kernel stored r, a hook stores a root, halving a grandparent); best at a, b < R; col_best at [wave < 4][column < 64].
+// kernel stored r, a hook stores a root, halving a grandparent); best at a, b < R.
 __global__ __launch_bounds__(DIST_THREADS) void kp_dist_clust_kernel(const uint64_t *__restrict__ planes, int32_t R, int64_t NW, int32_t nt,
                                                                      KpClustLevels levels, int32_t min_compared, int32_t *__restrict__ parent,
                                                                      unsigned long long *__restrict__ best) {
@@ -240,11 +273,11 @@ __global__ __launch_bounds__(DIST_THREADS) void kp_dist_clust_kernel(const uint6
     const int32_t K = levels.n;
     uint64_t col_key[RG];
 #pragma unroll
-    for (int j = 0; j < RG; ++j) col_key[j] = KP_CLUST_KEY_NONE;
+    for (int j = 0; j < RG; ++j) col_key[j] = KP_DIST_KEY_NONE;
 #pragma unroll
     for (int i = 0; i < RG; ++i) {
         const int64_t a = (int64_t)ti * T + ty + 16 * i;
-        uint64_t row_key = KP_CLUST_KEY_NONE;
+        uint64_t row_key = KP_DIST_KEY_NONE;
 #pragma unroll
         for (int j = 0; j < RG; ++j) {
             const int64_t b = (int64_t)tj * T + tx + 16 * j;
@@ -254,25 +287,12 @@ __global__ __launch_bounds__(DIST_THREADS) void kp_dist_clust_kernel(const uint6
                 kp_clust_edge(parent, R, K, kp_clust_first_level(levels, dif[i][j]), (int32_t)a, (int32_t)b);
             }
         }
-#pragma unroll
-        for (int o = 8; o >= 1; o >>= 1) row_key = std::min(row_key, (uint64_t)__shfl_xor((unsigned long long)row_key, o));
-        if (tx == 0 && a < R && row_key != KP_CLUST_KEY_NONE) atomicMin(best + a, (unsigned long long)row_key);
+        row_key = dist_row_min(row_key);
+        if (tx == 0 && a < R && row_key != KP_DIST_KEY_NONE) atomicMin(best + a, (unsigned long long)row_key);
     }
-    uint64_t (*col_best)[T] = reinterpret_cast<uint64_t (*)[T]>(&s[0][0][0][0]);  // [wave][column of the tile]
-    const int wave = tid >> 6;
-#pragma unroll
-    for (int j = 0; j < RG; ++j) {
-        uint64_t k = col_key[j];
-        k = std::min(k, (uint64_t)__shfl_xor((unsigned long long)k, 16));
-        k = std::min(k, (uint64_t)__shfl_xor((unsigned long long)k, 32));
-        if ((tid & 63) < 16) col_best[wave][tx + 16 * j] = k;
-    }
-    __syncthreads();
-    if (tid < T) {
-        const uint64_t k = std::min(std::min(col_best[0][tid], col_best[1][tid]), std::min(col_best[2][tid], col_best[3][tid]));
-        const int64_t b = (int64_t)tj * T + tid;
-        if (b < R && k != KP_CLUST_KEY_NONE) atomicMin(best + b, (unsigned long long)k);
-    }
+    const uint64_t k = dist_col_min(col_key, s);
+    const int64_t b = (int64_t)tj * T + tid;
+    if (tid < T && b < R && k != KP_DIST_KEY_NONE) atomicMin(best + b, (unsigned long long)k);
 }
 
 // label[k][r] = the root of r at level k.  A launch of its own: the kernel boundary is what orders it behind every hook.
@@ -287,32 +307,25 @@ __global__ __launch_bounds__(DIST_THREADS) void kp_clust_flatten_kernel(int32_t 
 // The nearest record of every row: the partner of best[r] and the pair's three counts, recomputed from the planes.
 __global__ __launch_bounds__(DIST_THREADS) void kp_dist_nearest_kernel(const uint64_t *__restrict__ planes, int32_t R, int64_t NW,
                                                                        const unsigned long long *__restrict__ best, kp_dist_nearest *__restrict__ out) {
-    const size_t plane = (size_t)NW * (size_t)R;
     for (int64_t r = (int64_t)blockIdx.x * DIST_THREADS + threadIdx.x; r < R; r += (int64_t)gridDim.x * DIST_THREADS) {
         const int32_t partner = kp_clust_key_row(best[r]);
-        int32_t c = 0, d = 0, u = 0;
-        if (partner >= 0 && partner < R)
-            for (int64_t w = 0; w < NW; ++w) {
-                const uint64_t *at = planes + (size_t)w * (size_t)R;
-                kp_dist_word_counts(at[r], at[plane + r], at[2 * plane + r], at[3 * plane + r], at[partner], at[plane + partner], at[2 * plane + partner],
-                                    at[3 * plane + partner], &c, &d, &u);
-            }
-        kp_dist_nearest_store(out + r, partner >= 0 && partner < R ? partner : -1, c, d, u);
+        KpDistCounts n{0, 0, 0};
+        if (partner >= 0 && partner < R) n = kp_dist_plane_counts(planes, R, NW, r, partner);
+        kp_dist_nearest_store(out + r, partner >= 0 && partner < R ? partner : -1, n.compared, n.differences, n.unshared);
     }
 }
 
 // ---- minimum spanning forest (kp_spec.h, TREE; the arithmetic: kp_tree.h) -------------------------------------------------------------
 // a round begins: no component has an edge, the round has none
 __global__ __launch_bounds__(DIST_THREADS) void kp_tree_round_kernel(int32_t R, unsigned long long *__restrict__ cbest, uint32_t *__restrict__ n_new) {
-    for (int64_t r = (int64_t)blockIdx.x * DIST_THREADS + threadIdx.x; r < R; r += (int64_t)gridDim.x * DIST_THREADS) cbest[r] = KP_TREE_KEY_NONE;
+    for (int64_t r = (int64_t)blockIdx.x * DIST_THREADS + threadIdx.x; r < R; r += (int64_t)gridDim.x * DIST_THREADS) cbest[r] = KP_DIST_KEY_NONE;
     if (blockIdx.x == 0 && threadIdx.x == 0) *n_new = 0u;
 }
 
 // The pair kernel's tiles and counts with a third epilogue.  A valid pair (a < b < R, compared >= min_compared) whose rows carry
 // different labels offers its packed key to label[a]'s and to label[b]'s component: the key is canonical, both sides send the same
-// value.  The reductions are those of the cluster kernel's nearest keys: row a's minimum over its sixteen tx by four xor-shuffles,
-// column b's over the wave's four ty and across the four waves through the free strips, then one 64-bit atomic minimum per row and
-// tile and one per column and tile.
+// value.  The reductions are those of the cluster kernel's nearest keys (dist_row_min, dist_col_min), then one 64-bit atomic minimum
+// per row and tile and one per column and tile.
 // KP_TREE_SKIP: the labels of the tile's 128 rows are compared with the first one's before any plane word is read; where none
 // differs the tile holds no outgoing edge and the whole block returns -- __syncthreads_or makes the branch uniform.
 // Bounds: label is read at rows < R; its values are roots, rows < R (kp_clust_flatten_kernel stored them), and index cbest.
@@ -341,13 +354,13 @@ __global__ __launch_bounds__(DIST_THREADS) void kp_dist_tree_kernel(const uint64
     for (int j = 0; j < RG; ++j) {
         const int64_t b = (int64_t)tj * T + tx + 16 * j;
         lb[j] = b < R ? label[b] : -1;
-        col_key[j] = KP_TREE_KEY_NONE;
+        col_key[j] = KP_DIST_KEY_NONE;
     }
 #pragma unroll
     for (int i = 0; i < RG; ++i) {
         const int64_t a = (int64_t)ti * T + ty + 16 * i;
         const int32_t la = a < R ? label[a] : -1;
-        uint64_t row_key = KP_TREE_KEY_NONE;
+        uint64_t row_key = KP_DIST_KEY_NONE;
 #pragma unroll
         for (int j = 0; j < RG; ++j) {
             const int64_t b = (int64_t)tj * T + tx + 16 * j;
@@ -357,25 +370,12 @@ __global__ __launch_bounds__(DIST_THREADS) void kp_dist_tree_kernel(const uint64
                 col_key[j] = std::min(col_key[j], k);
             }
         }
-#pragma unroll
-        for (int o = 8; o >= 1; o >>= 1) row_key = std::min(row_key, (uint64_t)__shfl_xor((unsigned long long)row_key, o));
-        if (tx == 0 && a < R && row_key != KP_TREE_KEY_NONE) atomicMin(cbest + la, (unsigned long long)row_key);
+        row_key = dist_row_min(row_key);
+        if (tx == 0 && a < R && row_key != KP_DIST_KEY_NONE) atomicMin(cbest + la, (unsigned long long)row_key);
     }
-    uint64_t (*col_best)[T] = reinterpret_cast<uint64_t (*)[T]>(&s[0][0][0][0]);  // [wave][column of the tile]
-    const int wave = tid >> 6;
-#pragma unroll
-    for (int j = 0; j < RG; ++j) {
-        uint64_t k = col_key[j];
-        k = std::min(k, (uint64_t)__shfl_xor((unsigned long long)k, 16));
-        k = std::min(k, (uint64_t)__shfl_xor((unsigned long long)k, 32));
-        if ((tid & 63) < 16) col_best[wave][tx + 16 * j] = k;
-    }
-    __syncthreads();
-    if (tid < T) {
-        const uint64_t k = std::min(std::min(col_best[0][tid], col_best[1][tid]), std::min(col_best[2][tid], col_best[3][tid]));
-        const int64_t b = (int64_t)tj * T + tid;
-        if (b < R && k != KP_TREE_KEY_NONE) atomicMin(cbest + label[b], (unsigned long long)k);
-    }
+    const uint64_t k = dist_col_min(col_key, s);
+    const int64_t b = (int64_t)tj * T + tid;
+    if (tid < T && b < R && k != KP_DIST_KEY_NONE) atomicMin(cbest + label[b], (unsigned long long)k);
 }
 
 // One lane per component that has an edge: the union of the edge's rows.  Under a strict total order the chosen edges close no
@@ -387,10 +387,10 @@ __global__ __launch_bounds__(DIST_THREADS) void kp_tree_hook_kernel(int32_t R, c
     for (int64_t r = (int64_t)blockIdx.x * DIST_THREADS + threadIdx.x; r < R; r += (int64_t)gridDim.x * DIST_THREADS) {
         if (label[r] != (int32_t)r) continue;
         const uint64_t key = cbest[r];
-        if (key == KP_TREE_KEY_NONE) continue;
+        if (key == KP_DIST_KEY_NONE) continue;
         const int32_t a = kp_tree_key_a(key), b = kp_tree_key_b(key);
         if (a >= b || b >= R) continue;  // (no key the tree kernel packs)
-        const int32_t moved = kp_tree_unite(parent, a, b);
+        const int32_t moved = kp_clust_unite_root(parent, a, b);
         if (moved >= 0) {
             slot[moved] = key;
             atomicAdd(n_new, 1u);
@@ -402,33 +402,47 @@ __global__ __launch_bounds__(DIST_THREADS) void kp_tree_hook_kernel(int32_t R, c
 // other row a record with a = -1.
 __global__ __launch_bounds__(DIST_THREADS) void kp_tree_edge_kernel(const uint64_t *__restrict__ planes, int32_t R, int64_t NW,
                                                                     const unsigned long long *__restrict__ slot, kp_dist_pair *__restrict__ out) {
-    const size_t plane = (size_t)NW * (size_t)R;
     for (int64_t r = (int64_t)blockIdx.x * DIST_THREADS + threadIdx.x; r < R; r += (int64_t)gridDim.x * DIST_THREADS) {
         const uint64_t key = slot[r];
         const int32_t a = kp_tree_key_a(key), b = kp_tree_key_b(key);
-        if (key == KP_TREE_KEY_NONE || a >= b || b >= R) {
+        if (key == KP_DIST_KEY_NONE || a >= b || b >= R) {
             kp_dist_pair_store(out + r, -1, -1, 0, 0, 0);
             continue;
         }
-        int32_t c = 0, d = 0, u = 0;
-        for (int64_t w = 0; w < NW; ++w) {
-            const uint64_t *at = planes + (size_t)w * (size_t)R;
-            kp_dist_word_counts(at[a], at[plane + a], at[2 * plane + a], at[3 * plane + a], at[b], at[plane + b], at[2 * plane + b], at[3 * plane + b], &c, &d, &u);
-        }
-        kp_dist_pair_store(out + r, a, b, c, d, u);
+        const KpDistCounts n = kp_dist_plane_counts(planes, R, NW, a, b);
+        kp_dist_pair_store(out + r, a, b, n.compared, n.differences, n.unshared);
     }
 }
 
-int dist_launch_pairs(kp_ctx *ctx, kp_dist *d, bool fill) {
+// ---- what every entry point shares ------------------------------------------------------------------------------------------------
+// A call's first checks: the context, the pointers it cannot do without (`args`: the handle and what `nulls` names), the device.
+int dist_enter(kp_ctx *ctx, const kp_dist *d, bool args, const char *nulls) {
+    if (!ctx) return kp_fail(nullptr, KP_EINVAL, "null context");
+    if (!d || !args) return kp_fail(ctx, KP_EINVAL, nulls);
+    if (d->device != ctx->device) return kp_fail(ctx, KP_EINVAL, "the distance handle belongs to another device");
+    return KP_OK;
+}
+
+// blocks of a grid-stride kernel over n items, `per` of them to a block of the first round
+unsigned dist_grid(int64_t n, int per = DIST_THREADS, int64_t most = 1 << 16) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + per - 1) / per, most)); }
+
+// All of a call's tables or none: the first reserve that fails ends the chain; done() refuses under the call's label, KP_ENOMEM when out of memory.
+struct DistReserve {
+    hipError_t e = hipSuccess;
+    template <class U> DistReserve &operator()(DevBuf<U> &buf, size_t n) { if (e == hipSuccess) e = buf.reserve(n); return *this; }
+    int done(kp_ctx *ctx, const char *what) const {
+        return e == hipSuccess ? KP_OK : kp_fail(ctx, e == hipErrorOutOfMemory ? KP_ENOMEM : KP_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+    }
+};
+
+// A tile kernel -- its first parameters are planes, R, NW, nt -- over the tiles on or above the diagonal, one workgroup each.  The
+// one place that looks at their number: kp_dist_create admits no matrix whose tiles overflow a grid (DIST_MAX_NT above).
+template <class Kernel, class... Args>
+int dist_launch_tiles(kp_ctx *ctx, const kp_dist *d, Kernel kernel, Args... args) {
     const int64_t tiles = kp_dist_tiles(d->nt);
     if (tiles <= 0) return KP_OK;
-    if (tiles * DIST_THREADS >= (1ll << 32)) return kp_fail(ctx, KP_EINVAL, "too many tiles for one grid (KP_DIST_MAX_ROWS)");  // (kp_dist_create refused it)
-    if (fill)
-        hipLaunchKernelGGL(kp_dist_pair_kernel<true>, dim3((unsigned)tiles), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, d->n_rows, d->n_words, d->nt,
-                           d->max_diff, d->min_compared, d->d_cnt.p, d->d_off.p, d->d_rec.p, d->n_pairs);
-    else
-        hipLaunchKernelGGL(kp_dist_pair_kernel<false>, dim3((unsigned)tiles), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, d->n_rows, d->n_words, d->nt,
-                           d->max_diff, d->min_compared, d->d_cnt.p, d->d_off.p, (kp_dist_pair *)nullptr, (int64_t)0);
+    if (tiles * DIST_THREADS >= (1ll << 32)) return kp_fail(ctx, KP_EINVAL, "too many tiles for one grid (KP_DIST_MAX_ROWS)");
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, d->n_rows, d->n_words, d->nt, args...);
     KP_HIP_CHECK(ctx, hipGetLastError());
     return KP_OK;
 }
@@ -461,14 +475,11 @@ int kp_dist_create(kp_ctx *ctx, const uint64_t *blocks, int32_t n_rows, int64_t 
         DevBuf<uint64_t> d_blocks;  // only the planes stay
         int rc;
         if ((rc = upload(ctx, d_blocks, blocks, (size_t)n_rows * (size_t)n_blocks))) return rc;
-        hipError_t e = d->d_planes.reserve(KP_DIST_PLANES * n);
-        if (e == hipSuccess) e = d->d_cnt.reserve((size_t)n_rows * (size_t)d->nt);
-        if (e == hipSuccess) e = d->d_off.reserve((size_t)n_rows * (size_t)d->nt);
-        if (e == hipSuccess) e = d->d_row_cnt.reserve((size_t)n_rows);
-        if (e == hipSuccess) e = d->d_row_off.reserve((size_t)n_rows + 1);
-        if (e != hipSuccess) return kp_fail(ctx, e == hipErrorOutOfMemory ? KP_ENOMEM : KP_EHIP, std::string("distance planes: ") + hipGetErrorString(e));
-        const unsigned grid = (unsigned)std::min<int64_t>(((int64_t)n + DIST_THREADS - 1) / DIST_THREADS, 1 << 16);
-        hipLaunchKernelGGL(kp_dist_plane_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, d_blocks.p, n_rows, n_blocks, d->n_words, d->d_planes.p);
+        const size_t entries = (size_t)n_rows * (size_t)d->nt;
+        if ((rc = DistReserve()(d->d_planes, KP_DIST_PLANES * n)(d->list.cnt, entries)(d->list.off, entries)(d->list.row_cnt, (size_t)n_rows)(
+                      d->list.row_off, (size_t)n_rows + 1).done(ctx, "distance planes")))
+            return rc;
+        hipLaunchKernelGGL(kp_dist_plane_kernel, dim3(dist_grid((int64_t)n)), dim3(DIST_THREADS), 0, ctx->stream, d_blocks.p, n_rows, n_blocks, d->n_words, d->d_planes.p);
         KP_HIP_CHECK(ctx, hipGetLastError());
         KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // (d_blocks goes away here)
     }
@@ -477,89 +488,79 @@ int kp_dist_create(kp_ctx *ctx, const uint64_t *blocks, int32_t n_rows, int64_t 
 }
 
 int kp_dist_count(kp_ctx *ctx, kp_dist *d, int32_t max_diff, int32_t min_compared, int64_t *n_pairs) {
-    if (!ctx) return kp_fail(nullptr, KP_EINVAL, "null context");
-    if (!d || !n_pairs) return kp_fail(ctx, KP_EINVAL, "null distance handle or count pointer");
-    if (d->device != ctx->device) return kp_fail(ctx, KP_EINVAL, "the distance handle belongs to another device");
-    d->counted = false;
-    d->max_diff = max_diff; d->min_compared = min_compared; d->n_pairs = 0;
+    int rc;
+    if ((rc = dist_enter(ctx, d, n_pairs, "null distance handle or count pointer"))) return rc;
+    kp_dist::Listing &l = d->list;
+    l.counted = false;
+    l.max_diff = max_diff; l.min_compared = min_compared; l.n_pairs = 0;
     if (d->n_rows > 1) {
         KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
         const int64_t entries = (int64_t)d->n_rows * d->nt;
         // (the entries of tile columns left of the diagonal belong to no workgroup: they stay zero)
-        KP_HIP_CHECK(ctx, hipMemsetAsync(d->d_cnt.p, 0, (size_t)entries * sizeof(uint32_t), ctx->stream));
-        int rc;
-        if ((rc = dist_launch_pairs(ctx, d, false))) return rc;
-        const unsigned grid = (unsigned)std::min<int64_t>(((int64_t)d->n_rows + DIST_WAVES - 1) / DIST_WAVES, 4096);
-        hipLaunchKernelGGL(kp_dist_row_sum_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, d->d_cnt.p, d->n_rows, d->nt, d->d_row_cnt.p);
-        kp_launch_count_scan(d->d_row_cnt.p, d->n_rows, d->d_row_off.p, ctx->stream);
-        hipLaunchKernelGGL(kp_dist_row_scan_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, d->d_cnt.p, d->d_row_off.p, d->n_rows, d->nt, d->d_off.p);
+        KP_HIP_CHECK(ctx, hipMemsetAsync(l.cnt.p, 0, (size_t)entries * sizeof(uint32_t), ctx->stream));
+        if ((rc = dist_launch_tiles(ctx, d, kp_dist_pair_kernel<false>, max_diff, min_compared, l.cnt.p, l.off.p, (kp_dist_pair *)nullptr, (int64_t)0))) return rc;
+        const unsigned grid = dist_grid(d->n_rows, DIST_WAVES, 4096);
+        hipLaunchKernelGGL(kp_dist_row_sum_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, l.cnt.p, d->n_rows, d->nt, l.row_cnt.p);
+        kp_launch_count_scan(l.row_cnt.p, d->n_rows, l.row_off.p, ctx->stream);
+        hipLaunchKernelGGL(kp_dist_row_scan_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, l.cnt.p, l.row_off.p, d->n_rows, d->nt, l.off.p);
         KP_HIP_CHECK(ctx, hipGetLastError());
-        if ((rc = fetch_all(ctx, ctx->stream, {{&d->n_pairs, d->d_row_off.p + d->n_rows, sizeof(int64_t)}}))) return rc;
+        if ((rc = fetch_all(ctx, ctx->stream, {{&l.n_pairs, l.row_off.p + d->n_rows, sizeof(int64_t)}}))) return rc;
     }
-    d->counted = true;
-    *n_pairs = d->n_pairs;
+    l.counted = true;
+    *n_pairs = l.n_pairs;
     return KP_OK;
 }
 
 int kp_dist_pairs(kp_ctx *ctx, kp_dist *d, kp_dist_pair *out, int64_t cap) {
-    if (!ctx) return kp_fail(nullptr, KP_EINVAL, "null context");
-    if (!d) return kp_fail(ctx, KP_EINVAL, "null distance handle");
-    if (d->device != ctx->device) return kp_fail(ctx, KP_EINVAL, "the distance handle belongs to another device");
-    if (!d->counted) return kp_fail(ctx, KP_ESTATE, "kp_dist_count must come first");
-    if (cap < d->n_pairs || (d->n_pairs > 0 && !out)) return kp_fail(ctx, KP_EINVAL, "room for fewer pairs than kp_dist_count counted");
-    if (d->n_pairs == 0) return KP_OK;
+    int rc;
+    if ((rc = dist_enter(ctx, d, true, "null distance handle"))) return rc;
+    kp_dist::Listing &l = d->list;
+    if (!l.counted) return kp_fail(ctx, KP_ESTATE, "kp_dist_count must come first");
+    if (cap < l.n_pairs || (l.n_pairs > 0 && !out)) return kp_fail(ctx, KP_EINVAL, "room for fewer pairs than kp_dist_count counted");
+    if (l.n_pairs == 0) return KP_OK;
     KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    if ((size_t)d->n_pairs > d->d_rec.n) {
+    if ((size_t)l.n_pairs > l.rec.n) {
         // a longer listing than every one before takes a buffer of its own size.  Handle-local growth is not counted by
         // kp_device_allocations (kaptive_amd.h says so): that count shows whether a stream of batches has settled
         DevBuf<kp_dist_pair> fresh;
-        d->d_rec = DevBuf<kp_dist_pair>();
-        const hipError_t e = fresh.reserve((size_t)d->n_pairs);
-        if (e != hipSuccess) return kp_fail(ctx, e == hipErrorOutOfMemory ? KP_ENOMEM : KP_EHIP, std::string("distance records: ") + hipGetErrorString(e));
-        d->d_rec = std::move(fresh);
+        l.rec = DevBuf<kp_dist_pair>();
+        if ((rc = DistReserve()(fresh, (size_t)l.n_pairs).done(ctx, "distance records"))) return rc;
+        l.rec = std::move(fresh);
     }
-    int rc;
-    if ((rc = dist_launch_pairs(ctx, d, true))) return rc;
-    KP_HIP_CHECK(ctx, hipMemcpyAsync(out, d->d_rec.p, (size_t)d->n_pairs * sizeof(kp_dist_pair), hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = dist_launch_tiles(ctx, d, kp_dist_pair_kernel<true>, l.max_diff, l.min_compared, l.cnt.p, l.off.p, l.rec.p, l.n_pairs))) return rc;
+    KP_HIP_CHECK(ctx, hipMemcpyAsync(out, l.rec.p, (size_t)l.n_pairs * sizeof(kp_dist_pair), hipMemcpyDeviceToHost, ctx->stream));
     KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return KP_OK;
 }
 
 int kp_dist_clusters(kp_ctx *ctx, kp_dist *d, const int32_t *levels, int32_t n_levels, int32_t min_compared, int32_t *labels, kp_dist_nearest *nearest) {
-    if (!ctx) return kp_fail(nullptr, KP_EINVAL, "null context");
-    if (!d) return kp_fail(ctx, KP_EINVAL, "null distance handle");
-    if (d->device != ctx->device) return kp_fail(ctx, KP_EINVAL, "the distance handle belongs to another device");
+    int rc;
+    if ((rc = dist_enter(ctx, d, true, "null distance handle"))) return rc;
     if (n_levels < 0 || n_levels > KP_CLUST_MAX_LEVELS) return kp_fail(ctx, KP_EINVAL, "number of cluster levels outside 0 .. KP_CLUST_MAX_LEVELS");
     if (n_levels > 0 && !levels) return kp_fail(ctx, KP_EINVAL, "null cluster levels");
     if (!kp_clust_levels_valid(levels, n_levels)) return kp_fail(ctx, KP_EINVAL, "cluster levels must be non-negative and strictly ascending");
     if (n_levels > 0 && d->n_rows > 0 && !labels) return kp_fail(ctx, KP_EINVAL, "null label table");
     const int32_t R = d->n_rows, K = n_levels;
     if (R == 0 || (K == 0 && !nearest)) return KP_OK;
-    const int64_t tiles = kp_dist_tiles(d->nt);
-    if (tiles * DIST_THREADS >= (1ll << 32)) return kp_fail(ctx, KP_EINVAL, "too many tiles for one grid (KP_DIST_MAX_ROWS)");  // (kp_dist_create refused it)
     KpClustLevels lv{};
     for (int32_t k = 0; k < KP_CLUST_MAX_LEVELS; ++k) lv.t[k] = k < K ? levels[k] : INT32_MAX;
     lv.n = K;
     KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    hipError_t e = d->d_parent.reserve((size_t)KP_CLUST_MAX_LEVELS * (size_t)R);
-    if (e == hipSuccess) e = d->d_label.reserve((size_t)KP_CLUST_MAX_LEVELS * (size_t)R);
-    if (e == hipSuccess) e = d->d_best.reserve((size_t)R);
-    if (e == hipSuccess) e = d->d_nearest.reserve((size_t)R);
-    if (e != hipSuccess) return kp_fail(ctx, e == hipErrorOutOfMemory ? KP_ENOMEM : KP_EHIP, std::string("cluster tables: ") + hipGetErrorString(e));
-    const auto grid_of = [](int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + DIST_THREADS - 1) / DIST_THREADS, 1 << 16)); };
-    hipLaunchKernelGGL(kp_clust_init_kernel, dim3(grid_of((int64_t)R * std::max(K, 1))), dim3(DIST_THREADS), 0, ctx->stream, R, K, d->d_parent.p, d->d_best.p);
-    if (R > 1)  // (one row: no pair; label 0 and no neighbour come from the init kernel's tables)
-        hipLaunchKernelGGL(kp_dist_clust_kernel, dim3((unsigned)tiles), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, R, d->n_words, d->nt, lv, min_compared,
-                           d->d_parent.p, d->d_best.p);
+    kp_dist::Clusters &c = d->clust;
+    const size_t all = (size_t)KP_CLUST_MAX_LEVELS * (size_t)R;
+    if ((rc = DistReserve()(c.parent, all)(c.label, all)(c.best, (size_t)R)(c.nearest, (size_t)R).done(ctx, "cluster tables"))) return rc;
+    hipLaunchKernelGGL(kp_clust_init_kernel, dim3(dist_grid((int64_t)R * std::max(K, 1))), dim3(DIST_THREADS), 0, ctx->stream, R, K, c.parent.p, c.best.p);
+    // (one row: no tile kernel; label 0 and no neighbour come from the init kernel's tables)
+    if (R > 1 && (rc = dist_launch_tiles(ctx, d, kp_dist_clust_kernel, lv, min_compared, c.parent.p, c.best.p))) return rc;
     if (K > 0) {
-        hipLaunchKernelGGL(kp_clust_flatten_kernel, dim3(grid_of((int64_t)R * K)), dim3(DIST_THREADS), 0, ctx->stream, R, K, d->d_parent.p, d->d_label.p);
+        hipLaunchKernelGGL(kp_clust_flatten_kernel, dim3(dist_grid((int64_t)R * K)), dim3(DIST_THREADS), 0, ctx->stream, R, K, c.parent.p, c.label.p);
         KP_HIP_CHECK(ctx, hipGetLastError());
-        KP_HIP_CHECK(ctx, hipMemcpyAsync(labels, d->d_label.p, (size_t)K * (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        KP_HIP_CHECK(ctx, hipMemcpyAsync(labels, c.label.p, (size_t)K * (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     }
     if (nearest) {
-        hipLaunchKernelGGL(kp_dist_nearest_kernel, dim3(grid_of(R)), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, R, d->n_words, d->d_best.p, d->d_nearest.p);
+        hipLaunchKernelGGL(kp_dist_nearest_kernel, dim3(dist_grid(R)), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, R, d->n_words, c.best.p, c.nearest.p);
         KP_HIP_CHECK(ctx, hipGetLastError());
-        KP_HIP_CHECK(ctx, hipMemcpyAsync(nearest, d->d_nearest.p, (size_t)R * sizeof(kp_dist_nearest), hipMemcpyDeviceToHost, ctx->stream));
+        KP_HIP_CHECK(ctx, hipMemcpyAsync(nearest, c.nearest.p, (size_t)R * sizeof(kp_dist_nearest), hipMemcpyDeviceToHost, ctx->stream));
     }
     KP_HIP_CHECK(ctx, hipGetLastError());
     KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -567,59 +568,48 @@ int kp_dist_clusters(kp_ctx *ctx, kp_dist *d, const int32_t *levels, int32_t n_l
 }
 
 int kp_dist_tree(kp_ctx *ctx, kp_dist *d, int32_t min_compared, kp_dist_pair *edges, int64_t cap, int64_t *n_edges, int32_t *component) {
-    if (!ctx) return kp_fail(nullptr, KP_EINVAL, "null context");
-    if (!d || !n_edges) return kp_fail(ctx, KP_EINVAL, "null distance handle or edge count pointer");
-    *n_edges = 0;
-    if (d->device != ctx->device) return kp_fail(ctx, KP_EINVAL, "the distance handle belongs to another device");
+    if (ctx && d && n_edges) *n_edges = 0;  // (whatever refuses the call from here on)
+    int rc;
+    if ((rc = dist_enter(ctx, d, n_edges, "null distance handle or edge count pointer"))) return rc;
     if (!kp_tree_fits(d->n_blocks)) return kp_fail(ctx, KP_EINVAL, "a locus of 2^28 columns or more does not fit the tree's edge key (KP_TREE_MAX_COLUMNS)");
     const int32_t R = d->n_rows;
     if (R > 1 && cap < (int64_t)R - 1) return kp_fail(ctx, KP_EINVAL, "room for fewer edges than a tree of the rows may have (n_rows - 1)");
     if (cap > 0 && !edges) return kp_fail(ctx, KP_EINVAL, "null edge table");
-    d->tree_rounds = 0;
+    kp_dist::Tree &t = d->tree;
+    t.rounds = 0;
     if (R == 0) return KP_OK;
     if (R == 1) {  // one row: its own tree, no edge, no launch
         if (component) component[0] = 0;
         return KP_OK;
     }
-    const int64_t tiles = kp_dist_tiles(d->nt);
-    if (tiles * DIST_THREADS >= (1ll << 32)) return kp_fail(ctx, KP_EINVAL, "too many tiles for one grid (KP_DIST_MAX_ROWS)");  // (kp_dist_create refused it)
     KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    hipError_t e = d->d_tree_parent.reserve((size_t)R);
-    if (e == hipSuccess) e = d->d_tree_label.reserve((size_t)R);
-    if (e == hipSuccess) e = d->d_tree_best.reserve((size_t)R);
-    if (e == hipSuccess) e = d->d_tree_slot.reserve((size_t)R);
-    if (e == hipSuccess) e = d->d_tree_rec.reserve((size_t)R);
-    if (e == hipSuccess) e = d->d_tree_new.reserve(1);
-    if (e != hipSuccess) return kp_fail(ctx, e == hipErrorOutOfMemory ? KP_ENOMEM : KP_EHIP, std::string("tree tables: ") + hipGetErrorString(e));
-    const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)R + DIST_THREADS - 1) / DIST_THREADS, 1 << 16));
+    if ((rc = DistReserve()(t.parent, (size_t)R)(t.label, (size_t)R)(t.best, (size_t)R)(t.slot, (size_t)R)(t.rec, (size_t)R)(t.fresh, 1).done(ctx, "tree tables"))) return rc;
+    const unsigned grid = dist_grid(R);
     // identity parents and empty slots; the first round's labels are the rows themselves
-    hipLaunchKernelGGL(kp_clust_init_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, R, 1, d->d_tree_parent.p, d->d_tree_slot.p);
-    hipLaunchKernelGGL(kp_clust_flatten_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, R, 1, d->d_tree_parent.p, d->d_tree_label.p);
+    hipLaunchKernelGGL(kp_clust_init_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, R, 1, t.parent.p, t.slot.p);
+    hipLaunchKernelGGL(kp_clust_flatten_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, R, 1, t.parent.p, t.label.p);
     KP_HIP_CHECK(ctx, hipGetLastError());
     const int32_t bound = kp_tree_max_rounds(R);
     uint32_t fresh = 1;
     int64_t total = 0;
     for (int32_t round = 0; round < bound && fresh != 0; ++round) {
-        hipLaunchKernelGGL(kp_tree_round_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, R, d->d_tree_best.p, d->d_tree_new.p);
-        hipLaunchKernelGGL(kp_dist_tree_kernel, dim3((unsigned)tiles), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, R, d->n_words, d->nt, min_compared,
-                           d->d_tree_label.p, d->d_tree_best.p);
-        hipLaunchKernelGGL(kp_tree_hook_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, R, d->d_tree_label.p, d->d_tree_best.p, d->d_tree_parent.p,
-                           d->d_tree_slot.p, d->d_tree_new.p);
-        hipLaunchKernelGGL(kp_clust_flatten_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, R, 1, d->d_tree_parent.p, d->d_tree_label.p);
+        hipLaunchKernelGGL(kp_tree_round_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, R, t.best.p, t.fresh.p);
+        if ((rc = dist_launch_tiles(ctx, d, kp_dist_tree_kernel, min_compared, t.label.p, t.best.p))) return rc;
+        hipLaunchKernelGGL(kp_tree_hook_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, R, t.label.p, t.best.p, t.parent.p, t.slot.p, t.fresh.p);
+        hipLaunchKernelGGL(kp_clust_flatten_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, R, 1, t.parent.p, t.label.p);
         KP_HIP_CHECK(ctx, hipGetLastError());
-        int rc;
-        if ((rc = fetch_all(ctx, ctx->stream, {{&fresh, d->d_tree_new.p, sizeof(uint32_t)}}))) return rc;
-        d->tree_rounds = round + 1;
+        if ((rc = fetch_all(ctx, ctx->stream, {{&fresh, t.fresh.p, sizeof(uint32_t)}}))) return rc;
+        t.rounds = round + 1;
         total += fresh;
     }
     // the bound holds for every matrix (kp_tree_max_rounds); past it the loop does not go round again
     if (fresh != 0) return kp_fail(ctx, KP_ESTATE, "the tree's rounds reached their bound with edges still arriving");
     if (total > (int64_t)R - 1) return kp_fail(ctx, KP_ESTATE, "more tree edges than rows");
-    hipLaunchKernelGGL(kp_tree_edge_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, R, d->n_words, d->d_tree_slot.p, d->d_tree_rec.p);
+    hipLaunchKernelGGL(kp_tree_edge_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, R, d->n_words, t.slot.p, t.rec.p);
     KP_HIP_CHECK(ctx, hipGetLastError());
     std::vector<kp_dist_pair> rec((size_t)R);
-    KP_HIP_CHECK(ctx, hipMemcpyAsync(rec.data(), d->d_tree_rec.p, (size_t)R * sizeof(kp_dist_pair), hipMemcpyDeviceToHost, ctx->stream));
-    if (component) KP_HIP_CHECK(ctx, hipMemcpyAsync(component, d->d_tree_label.p, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    KP_HIP_CHECK(ctx, hipMemcpyAsync(rec.data(), t.rec.p, (size_t)R * sizeof(kp_dist_pair), hipMemcpyDeviceToHost, ctx->stream));
+    if (component) KP_HIP_CHECK(ctx, hipMemcpyAsync(component, t.label.p, (size_t)R * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     // compact the slots and sort them by key (at most 2^18 records)
     int64_t n = 0;
@@ -634,7 +624,7 @@ int kp_dist_tree(kp_ctx *ctx, kp_dist *d, int32_t min_compared, kp_dist_pair *ed
     return KP_OK;
 }
 
-int32_t kp_dist_tree_rounds(const kp_dist *d) { return d ? d->tree_rounds : 0; }
+int32_t kp_dist_tree_rounds(const kp_dist *d) { return d ? d->tree.rounds : 0; }
 
 void kp_dist_destroy(kp_dist *d) {
     if (!d) return;

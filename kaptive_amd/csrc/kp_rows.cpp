@@ -60,6 +60,28 @@ struct Out {
 inline bool alive(const kp_kept &k) { return (k.flags & KP_F_SPURIOUS) == 0; }
 template <class Off>  // (the name tables of the rows have 32-bit offsets, the others 64-bit ones)
 inline void put_name(Out &o, const char *names, const Off *off, int64_t i) { o.put(names + off[i], off[i + 1] - off[i]); }
+
+// ---- the tables over the rows of one locus's matrix (kp_spec.h, DISTANCES, CLUSTERS, TREE) ----
+// The names of the n rows, as the caller stacked them: row r is called names[name_off[at(r)] .. name_off[at(r) + 1]), at(r) = rows[r]
+// where a mapping is given.
+struct RowNames {
+    const char *names; const int64_t *name_off; int32_t n; const int32_t *rows;
+    int32_t at(int32_t r) const { return rows ? rows[r] : r; }
+    bool valid(int32_t r) const {  // r is a row and its name a run of the table (name_off is not null)
+        if (r < 0 || r >= n || at(r) < 0 || at(r) >= n) return false;
+        const int64_t *off = name_off + at(r);
+        return off[1] >= off[0] && (off[1] == off[0] || names);
+    }
+    bool valid() const {  // every row
+        bool ok = n >= 0 && (n == 0 || name_off);
+        for (int32_t r = 0; ok && r < n; ++r) ok = valid(r);
+        return ok;
+    }
+    void put(Out &o, int32_t r) const { put_name(o, names, name_off, at(r)); }
+};
+// the locus name and the output buffer of a call; an empty name may come as a null pointer
+inline bool locus_and_out_ok(const char *locus_name, int32_t len, const char *out, int64_t cap) { return len >= 0 && (len == 0 || locus_name) && cap >= 0 && (cap == 0 || out); }
+inline void put_locus(Out &o, const char *locus_name, int32_t len) { if (len > 0) o.put(locus_name, len); }
 // a record's gene is one of the database's and its contig one of the `nc` contigs of its assembly
 template <class Rec>
 inline bool gene_contig_ok(const Rec &r, int32_t n_genes, int64_t nc) { return r.gene >= 0 && r.gene < n_genes && r.contig >= 0 && r.contig < nc; }
@@ -535,19 +557,19 @@ extern "C" int64_t kp_format_rescue(const kp_allele_tables *t, int32_t n_asm, co
 }
 
 // ---- distance table (kp_spec.h, DISTANCES) ----------------------------------------------------------------------------------------
-// One line per listed pair of one locus; the rows of the matrix are named by the caller, in the order it stacked them.
+// One line per listed pair of one locus; the rows of the matrix are named by the caller, in the order it stacked them (no mapping).
 extern "C" int64_t kp_format_distances(const char *locus_name, int32_t locus_name_len, int64_t columns, const char *names, const int64_t *name_off,
                                        int32_t n_names, const kp_dist_pair *pairs, int64_t n_pairs, char *out, int64_t cap) {
-    if (locus_name_len < 0 || (locus_name_len > 0 && !locus_name) || columns < 0 || n_names < 0 || n_pairs < 0 || cap < 0 || (cap > 0 && !out)) return KP_EINVAL;
+    if (!locus_and_out_ok(locus_name, locus_name_len, out, cap) || columns < 0 || n_names < 0 || n_pairs < 0) return KP_EINVAL;
     if (n_pairs > 0 && (!pairs || !name_off || n_names == 0)) return KP_EINVAL;
+    const RowNames t{names, name_off, n_names, nullptr};
     Out o{out, cap};
     for (int64_t i = 0; i < n_pairs; ++i) {
         const kp_dist_pair &r = pairs[i];
-        if (r.a < 0 || r.a >= n_names || r.b < 0 || r.b >= n_names) return KP_EINVAL;
-        if (name_off[r.a + 1] < name_off[r.a] || name_off[r.b + 1] < name_off[r.b] || ((name_off[r.a + 1] > name_off[r.a] || name_off[r.b + 1] > name_off[r.b]) && !names)) return KP_EINVAL;
-        o.put(locus_name, locus_name_len); o.put('\t');
-        put_name(o, names, name_off, r.a); o.put('\t');
-        put_name(o, names, name_off, r.b); o.put('\t');
+        if (!t.valid(r.a) || !t.valid(r.b)) return KP_EINVAL;  // (only the rows a pair names are looked at)
+        put_locus(o, locus_name, locus_name_len); o.put('\t');
+        t.put(o, r.a); o.put('\t');
+        t.put(o, r.b); o.put('\t');
         put_i(o, columns); o.put('\t');
         put_i(o, r.compared); o.put('\t');
         put_i(o, r.differences); o.put('\t');
@@ -561,26 +583,22 @@ extern "C" int64_t kp_format_distances(const char *locus_name, int32_t locus_nam
 // One line per row of one locus's matrix, in row order: its cluster number at every level (kp_clust_numbers), then its nearest row.
 extern "C" int64_t kp_format_clusters(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
                                       const int32_t *rows, int32_t n_levels, const int32_t *labels, const kp_dist_nearest *nearest, char *out, int64_t cap) {
-    if (locus_name_len < 0 || (locus_name_len > 0 && !locus_name) || n_names < 0 || n_levels < 0 || n_levels > KP_CLUST_MAX_LEVELS || cap < 0 || (cap > 0 && !out)) return KP_EINVAL;
-    if (n_names > 0 && (!name_off || !nearest || (n_levels > 0 && !labels))) return KP_EINVAL;
-    const auto name_of = [&](int32_t r) { return rows ? rows[r] : r; };
-    for (int32_t r = 0; r < n_names; ++r) {
-        const int32_t at = name_of(r);
-        if (at < 0 || at >= n_names || name_off[at + 1] < name_off[at] || (name_off[at + 1] > name_off[at] && !names)) return KP_EINVAL;
+    const RowNames t{names, name_off, n_names, rows};
+    if (!locus_and_out_ok(locus_name, locus_name_len, out, cap) || !t.valid() || n_levels < 0 || n_levels > KP_CLUST_MAX_LEVELS) return KP_EINVAL;
+    if (n_names > 0 && (!nearest || (n_levels > 0 && !labels))) return KP_EINVAL;
+    for (int32_t r = 0; r < n_names; ++r)
         if (nearest[r].row < -1 || nearest[r].row >= n_names) return KP_EINVAL;
-    }
     std::vector<int32_t> number((size_t)n_levels * (size_t)n_names), rank((size_t)n_names);
     for (int32_t k = 0; k < n_levels; ++k)
         if (!kp_clust_numbers(labels + (size_t)k * (size_t)n_names, n_names, rank.data(), number.data() + (size_t)k * (size_t)n_names)) return KP_EINVAL;
     Out o{out, cap};
     for (int32_t r = 0; r < n_names; ++r) {
         const kp_dist_nearest &nr = nearest[r];
-        if (locus_name_len > 0) o.put(locus_name, locus_name_len);  // (an empty name may come as a null pointer)
-        o.put('\t');
-        put_name(o, names, name_off, name_of(r)); o.put('\t');
+        put_locus(o, locus_name, locus_name_len); o.put('\t');
+        t.put(o, r); o.put('\t');
         for (int32_t k = 0; k < n_levels; ++k) { put_i(o, number[(size_t)k * (size_t)n_names + (size_t)r]); o.put('\t'); }
         if (nr.row >= 0) {
-            put_name(o, names, name_off, name_of(nr.row)); o.put('\t');
+            t.put(o, nr.row); o.put('\t');
             put_i(o, nr.differences); o.put('\t');
             put_i(o, nr.compared); o.put('\t');
             put_i(o, nr.unshared);
@@ -613,15 +631,11 @@ static void put_newick_name(Out &o, const char *s, int64_t n) {
 // children ascending by (differences, row), written with a stack of its own -- a chain of 2^18 rows is a legal tree.
 extern "C" int64_t kp_format_newick(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
                                     const int32_t *rows, const kp_dist_pair *edges, int64_t n_edges, const int32_t *component, char *out, int64_t cap) {
-    if (locus_name_len < 0 || (locus_name_len > 0 && !locus_name) || n_names < 0 || n_edges < 0 || cap < 0 || (cap > 0 && !out)) return KP_EINVAL;
-    if (n_names > 0 && (!name_off || !component)) return KP_EINVAL;
+    const RowNames t{names, name_off, n_names, rows};
+    if (!locus_and_out_ok(locus_name, locus_name_len, out, cap) || !t.valid() || n_edges < 0) return KP_EINVAL;
+    if (n_names > 0 && !component) return KP_EINVAL;
     if (n_edges > 0 && !edges) return KP_EINVAL;
     const int32_t R = n_names;
-    const auto name_of = [&](int32_t r) { return rows ? rows[r] : r; };
-    for (int32_t r = 0; r < R; ++r) {
-        const int32_t at = name_of(r);
-        if (at < 0 || at >= R || name_off[at + 1] < name_off[at] || (name_off[at + 1] > name_off[at] && !names)) return KP_EINVAL;
-    }
     // the edges must be a forest over the rows, and component[] the smallest row of every row's tree
     std::vector<int32_t> parent((size_t)R);
     for (int32_t r = 0; r < R; ++r) parent[(size_t)r] = r;
@@ -658,8 +672,7 @@ extern "C" int64_t kp_format_newick(const char *locus_name, int32_t locus_name_l
     long long tree = 0;
     for (int32_t root = 0; root < R; ++root) {
         if (component[root] != root) continue;
-        if (locus_name_len > 0) o.put(locus_name, locus_name_len);
-        o.put('\t');
+        put_locus(o, locus_name, locus_name_len); o.put('\t');
         put_i(o, ++tree); o.put('\t');
         put_i(o, size[(size_t)root]); o.put('\t');
         stack.push_back(Frame{root, -1, 0, first[(size_t)root], false});
@@ -675,7 +688,7 @@ extern "C" int64_t kp_format_newick(const char *locus_name, int32_t locus_name_l
                 continue;
             }
             if (f.open) o.put(')');
-            const int32_t at = name_of(f.row);
+            const int32_t at = t.at(f.row);
             put_newick_name(o, names + name_off[at], name_off[at + 1] - name_off[at]);
             const bool is_root = f.from < 0;
             const int32_t length = f.length;

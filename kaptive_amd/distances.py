@@ -175,55 +175,6 @@ class LocusRows:
             return idx, np.zeros((len(_native.check_cluster_levels(levels)), len(idx)), np.int32), near
         return (idx, *self._handle(ctx, locus).clusters(levels, min_compared))
 
-    def distances(self, ctx, max_diff: "int | None" = _native.DIST_MAX_DIFF, min_compared: int = _native.DIST_MIN_COMPARED) -> np.ndarray:
-        """DIST_RECORD_DTYPE records ``(locus, a, b, compared, differences, unshared)`` of the listed pairs: loci in database order, one
-        ``Distances`` handle each; a and b number the assemblies in the order they were added, a < b, ascending within a locus."""
-        out = []
-        for L in self.loci():
-            idx, p = self._locus_pairs(ctx, L, max_diff, min_compared)
-            rec = np.zeros(len(p), DIST_RECORD_DTYPE)
-            rec["locus"] = L
-            rec["a"], rec["b"] = idx[p["a"]], idx[p["b"]]
-            for f in ("compared", "differences", "unshared"):
-                rec[f] = p[f]
-            out.append(rec)
-        return np.concatenate(out) if out else np.zeros(0, DIST_RECORD_DTYPE)
-
-    def tsv(self, ctx, max_diff: "int | None" = _native.DIST_MAX_DIFF, min_compared: int = _native.DIST_MIN_COMPARED) -> bytes:
-        """The lines of the distance table (``--distances``; no header: ``_native.DISTANCES_HEADER``), formatted by the native library
-        (kp_format_distances): loci in database order, pairs in input order with A before B."""
-        out = []
-        for L in self.loci():
-            idx, p = self._locus_pairs(ctx, L, max_diff, min_compared)
-            out.append(_native.format_distances(self.db.loci.ids[L], self.columns(L), [self.ids[i] for i in idx], p))
-        return b"".join(out)
-
-    def clusters(self, ctx, levels=_native.CLUSTER_LEVELS, min_compared: int = _native.DIST_MIN_COMPARED) -> np.ndarray:
-        """``clust_record_dtype(len(levels))`` records, one per assembly: loci in database order, assemblies in input order within a
-        locus; ``labels[k]`` is the smallest assembly number of the assembly's cluster at ``levels[k]``, ``nearest`` the number of
-        its nearest assembly (-1: none) with the pair's three counts."""
-        dt = clust_record_dtype(len(_native.check_cluster_levels(levels)))
-        out = []
-        for L in self.loci():
-            idx, labels, near = self._locus_clusters(ctx, L, levels, min_compared)
-            rec = np.zeros(len(idx), dt)
-            rec["locus"], rec["assembly"] = L, idx
-            rec["labels"] = idx[labels].T
-            rec["nearest"] = np.where(near["row"] >= 0, idx[np.maximum(near["row"], 0)], -1)
-            for f in ("compared", "differences", "unshared"):
-                rec[f] = near[f]
-            out.append(rec)
-        return np.concatenate(out) if out else np.zeros(0, dt)
-
-    def clusters_tsv(self, ctx, levels=_native.CLUSTER_LEVELS, min_compared: int = _native.DIST_MIN_COMPARED) -> bytes:
-        """The lines of the cluster table (``--clusters``; no header: ``_native.clusters_header(levels)``), formatted by the native
-        library (kp_format_clusters): loci in database order, a line per assembly in input order."""
-        out = []
-        for L in self.loci():
-            idx, labels, near = self._locus_clusters(ctx, L, levels, min_compared)
-            out.append(_native.format_clusters(self.db.loci.ids[L], [self.ids[i] for i in idx], labels, near))
-        return b"".join(out)
-
     def _locus_tree(self, ctx, locus: int, min_compared):
         """(assembly numbers [R], edges as rows of the matrix, component int32 [R]) of one locus."""
         idx, mat = self.locus_matrix(locus)
@@ -231,38 +182,82 @@ class LocusRows:
             return idx, np.zeros(0, _native.DIST_PAIR_DTYPE), np.zeros(len(idx), np.int32)
         return (idx, *self._handle(ctx, locus).tree(min_compared))
 
+    def _per_locus(self, table, empty):
+        """``table(L)`` of every locus that has a row, in database order, joined; ``empty`` where there is none."""
+        out = [table(L) for L in self.loci()]
+        return empty if not out else b"".join(out) if isinstance(empty, bytes) else np.concatenate(out)
+
+    @staticmethod
+    def _pair_records(locus: int, idx, p) -> np.ndarray:
+        """DIST_RECORD_DTYPE records of one locus's pair records ``p`` (rows of its matrix -> the assembly numbers ``idx``)."""
+        rec = np.zeros(len(p), DIST_RECORD_DTYPE)
+        rec["locus"] = locus
+        rec["a"], rec["b"] = idx[p["a"]], idx[p["b"]]
+        for f in ("compared", "differences", "unshared"):
+            rec[f] = p[f]
+        return rec
+
+    def _pair_lines(self, locus: int, idx, p) -> bytes:
+        return _native.format_distances(self.db.loci.ids[locus], self.columns(locus), [self.ids[i] for i in idx], p)
+
+    def distances(self, ctx, max_diff: "int | None" = _native.DIST_MAX_DIFF, min_compared: int = _native.DIST_MIN_COMPARED) -> np.ndarray:
+        """DIST_RECORD_DTYPE records ``(locus, a, b, compared, differences, unshared)`` of the listed pairs: loci in database order, one
+        ``Distances`` handle each; a and b number the assemblies in the order they were added, a < b, ascending within a locus."""
+        return self._per_locus(lambda L: self._pair_records(L, *self._locus_pairs(ctx, L, max_diff, min_compared)), np.zeros(0, DIST_RECORD_DTYPE))
+
+    def tsv(self, ctx, max_diff: "int | None" = _native.DIST_MAX_DIFF, min_compared: int = _native.DIST_MIN_COMPARED) -> bytes:
+        """The lines of the distance table (``--distances``; no header: ``_native.DISTANCES_HEADER``), formatted by the native library
+        (kp_format_distances): loci in database order, pairs in input order with A before B."""
+        return self._per_locus(lambda L: self._pair_lines(L, *self._locus_pairs(ctx, L, max_diff, min_compared)), b"")
+
+    def clusters(self, ctx, levels=_native.CLUSTER_LEVELS, min_compared: int = _native.DIST_MIN_COMPARED) -> np.ndarray:
+        """``clust_record_dtype(len(levels))`` records, one per assembly: loci in database order, assemblies in input order within a
+        locus; ``labels[k]`` is the smallest assembly number of the assembly's cluster at ``levels[k]``, ``nearest`` the number of
+        its nearest assembly (-1: none) with the pair's three counts."""
+        dt = clust_record_dtype(len(_native.check_cluster_levels(levels)))
+
+        def table(L):
+            idx, labels, near = self._locus_clusters(ctx, L, levels, min_compared)
+            rec = np.zeros(len(idx), dt)
+            rec["locus"], rec["assembly"] = L, idx
+            rec["labels"] = idx[labels].T
+            rec["nearest"] = np.where(near["row"] >= 0, idx[np.maximum(near["row"], 0)], -1)
+            for f in ("compared", "differences", "unshared"):
+                rec[f] = near[f]
+            return rec
+
+        return self._per_locus(table, np.zeros(0, dt))
+
+    def clusters_tsv(self, ctx, levels=_native.CLUSTER_LEVELS, min_compared: int = _native.DIST_MIN_COMPARED) -> bytes:
+        """The lines of the cluster table (``--clusters``; no header: ``_native.clusters_header(levels)``), formatted by the native
+        library (kp_format_clusters): loci in database order, a line per assembly in input order."""
+
+        def table(L):
+            idx, labels, near = self._locus_clusters(ctx, L, levels, min_compared)
+            return _native.format_clusters(self.db.loci.ids[L], [self.ids[i] for i in idx], labels, near)
+
+        return self._per_locus(table, b"")
+
     def tree(self, ctx, min_compared: int = _native.DIST_MIN_COMPARED) -> np.ndarray:
         """DIST_RECORD_DTYPE records ``(locus, a, b, compared, differences, unshared)`` of the edges of every locus's minimum spanning
         forest (include/kp_spec.h, TREE): loci in database order, a and b assembly numbers, a < b, ascending by (differences, a, b)
         within a locus."""
-        out = []
-        for L in self.loci():
-            idx, p, _ = self._locus_tree(ctx, L, min_compared)
-            rec = np.zeros(len(p), DIST_RECORD_DTYPE)
-            rec["locus"] = L
-            rec["a"], rec["b"] = idx[p["a"]], idx[p["b"]]
-            for f in ("compared", "differences", "unshared"):
-                rec[f] = p[f]
-            out.append(rec)
-        return np.concatenate(out) if out else np.zeros(0, DIST_RECORD_DTYPE)
+        return self._per_locus(lambda L: self._pair_records(L, *self._locus_tree(ctx, L, min_compared)[:2]), np.zeros(0, DIST_RECORD_DTYPE))
 
     def tree_tsv(self, ctx, min_compared: int = _native.DIST_MIN_COMPARED) -> bytes:
         """The lines of the edge table (``--mst``; no header: ``_native.DISTANCES_HEADER``, the columns of the distance table),
         formatted by the native library (kp_format_distances): loci in database order, edges in key order within a locus."""
-        out = []
-        for L in self.loci():
-            idx, p, _ = self._locus_tree(ctx, L, min_compared)
-            out.append(_native.format_distances(self.db.loci.ids[L], self.columns(L), [self.ids[i] for i in idx], p))
-        return b"".join(out)
+        return self._per_locus(lambda L: self._pair_lines(L, *self._locus_tree(ctx, L, min_compared)[:2]), b"")
 
     def newick_tsv(self, ctx, min_compared: int = _native.DIST_MIN_COMPARED) -> bytes:
         """The lines of the Newick table (``--newick``; no header: ``_native.newick_header()``), formatted by the native library
         (kp_format_newick): loci in database order, a line per tree, ascending in the tree's first assembly."""
-        out = []
-        for L in self.loci():
+
+        def table(L):
             idx, p, comp = self._locus_tree(ctx, L, min_compared)
-            out.append(_native.format_newick(self.db.loci.ids[L], [self.ids[i] for i in idx], p, comp))
-        return b"".join(out)
+            return _native.format_newick(self.db.loci.ids[L], [self.ids[i] for i in idx], p, comp)
+
+        return self._per_locus(table, b"")
 
     def matrix(self, ctx, locus: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(assembly numbers [R], differences int32 [R, R], compared int32 [R, R]) of one locus, dense and symmetric, for small R."""

@@ -67,30 +67,23 @@ int kpy_clust_matrix(const uint64_t *blocks, int32_t R, int64_t nb, const int32_
     std::vector<int32_t> parent((size_t)K * (size_t)R);
     for (size_t e = 0; e < parent.size(); ++e) parent[e] = (int32_t)(e % (size_t)R);
     std::vector<uint64_t> best((size_t)R, KP_CLUST_KEY_NONE);
-    const auto counts = [&](int32_t a, int32_t b, int32_t *c) {
-        c[0] = c[1] = c[2] = 0;
-        for (int64_t w = 0; w < kp_dist_words(nb); ++w) {
-            const KpDistWord x = kp_dist_word_planes(blocks + (size_t)a * nb, nb, w), y = kp_dist_word_planes(blocks + (size_t)b * nb, nb, w);
-            kp_dist_word_counts(x.lo, x.hi, x.valid, x.present, y.lo, y.hi, y.valid, y.present, &c[0], &c[1], &c[2]);
-        }
-    };
+    const auto counts = [&](int32_t a, int32_t b) { return kp_dist_row_counts(blocks + (size_t)a * nb, blocks + (size_t)b * nb, nb); };
     for (int32_t a = 0; a < R; ++a)
         for (int32_t b = a + 1; b < R; ++b) {
-            int32_t c[3];
-            counts(a, b, c);
-            if (c[0] < min_compared) continue;
-            if (kp_clust_key(c[1], b) < best[a]) best[a] = kp_clust_key(c[1], b);
-            if (kp_clust_key(c[1], a) < best[b]) best[b] = kp_clust_key(c[1], a);
-            kp_clust_edge(parent.data(), R, K, kp_clust_first_level(L, c[1]), a, b);
+            const KpDistCounts c = counts(a, b);
+            if (c.compared < min_compared) continue;
+            if (kp_clust_key(c.differences, b) < best[a]) best[a] = kp_clust_key(c.differences, b);
+            if (kp_clust_key(c.differences, a) < best[b]) best[b] = kp_clust_key(c.differences, a);
+            kp_clust_edge(parent.data(), R, K, kp_clust_first_level(L, c.differences), a, b);
         }
     for (int32_t k = 0; k < K; ++k)
         for (int32_t x = 0; x < R; ++x) labels[(size_t)k * R + x] = kp_clust_find(parent.data() + (size_t)k * R, x);
     for (int32_t r = 0; r < R; ++r) {
         const int32_t s = kp_clust_key_row(best[r]);
-        int32_t c[3] = {0, 0, 0};
-        if (s >= 0) counts(r, s, c);
-        if (s >= 0 && c[1] != kp_clust_key_differences(best[r])) return -1;
-        kp_dist_nearest_store(nearest + r, s, c[0], c[1], c[2]);
+        KpDistCounts c{0, 0, 0};
+        if (s >= 0) c = counts(r, s);
+        if (s >= 0 && c.differences != kp_clust_key_differences(best[r])) return -1;
+        kp_dist_nearest_store(nearest + r, s, c.compared, c.differences, c.unshared);
     }
     return 0;
 }

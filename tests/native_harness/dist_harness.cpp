@@ -33,11 +33,8 @@ void kpy_dist_word_planes(const uint64_t *row, int64_t nb, uint64_t *out) {
 }
 
 void kpy_dist_pair_counts(const uint64_t *a, const uint64_t *b, int64_t nb, int32_t *out3) {
-    out3[0] = out3[1] = out3[2] = 0;
-    for (int64_t w = 0; w < kp_dist_words(nb); ++w) {
-        const KpDistWord x = kp_dist_word_planes(a, nb, w), y = kp_dist_word_planes(b, nb, w);
-        kp_dist_word_counts(x.lo, x.hi, x.valid, x.present, y.lo, y.hi, y.valid, y.present, &out3[0], &out3[1], &out3[2]);
-    }
+    const KpDistCounts n = kp_dist_row_counts(a, b, nb);
+    out3[0] = n.compared; out3[1] = n.differences; out3[2] = n.unshared;
 }
 
 int kpy_dist_listed(int32_t compared, int32_t differences, int32_t max_diff, int32_t min_compared) {

@@ -27,7 +27,7 @@ int32_t kpy_tree_max_rounds(int64_t n_rows) { return kp_tree_max_rounds(n_rows);
 void kpy_tree_unite(int32_t R, const int32_t *edges, int64_t n, int32_t *moved, int32_t *label) {
     std::vector<int32_t> parent((size_t)R);
     for (int32_t r = 0; r < R; ++r) parent[(size_t)r] = r;
-    for (int64_t i = 0; i < n; ++i) moved[i] = kp_tree_unite(parent.data(), edges[2 * i], edges[2 * i + 1]);
+    for (int64_t i = 0; i < n; ++i) moved[i] = kp_clust_unite_root(parent.data(), edges[2 * i], edges[2 * i + 1]);
     for (int32_t r = 0; r < R; ++r) label[r] = kp_clust_find(parent.data(), r);
 }
 

@@ -8,30 +8,21 @@ the whole route on the 9-locus miniature database: ``Serotyper(db, distances=Tru
 from __future__ import annotations
 
 import ctypes as C
-from types import SimpleNamespace
 
 import numpy as np
 import pytest
 
 from kaptive_amd import _native
-from kaptive_amd.distances import LocusRows
-from kaptive_amd.pack import pack_sequences_flat
 from tests import clusters_util as CU
 from tests import distances_util as D
+from tests.distances_util import CH, ROWS, SPLIT, T, Run, _count_handles, _device_count, _write_inputs
 from tests.test_gpu_distances import BLOCKS as DIST_BLOCKS
-from tests.test_gpu_distances import CH, ROWS, SPLIT, T
 
 pytestmark = pytest.mark.gpu
 
 BLOCKS = (1, 4, 4 * CH, 4 * CH + 1, 8 * CH + 3)
 EINVAL = -1
 LEVEL_SETS = ((0,), CU.LEVELS, (SPLIT,), CU.EIGHT)
-
-
-def _device_count() -> int:
-    import torch
-
-    return torch.cuda.device_count()
 
 
 @pytest.fixture(scope="module")
@@ -219,66 +210,6 @@ def test_allocation_count_around_a_handle_that_clustered(ctx):
 
 
 # ---- 5. the whole route on the miniature database --------------------------------------------------------------------------------------------
-def _genome(name, rng, locus_seq):
-    from kaptive_amd.core.genome import GenomeAssembly
-    from kaptive_amd.core.seq import SeqRecord, Sequences
-    from kaptive_amd.synth import random_dna
-
-    contigs = [random_dna(rng, 30_000, 0.5), np.concatenate([random_dna(rng, 12_000, 0.5), locus_seq, random_dna(rng, 12_000, 0.5)]), random_dna(rng, 8_000, 0.5)]
-    return GenomeAssembly(name, Sequences.from_records([SeqRecord(f"{name}_{i}", c.tobytes()) for i, c in enumerate(contigs)]))
-
-
-def _flip(seq, at):
-    out = seq.copy()
-    out[at] = {65: 67, 67: 71, 71: 84, 84: 65}[int(seq[at])]
-    return out
-
-
-class Run:
-    """A dozen 90 kb assemblies over three loci, typed in two batches by ``Serotyper(db, distances=True)`` (the recipe of
-    tests/test_gpu_distances.py)."""
-
-    def __init__(self):
-        from kaptive_amd.serotyping.core import Serotyper
-        from kaptive_amd.synth import make_db, mutate
-        from tests.test_gpu_aligned import restate_batch
-
-        self.db = db = make_db("kpsc_k", seed=7, n_loci=9)
-        rng = np.random.default_rng(2024)
-        genomes, self.plan = [], {}
-        for L, kinds in ((0, ("exact", "exact", "snp", "lacking", "far")), (3, ("exact", "snp", "snp", "exact")), (6, ("exact", "lacking", "snp"))):
-            o, n = int(db.loci.offsets[L]), int(db.loci.lengths[L])
-            ref = np.asarray(db.loci.seqs[o : o + n], np.uint8).copy()
-            g0 = int(db.locus_gene_offsets[L])
-            for k, kind in enumerate(kinds):
-                g = g0 + 2 + k  # the gene this assembly's edit lies in
-                s, e = int(db.gene_intervals.starts[g]), int(db.gene_intervals.ends[g])
-                seq = {"exact": lambda: ref, "snp": lambda: _flip(ref, (s + e) // 2 + 1), "lacking": lambda: np.concatenate([ref[:s], ref[e:]]),
-                       "far": lambda: mutate(rng, ref, 0.01)}[kind]()  # fmt: skip
-                name = f"L{L}_{kind}_{k}"
-                self.plan[name] = (L, kind, g)
-                genomes.append(_genome(name, rng, seq))
-        order = rng.permutation(len(genomes))  # the loci interleaved: a locus's rows come from both batches
-        self.genomes = [genomes[i] for i in order]
-        self.ids = [g.id for g in self.genomes]
-        self.typer = Serotyper(db, distances=True)
-        eng = self.typer.engine
-        codes, off = pack_sequences_flat(db.genes)
-        self.want_rows, self.bts = LocusRows(db), []
-        for part in (self.genomes[:7], self.genomes[7:]):
-            packed = [g.packed() for g in part]
-            batch = eng.ctx.batch(packed)
-            bt = eng.type_batch(self.typer, batch, [g.id for g in part], part)
-            restated = restate_batch(bt, *batch.hits(), *batch.cigars(), codes, off, packed)
-            self.want_rows.add(SimpleNamespace(ids=bt.ids, sums=bt.sums, kept=bt.kept, best_locus=bt.best_locus, aligned=lambda r=restated: r))
-            self.bts.append((bt, restated))
-            batch.close()
-        self.tsv = b"".join(bt.tsv() for bt, _ in self.bts)
-
-    def close(self):
-        self.typer.engine.close()
-
-
 @pytest.fixture(scope="module")
 def run():
     r = Run()
@@ -313,27 +244,6 @@ def test_serotyper_over_two_batches(run):
 
     assert got.tsv(ctx) == _want_tsv(want)  # the other table of the same handles
     got.close()
-
-
-def _write_inputs(db, genomes, tmp_path):
-    paths = []
-    for g in genomes:
-        p = tmp_path / f"{g.id}.fasta"
-        p.write_bytes(g.contigs.to_fasta())
-        paths.append(str(p))
-    return str(db.save(tmp_path / "k.npz")), paths
-
-
-def _count_handles(monkeypatch):
-    made = []
-    init = _native.Distances.__init__
-
-    def counting(self, ctx, rows_matrix):
-        made.append(np.asarray(rows_matrix).shape)
-        init(self, ctx, rows_matrix)
-
-    monkeypatch.setattr(_native.Distances, "__init__", counting)
-    return made
 
 
 def test_command_line(run, tmp_path, monkeypatch):

@@ -16,9 +16,8 @@ import pytest
 from kaptive_amd import _native
 from tests import clusters_util as CU
 from tests import distances_util as D
+from tests.distances_util import CH, ROWS, SPLIT, T, Run, _count_handles, _device_count, _write_inputs
 from tests import tree_util as TU
-from tests.test_gpu_clusters import Run, _count_handles, _device_count, _write_inputs
-from tests.test_gpu_distances import CH, ROWS, SPLIT, T
 
 pytestmark = pytest.mark.gpu
 
