@@ -613,6 +613,40 @@ KP_API int32_t kp_dist_tree_rounds(const kp_dist *d);
 KP_API int64_t kp_format_newick(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
                                 const int32_t *rows /* [n_names] or null */, const kp_dist_pair *edges, int64_t n_edges, const int32_t *component,
                                 char *out, int64_t cap);
+/* Variable sites of a handle's rows (kp_spec.h, SITES): a reduction over the columns of the same planes, no pair looked at.
+ *   kp_dist_profile    : out [cap >= 16 * n_blocks]: the profile of every column of the matrix, padding columns included, as
+ *                        kp_site records with `column` filled, ascending.  Computed on the handle's first need of it and kept.
+ *   kp_dist_sites_count: counts the sites for `flags` (0 or KP_SITES_CORE) into *n_sites.
+ *   kp_dist_sites      : the sites of the last kp_dist_sites_count, ascending in column; KP_ESTATE without one, KP_EINVAL if cap
+ *                        is short.
+ *   kp_dist_site_rows  : blocks [n_rows][(n_sites + 15) / 16], row-major: the site rows of the last kp_dist_sites_count -- a matrix
+ *                        kp_dist_create takes; KP_ESTATE without a count, KP_EINVAL if cap_blocks is short.
+ * KP_EINVAL for a null context, handle or n_sites, a handle of another device, unknown flag bits, and a null table with room asked
+ * for.  n_rows of 0 and 1 are valid and give no site (one row still has a profile).  The calls leave the handle's listing state,
+ * its cluster tables and its tree tables alone, and those calls leave the profile and the last site count alone.  Their tables are
+ * the handle's own, allocated once, on the first of these calls -- but for the site rows, whose buffer is replaced when a table is
+ * larger than every one before it; like everything a handle does, kp_device_allocations does not count them. */
+KP_API int kp_dist_profile(kp_ctx *ctx, kp_dist *d, kp_site *out, int64_t cap);
+KP_API int kp_dist_sites_count(kp_ctx *ctx, kp_dist *d, int32_t flags, int64_t *n_sites);
+KP_API int kp_dist_sites(kp_ctx *ctx, kp_dist *d, kp_site *out, int64_t cap);
+KP_API int kp_dist_site_rows(kp_ctx *ctx, kp_dist *d, uint64_t *blocks, int64_t cap_blocks);
+/* The site table of one locus (host only): one tab-separated line per site, in the sites' order: Locus, Gene, Position (1-based in
+ * the gene: the coordinates of kp_format_variants' Gene position), Column (1-based in the locus's genes strung together, padding
+ * not counted: 1 .. Columns of kp_format_distances), Assemblies (n_rows), A, C, G, T, N, Gap, Alleles, Major (one of acgt),
+ * Informative (yes / no).  No header line.  gene_names / gene_name_off [n_genes + 1] and gene_len [n_genes]: the locus's genes in
+ * database order; gene i is named gene_names[genes[i]], or gene_names[i] when genes is null.  Return value as kp_format_variants
+ * has it; KP_EINVAL also for a site in a padding column or outside the matrix, counts that are negative or exceed n_rows, fewer
+ * than two non-zero bases, sites that do not ascend, and an entry of genes outside [0, n_genes). */
+KP_API int64_t kp_format_sites(const char *locus_name, int32_t locus_name_len, const char *gene_names, const int64_t *gene_name_off, int32_t n_genes,
+                               const int32_t *genes /* [n_genes] or null */, const int32_t *gene_len, int32_t n_rows, const kp_site *sites, int64_t n_sites,
+                               char *out, int64_t cap);
+/* The SNP alignment of one locus (host only): one tab-separated line per row, in row order: Locus, Assembly, Sites, Alignment -- exactly
+ * Sites characters of acgtn-.  No header line; no line at all when n_sites is 0.  names / name_off [n_names + 1]: the assemblies'
+ * names; row i of the matrix is named names[rows[i]], or names[i] when rows is null; blocks [n_names][(n_sites + 15) / 16] as
+ * kp_dist_site_rows filled them.  Return value as kp_format_variants has it; KP_EINVAL also for an entry of rows outside [0,
+ * n_names), a column that is flagged both N and GAP, and a column at or beyond n_sites that is not GAP-flagged. */
+KP_API int64_t kp_format_site_rows(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
+                                   const int32_t *rows /* [n_names] or null */, int64_t n_sites, const uint64_t *blocks, char *out, int64_t cap);
 
 /* ---- JSON lines of a whole batch (host only) ----------------------------------------------------------------------------------
  * Replaces orjson.dumps(SerotypingResult.to_dict(), OPT_SERIALIZE_NUMPY | OPT_APPEND_NEWLINE) per genome

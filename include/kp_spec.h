@@ -735,4 +735,38 @@ typedef struct kp_dist_nearest { int32_t row, compared, differences, unshared; }
  * OUT OF SCOPE.  Any linkage other than single; neighbour-joining or any tree with inferred inner nodes; names that are stable
  * across runs; any change to an existing report byte. */
 
+/* ---- SITES (optional; a reduction over the COLUMNS of a DISTANCES matrix: no pair, no pair record, no report byte depends on it) ------
+ * Where do the isolates of one locus differ, how many of them carry each base there, and what is the alignment of those columns
+ * alone?  The pair reports answer "how far apart"; this one answers "where".  It reads the same matrix of locus rows, column by
+ * column over all rows.
+ *
+ * PROFILE.  For a matrix of R locus rows of NB blocks (DISTANCES, LOCUS ROW, padding flagged) and a column c in [0, 16 NB): n[k] is
+ * the number of rows whose code at c is k, k = 0..3; n_n the number of rows that hold an N there; gap = R - n[0] - n[1] - n[2] -
+ * n[3] - n_n.
+ * SITE.  Column c is a site iff at least two of n[0..3] are non-zero.  With the flag KP_SITES_CORE it must also have n_n == 0 and
+ * gap == 0: every row holds a base.  A padding column is GAP in every row and is therefore never a site.  Sites ascend in column;
+ * the order depends on nothing else -- not on the slab shape, not on scheduling.
+ * RECORD.  kp_site: column, n[4], n_n -- 24 bytes, three 8-byte words, stored as a kp_dist_pair is.
+ * DERIVED.  ALLELES: the number of non-zero n[k].  MAJOR: the smallest k among those with the largest n[k].  INFORMATIVE: at least
+ * two k have n[k] >= 2.
+ * SITE ROWS.  Row r's site row holds its codes at the S listed sites, in order, in the ALIGNED ROWS packed form: (S + 15) / 16
+ * blocks, the columns at or beyond S GAP-flagged as LOCUS ROW padding is; S = 0 gives rows of 0 blocks.  A site matrix is therefore
+ * itself a valid DISTANCES matrix.
+ * PROPERTY.  Without KP_SITES_CORE every pair (a, b) has the same `differences` over the site matrix as over the full matrix: a
+ * column in which a and b hold different bases is a site.
+ * PURE FUNCTION of the matrix and the flag: the counts are integer sums, which no order of addition changes.
+ * KNOWN ANSWERS, on the three rows of the DISTANCES known answers: A "--acgt--nacg--------", B "--cgtn--acgt--------", C all GAP.
+ * The sites are the 0-based columns 2, 3, 4, 9, 10, 11; columns 5 and 8 hold one base and an N and are not sites.  Column 2 has n =
+ * (1, 1, 0, 0), n_n = 0, gap 1, ALLELES 2, MAJOR a (the tie goes to the first) and is not informative.  The site rows are "acgacg",
+ * "cgtcgt" and "------": blocks ffc0000000000924, ffc0000000000e79 and ffff000000000000.  With KP_SITES_CORE there are no sites;
+ * for rows A and B alone it gives the same six.
+ * OUT OF SCOPE.  Indel events as characters; sites between isolates of different loci; merging fragments of a split gene;
+ * ambiguity codes; any change to an existing report byte. */
+#define KP_SITES_CORE 1 /* flag: a site must hold a base in every row */
+typedef struct kp_site {
+    int32_t column; /* of the matrix, 0-based, padding columns counted */
+    int32_t n[4];   /* rows that hold a, c, g, t there */
+    int32_t n_n;    /* rows that hold an N there */
+} kp_site;
+
 #endif /* KP_SPEC_H */

@@ -114,6 +114,15 @@ def newick_header() -> bytes:
     return NEWICK_HEADER
 
 
+# Variable sites of the same rows (include/kp_spec.h, SITES)
+SITE_DTYPE = np.dtype([("column", "<i4"), ("n", "<i4", (4,)), ("n_n", "<i4")])  # kp_site: 24 bytes
+SITES_HEADER = b"Locus\tGene\tPosition\tColumn\tAssemblies\tA\tC\tG\tT\tN\tGap\tAlleles\tMajor\tInformative\n"  # the columns of kp_format_sites
+SNP_ALIGNMENT_HEADER = b"Locus\tAssembly\tSites\tAlignment\n"  # the columns of kp_format_site_rows
+SITES_CORE = 1  # KP_SITES_CORE of include/kp_spec.h: a site must hold a base in every row
+SITES_THREADS = 256  # KP_SITES_THREADS of kaptive_amd/csrc/kp_sites.h: lanes of a workgroup of the profile kernel (tests/test_sites_cpu.py compares the mirrors)
+SITES_LANE_ROWS = 15  # KP_SITES_LANE_ROWS: rows a lane adds into its four-plane bit-sliced counters
+SITES_SLAB = SITES_THREADS * SITES_LANE_ROWS  # KP_SITES_SLAB: rows of one workgroup
+
 JOIN_MAX_PIECES = 8  # KP_JOIN_MAX_PIECES
 JOIN_DTYPE = np.dtype(
     [("gs", "<i4"), ("contig", "<i4"), ("n_pieces", "<i4"), ("n_anchors", "<i4"), ("chain_score", "<i4"), ("width", "<i4"),
@@ -130,6 +139,7 @@ EXPORTS = (
     "kp_fasta_free", "kp_format_rows", "kp_format_json", "kp_format_fasta", "kp_protein_align_seeded", "kp_randstrobes", "kp_randstrobe_top_hits",
     "kp_dist_create", "kp_dist_count", "kp_dist_pairs", "kp_dist_destroy", "kp_format_distances", "kp_dist_clusters", "kp_format_clusters",
     "kp_dist_tree", "kp_dist_tree_rounds", "kp_format_newick",
+    "kp_dist_profile", "kp_dist_sites_count", "kp_dist_sites", "kp_dist_site_rows", "kp_format_sites", "kp_format_site_rows",
 )  # fmt: skip
 
 
@@ -834,6 +844,43 @@ def format_newick(locus_name: str, names, edges, component, rows=None) -> bytes:
     return _sized("kp_format_newick", 64 * R + len(nm_b) + 64, lambda out, cap: h.kp_format_newick(
         C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows), _p(edges), C.c_int64(len(edges)),
         _p(component), out, cap))  # fmt: skip
+
+
+def format_sites(locus_name: str, gene_names, gene_lengths, n_rows: int, sites, genes=None) -> bytes:
+    """The lines of one locus's site table (kp_format_sites; host only; no header: ``SITES_HEADER``): one per record of ``sites``
+    (SITE_DTYPE, as ``Distances.sites`` returns them).  ``gene_names`` and ``gene_lengths``: the locus's genes in database order --
+    or, with ``genes`` (int32, one entry per gene), gene i is named ``gene_names[genes[i]]``; ``n_rows`` the rows of the matrix."""
+    nm_b, nm_o = _blob64(gene_names)
+    lens = np.ascontiguousarray(gene_lengths, np.int32)
+    if len(nm_o) - 1 != len(lens) or (genes is not None and len(genes) != len(lens)):
+        raise ValueError("a name and a length for every gene")
+    genes = None if genes is None else np.ascontiguousarray(genes, np.int32)
+    sites = np.ascontiguousarray(sites, dtype=SITE_DTYPE)
+    locus = locus_name.encode("utf-8")
+    h = lib()
+    h.kp_format_sites.restype = C.c_int64
+    return _sized("kp_format_sites", 128 * len(sites), lambda out, cap: h.kp_format_sites(
+        C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(len(lens)), None if genes is None else _p(genes), _p(lens), C.c_int32(int(n_rows)),
+        _p(sites), C.c_int64(len(sites)), out, cap))  # fmt: skip
+
+
+def format_site_rows(locus_name: str, names, n_sites: int, blocks, rows=None) -> bytes:
+    """The lines of one locus's SNP alignment (kp_format_site_rows; host only; no header: ``SNP_ALIGNMENT_HEADER``): one per row of
+    the locus's matrix, none when ``n_sites`` is 0.  ``blocks`` uint64 [R, (n_sites + 15) // 16] as ``Distances.site_rows`` returns
+    them; ``names`` the R assemblies' names, by row -- or, with ``rows`` (int32 [R]), row i is ``names[rows[i]]``."""
+    nm_b, nm_o = _blob64(names)
+    R, S = len(nm_o) - 1, int(n_sites)
+    if S < 0 or (rows is not None and len(rows) != R):
+        raise ValueError("a name for every row and no negative number of sites")
+    blocks = np.ascontiguousarray(blocks, np.uint64).reshape(R, -1) if R else np.zeros((0, (S + 15) // 16), np.uint64)
+    if blocks.shape[1] != (S + 15) // 16:
+        raise ValueError("site rows of (n_sites + 15) // 16 blocks for every row")
+    rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+    locus = locus_name.encode("utf-8")
+    h = lib()
+    h.kp_format_site_rows.restype = C.c_int64
+    return _sized("kp_format_site_rows", R * (S + 64) + len(nm_b), lambda out, cap: h.kp_format_site_rows(
+        C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows), C.c_int64(S), _p(blocks), out, cap))  # fmt: skip
 
 
 class JsonTables(C.Structure):  # kp_json_tables
@@ -1546,6 +1593,38 @@ class Distances:
         h = lib()
         h.kp_dist_tree_rounds.restype = C.c_int32
         return int(h.kp_dist_tree_rounds(self._h))
+
+
+    def profile(self) -> np.ndarray:
+        """SITE_DTYPE records of all ``16 * n_blocks`` columns of the matrix, padding columns included, ascending (kp_dist_profile;
+        include/kp_spec.h, SITES): how many rows hold a, c, g, t and N at the column.  Computed once per handle."""
+        out = np.zeros(16 * self.n_blocks if self.n_rows else 0, SITE_DTYPE)
+        self.ctx._check(lib().kp_dist_profile(self.ctx._h, self._h, _p(out) if len(out) else None, C.c_int64(len(out))), "kp_dist_profile")
+        return out
+
+    def sites_count(self, core: bool = False) -> int:
+        """How many sites ``sites`` would list (kp_dist_sites_count)."""
+        n = C.c_int64(0)
+        self.ctx._check(lib().kp_dist_sites_count(self.ctx._h, self._h, C.c_int32(SITES_CORE if core else 0), C.byref(n)), "kp_dist_sites_count")
+        self._n_sites = n.value  # (``site_rows`` sizes its table by it)
+        return n.value
+
+    def sites(self, core: bool = False) -> np.ndarray:
+        """SITE_DTYPE records of the columns at which at least two bases occur among the rows, ascending in column (kp_dist_sites);
+        with ``core`` only those at which every row holds a base.  No pair is looked at for it; the listing state, the cluster
+        tables and the tree tables are left alone."""
+        out = np.zeros(self.sites_count(core), SITE_DTYPE)
+        self.ctx._check(lib().kp_dist_sites(self.ctx._h, self._h, _p(out) if len(out) else None, C.c_int64(len(out))), "kp_dist_sites")
+        return out
+
+    def site_rows(self) -> np.ndarray:
+        """uint64 [n_rows, (S + 15) // 16]: every row's codes at the S sites of the last ``sites`` / ``sites_count``, in the packed
+        form of the rows themselves, the columns at or beyond S GAP-flagged (kp_dist_site_rows) -- a matrix ``Distances`` takes.
+        Without a count the library refuses the call."""
+        S = getattr(self, "_n_sites", None)
+        out = np.zeros((self.n_rows, ((S or 0) + 15) // 16), np.uint64)
+        self.ctx._check(lib().kp_dist_site_rows(self.ctx._h, self._h, _p(out) if out.size else None, C.c_int64(out.size)), "kp_dist_site_rows")
+        return out
 
 
 RANDSTROBE_DTYPE = np.dtype([("hash", "<u8"), ("seq_idx", "<u4"), ("pos1", "<u4"), ("pos2", "<u4")])

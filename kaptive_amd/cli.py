@@ -154,6 +154,14 @@ def _add_outputs(p: argparse.ArgumentParser, tsv_flags, include_json: bool) -> N
                             "write its edges as a TSV table with the columns of --distances to a file; no pair is listed for it")
         g.add_argument("--newick", metavar="FILE", default=argparse.SUPPRESS,
                        help="The same trees as Newick text, one line per tree, as a TSV table to a file")
+        g.add_argument("--sites", metavar="FILE", default=argparse.SUPPRESS,
+                       help="List the gene positions at which the assemblies that carry the same locus hold different bases, with the "
+                            "number of assemblies that carry each base there, as a TSV table to a file; no pair is looked at for it")
+        g.add_argument("--snp-alignment", metavar="FILE", default=argparse.SUPPRESS,
+                       help="Write every assembly's bases at those positions, one row of exactly as many columns as its locus has "
+                            "sites, as a TSV table to a file")
+        g.add_argument("--core-sites", action="store_true", default=argparse.SUPPRESS,
+                       help="With --sites or --snp-alignment: only positions at which every assembly of the locus holds a base")
     g.add_argument("--pha4ge", metavar="FILE", nargs="?", const="kaptive_results.pha4ge", type=Path,
                    help="Write PHA4GE-compliant serotyping report to a TSV file (default: %(const)s)")
 
@@ -178,6 +186,8 @@ class _Parser(argparse.ArgumentParser):
                     self.error(f"--{flag.replace('_', '-')} requires " + " or ".join(f"--{b} FILE" for b in beside))
                 if not 0 <= getattr(ns, flag) <= 2**31 - 1:
                     self.error(f"--{flag.replace('_', '-')} is out of range")
+        if getattr(ns, "core_sites", False) and not (getattr(ns, "sites", None) or getattr(ns, "snp_alignment", None)):
+            self.error("--core-sites requires --sites FILE or --snp-alignment FILE")
         if getattr(ns, "cluster_levels", None) is not None:
             if not getattr(ns, "clusters", None):
                 self.error("--cluster-levels requires --clusters FILE")
@@ -658,11 +668,11 @@ def hits_to_paf(engine, genomes, hits, hit_off, ops, cigar_off, cs=None, cs_off=
 
 
 LOCUS_ROWS_KEY = "locus_rows"  # a chunk's outputs: the ``LocusRows.state()`` of its assemblies (PAIR_TABLES); never written to a file
-PAIR_TABLES = ("distances", "clusters", "mst", "newick")  # the flags whose tables are made of the run's locus rows
+PAIR_TABLES = ("distances", "clusters", "mst", "newick", "sites", "snp_alignment")  # the flags whose tables are made of the run's locus rows
 
 
 class _RunDistances:
-    """``--distances``, ``--clusters``, ``--mst`` and ``--newick``: the locus rows of the whole run, collected once for all of them,
+    """``--distances``, ``--clusters``, ``--mst``, ``--newick``, ``--sites`` and ``--snp-alignment``: the locus rows of the whole run, collected once for all of them,
     merged chunk by chunk in input order -- one ``LocusRows`` per database -- and, after the last chunk, compared on a device and
     written: one table each, or with ``--db`` one per database (``per_database_path``).  All tables of a locus come from one device
     handle."""
@@ -672,6 +682,9 @@ class _RunDistances:
         self.clusters_path = getattr(args, "clusters", None)
         self.mst_path = getattr(args, "mst", None)
         self.newick_path = getattr(args, "newick", None)
+        self.sites_path = getattr(args, "sites", None)
+        self.snp_alignment_path = getattr(args, "snp_alignment", None)
+        self.core_sites = bool(getattr(args, "core_sites", False))
         self.levels = getattr(args, "cluster_levels", None)
         self.max_diff = getattr(args, "max_distance", None)
         self.min_compared = getattr(args, "min_compared", None)
@@ -711,6 +724,10 @@ class _RunDistances:
                 tables.append((self.mst_path, _native.DISTANCES_HEADER + rows.tree_tsv(ctx, mc)))
             if self.newick_path:
                 tables.append((self.newick_path, _native.newick_header() + rows.newick_tsv(ctx, mc)))
+            if self.sites_path:
+                tables.append((self.sites_path, _native.SITES_HEADER + rows.sites_tsv(ctx, self.core_sites)))
+            if self.snp_alignment_path:
+                tables.append((self.snp_alignment_path, _native.SNP_ALIGNMENT_HEADER + rows.snp_alignment_tsv(ctx, self.core_sites)))
             rows.close()  # (the handles of this database's loci: every table has been made of them)
             for path, text in tables:
                 if kw is None and _is_stdout(path):
@@ -902,7 +919,7 @@ def run_type(args: argparse.Namespace) -> int:
             raise ValueError(f"--{r.name} with --db writes a table per database: it needs a file name, not stdout")
     for flag in PAIR_TABLES:
         if getattr(args, "db", None) and (v := getattr(args, flag, None)) and _is_stdout(v):
-            raise ValueError(f"--{flag} with --db writes a table per database: it needs a file name, not stdout")
+            raise ValueError(f"--{flag.replace('_', '-')} with --db writes a table per database: it needs a file name, not stdout")
     dist = _RunDistances(args) if any(getattr(args, f, None) for f in PAIR_TABLES) else None
     run_dbs = None  # the databases of the run, where this process has loaded them (one device)
     handles = {}

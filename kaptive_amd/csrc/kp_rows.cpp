@@ -16,6 +16,7 @@
 #include "../../include/kaptive_amd.h"
 #include "kp_alleles.h"
 #include "kp_clust.h"
+#include "kp_sites.h"
 
 namespace {
 
@@ -61,7 +62,7 @@ inline bool alive(const kp_kept &k) { return (k.flags & KP_F_SPURIOUS) == 0; }
 template <class Off>  // (the name tables of the rows have 32-bit offsets, the others 64-bit ones)
 inline void put_name(Out &o, const char *names, const Off *off, int64_t i) { o.put(names + off[i], off[i + 1] - off[i]); }
 
-// ---- the tables over the rows of one locus's matrix (kp_spec.h, DISTANCES, CLUSTERS, TREE) ----
+// ---- the tables over the rows of one locus's matrix (kp_spec.h, DISTANCES, CLUSTERS, TREE, SITES) ----
 // The names of the n rows, as the caller stacked them: row r is called names[name_off[at(r)] .. name_off[at(r) + 1]), at(r) = rows[r]
 // where a mapping is given.
 struct RowNames {
@@ -696,6 +697,82 @@ extern "C" int64_t kp_format_newick(const char *locus_name, int32_t locus_name_l
             if (!is_root) { o.put(':'); put_i(o, length); }
         }
         o.lit(";\n");
+    }
+    return o.n;
+}
+
+// ---- site table (kp_spec.h, SITES) ---------------------------------------------------------------------------------------------------
+// One line per site of one locus, in the sites' order; the genes of the locus are named by the caller (RowNames: a gene per "row").
+extern "C" int64_t kp_format_sites(const char *locus_name, int32_t locus_name_len, const char *gene_names, const int64_t *gene_name_off, int32_t n_genes,
+                                   const int32_t *genes, const int32_t *gene_len, int32_t n_rows, const kp_site *sites, int64_t n_sites, char *out, int64_t cap) {
+    const RowNames t{gene_names, gene_name_off, n_genes, genes};
+    if (!locus_and_out_ok(locus_name, locus_name_len, out, cap) || !t.valid() || n_rows < 0 || n_sites < 0) return KP_EINVAL;
+    if ((n_genes > 0 && !gene_len) || (n_sites > 0 && !sites)) return KP_EINVAL;
+    std::vector<int64_t> blocks((size_t)n_genes), before((size_t)n_genes);  // every gene's blocks, and the real columns of the genes before it
+    int64_t real = 0;
+    for (int32_t g = 0; g < n_genes; ++g) {
+        if (gene_len[g] < 0) return KP_EINVAL;
+        blocks[(size_t)g] = ((int64_t)gene_len[g] + 15) / 16;
+        before[(size_t)g] = real;
+        real += gene_len[g];
+    }
+    Out o{out, cap};
+    for (int64_t i = 0; i < n_sites; ++i) {
+        const kp_site &s = sites[i];
+        int64_t pos = 0;
+        const int32_t g = kp_site_gene(blocks.data(), n_genes, s.column, &pos);
+        if (g < 0 || pos >= gene_len[g]) return KP_EINVAL;  // outside the matrix, or padding
+        if (i > 0 && s.column <= sites[i - 1].column) return KP_EINVAL;
+        int64_t held = s.n_n;
+        for (int k = 0; k < 4; ++k) {
+            if (s.n[k] < 0) return KP_EINVAL;
+            held += s.n[k];
+        }
+        if (s.n_n < 0 || held > n_rows || kp_site_alleles(s.n) < 2) return KP_EINVAL;
+        put_locus(o, locus_name, locus_name_len); o.put('\t');
+        t.put(o, g); o.put('\t');
+        put_i(o, pos + 1); o.put('\t');
+        put_i(o, before[(size_t)g] + pos + 1); o.put('\t');
+        put_i(o, n_rows); o.put('\t');
+        for (int k = 0; k < 4; ++k) { put_i(o, s.n[k]); o.put('\t'); }
+        put_i(o, s.n_n); o.put('\t');
+        put_i(o, kp_site_gap(s.n, s.n_n, n_rows)); o.put('\t');
+        put_i(o, kp_site_alleles(s.n)); o.put('\t');
+        o.put("acgt"[kp_site_major(s.n)]); o.put('\t');
+        o.lit(kp_site_informative(s.n) ? "yes" : "no");
+        o.put('\n');
+    }
+    return o.n;
+}
+
+// ---- SNP alignment (kp_spec.h, SITES, SITE ROWS) ------------------------------------------------------------------------------------------
+// One line per row of one locus's matrix, in row order: its codes at the locus's sites as text.
+extern "C" int64_t kp_format_site_rows(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
+                                       const int32_t *rows, int64_t n_sites, const uint64_t *blocks, char *out, int64_t cap) {
+    const RowNames t{names, name_off, n_names, rows};
+    if (!locus_and_out_ok(locus_name, locus_name_len, out, cap) || !t.valid() || n_sites < 0) return KP_EINVAL;
+    const int64_t SB = kp_site_row_blocks(n_sites);
+    if (n_names > 0 && SB > 0 && !blocks) return KP_EINVAL;
+    Out o{out, cap};
+    if (n_sites == 0) return 0;  // a locus without a site writes no line
+    for (int32_t r = 0; r < n_names; ++r) {
+        put_locus(o, locus_name, locus_name_len); o.put('\t');
+        t.put(o, r); o.put('\t');
+        put_i(o, n_sites); o.put('\t');
+        for (int64_t b = 0; b < SB; ++b) {
+            const uint64_t v = blocks[(size_t)r * (size_t)SB + (size_t)b];
+            const uint32_t m = (uint32_t)(v >> KP_DIST_N_SHIFT) & 0xffffu, g = (uint32_t)(v >> KP_DIST_GAP_SHIFT) & 0xffffu;
+            if (m & g) return KP_EINVAL;
+            for (int k = 0; k < KP_SITES_BLOCK; ++k) {
+                const bool gap = (g >> k) & 1u;
+                if (b * KP_SITES_BLOCK + k >= n_sites) {
+                    if (!gap) return KP_EINVAL;  // (padding is flagged)
+                    continue;
+                }
+                o.put(gap ? '-' : ((m >> k) & 1u) ? 'n' : "acgt"[(v >> (2 * k)) & 3u]);
+            }
+        }
+        o.put('\n');
     }
     return o.n;
 }

@@ -6,7 +6,9 @@ the primary kept records of its best locus's genes, strung together in database 
 hands the rows of every locus to the device as one matrix (``_native.Distances``: kp_dist.hip compares them all against all).  Two
 tables come of a matrix: the listed pairs (``distances`` / ``tsv``) and, with no pair listed, every row's single-linkage cluster at a
 few thresholds and its nearest neighbour (``clusters`` / ``clusters_tsv``; include/kp_spec.h, CLUSTERS), and the minimum spanning forest
-of the rows as an edge table and as Newick text (``tree`` / ``tree_tsv`` / ``newick_tsv``; include/kp_spec.h, TREE).  One device handle
+of the rows as an edge table and as Newick text (``tree`` / ``tree_tsv`` / ``newick_tsv``; include/kp_spec.h, TREE).  A fourth reads
+the matrix by columns, not by pairs: the variable sites of a locus with every base's count, and the rows cut down to those sites
+(``profile`` / ``sites`` / ``site_rows`` / ``sites_tsv`` / ``snp_alignment_tsv``; include/kp_spec.h, SITES).  One device handle
 per locus serves them all: it is kept until the rows change or ``close()``.
 
 It spans batches and, on a multi-GPU run, processes: ``state()`` is a picklable payload of what was added, ``merge()`` absorbs one.
@@ -21,6 +23,9 @@ from kaptive_amd.serotyping.batch import F_PRIMARY
 
 GAP_BLOCK = np.uint64(0xFFFF << 48)  # sixteen GAP columns: a gene without a primary record, and what padding adds to a last block
 DIST_RECORD_DTYPE = np.dtype([("locus", "<i4"), ("a", "<i4"), ("b", "<i4"), ("compared", "<i4"), ("differences", "<i4"), ("unshared", "<i4")])
+
+
+SITE_RECORD_DTYPE = np.dtype([("locus", "<i4"), ("gene", "<i4"), ("position", "<i4"), ("column", "<i4"), ("n", "<i4", (4,)), ("n_n", "<i4")])
 
 
 def clust_record_dtype(n_levels: int) -> np.dtype:
@@ -256,6 +261,83 @@ class LocusRows:
         def table(L):
             idx, p, comp = self._locus_tree(ctx, L, min_compared)
             return _native.format_newick(self.db.loci.ids[L], [self.ids[i] for i in idx], p, comp)
+
+        return self._per_locus(table, b"")
+
+    # -- sites: the matrix by columns ---------------------------------------------------------------------------------------------------
+    def profile(self, ctx, locus: int) -> np.ndarray:
+        """``_native.SITE_DTYPE`` records of every column of ``locus``'s matrix, padding columns included: how many of its rows hold
+        a, c, g, t and N there.  Fewer than two rows: counted here, without a device call."""
+        idx, mat = self.locus_matrix(locus)
+        if len(idx) >= 2:
+            return self._handle(ctx, locus).profile()
+        out = np.zeros(16 * mat.shape[1], _native.SITE_DTYPE)
+        out["column"] = np.arange(len(out))
+        for row in mat:
+            j = np.arange(16, dtype=np.uint64)
+            n, gap = ((row[:, None] >> (j + np.uint64(32))) & np.uint64(1)).ravel() != 0, ((row[:, None] >> (j + np.uint64(48))) & np.uint64(1)).ravel() != 0
+            code = ((row[:, None] >> (2 * j)) & np.uint64(3)).ravel().astype(np.int64)
+            base = ~n & ~gap
+            out["n"][np.flatnonzero(base), code[base]] += 1
+            out["n_n"] += n & ~gap
+        return out
+
+    def _locus_sites(self, ctx, locus: int, core: bool, rows: bool = False):
+        """(assembly numbers [R], site records of the matrix, site rows uint64 [R, (S + 15) // 16] or None) of one locus."""
+        idx, mat = self.locus_matrix(locus)
+        if len(idx) < 2:  # one row differs from nobody: no site, rows of 0 blocks
+            return idx, np.zeros(0, _native.SITE_DTYPE), np.zeros((len(idx), 0), np.uint64) if rows else None
+        h = self._handle(ctx, locus)
+        sites = h.sites(core)
+        return idx, sites, h.site_rows() if rows else None
+
+    def _site_genes(self, locus: int, columns):
+        """(gene of the locus, 0-based position in it) of matrix columns of ``locus``."""
+        g0, g1 = self.locus_genes(locus)
+        first = np.concatenate([[0], np.cumsum(self._gene_blocks[g0:g1])]).astype(np.int64) * 16
+        gene = np.searchsorted(first, np.asarray(columns, np.int64), side="right") - 1
+        return gene, np.asarray(columns, np.int64) - first[gene]
+
+    def sites(self, ctx, core: bool = False) -> np.ndarray:
+        """SITE_RECORD_DTYPE records ``(locus, gene, position, column, n[4], n_n)`` of the variable sites: loci in database order,
+        sites ascending within a locus.  ``gene`` is the database's gene index, ``position`` 0-based in it, ``column`` 0-based in the
+        locus's genes strung together without padding; ``n`` the rows that hold a, c, g, t there and ``n_n`` those that hold an N."""
+
+        def table(L):
+            _, s, _ = self._locus_sites(ctx, L, core)
+            g0, g1 = self.locus_genes(L)
+            gene, pos = self._site_genes(L, s["column"])
+            rec = np.zeros(len(s), SITE_RECORD_DTYPE)
+            rec["locus"], rec["gene"], rec["position"] = L, g0 + gene, pos
+            rec["column"] = np.concatenate([[0], np.cumsum(self._gene_lengths[g0:g1])])[gene] + pos
+            rec["n"], rec["n_n"] = s["n"], s["n_n"]
+            return rec
+
+        return self._per_locus(table, np.zeros(0, SITE_RECORD_DTYPE))
+
+    def site_rows(self, ctx, locus: int, core: bool = False) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(assembly numbers [R], site records of the matrix [S], site rows uint64 [R, (S + 15) // 16]) of one locus: every row cut
+        down to the locus's sites, in the packed form of the rows themselves -- a matrix ``_native.Distances`` takes."""
+        return self._locus_sites(ctx, locus, core, rows=True)
+
+    def sites_tsv(self, ctx, core: bool = False) -> bytes:
+        """The lines of the site table (``--sites``; no header: ``_native.SITES_HEADER``), formatted by the native library
+        (kp_format_sites): loci in database order, a line per site in column order."""
+
+        def table(L):
+            idx, s, _ = self._locus_sites(ctx, L, core)
+            g0, g1 = self.locus_genes(L)
+            return _native.format_sites(self.db.loci.ids[L], list(self.db.genes.ids[g0:g1]), self._gene_lengths[g0:g1], len(idx), s)
+
+        return self._per_locus(table, b"")
+
+    def snp_alignment_tsv(self, ctx, core: bool = False) -> bytes:
+        """The lines of the SNP alignment (``--snp-alignment``; no header: ``_native.SNP_ALIGNMENT_HEADER``), formatted by the native
+        library (kp_format_site_rows): loci in database order, a line per assembly in input order; a locus without a site has none."""
+
+        def table(L):
+            idx, s, blocks = self._locus_sites(ctx, L, core, rows=True)
+            return _native.format_site_rows(self.db.loci.ids[L], [self.ids[i] for i in idx], len(s), blocks)
 
         return self._per_locus(table, b"")
 
