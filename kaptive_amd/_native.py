@@ -51,6 +51,7 @@ ALIGNED_ROW_DTYPE = np.dtype([("off", "<i8"), ("gene_len", "<i4"), ("covered", "
 ALIGNED_HEADER = (b"Assembly\tGene\tContig\tStart\tEnd\tStrand\tGene length\tGene start\tGene end\tCovered\tInserted\tInsertions\t"
                   b"Aligned\n")  # the columns of kp_format_aligned
 ALIGNED_GAP = 5  # the code ``aligned_codes`` gives a GAP column (0..3 bases, 4 inside an N run)
+BLOCK_N_SHIFT, BLOCK_GAP_SHIFT = 32, 48  # KP_DIST_N_SHIFT, KP_DIST_GAP_SHIFT of kaptive_amd/csrc/kp_dist.h: the N mask and the gap mask of a 16-column block
 
 RESCUE_DTYPE = np.dtype(
     [("gene", "<i4"), ("piece", "<i4"), ("contig", "<i4"), ("t_start", "<i4"), ("t_end", "<i4"), ("score", "<i4"), ("matches", "<i4"),
@@ -467,16 +468,22 @@ class RowFormatter:
         stride = kept.shape[1] if kept.ndim == 2 else 0
         h = lib()
         h.kp_format_rows.restype = C.c_int64
-        out = np.empty(max(4096, 1200 * n), np.uint8)
-        for _ in range(2):
-            need = h.kp_format_rows(C.byref(self._tables), C.c_int32(n), _p(sums), _p(kept), C.c_int32(stride), C.byref(c),
-                                    _p(out), C.c_int64(len(out)))
-            if need < 0:
-                raise ValueError(f"kp_format_rows failed ({need})")
-            if need <= len(out):
-                return out[:need].tobytes()
-            out = np.empty(int(need), np.uint8)
-        raise NativeError("kp_format_rows: size kept changing")
+        return _sized("kp_format_rows", 1200 * n, lambda out, cap: h.kp_format_rows(
+            C.byref(self._tables), C.c_int32(n), _p(sums), _p(kept), C.c_int32(stride), C.byref(c), out, cap))
+
+
+def _sized(name: str, room: int, call) -> bytes:
+    """The bytes of one of the formatters: ``call(out, cap)`` formats into ``out`` and returns the room the table needs -- so a first
+    buffer of ``room`` bytes is tried, and one of exactly the size asked for if that was too small."""
+    out = np.empty(max(4096, room), np.uint8)
+    for _ in range(2):
+        need = call(_p(out), C.c_int64(len(out)))
+        if need < 0:
+            raise ValueError(f"{name} failed ({need})")
+        if need <= len(out):
+            return out[:need].tobytes()
+        out = np.empty(int(need), np.uint8)
+    raise NativeError(f"{name}: size kept changing")
 
 
 class PafTables(C.Structure):  # kp_paf_tables
@@ -484,38 +491,43 @@ class PafTables(C.Structure):  # kp_paf_tables
                 ("ctg_names", C.c_void_p), ("ctg_name_off", C.c_void_p), ("ctg_len", C.c_void_p), ("asm_first_ctg", C.c_void_p)]  # fmt: skip
 
 
+PAF_CS, PAF_EQX = 1, 2  # KP_PAF_CS, KP_PAF_EQX
+
+
+def _format_paf(gene_names, gene_lengths, contig_names, contig_lengths, asm_first_ctg, hits, hit_off, ops, cigar_off, cs=None, cs_off=None,
+                flags: int = 0) -> bytes:
+    """``format_paf`` (kp_format_paf), or with ``cs_off`` ``format_paf_tags`` (kp_format_paf_tags)."""
+    tags = cs_off is not None
+    gn_b, gn_o = _blob(gene_names)
+    cn_b, cn_o = _blob64(contig_names)
+    gene_len, ctg_len, first = _c(gene_lengths, np.int32), _c(contig_lengths, np.int32), _c(asm_first_ctg, np.int64)
+    hits, hit_off = np.ascontiguousarray(hits, dtype=HIT_DTYPE), _c(hit_off, np.int64)
+    ops, cigar_off = _c(ops, np.uint32), _c(cigar_off, np.int64)
+    n_asm, n_hits = len(hit_off) - 1, len(hits)
+    if tags:
+        cs, cs_off = _c(np.frombuffer(cs, np.uint8) if isinstance(cs, (bytes, bytearray)) else cs, np.uint8), _c(cs_off, np.int64)
+    if len(first) != n_asm + 1 or len(cigar_off) != n_hits + 1 or (tags and len(cs_off) != n_hits + 1) or int(hit_off[-1]) != n_hits:
+        raise ValueError("offsets do not describe the hit table")
+    if int(first[-1]) > len(ctg_len) or len(cn_o) != len(ctg_len) + 1 or len(gene_len) != len(gn_o) - 1:
+        raise ValueError("name and length tables disagree")
+    if tags and (int(cs_off[-1]) > len(cs) or int(cigar_off[-1]) > len(ops)):
+        raise ValueError("offsets run past their arrays")
+    t = PafTables(gene_names=_p(gn_b).value, gene_name_off=_p(gn_o).value, gene_len=_p(gene_len).value, n_genes=len(gn_o) - 1,
+                  ctg_names=_p(cn_b).value, ctg_name_off=_p(cn_o).value, ctg_len=_p(ctg_len).value, asm_first_ctg=_p(first).value)  # fmt: skip
+    h = lib()
+    h.kp_format_paf.restype = h.kp_format_paf_tags.restype = C.c_int64
+    if not tags:
+        return _sized("kp_format_paf", 160 * n_hits + 8 * len(ops), lambda out, cap: h.kp_format_paf(
+            C.byref(t), C.c_int32(n_asm), _p(hits), _p(hit_off), _p(ops), _p(cigar_off), out, cap))
+    return _sized("kp_format_paf_tags", 176 * n_hits + 8 * len(ops) + 2 * len(cs), lambda out, cap: h.kp_format_paf_tags(
+        C.byref(t), C.c_int32(n_asm), _p(hits), _p(hit_off), _p(ops), _p(cigar_off), _p(cs), _p(cs_off), C.c_int32(int(flags)), out, cap))
+
+
 def format_paf(gene_names, gene_lengths, contig_names, contig_lengths, asm_first_ctg, hits, hit_off, ops, cigar_off) -> bytes:
     """PAF lines of a hit table (kp_format_paf; host only): one per hit, in the table's order.  ``contig_names`` /
     ``contig_lengths`` list the contigs of all assemblies back to back, assembly a's are ``asm_first_ctg[a]:asm_first_ctg[a + 1]``;
     ``hits`` are HIT_DTYPE rows, ``hit_off`` their per-assembly offsets, ``ops`` / ``cigar_off`` as ``Batch.cigars`` returns them."""
-    gn_b, gn_o = _blob(gene_names)
-    cn_b, cn_o = _blob64(contig_names)
-    keep = dict(gene_len=_c(gene_lengths, np.int32), ctg_len=_c(contig_lengths, np.int32), first=_c(asm_first_ctg, np.int64),
-                hits=np.ascontiguousarray(hits, dtype=HIT_DTYPE), hit_off=_c(hit_off, np.int64),
-                ops=_c(ops, np.uint32), cigar_off=_c(cigar_off, np.int64))  # fmt: skip
-    n_asm = len(keep["hit_off"]) - 1
-    if len(keep["first"]) != n_asm + 1 or len(keep["cigar_off"]) != len(keep["hits"]) + 1 or int(keep["hit_off"][-1]) != len(keep["hits"]):
-        raise ValueError("offsets do not describe the hit table")
-    if int(keep["first"][-1]) > len(keep["ctg_len"]) or len(cn_o) != len(keep["ctg_len"]) + 1 or len(keep["gene_len"]) != len(gn_o) - 1:
-        raise ValueError("name and length tables disagree")
-    t = PafTables(gene_names=_p(gn_b).value, gene_name_off=_p(gn_o).value, gene_len=_p(keep["gene_len"]).value, n_genes=len(gn_o) - 1,
-                  ctg_names=_p(cn_b).value, ctg_name_off=_p(cn_o).value, ctg_len=_p(keep["ctg_len"]).value,
-                  asm_first_ctg=_p(keep["first"]).value)  # fmt: skip
-    h = lib()
-    h.kp_format_paf.restype = C.c_int64
-    out = np.empty(max(4096, 160 * len(keep["hits"]) + 8 * len(keep["ops"])), np.uint8)
-    for _ in range(2):
-        need = h.kp_format_paf(C.byref(t), C.c_int32(n_asm), _p(keep["hits"]), _p(keep["hit_off"]), _p(keep["ops"]),
-                               _p(keep["cigar_off"]), _p(out), C.c_int64(len(out)))
-        if need < 0:
-            raise ValueError(f"kp_format_paf failed ({need})")
-        if need <= len(out):
-            return out[:need].tobytes()
-        out = np.empty(int(need), np.uint8)
-    raise NativeError("kp_format_paf: size kept changing")
-
-
-PAF_CS, PAF_EQX = 1, 2  # KP_PAF_CS, KP_PAF_EQX
+    return _format_paf(gene_names, gene_lengths, contig_names, contig_lengths, asm_first_ctg, hits, hit_off, ops, cigar_off)
 
 
 def format_paf_tags(gene_names, gene_lengths, contig_names, contig_lengths, asm_first_ctg, hits, hit_off, ops, cigar_off, cs, cs_off,
@@ -523,35 +535,7 @@ def format_paf_tags(gene_names, gene_lengths, contig_names, contig_lengths, asm_
     """``format_paf`` with what the cs strings add (kp_format_paf_tags): ``flags`` is ``PAF_CS`` (a ``cs:Z:`` tag behind ``cg:Z:``),
     ``PAF_EQX`` (``cg:Z:`` in =/X form) or both; ``cs`` / ``cs_off`` as ``Batch.cs`` returns them.  A cs string that does not fit
     its hit's ops raises ``ValueError``."""
-    gn_b, gn_o = _blob(gene_names)
-    cn_b, cn_o = _blob64(contig_names)
-    keep = dict(gene_len=_c(gene_lengths, np.int32), ctg_len=_c(contig_lengths, np.int32), first=_c(asm_first_ctg, np.int64),
-                hits=np.ascontiguousarray(hits, dtype=HIT_DTYPE), hit_off=_c(hit_off, np.int64),
-                ops=_c(ops, np.uint32), cigar_off=_c(cigar_off, np.int64), cs=_c(np.frombuffer(cs, np.uint8) if isinstance(cs, (bytes, bytearray)) else cs, np.uint8),
-                cs_off=_c(cs_off, np.int64))  # fmt: skip
-    n_asm = len(keep["hit_off"]) - 1
-    n_hits = len(keep["hits"])
-    if len(keep["first"]) != n_asm + 1 or len(keep["cigar_off"]) != n_hits + 1 or len(keep["cs_off"]) != n_hits + 1 or int(keep["hit_off"][-1]) != n_hits:
-        raise ValueError("offsets do not describe the hit table")
-    if int(keep["first"][-1]) > len(keep["ctg_len"]) or len(cn_o) != len(keep["ctg_len"]) + 1 or len(keep["gene_len"]) != len(gn_o) - 1:
-        raise ValueError("name and length tables disagree")
-    if int(keep["cs_off"][-1]) > len(keep["cs"]) or int(keep["cigar_off"][-1]) > len(keep["ops"]):
-        raise ValueError("offsets run past their arrays")
-    t = PafTables(gene_names=_p(gn_b).value, gene_name_off=_p(gn_o).value, gene_len=_p(keep["gene_len"]).value, n_genes=len(gn_o) - 1,
-                  ctg_names=_p(cn_b).value, ctg_name_off=_p(cn_o).value, ctg_len=_p(keep["ctg_len"]).value,
-                  asm_first_ctg=_p(keep["first"]).value)  # fmt: skip
-    h = lib()
-    h.kp_format_paf_tags.restype = C.c_int64
-    out = np.empty(max(4096, 176 * n_hits + 8 * len(keep["ops"]) + 2 * len(keep["cs"])), np.uint8)
-    for _ in range(2):
-        need = h.kp_format_paf_tags(C.byref(t), C.c_int32(n_asm), _p(keep["hits"]), _p(keep["hit_off"]), _p(keep["ops"]), _p(keep["cigar_off"]),
-                                    _p(keep["cs"]), _p(keep["cs_off"]), C.c_int32(int(flags)), _p(out), C.c_int64(len(out)))
-        if need < 0:
-            raise ValueError(f"kp_format_paf_tags failed ({need})")
-        if need <= len(out):
-            return out[:need].tobytes()
-        out = np.empty(int(need), np.uint8)
-    raise NativeError("kp_format_paf_tags: size kept changing")
+    return _format_paf(gene_names, gene_lengths, contig_names, contig_lengths, asm_first_ctg, hits, hit_off, ops, cigar_off, cs, cs_off, flags)
 
 
 class VariantTables(C.Structure):  # kp_variant_tables
@@ -559,71 +543,78 @@ class VariantTables(C.Structure):  # kp_variant_tables
                 ("asm_name_off", C.c_void_p), ("ctg_names", C.c_void_p), ("ctg_name_off", C.c_void_p), ("asm_first_ctg", C.c_void_p)]  # fmt: skip
 
 
+class AlleleTables(C.Structure):  # kp_allele_tables
+    _fields_ = [("names", VariantTables), ("locus_names", C.c_void_p), ("locus_name_off", C.c_void_p), ("n_loci", C.c_int32)]
+
+
+def _batch_names(gene_names, asm_names, contig_names, asm_first_ctg, n_asm: int, locus_names=None, per_asm=(), per_gene=()):
+    """The name tables of a batch of ``n_asm`` assemblies as kp_variant_tables -- with ``locus_names`` as kp_allele_tables --, and the
+    arrays the struct points into, which the caller keeps for as long as it uses it.  ``per_asm`` / ``per_gene``: further columns that
+    must have an entry per assembly / per gene."""
+    gn_b, gn_o = _blob(gene_names)
+    an_b, an_o = _blob64(asm_names)
+    cn_b, cn_o = _blob64(contig_names)
+    first = _c(asm_first_ctg, np.int64)
+    if (len(first) != n_asm + 1 or len(an_o) != n_asm + 1 or any(len(c) != n_asm for c in per_asm) or any(len(c) != len(gn_o) - 1 for c in per_gene)
+            or (n_asm and int(first[-1]) > len(cn_o) - 1)):
+        raise ValueError("name tables do not describe the batch")
+    t = VariantTables(gene_names=_p(gn_b).value, gene_name_off=_p(gn_o).value, n_genes=len(gn_o) - 1, asm_names=_p(an_b).value,
+                      asm_name_off=_p(an_o).value, ctg_names=_p(cn_b).value, ctg_name_off=_p(cn_o).value, asm_first_ctg=_p(first).value)  # fmt: skip
+    keep = [gn_b, gn_o, an_b, an_o, cn_b, cn_o, first]
+    if locus_names is not None:
+        ln_b, ln_o = _blob(locus_names)
+        t = AlleleTables(names=t, locus_names=_p(ln_b).value, locus_name_off=_p(ln_o).value, n_loci=len(ln_o) - 1)
+        keep += [ln_b, ln_o]
+    return t, keep
+
+
+def _kept_table(kept, n_asm: int, records=None, and_records: str = ""):
+    """``kept`` as the contiguous [n_asm, stride] table of ``Batch.typing`` and its stride; ``records``, where given, has its shape."""
+    from kaptive_amd.serotyping.batch import KEPT_DTYPE
+
+    kept = np.ascontiguousarray(kept)
+    if kept.itemsize != KEPT_DTYPE.itemsize or (n_asm and (kept.ndim != 2 or kept.shape[0] != n_asm)) or (records is not None and records.shape != kept.shape):
+        raise ValueError("kept must be the [n_asm, stride] table of Batch.typing" + and_records)
+    return kept, (kept.shape[1] if kept.ndim == 2 else 0)
+
+
+def _record_runs(off, records) -> np.ndarray:
+    """The per-assembly offsets of ``records`` as int64 [n_asm + 1]: they must lie inside the records."""
+    off = _c(off, np.int64)
+    if len(off) > 1 and (int(off[0]) < 0 or int(off[-1]) > len(records)):
+        raise ValueError("offsets run past the records")
+    return off
+
+
 def format_variants(gene_names, asm_names, contig_names, asm_first_ctg, kept, variants, var_off) -> bytes:
     """The lines of the variant table (kp_format_variants; host only; no header: ``VARIANTS_HEADER``): one per record of
     ``variants`` (VARIANT_DTYPE), assembly a's being ``var_off[a]:var_off[a + 1]``.  ``kept`` is the [n_asm, stride] table of
     ``Batch.typing``; ``contig_names`` lists the contigs of all assemblies back to back, assembly a's are
     ``asm_first_ctg[a]:asm_first_ctg[a + 1]``."""
-    gn_b, gn_o = _blob(gene_names)
-    an_b, an_o = _blob64(asm_names)
-    cn_b, cn_o = _blob64(contig_names)
-    first, var_off = _c(asm_first_ctg, np.int64), _c(var_off, np.int64)
-    kept = np.ascontiguousarray(kept)
     variants = np.ascontiguousarray(variants, dtype=VARIANT_DTYPE)
     n_asm = len(var_off) - 1
-    if kept.itemsize != 84 or (n_asm and (kept.ndim != 2 or kept.shape[0] != n_asm)):
-        raise ValueError("kept must be the [n_asm, stride] table of Batch.typing")
-    if len(first) != n_asm + 1 or len(an_o) != n_asm + 1 or (n_asm and int(first[-1]) > len(cn_o) - 1):
-        raise ValueError("name tables do not describe the batch")
-    if n_asm and (int(var_off[0]) < 0 or int(var_off[-1]) > len(variants)):
-        raise ValueError("offsets run past the records")
-    t = VariantTables(gene_names=_p(gn_b).value, gene_name_off=_p(gn_o).value, n_genes=len(gn_o) - 1, asm_names=_p(an_b).value,
-                      asm_name_off=_p(an_o).value, ctg_names=_p(cn_b).value, ctg_name_off=_p(cn_o).value, asm_first_ctg=_p(first).value)  # fmt: skip
+    kept, stride = _kept_table(kept, n_asm)
+    t, keep = _batch_names(gene_names, asm_names, contig_names, asm_first_ctg, n_asm)
+    var_off = _record_runs(var_off, variants)
     h = lib()
     h.kp_format_variants.restype = C.c_int64
-    out = np.empty(max(4096, 160 * len(variants)), np.uint8)
-    for _ in range(2):
-        need = h.kp_format_variants(C.byref(t), C.c_int32(n_asm), _p(kept), C.c_int32(kept.shape[1] if kept.ndim == 2 else 0), _p(variants),
-                                    _p(var_off), _p(out), C.c_int64(len(out)))
-        if need < 0:
-            raise ValueError(f"kp_format_variants failed ({need})")
-        if need <= len(out):
-            return out[:need].tobytes()
-        out = np.empty(int(need), np.uint8)
-    raise NativeError("kp_format_variants: size kept changing")
+    return _sized("kp_format_variants", 160 * len(variants), lambda out, cap: h.kp_format_variants(
+        C.byref(t), C.c_int32(n_asm), _p(kept), C.c_int32(stride), _p(variants), _p(var_off), out, cap))
 
 
 def format_breakpoints(gene_names, asm_names, contig_names, asm_first_ctg, kept, breakpoints, bp_off, edge_tolerance: int) -> bytes:
     """The lines of the breakpoint table (kp_format_breakpoints; host only; no header: ``BREAKPOINTS_HEADER``): one per record of
     ``breakpoints`` (BREAKPOINT_DTYPE), assembly a's being ``bp_off[a]:bp_off[a + 1]``.  The name tables and ``kept`` are those of
     ``format_variants``; ``edge_tolerance`` (the typer's ``partial_edge_tolerance``) decides between contig_break and translocation."""
-    gn_b, gn_o = _blob(gene_names)
-    an_b, an_o = _blob64(asm_names)
-    cn_b, cn_o = _blob64(contig_names)
-    first, bp_off = _c(asm_first_ctg, np.int64), _c(bp_off, np.int64)
-    kept = np.ascontiguousarray(kept)
     breakpoints = np.ascontiguousarray(breakpoints, dtype=BREAKPOINT_DTYPE)
     n_asm = len(bp_off) - 1
-    if kept.itemsize != 84 or (n_asm and (kept.ndim != 2 or kept.shape[0] != n_asm)):
-        raise ValueError("kept must be the [n_asm, stride] table of Batch.typing")
-    if len(first) != n_asm + 1 or len(an_o) != n_asm + 1 or (n_asm and int(first[-1]) > len(cn_o) - 1):
-        raise ValueError("name tables do not describe the batch")
-    if n_asm and (int(bp_off[0]) < 0 or int(bp_off[-1]) > len(breakpoints)):
-        raise ValueError("offsets run past the records")
-    t = VariantTables(gene_names=_p(gn_b).value, gene_name_off=_p(gn_o).value, n_genes=len(gn_o) - 1, asm_names=_p(an_b).value,
-                      asm_name_off=_p(an_o).value, ctg_names=_p(cn_b).value, ctg_name_off=_p(cn_o).value, asm_first_ctg=_p(first).value)  # fmt: skip
+    kept, stride = _kept_table(kept, n_asm)
+    t, keep = _batch_names(gene_names, asm_names, contig_names, asm_first_ctg, n_asm)
+    bp_off = _record_runs(bp_off, breakpoints)
     h = lib()
     h.kp_format_breakpoints.restype = C.c_int64
-    out = np.empty(max(4096, 256 * len(breakpoints)), np.uint8)
-    for _ in range(2):
-        need = h.kp_format_breakpoints(C.byref(t), C.c_int32(n_asm), _p(kept), C.c_int32(kept.shape[1] if kept.ndim == 2 else 0), _p(breakpoints),
-                                       _p(bp_off), C.c_int32(int(edge_tolerance)), _p(out), C.c_int64(len(out)))
-        if need < 0:
-            raise ValueError(f"kp_format_breakpoints failed ({need})")
-        if need <= len(out):
-            return out[:need].tobytes()
-        out = np.empty(int(need), np.uint8)
-    raise NativeError("kp_format_breakpoints: size kept changing")
+    return _sized("kp_format_breakpoints", 256 * len(breakpoints), lambda out, cap: h.kp_format_breakpoints(
+        C.byref(t), C.c_int32(n_asm), _p(kept), C.c_int32(stride), _p(breakpoints), _p(bp_off), C.c_int32(int(edge_tolerance)), out, cap))
 
 
 def format_rescue(gene_names, locus_names, asm_names, contig_names, asm_first_ctg, prot_len, best_locus, records, rescue_off,
@@ -632,37 +623,15 @@ def format_rescue(gene_names, locus_names, asm_names, contig_names, asm_first_ct
     (RESCUE_DTYPE), assembly a's being ``rescue_off[a]:rescue_off[a + 1]``.  The name tables are those of ``format_alleles``;
     ``prot_len`` the database's protein lengths by gene (``Database.translations.lengths``); ``min_score`` decides between ``absent``
     and a call."""
-    gn_b, gn_o = _blob(gene_names)
-    ln_b, ln_o = _blob(locus_names)
-    an_b, an_o = _blob64(asm_names)
-    cn_b, cn_o = _blob64(contig_names)
-    first, rescue_off = _c(asm_first_ctg, np.int64), _c(rescue_off, np.int64)
     prot_len, best_locus = _c(prot_len, np.int32), _c(best_locus, np.int32)
     records = np.ascontiguousarray(records, dtype=RESCUE_DTYPE)
     n_asm = len(rescue_off) - 1
-    if len(first) != n_asm + 1 or len(an_o) != n_asm + 1 or len(best_locus) != n_asm or len(prot_len) != len(gn_o) - 1 or (n_asm and int(first[-1]) > len(cn_o) - 1):
-        raise ValueError("name tables do not describe the batch")
-    if n_asm and (int(rescue_off[0]) < 0 or int(rescue_off[-1]) > len(records)):
-        raise ValueError("offsets run past the records")
-    names = VariantTables(gene_names=_p(gn_b).value, gene_name_off=_p(gn_o).value, n_genes=len(gn_o) - 1, asm_names=_p(an_b).value,
-                          asm_name_off=_p(an_o).value, ctg_names=_p(cn_b).value, ctg_name_off=_p(cn_o).value, asm_first_ctg=_p(first).value)  # fmt: skip
-    t = AlleleTables(names=names, locus_names=_p(ln_b).value, locus_name_off=_p(ln_o).value, n_loci=len(ln_o) - 1)
+    t, keep = _batch_names(gene_names, asm_names, contig_names, asm_first_ctg, n_asm, locus_names, per_asm=(best_locus,), per_gene=(prot_len,))
+    rescue_off = _record_runs(rescue_off, records)
     h = lib()
     h.kp_format_rescue.restype = C.c_int64
-    out = np.empty(max(4096, 320 * len(records)), np.uint8)
-    for _ in range(2):
-        need = h.kp_format_rescue(C.byref(t), C.c_int32(n_asm), _p(prot_len), _p(best_locus), _p(records), _p(rescue_off), C.c_int32(int(min_score)),
-                                  _p(out), C.c_int64(len(out)))
-        if need < 0:
-            raise ValueError(f"kp_format_rescue failed ({need})")
-        if need <= len(out):
-            return out[:need].tobytes()
-        out = np.empty(int(need), np.uint8)
-    raise NativeError("kp_format_rescue: size kept changing")
-
-
-class AlleleTables(C.Structure):  # kp_allele_tables
-    _fields_ = [("names", VariantTables), ("locus_names", C.c_void_p), ("locus_name_off", C.c_void_p), ("n_loci", C.c_int32)]
+    return _sized("kp_format_rescue", 320 * len(records), lambda out, cap: h.kp_format_rescue(
+        C.byref(t), C.c_int32(n_asm), _p(prot_len), _p(best_locus), _p(records), _p(rescue_off), C.c_int32(int(min_score)), out, cap))
 
 
 def piece_order(pieces, n_pieces) -> np.ndarray:
@@ -698,41 +667,22 @@ def format_alleles(gene_names, locus_names, asm_names, contig_names, asm_first_c
     """The lines of the allele table (kp_format_alleles; host only; no header: ``ALLELES_HEADER``): one per kept record that is not
     spurious.  The name tables and ``kept`` are those of ``format_variants`` plus the loci's names; ``alleles`` (ALLELE_DTYPE, the
     shape of ``kept``) and ``piece_digests`` as ``Batch.alleles`` returns them, ``order`` as ``piece_order`` gives it."""
-    gn_b, gn_o = _blob(gene_names)
-    ln_b, ln_o = _blob(locus_names)
-    an_b, an_o = _blob64(asm_names)
-    cn_b, cn_o = _blob64(contig_names)
-    first = _c(asm_first_ctg, np.int64)
     n_kept, n_pieces, best_locus = _c(n_kept, np.int32), _c(n_pieces, np.int32), _c(best_locus, np.int32)
-    kept = np.ascontiguousarray(kept)
     alleles = np.ascontiguousarray(alleles, dtype=ALLELE_DTYPE)
     piece_digests, order = np.ascontiguousarray(piece_digests, np.uint64), np.ascontiguousarray(order, np.int32)
     n_asm = len(n_kept)
-    if kept.itemsize != 84 or (n_asm and (kept.ndim != 2 or kept.shape[0] != n_asm)) or alleles.shape != kept.shape:
-        raise ValueError("kept must be the [n_asm, stride] table of Batch.typing and alleles the records of Batch.alleles for it")
-    if len(first) != n_asm + 1 or len(an_o) != n_asm + 1 or len(n_pieces) != n_asm or len(best_locus) != n_asm or (n_asm and int(first[-1]) > len(cn_o) - 1):
-        raise ValueError("name tables do not describe the batch")
+    kept, stride = _kept_table(kept, n_asm, alleles, " and alleles the records of Batch.alleles for it")
+    t, keep = _batch_names(gene_names, asm_names, contig_names, asm_first_ctg, n_asm, locus_names, per_asm=(n_pieces, best_locus))
     pstride = piece_digests.shape[1] if piece_digests.ndim == 2 else 0
     if n_asm and (piece_digests.ndim != 2 or piece_digests.shape[0] != n_asm or order.ndim != 2 or order.shape[0] != n_asm or order.shape[1] < pstride):
         raise ValueError("piece digests and piece order must be [n_asm, stride] tables")
     if n_asm and order.shape[1] != pstride:
         order = np.ascontiguousarray(order[:, :pstride])
-    names = VariantTables(gene_names=_p(gn_b).value, gene_name_off=_p(gn_o).value, n_genes=len(gn_o) - 1, asm_names=_p(an_b).value,
-                          asm_name_off=_p(an_o).value, ctg_names=_p(cn_b).value, ctg_name_off=_p(cn_o).value, asm_first_ctg=_p(first).value)  # fmt: skip
-    t = AlleleTables(names=names, locus_names=_p(ln_b).value, locus_name_off=_p(ln_o).value, n_loci=len(ln_o) - 1)
     h = lib()
     h.kp_format_alleles.restype = C.c_int64
-    out = np.empty(max(4096, 256 * int(n_kept.sum()) if n_asm else 0), np.uint8)
-    for _ in range(2):
-        need = h.kp_format_alleles(C.byref(t), C.c_int32(n_asm), _p(n_kept), _p(n_pieces), _p(best_locus), _p(kept), _p(alleles),
-                                   C.c_int32(kept.shape[1] if kept.ndim == 2 else 0), _p(piece_digests), _p(order), C.c_int32(pstride), _p(out),
-                                   C.c_int64(len(out)))  # fmt: skip
-        if need < 0:
-            raise ValueError(f"kp_format_alleles failed ({need})")
-        if need <= len(out):
-            return out[:need].tobytes()
-        out = np.empty(int(need), np.uint8)
-    raise NativeError("kp_format_alleles: size kept changing")
+    return _sized("kp_format_alleles", 256 * int(n_kept.sum()) if n_asm else 0, lambda out, cap: h.kp_format_alleles(
+        C.byref(t), C.c_int32(n_asm), _p(n_kept), _p(n_pieces), _p(best_locus), _p(kept), _p(alleles), C.c_int32(stride), _p(piece_digests), _p(order),
+        C.c_int32(pstride), out, cap))  # fmt: skip
 
 
 def aligned_codes(row, blocks) -> np.ndarray:
@@ -745,8 +695,8 @@ def aligned_codes(row, blocks) -> np.ndarray:
     v = np.ascontiguousarray(blocks[off:off + nb], np.uint64)[:, None]
     c = np.arange(16, dtype=np.uint64)[None, :]
     code = ((v >> (2 * c)) & np.uint64(3)).astype(np.uint8)
-    code[((v >> (c + np.uint64(32))) & np.uint64(1)) != 0] = 4
-    code[((v >> (c + np.uint64(48))) & np.uint64(1)) != 0] = ALIGNED_GAP
+    code[((v >> (c + np.uint64(BLOCK_N_SHIFT))) & np.uint64(1)) != 0] = 4
+    code[((v >> (c + np.uint64(BLOCK_GAP_SHIFT))) & np.uint64(1)) != 0] = ALIGNED_GAP
     return code.reshape(-1)[:L]
 
 
@@ -754,46 +704,16 @@ def format_aligned(gene_names, asm_names, contig_names, asm_first_ctg, n_kept, k
     """The lines of the aligned table (kp_format_aligned; host only; no header: ``ALIGNED_HEADER``): one per kept record that is not
     spurious.  The name tables and ``kept`` are those of ``format_variants``; ``rows`` (ALIGNED_ROW_DTYPE, the shape of ``kept``) and
     ``blocks`` as ``Batch.aligned`` returns them."""
-    gn_b, gn_o = _blob(gene_names)
-    an_b, an_o = _blob64(asm_names)
-    cn_b, cn_o = _blob64(contig_names)
-    first, n_kept = _c(asm_first_ctg, np.int64), _c(n_kept, np.int32)
-    kept = np.ascontiguousarray(kept)
+    n_kept = _c(n_kept, np.int32)
     rows = np.ascontiguousarray(rows, dtype=ALIGNED_ROW_DTYPE)
     blocks = np.ascontiguousarray(blocks, np.uint64)
     n_asm = len(n_kept)
-    if kept.itemsize != 84 or (n_asm and (kept.ndim != 2 or kept.shape[0] != n_asm)) or rows.shape != kept.shape:
-        raise ValueError("kept must be the [n_asm, stride] table of Batch.typing and rows the records of Batch.aligned for it")
-    if len(first) != n_asm + 1 or len(an_o) != n_asm + 1 or (n_asm and int(first[-1]) > len(cn_o) - 1):
-        raise ValueError("name tables do not describe the batch")
-    t = VariantTables(gene_names=_p(gn_b).value, gene_name_off=_p(gn_o).value, n_genes=len(gn_o) - 1, asm_names=_p(an_b).value,
-                      asm_name_off=_p(an_o).value, ctg_names=_p(cn_b).value, ctg_name_off=_p(cn_o).value, asm_first_ctg=_p(first).value)  # fmt: skip
+    kept, stride = _kept_table(kept, n_asm, rows, " and rows the records of Batch.aligned for it")
+    t, keep = _batch_names(gene_names, asm_names, contig_names, asm_first_ctg, n_asm)
     h = lib()
     h.kp_format_aligned.restype = C.c_int64
-    out = np.empty(max(4096, 16 * len(blocks) + 256 * int(n_kept.sum()) if n_asm else 0), np.uint8)
-    for _ in range(2):
-        need = h.kp_format_aligned(C.byref(t), C.c_int32(n_asm), _p(n_kept), _p(kept), C.c_int32(kept.shape[1] if kept.ndim == 2 else 0), _p(rows),
-                                   _p(blocks), C.c_int64(len(blocks)), _p(out), C.c_int64(len(out)))
-        if need < 0:
-            raise ValueError(f"kp_format_aligned failed ({need})")
-        if need <= len(out):
-            return out[:need].tobytes()
-        out = np.empty(int(need), np.uint8)
-    raise NativeError("kp_format_aligned: size kept changing")
-
-
-def _sized(name: str, room: int, call) -> bytes:
-    """The bytes of one of the pair formatters below: ``call(out, cap)`` formats into ``out`` and returns the room the table needs --
-    so a first buffer of ``room`` bytes is tried, and one of exactly the size asked for if that was too small."""
-    out = np.empty(max(4096, room), np.uint8)
-    for _ in range(2):
-        need = call(_p(out), C.c_int64(len(out)))
-        if need < 0:
-            raise ValueError(f"{name} failed ({need})")
-        if need <= len(out):
-            return out[:need].tobytes()
-        out = np.empty(int(need), np.uint8)
-    raise NativeError(f"{name}: size kept changing")
+    return _sized("kp_format_aligned", 16 * len(blocks) + 256 * int(n_kept.sum()) if n_asm else 0, lambda out, cap: h.kp_format_aligned(
+        C.byref(t), C.c_int32(n_asm), _p(n_kept), _p(kept), C.c_int32(stride), _p(rows), _p(blocks), C.c_int64(len(blocks)), out, cap))
 
 
 def format_distances(locus_name: str, columns: int, names, pairs) -> bytes:
@@ -1001,16 +921,9 @@ class JsonFormatter:
         q = self._prepare(*columns)
         h = lib()
         h.kp_format_json.restype = C.c_int64
-        out = np.empty(max(1 << 16, 80_000 * q["n"]), np.uint8)
-        for _ in range(2):
-            need = h.kp_format_json(C.byref(self._tables), C.c_int32(q["n"]), _p(q["sums"]), _p(q["kept"]), C.c_int32(q["kstride"]),
-                                    _p(q["pieces"]), C.c_int32(q["pstride"]), C.byref(q["c"]), _p(out), C.c_int64(len(out)))
-            if need < 0:
-                raise ValueError(f"kp_format_json failed ({need})")
-            if need <= len(out):
-                return out[:need].tobytes()
-            out = np.empty(int(need), np.uint8)
-        raise NativeError("kp_format_json: size kept changing")
+        return _sized("kp_format_json", max(1 << 16, 80_000 * q["n"]), lambda out, cap: h.kp_format_json(
+            C.byref(self._tables), C.c_int32(q["n"]), _p(q["sums"]), _p(q["kept"]), C.c_int32(q["kstride"]), _p(q["pieces"]), C.c_int32(q["pstride"]),
+            C.byref(q["c"]), out, cap))
 
     def fasta(self, kinds, *columns) -> dict:
         """Per-assembly FASTA bytes (kp_format_fasta) for every kind asked for -- "loci", "genes", "proteins": what
@@ -1028,20 +941,10 @@ class JsonFormatter:
         for kind in kinds:
             code = {"loci": 0, "genes": 1, "proteins": 2}[kind]
             nb, no = (piece_b, piece_o) if code == 0 else self._keep["gene_names_raw"]
-            ends = np.zeros(n, np.int64)
-            buf = np.empty(max(1 << 16, (40_000 if code < 2 else 12_000) * n), np.uint8)
-            for _ in range(2):
-                need = h.kp_format_fasta(C.byref(self._tables), C.c_int32(n), _p(q["sums"]), _p(q["kept"]), C.c_int32(q["kstride"]),
-                                         _p(q["pieces"]), C.c_int32(q["pstride"]), C.byref(q["c"]), C.c_int32(code), _p(nb), _p(no),
-                                         _p(buf), C.c_int64(len(buf)), _p(ends))
-                if need < 0:
-                    raise ValueError(f"kp_format_fasta failed ({need})")
-                if need <= len(buf):
-                    break
-                buf = np.empty(int(need), np.uint8)
-            else:
-                raise NativeError("kp_format_fasta: size kept changing")
-            blob = buf[:need].tobytes()
+            ends = np.zeros(n, np.int64)  # (filled by the call that fits)
+            blob = _sized("kp_format_fasta", max(1 << 16, (40_000 if code < 2 else 12_000) * n), lambda out, cap: h.kp_format_fasta(
+                C.byref(self._tables), C.c_int32(n), _p(q["sums"]), _p(q["kept"]), C.c_int32(q["kstride"]), _p(q["pieces"]), C.c_int32(q["pstride"]),
+                C.byref(q["c"]), C.c_int32(code), _p(nb), _p(no), out, cap, _p(ends)))
             starts = np.concatenate([[0], ends[:-1]])
             out[kind] = [blob[int(a):int(b)] for a, b in zip(starts, ends)]
         return out

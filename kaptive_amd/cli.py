@@ -52,7 +52,7 @@ class ResultExporter:
         self.handles, self.writers = [], []
 
         def stream(path):
-            h = sys.stdout.buffer if str(path) in ("-", "stdout") else open(path, "wb")
+            h = sys.stdout.buffer if _is_stdout(path) else open(path, "wb")
             self.handles.append(h)
             return h
 
@@ -678,12 +678,6 @@ class _RunDistances:
     handle."""
 
     def __init__(self, args: argparse.Namespace) -> None:
-        self.path = getattr(args, "distances", None)
-        self.clusters_path = getattr(args, "clusters", None)
-        self.mst_path = getattr(args, "mst", None)
-        self.newick_path = getattr(args, "newick", None)
-        self.sites_path = getattr(args, "sites", None)
-        self.snp_alignment_path = getattr(args, "snp_alignment", None)
         self.core_sites = bool(getattr(args, "core_sites", False))
         self.levels = getattr(args, "cluster_levels", None)
         self.max_diff = getattr(args, "max_distance", None)
@@ -714,20 +708,17 @@ class _RunDistances:
         md = _native.DIST_MAX_DIFF if self.max_diff is None else self.max_diff
         mc = _native.DIST_MIN_COMPARED if self.min_compared is None else self.min_compared
         levels = _native.CLUSTER_LEVELS if self.levels is None else self.levels
+        # one row per table, in PAIR_TABLES' order: the option that asks for it, its header, the LocusRows method that makes its lines, that method's arguments
+        kinds = (
+            ("distances", _native.DISTANCES_HEADER, "tsv", (md, mc)),
+            ("clusters", _native.clusters_header(levels), "clusters_tsv", (levels, mc)),
+            ("mst", _native.DISTANCES_HEADER, "tree_tsv", (mc,)),
+            ("newick", _native.newick_header(), "newick_tsv", (mc,)),
+            ("sites", _native.SITES_HEADER, "sites_tsv", (self.core_sites,)),
+            ("snp_alignment", _native.SNP_ALIGNMENT_HEADER, "snp_alignment_tsv", (self.core_sites,)),
+        )
         for kw, rows in self.rows or []:
-            tables = []
-            if self.path:
-                tables.append((self.path, _native.DISTANCES_HEADER + rows.tsv(ctx, md, mc)))
-            if self.clusters_path:
-                tables.append((self.clusters_path, _native.clusters_header(levels) + rows.clusters_tsv(ctx, levels, mc)))
-            if self.mst_path:
-                tables.append((self.mst_path, _native.DISTANCES_HEADER + rows.tree_tsv(ctx, mc)))
-            if self.newick_path:
-                tables.append((self.newick_path, _native.newick_header() + rows.newick_tsv(ctx, mc)))
-            if self.sites_path:
-                tables.append((self.sites_path, _native.SITES_HEADER + rows.sites_tsv(ctx, self.core_sites)))
-            if self.snp_alignment_path:
-                tables.append((self.snp_alignment_path, _native.SNP_ALIGNMENT_HEADER + rows.snp_alignment_tsv(ctx, self.core_sites)))
+            tables = [(path, header + getattr(rows, method)(ctx, *a)) for flag, header, method, a in kinds if (path := getattr(self.args, flag, None))]
             rows.close()  # (the handles of this database's loci: every table has been made of them)
             for path, text in tables:
                 if kw is None and _is_stdout(path):
@@ -834,34 +825,38 @@ def interleave_lines(blocks) -> bytes:
     return np.concatenate(arrs)[gather].tobytes()
 
 
+def _batch_outputs() -> tuple:
+    """One row per output a chunk's bytes go to, in the order they are opened: the key of the chunk's outputs, the option that names the
+    file, and the header line."""
+    from kaptive_amd.serotyping.io import KaptiveRow, Pha4geRow
+
+    return (("tsv", "out", KaptiveRow.header()), ("pha4ge", "pha4ge", Pha4geRow.header()), ("json", "json", b""), ("paf", "paf", b""),
+            *((r.name, r.name, r.header) for r in REPORTS))
+
+
 class _PerDatabaseOutputs:
     """The TSV / PHA4GE / JSON reports of a run with several databases: a file per database and report
     (``per_database_path``), each with its own header line; a report on stdout gets one header and the databases' lines
     genome by genome (``interleave_lines``).  The files are opened with the first chunk's outputs, which carry the
     databases' keywords."""
 
-    KINDS = (("tsv", "out"), ("pha4ge", "pha4ge"), ("json", "json"), ("paf", "paf"), *((r.name, r.name) for r in REPORTS))
-
     def __init__(self, args: argparse.Namespace) -> None:
-        self.wanted = [(key, path) for key, attr in self.KINDS if (path := getattr(args, attr, None))]
+        self.wanted = [(key, path, header) for key, attr, header in _batch_outputs() if (path := getattr(args, attr, None))]
         self.streams: "dict | None" = None  # key -> one handle per database, or the shared stdout
         self.files: list = []
 
     def _open(self, keywords) -> None:
-        from kaptive_amd.serotyping.io import KaptiveRow, Pha4geRow
-
-        headers = {"tsv": KaptiveRow.header(), "pha4ge": Pha4geRow.header(), "json": b"", "paf": b"", **{r.name: r.header for r in REPORTS}}
         self.streams = {}
-        for key, path in self.wanted:
+        for key, path, header in self.wanted:
             if _is_stdout(path):
-                sys.stdout.buffer.write(headers[key])
+                sys.stdout.buffer.write(header)
                 self.streams[key] = sys.stdout.buffer
                 continue
             self.streams[key] = []
             for kw in keywords:
                 h = open(per_database_path(path, kw), "wb")
                 self.files.append(h)
-                h.write(headers[key])
+                h.write(header)
                 self.streams[key].append(h)
 
     def write(self, outs) -> None:
@@ -912,12 +907,7 @@ def run_type(args: argparse.Namespace) -> int:
             except OSError:
                 raise FileNotFoundError(f"{p} does not exist") from None
     t_check = time.perf_counter() - t_check
-    from kaptive_amd.serotyping.io import KaptiveRow, Pha4geRow
-
-    for r in REPORTS:
-        if getattr(args, "db", None) and (v := getattr(args, r.name, None)) and _is_stdout(v):
-            raise ValueError(f"--{r.name} with --db writes a table per database: it needs a file name, not stdout")
-    for flag in PAIR_TABLES:
+    for flag in (*(r.name for r in REPORTS), *PAIR_TABLES):
         if getattr(args, "db", None) and (v := getattr(args, flag, None)) and _is_stdout(v):
             raise ValueError(f"--{flag.replace('_', '-')} with --db writes a table per database: it needs a file name, not stdout")
     dist = _RunDistances(args) if any(getattr(args, f, None) for f in PAIR_TABLES) else None
@@ -926,23 +916,13 @@ def run_type(args: argparse.Namespace) -> int:
     per_db = _PerDatabaseOutputs(args) if getattr(args, "db", None) else None  # several databases: reports per database
 
     def stream(path):
-        return sys.stdout.buffer if str(path) in ("-", "stdout") else open(path, "wb")
+        return sys.stdout.buffer if _is_stdout(path) else open(path, "wb")
 
     if per_db is None:
-        if tsv := getattr(args, "out", None):
-            handles["tsv"] = stream(tsv)
-            handles["tsv"].write(KaptiveRow.header())
-        if p := getattr(args, "pha4ge", None):
-            handles["pha4ge"] = stream(p)
-            handles["pha4ge"].write(Pha4geRow.header())
-        if j := getattr(args, "json", None):
-            handles["json"] = stream(j)
-        if f := getattr(args, "paf", None):
-            handles["paf"] = stream(f)
-        for r in REPORTS:
-            if f := getattr(args, r.name, None):
-                handles[r.name] = stream(f)
-                handles[r.name].write(r.header)
+        for key, attr, header in _batch_outputs():
+            if path := getattr(args, attr, None):
+                handles[key] = stream(path)
+                handles[key].write(header)
     done = 0
     timing_path = os.environ.get("KAPTIVE_AMD_CLI_TIMING")  # bench.py: when each chunk's rows were written
     t_start, chunk_times, phases = time.perf_counter(), [], {}

@@ -51,16 +51,61 @@ struct Out {
         do { buf[--at] = (char)('0' + cents % 10); cents /= 10; } while (cents);
         put(buf + at, 24 - at);
     }
-    inline void num(long long v) {
-        char buf[32];
-        const int len = std::snprintf(buf, sizeof buf, "%lld", v);
-        put(buf, len);
+    inline void unum(unsigned long long v) {  // "%llu"
+        char buf[24];
+        int at = 24;
+        do { buf[--at] = (char)('0' + v % 10); v /= 10; } while (v);
+        put(buf + at, 24 - at);
+    }
+    inline void num(long long v) {  // "%lld" (negated as unsigned: LLONG_MIN has no positive twin)
+        if (v < 0) { put('-'); unum(0ull - (unsigned long long)v); }
+        else unum((unsigned long long)v);
     }
 };
 
+inline bool out_ok(const char *out, int64_t cap) { return cap >= 0 && (cap == 0 || out); }  // the output buffer of a call
 inline bool alive(const kp_kept &k) { return (k.flags & KP_F_SPURIOUS) == 0; }
+inline void put_strand(Out &o, int strand) { o.put(strand < 0 ? '-' : '+'); }
+inline void put_hex(Out &o, uint64_t v) {  // 16 digits
+    char buf[16];
+    for (int i = 15; i >= 0; --i, v >>= 4) buf[i] = "0123456789abcdef"[v & 15u];
+    o.put(buf, 16);
+}
 template <class Off>  // (the name tables of the rows have 32-bit offsets, the others 64-bit ones)
 inline void put_name(Out &o, const char *names, const Off *off, int64_t i) { o.put(names + off[i], off[i + 1] - off[i]); }
+static const char *const STATE_NAMES[] = {"normal", "partial", "truncated", "below_id_threshold"};  // by KP_STATE_*
+inline const char *state_name(int state) { return state >= KP_STATE_NORMAL && state <= KP_STATE_NOVEL ? STATE_NAMES[state] : nullptr; }  // (null: no such state)
+// The first n columns of a block as text (kp_spec.h, ALIGNED ROWS; a site row's blocks have the same layout, kp_dist.h): a gap bit
+// gives '-', an N bit 'n', anything else the letter of its 2-bit code.
+inline void put_block_text(Out &o, uint64_t v, int n) {
+    const uint32_t m = (uint32_t)(v >> KP_DIST_N_SHIFT) & 0xffffu, g = (uint32_t)(v >> KP_DIST_GAP_SHIFT) & 0xffffu;
+    char buf[16];
+    for (int k = 0; k < n; ++k) buf[k] = ((g >> k) & 1u) ? '-' : (((m >> k) & 1u) ? 'n' : "acgt"[(v >> (2 * k)) & 3u]);
+    o.put(buf, n);
+}
+
+// ---- the tables over the records of a batch (kp_spec.h, VARIANTS, BREAKPOINTS, ALLELES, ALIGNED ROWS, RESCUE) ----
+// The names of a batch: its genes, its assemblies and, assembly by assembly, their contigs.
+struct BatchNames {
+    const kp_variant_tables *t;
+    struct Window { int64_t c0, nc; };  // the contigs of one assembly: nc of them from c0 on
+    bool ok(int32_t n_asm) const { return t && (n_asm <= 0 || (t->asm_name_off && t->asm_first_ctg)); }
+    Window window(int a) const { return Window{t->asm_first_ctg[a], t->asm_first_ctg[a + 1] - t->asm_first_ctg[a]}; }
+    bool gene_ok(int32_t gene) const { return gene >= 0 && gene < t->n_genes; }
+    static bool contig_ok(Window w, int32_t contig) { return contig >= 0 && contig < w.nc; }
+    template <class Rec>  // a record's gene is one of the database's and its contig one of its assembly's
+    bool gene_contig_ok(const Rec &r, Window w) const { return gene_ok(r.gene) && contig_ok(w, r.contig); }
+    void put_asm(Out &o, int a) const { put_name(o, t->asm_names, t->asm_name_off, a); }
+    void put_gene(Out &o, int32_t gene) const { put_name(o, t->gene_names, t->gene_name_off, gene); }
+    void put_contig(Out &o, Window w, int32_t contig) const { put_name(o, t->ctg_names, t->ctg_name_off, w.c0 + contig); }
+};
+// The records of a batch, assembly a's being off[a] .. off[a + 1]: the ends ascend, there are records where any are counted, every run ascends.
+inline bool run_ok(const int64_t *off, int a) { return off[a + 1] >= off[a]; }
+inline bool runs_ok(const int64_t *off, int32_t n_asm, const void *recs) {
+    bool ok = n_asm <= 0 || (off && off[n_asm] >= off[0] && (off[n_asm] == off[0] || recs));
+    for (int a = 0; ok && a < n_asm; ++a) ok = run_ok(off, a);
+    return ok;
+}
 
 // ---- the tables over the rows of one locus's matrix (kp_spec.h, DISTANCES, CLUSTERS, TREE, SITES) ----
 // The names of the n rows, as the caller stacked them: row r is called names[name_off[at(r)] .. name_off[at(r) + 1]), at(r) = rows[r]
@@ -81,11 +126,8 @@ struct RowNames {
     void put(Out &o, int32_t r) const { put_name(o, names, name_off, at(r)); }
 };
 // the locus name and the output buffer of a call; an empty name may come as a null pointer
-inline bool locus_and_out_ok(const char *locus_name, int32_t len, const char *out, int64_t cap) { return len >= 0 && (len == 0 || locus_name) && cap >= 0 && (cap == 0 || out); }
+inline bool locus_and_out_ok(const char *locus_name, int32_t len, const char *out, int64_t cap) { return len >= 0 && (len == 0 || locus_name) && out_ok(out, cap); }
 inline void put_locus(Out &o, const char *locus_name, int32_t len) { if (len > 0) o.put(locus_name, len); }
-// a record's gene is one of the database's and its contig one of the `nc` contigs of its assembly
-template <class Rec>
-inline bool gene_contig_ok(const Rec &r, int32_t n_genes, int64_t nc) { return r.gene >= 0 && r.gene < n_genes && r.contig >= 0 && r.contig < nc; }
 
 // how many distinct genes the selected hits have (np.unique(gene_indices[mask]) in the reference)
 template <class Pred>
@@ -113,9 +155,7 @@ void details(Out &o, const kp_row_tables *t, const kp_kept *k, int n, Pred pred)
         o.pct_f32(k[i].pident);
         o.put(',');
         o.pct_f32(k[i].coverage);
-        if (k[i].state == KP_STATE_PARTIAL) o.lit(",partial");
-        else if (k[i].state == KP_STATE_TRUNCATED) o.lit(",truncated");
-        else if (k[i].state == KP_STATE_NOVEL) o.lit(",below_id_threshold");
+        if (k[i].state != KP_STATE_NORMAL && state_name(k[i].state)) { o.put(','); o.lit(state_name(k[i].state)); }  // (a normal gene gets no word)
     }
 }
 
@@ -130,7 +170,7 @@ void share(Out &o, int n, int total) {  // "%d / %d (%.2f%%)"
 
 extern "C" int64_t kp_format_rows(const kp_row_tables *t, int32_t n_asm, const kp_asm_summary *sums, const kp_kept *kept,
                                   int32_t kept_stride, const kp_row_columns *c, char *out, int64_t cap) {
-    if (!t || !c || n_asm < 0 || (n_asm > 0 && (!sums || !kept)) || cap < 0 || (cap > 0 && !out)) return KP_EINVAL;
+    if (!t || !c || n_asm < 0 || (n_asm > 0 && (!sums || !kept)) || !out_ok(out, cap)) return KP_EINVAL;
     Out o{out, cap};
     for (int a = 0; a < n_asm; ++a) {
         const kp_asm_summary &s = sums[a];
@@ -190,17 +230,6 @@ extern "C" int64_t kp_format_rows(const kp_row_tables *t, int32_t n_asm, const k
 // thousand times the typing of the batch it sits beside.
 namespace {
 
-inline void put_u(Out &o, unsigned long long v) {
-    char buf[24];
-    int at = 24;
-    do { buf[--at] = (char)('0' + v % 10); v /= 10; } while (v);
-    o.put(buf + at, 24 - at);
-}
-inline void put_i(Out &o, long long v) {
-    if (v < 0) { o.put('-'); put_u(o, (unsigned long long)(-v)); }
-    else put_u(o, (unsigned long long)v);
-}
-
 // cs string of one hit (kp_spec.h, CS) checked against its ops: grammar, canonical form, column totals.  With `eqx` the =/X
 // CIGAR it stands for goes to `o`.
 bool cs_check(const char *cs, int64_t n, const uint32_t *ops, int64_t n_ops, Out *eqx) {
@@ -219,7 +248,7 @@ bool cs_check(const char *cs, int64_t n, const uint32_t *ops, int64_t n_ops, Out
             for (; i < n && cs[i] >= '0' && cs[i] <= '9' && i - i0 < 10; ++i) v = v * 10 + (unsigned)(cs[i] - '0');
             if (i == i0 || cs[i0] == '0' || prev == ':') return false;  // no number, :0 or a leading zero, two : tokens touching
             got[KP_CIGAR_M] += (long long)v;
-            if (eqx) { put_u(*eqx, v); eqx->put('='); }
+            if (eqx) { eqx->unum(v); eqx->put('='); }
         } else if (kind == '*') {
             if (i + 2 > n || !base(cs[i]) || !base(cs[i + 1])) return false;
             i += 2;
@@ -227,14 +256,14 @@ bool cs_check(const char *cs, int64_t n, const uint32_t *ops, int64_t n_ops, Out
             if (eqx) {  // a run of * tokens is one X op
                 unsigned long long k = 1;
                 for (; i + 3 <= n && cs[i] == '*' && base(cs[i + 1]) && base(cs[i + 2]); i += 3) { ++k; got[KP_CIGAR_M] += 1; }
-                put_u(*eqx, k); eqx->put('X');
+                eqx->unum(k); eqx->put('X');
             }
         } else if (kind == '+' || kind == '-') {
             const int64_t i0 = i;
             while (i < n && base(cs[i])) ++i;
             if (i == i0) return false;
             got[kind == '+' ? KP_CIGAR_I : KP_CIGAR_D] += i - i0;
-            if (eqx) { put_u(*eqx, (unsigned long long)(i - i0)); eqx->put(kind == '+' ? 'I' : 'D'); }
+            if (eqx) { eqx->unum((unsigned long long)(i - i0)); eqx->put(kind == '+' ? 'I' : 'D'); }
         } else return false;
         prev = kind;
     }
@@ -243,39 +272,40 @@ bool cs_check(const char *cs, int64_t n, const uint32_t *ops, int64_t n_ops, Out
 
 int64_t format_paf(const kp_paf_tables *t, int32_t n_asm, const kp_hit *hits, const int64_t *hit_off, const uint32_t *ops,
                    const int64_t *cigar_off, const char *cs, const int64_t *cs_off, int32_t flags, char *out, int64_t cap) {
-    if (!t || n_asm < 0 || !hit_off || !cigar_off || cap < 0 || (cap > 0 && !out)) return KP_EINVAL;
-    if (n_asm > 0 && (!t->asm_first_ctg || hit_off[n_asm] < hit_off[0] || (hit_off[n_asm] > 0 && !hits))) return KP_EINVAL;
+    if (!t || n_asm < 0 || !hit_off || !cigar_off || !out_ok(out, cap)) return KP_EINVAL;
+    if (n_asm > 0 && (!t->asm_first_ctg || !runs_ok(hit_off, n_asm, hits) || (hit_off[n_asm] > 0 && !hits))) return KP_EINVAL;
     if (flags & ~(KP_PAF_CS | KP_PAF_EQX)) return KP_EINVAL;
     if (flags && !cs_off) return KP_EINVAL;
+    const kp_variant_tables tables{t->gene_names, t->gene_name_off, t->n_genes, nullptr, nullptr, t->ctg_names, t->ctg_name_off, t->asm_first_ctg};
+    const BatchNames names{&tables};  // (a hit table names no assembly)
     Out o{out, cap};
     for (int a = 0; a < n_asm; ++a) {
-        const int64_t c0 = t->asm_first_ctg[a], nc = t->asm_first_ctg[a + 1] - c0;
+        const BatchNames::Window w = names.window(a);
         for (int64_t i = hit_off[a]; i < hit_off[a + 1]; ++i) {
             const kp_hit &h = hits[i];
-            if (!gene_contig_ok(h, t->n_genes, nc)) return KP_EINVAL;
-            const int64_t c = c0 + h.contig;
+            if (!names.gene_contig_ok(h, w)) return KP_EINVAL;
             if (cigar_off[i + 1] < cigar_off[i] || (cigar_off[i + 1] > cigar_off[i] && !ops)) return KP_EINVAL;
             if (flags && (cs_off[i + 1] < cs_off[i] || (cs_off[i + 1] > cs_off[i] && !cs))) return KP_EINVAL;
-            put_name(o, t->gene_names, t->gene_name_off, h.gene); o.put('\t');
-            put_i(o, t->gene_len[h.gene]); o.put('\t');
-            put_i(o, h.q_start); o.put('\t');
-            put_i(o, h.q_end); o.put('\t');
-            o.put(h.strand < 0 ? '-' : '+'); o.put('\t');
-            put_name(o, t->ctg_names, t->ctg_name_off, c); o.put('\t');
-            put_i(o, t->ctg_len[c]); o.put('\t');
-            put_i(o, h.t_start); o.put('\t');
-            put_i(o, h.t_end); o.put('\t');
-            put_i(o, h.matches); o.put('\t');
-            put_i(o, h.block_len); o.put('\t');
-            put_u(o, h.mapq); o.lit("\tAS:i:");
-            put_i(o, h.score); o.lit("\tNM:i:");
-            put_i(o, (long long)h.block_len - h.matches); o.lit("\tcg:Z:");
+            names.put_gene(o, h.gene); o.put('\t');
+            o.num(t->gene_len[h.gene]); o.put('\t');
+            o.num(h.q_start); o.put('\t');
+            o.num(h.q_end); o.put('\t');
+            put_strand(o, h.strand); o.put('\t');
+            names.put_contig(o, w, h.contig); o.put('\t');
+            o.num(t->ctg_len[w.c0 + h.contig]); o.put('\t');
+            o.num(h.t_start); o.put('\t');
+            o.num(h.t_end); o.put('\t');
+            o.num(h.matches); o.put('\t');
+            o.num(h.block_len); o.put('\t');
+            o.unum(h.mapq); o.lit("\tAS:i:");
+            o.num(h.score); o.lit("\tNM:i:");
+            o.num((long long)h.block_len - h.matches); o.lit("\tcg:Z:");
             const char *s = flags ? cs + cs_off[i] : nullptr;
             const int64_t ns = flags ? cs_off[i + 1] - cs_off[i] : 0;
             if (flags && !cs_check(s, ns, ops + cigar_off[i], cigar_off[i + 1] - cigar_off[i], (flags & KP_PAF_EQX) ? &o : nullptr)) return KP_EINVAL;
             if (!(flags & KP_PAF_EQX))
                 for (int64_t z = cigar_off[i]; z < cigar_off[i + 1]; ++z) {
-                    put_u(o, ops[z] >> 4);
+                    o.unum(ops[z] >> 4);
                     o.put("MIDNSHP=XB??????"[ops[z] & 15u]);
                 }
             if (flags & KP_PAF_CS) { o.lit("\tcs:Z:"); o.put(s, ns); }
@@ -302,31 +332,29 @@ extern "C" int64_t kp_format_paf_tags(const kp_paf_tables *t, int32_t n_asm, con
 // let alone per variant.
 extern "C" int64_t kp_format_variants(const kp_variant_tables *t, int32_t n_asm, const kp_kept *kept, int32_t kept_stride, const kp_variant *variants,
                                       const int64_t *var_off, char *out, int64_t cap) {
-    if (!t || n_asm < 0 || cap < 0 || (cap > 0 && !out) || (n_asm > 0 && (!var_off || !t->asm_name_off || !t->asm_first_ctg))) return KP_EINVAL;
-    if (n_asm > 0 && (var_off[n_asm] < var_off[0] || (var_off[n_asm] > var_off[0] && (!variants || !kept)))) return KP_EINVAL;
+    const BatchNames names{t};
+    if (n_asm < 0 || !out_ok(out, cap) || !names.ok(n_asm) || !runs_ok(var_off, n_asm, kept ? variants : nullptr)) return KP_EINVAL;  // (a record names a kept one)
     static const char letters[] = "acgtn";
     Out o{out, cap};
     for (int a = 0; a < n_asm; ++a) {
-        const int64_t c0 = t->asm_first_ctg[a], nc = t->asm_first_ctg[a + 1] - c0;
-        if (var_off[a + 1] < var_off[a]) return KP_EINVAL;
+        const BatchNames::Window w = names.window(a);
         for (int64_t i = var_off[a]; i < var_off[a + 1]; ++i) {
             const kp_variant &v = variants[i];
             if (v.kept < 0 || v.kept >= kept_stride || v.kind > KP_VAR_DEL) return KP_EINVAL;
             const kp_kept &k = kept[(size_t)a * (size_t)kept_stride + (size_t)v.kept];
-            if (!gene_contig_ok(k, t->n_genes, nc)) return KP_EINVAL;
-            const int64_t c = c0 + k.contig;
-            put_name(o, t->asm_names, t->asm_name_off, a); o.put('\t');
-            put_name(o, t->ctg_names, t->ctg_name_off, c); o.put('\t');
-            put_i(o, (long long)v.t_pos + 1); o.put('\t');
-            o.put(k.strand < 0 ? '-' : '+'); o.put('\t');
-            put_name(o, t->gene_names, t->gene_name_off, k.gene); o.put('\t');
-            put_i(o, (long long)v.q_pos + 1); o.put('\t');
+            if (!names.gene_contig_ok(k, w)) return KP_EINVAL;
+            names.put_asm(o, a); o.put('\t');
+            names.put_contig(o, w, k.contig); o.put('\t');
+            o.num((long long)v.t_pos + 1); o.put('\t');
+            put_strand(o, k.strand); o.put('\t');
+            names.put_gene(o, k.gene); o.put('\t');
+            o.num((long long)v.q_pos + 1); o.put('\t');
             o.lit(v.kind == KP_VAR_SNV ? "snv" : (v.kind == KP_VAR_INS ? "ins" : "del")); o.put('\t');
-            put_i(o, v.len); o.put('\t');
+            o.num(v.len); o.put('\t');
             if (v.kind == KP_VAR_SNV) {
                 o.put(letters[v.ref > 4 ? 4 : v.ref]); o.put('\t');
                 o.put(letters[v.alt > 4 ? 4 : v.alt]); o.put('\t');
-                put_i(o, (long long)v.q_pos / 3 + 1); o.put('\t');
+                o.num((long long)v.q_pos / 3 + 1); o.put('\t');
                 o.put((char)v.ref_aa); o.put('\t');
                 o.put((char)v.alt_aa); o.put('\t');
                 if (v.ref > 3 || v.alt > 3) o.lit("ambiguous");
@@ -348,41 +376,39 @@ extern "C" int64_t kp_format_variants(const kp_variant_tables *t, int32_t n_asm,
 // One line per record; the event's name is derived here, from the record's kind, its two gaps and its two edges.
 extern "C" int64_t kp_format_breakpoints(const kp_variant_tables *t, int32_t n_asm, const kp_kept *kept, int32_t kept_stride, const kp_breakpoint *bps,
                                          const int64_t *bp_off, int32_t edge_tolerance, char *out, int64_t cap) {
-    if (!t || n_asm < 0 || cap < 0 || (cap > 0 && !out) || (n_asm > 0 && (!bp_off || !t->asm_name_off || !t->asm_first_ctg))) return KP_EINVAL;
-    if (n_asm > 0 && (bp_off[n_asm] < bp_off[0] || (bp_off[n_asm] > bp_off[0] && (!bps || !kept)))) return KP_EINVAL;
+    const BatchNames names{t};
+    if (n_asm < 0 || !out_ok(out, cap) || !names.ok(n_asm) || !runs_ok(bp_off, n_asm, kept ? bps : nullptr)) return KP_EINVAL;  // (a record names two kept ones)
     Out o{out, cap};
     for (int a = 0; a < n_asm; ++a) {
-        const int64_t c0 = t->asm_first_ctg[a], nc = t->asm_first_ctg[a + 1] - c0;
-        if (bp_off[a + 1] < bp_off[a]) return KP_EINVAL;
+        const BatchNames::Window w = names.window(a);
         for (int64_t i = bp_off[a]; i < bp_off[a + 1]; ++i) {
             const kp_breakpoint &r = bps[i];
             if (r.kept_a < 0 || r.kept_a >= kept_stride || r.kept_b < 0 || r.kept_b >= kept_stride || r.kind > KP_BP_CONTIGS) return KP_EINVAL;
             const kp_kept &ka = kept[(size_t)a * (size_t)kept_stride + (size_t)r.kept_a], &kb = kept[(size_t)a * (size_t)kept_stride + (size_t)r.kept_b];
-            if (!gene_contig_ok(ka, t->n_genes, nc) || kb.contig < 0 || kb.contig >= nc) return KP_EINVAL;
+            if (!names.gene_contig_ok(ka, w) || !names.contig_ok(w, kb.contig)) return KP_EINVAL;
             const char *event;
             if (r.kind == KP_BP_COLLINEAR) event = r.t_gap > 0 ? (r.q_gap > 0 ? "replacement" : "insertion") : (r.q_gap > 0 ? "deletion" : "overlap");
             else if (r.kind == KP_BP_INVERTED) event = "inversion";
             else if (r.kind == KP_BP_DISORDERED) event = "rearrangement";
             else event = (r.edge_a <= edge_tolerance && r.edge_b <= edge_tolerance) ? "contig_break" : "translocation";
             const bool fa = ka.strand >= 0, fb = kb.strand >= 0;
-            const int64_t ca = c0 + ka.contig, cb = c0 + kb.contig;
-            put_name(o, t->asm_names, t->asm_name_off, a); o.put('\t');
-            put_name(o, t->gene_names, t->gene_name_off, ka.gene); o.put('\t');
+            names.put_asm(o, a); o.put('\t');
+            names.put_gene(o, ka.gene); o.put('\t');
             o.lit(event); o.put('\t');
-            put_i(o, ka.q_end); o.put('\t');
-            put_i(o, r.q_gap); o.put('\t');
-            put_name(o, t->ctg_names, t->ctg_name_off, ca); o.put('\t');
-            put_i(o, fa ? (long long)ka.t_end : (long long)ka.t_start + 1); o.put('\t');  // pos_a + 1
-            o.put(fa ? '+' : '-'); o.put('\t');
-            put_name(o, t->ctg_names, t->ctg_name_off, cb); o.put('\t');
-            put_i(o, fb ? (long long)kb.t_start + 1 : (long long)kb.t_end); o.put('\t');  // pos_b + 1
-            o.put(fb ? '+' : '-'); o.put('\t');
-            if (r.kind == KP_BP_COLLINEAR) put_i(o, r.t_gap); else o.put('.');
+            o.num(ka.q_end); o.put('\t');
+            o.num(r.q_gap); o.put('\t');
+            names.put_contig(o, w, ka.contig); o.put('\t');
+            o.num(fa ? (long long)ka.t_end : (long long)ka.t_start + 1); o.put('\t');  // pos_a + 1
+            put_strand(o, ka.strand); o.put('\t');
+            names.put_contig(o, w, kb.contig); o.put('\t');
+            o.num(fb ? (long long)kb.t_start + 1 : (long long)kb.t_end); o.put('\t');  // pos_b + 1
+            put_strand(o, kb.strand); o.put('\t');
+            if (r.kind == KP_BP_COLLINEAR) o.num(r.t_gap); else o.put('.');
             o.put('\t');
-            put_i(o, r.q_gap < 0 ? -(long long)r.q_gap : 0); o.put('\t');
-            put_i(o, r.edge_a); o.put('\t');
-            put_i(o, r.edge_b); o.put('\t');
-            if (r.ir_cols) { put_i(o, r.ir_matches); o.put('/'); put_i(o, r.ir_cols); } else o.put('.');
+            o.num(r.q_gap < 0 ? -(long long)r.q_gap : 0); o.put('\t');
+            o.num(r.edge_a); o.put('\t');
+            o.num(r.edge_b); o.put('\t');
+            if (r.ir_cols) { o.num(r.ir_matches); o.put('/'); o.num(r.ir_cols); } else o.put('.');
             o.put('\n');
         }
     }
@@ -393,16 +419,6 @@ extern "C" int64_t kp_format_breakpoints(const kp_variant_tables *t, int32_t n_a
 // One line per kept record the report lists; the locus digest of an assembly is combined here, by kp_alleles.h's one function, from
 // the piece digests in the product's order.
 
-namespace {
-
-inline void put_hex(Out &o, uint64_t v) {
-    char buf[16];
-    for (int i = 15; i >= 0; --i, v >>= 4) buf[i] = "0123456789abcdef"[v & 15u];
-    o.put(buf, 16);
-}
-
-}  // namespace
-
 extern "C" uint64_t kp_allele_locus_digest(const uint64_t *piece_digests, const int32_t *order, int32_t n) {
     if (n <= 0 || !piece_digests || !order) return 0;
     return kp_al_locus_digest(piece_digests, order, n);
@@ -411,8 +427,9 @@ extern "C" uint64_t kp_allele_locus_digest(const uint64_t *piece_digests, const 
 extern "C" int64_t kp_format_alleles(const kp_allele_tables *t, int32_t n_asm, const int32_t *n_kept, const int32_t *n_pieces, const int32_t *best_locus,
                                      const kp_kept *kept, const kp_allele *alleles, int32_t kept_stride, const uint64_t *piece_digests,
                                      const int32_t *piece_order, int32_t piece_stride, char *out, int64_t cap) {
-    if (!t || n_asm < 0 || cap < 0 || (cap > 0 && !out) || kept_stride < 0 || piece_stride < 0) return KP_EINVAL;
-    if (n_asm > 0 && (!n_kept || !n_pieces || !best_locus || !t->names.asm_name_off || !t->names.asm_first_ctg || !t->locus_name_off)) return KP_EINVAL;
+    const BatchNames names{t ? &t->names : nullptr};
+    if (n_asm < 0 || !out_ok(out, cap) || kept_stride < 0 || piece_stride < 0 || !names.ok(n_asm) || (n_asm > 0 && (!n_kept || !n_pieces || !best_locus || !t->locus_name_off)))
+        return KP_EINVAL;
     Out o{out, cap};
     for (int a = 0; a < n_asm; ++a) {
         const int nk = n_kept[a], np = n_pieces[a], best = best_locus[a];
@@ -420,7 +437,7 @@ extern "C" int64_t kp_format_alleles(const kp_allele_tables *t, int32_t n_asm, c
             return KP_EINVAL;
         if (nk == 0) continue;
         if (best < 0 || best >= t->n_loci) return KP_EINVAL;
-        const int64_t c0 = t->names.asm_first_ctg[a], nc = t->names.asm_first_ctg[a + 1] - c0;
+        const BatchNames::Window w = names.window(a);
         const int32_t *order = np ? piece_order + (size_t)a * (size_t)piece_stride : nullptr;
         for (int p = 0; p < np; ++p)
             if (order[p] < 0 || order[p] >= np) return KP_EINVAL;
@@ -429,24 +446,22 @@ extern "C" int64_t kp_format_alleles(const kp_allele_tables *t, int32_t n_asm, c
             const kp_kept &k = kept[(size_t)a * (size_t)kept_stride + (size_t)i];
             const kp_allele &d = alleles[(size_t)a * (size_t)kept_stride + (size_t)i];
             if (!alive(k)) continue;
-            if (!gene_contig_ok(k, t->names.n_genes, nc) || k.state < KP_STATE_NORMAL || k.state > KP_STATE_NOVEL) return KP_EINVAL;
-            const int64_t c = c0 + k.contig;
-            put_name(o, t->names.asm_names, t->names.asm_name_off, a); o.put('\t');
+            if (!names.gene_contig_ok(k, w) || !state_name(k.state)) return KP_EINVAL;
+            names.put_asm(o, a); o.put('\t');
             put_name(o, t->locus_names, t->locus_name_off, best); o.put('\t');
             if (np) put_hex(o, locus); else o.put('.');
             o.put('\t');
-            put_name(o, t->names.gene_names, t->names.gene_name_off, k.gene); o.put('\t');
+            names.put_gene(o, k.gene); o.put('\t');
             o.lit((k.flags & KP_F_EXPECTED) ? "expected" : ((k.flags & KP_F_EXTRA) ? "extra" : "other"));
             o.lit((k.flags & KP_F_INSIDE) ? "_in" : "_out"); o.put('\t');
-            put_name(o, t->names.ctg_names, t->names.ctg_name_off, c); o.put('\t');
-            put_i(o, (long long)k.t_start + 1); o.put('\t');
-            put_i(o, k.t_end); o.put('\t');
-            o.put(k.strand < 0 ? '-' : '+'); o.put('\t');
-            o.lit(k.state == KP_STATE_PARTIAL ? "partial" : (k.state == KP_STATE_TRUNCATED ? "truncated" : (k.state == KP_STATE_NOVEL ? "below_id_threshold" : "normal")));
-            o.put('\t');
-            put_i(o, (long long)k.t_end - k.t_start); o.put('\t');
+            names.put_contig(o, w, k.contig); o.put('\t');
+            o.num((long long)k.t_start + 1); o.put('\t');
+            o.num(k.t_end); o.put('\t');
+            put_strand(o, k.strand); o.put('\t');
+            o.lit(state_name(k.state)); o.put('\t');  // ("normal" included)
+            o.num((long long)k.t_end - k.t_start); o.put('\t');
             put_hex(o, d.nt); o.put('\t');
-            put_i(o, k.prot_len); o.put('\t');
+            o.num(k.prot_len); o.put('\t');
             if (k.prot_len > 0) put_hex(o, d.aa); else o.put('.');
             o.put('\n');
         }
@@ -455,44 +470,36 @@ extern "C" int64_t kp_format_alleles(const kp_allele_tables *t, int32_t n_asm, c
 }
 
 // ---- aligned table (kp_spec.h, ALIGNED ROWS) --------------------------------------------------------------------------------------
-// One line per kept record the report lists; the row is unpacked here, sixteen columns a block: a gap bit gives '-', an N bit 'n',
-// anything else the letter of its 2-bit code.
+// One line per kept record the report lists; the row is unpacked here, sixteen columns a block (put_block_text).
 extern "C" int64_t kp_format_aligned(const kp_variant_tables *t, int32_t n_asm, const int32_t *n_kept, const kp_kept *kept, int32_t kept_stride,
                                      const kp_aligned_row *rows, const uint64_t *blocks, int64_t n_blocks, char *out, int64_t cap) {
-    if (!t || n_asm < 0 || cap < 0 || (cap > 0 && !out) || kept_stride < 0 || n_blocks < 0 || (n_blocks > 0 && !blocks)) return KP_EINVAL;
-    if (n_asm > 0 && (!n_kept || !t->asm_name_off || !t->asm_first_ctg)) return KP_EINVAL;
+    const BatchNames names{t};
+    if (n_asm < 0 || !out_ok(out, cap) || kept_stride < 0 || n_blocks < 0 || (n_blocks > 0 && !blocks) || !names.ok(n_asm) || (n_asm > 0 && !n_kept)) return KP_EINVAL;
     Out o{out, cap};
     for (int a = 0; a < n_asm; ++a) {
         const int nk = n_kept[a];
         if (nk < 0 || nk > kept_stride || (nk > 0 && (!kept || !rows))) return KP_EINVAL;
-        const int64_t c0 = t->asm_first_ctg[a], nc = t->asm_first_ctg[a + 1] - c0;
+        const BatchNames::Window w = names.window(a);
         for (int i = 0; i < nk; ++i) {
             const kp_kept &k = kept[(size_t)a * (size_t)kept_stride + (size_t)i];
             const kp_aligned_row &r = rows[(size_t)a * (size_t)kept_stride + (size_t)i];
             if (!alive(k)) continue;
-            if (!gene_contig_ok(k, t->n_genes, nc)) return KP_EINVAL;
+            if (!names.gene_contig_ok(k, w)) return KP_EINVAL;
             const int64_t nb = r.gene_len < 0 ? -1 : ((int64_t)r.gene_len + 15) / 16;
             if (nb < 0 || r.off < 0 || r.off > n_blocks || nb > n_blocks - r.off) return KP_EINVAL;
-            const int64_t c = c0 + k.contig;
-            put_name(o, t->asm_names, t->asm_name_off, a); o.put('\t');
-            put_name(o, t->gene_names, t->gene_name_off, k.gene); o.put('\t');
-            put_name(o, t->ctg_names, t->ctg_name_off, c); o.put('\t');
-            put_i(o, (long long)k.t_start + 1); o.put('\t');
-            put_i(o, k.t_end); o.put('\t');
-            o.put(k.strand < 0 ? '-' : '+'); o.put('\t');
-            put_i(o, r.gene_len); o.put('\t');
-            put_i(o, (long long)k.q_start + 1); o.put('\t');
-            put_i(o, k.q_end); o.put('\t');
-            put_i(o, r.covered); o.put('\t');
-            put_i(o, r.inserted); o.put('\t');
-            put_i(o, r.n_ins); o.put('\t');
-            for (int64_t j = 0; j < nb; ++j) {
-                const uint64_t v = blocks[r.off + j];
-                const int n = (int)std::min<int64_t>(16, (int64_t)r.gene_len - 16 * j);
-                char buf[16];
-                for (int x = 0; x < n; ++x) buf[x] = ((v >> (48 + x)) & 1u) ? '-' : (((v >> (32 + x)) & 1u) ? 'n' : "acgt"[(v >> (2 * x)) & 3u]);
-                o.put(buf, n);
-            }
+            names.put_asm(o, a); o.put('\t');
+            names.put_gene(o, k.gene); o.put('\t');
+            names.put_contig(o, w, k.contig); o.put('\t');
+            o.num((long long)k.t_start + 1); o.put('\t');
+            o.num(k.t_end); o.put('\t');
+            put_strand(o, k.strand); o.put('\t');
+            o.num(r.gene_len); o.put('\t');
+            o.num((long long)k.q_start + 1); o.put('\t');
+            o.num(k.q_end); o.put('\t');
+            o.num(r.covered); o.put('\t');
+            o.num(r.inserted); o.put('\t');
+            o.num(r.n_ins); o.put('\t');
+            for (int64_t j = 0; j < nb; ++j) put_block_text(o, blocks[r.off + j], (int)std::min<int64_t>(16, (int64_t)r.gene_len - 16 * j));
             o.put('\n');
         }
     }
@@ -503,53 +510,51 @@ extern "C" int64_t kp_format_aligned(const kp_variant_tables *t, int32_t n_asm, 
 // One line per record; the call is derived here, from the record's score, stops, edge and the share of the protein it covers.
 extern "C" int64_t kp_format_rescue(const kp_allele_tables *t, int32_t n_asm, const int32_t *prot_len, const int32_t *best_locus, const kp_rescue *recs,
                                     const int64_t *rescue_off, int32_t min_score, char *out, int64_t cap) {
-    if (!t || n_asm < 0 || cap < 0 || (cap > 0 && !out)) return KP_EINVAL;
-    if (n_asm > 0 && (!rescue_off || !best_locus || !prot_len || !t->names.asm_name_off || !t->names.asm_first_ctg || !t->locus_name_off)) return KP_EINVAL;
-    if (n_asm > 0 && (rescue_off[n_asm] < rescue_off[0] || (rescue_off[n_asm] > rescue_off[0] && !recs))) return KP_EINVAL;
+    const BatchNames names{t ? &t->names : nullptr};
+    if (n_asm < 0 || !out_ok(out, cap) || !names.ok(n_asm) || !runs_ok(rescue_off, n_asm, recs) || (n_asm > 0 && (!best_locus || !prot_len || !t->locus_name_off))) return KP_EINVAL;
     Out o{out, cap};
     auto fixed2 = [&o](long long num, long long den) {  // "%.2f" of num / den (0 where den is 0)
         char buf[64];
         o.put(buf, std::snprintf(buf, sizeof buf, "%.2f", den > 0 ? (double)num / (double)den : 0.0));
     };
     for (int a = 0; a < n_asm; ++a) {
-        if (rescue_off[a + 1] < rescue_off[a]) return KP_EINVAL;
         if (rescue_off[a + 1] == rescue_off[a]) continue;
         const int best = best_locus[a];
         if (best < 0 || best >= t->n_loci) return KP_EINVAL;
-        const int64_t c0 = t->names.asm_first_ctg[a], nc = t->names.asm_first_ctg[a + 1] - c0;
+        const BatchNames::Window w = names.window(a);
         for (int64_t i = rescue_off[a]; i < rescue_off[a + 1]; ++i) {
             const kp_rescue &r = recs[i];
             const bool found = r.score > 0;
-            if (r.gene < 0 || r.gene >= t->names.n_genes || (found && (r.contig < 0 || r.contig >= nc || r.frame > 2))) return KP_EINVAL;
+            if (!names.gene_ok(r.gene) || (found && (!names.contig_ok(w, r.contig) || r.frame > 2))) return KP_EINVAL;
             const long long plen = prot_len[r.gene], span = (long long)r.p_end - r.p_start, cols = (long long)r.matches + r.mismatches + r.gaps;
             const bool short_cov = span * 100 < 90 * plen;
             // (an alignment that reaches the protein's trailing * ends on the gene's own stop: a local path ends on a positive column, and * scores
             // positive against * only.  That stop interrupts nothing.)
             const long long inner_stops = (long long)r.stops - (found && plen > 0 && r.p_end == plen ? 1 : 0);
             const char *call = r.score < min_score ? "absent" : (inner_stops > 0 ? "interrupted" : (short_cov ? (r.edge ? "partial" : "fragment") : "diverged"));
-            put_name(o, t->names.asm_names, t->names.asm_name_off, a); o.put('\t');
+            names.put_asm(o, a); o.put('\t');
             put_name(o, t->locus_names, t->locus_name_off, best); o.put('\t');
-            put_name(o, t->names.gene_names, t->names.gene_name_off, r.gene); o.put('\t');
-            put_i(o, plen); o.put('\t');
+            names.put_gene(o, r.gene); o.put('\t');
+            o.num(plen); o.put('\t');
             o.lit(call); o.put('\t');
-            put_i(o, r.score); o.put('\t');
+            o.num(r.score); o.put('\t');
             if (found) {
-                put_name(o, t->names.ctg_names, t->names.ctg_name_off, c0 + r.contig); o.put('\t');
-                put_i(o, (long long)r.t_start + 1); o.put('\t');
-                put_i(o, r.t_end); o.put('\t');
-                o.put(r.strand < 0 ? '-' : '+'); o.put('\t');
-                put_i(o, (long long)r.frame + 1); o.put('\t');
-                put_i(o, (long long)r.p_start + 1); o.put('\t');
-                put_i(o, r.p_end); o.put('\t');
+                names.put_contig(o, w, r.contig); o.put('\t');
+                o.num((long long)r.t_start + 1); o.put('\t');
+                o.num(r.t_end); o.put('\t');
+                put_strand(o, r.strand); o.put('\t');
+                o.num((long long)r.frame + 1); o.put('\t');
+                o.num((long long)r.p_start + 1); o.put('\t');
+                o.num(r.p_end); o.put('\t');
             } else {
                 o.lit(".\t.\t.\t.\t.\t.\t.\t");
             }
-            put_i(o, r.matches); o.put('\t');
-            put_i(o, r.mismatches); o.put('\t');
-            put_i(o, r.gaps); o.put('\t');
+            o.num(r.matches); o.put('\t');
+            o.num(r.mismatches); o.put('\t');
+            o.num(r.gaps); o.put('\t');
             fixed2((long long)r.matches * 100, cols); o.put('\t');
             fixed2(span * 100, plen); o.put('\t');
-            put_i(o, r.stops); o.put('\t');
+            o.num(r.stops); o.put('\t');
             o.lit(!found || !r.edge ? "." : (r.edge == 3 ? "both" : (r.edge == 1 ? "start" : "end")));
             o.put('\n');
         }
@@ -571,10 +576,10 @@ extern "C" int64_t kp_format_distances(const char *locus_name, int32_t locus_nam
         put_locus(o, locus_name, locus_name_len); o.put('\t');
         t.put(o, r.a); o.put('\t');
         t.put(o, r.b); o.put('\t');
-        put_i(o, columns); o.put('\t');
-        put_i(o, r.compared); o.put('\t');
-        put_i(o, r.differences); o.put('\t');
-        put_i(o, r.unshared);
+        o.num(columns); o.put('\t');
+        o.num(r.compared); o.put('\t');
+        o.num(r.differences); o.put('\t');
+        o.num(r.unshared);
         o.put('\n');
     }
     return o.n;
@@ -597,12 +602,12 @@ extern "C" int64_t kp_format_clusters(const char *locus_name, int32_t locus_name
         const kp_dist_nearest &nr = nearest[r];
         put_locus(o, locus_name, locus_name_len); o.put('\t');
         t.put(o, r); o.put('\t');
-        for (int32_t k = 0; k < n_levels; ++k) { put_i(o, number[(size_t)k * (size_t)n_names + (size_t)r]); o.put('\t'); }
+        for (int32_t k = 0; k < n_levels; ++k) { o.num(number[(size_t)k * (size_t)n_names + (size_t)r]); o.put('\t'); }
         if (nr.row >= 0) {
             t.put(o, nr.row); o.put('\t');
-            put_i(o, nr.differences); o.put('\t');
-            put_i(o, nr.compared); o.put('\t');
-            put_i(o, nr.unshared);
+            o.num(nr.differences); o.put('\t');
+            o.num(nr.compared); o.put('\t');
+            o.num(nr.unshared);
         } else {
             o.lit(".\t.\t.\t.");
         }
@@ -674,8 +679,8 @@ extern "C" int64_t kp_format_newick(const char *locus_name, int32_t locus_name_l
     for (int32_t root = 0; root < R; ++root) {
         if (component[root] != root) continue;
         put_locus(o, locus_name, locus_name_len); o.put('\t');
-        put_i(o, ++tree); o.put('\t');
-        put_i(o, size[(size_t)root]); o.put('\t');
+        o.num(++tree); o.put('\t');
+        o.num(size[(size_t)root]); o.put('\t');
         stack.push_back(Frame{root, -1, 0, first[(size_t)root], false});
         while (!stack.empty()) {
             Frame &f = stack.back();
@@ -694,7 +699,7 @@ extern "C" int64_t kp_format_newick(const char *locus_name, int32_t locus_name_l
             const bool is_root = f.from < 0;
             const int32_t length = f.length;
             stack.pop_back();
-            if (!is_root) { o.put(':'); put_i(o, length); }
+            if (!is_root) { o.put(':'); o.num(length); }
         }
         o.lit(";\n");
     }
@@ -731,13 +736,13 @@ extern "C" int64_t kp_format_sites(const char *locus_name, int32_t locus_name_le
         if (s.n_n < 0 || held > n_rows || kp_site_alleles(s.n) < 2) return KP_EINVAL;
         put_locus(o, locus_name, locus_name_len); o.put('\t');
         t.put(o, g); o.put('\t');
-        put_i(o, pos + 1); o.put('\t');
-        put_i(o, before[(size_t)g] + pos + 1); o.put('\t');
-        put_i(o, n_rows); o.put('\t');
-        for (int k = 0; k < 4; ++k) { put_i(o, s.n[k]); o.put('\t'); }
-        put_i(o, s.n_n); o.put('\t');
-        put_i(o, kp_site_gap(s.n, s.n_n, n_rows)); o.put('\t');
-        put_i(o, kp_site_alleles(s.n)); o.put('\t');
+        o.num(pos + 1); o.put('\t');
+        o.num(before[(size_t)g] + pos + 1); o.put('\t');
+        o.num(n_rows); o.put('\t');
+        for (int k = 0; k < 4; ++k) { o.num(s.n[k]); o.put('\t'); }
+        o.num(s.n_n); o.put('\t');
+        o.num(kp_site_gap(s.n, s.n_n, n_rows)); o.put('\t');
+        o.num(kp_site_alleles(s.n)); o.put('\t');
         o.put("acgt"[kp_site_major(s.n)]); o.put('\t');
         o.lit(kp_site_informative(s.n) ? "yes" : "no");
         o.put('\n');
@@ -758,19 +763,12 @@ extern "C" int64_t kp_format_site_rows(const char *locus_name, int32_t locus_nam
     for (int32_t r = 0; r < n_names; ++r) {
         put_locus(o, locus_name, locus_name_len); o.put('\t');
         t.put(o, r); o.put('\t');
-        put_i(o, n_sites); o.put('\t');
+        o.num(n_sites); o.put('\t');
         for (int64_t b = 0; b < SB; ++b) {
             const uint64_t v = blocks[(size_t)r * (size_t)SB + (size_t)b];
-            const uint32_t m = (uint32_t)(v >> KP_DIST_N_SHIFT) & 0xffffu, g = (uint32_t)(v >> KP_DIST_GAP_SHIFT) & 0xffffu;
-            if (m & g) return KP_EINVAL;
-            for (int k = 0; k < KP_SITES_BLOCK; ++k) {
-                const bool gap = (g >> k) & 1u;
-                if (b * KP_SITES_BLOCK + k >= n_sites) {
-                    if (!gap) return KP_EINVAL;  // (padding is flagged)
-                    continue;
-                }
-                o.put(gap ? '-' : ((m >> k) & 1u) ? 'n' : "acgt"[(v >> (2 * k)) & 3u]);
-            }
+            const uint64_t pad = b == SB - 1 ? kp_dist_pad_mask(n_sites) : 0ull;  // (padding is flagged as gap)
+            if (((v >> KP_DIST_N_SHIFT) & (v >> KP_DIST_GAP_SHIFT) & 0xffffu) || (v & pad) != pad) return KP_EINVAL;  // (N and gap never both)
+            put_block_text(o, v, (int)std::min<int64_t>(KP_SITES_BLOCK, n_sites - b * KP_SITES_BLOCK));
         }
         o.put('\n');
     }
