@@ -242,7 +242,7 @@ def load_database(path: str):
 
 
 class _TypingPipeline:
-    """One device's share of ``kaptive assembly``: files -> reader pool -> pinned shard -> ``Engine.type_stream`` -> bytes.
+    """One device's share of ``kaptive assembly``: files -> reader pool -> pinned shard -> the engine's typing window -> bytes.
 
     The stages run beside each other: while the GPU types chunk k, the reader threads parse and pack chunk k + 1 .. k + 2
     (``kp_fasta_ingest`` releases the interpreter lock), their packed words are copied into page-locked memory and
@@ -354,8 +354,12 @@ class _TypingPipeline:
                 self.engine.ctx.set_option("cs", 1)
         self.marks["context_ready"] = time.perf_counter()
         self.want_tsv = bool(getattr(args, "out", None))
-        # several databases: every chunk's outputs are ((keyword, outputs), ...), one entry per database in order
-        self.keywords = tuple(t._db.metadata.keyword for t in typer.serotypers) if isinstance(typer, MultiSerotyper) else None
+        # A run is one typing group per database, and a run without --db is a run with one: every chunk's outputs are
+        # ((keyword, outputs), ...), one entry per database in order, and the keyword of the one database of a plain run is None
+        # (its files are named as given).  A Serotyper of a MultiSerotyper types the group its engine views.
+        several = isinstance(typer, MultiSerotyper)
+        self.typers = tuple(typer.serotypers) if several else (typer,)
+        self.keywords = tuple(t._db.metadata.keyword for t in self.typers) if several else (None,)
 
     def _abandon_reads(self) -> None:
         """Cancel every queued read, drop what finished reads hold (shards' page-locked blocks), keep no worker waiting."""
@@ -503,23 +507,24 @@ class _TypingPipeline:
         return batch
 
     def _source(self, chunks):
-        """(batch, ids, genomes) per chunk, as an iterator with ``ready()`` (``Engine.type_stream`` asks before it would
+        """(batch, ids, genomes) per chunk, as an iterator with ``ready()`` (the engine's typing window asks before it would
         wait): the files of the next PREFETCH chunks are being read while a chunk is handed on; their batches are created
         (uploads enqueued) as soon as the reads are through."""
         return _ChunkSource(self, chunks)
 
     # -- stage 3: records -> bytes ------------------------------------------------------------------------------------------------
     def run(self, chunks):
-        """Yields ``(k, outputs)`` for every ``(k, paths)`` of ``chunks``, in order; ``outputs`` maps "tsv" / "pha4ge" /
-        "json" to the bytes this chunk adds to that stream (per-assembly fasta files are written here).  With several
-        databases ``outputs`` is ``((keyword, that mapping), ...)``, one entry per database in order, and the fasta files of
-        a database go to ``DIR/<keyword>/``."""
+        """Yields ``(k, ((keyword, outputs), ...))`` for every ``(k, paths)`` of ``chunks``, in order: one entry per database
+        in order (``self.keywords``), where ``outputs`` maps "tsv" / "pha4ge" / "json" / ... to the bytes this chunk adds to that
+        database's stream.  Per-assembly fasta files are written here: to ``DIR/<keyword>/``, or to ``DIR`` itself for the
+        keyword ``None`` of a run without ``--db``."""
         from collections import deque
 
         args = self.args
         self._order = []
+        groups = tuple(t.engine.group for t in self.typers)  # (a MultiSerotyper's typers view the shared engine, one group each)
 
-        def render(bt, keyword=None, aligned=None, group=0) -> dict:
+        def render(bt, keyword, group, aligned) -> dict:
             out = {}
             if aligned is not None:
                 out["paf"] = hits_to_paf(self.engine.view(group), bt.genomes, *aligned, cs_tag=self.paf_cs, eqx=self.paf_eqx)
@@ -552,25 +557,17 @@ class _TypingPipeline:
         # of JSON per 512 assemblies would otherwise stand between two submissions to the device); they leave in input order.
         rendering: deque = deque()
         done = 0
-        if self.keywords is None:
-            stream = self.engine.type_stream(self.typer, self._source(chunks))
 
-            def job(bt, aligned=None) -> dict:
-                return render(bt, None, aligned)
-        else:  # every database's records from the one alignment pass of the batch, rendered by the same formatters
-            kws = self.keywords
-            stream = self.engine.type_stream_groups(self.typer.serotypers, self._source(chunks))
+        def job(bts, aligned) -> tuple:  # every database's records from the one alignment pass of the batch
+            return tuple((kw, render(bt, kw, g, aligned)) for kw, g, bt in zip(self.keywords, groups, bts))
 
-            def job(bts, aligned=None) -> tuple:
-                return tuple((kw, render(bt, kw, aligned, g)) for g, (kw, bt) in enumerate(zip(kws, bts)))
-
-        for bt, batch in stream:
+        for bts, batch in self.engine._window(self.typers, groups, self._source(chunks)):
             pb, batch._pin = getattr(batch, "_pin", None), None
             aligned = (*batch.hits(), *batch.cigars(), *(batch.cs() if self.paf_cs or self.paf_eqx else ())) if self.want_paf else None  # (the batch's results go with it)
             batch.close()  # (waits for whatever of the batch is still in flight: the pinned words are free after it)
             if pb is not None:
                 self._give_back(pb)
-            rendering.append(self.formatters.submit(job, bt, aligned))
+            rendering.append(self.formatters.submit(job, bts, aligned))
             while rendering and (rendering[0].done() or len(rendering) > 2):
                 yield self._order[done], rendering.popleft().result()
                 done += 1
@@ -691,16 +688,13 @@ class _RunDistances:
         several = bool(getattr(self.args, "db", None))
         self.rows = [(db.metadata.keyword if several else None, LocusRows(db)) for db in dbs]
 
-    def take(self, out, dbs=None) -> None:
-        """Removes the payload(s) from one chunk's outputs and merges them.  ``dbs``: the run's databases, where somebody has them
-        loaded already (the single-device pipeline); otherwise they are read from the command line's paths on first use."""
+    def take(self, outs, dbs=None) -> None:
+        """Removes every database's payload from one chunk's outputs and merges it.  ``dbs``: the run's databases, where somebody has
+        them loaded already (the single-device pipeline); otherwise they are read from the command line's paths on first use."""
         if self.rows is None:
             self._start(dbs if dbs is not None else [load_database(p) for p in (self.args.database, *(getattr(self.args, "db", None) or []))])
-        if isinstance(out, dict):
-            self.rows[0][1].merge(out.pop(LOCUS_ROWS_KEY))
-        else:
-            for (_, rows), (_, o) in zip(self.rows, out):
-                rows.merge(o.pop(LOCUS_ROWS_KEY))
+        for (_, rows), (_, out) in zip(self.rows, outs):
+            rows.merge(out.pop(LOCUS_ROWS_KEY))
 
     def write(self, ctx) -> None:
         from kaptive_amd import _native
@@ -835,26 +829,29 @@ def _batch_outputs() -> tuple:
 
 
 class _PerDatabaseOutputs:
-    """The TSV / PHA4GE / JSON reports of a run with several databases: a file per database and report
-    (``per_database_path``), each with its own header line; a report on stdout gets one header and the databases' lines
-    genome by genome (``interleave_lines``).  The files are opened with the first chunk's outputs, which carry the
-    databases' keywords."""
+    """Where the bytes of a run's chunks go (``_batch_outputs``): a file per database and report, each with its own header line;
+    a report on stdout gets one header and the databases' lines genome by genome (``interleave_lines``: of one database, its
+    block as it is).  A run without ``--db`` has one database, whose keyword is ``None``: its files are named as given, and they
+    are opened -- headers written -- here, before anything is typed.  With ``--db`` the files are named by keyword
+    (``per_database_path``) and opened with the first chunk's outputs, which carry the keywords."""
 
     def __init__(self, args: argparse.Namespace) -> None:
         self.wanted = [(key, path, header) for key, attr, header in _batch_outputs() if (path := getattr(args, attr, None))]
-        self.streams: "dict | None" = None  # key -> one handle per database, or the shared stdout
+        self.streams: "dict | None" = None  # key -> one file per database, or None for stdout
         self.files: list = []
+        if not getattr(args, "db", None):
+            self._open((None,))
 
     def _open(self, keywords) -> None:
         self.streams = {}
         for key, path, header in self.wanted:
             if _is_stdout(path):
                 sys.stdout.buffer.write(header)
-                self.streams[key] = sys.stdout.buffer
+                self.streams[key] = None
                 continue
             self.streams[key] = []
             for kw in keywords:
-                h = open(per_database_path(path, kw), "wb")
+                h = open(path if kw is None else per_database_path(path, kw), "wb")
                 self.files.append(h)
                 h.write(header)
                 self.streams[key].append(h)
@@ -863,17 +860,19 @@ class _PerDatabaseOutputs:
         """``outs``: ``((keyword, {key: bytes}), ...)`` of one chunk, one entry per database in order."""
         if self.streams is None:
             self._open([kw for kw, _ in outs])
-        for key, target in self.streams.items():
-            if isinstance(target, list):
-                for h, (_, out) in zip(target, outs):
-                    h.write(out[key])
-            else:
-                target.write(interleave_lines([out[key] for _, out in outs]))
+        for key in outs[0][1]:  # (in the order the chunk was rendered)
+            if key in self.streams:
+                blocks = [out[key] for _, out in outs]
+                if self.streams[key] is None:
+                    sys.stdout.buffer.write(interleave_lines(blocks))
+                else:
+                    for h, block in zip(self.streams[key], blocks):
+                        h.write(block)
 
     def close(self) -> None:
         for h in self.files:
             h.close()
-        if self.streams and any(not isinstance(t, list) for t in self.streams.values()):
+        if self.streams and None in self.streams.values():
             sys.stdout.buffer.flush()
 
 
@@ -912,30 +911,16 @@ def run_type(args: argparse.Namespace) -> int:
             raise ValueError(f"--{flag.replace('_', '-')} with --db writes a table per database: it needs a file name, not stdout")
     dist = _RunDistances(args) if any(getattr(args, f, None) for f in PAIR_TABLES) else None
     run_dbs = None  # the databases of the run, where this process has loaded them (one device)
-    handles = {}
-    per_db = _PerDatabaseOutputs(args) if getattr(args, "db", None) else None  # several databases: reports per database
-
-    def stream(path):
-        return sys.stdout.buffer if _is_stdout(path) else open(path, "wb")
-
-    if per_db is None:
-        for key, attr, header in _batch_outputs():
-            if path := getattr(args, attr, None):
-                handles[key] = stream(path)
-                handles[key].write(header)
+    outputs = _PerDatabaseOutputs(args)  # (without --db its files are open, headers written, from here on)
     done = 0
     timing_path = os.environ.get("KAPTIVE_AMD_CLI_TIMING")  # bench.py: when each chunk's rows were written
     t_start, chunk_times, phases = time.perf_counter(), [], {}
 
-    def write(out, n):
+    def write(outs, n):
         nonlocal done
         if dist is not None:
-            dist.take(out, run_dbs)
-        if per_db is not None:
-            per_db.write(out)
-        else:
-            for key, blob in out.items():
-                handles[key].write(blob)
+            dist.take(outs, run_dbs)
+        outputs.write(outs)
         done += n
         chunk_times.append((done, time.perf_counter() - t_start))
         if args.verbose:
@@ -945,7 +930,7 @@ def run_type(args: argparse.Namespace) -> int:
         if len(devices) == 1:
             pipe = _TypingPipeline(args, devices[0], chunks=chunks)
             try:
-                run_dbs = [t._db for t in pipe.typer.serotypers] if pipe.keywords is not None else [pipe.typer._db]
+                run_dbs = [t._db for t in pipe.typers]
                 for k, out in pipe.run(chunks):
                     write(out, len(chunks[k][1]))
                 if dist is not None:  # after the last chunk, on the pipeline's own context
@@ -1015,13 +1000,7 @@ def run_type(args: argparse.Namespace) -> int:
                 finally:
                     dctx.close()
     finally:
-        for h in handles.values():
-            if h is not sys.stdout.buffer:
-                h.close()
-            else:
-                h.flush()
-        if per_db is not None:
-            per_db.close()
+        outputs.close()
     if FAST_EXIT:
         # every stream this command writes is closed or flushed: what is left (reader threads, page-locked shards, the device
         # context) may leave with the process.  Other subcommands, and a run that raised, end through the interpreter.

@@ -186,192 +186,131 @@ class Engine:
             typer.locus_rows.add(bt)
         return bt
 
-    def type_batch(self, typer, batch, ids: Sequence[str], genomes: Sequence[GenomeAssembly] | None = None,
-                   aligned: bool = False):
-        """Whole typing of a resident batch: alignment and reduction on the device, the numpy float steps, and the
-        per-assembly decisions as columns.  Returns a ``BatchTyping``; ``.results()`` / ``.rows()`` materialise objects
-        and TSV lines.  ``genomes`` (optional) lets the result objects carry the extracted sequences; ``aligned`` says
-        that ``batch.align_async()`` has already been enqueued."""
+    # -- typing: one stage step, one window ----------------------------------------------------------------------------------
+    # A single database is one typing group: every entry point below goes over ``[(group, typer, params)]``.
+    def _groups(self, typers: Sequence, groups: Sequence[int]) -> list:
+        return [(g, t, self.view(g).typing_params(t)) for g, t in zip(groups, typers)]
+
+    def _scores(self, batch, groups: list) -> list:
+        """``(scores, best loci)`` of every group, in group order (numpy argmax: part of the bit-exact contract)."""
         from kaptive_amd.serotyping import batch as B
 
-        if not aligned:
-            batch.align_async()
-        scores, counts = batch.score(typer.min_gene_coverage, self.group)
-        best, _, _ = B.choose_best_loci(scores, counts, typer._expected_genes_per_locus)
-        batch.reduce_async(best, self.typing_params(typer), self.group)
-        return self._collect(typer, batch, ids, scores, best, genomes)
-
-    def type_batches(self, typer, batches: Sequence, ids: Sequence[Sequence[str]], aligned: bool = False) -> list:
-        """Any number of resident batches through the same context, software-pipelined as a sliding window.
-
-        A context keeps the results of its ``_native.WORK_SLOTS`` most recent alignment passes (the work sets rotate
-        at ``kp_batch_align``), so at most that many batches are between "alignment enqueued" and "records
-        collected" at any time: batch i's scores are read and its reduction enqueued, then batch i-1's records are
-        collected (its reduction ran while i was being scored), and alignment passes are enqueued ahead only as far
-        as the free work sets allow.  The stream never waits for the host and no pass is displaced before it was
-        read.  ``aligned=True`` (the caller already enqueued every pass) is only possible for up to WORK_SLOTS batches."""
-        from kaptive_amd.serotyping import batch as B
-
-        n, depth = len(batches), _native.WORK_SLOTS
-        if aligned and n > depth:
-            raise ValueError(f"{n} batches were aligned up front but a context keeps only {depth} alignment results "
-                             "(WORK_SLOTS); pass aligned=False and let type_batches schedule the passes")  # fmt: skip
-        out: list = []
-        enqueued = n if aligned else 0
-        pending = None  # (index, scores, best) of the batch whose reduction is enqueued but not yet collected
-
-        def collect(item) -> None:
-            i, scores, best = item
-            out.append(self._collect(typer, batches[i], ids[i], scores, best))
-
-        for i in range(n):
-            first_live = pending[0] if pending is not None else i
-            while enqueued < n and enqueued < first_live + depth:
-                batches[enqueued].align_async()
-                enqueued += 1
-            scores, counts = batches[i].score(typer.min_gene_coverage, self.group)
+        staged = []
+        for g, typer, _ in groups:
+            scores, counts = batch.score(typer.min_gene_coverage, g)
             best, _, _ = B.choose_best_loci(scores, counts, typer._expected_genes_per_locus)
-            batches[i].reduce_async(best, self.typing_params(typer), self.group)
-            if pending is not None:
-                collect(pending)
-            pending = (i, scores, best)
-        if pending is not None:
-            collect(pending)
-        return out
+            staged.append((scores, best))
+        return staged
 
-    def type_stream(self, typer, source):
-        """``type_batches`` for a stream whose length is not known in advance (the CLI: batches are made while files are
-        still being read).  ``source`` yields ``(batch, ids, genomes_or_None)``; what comes out, in the same order, is
-        ``(BatchTyping, batch)`` -- the caller closes the batch.  Same sliding window: at most ``_native.WORK_SLOTS``
-        batches are between "alignment enqueued" and "records collected", the next batch is only pulled from ``source``
-        (created and uploaded) when a work set is free for it, and batch i's records are collected after batch i + 1's
-        reduction has been enqueued -- or at once, when the source has no further batch ready yet."""
+    def _stage(self, batch, groups: list, staged: "list | None" = None) -> list:
+        """The stage step of an aligned batch: the scores of every group are read back and its best loci chosen, then every
+        group's reduction is enqueued -- in that order, so that no database's scores queue up behind another one's reduction
+        kernels.  ``staged``: the scores, where the caller has read them already (``score_batches``)."""
+        if staged is None:
+            staged = self._scores(batch, groups)
+        for (g, _, params), (_, best) in zip(groups, staged):
+            batch.reduce_async(best, params, g)
+        return staged
+
+    def _window(self, typers: Sequence, groups: Sequence[int], source, align: bool = True, own: bool = True):
+        """The typing window: ``source`` yields ``(batch, ids, genomes_or_None)``; what comes out, in the same order, is
+        ``(tuple of one BatchTyping per group, batch)``.
+
+        A context keeps the results of its ``_native.WORK_SLOTS`` most recent alignment passes (the work sets rotate at
+        ``kp_batch_align``), so at most that many batches are between "alignment enqueued" and "records collected" at any
+        time: the next batch is only pulled from ``source`` (created, uploaded, its pass enqueued) when a work set is free for
+        it, the oldest aligned batch goes through the stage step, and then the batch before it is collected (its reduction ran
+        while this one was being scored) -- or at once, when nothing is waiting.  The stream never waits for the host and no
+        pass is displaced before it was read.
+
+        A source may say whether its next item can be had without waiting (``ready()``: the CLI's reader pipeline): the window
+        is then only topped up with what is there, and the driver waits for the source only when it has nothing else to do --
+        the first chunk's rows leave as soon as its reduction is through, not after two more chunks were read.
+
+        ``align=False``: the caller has enqueued every pass.  ``own``: what is still in the window on the way out (the source
+        ran dry, an error, a consumer that stopped early) is closed before the context goes, waiting batches first; what was
+        handed on is the caller's to close."""
         from collections import deque
 
-        from kaptive_amd.serotyping import batch as B
-
+        groups = self._groups(typers, groups)
         depth = _native.WORK_SLOTS
         it = iter(source)
-        live: deque = deque()  # aligned, not yet scored
-        pending = None  # reduction enqueued, records not yet collected
-        exhausted = False
-
-        def collect(item):
-            batch, ids, genomes, scores, best = item
-            return self._collect(typer, batch, ids, scores, best, genomes), batch
-
-        # A source may say whether its next item can be had without waiting (``ready()``: the CLI's reader pipeline): the
-        # window is then only topped up with what is there, and the driver waits for the source only when it has nothing
-        # else to do -- the first chunk's rows leave as soon as its reduction is through, not after two more chunks were read.
         can_pull = getattr(source, "ready", None)
-
-        def fill_ready() -> None:
-            nonlocal exhausted
-            while not exhausted and len(live) + (1 if pending is not None else 0) < depth:
-                if can_pull is not None and (live or pending is not None) and not can_pull():
-                    return
-                try:
-                    item = next(it)
-                except StopIteration:
-                    exhausted = True
-                    return
-                item[0].align_async()
-                live.append(item)
-
-        try:
-            while True:
-                fill_ready()
-                if live:
-                    batch, ids, genomes = live.popleft()
-                    scores, counts = batch.score(typer.min_gene_coverage, self.group)
-                    best, _, _ = B.choose_best_loci(scores, counts, typer._expected_genes_per_locus)
-                    batch.reduce_async(best, self.typing_params(typer), self.group)
-                    if pending is not None:
-                        done, pending = pending, None
-                        yield collect(done)
-                    pending = (batch, ids, genomes, scores, best)
-                elif pending is not None:
-                    done, pending = pending, None
-                    yield collect(done)
-                elif exhausted:
-                    break
-        finally:  # (an error, or a consumer that stopped early: whatever is still in the window is closed before the context goes)
-            for item in list(live) + ([pending] if pending is not None else []):
-                try:
-                    item[0].close()
-                except Exception:  # noqa: BLE001
-                    pass
-
-    def type_stream_groups(self, typers: Sequence, source):
-        """``type_stream`` for every typing group at once: ``typers[g]`` types database ``g`` of this engine (one per
-        database, in order).  Same sliding window and the same ``source``; what comes out, in order, is
-        ``(tuple of one BatchTyping per group, batch)`` -- the caller closes the batch.  Every batch is aligned once; then
-        the scores of all groups are read back and their best loci chosen, all groups' reductions are enqueued, and only
-        then are the previous batch's records collected (``score_batches``: no database's scores queue up behind another
-        one's reduction)."""
-        from collections import deque
-
-        from kaptive_amd.serotyping import batch as B
-
-        typers = tuple(typers)
-        if len(typers) != len(self.dbs):
-            raise ValueError(f"{len(typers)} typers for an engine of {len(self.dbs)} databases: one per database, in order")
-        params = [self.view(g).typing_params(t) for g, t in enumerate(typers)]
-        depth = _native.WORK_SLOTS
-        it = iter(source)
         live: deque = deque()  # aligned, not yet scored
         pending = None  # reductions enqueued, records not yet collected
         exhausted = False
 
         def collect(item):
             batch, ids, genomes, staged = item
-            out = []
-            for g, (typer, (scores, best)) in enumerate(zip(typers, staged)):
-                out.append(self._collect(typer, batch, ids, scores, best, genomes, g))
-            return tuple(out), batch
-
-        can_pull = getattr(source, "ready", None)
-
-        def fill_ready() -> None:
-            nonlocal exhausted
-            while not exhausted and len(live) + (1 if pending is not None else 0) < depth:
-                if can_pull is not None and (live or pending is not None) and not can_pull():
-                    return
-                try:
-                    item = next(it)
-                except StopIteration:
-                    exhausted = True
-                    return
-                item[0].align_async()
-                live.append(item)
+            return tuple(self._collect(t, batch, ids, scores, best, genomes, g) for (g, t, _), (scores, best) in zip(groups, staged)), batch
 
         try:
-            while True:
-                fill_ready()
+            while live or pending is not None or not exhausted:
+                while not exhausted and len(live) + (pending is not None) < depth:
+                    if can_pull is not None and (live or pending is not None) and not can_pull():
+                        break
+                    item = next(it, None)
+                    if item is None:
+                        exhausted = True
+                        break
+                    if align:
+                        item[0].align_async()
+                    live.append(item)
+                reduced = None
                 if live:
                     batch, ids, genomes = live.popleft()
-                    staged = []
-                    for g, typer in enumerate(typers):
-                        scores, counts = batch.score(typer.min_gene_coverage, g)
-                        best, _, _ = B.choose_best_loci(scores, counts, typer._expected_genes_per_locus)
-                        staged.append((scores, best))
-                    for g, (_, best) in enumerate(staged):
-                        batch.reduce_async(best, params[g], g)
-                    if pending is not None:
-                        done, pending = pending, None
-                        yield collect(done)
-                    pending = (batch, ids, genomes, staged)
-                elif pending is not None:
-                    done, pending = pending, None
+                    reduced = (batch, ids, genomes, self._stage(batch, groups))
+                done, pending = pending, None  # (handed on: no longer the window's)
+                if done is not None:
                     yield collect(done)
-                elif exhausted:
-                    break
-        finally:  # (as in type_stream: what is still in the window is closed before the context goes)
-            for item in list(live) + ([pending] if pending is not None else []):
-                try:
-                    item[0].close()
-                except Exception:  # noqa: BLE001
-                    pass
+                pending = reduced
+        finally:
+            if own:
+                for item in (*live, *([pending] if pending is not None else ())):
+                    try:
+                        item[0].close()
+                    except Exception:  # noqa: BLE001
+                        pass
+
+    def type_batch(self, typer, batch, ids: Sequence[str], genomes: Sequence[GenomeAssembly] | None = None,
+                   aligned: bool = False):
+        """Whole typing of a resident batch: alignment and reduction on the device, the numpy float steps, and the
+        per-assembly decisions as columns.  Returns a ``BatchTyping``; ``.results()`` / ``.rows()`` materialise objects
+        and TSV lines.  ``genomes`` (optional) lets the result objects carry the extracted sequences; ``aligned`` says
+        that ``batch.align_async()`` has already been enqueued."""
+        if not aligned:
+            batch.align_async()
+        ((scores, best),) = self._stage(batch, self._groups([typer], [self.group]))
+        return self._collect(typer, batch, ids, scores, best, genomes)
+
+    def type_batches(self, typer, batches: Sequence, ids: Sequence[Sequence[str]], aligned: bool = False) -> list:
+        """Any number of resident batches through the same context, software-pipelined by the typing window (``_window``);
+        the batches stay the caller's.  ``aligned=True`` (the caller already enqueued every pass) is only possible for up to
+        WORK_SLOTS batches."""
+        if aligned and len(batches) > _native.WORK_SLOTS:
+            raise ValueError(f"{len(batches)} batches were aligned up front but a context keeps only {_native.WORK_SLOTS} alignment results "
+                             "(WORK_SLOTS); pass aligned=False and let type_batches schedule the passes")  # fmt: skip
+        source = ((b, i, None) for b, i in zip(batches, ids))
+        return [bts[0] for bts, _ in self._window([typer], [self.group], source, align=not aligned, own=False)]
+
+    def type_stream(self, typer, source):
+        """The typing window for a stream whose length is not known in advance (the CLI: batches are made while files are
+        still being read).  ``source`` yields ``(batch, ids, genomes_or_None)``; what comes out, in the same order, is
+        ``(BatchTyping, batch)`` -- the caller closes the batch."""
+        from contextlib import closing
+
+        with closing(self._window([typer], [self.group], source)) as window:  # (a consumer that stops early ends the window too)
+            for (bt,), batch in window:
+                yield bt, batch
+
+    def type_stream_groups(self, typers: Sequence, source):
+        """The typing window for every typing group at once: ``typers[g]`` types database ``g`` of this engine (one per
+        database, in order).  What comes out, in order, is ``(tuple of one BatchTyping per group, batch)`` -- the caller closes
+        the batch.  Every batch is aligned once."""
+        typers = tuple(typers)
+        if len(typers) != len(self.dbs):
+            raise ValueError(f"{len(typers)} typers for an engine of {len(self.dbs)} databases: one per database, in order")
+        yield from self._window(typers, range(len(typers)), source)
 
     def reduce_batches(self, typer, batches: Sequence, aligned: bool = False) -> list:
         """Scores back, best loci chosen (numpy), reductions enqueued, for up to WORK_SLOTS batches at once.  Returns what
@@ -386,29 +325,19 @@ class Engine:
         return self.enqueue_reductions(typer, batches, self.score_batches(typer, batches))
 
     def score_batches(self, typer, batches: Sequence) -> list:
-        """Locus scores of every batch read back and the best loci chosen (numpy argmax: part of the bit-exact
-        contract).  Cheap on the device; callers with several databases score all of them before any reduction is
-        enqueued, so that no database's scores queue up behind another one's reduction kernels."""
-        from kaptive_amd.serotyping import batch as B
-
-        staged = []
-        for b in batches:
-            scores, counts = b.score(typer.min_gene_coverage, self.group)
-            best, _, _ = B.choose_best_loci(scores, counts, typer._expected_genes_per_locus)
-            staged.append((scores, best))
-        return staged
+        """Locus scores of every batch read back and the best loci chosen.  Cheap on the device; callers with several
+        engines score all of them before any reduction is enqueued, as the stage step does for the groups of one."""
+        return [self._scores(b, [(self.group, typer, None)])[0] for b in batches]  # (scores need no typing parameters)
 
     def enqueue_reductions(self, typer, batches: Sequence, staged: list) -> list:
-        for b, (_, best) in zip(batches, staged):
-            b.reduce_async(best, self.typing_params(typer), self.group)
+        groups = self._groups([typer], [self.group])
+        for b, s in zip(batches, staged):
+            self._stage(b, groups, [s])
         return staged
 
     def collect_batches(self, typer, batches: Sequence, ids: Sequence[Sequence[str]], staged: list) -> list:
         """Second half: fetch the reduction records and finish them column-wise (``BatchTyping``)."""
-        out = []
-        for b, i, (scores, best) in zip(batches, ids, staged):
-            out.append(self._collect(typer, b, i, scores, best))
-        return out
+        return [self._collect(typer, b, i, scores, best) for b, i, (scores, best) in zip(batches, ids, staged)]
 
     def type_many(self, typer, genomes: Sequence[GenomeAssembly]) -> list:
         """One device submission for all genomes: alignment and reduction both run on the GPU."""

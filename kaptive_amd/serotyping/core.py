@@ -110,13 +110,7 @@ class Serotyper:
     def engine(self):
         """Lazily created HIP context with this database resident on the device."""
         if self._engine is None:
-            from kaptive_amd.engine import Engine
-
-            early = getattr(self, "_ctx_early", None)  # (a future of _native.Context: kaptive_amd/cli.py starts the runtime early)
-            self._ctx_early = None
-            self._engine = Engine(self._db, device=self._device, ctx=early.result() if early is not None else None, variants=self._variants,
-                                  breakpoints=self._breakpoints, alleles=self._alleles, aligned=self._aligned, rescue=self._rescue,
-                                  rescue_flank=self._rescue_flank)
+            self._engine = _make_engine(self, self._db)
         return self._engine
 
     def align(self, genome: GenomeAssembly) -> Alignments:
@@ -156,19 +150,11 @@ class Serotyper:
         src/kaptive/serotyping/cli.py:183-210): FASTA files -> chunks of ``batch_size`` parsed by the library's threads ->
         pinned shards -> the batched typing -> the ``KaptiveRow`` bytes of every chunk, in input order, without a Python
         object per assembly.  Yields one ``bytes`` per chunk (no header line: ``KaptiveRow.header()``)."""
-        import argparse
+        from contextlib import closing
 
-        from kaptive_amd.cli import _TypingPipeline
-
-        args = argparse.Namespace(out="-", threads=threads, json=None, loci=None, genes=None, proteins=None, pha4ge=None)
-        paths = [str(p) for p in paths]
-        chunks = [(k, paths[i : i + batch_size]) for k, i in enumerate(range(0, len(paths), batch_size))]
-        pipe = _TypingPipeline(args, 0, typer=self)  # (the device is the one this Serotyper was made for)
-        try:
-            for _, out in pipe.run(chunks):
-                yield out["tsv"]
-        finally:
-            pipe.close()
+        with closing(_tsv_chunks(self, paths, batch_size, threads)) as chunks:
+            for (rows,) in chunks:
+                yield rows
 
     # -- reduction ------------------------------------------------------------------------------------------------
     def score_loci(self, alns: Alignments, gene_idx: np.ndarray) -> tuple[np.ndarray, np.ndarray, int]:
@@ -398,6 +384,35 @@ class Serotyper:
         return name
 
 
+def _make_engine(typer, db):
+    """The engine of a ``Serotyper`` (``db``: its database) or a ``MultiSerotyper`` (its databases), made for the reports the typer
+    was made for -- on the context the command line started early, where it did (``_ctx_early``: a future of
+    ``_native.Context``, kaptive_amd/cli.py)."""
+    from kaptive_amd.engine import Engine
+
+    early, typer._ctx_early = getattr(typer, "_ctx_early", None), None
+    return Engine(db, device=typer._device, ctx=early.result() if early is not None else None, variants=typer._variants,
+                  breakpoints=typer._breakpoints, alleles=typer._alleles, aligned=typer._aligned, rescue=typer._rescue,
+                  rescue_flank=typer._rescue_flank)  # fmt: skip
+
+
+def _tsv_chunks(typer, paths: Sequence[str | Path], batch_size: int, threads: int) -> "Iterator[tuple[bytes, ...]]":
+    """``tsv_from_files`` of a ``Serotyper`` or a ``MultiSerotyper``: per chunk, one block of ``KaptiveRow`` bytes per database."""
+    import argparse
+
+    from kaptive_amd.cli import _TypingPipeline
+
+    args = argparse.Namespace(out="-", threads=threads, json=None, loci=None, genes=None, proteins=None, pha4ge=None)
+    paths = [str(p) for p in paths]
+    chunks = [(k, paths[i : i + batch_size]) for k, i in enumerate(range(0, len(paths), batch_size))]
+    pipe = _TypingPipeline(args, typer._device, typer=typer)  # (the device is the one the typer was made for)
+    try:
+        for _, outs in pipe.run(chunks):
+            yield tuple(out["tsv"] for _, out in outs)
+    finally:
+        pipe.close()
+
+
 def check_databases(dbs: Sequence[Database]) -> None:
     """What one context can type together, checked before it is created: distinct keywords (each database's outputs are
     named by its keyword), at most ``KP_MAX_TYPING_GROUPS`` databases and ``KP_MAX_GENES`` genes in all.  Raises
@@ -466,13 +481,7 @@ class MultiSerotyper:
     def engine(self):
         """The shared engine (one context); each of ``.serotypers`` is given its database's view of it."""
         if self._engine is None:
-            from kaptive_amd.engine import Engine
-
-            early = getattr(self, "_ctx_early", None)  # (as Serotyper.engine: a context the command line started early)
-            self._ctx_early = None
-            self._engine = Engine(self.dbs, device=self._device, ctx=early.result() if early is not None else None, variants=self._variants,
-                                  breakpoints=self._breakpoints, alleles=self._alleles, aligned=self._aligned, rescue=self._rescue,
-                                  rescue_flank=self._rescue_flank)
+            self._engine = _make_engine(self, self.dbs)
             for i, s in enumerate(self.serotypers):
                 s._engine = self._engine.view(i)
         return self._engine
@@ -502,16 +511,4 @@ class MultiSerotyper:
     def tsv_from_files(self, paths: Sequence[str | Path], batch_size: int = 512, threads: int = 0) -> "Iterator[tuple[bytes, ...]]":
         """``Serotyper.tsv_from_files`` for every database in one pass: per chunk, a tuple of one block of ``KaptiveRow``
         bytes per database (no header lines)."""
-        import argparse
-
-        from kaptive_amd.cli import _TypingPipeline
-
-        args = argparse.Namespace(out="-", threads=threads, json=None, loci=None, genes=None, proteins=None, pha4ge=None)
-        paths = [str(p) for p in paths]
-        chunks = [(k, paths[i : i + batch_size]) for k, i in enumerate(range(0, len(paths), batch_size))]
-        pipe = _TypingPipeline(args, self._device, typer=self)
-        try:
-            for _, outs in pipe.run(chunks):
-                yield tuple(out["tsv"] for _, out in outs)
-        finally:
-            pipe.close()
+        yield from _tsv_chunks(self, paths, batch_size, threads)
