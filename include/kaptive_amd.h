@@ -613,6 +613,31 @@ KP_API int32_t kp_dist_tree_rounds(const kp_dist *d);
 KP_API int64_t kp_format_newick(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
                                 const int32_t *rows /* [n_names] or null */, const kp_dist_pair *edges, int64_t n_edges, const int32_t *component,
                                 char *out, int64_t cap);
+/* The neighbour-joining tree of a handle's rows (kp_spec.h, NJ): the taxa -- the rows that hold a base in more than half of the
+ * columns -- numbered, their dense matrix of p-distances filled by the same tiles, and every join run on the device.
+ *   taxa  [cap_taxa] : the rows of the *n_taxa taxa, ascending; a record's node id below n_taxa is an index into it.
+ *   nodes [cap_nodes]: the *n_nodes records, in the order the joins made them: n_taxa - 2, one for two taxa, none below that.
+ * The counting form -- taxa and nodes null, both caps 0 -- only counts the taxa into *n_taxa (n_nodes may then be null); the
+ * caller sizes its tables by it: cap_taxa >= n_taxa and cap_nodes >= max(n_taxa - 2, 1) always suffice.  KP_EINVAL for a null
+ * context, handle or n_taxa, a null n_nodes outside the counting form, a handle of another device, a negative cap, a null table
+ * with room asked for, caps short of the taxa or the records, and a matrix of more than KP_NJ_MAX_TAXA taxa (kp_caps.h), which this
+ * call alone refuses, after the taxa are counted -- *n_taxa holds their number -- and before the matrix is allocated (the counting
+ * form counts them without refusing).  min_compared as kp_dist_clusters takes it; here it moves the bar a row must clear to be a
+ * taxon.  n_rows of 0 and 1 are valid.  KP_ENOMEM if the matrix, n_taxa^2 doubles, does not fit.  The call leaves the handle's
+ * listing state, its cluster, tree and site tables alone.  Its O(n_rows) tables are the handle's own, allocated once, on the first
+ * call; the matrix and the picks' partial results are allocated by every call and freed before it returns -- 2 GiB at the limit
+ * must not stay with every handle a caller keeps open.  kp_device_allocations counts neither. */
+KP_API int kp_dist_nj(kp_ctx *ctx, kp_dist *d, int32_t min_compared, int32_t *taxa /* [cap_taxa] rows of the taxa, ascending */, int64_t cap_taxa,
+                      int32_t *n_taxa, kp_nj_node *nodes /* [cap_nodes] */, int64_t cap_nodes, int64_t *n_nodes);
+/* The neighbour-joining table of one locus (host only): one tab-separated line -- Locus, Assemblies (n_names, the rows of the
+ * matrix), Taxa (n_taxa), Newick (kp_spec.h, NJ, NEWICK) --, or no line for fewer than two taxa.  No header line.  names / name_off
+ * [n_names + 1]: the assemblies' names; row i of the matrix is named names[rows[i]], or names[i] when rows is null; taxa [n_taxa]
+ * and nodes [n_nodes] as kp_dist_nj filled them.  Written without recursion.  Return value as kp_format_variants has it; KP_EINVAL
+ * also for taxa that do not ascend or lie outside [0, n_names), n_nodes other than the tree of n_taxa has, a node id outside the
+ * nodes made before its record, a third child anywhere but in the last record, and a node that is a child twice. */
+KP_API int64_t kp_format_nj(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
+                            const int32_t *rows /* [n_names] or null */, const int32_t *taxa, int32_t n_taxa, const kp_nj_node *nodes, int64_t n_nodes,
+                            char *out, int64_t cap);
 /* Variable sites of a handle's rows (kp_spec.h, SITES): a reduction over the columns of the same planes, no pair looked at.
  *   kp_dist_profile    : out [cap >= 16 * n_blocks]: the profile of every column of the matrix, padding columns included, as
  *                        kp_site records with `column` filled, ascending.  Computed on the handle's first need of it and kept.

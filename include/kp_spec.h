@@ -666,8 +666,8 @@ typedef struct kp_rescue {
  * measurements: ten differences in a 25 kb locus is 0.04 %, well inside one outbreak and well below two variants of a locus; one
  * compared column keeps pairs of empty rows out of the table.
  * OUT OF SCOPE.  Merging fragments of one gene; distances between isolates of different loci or different databases; indel events
- * as events (an inserted run counts through `unshared` only); neighbour-joining or any tree with inferred inner nodes (clusters:
- * CLUSTERS, a minimum spanning tree: TREE, below); any change to an existing report byte. */
+ * as events (an inserted run counts through `unshared` only); any change to an existing report byte.  (Clusters: CLUSTERS, a
+ * minimum spanning tree: TREE, a neighbour-joining tree with inferred inner nodes: NJ, all below.) */
 #define KP_DIST_MAX_DIFF 10
 #define KP_DIST_MIN_COMPARED 1
 typedef struct kp_dist_pair {
@@ -699,9 +699,9 @@ typedef struct kp_dist_pair {
  * compared 6, differences 6, unshared 0), B -> (0; 6, 6, 0), C -> none.  min_compared = 0: labels 0, 0, 0 at both levels; nearest
  * A -> 2, B -> 2, C -> 0, each with counts (0, 0, 8) -- the empty row is 0 differences from everything and links A to B, which is
  * the reason for the default of 1.
- * OUT OF SCOPE.  Any linkage other than single; neighbour-joining or any tree with inferred inner nodes (the minimum spanning tree
- * of the same edges: TREE, below); cluster names that are stable across runs; a threshold on `unshared`; merging fragments of a
- * split gene; any change to an existing report byte. */
+ * OUT OF SCOPE.  Any linkage other than single (the minimum spanning tree of the same edges: TREE, a neighbour-joining tree with
+ * inferred inner nodes: NJ, both below); cluster names that are stable across runs; a threshold on `unshared`; merging fragments of
+ * a split gene; any change to an existing report byte. */
 #define KP_CLUST_MAX_LEVELS 8
 typedef struct kp_dist_nearest { int32_t row, compared, differences, unshared; } kp_dist_nearest;  /* 16 bytes */
 
@@ -732,8 +732,8 @@ typedef struct kp_dist_nearest { int32_t row, compared, differences, unshared; }
  * row); the branch length is the integer `differences`.  A node with children is written (child:len,child:len)name, a leaf name,
  * and the tree ends in ;.  A name is written bare when every byte is in A-Za-z0-9_.- and otherwise in single quotes with every '
  * doubled.  The known answers: (B:6)A; and C; with min_compared = 1, ((B:0)C:0)A; with 0.
- * OUT OF SCOPE.  Any linkage other than single; neighbour-joining or any tree with inferred inner nodes; names that are stable
- * across runs; any change to an existing report byte. */
+ * OUT OF SCOPE.  Any linkage other than single; inferred inner nodes (the neighbour-joining tree of the same rows: NJ, below);
+ * names that are stable across runs; any change to an existing report byte. */
 
 /* ---- SITES (optional; a reduction over the COLUMNS of a DISTANCES matrix: no pair, no pair record, no report byte depends on it) ------
  * Where do the isolates of one locus differ, how many of them carry each base there, and what is the alignment of those columns
@@ -768,5 +768,50 @@ typedef struct kp_site {
     int32_t n[4];   /* rows that hold a, c, g, t there */
     int32_t n_n;    /* rows that hold an N there */
 } kp_site;
+
+/* ---- NJ (optional; a fourth reduction over the pairs of DISTANCES, and the first in floating point: no report byte depends on it) ----
+ * How are the isolates of one locus related when they are not one outbreak?  The minimum spanning tree puts assemblies on inner
+ * nodes; between lineages the neighbour-joining tree, whose inner nodes are inferred, is the usual picture.  Its update halves
+ * distances at every join, so it cannot stay in integers: this section fixes every operation and its order instead, and the tree is
+ * still a PURE FUNCTION of the matrix and min_compared -- the same bytes from the device, from kp_nj.h under g++ and from NumPy.
+ *
+ * TAXA.  For a matrix of R locus rows of NB blocks: W = 16 NB (padding columns counted); bases(r) the number of columns in which row
+ * r holds a code 0..3 (the popcount of its `valid` plane); m0 = max(min_compared, 1).  Row r is a taxon iff 2 bases(r) >= W + m0.
+ * Taxa are numbered 0 .. n - 1 in ascending row order.  The reason for the rule: two taxa a, b hold bases in bases(a) + bases(b)
+ * columns of W, so by pigeonhole compared(a, b) >= bases(a) + bases(b) - W >= m0 -- every pair of taxa has a distance, and no pair
+ * needs a check.  Rows that are not taxa are left out of the tree: an isolate with under half of the locus has no place in it.
+ * DISTANCE.  d(a, b) = (double)differences / (double)compared, the p-distance, in IEEE binary64 with one correctly rounded division;
+ * d(a, a) = +0.0.
+ * SUM64(v[0 .. m)).  64 partial sums S_l, each the left fold from +0.0 of v[k] over k = l (mod 64), ascending; then for o = 32, 16,
+ * 8, 4, 2, 1: S_l = S_l + S_{l+o} for l < o.  The result is S_0.  (One wavefront's strided adds and xor shuffles.)
+ * STATE.  Slots 0 .. m - 1, always dense.  node[slot] is a node id: taxa are 0 .. n - 1, inner nodes n, n + 1, ... in the order they
+ * are made.  Initially m = n, slot k holds taxon k and R_k = SUM64(d(k, .)).
+ * JOIN, while m > 3.  With f = (double)(m - 2); every operation below is rounded to binary64 and none is fused into a multiply-add.
+ *   Q(a, b) = ((f * d(a, b)) - R_a) - R_b for slots a < b; the pair (i, j) is the minimum of (Q, a, b), compared lexicographically.
+ *   delta = (R_i - R_j) / f;  L_i = 0.5 * (d(i, j) + delta);  L_j = d(i, j) - L_i.  Emit (node[i], node[j], -1; L_i, L_j, 0).
+ *   For every slot k other than i, j:  u_k = 0.5 * ((d(i, k) + d(j, k)) - d(i, j));  R_k = ((R_k - d(i, k)) - d(j, k)) + u_k.
+ *   Slot i becomes the new node: d(i, k) = u_k, d(i, i) = 0.  If j != m - 1 the node in slot m - 1 moves to slot j with its row,
+ *   its column and its R.  m becomes m - 1.  R_i = SUM64 over the slots 0 .. m - 1 of row i.
+ * END.  With m = 3 and the slots as x, y, z = 0, 1, 2, emit (node[0], node[1], node[2]; l_x, l_y, l_z) with l_x = 0.5 * ((d_xy +
+ * d_xz) - d_yz), l_y = 0.5 * ((d_xy + d_yz) - d_xz), l_z = 0.5 * ((d_xz + d_yz) - d_xy).  n = 3 gives this record only; n = 2 the
+ * one record (0, 1, -1; 0.5 d, 0.5 d, 0); n <= 1 none; otherwise there are n - 2 records.  Negative lengths are left as they come.
+ * RECORD.  kp_nj_node: a, b, c, pad_; la, lb, lc -- 40 bytes; c = -1 and lc = +0.0 for a binary join, pad_ zero.
+ * KNOWN ANSWERS, on the level of a distance matrix (kp_nj_host).  The rows (0 5 9 9 8), (5 0 10 10 9), (9 10 0 8 7), (9 10 8 0 3),
+ * (8 9 7 3 0) give (0, 1, -1; 2, 3, 0), (5, 2, -1; 3, 4, 0), (6, 4, 3; 2, 1, 2): the second join is a tie of Q = -28 between slots
+ * (0, 2) and (1, 3), and the slot order decides it.  Six taxa with all distances 0 give (0, 1, -1), (6, 5, -1), (7, 4, -1), (8, 3, 2)
+ * with every length 0: every choice is a tie, and every move of the last slot shows.
+ * NEWICK (host only).  The tree is unrooted and written from the last record: (X:lx,Y:ly,Z:lz); -- a binary last record, which only
+ * n = 2 gives, (A:l,B:l);.  An inner node is written (A:la,B:lb), unnamed, its children in record order; a leaf is its assembly's
+ * name under the quoting rule of TREE's NEWICK.  Lengths are printed with %.9g.  The first known answer with the names a .. e:
+ * (((a:2,b:3):3,c:4):2,e:1,d:2);
+ * LIMIT.  KP_NJ_MAX_TAXA = 16384 (kp_caps.h): the dense matrix is n * n doubles, 2 GiB at the limit.  A matrix with more taxa is
+ * refused by this call alone, after the taxa are counted and before anything large is allocated.
+ * OUT OF SCOPE.  Any distance correction (JC69 and the like); bootstrap; rooting; clamping of negative lengths; BIONJ or FastME;
+ * merging fragments of a split gene; trees across loci; any change to an existing report byte. */
+typedef struct kp_nj_node {
+    int32_t a, b, c;   /* node ids: taxa 0 .. n - 1, inner nodes from n on; c = -1 for a binary join */
+    int32_t pad_;      /* zero */
+    double la, lb, lc; /* their branch lengths; lc = +0.0 for a binary join */
+} kp_nj_node;
 
 #endif /* KP_SPEC_H */

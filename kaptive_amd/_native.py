@@ -115,6 +115,17 @@ def newick_header() -> bytes:
     return NEWICK_HEADER
 
 
+# Neighbour-joining tree of the same rows (include/kp_spec.h, NJ)
+NJ_NODE_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4"), ("c", "<i4"), ("pad", "<i4"), ("la", "<f8"), ("lb", "<f8"), ("lc", "<f8")])  # kp_nj_node: 40 bytes
+NJ_MAX_TAXA = 16384  # KP_NJ_MAX_TAXA of kaptive_amd/csrc/kp_caps.h: the dense matrix of as many taxa is 2 GiB
+NJ_HEADER = b"Locus\tAssemblies\tTaxa\tNewick\n"  # the columns of kp_format_nj
+
+
+def nj_header() -> bytes:
+    """The header line of the neighbour-joining table (the columns of kp_format_nj)."""
+    return NJ_HEADER
+
+
 # Variable sites of the same rows (include/kp_spec.h, SITES)
 SITE_DTYPE = np.dtype([("column", "<i4"), ("n", "<i4", (4,)), ("n_n", "<i4")])  # kp_site: 24 bytes
 SITES_HEADER = b"Locus\tGene\tPosition\tColumn\tAssemblies\tA\tC\tG\tT\tN\tGap\tAlleles\tMajor\tInformative\n"  # the columns of kp_format_sites
@@ -139,7 +150,7 @@ EXPORTS = (
     "kp_device_count", "kp_device_numa_node", "kp_batch_typing", "kp_batch_proteins", "kp_protein_align", "kp_fasta_pack", "kp_fasta_ingest", "kp_fasta_ingest_many", "kp_fasta_ingest_file", "kp_fasta_ingest_shard", "kp_shard_words_into", "kp_shard_free", "kp_fasta_simd", "kp_pack_contigs",
     "kp_fasta_free", "kp_format_rows", "kp_format_json", "kp_format_fasta", "kp_protein_align_seeded", "kp_randstrobes", "kp_randstrobe_top_hits",
     "kp_dist_create", "kp_dist_count", "kp_dist_pairs", "kp_dist_destroy", "kp_format_distances", "kp_dist_clusters", "kp_format_clusters",
-    "kp_dist_tree", "kp_dist_tree_rounds", "kp_format_newick",
+    "kp_dist_tree", "kp_dist_tree_rounds", "kp_format_newick", "kp_dist_nj", "kp_format_nj",
     "kp_dist_profile", "kp_dist_sites_count", "kp_dist_sites", "kp_dist_site_rows", "kp_format_sites", "kp_format_site_rows",
 )  # fmt: skip
 
@@ -764,6 +775,25 @@ def format_newick(locus_name: str, names, edges, component, rows=None) -> bytes:
     return _sized("kp_format_newick", 64 * R + len(nm_b) + 64, lambda out, cap: h.kp_format_newick(
         C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows), _p(edges), C.c_int64(len(edges)),
         _p(component), out, cap))  # fmt: skip
+
+
+def format_nj(locus_name: str, names, taxa, nodes, rows=None) -> bytes:
+    """The line of one locus's neighbour-joining table (kp_format_nj; host only; no header: ``nj_header``), or nothing for fewer
+    than two taxa.  ``taxa`` (int32 [n]) and ``nodes`` (NJ_NODE_DTYPE) as ``Distances.nj`` returns them; ``names`` the R assemblies'
+    names, by row of the matrix -- or, with ``rows`` (int32 [R]), row i is ``names[rows[i]]``."""
+    nm_b, nm_o = _blob64(names)
+    taxa = np.ascontiguousarray(taxa, np.int32)
+    nodes = np.ascontiguousarray(nodes, dtype=NJ_NODE_DTYPE)
+    R = len(nm_o) - 1
+    if rows is not None and len(rows) != R:
+        raise ValueError("a name for every row")
+    rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+    locus = locus_name.encode("utf-8")
+    h = lib()
+    h.kp_format_nj.restype = C.c_int64
+    return _sized("kp_format_nj", 48 * len(taxa) + len(nm_b) + len(locus) + 64, lambda out, cap: h.kp_format_nj(
+        C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows), _p(taxa) if len(taxa) else None,
+        C.c_int32(len(taxa)), _p(nodes) if len(nodes) else None, C.c_int64(len(nodes)), out, cap))  # fmt: skip
 
 
 def format_sites(locus_name: str, gene_names, gene_lengths, n_rows: int, sites, genes=None) -> bytes:
@@ -1497,6 +1527,24 @@ class Distances:
         h.kp_dist_tree_rounds.restype = C.c_int32
         return int(h.kp_dist_tree_rounds(self._h))
 
+    def nj_taxa(self, min_compared: int = DIST_MIN_COMPARED) -> int:
+        """How many taxa ``nj`` would join (the counting form of kp_dist_nj): the rows that hold a base in at least half of the
+        columns plus half of ``max(min_compared, 1)``."""
+        n = C.c_int32(0)
+        self.ctx._check(lib().kp_dist_nj(self.ctx._h, self._h, C.c_int32(int(min_compared)), None, C.c_int64(0), C.byref(n), None, C.c_int64(0), None), "kp_dist_nj")
+        return n.value
+
+    def nj(self, min_compared: int = DIST_MIN_COMPARED):
+        """(taxa int32 [n], nodes NJ_NODE_DTYPE) of the rows' neighbour-joining tree (kp_dist_nj; include/kp_spec.h, NJ): ``taxa``
+        the rows that are taxa, ascending; ``nodes`` the records of the joins in the order they were made -- node ids below n index
+        ``taxa``, the id n + r is the inner node record r made -- and the last one holds the three nodes that were left.  More than
+        ``NJ_MAX_TAXA`` taxa are refused.  The listing state and every other table of the handle are left alone."""
+        n = self.nj_taxa(min_compared)
+        taxa, nodes = np.zeros(n, np.int32), np.zeros(max(n - 2, 1 if n == 2 else 0), NJ_NODE_DTYPE)
+        got, made = C.c_int32(0), C.c_int64(0)
+        self.ctx._check(lib().kp_dist_nj(self.ctx._h, self._h, C.c_int32(int(min_compared)), _p(taxa) if n else None, C.c_int64(n), C.byref(got),
+                                         _p(nodes) if len(nodes) else None, C.c_int64(len(nodes)), C.byref(made)), "kp_dist_nj")  # fmt: skip
+        return taxa[: got.value].copy(), nodes[: made.value].copy()
 
     def profile(self) -> np.ndarray:
         """SITE_DTYPE records of all ``16 * n_blocks`` columns of the matrix, padding columns included, ascending (kp_dist_profile;

@@ -142,7 +142,7 @@ def _add_outputs(p: argparse.ArgumentParser, tsv_flags, include_json: bool) -> N
         g.add_argument("--max-distance", type=int, metavar="N", default=argparse.SUPPRESS,
                        help="With --distances: most differing bases a listed pair may have (default: 10)")
         g.add_argument("--min-compared", type=int, metavar="N", default=argparse.SUPPRESS,
-                       help="With --distances, --clusters, --mst or --newick: fewest columns both assemblies must hold a base in (default: 1)")
+                       help="With --distances, --clusters, --mst, --newick or --nj: fewest columns both assemblies must hold a base in (default: 1)")
         g.add_argument("--clusters", metavar="FILE", default=argparse.SUPPRESS,
                        help="Group the assemblies that carry the same locus by single linkage at every one of --cluster-levels "
                             "differing bases, name every assembly's nearest neighbour, and write one line per assembly as a TSV "
@@ -154,6 +154,10 @@ def _add_outputs(p: argparse.ArgumentParser, tsv_flags, include_json: bool) -> N
                             "write its edges as a TSV table with the columns of --distances to a file; no pair is listed for it")
         g.add_argument("--newick", metavar="FILE", default=argparse.SUPPRESS,
                        help="The same trees as Newick text, one line per tree, as a TSV table to a file")
+        g.add_argument("--nj", metavar="FILE", default=argparse.SUPPRESS,
+                       help="Build the neighbour-joining tree, with inferred inner nodes, of the assemblies that carry the same locus "
+                            "and hold a base in more than half of it, from the share of differing bases, and write it as Newick "
+                            "text, one line per locus, as a TSV table to a file")
         g.add_argument("--sites", metavar="FILE", default=argparse.SUPPRESS,
                        help="List the gene positions at which the assemblies that carry the same locus hold different bases, with the "
                             "number of assemblies that carry each base there, as a TSV table to a file; no pair is looked at for it")
@@ -180,7 +184,7 @@ class _Parser(argparse.ArgumentParser):
                     self.error(f"--{flag.replace('_', '-')} requires --rescue FILE")
                 if getattr(ns, flag) < 0 or (flag == "rescue_flank" and ns.rescue_flank > 65535):
                     self.error(f"--{flag.replace('_', '-')} is out of range")
-        for flag, beside in (("max_distance", ("distances",)), ("min_compared", ("distances", "clusters", "mst", "newick"))):
+        for flag, beside in (("max_distance", ("distances",)), ("min_compared", ("distances", "clusters", "mst", "newick", "nj"))):
             if getattr(ns, flag, None) is not None:
                 if not any(getattr(ns, b, None) for b in beside):
                     self.error(f"--{flag.replace('_', '-')} requires " + " or ".join(f"--{b} FILE" for b in beside))
@@ -665,11 +669,11 @@ def hits_to_paf(engine, genomes, hits, hit_off, ops, cigar_off, cs=None, cs_off=
 
 
 LOCUS_ROWS_KEY = "locus_rows"  # a chunk's outputs: the ``LocusRows.state()`` of its assemblies (PAIR_TABLES); never written to a file
-PAIR_TABLES = ("distances", "clusters", "mst", "newick", "sites", "snp_alignment")  # the flags whose tables are made of the run's locus rows
+PAIR_TABLES = ("distances", "clusters", "mst", "newick", "nj", "sites", "snp_alignment")  # the flags whose tables are made of the run's locus rows
 
 
 class _RunDistances:
-    """``--distances``, ``--clusters``, ``--mst``, ``--newick``, ``--sites`` and ``--snp-alignment``: the locus rows of the whole run, collected once for all of them,
+    """``--distances``, ``--clusters``, ``--mst``, ``--newick``, ``--nj``, ``--sites`` and ``--snp-alignment``: the locus rows of the whole run, collected once for all of them,
     merged chunk by chunk in input order -- one ``LocusRows`` per database -- and, after the last chunk, compared on a device and
     written: one table each, or with ``--db`` one per database (``per_database_path``).  All tables of a locus come from one device
     handle."""
@@ -696,6 +700,15 @@ class _RunDistances:
         for (_, rows), (_, out) in zip(self.rows, outs):
             rows.merge(out.pop(LOCUS_ROWS_KEY))
 
+    @staticmethod
+    def _lines(rows, made) -> bytes:
+        """A table's lines; a method that may skip loci returns them beside its lines (``nj_tsv``): one line to stderr for each."""
+        if isinstance(made, tuple):
+            made, skipped = made
+            for L in skipped:
+                print(f"--nj: locus {rows.db.loci.ids[L]} has more than the most taxa a neighbour-joining tree may have; it gets no line", file=sys.stderr)
+        return made
+
     def write(self, ctx) -> None:
         from kaptive_amd import _native
 
@@ -708,11 +721,12 @@ class _RunDistances:
             ("clusters", _native.clusters_header(levels), "clusters_tsv", (levels, mc)),
             ("mst", _native.DISTANCES_HEADER, "tree_tsv", (mc,)),
             ("newick", _native.newick_header(), "newick_tsv", (mc,)),
+            ("nj", _native.nj_header(), "nj_tsv", (mc,)),
             ("sites", _native.SITES_HEADER, "sites_tsv", (self.core_sites,)),
             ("snp_alignment", _native.SNP_ALIGNMENT_HEADER, "snp_alignment_tsv", (self.core_sites,)),
         )
         for kw, rows in self.rows or []:
-            tables = [(path, header + getattr(rows, method)(ctx, *a)) for flag, header, method, a in kinds if (path := getattr(self.args, flag, None))]
+            tables = [(path, header + self._lines(rows, getattr(rows, method)(ctx, *a))) for flag, header, method, a in kinds if (path := getattr(self.args, flag, None))]
             rows.close()  # (the handles of this database's loci: every table has been made of them)
             for path, text in tables:
                 if kw is None and _is_stdout(path):

@@ -283,3 +283,9 @@ constexpr int KP_TREE_ROW_BITS = 18, KP_TREE_DIFF_BITS = 28;
 constexpr int64_t KP_TREE_MAX_COLUMNS = 1ll << KP_TREE_DIFF_BITS;
 static_assert(KP_TREE_DIFF_BITS + KP_TREE_ROW_BITS + KP_TREE_ROW_BITS == 64, "28 + 18 + 18: the key fills one 64-bit word");
 static_assert(KP_DIST_MAX_ROWS <= (1 << KP_TREE_ROW_BITS), "every row of the largest matrix must fit the key's row fields");
+
+// most taxa of a neighbour-joining tree (kp_dist_nj; kp_spec.h, NJ).  The join loop keeps the dense matrix of the taxa on the
+// device: n * n doubles, 2 GiB at 16384 taxa, beside the planes of the rows -- and its picks read some n^3 / 3 of them.  A matrix
+// with more taxa is refused by kp_dist_nj, and by it alone, once the taxa are counted and before the matrix is allocated.
+constexpr int32_t KP_NJ_MAX_TAXA = 16384;
+static_assert((int64_t)KP_NJ_MAX_TAXA * KP_NJ_MAX_TAXA * 8 == (2ll << 30), "the dense matrix of the most taxa is 2 GiB");

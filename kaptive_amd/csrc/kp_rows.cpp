@@ -17,6 +17,7 @@
 #include "kp_alleles.h"
 #include "kp_clust.h"
 #include "kp_sites.h"
+#include "kp_nj.h"
 
 namespace {
 
@@ -703,6 +704,73 @@ extern "C" int64_t kp_format_newick(const char *locus_name, int32_t locus_name_l
         }
         o.lit(";\n");
     }
+    return o.n;
+}
+
+// ---- neighbour-joining table (kp_spec.h, NJ) -------------------------------------------------------------------------------------------
+// One line for one locus's tree, none for fewer than two taxa: the unrooted tree written from its last record, inner nodes unnamed,
+// lengths with %.9g, with a stack of its own -- a caterpillar of 16384 taxa is a legal tree.
+extern "C" int64_t kp_format_nj(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
+                                const int32_t *rows, const int32_t *taxa, int32_t n_taxa, const kp_nj_node *nodes, int64_t n_nodes, char *out, int64_t cap) {
+    const RowNames t{names, name_off, n_names, rows};
+    if (!locus_and_out_ok(locus_name, locus_name_len, out, cap) || !t.valid() || n_taxa < 0 || n_taxa > n_names || n_nodes < 0) return KP_EINVAL;
+    if ((n_taxa > 0 && !taxa) || (n_nodes > 0 && !nodes)) return KP_EINVAL;
+    const int64_t n = n_taxa;
+    if (n_nodes != kp_nj_records(n)) return KP_EINVAL;
+    for (int64_t k = 0; k < n; ++k)
+        if (taxa[k] < 0 || taxa[k] >= n_names || (k > 0 && taxa[k] <= taxa[k - 1])) return KP_EINVAL;
+    // record r makes node n + r out of nodes made before it, and no node is a child twice: a tree, and no cycle
+    std::vector<char> used((size_t)(n + n_nodes), 0);
+    for (int64_t r = 0; r < n_nodes; ++r) {
+        const kp_nj_node &p = nodes[r];
+        const bool last = r == n_nodes - 1, three = last && n > 2;
+        const int32_t child[3] = {p.a, p.b, p.c};
+        if (!three && p.c != -1) return KP_EINVAL;
+        for (int k = 0; k < (three ? 3 : 2); ++k) {
+            if (child[k] < 0 || child[k] >= n + r || used[(size_t)child[k]]) return KP_EINVAL;
+            used[(size_t)child[k]] = 1;
+        }
+    }
+    Out o{out, cap};
+    if (n_nodes == 0) return 0;
+    put_locus(o, locus_name, locus_name_len); o.put('\t');
+    o.num(n_names); o.put('\t');
+    o.num(n); o.put('\t');
+    const auto put_length = [&o](double v) {
+        char buf[40];
+        o.put(':');
+        o.put(buf, std::snprintf(buf, sizeof buf, "%.9g", v));
+    };
+    struct Frame { int64_t rec; int next; };  // the record of an open inner node, and which of its children comes next
+    std::vector<Frame> stack;
+    stack.push_back(Frame{n_nodes - 1, 0});
+    o.put('(');
+    while (!stack.empty()) {
+        const Frame f = stack.back();
+        const kp_nj_node &p = nodes[f.rec];
+        if (f.next == (p.c >= 0 ? 3 : 2)) {  // closed: its own length follows, unless it is the tree
+            o.put(')');
+            stack.pop_back();
+            if (!stack.empty()) {
+                const Frame &up = stack.back();
+                const kp_nj_node &q = nodes[up.rec];
+                put_length(up.next == 1 ? q.la : (up.next == 2 ? q.lb : q.lc));
+            }
+            continue;
+        }
+        if (f.next > 0) o.put(',');
+        const int32_t id = f.next == 0 ? p.a : (f.next == 1 ? p.b : p.c);
+        ++stack.back().next;
+        if (id < n) {
+            const int32_t at = t.at(taxa[id]);
+            put_newick_name(o, names + name_off[at], name_off[at + 1] - name_off[at]);
+            put_length(f.next == 0 ? p.la : (f.next == 1 ? p.lb : p.lc));
+        } else {
+            o.put('(');
+            stack.push_back(Frame{(int64_t)id - n, 0});
+        }
+    }
+    o.lit(";\n");
     return o.n;
 }
 

@@ -6,7 +6,8 @@ the primary kept records of its best locus's genes, strung together in database 
 hands the rows of every locus to the device as one matrix (``_native.Distances``: kp_dist.hip compares them all against all).  Two
 tables come of a matrix: the listed pairs (``distances`` / ``tsv``) and, with no pair listed, every row's single-linkage cluster at a
 few thresholds and its nearest neighbour (``clusters`` / ``clusters_tsv``; include/kp_spec.h, CLUSTERS), and the minimum spanning forest
-of the rows as an edge table and as Newick text (``tree`` / ``tree_tsv`` / ``newick_tsv``; include/kp_spec.h, TREE).  A fourth reads
+of the rows as an edge table and as Newick text (``tree`` / ``tree_tsv`` / ``newick_tsv``; include/kp_spec.h, TREE), and the
+neighbour-joining tree of the rows that hold most of the locus (``nj`` / ``nj_tsv``; include/kp_spec.h, NJ).  Another reads
 the matrix by columns, not by pairs: the variable sites of a locus with every base's count, and the rows cut down to those sites
 (``profile`` / ``sites`` / ``site_rows`` / ``sites_tsv`` / ``snp_alignment_tsv``; include/kp_spec.h, SITES).  One device handle
 per locus serves them all: it is kept until the rows change or ``close()``.
@@ -44,7 +45,7 @@ class LocusRows:
     """The locus rows of a run, for one database.
 
     ``add(bt)`` takes a ``BatchTyping`` of an engine made with ``aligned=True``; ``distances(ctx)`` / ``tsv(ctx)`` / ``matrix(ctx,
-    locus)``, ``clusters(ctx)`` / ``clusters_tsv(ctx)`` and ``tree(ctx)`` / ``tree_tsv(ctx)`` / ``newick_tsv(ctx)`` compare them on the device of ``ctx`` (a ``_native.Context``; no database
+    locus)``, ``clusters(ctx)`` / ``clusters_tsv(ctx)``, ``tree(ctx)`` / ``tree_tsv(ctx)`` / ``newick_tsv(ctx)`` and ``nj(ctx, locus)`` / ``nj_tsv(ctx)`` compare them on the device of ``ctx`` (a ``_native.Context``; no database
     needs to be resident in it).  Assemblies are numbered in the order they were added.  A locus's matrix is uploaded once, by the
     first of these calls that needs it; ``close()`` -- or another ``add`` / ``merge`` -- frees the handles."""
 
@@ -263,6 +264,30 @@ class LocusRows:
             return _native.format_newick(self.db.loci.ids[L], [self.ids[i] for i in idx], p, comp)
 
         return self._per_locus(table, b"")
+
+    def nj(self, ctx, locus: int, min_compared: int = _native.DIST_MIN_COMPARED) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(assembly numbers [R], taxa int32 [n] as rows of the matrix, nodes ``_native.NJ_NODE_DTYPE``) of one locus's
+        neighbour-joining tree (include/kp_spec.h, NJ): node ids below n index ``taxa``, the id n + r is the node record r made."""
+        idx, mat = self.locus_matrix(locus)
+        if len(idx) == 0:
+            return idx, np.zeros(0, np.int32), np.zeros(0, _native.NJ_NODE_DTYPE)
+        return (idx, *self._handle(ctx, locus).nj(min_compared))
+
+    def nj_tsv(self, ctx, min_compared: int = _native.DIST_MIN_COMPARED) -> tuple[bytes, list]:
+        """(the lines of the neighbour-joining table, the loci that were skipped) (``--nj``; no header: ``_native.nj_header()``),
+        formatted by the native library (kp_format_nj): loci in database order, a line for every locus with at least two taxa.  A
+        locus of more than ``_native.NJ_MAX_TAXA`` taxa gets no line: its dense matrix is not built, and its number is returned."""
+        out, skipped = [], []
+        for L in self.loci():
+            idx, mat = self.locus_matrix(L)
+            if len(idx) < 2:
+                continue
+            if self._handle(ctx, L).nj_taxa(min_compared) > _native.NJ_MAX_TAXA:
+                skipped.append(L)
+                continue
+            _, taxa, nodes = self.nj(ctx, L, min_compared)
+            out.append(_native.format_nj(self.db.loci.ids[L], [self.ids[i] for i in idx], taxa, nodes))
+        return b"".join(out), skipped
 
     # -- sites: the matrix by columns ---------------------------------------------------------------------------------------------------
     def profile(self, ctx, locus: int) -> np.ndarray:
