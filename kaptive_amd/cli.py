@@ -4,7 +4,8 @@ Same positionals and flags as the reference's ``kaptive type`` (alias ``assembly
 (src/kaptive/serotyping/cli.py:118-267, shared output flags src/kaptive/cli.py:424-504), minus the plot output.  What
 differs underneath: genomes are read and packed by a thread pool (``--threads`` is honoured; the reference parses and
 ignores it) while earlier ones are being typed, in batches, on the GPU(s) (``--devices``: one process per
-device; ``--batch-size``), and written in input order (``_TypingPipeline``).
+device; ``--batch-size``), and written in input order (``kaptive_amd/pipeline.py``: ``TypingPipeline``, which this
+module gives its ``PipelineOptions``: ``pipeline_options``).
 DATABASE is a ``.npz`` blob written by ``Database.save`` or a GenBank file with its ``.toml`` next to it.
 
 ``--db DATABASE`` (repeatable) adds databases to the same run: ``kaptive_amd assembly kpsc_k.gbk genomes/*.fasta --db
@@ -22,14 +23,13 @@ import json
 import os
 import sys
 import time
-from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 import numpy as np
 
 from kaptive_amd._native import REPORTS  # the tables derived from the kept lists: one row per report, every loop below goes over it
+from kaptive_amd.pipeline import FILE_SUFFIX, LOCUS_ROWS_KEY, PipelineOptions, TypingPipeline, load_database
 
-FILE_SUFFIX = "kaptive_results"
 _KEEP: list = []  # FAST_EXIT: what must not be finalised one object at a time on the way out
 FAST_EXIT = False  # set by __main__: the process ends right after main() returns, so nothing needs to be torn down in order
 FAST_EXIT_ARMED = False  # set by run_type once its output handles are closed: only then may __main__ skip the interpreter's teardown
@@ -234,442 +234,21 @@ def build_parser() -> argparse.ArgumentParser:
     return ap
 
 
-def load_database(path: str):
-    from kaptive_amd.db import Database
-
-    p = Path(path)
-    if p.suffix in (".gbk", ".gb", ".genbank"):
-        from kaptive_amd.db.genbank import database_from_genbank
-
-        return database_from_genbank(p)
-    return Database.load(p)
-
-
-class _TypingPipeline:
-    """One device's share of ``kaptive assembly``: files -> reader pool -> pinned shard -> the engine's typing window -> bytes.
-
-    The stages run beside each other: while the GPU types chunk k, the reader threads parse and pack chunk k + 1 .. k + 2
-    (``kp_fasta_ingest`` releases the interpreter lock), their packed words are copied into page-locked memory and
-    uploaded on the copy stream, and chunk k - 1's rows are formatted.  When only the TSV and / or PHA4GE reports are asked for,
-    no per-assembly object is ever built: the rows come from ``BatchTyping.tsv()`` (``kp_format_rows``, byte for byte what
-    ``KaptiveRow.from_result`` gives) and ``BatchTyping.pha4ge()``, and the files' sequence text is not even kept.  The
-    JSON lines (``-j``) come from ``BatchTyping.jsonl()`` (``kp_format_json``) and the records of the per-assembly fasta files
-    (``-l``, ``-g``, ``-p``) from ``BatchTyping.fasta()`` (``kp_format_fasta``): they need the files' text but no objects either
-    (the reference's writers work on one ``SerotypingResult`` at a time, src/kaptive/serotyping/cli.py:20-114).  The readers
-    start with the process: their buffers are plain huge-page memory (``kp_host_reserve``) until a batch is made of them."""
-
-    PREFETCH = 2  # chunks being read / uploaded ahead of the one whose alignment pass is enqueued next
-
-    def __init__(self, args: argparse.Namespace, device: int, typer=None, chunks=None) -> None:
-        """``typer``: a ``Serotyper`` the caller already holds (``Serotyper.tsv_from_files``); otherwise one is made from the
-        command line's database and thresholds.  ``chunks``: what ``run`` will be given -- the first of them are handed to
-        the reader threads before the database is loaded and the device context created (0.3 s in which nothing else
-        would read a file)."""
-        import threading
-
-        from kaptive_amd import usable_cpus
-        from kaptive_amd.serotyping.core import Serotyper
-
-        self.args = args
-        self.marks = {"pipeline_start": time.perf_counter()}  # (KAPTIVE_AMD_CLI_TIMING: where the time before the first rows goes)
-        self.want_paf = bool(getattr(args, "paf", None))  # every hit with its CIGAR: the alignment passes of this run leave them
-        self.paf_cs, self.paf_eqx = bool(getattr(args, "cs", False)), bool(getattr(args, "eqx", False))  # ... and its cs string
-        self.want = {r.name: bool(getattr(args, r.name, None)) for r in REPORTS}  # the tables of the kept lists: the reductions of this run leave their records
-        self.want_distances = any(getattr(args, f, None) for f in PAIR_TABLES)  # the run's locus rows: every chunk's go with its outputs (LOCUS_ROWS_KEY)
-        self.typer_options = {**self.want, "aligned": self.want["aligned"] or self.want_distances, **{k: getattr(args, k) for k in ("rescue_flank", "rescue_min_score") if getattr(args, k, None) is not None}}
-        self.objects = any(getattr(args, f, None) for f in ("json", "loci", "genes", "proteins", "paf", *self.want))  # the files' text (and contig names) are kept
-        self.fasta_outputs = any(getattr(args, f, None) for f in ("loci", "genes", "proteins"))  # ... and result objects are built
-        self.threads = max(1, args.threads or usable_cpus())  # (the cgroup's quota, not the 256 CPUs a container may see)
-        # PREFETCH + 1 chunks are being parsed at any time, each by one native call: the thread budget is shared out among them
-        # (measured on the 16-CPU box, threads per call 4 / 6 / 8 / 12 / 16 / 24 / 32: 12.5 / 15.2 / 12.1 / 11.0 / 11.0 / 7.4 / 6.5 k
-        # assemblies/s -- a cgroup throttles what oversubscribes its quota)
-        self.shard_threads = int(os.environ.get("KAPTIVE_AMD_SHARD_THREADS", 0)) or max(1, -(-self.threads // (self.PREFETCH + 1)))
-        self.readers = ThreadPoolExecutor(max_workers=self.threads)
-        # whole chunks (TSV-only runs) are parsed PREFETCH + 1 at a time, each by shard_threads native threads, in input order
-        self.shard_readers = ThreadPoolExecutor(max_workers=self.PREFETCH + 1)
-        self.formatters = ThreadPoolExecutor(max_workers=2)  # a chunk's rows and JSON lines, beside the driving thread
-        self.copiers = ThreadPoolExecutor(max_workers=min(4, self.threads))  # object mode: copies into pinned memory (not queued behind reads)
-        self.janitor = ThreadPoolExecutor(max_workers=1)  # gives page-locked buffers back to the system while the run goes on
-        self._pins: list = []  # recycled page-locked buffers
-        self._pin_lock = threading.Lock()
-        self._pin_need = 0  # the largest buffer asked for so far: smaller ones are not worth keeping
-        self._unread = 0  # chunks that have not been handed to the readers yet
-        self._early: list = []
-        self._order: list = []
-        if chunks is not None:
-            chunks = list(chunks)
-            # The readers start before the database is loaded and the device context exists (0.4-1 s), and they keep going for
-            # as long as the read-ahead budget lasts: the words land in plain huge-page memory (kp_host_reserve: no device
-            # runtime involved) that is page-locked when its batch is created.  A run is then as long as reading its files
-            # takes, plus what the last chunk needs on the device.
-            budget, ahead, sizes = _read_ahead_bytes() // max(1, getattr(args, "read_ahead_share", 1)), 0, {}
-            for n, (k, paths) in enumerate(chunks):
-                if n >= self.PREFETCH + 1:
-                    if self.objects or any(str(p).endswith((".gz", ".bz2", ".xz")) for p in paths):
-                        break  # (texts are kept / sizes unknown: no deeper than the steady state reads ahead)
-                    try:
-                        for p in paths:
-                            if p not in sizes:
-                                sizes[p] = os.stat(p).st_size
-                    except OSError:
-                        break
-                    ahead += int(sum(sizes[p] for p in paths) * 0.3)  # 2 bits per base and the tables, with head-room
-                    if ahead > budget:
-                        break
-                self._early.append((k, self.submit_read(paths)))
-            self._unread = len(chunks) - len(self._early)
-        self._own_typer = typer is None
-        from kaptive_amd.serotyping.core import MultiSerotyper
-
-        early_ctx = None
-        if typer is None:
-            # the HIP runtime and the device context come up on a thread of their own (0.2 s, interpreter lock released) while this
-            # one reads and unpacks the database file (0.12 s): the context is waiting when the Serotyper asks for it
-            from kaptive_amd import _native
-
-            self._ctx_pool = ThreadPoolExecutor(max_workers=1)
-            early_ctx = self._ctx_pool.submit(_native.Context, device)
-        try:
-            if typer is None:
-                self.db = load_database(args.database)
-                more = [load_database(p) for p in getattr(args, "db", None) or []]
-                self.marks["database_loaded"] = time.perf_counter()
-                if more:  # one pass for all of them; duplicate keywords and too many genes are refused here, before any typing
-                    typer = MultiSerotyper([self.db, *more], max_other_genes=args.max_other_genes, min_completeness=args.min_completeness,
-                                           allow_below_threshold=args.below_threshold, partial_edge_tolerance=args.partial_edge_tolerance,
-                                           device=device, **self.typer_options)  # fmt: skip
-                else:
-                    typer = Serotyper(self.db, max_other_genes=args.max_other_genes, min_completeness=args.min_completeness,
-                                      allow_below_threshold=args.below_threshold, partial_edge_tolerance=args.partial_edge_tolerance,
-                                      device=device, **self.typer_options)  # fmt: skip
-                typer._ctx_early = early_ctx
-            self.typer = typer
-            self.engine = self.typer.engine  # the context is created here, on the thread that will drive it
-        except BaseException:
-            # a bad database path, no device, no memory: the reads queued above must not be drained (gigabytes of FASTA) by
-            # the interpreter's exit hook before the error is reported
-            self._abandon_reads()
-            if early_ctx is not None:
-                self._ctx_pool.shutdown(wait=False, cancel_futures=True)
-            raise
-        if self.want_paf:
-            self.engine.ctx.set_option("cigar", 1)  # (this run's context only)
-            if self.paf_cs or self.paf_eqx:
-                self.engine.ctx.set_option("cs", 1)
-        self.marks["context_ready"] = time.perf_counter()
-        self.want_tsv = bool(getattr(args, "out", None))
-        # A run is one typing group per database, and a run without --db is a run with one: every chunk's outputs are
-        # ((keyword, outputs), ...), one entry per database in order, and the keyword of the one database of a plain run is None
-        # (its files are named as given).  A Serotyper of a MultiSerotyper types the group its engine views.
-        several = isinstance(typer, MultiSerotyper)
-        self.typers = tuple(typer.serotypers) if several else (typer,)
-        self.keywords = tuple(t._db.metadata.keyword for t in self.typers) if several else (None,)
-
-    def _abandon_reads(self) -> None:
-        """Cancel every queued read, drop what finished reads hold (shards' page-locked blocks), keep no worker waiting."""
-        for pool in (self.readers, self.shard_readers, self.copiers, self.formatters, self.janitor):
-            pool.shutdown(wait=False, cancel_futures=True)
-        for _, futures in self._early:
-            for f in futures if isinstance(futures, list) else [futures]:
-                if f.done() and not f.cancelled() and f.exception() is None:
-                    got = f.result()
-                    if isinstance(got, tuple) and isinstance(got[0], tuple):  # ((tables, words, pinned buffer), ids)
-                        try:
-                            got[0][2].close()
-                        except Exception:
-                            pass
-        self._early = []
-        for pb in self._pins:
-            try:
-                pb.close()
-            except Exception:
-                pass
-        self._pins = []
-
-    def release_pin(self, batch) -> None:
-        """The batch's page-locked words back to the pool, once its upload has completed (waits for it if need be)."""
-        pb = getattr(batch, "_pin", None)
-        if pb is None:
-            return
-        batch._pin = None
-        try:
-            batch.upload_wait()
-        finally:
-            self._give_back(pb)
-
-    def _give_back(self, pb) -> None:
-        """A buffer whose upload is through: kept for one of the chunks still to be read (if it is large enough for
-        them), otherwise unlocked and unmapped now, beside the run, rather than by the exiting process (30 ms per 0.8 GB
-        either way, but the exit is on the command's clock)."""
-        with self._pin_lock:
-            if len(pb.array) >= self._pin_need and len(self._pins) < min(self.PREFETCH + 2, self._unread + self.PREFETCH + 1):
-                self._pins.append(pb)
-                return
-        try:
-            self.janitor.submit(pb.close)
-        except RuntimeError:  # (shut down already: the process is ending)
-            pass
-
-    def submit_read(self, paths):
-        """One chunk to the reader threads: a future of ``_load_shard`` (TSV / PHA4GE only) or a list of ``_load`` futures."""
-        if self.objects:
-            return [self.readers.submit(self._load, p) for p in paths]
-        return self.shard_readers.submit(self._load_shard, paths)
-
-    def close(self, fast: bool = False) -> None:
-        """``fast``: the process is about to exit (the command line): reads are cancelled, nothing is waited for or freed --
-        the operating system takes the page-locked memory and the device context back faster than the runtime unwinds them."""
-        for pool in (self.readers, self.shard_readers, self.copiers, self.formatters, self.janitor, *([self._ctx_pool] if getattr(self, "_ctx_pool", None) else [])):
-            pool.shutdown(wait=not fast, cancel_futures=True)
-        if fast:
-            return
-        if self._own_typer and self.typer._engine is not None:
-            self.typer._engine.close()
-        for pb in self._pins:
-            pb.close()
-
-    # -- stage 1: files -> packed assemblies (reader threads) --------------------------------------------------------------------
-    def _load(self, path):
-        from kaptive_amd.core.genome import GenomeAssembly
-
-        g = GenomeAssembly.from_file(path, keep_text=self.objects)
-        g.packed()
-        return g
-
-    def _load_shard(self, paths):
-        """A whole chunk in one native call (TSV-only runs: nothing but the packed form and the assembly names is needed):
-        the library's threads map, parse and pack the files and lay out the batch's tables (kp_fasta_ingest_shard); the
-        interpreter does nothing per file but derive the assembly's name from the path.  A chunk with a file the library
-        could not take goes the per-file way, which knows the fall-backs and raises the reference's errors."""
-        from kaptive_amd import _native
-        from kaptive_amd.core.genome import _FASTA_NAME
-
-        ids, comps = [], []
-        for path in paths:
-            name = os.path.basename(os.fspath(path))
-            m = _FASTA_NAME.search(name)
-            if not m:
-                raise NotImplementedError(f"Unsupported format: {path}")
-            ids.append(name.removesuffix(m.group()))
-            comps.append(m.group("compression"))
-        shard = _native.FastaShard(paths, comps, self.shard_threads)
-        if shard.failed:
-            shard.close()
-            return [self._load(path) for path in paths]
-        # the words go to page-locked memory here, on the reader's side of the pipeline (the driving thread only creates the
-        # batch): 0.6 GB per chunk of 512 assemblies, copied by the library's threads
-        pb = self._pinned(shard.total_words)
-        shard.words_into(pb.array, self.shard_threads)
-        tables = tuple(np.array(t) for t in shard.tables())
-        total = shard.total_words
-        shard.close()
-        return (tables, total, pb), ids
-
-    # -- stage 2: one chunk's packed words -> page-locked memory -> device (asynchronous upload) ---------------------------------
-    def _pinned(self, n_words: int):
-        from kaptive_amd import _native
-
-        with self._pin_lock:  # (reader threads take buffers, the driving thread gives them back)
-            self._pin_need = max(self._pin_need, n_words)
-            for i, pb in enumerate(self._pins):
-                if len(pb.array) >= n_words:
-                    return self._pins.pop(i)
-        return _native.PinnedBuffer(n_words + n_words // 8, np.uint32, lazy=True)  # page-locked in _make_batch, once it is full
-
-    def _locked(self, pb, n_words: int):
-        """``pb`` page-locked -- or, on a host that refuses to register it, a block of the runtime's own with the same words."""
-        from kaptive_amd import _native
-
-        try:
-            pb.lock()
-            return pb
-        except _native.NativeError:
-            eager = _native.PinnedBuffer(len(pb.array), np.uint32)
-            eager.array[:n_words] = pb.array[:n_words]
-            pb.close()
-            return eager
-
-    def _make_batch(self, genomes):
-        if isinstance(genomes, tuple):  # ((tables, words, pinned buffer), ids) of _load_shard
-            tables, total, pb = genomes[0]
-            pb = self._locked(pb, total)
-            batch = self.engine.ctx.batch(None, pinned_words=pb.array[:total], tables=tables)
-            batch._pin = pb
-            return batch
-        packed = [g.packed() for g in genomes]
-        sizes = [len(pa.words) for pa in packed]
-        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        pb = self._pinned(int(offs[-1]))
-
-        def copy(i):
-            pb.array[offs[i] : offs[i + 1]] = packed[i].words
-
-        list(self.copiers.map(copy, range(len(packed))))  # (numpy copies of this size run without the interpreter lock; an executor of their own: the readers' queue holds the next chunks' files)
-        pb = self._locked(pb, int(offs[-1]))
-        batch = self.engine.ctx.batch(packed, pinned_words=pb.array[: int(offs[-1])])
-        batch._pin = pb
-        return batch
-
-    def _source(self, chunks):
-        """(batch, ids, genomes) per chunk, as an iterator with ``ready()`` (the engine's typing window asks before it would
-        wait): the files of the next PREFETCH chunks are being read while a chunk is handed on; their batches are created
-        (uploads enqueued) as soon as the reads are through."""
-        return _ChunkSource(self, chunks)
-
-    # -- stage 3: records -> bytes ------------------------------------------------------------------------------------------------
-    def run(self, chunks):
-        """Yields ``(k, ((keyword, outputs), ...))`` for every ``(k, paths)`` of ``chunks``, in order: one entry per database
-        in order (``self.keywords``), where ``outputs`` maps "tsv" / "pha4ge" / "json" / ... to the bytes this chunk adds to that
-        database's stream.  Per-assembly fasta files are written here: to ``DIR/<keyword>/``, or to ``DIR`` itself for the
-        keyword ``None`` of a run without ``--db``."""
-        from collections import deque
-
-        args = self.args
-        self._order = []
-        groups = tuple(t.engine.group for t in self.typers)  # (a MultiSerotyper's typers view the shared engine, one group each)
-
-        def render(bt, keyword, group, aligned) -> dict:
-            out = {}
-            if aligned is not None:
-                out["paf"] = hits_to_paf(self.engine.view(group), bt.genomes, *aligned, cs_tag=self.paf_cs, eqx=self.paf_eqx)
-            for r in REPORTS:
-                if self.want[r.name]:
-                    out[r.name] = getattr(bt, r.tsv)()
-            if self.want_distances:  # (a payload for the parent to merge, not bytes for a file; no --aligned table is made of the rows)
-                from kaptive_amd.distances import LocusRows
-
-                chunk_rows = LocusRows(bt.typer._db)
-                chunk_rows.add(bt)
-                out[LOCUS_ROWS_KEY] = chunk_rows.state()
-            if self.want_tsv:
-                out["tsv"] = bt.tsv()
-            if getattr(args, "pha4ge", None):
-                out["pha4ge"] = bt.pha4ge()
-            if getattr(args, "json", None):  # one native call per batch (kp_format_json): byte for byte result_to_json of every result
-                out["json"] = bt.jsonl()
-            if self.fasta_outputs:  # a file per assembly and kind, as the reference writes them; the records come per batch (kp_format_fasta)
-                wanted = {flag: (Path(d) if keyword is None else Path(d) / keyword, ext)
-                          for flag, ext in (("loci", "fna"), ("genes", "ffn"), ("proteins", "faa")) if (d := getattr(args, flag, None))}
-                for flag, per_asm in bt.fasta(tuple(wanted)).items():
-                    d, ext = wanted[flag]
-                    d.mkdir(parents=True, exist_ok=True)
-                    for genome, blob in zip(bt.ids, per_asm):
-                        (d / f"{genome}_{FILE_SUFFIX}.{ext}").write_bytes(blob)
-            return out
-
-        # The rows of a chunk are rendered beside the driving thread (the native formatters release the interpreter lock: 35 MB
-        # of JSON per 512 assemblies would otherwise stand between two submissions to the device); they leave in input order.
-        rendering: deque = deque()
-        done = 0
-
-        def job(bts, aligned) -> tuple:  # every database's records from the one alignment pass of the batch
-            return tuple((kw, render(bt, kw, g, aligned)) for kw, g, bt in zip(self.keywords, groups, bts))
-
-        for bts, batch in self.engine._window(self.typers, groups, self._source(chunks)):
-            pb, batch._pin = getattr(batch, "_pin", None), None
-            aligned = (*batch.hits(), *batch.cigars(), *(batch.cs() if self.paf_cs or self.paf_eqx else ())) if self.want_paf else None  # (the batch's results go with it)
-            batch.close()  # (waits for whatever of the batch is still in flight: the pinned words are free after it)
-            if pb is not None:
-                self._give_back(pb)
-            rendering.append(self.formatters.submit(job, bts, aligned))
-            while rendering and (rendering[0].done() or len(rendering) > 2):
-                yield self._order[done], rendering.popleft().result()
-                done += 1
-        while rendering:
-            yield self._order[done], rendering.popleft().result()
-            done += 1
-
-
-class _ChunkSource:
-    """Reads ahead of the device: PREFETCH + 1 chunks are with the reader threads at any time (started by
-    ``_TypingPipeline.__init__`` -- as many as its read-ahead budget allows -- before the device context even exists)."""
-
-    def __init__(self, pipe: "_TypingPipeline", chunks) -> None:
-        from collections import deque
-
-        self.pipe = pipe
-        self.it = iter(chunks)
-        self._prev = None
-        self.reading: deque = deque(pipe._early)  # (k, future or list of futures)
-        pipe._early = []
-        for _ in self.reading:
-            next(self.it)  # (those chunks are already being read)
-        while len(self.reading) < pipe.PREFETCH + 1 and self._start_read():
-            pass
-
-    def _start_read(self) -> bool:
-        try:
-            k, paths = next(self.it)
-        except StopIteration:
-            return False
-        self.pipe._unread -= 1
-        self.reading.append((k, self.pipe.submit_read(paths)))
-        return True
-
-    def ready(self) -> bool:
-        """Whether ``next()`` would return without waiting for a read."""
-        if not self.reading:
-            return True  # (nothing left: StopIteration comes at once)
-        futures = self.reading[0][1]
-        return all(f.done() for f in futures) if isinstance(futures, list) else futures.done()
-
-    def __iter__(self):
-        return self
-
-    def __next__(self):
-        if not self.reading:
-            raise StopIteration
-        k, futures = self.reading.popleft()
-        genomes = [f.result() for f in futures] if isinstance(futures, list) else futures.result()
-        self._start_read()
-        pipe = self.pipe
-        ids = genomes[1] if isinstance(genomes, tuple) else [g.id for g in genomes]
-        pipe.marks.setdefault("first_chunk_parsed", time.perf_counter())
-        batch = pipe._make_batch(genomes)
-        pipe.marks.setdefault("first_batch_created", time.perf_counter())
-        pipe._order.append(k)
-        # the batch before this one has had its upload enqueued for at least a chunk's parse: its page-locked words go back to
-        # the pool now, not when its rows are written (a run then page-locks 3 GB instead of 5: a second less to lock at the
-        # start and to unlock at exit)
-        prev, self._prev = self._prev, batch
-        if prev is not None:
-            pipe.release_pin(prev)
-        return batch, ids, genomes if pipe.objects else None
-
-
-def hits_to_paf(engine, genomes, hits, hit_off, ops, cigar_off, cs=None, cs_off=None, cs_tag: bool = False, eqx: bool = False) -> bytes:
-    """PAF lines (``--paf``) of a batch's hit table for the database ``engine`` views: its genes' hits of every genome, in
-    the table's order, genomes in the batch's order.  Column-wise: the rows of the database are picked by a mask and the
-    lines come from one native call (``_native.format_paf``; with ``--cs`` / ``--eqx`` ``_native.format_paf_tags``, which
-    takes the batch's cs bytes ``cs`` / ``cs_off`` as well)."""
-    from kaptive_amd import _native
-    from kaptive_amd.core.alignment import Cigars, _ragged_take
-
-    lo, hi = engine.gene_ranges[engine.group]
-    keep = (hits["gene"] >= lo) & (hits["gene"] < hi)
-    if not keep.all():
-        kept_before = np.concatenate([[0], np.cumsum(keep)])
-        hit_off = kept_before[hit_off]
-        cig = Cigars.from_offsets(ops, cigar_off)[keep]
-        ops, cigar_off = cig.data, np.concatenate([[0], np.cumsum(cig.lengths, dtype=np.int64)])
-        if cs_off is not None:  # the cs bytes are sliced as the ops are
-            cs_off = np.asarray(cs_off, np.int64)
-            cs_len = np.diff(cs_off)
-            cs = _ragged_take(np.asarray(cs, np.uint8), cs_off[:-1], cs_len, np.flatnonzero(keep))[0]
-            cs_off = np.concatenate([[0], np.cumsum(cs_len[keep], dtype=np.int64)])
-        hits = hits[keep].copy()
-        hits["gene"] -= lo
-    first = np.concatenate([[0], np.cumsum([len(g.contigs.ids) for g in genomes])])
-    names = [n for g in genomes for n in g.contigs.ids]
-    lengths = np.concatenate([np.asarray(g.contigs.lengths, np.int32) for g in genomes]) if genomes else np.zeros(0, np.int32)
-    if cs_tag or eqx:
-        return _native.format_paf_tags(engine.db.genes.ids, engine.db.genes.lengths, names, lengths, first, hits, hit_off, ops, cigar_off,
-                                       cs, cs_off, (_native.PAF_CS if cs_tag else 0) | (_native.PAF_EQX if eqx else 0))
-    return _native.format_paf(engine.db.genes.ids, engine.db.genes.lengths, names, lengths, first, hits, hit_off, ops, cigar_off)
-
-
-LOCUS_ROWS_KEY = "locus_rows"  # a chunk's outputs: the ``LocusRows.state()`` of its assemblies (PAIR_TABLES); never written to a file
 PAIR_TABLES = ("distances", "clusters", "mst", "newick", "nj", "sites", "snp_alignment")  # the flags whose tables are made of the run's locus rows
+
+
+def pipeline_options(args: argparse.Namespace, threads: "int | None" = None, read_ahead_share: int = 1) -> PipelineOptions:
+    """What a pipeline of this command line reads (an option declared with ``default=SUPPRESS`` is absent from the namespace unless
+    given).  ``threads``, ``read_ahead_share``: this pipeline's part of the host, where several device processes share it."""
+    def on(name) -> bool:
+        return bool(getattr(args, name, None))
+
+    return PipelineOptions(
+        threads=args.threads if threads is None else threads, read_ahead_share=read_ahead_share, tsv=bool(args.out), pha4ge=bool(args.pha4ge),
+        json=bool(args.json), loci=args.loci or None, genes=args.genes or None, proteins=args.proteins or None, paf=on("paf"), cs=on("cs"), eqx=on("eqx"),
+        reports=frozenset(r.name for r in REPORTS if on(r.name)), locus_rows=any(on(f) for f in PAIR_TABLES),
+        max_other_genes=args.max_other_genes, min_completeness=args.min_completeness, below_threshold=args.below_threshold,
+        partial_edge_tolerance=args.partial_edge_tolerance, rescue_flank=getattr(args, "rescue_flank", None), rescue_min_score=getattr(args, "rescue_min_score", None))  # fmt: skip
 
 
 class _RunDistances:
@@ -737,31 +316,7 @@ class _RunDistances:
                         h.write(text)
 
 
-def _read_ahead_bytes() -> int:
-    """How much packed input the readers may hold before the device has taken any (KAPTIVE_AMD_READ_AHEAD_GB; default: a
-    quarter of what the machine / the cgroup has available, at most 12 GB)."""
-    if v := os.environ.get("KAPTIVE_AMD_READ_AHEAD_GB"):
-        return int(float(v) * 2**30)
-    avail = 64 * 2**30
-    try:
-        with open("/proc/meminfo") as f:
-            for line in f:
-                if line.startswith("MemAvailable:"):
-                    avail = int(line.split()[1]) * 1024
-                    break
-        for name in ("/sys/fs/cgroup/memory.max", "/sys/fs/cgroup/memory/memory.limit_in_bytes"):
-            if os.path.exists(name):
-                with open(name) as f:
-                    text = f.read().strip()
-                if text.isdigit():
-                    avail = min(avail, int(text))
-                break
-    except (OSError, ValueError):
-        pass
-    return min(12 * 2**30, avail // 4)
-
-
-def _device_worker(args: argparse.Namespace, device: int, chunks: list, conn, devices=None, nodes=None) -> None:
+def _device_worker(options: PipelineOptions, databases: list, device: int, chunks: list, conn, devices=None, nodes=None) -> None:
     """One process per device (``--devices a,b,...``): types its chunks and sends ``(k, outputs)`` up the pipe; an
     exception travels the same way and ends the worker.  Before it reads a file the process moves to its device's share of
     the granted CPUs on the device's NUMA node (kaptive_amd/affinity.py): reader threads and page-locked shards follow."""
@@ -774,7 +329,7 @@ def _device_worker(args: argparse.Namespace, device: int, chunks: list, conn, de
         print(f"[kaptive_amd] device {device}: NUMA node {placed['numa_node']}, {len(placed['cpus'] or [])} CPUs, pinned={placed['applied']}", file=sys.stderr)
     pipe = None
     try:
-        pipe = _TypingPipeline(args, device, chunks=chunks)
+        pipe = TypingPipeline(options, device, databases=databases, chunks=chunks)
         for k, out in pipe.run(chunks):
             conn.send((k, out))
         conn.send(None)
@@ -923,6 +478,7 @@ def run_type(args: argparse.Namespace) -> int:
     for flag in (*(r.name for r in REPORTS), *PAIR_TABLES):
         if getattr(args, "db", None) and (v := getattr(args, flag, None)) and _is_stdout(v):
             raise ValueError(f"--{flag.replace('_', '-')} with --db writes a table per database: it needs a file name, not stdout")
+    databases = [args.database, *(args.db or [])]
     dist = _RunDistances(args) if any(getattr(args, f, None) for f in PAIR_TABLES) else None
     run_dbs = None  # the databases of the run, where this process has loaded them (one device)
     outputs = _PerDatabaseOutputs(args)  # (without --db its files are open, headers written, from here on)
@@ -942,7 +498,7 @@ def run_type(args: argparse.Namespace) -> int:
 
     try:
         if len(devices) == 1:
-            pipe = _TypingPipeline(args, devices[0], chunks=chunks)
+            pipe = TypingPipeline(pipeline_options(args), devices[0], databases=databases, chunks=chunks)
             try:
                 run_dbs = [t._db for t in pipe.typers]
                 for k, out in pipe.run(chunks):
@@ -964,15 +520,14 @@ def run_type(args: argparse.Namespace) -> int:
             conns, procs = [], []
             from kaptive_amd import usable_cpus
 
-            # the device processes share the host: each gets its part of the reader-thread budget
-            args.threads = max(1, (args.threads or usable_cpus()) // len(devices))
-            args.read_ahead_share = len(devices)  # ... and of the read-ahead memory
+            # the device processes share the host: each gets its part of the reader-thread budget and of the read-ahead memory
+            options = pipeline_options(args, max(1, (args.threads or usable_cpus()) // len(devices)), len(devices))
             from kaptive_amd import affinity
 
             nodes = affinity.device_numa_nodes(list(devices))  # asked once, in a process of its own (0.3 s beside the first reads)
             for i, d in enumerate(devices):
                 parent, child = ctx.Pipe(duplex=False)
-                proc = ctx.Process(target=_device_worker, args=(args, d, chunks[i :: len(devices)], child, list(devices), nodes), daemon=True)
+                proc = ctx.Process(target=_device_worker, args=(options, databases, d, chunks[i :: len(devices)], child, list(devices), nodes), daemon=True)
                 proc.start()
                 child.close()
                 conns.append(parent)

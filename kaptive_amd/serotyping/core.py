@@ -41,6 +41,7 @@ class Serotyper:
         partial_edge_tolerance: int = 5,
         *,
         device: int = 0,
+        ctx: Any = None,
         aligner: Callable[[GenomeAssembly], Alignments] | None = None,
         protein_aligner: Callable[[Sequences, Sequences], Any] | None = None,
         variants: bool = False,
@@ -53,7 +54,8 @@ class Serotyper:
         distances: bool = False,
     ) -> None:
         """``preset`` and ``scoring_metric`` are accepted and ignored, as in the reference.
-        ``aligner`` / ``protein_aligner`` replace the HIP stages; tests use them to feed recorded hits.  ``variants``: the engine
+        ``aligner`` / ``protein_aligner`` replace the HIP stages; tests use them to feed recorded hits.  ``ctx``: a context of
+        ``device`` created ahead of time, or a future of one, for the engine to take (``Engine(db, ctx=...)``).  ``variants``: the engine
         this typer creates also leaves the variant records of the kept hits (``Engine(db, variants=True)``); ``breakpoints``: it leaves
         the breakpoint records of the kept lists (``Engine(db, breakpoints=True)``); ``alleles``: it leaves the allele digests of the
         kept records and the locus pieces (``Engine(db, alleles=True)``); ``aligned``: it leaves the aligned rows of the kept hits
@@ -85,7 +87,7 @@ class Serotyper:
         self.scoring_metric = scoring_metric
         self.min_gene_coverage = min_gene_coverage
         self.partial_edge_tolerance = partial_edge_tolerance
-        self._device = device
+        self._device, self._ctx = device, ctx
         self._aligner = aligner
         self._protein_aligner = protein_aligner
         self._engine = None
@@ -386,26 +388,22 @@ class Serotyper:
 
 def _make_engine(typer, db):
     """The engine of a ``Serotyper`` (``db``: its database) or a ``MultiSerotyper`` (its databases), made for the reports the typer
-    was made for -- on the context the command line started early, where it did (``_ctx_early``: a future of
-    ``_native.Context``, kaptive_amd/cli.py)."""
+    was made for -- on the context the typer was given, where it was (a future of one is waited for here)."""
     from kaptive_amd.engine import Engine
 
-    early, typer._ctx_early = getattr(typer, "_ctx_early", None), None
-    return Engine(db, device=typer._device, ctx=early.result() if early is not None else None, variants=typer._variants,
+    ctx, typer._ctx = typer._ctx, None  # (the engine's from here on: a later engine of this typer makes its own)
+    return Engine(db, device=typer._device, ctx=ctx.result() if hasattr(ctx, "result") else ctx, variants=typer._variants,
                   breakpoints=typer._breakpoints, alleles=typer._alleles, aligned=typer._aligned, rescue=typer._rescue,
                   rescue_flank=typer._rescue_flank)  # fmt: skip
 
 
 def _tsv_chunks(typer, paths: Sequence[str | Path], batch_size: int, threads: int) -> "Iterator[tuple[bytes, ...]]":
     """``tsv_from_files`` of a ``Serotyper`` or a ``MultiSerotyper``: per chunk, one block of ``KaptiveRow`` bytes per database."""
-    import argparse
+    from kaptive_amd.pipeline import PipelineOptions, TypingPipeline
 
-    from kaptive_amd.cli import _TypingPipeline
-
-    args = argparse.Namespace(out="-", threads=threads, json=None, loci=None, genes=None, proteins=None, pha4ge=None)
     paths = [str(p) for p in paths]
     chunks = [(k, paths[i : i + batch_size]) for k, i in enumerate(range(0, len(paths), batch_size))]
-    pipe = _TypingPipeline(args, typer._device, typer=typer)  # (the device is the one the typer was made for)
+    pipe = TypingPipeline(PipelineOptions(tsv=True, threads=threads), typer._device, typer=typer)  # (the device is the one the typer was made for)
     try:
         for _, outs in pipe.run(chunks):
             yield tuple(out["tsv"] for _, out in outs)
@@ -451,6 +449,7 @@ class MultiSerotyper:
         partial_edge_tolerance: int = 5,
         *,
         device: int = 0,
+        ctx: Any = None,
         variants: bool = False,
         breakpoints: bool = False,
         alleles: bool = False,
@@ -460,11 +459,11 @@ class MultiSerotyper:
         rescue_min_score: "int | None" = None,
         distances: bool = False,
     ) -> None:
-        """``distances``: every one of ``.serotypers`` keeps the ``locus_rows`` of its database (it implies ``aligned``); they feed the
+        """``ctx``: as ``Serotyper``'s, for the shared engine.  ``distances``: every one of ``.serotypers`` keeps the ``locus_rows`` of its database (it implies ``aligned``); they feed the
         distance table and the cluster table alike."""
         self.dbs = list(dbs)
         check_databases(self.dbs)
-        self._device = device
+        self._device, self._ctx = device, ctx
         self._variants = bool(variants)
         self._breakpoints = bool(breakpoints)
         self._alleles = bool(alleles)

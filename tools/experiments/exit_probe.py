@@ -10,12 +10,12 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
     t0 = time.perf_counter()
     cli.FAST_EXIT = mode != "slow"
     # monkeypatch close to time steps
-    orig_close = cli._TypingPipeline.close
+    orig_close = cli.TypingPipeline.close
     def timed_close(self, fast=False):
         t = time.perf_counter()
         if mode == "free_pins":
-            with self._pin_lock:
-                pins, self._pins = self._pins, []
+            with self.pins.lock:
+                pins, self.pins.kept = self.pins.kept, []
             for pb in pins: pb.close()
             print(f"[child] closed {len(pins)} pooled buffers in {time.perf_counter()-t:.3f}s", file=sys.stderr)
         if mode == "free_all":
@@ -23,7 +23,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
             print(f"[child] full close in {time.perf_counter()-t:.3f}s", file=sys.stderr)
             return
         orig_close(self, fast=fast)
-    cli._TypingPipeline.close = timed_close
+    cli.TypingPipeline.close = timed_close
     rc = cli.main(argv)
     from kaptive_amd import _native
     print(f"[child] pinned bytes at exit {_native.lib().kp_host_pinned_bytes()/2**30:.2f} GB, threads {len(os.listdir('/proc/self/task'))}, "
