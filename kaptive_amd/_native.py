@@ -1031,6 +1031,8 @@ def lib() -> C.CDLL:
                     getattr(h, f).restype = C.c_int64
                 h.kp_ctx_destroy.restype = None
                 h.kp_batch_destroy.restype = None
+                h.kp_dist_destroy.restype = None
+                h.kp_dist_tree_rounds.restype = C.c_int32
                 h.kp_batch_device_words.restype = C.c_void_p
                 h.kp_host_free.restype = None
                 h.kp_host_free.argtypes = [C.c_void_p]
@@ -1467,9 +1469,7 @@ class Distances:
     def close(self) -> None:
         if getattr(self, "_h", None):
             if getattr(self.ctx, "_h", None):  # (as a batch: without its context there is nothing left to free)
-                h = lib()
-                h.kp_dist_destroy.restype = None
-                h.kp_dist_destroy(self._h)
+                lib().kp_dist_destroy(self._h)
             self._h = None
 
     __del__ = close
@@ -1523,9 +1523,7 @@ class Distances:
 
     def tree_rounds(self) -> int:
         """The rounds the last ``tree`` ran on the device, the empty last one included (kp_dist_tree_rounds)."""
-        h = lib()
-        h.kp_dist_tree_rounds.restype = C.c_int32
-        return int(h.kp_dist_tree_rounds(self._h))
+        return int(lib().kp_dist_tree_rounds(self._h))
 
     def nj_taxa(self, min_compared: int = DIST_MIN_COMPARED) -> int:
         """How many taxa ``nj`` would join (the counting form of kp_dist_nj): the rows that hold a base in at least half of the

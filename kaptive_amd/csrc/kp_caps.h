@@ -271,7 +271,7 @@ inline bool kp_caps_set_option(KpCapOptions &o, KpLearnt &L, std::vector<KpRunCa
 // most rows of a distance matrix (kp_dist_create; kp_spec.h, DISTANCES).  The pair kernel's grid holds one block per tile on or
 // above the diagonal in its x dimension, 256 lanes each: with nt = ceil(rows / 64) tile rows that is nt (nt + 1) / 2 blocks.  HIP
 // launches no grid whose gridDim.x * blockDim.x reaches 2^32, so the blocks must stay below 2^24: nt <= 5792, some 370 000 rows.
-// 2^18 rows are nt = 4096 and 8 390 656 blocks, 2 148 007 936 work items -- half the limit (kp_dist.hip asserts it) --; the
+// 2^18 rows are nt = 4096 and 8 390 656 blocks, 2 148 007 936 work items -- half the limit (kp_dist_handle.h asserts it) --; the
 // listing's count table then has rows * nt = 2^30 entries, indexed in 64 bits, and every tile index fits an int32.
 constexpr int32_t KP_DIST_MAX_ROWS = 1 << 18;
 

@@ -1,6 +1,6 @@
 // kp_clust.h -- single-linkage clusters and nearest neighbours of locus rows (kp_spec.h, CLUSTERS), written once as plain functions:
 // the first level of a pair, the nearest key, find / unite over a parent array, and the cluster number of a label.  The cluster
-// kernel of kp_dist.hip and its host share them.  No HIP header: tests/native_harness compiles it with g++.
+// kernel of kp_dist_graph.hip and its host share them.  No HIP header: tests/native_harness compiles it with g++.
 #pragma once
 
 #include <stdint.h>

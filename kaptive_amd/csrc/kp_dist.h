@@ -1,7 +1,7 @@
 // kp_dist.h -- pairwise distances between locus rows (kp_spec.h, DISTANCES), written once as plain functions: the padding mask of a
 // gene's last block, the bit planes of a block and of four blocks (one plane word: 64 columns), the three counts of one plane word
 // of a pair and of a whole pair (from planes; from two block rows), the key that loses every minimum, the listing predicate, and the
-// tile geometry the pair kernel (kp_dist.hip) and its host share.  No HIP header: tests/native_harness compiles it with g++.
+// tile geometry the tile kernels (kp_dist_handle.h, kp_dist.hip) and their host share.  No HIP header: tests/native_harness compiles it with g++.
 #pragma once
 
 #include <stddef.h>

@@ -1,6 +1,6 @@
 // kp_nj.h -- neighbour-joining over locus rows (kp_spec.h, NJ), written once as plain functions: the taxon predicate, the distance of
 // a pair, SUM64, the Q, length and update expressions, the order of the pick, a serial host NJ over a dense matrix, and the taxa and
-// the matrix of a matrix of blocks.  The NJ kernels of kp_dist.hip and their host share them.  No HIP header: tests/native_harness
+// the matrix of a matrix of blocks.  The NJ kernels of kp_dist_nj.hip and their host share them.  No HIP header: tests/native_harness
 // compiles it with g++.
 //
 // Every floating-point operation of the section is rounded to binary64 on its own.  hipcc contracts a * b + c into one fused

@@ -2,7 +2,7 @@
 // plane word, the bit-sliced vertical counter a lane of the profile kernel adds them into, the bit-matrix transposition that turns
 // the counters of a wave's 64 lanes into per-column counts, the site predicate with its flag, ALLELES / MAJOR / INFORMATIVE, the
 // mapping from a matrix column to its gene, the codes of a site row's block, the record store, and the geometry the kernels
-// (kp_dist.hip) and their host share.  No HIP header: tests/native_harness compiles it with g++.
+// (kp_dist_sites.hip) and their host share.  No HIP header: tests/native_harness compiles it with g++.
 #pragma once
 
 #include <stddef.h>

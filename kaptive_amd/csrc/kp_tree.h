@@ -1,6 +1,6 @@
 // kp_tree.h -- the minimum spanning forest of locus rows (kp_spec.h, TREE), written once as plain functions: the packed edge key, the
 // predicate for a matrix that fits it, the bound on Boruvka's rounds, and a serial host
-// Boruvka over a matrix of blocks.  The tree kernels of kp_dist.hip and their host share them.  No HIP header:
+// Boruvka over a matrix of blocks.  The tree kernels of kp_dist_graph.hip and their host share them.  No HIP header:
 // tests/native_harness compiles it with g++.
 #pragma once
 

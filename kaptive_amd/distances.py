@@ -3,7 +3,7 @@
 Every other report answers a question about one assembly; this one is about pairs: which isolates carry the same or nearly the same
 locus, and how many bases apart they are.  ``LocusRows`` collects, batch after batch, one LOCUS ROW per assembly -- the aligned rows of
 the primary kept records of its best locus's genes, strung together in database order, padding flagged -- and, when the run is over,
-hands the rows of every locus to the device as one matrix (``_native.Distances``: kp_dist.hip compares them all against all).  Two
+hands the rows of every locus to the device as one matrix (``_native.Distances``: kp_dist.hip compares them all against all; kp_dist_graph.hip, kp_dist_nj.hip and kp_dist_sites.hip hold the reports below).  Two
 tables come of a matrix: the listed pairs (``distances`` / ``tsv``) and, with no pair listed, every row's single-linkage cluster at a
 few thresholds and its nearest neighbour (``clusters`` / ``clusters_tsv``; include/kp_spec.h, CLUSTERS), and the minimum spanning forest
 of the rows as an edge table and as Newick text (``tree`` / ``tree_tsv`` / ``newick_tsv``; include/kp_spec.h, TREE), and the

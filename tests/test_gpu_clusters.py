@@ -1,4 +1,4 @@
-"""Clusters and nearest neighbours of locus rows on the device (include/kp_spec.h, CLUSTERS; kaptive_amd/csrc/kp_dist.hip) against the
+"""Clusters and nearest neighbours of locus rows on the device (include/kp_spec.h, CLUSTERS; kaptive_amd/csrc/kp_dist_graph.hip) against the
 numpy restatement of tests/clusters_util.py: integers, order and bytes, exactly.  Random populations at every shape at which the
 epilogue takes another path; a chain, in row order and permuted, which a union-find that loses a hook or a nearest pass that forgets
 one side of a pair gets wrong; stars and ties across tiles; the refusals of the entry point and the state it must leave alone; then

@@ -1,4 +1,4 @@
-"""The neighbour-joining tree of locus rows on the device (include/kp_spec.h, NJ; kaptive_amd/csrc/kp_dist.hip) against the NumPy
+"""The neighbour-joining tree of locus rows on the device (include/kp_spec.h, NJ; kaptive_amd/csrc/kp_dist_nj.hip) against the NumPy
 restatement in tests/nj_util.py: taxa and records as bytes -- node ids, order and every bit of every length.  Random populations at
 every shape at which the tile epilogue, the row sums or the pick take another path; identical rows, where every Q ties and only the
 slot order decides; a planted additive tree; the state the call must leave alone; what it allocates; its refusals; then the whole

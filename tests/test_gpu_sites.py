@@ -1,4 +1,4 @@
-"""The variable sites of locus rows on the device (include/kp_spec.h, SITES; kaptive_amd/csrc/kp_dist.hip) against the restatement in
+"""The variable sites of locus rows on the device (include/kp_spec.h, SITES; kaptive_amd/csrc/kp_dist_sites.hip) against the restatement in
 tests/sites_util.py: integers, order and bytes, exactly.  Random populations with planted columns at every number of rows at which
 a lane, a wave, a workgroup or a slab fills up and at every row width at which a plane word is short; matrices without a site; the
 property that ties the site matrix to DISTANCES; the state the calls must leave alone and their refusals; then the whole route on

@@ -1,4 +1,4 @@
-"""The minimum spanning forest of locus rows on the device (include/kp_spec.h, TREE; kaptive_amd/csrc/kp_dist.hip) against Kruskal in
+"""The minimum spanning forest of locus rows on the device (include/kp_spec.h, TREE; kaptive_amd/csrc/kp_dist_graph.hip) against Kruskal in
 tests/tree_util.py: integers, order and bytes, exactly.  Random populations at every shape at which the epilogue takes another path;
 identical rows, where every key ties on differences and only (a, b) decides; a chain whose components merge in pairs, so that the
 rounds run as long as rounds can; two rows, whose one edge both sides choose; the two properties that tie the forest to CLUSTERS;

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the neighbour-joining tree costs on the device and on the host (include/kp_spec.h, NJ; kaptive_amd/csrc/kp_dist.hip,
+"""What the neighbour-joining tree costs on the device and on the host (include/kp_spec.h, NJ; kaptive_amd/csrc/kp_dist_nj.hip,
 kp_nj.h), on the population of tools/distances_probe.py: synthetic locus rows of NB = 1 600 blocks (25 600 columns) without N or
 GAP, so every row is a taxon.
 

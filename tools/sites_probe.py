@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What the variable sites cost on the device beside the count pass of the same handle (include/kp_spec.h, SITES;
-kaptive_amd/csrc/kp_dist.hip): R = 4096 synthetic locus rows of the largest locus of the ``kpsc_k`` synthetic database.
+kaptive_amd/csrc/kp_dist_sites.hip): R = 4096 synthetic locus rows of the largest locus of the ``kpsc_k`` synthetic database.
 
     python tools/sites_probe.py [--rows 4096] [--repeats 5]
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/sites_probe.py      # the kernels' own times, in a run of its own

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """What the minimum spanning forest costs on the device beside the count pass of the same matrix (include/kp_spec.h, TREE;
-kaptive_amd/csrc/kp_dist.hip), at the shape of tools/distances_probe.py: R = 10 000 synthetic locus rows of NB = 1 600 blocks
+kaptive_amd/csrc/kp_dist_graph.hip), at the shape of tools/distances_probe.py: R = 10 000 synthetic locus rows of NB = 1 600 blocks
 (25 600 columns), 5e7 pairs.
 
     python tools/tree_probe.py [--rows 10000] [--blocks 1600] [--repeats 5]           # clusters of 100 rows around a founder each
