@@ -5,7 +5,7 @@
 // Every table is a heap block of exactly the size the call may read or write: an access past an end stops the program.  It makes
 // locus rows of 1 to 70 blocks -- short last plane words included -- from random codes, compares the counts of every pair, summed
 // plane word by plane word, with a walk column by column; checks the padding mask of every length and the tile of every index of
-// small grids; then formats a table twice (sizing call with cap 0, then into a buffer of exactly the size returned) and checks
+// small grids and of the grids of 4097, 16385 and 2^18 rows; then formats a table twice (sizing call with cap 0, then into a buffer of exactly the size returned) and checks
 // every refusal.
 #include <cstdio>
 #include <cstdlib>
@@ -84,6 +84,22 @@ int main() {
                 CHECK(ti == i && tj == j);
             }
         CHECK(t == kp_dist_tiles(nt));
+    }
+    // every tile of the grids of 4097 rows, of 16385 rows and of KP_DIST_MAX_ROWS rows (8 390 656 tiles: the square root of
+    // kp_dist_tile_of at its largest argument) against two nested counters
+    for (const int64_t nt : {(int64_t)65, (int64_t)257, (int64_t)4096}) {
+        int64_t t = 0, wrong = 0;
+        for (int64_t i = 0; i < nt; ++i) {
+            CHECK(kp_dist_tile_row_first(i, nt) == t);
+            for (int64_t j = i; j < nt; ++j, ++t) {
+                int32_t ti = -1, tj = -1;
+                kp_dist_tile_of(t, nt, &ti, &tj);
+                wrong += !(ti == i && tj == j);
+            }
+        }
+        CHECK(wrong == 0);
+        CHECK(t == kp_dist_tiles(nt));
+        std::printf("tiles of nt %lld: %lld walked\n", (long long)nt, (long long)t);
     }
     {   // the known answers of the specification
         const Exact<uint64_t> a({0xf0c3010000900e40ull, 0x000f000000000000ull | kp_dist_pad_mask(20)}), b({0xf0c3002000e40390ull, 0x000f000000000000ull | kp_dist_pad_mask(20)});
