@@ -638,6 +638,39 @@ KP_API int kp_dist_nj(kp_ctx *ctx, kp_dist *d, int32_t min_compared, int32_t *ta
 KP_API int64_t kp_format_nj(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
                             const int32_t *rows /* [n_names] or null */, const int32_t *taxa, int32_t n_taxa, const kp_nj_node *nodes, int64_t n_nodes,
                             char *out, int64_t cap);
+/* Bootstrap support of that tree (kp_spec.h, BOOTSTRAP): `replicates` resamplings of the matrix's block columns, each one's
+ * weighted matrix filled by the same tiles and joined by the same loop, a batch of them to every launch, and the splits of every
+ * replicate tree counted against those of the tree the caller holds.
+ *   ref_nodes [n_ref]      : the records of the supported tree, as kp_dist_nj made them for the same handle and min_compared.
+ *   support [cap_support]  : support[t], t < n_ref: the replicates whose tree holds the split of the node record t made, 0 ..
+ *                            replicates; -1 for a record without an inner edge: the last one, and every record of two or three taxa.
+ *   trees [cap_trees]      : null, or the records of every replicate's tree, replicate r's at trees + r * n_ref.
+ *   max_batch              : 0, or the most replicates joined at once; the library's own choice (kp_caps.h: the largest b with
+ *                            b * n_taxa^2 * 8 <= KP_BOOT_MATRIX_BYTES) is never exceeded.  No result depends on it.
+ * The same rows, min_compared, seed and replicates give the same bytes on every run.  KP_EINVAL for a null context or handle, a
+ * handle of another device, replicates outside 1 .. KP_BOOT_MAX_REPLICATES (kp_caps.h), a negative max_batch or cap, a null
+ * ref_nodes or support with n_ref > 0, a null trees with room asked for, n_ref other than the tree of the handle's taxa has
+ * (n_taxa - 2; one for two taxa; none below), a node id of ref_nodes outside the nodes made before its record, cap_support < n_ref,
+ * trees with cap_trees < replicates * n_ref, more than KP_NJ_MAX_TAXA taxa, and a matrix of KP_TREE_MAX_COLUMNS columns or more
+ * (the weighted counts must fit 32 bits).  KP_ENOMEM if the tables of even one replicate -- its matrix above all -- do not fit.
+ * Fewer than four taxa have no inner edge: every support is -1 and nothing is joined, unless trees asks for the replicates'
+ * records.  The call leaves the handle's listing state, its cluster, tree and site tables alone; it numbers the taxa as kp_dist_nj
+ * does and leaves kp_dist_nj's other tables alone.  Three O(n_rows) tables stay with the handle; the matrices, the weights and every
+ * other table of a batch are allocated by the call and freed before it returns.  kp_device_allocations counts neither.
+ *   kp_dist_boot_weights: weights [cap >= 16 * n_blocks]: the weight of every block column in replicate `replicate` (0 ..
+ * KP_BOOT_MAX_REPLICATES - 1) of `seed`, as the device's weight planes hold them.  They depend on the column count alone. */
+KP_API int kp_dist_nj_bootstrap(kp_ctx *ctx, kp_dist *d, int32_t min_compared, uint64_t seed, int32_t replicates, int32_t max_batch /* 0: the library's choice */,
+                                const kp_nj_node *ref_nodes, int64_t n_ref, int32_t *support, int64_t cap_support,
+                                kp_nj_node *trees /* null, or [replicates x n_ref] */, int64_t cap_trees);
+KP_API int kp_dist_boot_weights(kp_ctx *ctx, kp_dist *d, uint64_t seed, int32_t replicate, uint8_t *weights, int64_t cap);
+/* kp_format_nj with support values (host only): the line has a fifth column -- Locus, Assemblies, Taxa, Replicates, Newick -- and
+ * the closing parenthesis of the node record t < n_taxa - 3 made is followed by support[t] as a decimal integer, a count out of
+ * `replicates`: (A:0.1,B:0.2)87:0.05.  The outermost node has no label.  Otherwise byte for byte kp_format_nj's line, and its
+ * refusals; KP_EINVAL also for a null support with records, replicates outside 1 .. KP_BOOT_MAX_REPLICATES, a support outside 0 ..
+ * replicates at a record with an inner edge, and one other than -1 at a record without. */
+KP_API int64_t kp_format_nj_support(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
+                                    const int32_t *rows /* [n_names] or null */, const int32_t *taxa, int32_t n_taxa, const kp_nj_node *nodes, int64_t n_nodes,
+                                    const int32_t *support /* [n_nodes] */, int32_t replicates, char *out, int64_t cap);
 /* Variable sites of a handle's rows (kp_spec.h, SITES): a reduction over the columns of the same planes, no pair looked at.
  *   kp_dist_profile    : out [cap >= 16 * n_blocks]: the profile of every column of the matrix, padding columns included, as
  *                        kp_site records with `column` filled, ascending.  Computed on the handle's first need of it and kept.

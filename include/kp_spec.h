@@ -806,12 +806,50 @@ typedef struct kp_site {
  * (((a:2,b:3):3,c:4):2,e:1,d:2);
  * LIMIT.  KP_NJ_MAX_TAXA = 16384 (kp_caps.h): the dense matrix is n * n doubles, 2 GiB at the limit.  A matrix with more taxa is
  * refused by this call alone, after the taxa are counted and before anything large is allocated.
- * OUT OF SCOPE.  Any distance correction (JC69 and the like); bootstrap; rooting; clamping of negative lengths; BIONJ or FastME;
- * merging fragments of a split gene; trees across loci; any change to an existing report byte. */
+ * OUT OF SCOPE.  Any distance correction (JC69 and the like); rooting; clamping of negative lengths; BIONJ or FastME;
+ * merging fragments of a split gene; trees across loci; any change to an existing report byte.  (Support values: BOOTSTRAP, below.) */
 typedef struct kp_nj_node {
     int32_t a, b, c;   /* node ids: taxa 0 .. n - 1, inner nodes from n on; c = -1 for a binary join */
     int32_t pad_;      /* zero */
     double la, lb, lc; /* their branch lengths; lc = +0.0 for a binary join */
 } kp_nj_node;
+
+/* ---- BOOTSTRAP (optional; support values for the tree of NJ: no byte of NJ or of any other report depends on it) ----
+ * Which inner branches of the neighbour-joining tree mean anything?  A replicate resamples the columns of the matrix with
+ * replacement, its tree is NJ's tree of the resampled matrix, and the support of a branch is the number of replicates whose tree has
+ * it.  Everything below is fixed, so the same rows, min_compared, seed and number of replicates give the same bytes on any run, on
+ * any device and under any batching: the tree of a replicate is a PURE FUNCTION of the matrix, min_compared, the seed and the
+ * replicate's number (kp_boot.h holds the arithmetic once, for the kernels and for g++).
+ *
+ * MIX(x), all of it mod 2^64:  z = x + 0x9e3779b97f4a7c15;  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9;  z = (z ^ (z >> 27)) *
+ * 0x94d049bb133111eb;  MIX = z ^ (z >> 31).
+ * DRAWS.  A matrix of NB blocks has W = 16 NB block columns, padding columns included: no row holds a base in a padding column, so
+ * a draw that lands on one adds nothing to any count.  Replicate r (0-based) makes W draws; draw t, 0 <= t < W, is column
+ * MULHI64(MIX(MIX(MIX(seed) + r) + t), W), MULHI64 the high 64 bits of the 128-bit product -- below W always.  weight[c] =
+ * min(number of draws of c, 255): the clamp does not depend on the order of the draws, and is never reached in practice (a column
+ * drawn 256 times out of W >= 16 draws of W columns).
+ * WEIGHTED COUNTS.  compared_w(a, b) = sum over c of weight[c] * [both rows hold a base at c]; differences_w(a, b) = sum over c of
+ * weight[c] * [both hold a base and the bases differ].  Integers; both are at most the sum of the weights, W, and fit an int32: a
+ * matrix of KP_TREE_MAX_COLUMNS = 2^28 columns or more is refused.  The distance is NJ's DISTANCE of (differences_w, compared_w),
+ * unchanged, with its rule that a pair without a compared column is 0 apart: a replicate can draw such a pair -- the taxon rule
+ * speaks of the unweighted rows and does not exclude it.
+ * TAXA.  Those of NJ, from the unweighted rows.  Weights do not move them: every replicate tree has the taxa of the tree it supports.
+ * TREE.  The tree of a replicate is NJ's tree of its weighted matrix, every rule unchanged: Q, the order of the pick, the lengths, the
+ * update, SUM64 and the slot moves.
+ * SPLITS.  For n >= 4 taxa, record t < n - 3 of a tree made node n + t; its split is the set of taxa below that node, taken on the
+ * side without taxon 0.  These are the tree's n - 3 inner edges; the last record has none, and trees of 2 or 3 taxa have none.  Two
+ * splits are equal when the sets are equal.  The device compares the pair (size, key) instead of the sets: key is the sum mod 2^64
+ * of MIX(k + 1) over the taxa k of the set; the other side of a split has size n - size and key total - key, total the key of all
+ * taxa.  Different sets of one size with one key would be counted as equal, which can only over-count: for keys that behave as
+ * random words that happens with probability at most pairs-compared * 2^-64, pairs-compared <= replicates * (n - 3)^2 < 2^42.
+ * SUPPORT.  support[t] of record t of the supported tree is the number of replicates, 0 .. N, whose tree holds record t's split; -1
+ * for a record without an inner edge.  A count, not a percentage: nothing is rounded.
+ * NEWICK (host only).  NJ's text byte for byte, but the closing parenthesis of the node of record t < n - 3 is followed by support[t]
+ * as a decimal integer -- (A:0.1,B:0.2)87:0.05 --; the outermost node has no label.  The line has the column Replicates before the
+ * Newick text.
+ * LIMITS.  KP_BOOT_MAX_REPLICATES = 10000 replicates a call; KP_NJ_MAX_TAXA taxa, as NJ.  Replicates are joined in batches of the
+ * largest b with b * n * n * 8 <= KP_BOOT_MATRIX_BYTES = 2 GiB (kp_caps.h), and no result depends on b.
+ * OUT OF SCOPE.  Percentages; a consensus tree; transfer bootstrap; resampling of real columns only, of sites only, or by gene;
+ * support for the minimum spanning tree; anything NJ leaves out. */
 
 #endif /* KP_SPEC_H */

@@ -126,6 +126,18 @@ def nj_header() -> bytes:
     return NJ_HEADER
 
 
+# Bootstrap support of that tree (include/kp_spec.h, BOOTSTRAP)
+BOOT_MAX_REPLICATES = 10000  # KP_BOOT_MAX_REPLICATES of kaptive_amd/csrc/kp_caps.h
+BOOT_MATRIX_BYTES = 2 << 30  # KP_BOOT_MATRIX_BYTES: the matrices of one batch of replicates together
+BOOT_MAX_BATCH = 65535  # KP_BOOT_MAX_BATCH: a replicate is a row of a grid
+NJ_SUPPORT_HEADER = b"Locus\tAssemblies\tTaxa\tReplicates\tNewick\n"  # the columns of kp_format_nj_support
+
+
+def nj_support_header() -> bytes:
+    """The header line of the neighbour-joining table with support values (the columns of kp_format_nj_support)."""
+    return NJ_SUPPORT_HEADER
+
+
 # Variable sites of the same rows (include/kp_spec.h, SITES)
 SITE_DTYPE = np.dtype([("column", "<i4"), ("n", "<i4", (4,)), ("n_n", "<i4")])  # kp_site: 24 bytes
 SITES_HEADER = b"Locus\tGene\tPosition\tColumn\tAssemblies\tA\tC\tG\tT\tN\tGap\tAlleles\tMajor\tInformative\n"  # the columns of kp_format_sites
@@ -150,7 +162,7 @@ EXPORTS = (
     "kp_device_count", "kp_device_numa_node", "kp_batch_typing", "kp_batch_proteins", "kp_protein_align", "kp_fasta_pack", "kp_fasta_ingest", "kp_fasta_ingest_many", "kp_fasta_ingest_file", "kp_fasta_ingest_shard", "kp_shard_words_into", "kp_shard_free", "kp_fasta_simd", "kp_pack_contigs",
     "kp_fasta_free", "kp_format_rows", "kp_format_json", "kp_format_fasta", "kp_protein_align_seeded", "kp_randstrobes", "kp_randstrobe_top_hits",
     "kp_dist_create", "kp_dist_count", "kp_dist_pairs", "kp_dist_destroy", "kp_format_distances", "kp_dist_clusters", "kp_format_clusters",
-    "kp_dist_tree", "kp_dist_tree_rounds", "kp_format_newick", "kp_dist_nj", "kp_format_nj",
+    "kp_dist_tree", "kp_dist_tree_rounds", "kp_format_newick", "kp_dist_nj", "kp_format_nj", "kp_dist_nj_bootstrap", "kp_dist_boot_weights", "kp_format_nj_support",
     "kp_dist_profile", "kp_dist_sites_count", "kp_dist_sites", "kp_dist_site_rows", "kp_format_sites", "kp_format_site_rows",
 )  # fmt: skip
 
@@ -794,6 +806,26 @@ def format_nj(locus_name: str, names, taxa, nodes, rows=None) -> bytes:
     return _sized("kp_format_nj", 48 * len(taxa) + len(nm_b) + len(locus) + 64, lambda out, cap: h.kp_format_nj(
         C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows), _p(taxa) if len(taxa) else None,
         C.c_int32(len(taxa)), _p(nodes) if len(nodes) else None, C.c_int64(len(nodes)), out, cap))  # fmt: skip
+
+
+def format_nj_support(locus_name: str, names, taxa, nodes, support, replicates: int, rows=None) -> bytes:
+    """``format_nj``'s line with support values (kp_format_nj_support; host only; no header: ``nj_support_header``): a Replicates
+    column before the Newick text, in which the node of every record with an inner edge is labelled with its ``support`` (int32, one
+    per record, as ``Distances.nj_support`` returns it), a count out of ``replicates``."""
+    nm_b, nm_o = _blob64(names)
+    taxa = np.ascontiguousarray(taxa, np.int32)
+    nodes = np.ascontiguousarray(nodes, dtype=NJ_NODE_DTYPE)
+    support = np.ascontiguousarray(support, np.int32)
+    R = len(nm_o) - 1
+    if (rows is not None and len(rows) != R) or len(support) != len(nodes):
+        raise ValueError("a name for every row and a support value for every record")
+    rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+    locus = locus_name.encode("utf-8")
+    h = lib()
+    h.kp_format_nj_support.restype = C.c_int64
+    return _sized("kp_format_nj_support", 60 * len(taxa) + len(nm_b) + len(locus) + 80, lambda out, cap: h.kp_format_nj_support(
+        C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows), _p(taxa) if len(taxa) else None,
+        C.c_int32(len(taxa)), _p(nodes) if len(nodes) else None, C.c_int64(len(nodes)), _p(support) if len(support) else None, C.c_int32(int(replicates)), out, cap))  # fmt: skip
 
 
 def format_sites(locus_name: str, gene_names, gene_lengths, n_rows: int, sites, genes=None) -> bytes:
@@ -1543,6 +1575,28 @@ class Distances:
         self.ctx._check(lib().kp_dist_nj(self.ctx._h, self._h, C.c_int32(int(min_compared)), _p(taxa) if n else None, C.c_int64(n), C.byref(got),
                                          _p(nodes) if len(nodes) else None, C.c_int64(len(nodes)), C.byref(made)), "kp_dist_nj")  # fmt: skip
         return taxa[: got.value].copy(), nodes[: made.value].copy()
+
+    def nj_support(self, min_compared: int, nodes, replicates: int, seed: int = 1, max_batch: int = 0, trees: bool = False):
+        """int32 [len(nodes)]: the bootstrap support of every record of ``nodes`` -- the tree ``nj(min_compared)`` gave -- out of
+        ``replicates`` resamplings of the block columns under ``seed`` (kp_dist_nj_bootstrap; include/kp_spec.h, BOOTSTRAP): how
+        many replicate trees hold the split of the node the record made, -1 for a record without an inner edge.  ``max_batch``: the
+        most replicates joined at once (0: the library's choice; no result depends on it).  With ``trees`` the result is
+        ``(support, NJ_NODE_DTYPE [replicates, len(nodes)])``: every replicate's records.  The state of every other report is left alone."""
+        nodes = np.ascontiguousarray(nodes, dtype=NJ_NODE_DTYPE)
+        support = np.zeros(len(nodes), np.int32)
+        reps = np.zeros((int(replicates) if 0 < int(replicates) <= BOOT_MAX_REPLICATES else 0, len(nodes)), NJ_NODE_DTYPE) if trees else None
+        self.ctx._check(lib().kp_dist_nj_bootstrap(self.ctx._h, self._h, C.c_int32(int(min_compared)), C.c_uint64(int(seed) & (2**64 - 1)), C.c_int32(int(replicates)),
+                                                   C.c_int32(int(max_batch)), _p(nodes) if len(nodes) else None, C.c_int64(len(nodes)), _p(support) if len(nodes) else None,
+                                                   C.c_int64(len(support)), _p(reps) if trees and reps.size else None, C.c_int64(reps.size if trees else 0)), "kp_dist_nj_bootstrap")  # fmt: skip
+        return (support, reps) if trees else support
+
+    def boot_weights(self, seed: int, replicate: int) -> np.ndarray:
+        """uint8 [16 * n_blocks]: how often every block column of the matrix, padding included, is drawn in replicate ``replicate`` of
+        ``seed``, clamped at 255 (kp_dist_boot_weights): the weights the replicate's counts are made under."""
+        out = np.zeros(16 * self.n_blocks, np.uint8)
+        self.ctx._check(lib().kp_dist_boot_weights(self.ctx._h, self._h, C.c_uint64(int(seed) & (2**64 - 1)), C.c_int32(int(replicate)), _p(out) if len(out) else None,
+                                                   C.c_int64(len(out))), "kp_dist_boot_weights")  # fmt: skip
+        return out
 
     def profile(self) -> np.ndarray:
         """SITE_DTYPE records of all ``16 * n_blocks`` columns of the matrix, padding columns included, ascending (kp_dist_profile;

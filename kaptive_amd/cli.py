@@ -158,6 +158,11 @@ def _add_outputs(p: argparse.ArgumentParser, tsv_flags, include_json: bool) -> N
                        help="Build the neighbour-joining tree, with inferred inner nodes, of the assemblies that carry the same locus "
                             "and hold a base in more than half of it, from the share of differing bases, and write it as Newick "
                             "text, one line per locus, as a TSV table to a file")
+        g.add_argument("--nj-bootstrap", type=int, metavar="N", default=argparse.SUPPRESS,
+                       help="With --nj: resample the columns of every locus N times (1 .. 10000), build every replicate's tree, and "
+                            "label every inner branch with the number of replicate trees that hold it; the table gets a Replicates column")
+        g.add_argument("--nj-seed", type=int, metavar="S", default=argparse.SUPPRESS,
+                       help="With --nj-bootstrap: the seed of the resampling (default: 1); the same seed gives the same table")
         g.add_argument("--sites", metavar="FILE", default=argparse.SUPPRESS,
                        help="List the gene positions at which the assemblies that carry the same locus hold different bases, with the "
                             "number of assemblies that carry each base there, as a TSV table to a file; no pair is looked at for it")
@@ -190,6 +195,16 @@ class _Parser(argparse.ArgumentParser):
                     self.error(f"--{flag.replace('_', '-')} requires " + " or ".join(f"--{b} FILE" for b in beside))
                 if not 0 <= getattr(ns, flag) <= 2**31 - 1:
                     self.error(f"--{flag.replace('_', '-')} is out of range")
+        if getattr(ns, "nj_bootstrap", None) is not None:
+            if not getattr(ns, "nj", None):
+                self.error("--nj-bootstrap requires --nj FILE")
+            if not 1 <= ns.nj_bootstrap <= 10000:
+                self.error("--nj-bootstrap is out of range (1 .. 10000)")
+        if getattr(ns, "nj_seed", None) is not None:
+            if getattr(ns, "nj_bootstrap", None) is None:
+                self.error("--nj-seed requires --nj-bootstrap N")
+            if not 0 <= ns.nj_seed <= 2**64 - 1:
+                self.error("--nj-seed is out of range")
         if getattr(ns, "core_sites", False) and not (getattr(ns, "sites", None) or getattr(ns, "snp_alignment", None)):
             self.error("--core-sites requires --sites FILE or --snp-alignment FILE")
         if getattr(ns, "cluster_levels", None) is not None:
@@ -262,6 +277,8 @@ class _RunDistances:
         self.levels = getattr(args, "cluster_levels", None)
         self.max_diff = getattr(args, "max_distance", None)
         self.min_compared = getattr(args, "min_compared", None)
+        self.bootstrap = getattr(args, "nj_bootstrap", None) or 0
+        self.seed = getattr(args, "nj_seed", None)
         self.rows: "list | None" = None  # [(keyword or None, LocusRows)]
         self.args = args
 
@@ -300,7 +317,7 @@ class _RunDistances:
             ("clusters", _native.clusters_header(levels), "clusters_tsv", (levels, mc)),
             ("mst", _native.DISTANCES_HEADER, "tree_tsv", (mc,)),
             ("newick", _native.newick_header(), "newick_tsv", (mc,)),
-            ("nj", _native.nj_header(), "nj_tsv", (mc,)),
+            ("nj", _native.nj_support_header() if self.bootstrap else _native.nj_header(), "nj_tsv", (mc, self.bootstrap, 1 if self.seed is None else self.seed)),
             ("sites", _native.SITES_HEADER, "sites_tsv", (self.core_sites,)),
             ("snp_alignment", _native.SNP_ALIGNMENT_HEADER, "snp_alignment_tsv", (self.core_sites,)),
         )

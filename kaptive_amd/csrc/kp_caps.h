@@ -289,3 +289,11 @@ static_assert(KP_DIST_MAX_ROWS <= (1 << KP_TREE_ROW_BITS), "every row of the lar
 // with more taxa is refused by kp_dist_nj, and by it alone, once the taxa are counted and before the matrix is allocated.
 constexpr int32_t KP_NJ_MAX_TAXA = 16384;
 static_assert((int64_t)KP_NJ_MAX_TAXA * KP_NJ_MAX_TAXA * 8 == (2ll << 30), "the dense matrix of the most taxa is 2 GiB");
+
+// bootstrap support of that tree (kp_dist_nj_bootstrap; kp_spec.h, BOOTSTRAP).  The replicates of a call are joined in batches: the
+// dense matrices of one batch together take no more than the one matrix of the largest tree may take already, so a batch is the
+// largest b with b * n * n * 8 <= KP_BOOT_MATRIX_BYTES -- at least 1, at most the replicates, and at most KP_BOOT_MAX_BATCH, the
+// rows of a grid: a replicate is blockIdx.y of every kernel of the batch (kp_boot.h: kp_boot_batch).  No result depends on it.
+constexpr int32_t KP_BOOT_MAX_REPLICATES = 10000;
+constexpr int64_t KP_BOOT_MATRIX_BYTES = (int64_t)KP_NJ_MAX_TAXA * KP_NJ_MAX_TAXA * 8;
+constexpr int32_t KP_BOOT_MAX_BATCH = 65535;

@@ -1,6 +1,6 @@
 // kp_dist_handle.h -- what the units of the pair reports share: the handle, the tile geometry, the chunk loop of the tile kernels and
 // the host helpers of their entry points.  The units: kp_dist.hip (kp_spec.h, DISTANCES), kp_dist_graph.hip (CLUSTERS, TREE),
-// kp_dist_sites.hip (SITES), kp_dist_nj.hip (NJ).  Internal; includes HIP headers.
+// kp_dist_sites.hip (SITES), kp_dist_nj.hip (NJ), kp_dist_boot.hip (BOOTSTRAP).  Internal; includes HIP headers.
 //
 // A handle (kp_dist) holds the bit planes of one matrix of R locus rows of NB blocks -- kp_dist.hip makes them, once -- and the state
 // of every report's most recent call, each in a struct of its own that only its unit touches.
@@ -18,6 +18,7 @@
 
 #include "kp_host.h"
 #include "kp_dist.h"
+#include "kp_boot.h"
 
 struct kp_dist {
     int device = 0;
@@ -71,7 +72,28 @@ struct kp_dist {
         DevBuf<int32_t> cell;              // [2] the pair (i, j) of the join under way
         DevBuf<kp_nj_node> rec;            // [n_rows] the records
     } nj;
+    struct Boot {  // kp_dist_nj_bootstrap: allocated on its first call.  Only these O(n_rows) tables stay: the matrices, the weights and every table of a batch live for one call
+        DevBuf<KpBootSplit> ref;           // [n_rows] the splits of the tree the call supports, ascending by (size, key)
+        DevBuf<int32_t> ref_rec;           // [n_rows] the record of every one of them
+        DevBuf<uint32_t> support;          // [n_rows] by record: the replicates that hold its split
+    } boot;
 };
+
+// ---- the join loop of kp_dist_nj.hip, for one tree or a batch of them -------------------------------------------------------------------
+struct NjBest { double q; int32_t a, b; };  // a pick: the smallest (Q, a, b) seen; nothing seen: (+inf, INT32_MAX, INT32_MAX)
+// The tables of the trees one launch joins, tree y (blockIdx.y) a stride behind tree y - 1: its matrix D [n][n], R of its slots and
+// their node ids, its records, the partials of its pick; its cell is two entries.  One tree: every stride may be 0.
+struct NjBatch {
+    double *D, *sum;
+    int32_t *node, *cell;
+    kp_nj_node *rec;
+    NjBest *part;
+    int64_t sD;
+    int32_t sN, sRec, sPart;  // of sum and node; of rec; of part
+};
+int dist_nj_taxa(kp_ctx *ctx, kp_dist *d, int32_t min_compared, int32_t *n_taxa);
+int32_t dist_nj_parts(int32_t n);  // partials of the picks of a tree of n taxa
+int dist_nj_joins(kp_ctx *ctx, const NjBatch &t, int32_t n, int32_t batch, int64_t *n_rec);
 
 constexpr int DIST_THREADS = 256;
 constexpr int T = KP_DIST_TILE, CH = KP_DIST_CHUNK, RG = KP_DIST_REG;
@@ -114,6 +136,67 @@ __device__ __forceinline__ void dist_tile_counts(const uint64_t *__restrict__ pl
 #pragma unroll
                 for (int j = 0; j < RG; ++j)
                     kp_dist_word_counts(la[i], ha[i], va[i], pa[i], lb[j], hb[j], vb[j], pb[j], &cmp[i][j], &dif[i][j], &uns[i][j]);
+        }
+        __syncthreads();  // (the next chunk overwrites the strips)
+    }
+}
+
+// The weighted chunk loop (kp_spec.h, BOOTSTRAP): the two weighted counts of a lane's 4 x 4 pairs of tile (ti, tj) under the weight
+// planes wplane [KP_BOOT_PLANES][NW] of one replicate, of which the first `top` hold a bit.  The strips hold three planes -- no
+// `present`: nothing counts unshared columns here --, 24 KiB.  A pair's v and d are made once per plane word and serve every weight
+// plane: two popcounts a plane.  wplane and top are the same for every lane of the workgroup and indexed by nothing a lane owns, so
+// the masks are scalar loads and live in scalar registers; `top` picks one of eight unrolled bodies once per chunk, a uniform branch.
+// Ends behind a __syncthreads.
+constexpr int BOOT_STRIP_PLANES = 3;  // lo, hi, valid
+template <int TOP>
+__device__ __forceinline__ void dist_chunk_counts_w(const uint64_t (&s)[2][BOOT_STRIP_PLANES][CH][T], const uint64_t *__restrict__ wplane, int64_t NW, int64_t w0,
+                                                    int32_t (&cmp)[RG][RG], int32_t (&dif)[RG][RG]) {
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+#pragma unroll 1
+    for (int w = 0; w < CH; ++w) {
+        if (w0 + w >= NW) break;  // (uniform)
+        uint64_t M[KP_BOOT_PLANES];
+#pragma unroll
+        for (int k = 0; k < KP_BOOT_PLANES; ++k) M[k] = k < TOP ? wplane[(size_t)k * (size_t)NW + (size_t)(w0 + w)] : 0ull;
+        uint64_t la[RG], ha[RG], va[RG], lb[RG], hb[RG], vb[RG];
+#pragma unroll
+        for (int i = 0; i < RG; ++i) {
+            la[i] = s[0][0][w][ty + 16 * i]; ha[i] = s[0][1][w][ty + 16 * i]; va[i] = s[0][2][w][ty + 16 * i];
+            lb[i] = s[1][0][w][tx + 16 * i]; hb[i] = s[1][1][w][tx + 16 * i]; vb[i] = s[1][2][w][tx + 16 * i];
+        }
+#pragma unroll
+        for (int i = 0; i < RG; ++i)
+#pragma unroll
+            for (int j = 0; j < RG; ++j) kp_boot_word_counts<TOP>(la[i], ha[i], va[i], lb[j], hb[j], vb[j], M, &cmp[i][j], &dif[i][j]);
+    }
+}
+__device__ __forceinline__ void dist_tile_counts_w(const uint64_t *__restrict__ planes, int32_t R, int64_t NW, int32_t ti, int32_t tj,
+                                                   const uint64_t *__restrict__ wplane, int top, uint64_t (&s)[2][BOOT_STRIP_PLANES][CH][T],
+                                                   int32_t (&cmp)[RG][RG], int32_t (&dif)[RG][RG]) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < RG; ++i)
+#pragma unroll
+        for (int j = 0; j < RG; ++j) cmp[i][j] = dif[i][j] = 0;
+    const size_t plane = (size_t)NW * (size_t)R;
+    for (int64_t w0 = 0; w0 < NW; w0 += CH) {
+        uint64_t *const flat = &s[0][0][0][0];
+        for (int e = tid; e < 2 * BOOT_STRIP_PLANES * CH * T; e += DIST_THREADS) {
+            const int row = e % T, w = (e / T) % CH, p = (e / (T * CH)) % BOOT_STRIP_PLANES, strip = e / (T * CH * BOOT_STRIP_PLANES);
+            const int64_t r = (int64_t)(strip ? tj : ti) * T + row, ww = w0 + w;
+            flat[e] = (r < R && ww < NW) ? planes[(size_t)p * plane + (size_t)ww * (size_t)R + (size_t)r] : 0ull;
+        }
+        __syncthreads();
+        switch (top) {  // (uniform: a replicate's highest weight plane)
+        case 0: break;
+        case 1: dist_chunk_counts_w<1>(s, wplane, NW, w0, cmp, dif); break;
+        case 2: dist_chunk_counts_w<2>(s, wplane, NW, w0, cmp, dif); break;
+        case 3: dist_chunk_counts_w<3>(s, wplane, NW, w0, cmp, dif); break;
+        case 4: dist_chunk_counts_w<4>(s, wplane, NW, w0, cmp, dif); break;
+        case 5: dist_chunk_counts_w<5>(s, wplane, NW, w0, cmp, dif); break;
+        case 6: dist_chunk_counts_w<6>(s, wplane, NW, w0, cmp, dif); break;
+        case 7: dist_chunk_counts_w<7>(s, wplane, NW, w0, cmp, dif); break;
+        default: dist_chunk_counts_w<8>(s, wplane, NW, w0, cmp, dif); break;
         }
         __syncthreads();  // (the next chunk overwrites the strips)
     }

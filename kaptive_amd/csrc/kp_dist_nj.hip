@@ -14,7 +14,9 @@
 //
 // The state of the join loop: the dense matrix D of the taxa, n x n doubles, row-major with the row stride n throughout -- the m
 // live slots are its first m rows and columns --, R of every slot (`sum`), the node id of every slot, and the pair of the join under
-// way in a device cell: the host enqueues every join of a tree without looking at one.
+// way in a device cell: the host enqueues every join of a tree without looking at one.  The kernels of the loop take these tables as
+// an NjBatch (kp_dist_handle.h) and join tree blockIdx.y of it: kp_dist_nj launches a batch of one, kp_dist_boot.hip (kp_spec.h,
+// BOOTSTRAP) the replicates of a batch, which all have m slots at the same join -- dist_nj_joins below is the loop for both.
 // Bounds: D is read and written at [slot < m][slot < m], m <= n; sum and node at slots < m; part at blockIdx.x < its grid, which the
 // host keeps at NJ_MAX_PARTS or less; rec at the record index the host passes, below kp_nj_records(n) <= n_rows.  A pair the cell
 // holds is used only when 0 <= i < j < m.
@@ -29,8 +31,8 @@ namespace {
 constexpr int NJ_THREADS = 256, NJ_WAVES = NJ_THREADS / 64, NJ_MAX_PARTS = 1024;
 static_assert(KP_NJ_LANES == 64, "SUM64 is one wavefront's reduction");
 
-struct NjBest { double q; int32_t a, b; };  // a pick: the smallest (Q, a, b) seen; nothing seen: (+inf, INT32_MAX, INT32_MAX)
-
+// (NjBest, a pick -- the smallest (Q, a, b) seen; nothing seen: (+inf, INT32_MAX, INT32_MAX) --, and NjBatch, the tables of the trees a
+// launch joins: kp_dist_handle.h)
 __device__ __forceinline__ NjBest nj_none() { return NjBest{__builtin_inf(), INT32_MAX, INT32_MAX}; }
 __device__ __forceinline__ NjBest nj_better(const NjBest &x, const NjBest &y) { return kp_nj_less(y.q, y.a, y.b, x.q, x.a, x.b) ? y : x; }
 // the wave's best in every lane
@@ -135,7 +137,10 @@ __global__ __launch_bounds__(DIST_THREADS) void kp_dist_nj_kernel(const uint64_t
 }
 
 // The initial state: a wave per slot k < n: sum[k] = SUM64 of row k, node[k] = k.
-__global__ __launch_bounds__(NJ_THREADS) void kp_nj_init_kernel(const double *__restrict__ D, int32_t n, double *__restrict__ sum, int32_t *__restrict__ node) {
+__global__ __launch_bounds__(NJ_THREADS) void kp_nj_init_kernel(NjBatch t, int32_t n) {
+    const double *__restrict__ D = t.D + (size_t)blockIdx.y * (size_t)t.sD;
+    double *__restrict__ sum = t.sum + (size_t)blockIdx.y * (size_t)t.sN;
+    int32_t *__restrict__ node = t.node + (size_t)blockIdx.y * (size_t)t.sN;
     const int lane = threadIdx.x & 63;
     for (int64_t k = (int64_t)blockIdx.x * NJ_WAVES + threadIdx.x / 64; k < n; k += (int64_t)gridDim.x * NJ_WAVES) {  // (k is the same in every lane of a wave)
         const double mine = nj_wave_sum64(nj_lane_fold(D + (size_t)k * (size_t)n, n, lane, -1, -1));
@@ -145,8 +150,11 @@ __global__ __launch_bounds__(NJ_THREADS) void kp_nj_init_kernel(const double *__
 
 // A join's pick, first step: workgroup g scans the rows a = g, g + grid, .. of the triangle a < b < m -- a row is one coalesced run
 // -- and leaves the smallest (Q, a, b) it met in part[g].
-__global__ __launch_bounds__(NJ_THREADS) void kp_nj_pick_kernel(const double *__restrict__ D, int32_t n, int32_t m, const double *__restrict__ sum, NjBest *__restrict__ part) {
+__global__ __launch_bounds__(NJ_THREADS) void kp_nj_pick_kernel(NjBatch t, int32_t n, int32_t m) {
     __shared__ NjBest s_best[NJ_WAVES];
+    const double *__restrict__ D = t.D + (size_t)blockIdx.y * (size_t)t.sD;
+    const double *__restrict__ sum = t.sum + (size_t)blockIdx.y * (size_t)t.sN;
+    NjBest *__restrict__ part = t.part + (size_t)blockIdx.y * (size_t)t.sPart;
     const double f = (double)(m - 2);
     NjBest best = nj_none();
     for (int32_t a = (int32_t)blockIdx.x; a < m - 1; a += (int32_t)gridDim.x) {
@@ -163,10 +171,14 @@ __global__ __launch_bounds__(NJ_THREADS) void kp_nj_pick_kernel(const double *__
 
 // Second step, one workgroup: the smallest of the partials is the pair (i, j).  It writes the join's record, makes slot i the new
 // node and publishes the pair; a pair that is none (no matrix gives one) is published as (-1, -1) and recorded as (-1, -1, -1).
-__global__ __launch_bounds__(NJ_THREADS) void kp_nj_join_kernel(const NjBest *__restrict__ part, int32_t n_parts, const double *__restrict__ D, int32_t n, int32_t m,
-                                                                const double *__restrict__ sum, int32_t *__restrict__ node, int32_t *__restrict__ cell,
-                                                                kp_nj_node *__restrict__ rec, int32_t at, int32_t new_id) {
+__global__ __launch_bounds__(NJ_THREADS) void kp_nj_join_kernel(NjBatch t, int32_t n_parts, int32_t n, int32_t m, int32_t at, int32_t new_id) {
     __shared__ NjBest s_best[NJ_WAVES];
+    const NjBest *__restrict__ part = t.part + (size_t)blockIdx.y * (size_t)t.sPart;
+    const double *__restrict__ D = t.D + (size_t)blockIdx.y * (size_t)t.sD;
+    const double *__restrict__ sum = t.sum + (size_t)blockIdx.y * (size_t)t.sN;
+    int32_t *__restrict__ node = t.node + (size_t)blockIdx.y * (size_t)t.sN;
+    int32_t *__restrict__ cell = t.cell + 2 * (size_t)blockIdx.y;
+    kp_nj_node *__restrict__ rec = t.rec + (size_t)blockIdx.y * (size_t)t.sRec;
     NjBest best = nj_none();
     for (int32_t p = (int32_t)threadIdx.x; p < n_parts; p += NJ_THREADS) best = nj_better(best, part[p]);
     best = nj_block_best(best, s_best);
@@ -186,7 +198,10 @@ __global__ __launch_bounds__(NJ_THREADS) void kp_nj_join_kernel(const NjBest *__
 
 // Third step, one lane per slot k other than i, j: u_k into row i and column i, R_k.  No lane reads what another writes: lane k
 // reads d(i, k), d(j, k) and R_k and writes d(i, k), d(k, i) and R_k; d(i, j) is read by all and written by none.
-__global__ __launch_bounds__(NJ_THREADS) void kp_nj_update_kernel(double *__restrict__ D, int32_t n, int32_t m, double *__restrict__ sum, const int32_t *__restrict__ cell) {
+__global__ __launch_bounds__(NJ_THREADS) void kp_nj_update_kernel(NjBatch t, int32_t n, int32_t m) {
+    double *__restrict__ D = t.D + (size_t)blockIdx.y * (size_t)t.sD;
+    double *__restrict__ sum = t.sum + (size_t)blockIdx.y * (size_t)t.sN;
+    const int32_t *__restrict__ cell = t.cell + 2 * (size_t)blockIdx.y;
     const int32_t i = cell[0], j = cell[1];
     if (i < 0 || j <= i || j >= m) return;
     double *row_i = D + (size_t)i * (size_t)n;
@@ -206,8 +221,11 @@ __global__ __launch_bounds__(NJ_THREADS) void kp_nj_update_kernel(double *__rest
 // slot k < m - 1 copies d(m - 1, k) into row j and column j --, and the first wave of workgroup 0 finishes R_i: SUM64 of row i over
 // the m - 1 slots as they stand after the move, its entry at j read from where it stood before, d(i, m - 1).  The move reads row
 // m - 1 and writes row j and column j; the sum reads row i, but for its entry in column j: no lane reads what another writes.
-__global__ __launch_bounds__(NJ_THREADS) void kp_nj_move_kernel(double *__restrict__ D, int32_t n, int32_t m, double *__restrict__ sum, int32_t *__restrict__ node,
-                                                                const int32_t *__restrict__ cell) {
+__global__ __launch_bounds__(NJ_THREADS) void kp_nj_move_kernel(NjBatch t, int32_t n, int32_t m) {
+    double *__restrict__ D = t.D + (size_t)blockIdx.y * (size_t)t.sD;
+    double *__restrict__ sum = t.sum + (size_t)blockIdx.y * (size_t)t.sN;
+    int32_t *__restrict__ node = t.node + (size_t)blockIdx.y * (size_t)t.sN;
+    const int32_t *__restrict__ cell = t.cell + 2 * (size_t)blockIdx.y;
     const int32_t i = cell[0], j = cell[1], last = m - 1;
     if (i < 0 || j <= i || j >= m) return;
     if (j != last) {
@@ -230,8 +248,11 @@ __global__ __launch_bounds__(NJ_THREADS) void kp_nj_move_kernel(double *__restri
 }
 
 // END, one lane: the last record of three slots, or the one record of two taxa.
-__global__ void kp_nj_end_kernel(const double *__restrict__ D, int32_t n, int32_t m, const int32_t *__restrict__ node, kp_nj_node *__restrict__ rec, int32_t at) {
+__global__ void kp_nj_end_kernel(NjBatch t, int32_t n, int32_t m, int32_t at) {
     KP_NJ_EXACT
+    const double *__restrict__ D = t.D + (size_t)blockIdx.y * (size_t)t.sD;
+    const int32_t *__restrict__ node = t.node + (size_t)blockIdx.y * (size_t)t.sN;
+    kp_nj_node *__restrict__ rec = t.rec + (size_t)blockIdx.y * (size_t)t.sRec;
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     if (m == 2) {
         const double h = 0.5 * D[1];
@@ -244,6 +265,54 @@ __global__ void kp_nj_end_kernel(const double *__restrict__ D, int32_t n, int32_
 }
 
 }  // namespace
+
+// The taxa of the handle's rows for min_compared, numbered (the first tables of kp_dist::Nj, all of them reserved here), and their
+// number: what kp_dist_nj and kp_dist_nj_bootstrap both begin with.
+int dist_nj_taxa(kp_ctx *ctx, kp_dist *d, int32_t min_compared, int32_t *n_taxa) {
+    const int32_t R = d->n_rows;
+    int rc;
+    kp_dist::Nj &t = d->nj;
+    const size_t rows = (size_t)R;
+    if ((rc = DistReserve()(t.bases, rows)(t.flag, rows)(t.off, rows + 1)(t.taxon, rows)(t.taxa, rows)(t.sum, rows)(t.node, rows)(t.cell, 2)(t.rec, rows).done(ctx, "neighbour-joining tables")))
+        return rc;
+    const unsigned grid = dist_grid(R);
+    KP_HIP_CHECK(ctx, hipMemsetAsync(t.bases.p, 0, rows * sizeof(uint32_t), ctx->stream));
+    hipLaunchKernelGGL(kp_nj_bases_kernel, dim3(dist_grid((int64_t)R * d->n_words)), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, R, d->n_words, t.bases.p);
+    hipLaunchKernelGGL(kp_nj_flag_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, t.bases.p, R, 16 * d->n_blocks, min_compared, t.flag.p);
+    kp_launch_count_scan(t.flag.p, R, t.off.p, ctx->stream);
+    hipLaunchKernelGGL(kp_nj_number_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, t.flag.p, t.off.p, R, t.taxon.p, t.taxa.p);
+    KP_HIP_CHECK(ctx, hipGetLastError());
+    int64_t counted = 0;
+    if ((rc = fetch_all(ctx, ctx->stream, {{&counted, t.off.p + R, sizeof(int64_t)}}))) return rc;
+    if (counted < 0 || counted > R) return kp_fail(ctx, KP_ESTATE, "more taxa than rows");
+    *n_taxa = (int32_t)counted;
+    return KP_OK;
+}
+
+int32_t dist_nj_parts(int32_t n) { return std::min<int32_t>(std::max<int32_t>(n, 1), NJ_MAX_PARTS); }
+
+// The trees of `batch` filled matrices of n >= 2 taxa each, enqueued without a look at the device: the row sums, every join -- four
+// launches a join, whatever the batch: a tree is blockIdx.y of each, and every tree of a batch has m slots at the same join -- and
+// the last record.  Returns the records a tree has through *n_rec.
+int dist_nj_joins(kp_ctx *ctx, const NjBatch &t, int32_t n, int32_t batch, int64_t *n_rec) {
+    const unsigned y = (unsigned)batch;
+    hipLaunchKernelGGL(kp_nj_init_kernel, dim3(dist_grid(n, NJ_WAVES, 4096), y), dim3(NJ_THREADS), 0, ctx->stream, t, n);
+    KP_HIP_CHECK(ctx, hipGetLastError());
+    int32_t at = 0;
+    for (int32_t m = n; m > 3; --m, ++at) {
+        const int32_t parts = std::min<int32_t>(m - 1, NJ_MAX_PARTS);
+        const unsigned slots = dist_grid(m, NJ_THREADS);
+        hipLaunchKernelGGL(kp_nj_pick_kernel, dim3((unsigned)parts, y), dim3(NJ_THREADS), 0, ctx->stream, t, n, m);
+        hipLaunchKernelGGL(kp_nj_join_kernel, dim3(1, y), dim3(NJ_THREADS), 0, ctx->stream, t, parts, n, m, at, n + at);
+        hipLaunchKernelGGL(kp_nj_update_kernel, dim3(slots, y), dim3(NJ_THREADS), 0, ctx->stream, t, n, m);
+        hipLaunchKernelGGL(kp_nj_move_kernel, dim3(slots, y), dim3(NJ_THREADS), 0, ctx->stream, t, n, m);
+        if ((at & 255) == 255) KP_HIP_CHECK(ctx, hipGetLastError());
+    }
+    hipLaunchKernelGGL(kp_nj_end_kernel, dim3(1, y), dim3(64), 0, ctx->stream, t, n, std::min<int32_t>(n, 3), at);
+    KP_HIP_CHECK(ctx, hipGetLastError());
+    *n_rec = at + 1;
+    return KP_OK;
+}
 
 extern "C" {
 
@@ -264,21 +333,9 @@ int kp_dist_nj(kp_ctx *ctx, kp_dist *d, int32_t min_compared, int32_t *taxa, int
     if (R == 0) return KP_OK;
     KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
     kp_dist::Nj &t = d->nj;
-    const size_t rows = (size_t)R;
-    if ((rc = DistReserve()(t.bases, rows)(t.flag, rows)(t.off, rows + 1)(t.taxon, rows)(t.taxa, rows)(t.sum, rows)(t.node, rows)(t.cell, 2)(t.rec, rows).done(ctx, "neighbour-joining tables")))
-        return rc;
     // ---- bases and taxa
-    const unsigned grid = dist_grid(R);
-    KP_HIP_CHECK(ctx, hipMemsetAsync(t.bases.p, 0, rows * sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(kp_nj_bases_kernel, dim3(dist_grid((int64_t)R * d->n_words)), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, R, d->n_words, t.bases.p);
-    hipLaunchKernelGGL(kp_nj_flag_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, t.bases.p, R, 16 * d->n_blocks, min_compared, t.flag.p);
-    kp_launch_count_scan(t.flag.p, R, t.off.p, ctx->stream);
-    hipLaunchKernelGGL(kp_nj_number_kernel, dim3(grid), dim3(DIST_THREADS), 0, ctx->stream, t.flag.p, t.off.p, R, t.taxon.p, t.taxa.p);
-    KP_HIP_CHECK(ctx, hipGetLastError());
-    int64_t counted = 0;
-    if ((rc = fetch_all(ctx, ctx->stream, {{&counted, t.off.p + R, sizeof(int64_t)}}))) return rc;
-    if (counted < 0 || counted > R) return kp_fail(ctx, KP_ESTATE, "more taxa than rows");
-    const int32_t n = (int32_t)counted;
+    int32_t n = 0;
+    if ((rc = dist_nj_taxa(ctx, d, min_compared, &n))) return rc;
     *n_taxa = n;
     if (counting) return KP_OK;
     if (n > KP_NJ_MAX_TAXA) return kp_fail(ctx, KP_EINVAL, "more taxa than a neighbour-joining tree may have (KP_NJ_MAX_TAXA)");
@@ -289,24 +346,13 @@ int kp_dist_nj(kp_ctx *ctx, kp_dist *d, int32_t min_compared, int32_t *taxa, int
         // ---- the matrix and the partials: this call's own, freed when it returns
         DevBuf<double> D;
         DevBuf<NjBest> part;
-        if ((rc = DistReserve()(D, (size_t)n * (size_t)n)(part, (size_t)std::min<int32_t>(n, NJ_MAX_PARTS)).done(ctx, "neighbour-joining matrix"))) return rc;
+        if ((rc = DistReserve()(D, (size_t)n * (size_t)n)(part, (size_t)dist_nj_parts(n)).done(ctx, "neighbour-joining matrix"))) return rc;
         if ((rc = dist_launch_tiles(ctx, d, kp_dist_nj_kernel, t.taxon.p, n, D.p))) return rc;
-        hipLaunchKernelGGL(kp_nj_init_kernel, dim3(dist_grid(n, NJ_WAVES, 4096)), dim3(NJ_THREADS), 0, ctx->stream, D.p, n, t.sum.p, t.node.p);
-        KP_HIP_CHECK(ctx, hipGetLastError());
-        // ---- every join, enqueued without a look at one: m is known here, the pair lives in the cell
-        int32_t at = 0;
-        for (int32_t m = n; m > 3; --m, ++at) {
-            const int32_t parts = std::min<int32_t>(m - 1, NJ_MAX_PARTS);
-            const unsigned slots = dist_grid(m, NJ_THREADS);
-            hipLaunchKernelGGL(kp_nj_pick_kernel, dim3((unsigned)parts), dim3(NJ_THREADS), 0, ctx->stream, D.p, n, m, t.sum.p, part.p);
-            hipLaunchKernelGGL(kp_nj_join_kernel, dim3(1), dim3(NJ_THREADS), 0, ctx->stream, part.p, parts, D.p, n, m, t.sum.p, t.node.p, t.cell.p, t.rec.p, at, n + at);
-            hipLaunchKernelGGL(kp_nj_update_kernel, dim3(slots), dim3(NJ_THREADS), 0, ctx->stream, D.p, n, m, t.sum.p, t.cell.p);
-            hipLaunchKernelGGL(kp_nj_move_kernel, dim3(slots), dim3(NJ_THREADS), 0, ctx->stream, D.p, n, m, t.sum.p, t.node.p, t.cell.p);
-            if ((at & 255) == 255) KP_HIP_CHECK(ctx, hipGetLastError());
-        }
-        hipLaunchKernelGGL(kp_nj_end_kernel, dim3(1), dim3(64), 0, ctx->stream, D.p, n, std::min<int32_t>(n, 3), t.node.p, t.rec.p, at);
-        KP_HIP_CHECK(ctx, hipGetLastError());
-        if (at + 1 != n_rec) return kp_fail(ctx, KP_ESTATE, "the joins do not add up to the tree's records");
+        // ---- every join, enqueued without a look at one: m is known to the host, the pair lives in the cell.  One tree: a batch of one
+        int64_t made = 0;
+        const NjBatch one{D.p, t.sum.p, t.node.p, t.cell.p, t.rec.p, part.p, 0, 0, 0, 0};
+        if ((rc = dist_nj_joins(ctx, one, n, 1, &made))) return rc;
+        if (made != n_rec) return kp_fail(ctx, KP_ESTATE, "the joins do not add up to the tree's records");
         KP_HIP_CHECK(ctx, hipMemcpyAsync(nodes, t.rec.p, (size_t)n_rec * sizeof(kp_nj_node), hipMemcpyDeviceToHost, ctx->stream));
     }
     if (n > 0) KP_HIP_CHECK(ctx, hipMemcpyAsync(taxa, t.taxa.p, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
