@@ -671,6 +671,33 @@ KP_API int kp_dist_boot_weights(kp_ctx *ctx, kp_dist *d, uint64_t seed, int32_t 
 KP_API int64_t kp_format_nj_support(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
                                     const int32_t *rows /* [n_names] or null */, const int32_t *taxa, int32_t n_taxa, const kp_nj_node *nodes, int64_t n_nodes,
                                     const int32_t *support /* [n_nodes] */, int32_t replicates, char *out, int64_t cap);
+/* Transfer bootstrap of that tree (kp_spec.h, TRANSFER): kp_dist_nj_bootstrap's replicates -- the same weights, matrices, joins and
+ * batches, so the same trees --, but every replicate's tree is compared with the supported tree by sets of taxa: phi_r(t) is the
+ * fewest taxa that must move for replicate r's tree to hold the split of record t, at most depth - 1.
+ *   support [cap_support]  : as kp_dist_nj_bootstrap's, but counted on exact sets: the replicates with phi_r(t) = 0.
+ *   transfer [cap_transfer]: transfer[t], t < n_ref: the sum of phi_r(t) over the replicates; -1 for a record without an inner edge.
+ *   per_replicate [cap_per]: null, or phi_r(t) at per_replicate[r * n_ref + t]; -1 likewise.
+ *   trees, max_batch       : as kp_dist_nj_bootstrap's.
+ * ref_nodes need not be the handle's own tree: any record list of the handle's taxa that passes the check of the node ids is
+ * compared.  KP_EINVAL as kp_dist_nj_bootstrap, and for a negative cap_transfer or cap_per, a null transfer with n_ref > 0, a null
+ * per_replicate with room asked for, cap_transfer < n_ref and per_replicate with cap_per < replicates * n_ref.  Fewer than four taxa:
+ * every support, sum and distance is -1, and nothing is joined unless trees asks for the records.  The same rows, min_compared,
+ * seed and replicates give the same bytes under any max_batch.  The call leaves the handle's listing state and its cluster, tree,
+ * site and NJ tables alone.  Two more O(n_rows) tables stay with the handle; the bit-packed membership of the supported tree (n_taxa
+ * * ceil((n_taxa - 3) / 32) words), O(n_taxa) tables and the distances of one batch are the call's own, and the rows of the counts
+ * lie in the replicates' matrix blocks: nothing else of order n_taxa^2 is allocated beyond kp_dist_nj_bootstrap's tables. */
+KP_API int kp_dist_nj_transfer(kp_ctx *ctx, kp_dist *d, int32_t min_compared, uint64_t seed, int32_t replicates, int32_t max_batch /* 0: the library's choice */,
+                               const kp_nj_node *ref_nodes, int64_t n_ref, int32_t *support, int64_t cap_support, int64_t *transfer, int64_t cap_transfer,
+                               int32_t *per_replicate /* null, or [replicates x n_ref] */, int64_t cap_per, kp_nj_node *trees /* null, or [replicates x n_ref] */,
+                               int64_t cap_trees);
+/* kp_format_nj_support's line byte for byte, the same five columns, but the label of the node record t < n_taxa - 3 made is its
+ * transfer support: 1 - transfer[t] / (replicates * (depth - 1)), depth the light side of its split worked out from `nodes`, rounded
+ * half up to thousandths and written with exactly three decimals, 0.000 .. 1.000: (A:0.1,B:0.2)0.934:0.05.  KP_EINVAL as
+ * kp_format_nj, and for a null transfer with records, replicates outside 1 .. KP_BOOT_MAX_REPLICATES, a transfer outside 0 ..
+ * replicates * (depth - 1) at a record with an inner edge, and one other than -1 at a record without.  Written without recursion. */
+KP_API int64_t kp_format_nj_transfer(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
+                                     const int32_t *rows /* [n_names] or null */, const int32_t *taxa, int32_t n_taxa, const kp_nj_node *nodes, int64_t n_nodes,
+                                     const int64_t *transfer /* [n_nodes] */, int32_t replicates, char *out, int64_t cap);
 /* Variable sites of a handle's rows (kp_spec.h, SITES): a reduction over the columns of the same planes, no pair looked at.
  *   kp_dist_profile    : out [cap >= 16 * n_blocks]: the profile of every column of the matrix, padding columns included, as
  *                        kp_site records with `column` filled, ascending.  Computed on the handle's first need of it and kept.

@@ -849,7 +849,43 @@ typedef struct kp_nj_node {
  * Newick text.
  * LIMITS.  KP_BOOT_MAX_REPLICATES = 10000 replicates a call; KP_NJ_MAX_TAXA taxa, as NJ.  Replicates are joined in batches of the
  * largest b with b * n * n * 8 <= KP_BOOT_MATRIX_BYTES = 2 GiB (kp_caps.h), and no result depends on b.
- * OUT OF SCOPE.  Percentages; a consensus tree; transfer bootstrap; resampling of real columns only, of sites only, or by gene;
- * support for the minimum spanning tree; anything NJ leaves out. */
+ * OUT OF SCOPE.  Percentages; a consensus tree; resampling of real columns only, of sites only, or by gene; support for the minimum
+ * spanning tree; anything NJ leaves out.  (Support that does not collapse on deep branches: TRANSFER, below.) */
+
+/* ---- TRANSFER (optional; transfer support for the tree of NJ from BOOTSTRAP's replicates: no byte of NJ, of BOOTSTRAP or of any other
+ * report depends on it) ----
+ * BOOTSTRAP's support counts the replicates that hold EXACTLY a branch's split.  In a tree of a thousand taxa one isolate that hops
+ * across a deep branch makes the replicate count as "branch absent", however well the rest agrees.  The transfer bootstrap
+ * expectation (Lemoine et al., Nature 2018) asks instead how many taxa would have to move for the replicate to hold the branch, and
+ * averages that.  The replicates are BOOTSTRAP's -- its draws, weights, counts, taxa and trees, unchanged --; this section fixes the
+ * comparison.  Everything is integer arithmetic: no floating point appears before the label is printed.
+ *
+ * SETS.  For n >= 4 taxa, record t < n - 3 of a tree has the split A_t of BOOTSTRAP's SPLITS: the set of taxa below node n + t, on
+ * the side without taxon 0.  s = |A_t|; its DEPTH is p_t = min(s, n - s), and p_t >= 2: a node has two taxa below it at least, and
+ * the last record leaves two outside it.
+ * DISTANCE OF TWO SPLITS.  For a split B of a replicate's tree: H = |A xor B| = |A| + |B| - 2 |A and B|, and delta(A, B) = min(H,
+ * n - H) -- n - H is H taken from B's other side, so delta does not depend on the side either split is written on.
+ * TRANSFER DISTANCE.  phi_r(t) = min(p_t - 1, min over the n - 3 splits B of replicate r's tree of delta(A_t, B)).  The bound
+ * p_t - 1 is what the replicate's leaf branches contribute: a leaf's split is one taxon against the rest, and for a leaf k on the
+ * light side of A_t, H = p_t - 1 from that side -- every other taxon of the light side moves.  No leaf does better, and every tree
+ * has all the leaves, so the leaves need no pass of their own: the minimum starts at p_t - 1.
+ * OUTPUT.  transfer[t] = sum over the replicates r of phi_r(t), in 64 bits; -1 for a record without an inner edge, exactly where
+ * support[t] is -1.
+ * SUPPORT RELATION.  support[t] as BOOTSTRAP defines it is the number of r with phi_r(t) = 0: delta is 0 for the same split only.
+ * This section's call computes it so, on exact sets, where it cannot over-count as the comparison of keys can; BOOTSTRAP's own path
+ * and its bytes are untouched.
+ * LABEL (host only).  D = replicates * (p_t - 1) and K = floor((2000 * (D - transfer[t]) + D) / (2 * D)), in 64-bit integers: the
+ * transfer support 1 - transfer[t] / D, rounded half up to thousandths.  The label is K / 1000 written with exactly three decimals,
+ * 0.000 .. 1.000, behind the closing parenthesis where BOOTSTRAP's NEWICK puts its count -- (A:0.1,B:0.2)0.934:0.05 --, and the
+ * line and its five columns are otherwise BOOTSTRAP's.  A label always contains a '.', and a count of BOOTSTRAP never does.
+ * KNOWN ANSWER.  Six taxa.  The supported tree (0, 1, -1), (6, 2, -1), (7, 3, -1), (8, 4, 5) has the splits {2,3,4,5}, {3,4,5},
+ * {4,5} with depths 2, 3, 2; one replicate's tree (0, 3, -1), (6, 1, -1), (7, 2, -1), (8, 4, 5) has {1,2,4,5}, {2,4,5}, {4,5}.
+ * phi = (1, 1, 0): {2,3,4,5} is 2 from {1,2,4,5}, 1 from {2,4,5} and capped at 1; {3,4,5} is 3, 2 and 1 from the three.  support =
+ * (0, 0, 1, -1), transfer = (1, 1, 0, -1), and with the one replicate the labels are 0.000, 0.500, 1.000: the middle branch is one
+ * that BOOTSTRAP calls absent and this section calls half there.
+ * LIMITS.  BOOTSTRAP's.  The taxa below a node are counted in 16 bits: KP_NJ_MAX_TAXA = 16384 (kp_caps.h asserts it).  D is below
+ * 10000 * 8191 < 2^27 and the label's numerator below 2^39.
+ * OUT OF SCOPE.  The transfer SET (which taxa move; lists of rogue taxa); percentages; a consensus tree; any change to a byte of
+ * --nj or of --nj-bootstrap without the new flag. */
 
 #endif /* KP_SPEC_H */

@@ -162,7 +162,7 @@ EXPORTS = (
     "kp_device_count", "kp_device_numa_node", "kp_batch_typing", "kp_batch_proteins", "kp_protein_align", "kp_fasta_pack", "kp_fasta_ingest", "kp_fasta_ingest_many", "kp_fasta_ingest_file", "kp_fasta_ingest_shard", "kp_shard_words_into", "kp_shard_free", "kp_fasta_simd", "kp_pack_contigs",
     "kp_fasta_free", "kp_format_rows", "kp_format_json", "kp_format_fasta", "kp_protein_align_seeded", "kp_randstrobes", "kp_randstrobe_top_hits",
     "kp_dist_create", "kp_dist_count", "kp_dist_pairs", "kp_dist_destroy", "kp_format_distances", "kp_dist_clusters", "kp_format_clusters",
-    "kp_dist_tree", "kp_dist_tree_rounds", "kp_format_newick", "kp_dist_nj", "kp_format_nj", "kp_dist_nj_bootstrap", "kp_dist_boot_weights", "kp_format_nj_support",
+    "kp_dist_tree", "kp_dist_tree_rounds", "kp_format_newick", "kp_dist_nj", "kp_format_nj", "kp_dist_nj_bootstrap", "kp_dist_boot_weights", "kp_format_nj_support", "kp_dist_nj_transfer", "kp_format_nj_transfer",
     "kp_dist_profile", "kp_dist_sites_count", "kp_dist_sites", "kp_dist_site_rows", "kp_format_sites", "kp_format_site_rows",
 )  # fmt: skip
 
@@ -826,6 +826,26 @@ def format_nj_support(locus_name: str, names, taxa, nodes, support, replicates: 
     return _sized("kp_format_nj_support", 60 * len(taxa) + len(nm_b) + len(locus) + 80, lambda out, cap: h.kp_format_nj_support(
         C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows), _p(taxa) if len(taxa) else None,
         C.c_int32(len(taxa)), _p(nodes) if len(nodes) else None, C.c_int64(len(nodes)), _p(support) if len(support) else None, C.c_int32(int(replicates)), out, cap))  # fmt: skip
+
+
+def format_nj_transfer(locus_name: str, names, taxa, nodes, transfer, replicates: int, rows=None) -> bytes:
+    """``format_nj_support``'s line, the same five columns, with transfer support (kp_format_nj_transfer; include/kp_spec.h,
+    TRANSFER): the node of every record with an inner edge is labelled with ``1 - transfer / (replicates * (depth - 1))`` in
+    thousandths, three decimals -- ``transfer`` (int64, one per record) as ``Distances.nj_transfer`` returns it."""
+    nm_b, nm_o = _blob64(names)
+    taxa = np.ascontiguousarray(taxa, np.int32)
+    nodes = np.ascontiguousarray(nodes, dtype=NJ_NODE_DTYPE)
+    transfer = np.ascontiguousarray(transfer, np.int64)
+    R = len(nm_o) - 1
+    if (rows is not None and len(rows) != R) or len(transfer) != len(nodes):
+        raise ValueError("a name for every row and a transfer sum for every record")
+    rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+    locus = locus_name.encode("utf-8")
+    h = lib()
+    h.kp_format_nj_transfer.restype = C.c_int64
+    return _sized("kp_format_nj_transfer", 60 * len(taxa) + len(nm_b) + len(locus) + 80, lambda out, cap: h.kp_format_nj_transfer(
+        C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows), _p(taxa) if len(taxa) else None,
+        C.c_int32(len(taxa)), _p(nodes) if len(nodes) else None, C.c_int64(len(nodes)), _p(transfer) if len(transfer) else None, C.c_int32(int(replicates)), out, cap))  # fmt: skip
 
 
 def format_sites(locus_name: str, gene_names, gene_lengths, n_rows: int, sites, genes=None) -> bytes:
@@ -1589,6 +1609,25 @@ class Distances:
                                                    C.c_int32(int(max_batch)), _p(nodes) if len(nodes) else None, C.c_int64(len(nodes)), _p(support) if len(nodes) else None,
                                                    C.c_int64(len(support)), _p(reps) if trees and reps.size else None, C.c_int64(reps.size if trees else 0)), "kp_dist_nj_bootstrap")  # fmt: skip
         return (support, reps) if trees else support
+
+    def nj_transfer(self, min_compared: int, nodes, replicates: int, seed: int = 1, max_batch: int = 0, per_replicate: bool = False, trees: bool = False):
+        """``(support int32, transfer int64)``, both ``[len(nodes)]``: the transfer bootstrap of every record of ``nodes`` -- any
+        record list of the handle's taxa -- out of ``nj_support``'s replicates (kp_dist_nj_transfer; include/kp_spec.h, TRANSFER):
+        ``transfer`` the sum over the replicates of the fewest taxa that must move for the replicate's tree to hold the record's
+        split, ``support`` the replicates in which none must, counted on exact sets; -1 for a record without an inner edge.  With
+        ``per_replicate`` the result also holds ``int32 [replicates, len(nodes)]``, every distance; with ``trees`` every replicate's
+        records, last.  The state of every other report is left alone."""
+        nodes = np.ascontiguousarray(nodes, dtype=NJ_NODE_DTYPE)
+        support, transfer = np.zeros(len(nodes), np.int32), np.zeros(len(nodes), np.int64)
+        N = int(replicates) if 0 < int(replicates) <= BOOT_MAX_REPLICATES else 0
+        phi = np.zeros((N, len(nodes)), np.int32) if per_replicate else None
+        reps = np.zeros((N, len(nodes)), NJ_NODE_DTYPE) if trees else None
+        self.ctx._check(lib().kp_dist_nj_transfer(self.ctx._h, self._h, C.c_int32(int(min_compared)), C.c_uint64(int(seed) & (2**64 - 1)), C.c_int32(int(replicates)),
+                                                  C.c_int32(int(max_batch)), _p(nodes) if len(nodes) else None, C.c_int64(len(nodes)), _p(support) if len(nodes) else None,
+                                                  C.c_int64(len(support)), _p(transfer) if len(nodes) else None, C.c_int64(len(transfer)),
+                                                  _p(phi) if per_replicate and phi.size else None, C.c_int64(phi.size if per_replicate else 0),
+                                                  _p(reps) if trees and reps.size else None, C.c_int64(reps.size if trees else 0)), "kp_dist_nj_transfer")  # fmt: skip
+        return (support, transfer, *((phi,) if per_replicate else ()), *((reps,) if trees else ()))
 
     def boot_weights(self, seed: int, replicate: int) -> np.ndarray:
         """uint8 [16 * n_blocks]: how often every block column of the matrix, padding included, is drawn in replicate ``replicate`` of

@@ -163,6 +163,9 @@ def _add_outputs(p: argparse.ArgumentParser, tsv_flags, include_json: bool) -> N
                             "label every inner branch with the number of replicate trees that hold it; the table gets a Replicates column")
         g.add_argument("--nj-seed", type=int, metavar="S", default=argparse.SUPPRESS,
                        help="With --nj-bootstrap: the seed of the resampling (default: 1); the same seed gives the same table")
+        g.add_argument("--nj-transfer", action="store_true", default=argparse.SUPPRESS,
+                       help="With --nj-bootstrap: label every inner branch with its transfer support instead, 0.000 .. 1.000: one "
+                            "minus the share of its lighter side that must move, on average, for a replicate tree to hold it")
         g.add_argument("--sites", metavar="FILE", default=argparse.SUPPRESS,
                        help="List the gene positions at which the assemblies that carry the same locus hold different bases, with the "
                             "number of assemblies that carry each base there, as a TSV table to a file; no pair is looked at for it")
@@ -205,6 +208,8 @@ class _Parser(argparse.ArgumentParser):
                 self.error("--nj-seed requires --nj-bootstrap N")
             if not 0 <= ns.nj_seed <= 2**64 - 1:
                 self.error("--nj-seed is out of range")
+        if getattr(ns, "nj_transfer", False) and getattr(ns, "nj_bootstrap", None) is None:
+            self.error("--nj-transfer requires --nj-bootstrap N")
         if getattr(ns, "core_sites", False) and not (getattr(ns, "sites", None) or getattr(ns, "snp_alignment", None)):
             self.error("--core-sites requires --sites FILE or --snp-alignment FILE")
         if getattr(ns, "cluster_levels", None) is not None:
@@ -279,6 +284,7 @@ class _RunDistances:
         self.min_compared = getattr(args, "min_compared", None)
         self.bootstrap = getattr(args, "nj_bootstrap", None) or 0
         self.seed = getattr(args, "nj_seed", None)
+        self.transfer = bool(getattr(args, "nj_transfer", False))
         self.rows: "list | None" = None  # [(keyword or None, LocusRows)]
         self.args = args
 
@@ -317,7 +323,7 @@ class _RunDistances:
             ("clusters", _native.clusters_header(levels), "clusters_tsv", (levels, mc)),
             ("mst", _native.DISTANCES_HEADER, "tree_tsv", (mc,)),
             ("newick", _native.newick_header(), "newick_tsv", (mc,)),
-            ("nj", _native.nj_support_header() if self.bootstrap else _native.nj_header(), "nj_tsv", (mc, self.bootstrap, 1 if self.seed is None else self.seed)),
+            ("nj", _native.nj_support_header() if self.bootstrap else _native.nj_header(), "nj_tsv", (mc, self.bootstrap, 1 if self.seed is None else self.seed, self.transfer)),
             ("sites", _native.SITES_HEADER, "sites_tsv", (self.core_sites,)),
             ("snp_alignment", _native.SNP_ALIGNMENT_HEADER, "snp_alignment_tsv", (self.core_sites,)),
         )

@@ -289,6 +289,7 @@ static_assert(KP_DIST_MAX_ROWS <= (1 << KP_TREE_ROW_BITS), "every row of the lar
 // with more taxa is refused by kp_dist_nj, and by it alone, once the taxa are counted and before the matrix is allocated.
 constexpr int32_t KP_NJ_MAX_TAXA = 16384;
 static_assert((int64_t)KP_NJ_MAX_TAXA * KP_NJ_MAX_TAXA * 8 == (2ll << 30), "the dense matrix of the most taxa is 2 GiB");
+static_assert(KP_NJ_MAX_TAXA <= 65535, "the taxa below a node are counted in 16 bits (kp_dist_nj_transfer; kp_spec.h, TRANSFER)");
 
 // bootstrap support of that tree (kp_dist_nj_bootstrap; kp_spec.h, BOOTSTRAP).  The replicates of a call are joined in batches: the
 // dense matrices of one batch together take no more than the one matrix of the largest tree may take already, so a batch is the

@@ -15,6 +15,8 @@
 //   kp_boot_walk_kernel    a lane per replicate walks its records (kp_boot_walk) and leaves its n - 3 splits.
 //   kp_boot_count_kernel   a lane per (replicate, split): a binary search of the supported tree's sorted splits, an atomic add into
 //                          the counter of the record it matches.
+// dist_boot_run is the body of kp_dist_nj_bootstrap and of kp_dist_nj_transfer (kp_dist_transfer.hip), which compares sets where the
+// last two kernels compare keys.
 // Bounds: count is indexed [rep < batch][column < W] -- a draw is below W by the high product --; wplane [rep][k < 8][word < NW]; top
 // [rep]; D [rep][taxon < n][taxon < n] as in kp_dist_nj_kernel; splits [rep][t < n - 3]; ref, ref_rec [n - 3]; support at ref_rec's
 // values, which the host checks to be below n - 3.
@@ -129,6 +131,131 @@ int boot_weigh(kp_ctx *ctx, const kp_dist *d, uint64_t seed, int64_t r0, int32_t
 
 }  // namespace
 
+// The body of kp_dist_nj_bootstrap and of kp_dist_nj_transfer (`pass`: kp_dist_transfer.hip): the checks, the tables, the batch loop.
+// Without a pass the splits of every batch are counted by their keys; with one the pass compares the sets, and support is its count of
+// the replicates at distance 0.
+int dist_boot_run(kp_ctx *ctx, kp_dist *d, int32_t min_compared, uint64_t seed, int32_t replicates, int32_t max_batch, const kp_nj_node *ref_nodes, int64_t n_ref,
+                  int32_t *support, int64_t cap_support, kp_nj_node *trees, int64_t cap_trees, TransferPass *pass) {
+    int rc;
+    if ((rc = dist_enter(ctx, d, true, "null distance handle"))) return rc;
+    if (replicates < 1 || replicates > KP_BOOT_MAX_REPLICATES) return kp_fail(ctx, KP_EINVAL, "replicates outside 1 .. KP_BOOT_MAX_REPLICATES");
+    if (max_batch < 0 || n_ref < 0 || cap_support < 0 || cap_trees < 0) return kp_fail(ctx, KP_EINVAL, "a negative batch limit, record count or room");
+    if (n_ref > 0 && !ref_nodes) return kp_fail(ctx, KP_EINVAL, "null record table of the supported tree");
+    if (n_ref > 0 && !support) return kp_fail(ctx, KP_EINVAL, "null support table");
+    if (cap_trees > 0 && !trees) return kp_fail(ctx, KP_EINVAL, "null table of replicate trees with room asked for");
+    if (pass) {
+        if (pass->cap_transfer < 0 || pass->cap_per < 0) return kp_fail(ctx, KP_EINVAL, "a negative batch limit, record count or room");
+        if (n_ref > 0 && !pass->transfer) return kp_fail(ctx, KP_EINVAL, "null transfer table");
+        if (pass->cap_per > 0 && !pass->per_replicate) return kp_fail(ctx, KP_EINVAL, "null table of transfer distances with room asked for");
+    }
+    const int32_t R = d->n_rows;
+    int32_t n = 0;
+    if (R > 0) {
+        if (16 * d->n_blocks >= KP_TREE_MAX_COLUMNS) return kp_fail(ctx, KP_EINVAL, "too many columns for weighted counts (KP_TREE_MAX_COLUMNS)");
+        KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
+        if ((rc = dist_nj_taxa(ctx, d, min_compared, &n))) return rc;
+    }
+    if (n > KP_NJ_MAX_TAXA) return kp_fail(ctx, KP_EINVAL, "more taxa than a neighbour-joining tree may have (KP_NJ_MAX_TAXA)");
+    const int64_t n_rec = kp_nj_records(n), S = kp_boot_splits(n);
+    if (n_ref != n_rec) return kp_fail(ctx, KP_EINVAL, "the supported tree has other than the records of the tree of the handle's taxa (n_taxa - 2; one for two taxa)");
+    if (cap_support < n_ref) return kp_fail(ctx, KP_EINVAL, "room for fewer support values than the tree has records");
+    if (trees && cap_trees < (int64_t)replicates * n_rec) return kp_fail(ctx, KP_EINVAL, "room for fewer records than the replicate trees have (replicates x records)");
+    if (pass && pass->cap_transfer < n_ref) return kp_fail(ctx, KP_EINVAL, "room for fewer transfer sums than the tree has records");
+    if (pass && pass->per_replicate && pass->cap_per < (int64_t)replicates * n_ref)
+        return kp_fail(ctx, KP_EINVAL, "room for fewer transfer distances than the replicates have (replicates x records)");
+    for (int64_t t = 0; t < n_ref; ++t) {  // (the walk below reads children made before their record only; say so here)
+        const kp_nj_node &p = ref_nodes[t];
+        const int32_t child[3] = {p.a, p.b, p.c};
+        for (int k = 0; k < (t == n_ref - 1 && n > 2 ? 3 : 2); ++k)
+            if (child[k] < 0 || child[k] >= n + t) return kp_fail(ctx, KP_EINVAL, "a node id of the supported tree outside the nodes made before its record");
+    }
+    if (S == 0 && !trees) {  // two or three taxa, or none: no inner edge, nothing to join
+        for (int64_t t = 0; t < n_ref; ++t) support[t] = -1;
+        if (pass) pass->none(replicates, n_ref);
+        return KP_OK;
+    }
+    if (n_rec == 0) return KP_OK;
+    const int64_t W = 16 * d->n_blocks, NW = d->n_words;
+    kp_dist::Boot &bt = d->boot;
+    const size_t rows = (size_t)R;
+    if ((rc = DistReserve()(bt.ref, rows)(bt.ref_rec, rows)(bt.support, rows).done(ctx, "bootstrap tables"))) return rc;
+    const uint64_t total = kp_boot_total_key(n);
+    // ---- the splits of the supported tree, sorted
+    if (S > 0 && !pass) {
+        std::vector<KpBootSplit> ref((size_t)S);
+        kp_boot_walk(ref_nodes, n, total, ref.data());
+        std::vector<int32_t> order((size_t)S);
+        for (int64_t t = 0; t < S; ++t) order[(size_t)t] = (int32_t)t;
+        std::sort(order.begin(), order.end(), [&ref](int32_t x, int32_t y) { return kp_boot_split_less(ref[(size_t)x], ref[(size_t)y]) || (!kp_boot_split_less(ref[(size_t)y], ref[(size_t)x]) && x < y); });
+        std::vector<KpBootSplit> sorted((size_t)S);
+        for (int64_t t = 0; t < S; ++t) sorted[(size_t)t] = ref[(size_t)order[(size_t)t]];
+        KP_HIP_CHECK(ctx, hipMemcpyAsync(bt.ref.p, sorted.data(), (size_t)S * sizeof(KpBootSplit), hipMemcpyHostToDevice, ctx->stream));
+        KP_HIP_CHECK(ctx, hipMemcpyAsync(bt.ref_rec.p, order.data(), (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        KP_HIP_CHECK(ctx, hipMemsetAsync(bt.support.p, 0, (size_t)S * sizeof(uint32_t), ctx->stream));
+        KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // (the host vectors go away)
+    }
+    // ---- a batch's tables: this call's own, freed when it returns
+    const int32_t batch = kp_boot_batch(n, replicates, max_batch);
+    const size_t B = (size_t)batch, N = (size_t)n;
+    const int32_t parts = dist_nj_parts(n);
+    DevBuf<uint32_t> count;
+    DevBuf<uint64_t> wplane;
+    DevBuf<int32_t> top, node, cell;
+    DevBuf<double> D, sum;
+    DevBuf<kp_nj_node> rec;
+    DevBuf<NjBest> part;
+    DevBuf<KpBootSplit> splits;
+    if ((rc = DistReserve()(count, B * (size_t)W)(wplane, B * KP_BOOT_PLANES * (size_t)NW)(top, B)(D, B * N * N)(sum, B * N)(node, B * N)(cell, 2 * B)(rec, B * (size_t)n_rec)
+                  (part, B * (size_t)parts)(splits, B * (size_t)std::max<int64_t>(S, 1)).done(ctx, "bootstrap matrices")))
+        return rc;
+    const NjBatch tables{D.p, sum.p, node.p, cell.p, rec.p, part.p, (int64_t)(N * N), n, (int32_t)n_rec, parts};
+    const int64_t tiles = kp_dist_tiles(d->nt);
+    if (tiles <= 0 || tiles * DIST_THREADS >= (1ll << 32)) return kp_fail(ctx, KP_EINVAL, "too many tiles for one grid (KP_DIST_MAX_ROWS)");
+    if (pass && S > 0) {  // ---- the sets of the supported tree
+        if ((rc = pass->reserve(ctx, d, n, batch))) return rc;
+        if ((rc = pass->begin(ctx, d, ref_nodes))) return rc;
+    }
+    for (int32_t r0 = 0; r0 < replicates; r0 += batch) {
+        const int32_t b = std::min<int32_t>(batch, replicates - r0);
+        if ((rc = boot_weigh(ctx, d, seed, r0, b, count.p, wplane.p, top.p))) return rc;
+        hipLaunchKernelGGL(kp_dist_boot_kernel, dim3((unsigned)tiles, (unsigned)b), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, R, NW, d->nt, wplane.p, top.p,
+                           d->nj.taxon.p, n, D.p);
+        KP_HIP_CHECK(ctx, hipGetLastError());
+        int64_t made = 0;
+        if ((rc = dist_nj_joins(ctx, tables, n, b, &made))) return rc;
+        if (made != n_rec) return kp_fail(ctx, KP_ESTATE, "the joins do not add up to the tree's records");
+        if (S > 0 && pass) {
+            if ((rc = pass->batch(ctx, d, rec.p, D.p, (int64_t)(N * N), b))) return rc;
+            if (pass->per_replicate)
+                KP_HIP_CHECK(ctx, hipMemcpyAsync(pass->per_replicate + (size_t)r0 * (size_t)n_rec, pass->phi.p, (size_t)b * (size_t)n_rec * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        } else if (S > 0) {
+            hipLaunchKernelGGL(kp_boot_walk_kernel, dim3(dist_grid(b)), dim3(DIST_THREADS), 0, ctx->stream, rec.p, n_rec, n, total, b, splits.p);
+            hipLaunchKernelGGL(kp_boot_count_kernel, dim3(dist_grid((int64_t)b * S)), dim3(DIST_THREADS), 0, ctx->stream, splits.p, (int64_t)b * S, bt.ref.p, bt.ref_rec.p,
+                               (int32_t)S, bt.support.p);
+            KP_HIP_CHECK(ctx, hipGetLastError());
+        }
+        if (trees) KP_HIP_CHECK(ctx, hipMemcpyAsync(trees + (size_t)r0 * (size_t)n_rec, rec.p, (size_t)b * (size_t)n_rec * sizeof(kp_nj_node), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    std::vector<uint32_t> got((size_t)S);
+    if (S > 0 && pass) {
+        if ((rc = pass->fetch(ctx, d))) return rc;
+    } else if (S > 0) KP_HIP_CHECK(ctx, hipMemcpyAsync(got.data(), bt.support.p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // (the matrices go away behind it)
+    if (trees)
+        for (int64_t r = 0; r < (int64_t)replicates * n_rec; ++r)
+            if (trees[r].a < 0) return kp_fail(ctx, KP_ESTATE, "a join found no pair");
+    if (pass && S == 0) pass->none(replicates, n_ref);
+    if (pass && S > 0) {
+        for (int64_t t = 0; t < n_ref; ++t) {
+            support[t] = t < S ? (int32_t)pass->got_exact[(size_t)t] : -1;
+            pass->transfer[t] = t < S ? (int64_t)pass->got_transfer[(size_t)t] : -1;
+        }
+        return KP_OK;
+    }
+    for (int64_t t = 0; t < n_ref; ++t) support[t] = t < S ? (int32_t)got[(size_t)t] : -1;
+    return KP_OK;
+}
+
 extern "C" {
 
 int kp_dist_boot_weights(kp_ctx *ctx, kp_dist *d, uint64_t seed, int32_t replicate, uint8_t *weights, int64_t cap) {
@@ -160,97 +287,7 @@ int kp_dist_boot_weights(kp_ctx *ctx, kp_dist *d, uint64_t seed, int32_t replica
 
 int kp_dist_nj_bootstrap(kp_ctx *ctx, kp_dist *d, int32_t min_compared, uint64_t seed, int32_t replicates, int32_t max_batch, const kp_nj_node *ref_nodes,
                          int64_t n_ref, int32_t *support, int64_t cap_support, kp_nj_node *trees, int64_t cap_trees) {
-    int rc;
-    if ((rc = dist_enter(ctx, d, true, "null distance handle"))) return rc;
-    if (replicates < 1 || replicates > KP_BOOT_MAX_REPLICATES) return kp_fail(ctx, KP_EINVAL, "replicates outside 1 .. KP_BOOT_MAX_REPLICATES");
-    if (max_batch < 0 || n_ref < 0 || cap_support < 0 || cap_trees < 0) return kp_fail(ctx, KP_EINVAL, "a negative batch limit, record count or room");
-    if (n_ref > 0 && !ref_nodes) return kp_fail(ctx, KP_EINVAL, "null record table of the supported tree");
-    if (n_ref > 0 && !support) return kp_fail(ctx, KP_EINVAL, "null support table");
-    if (cap_trees > 0 && !trees) return kp_fail(ctx, KP_EINVAL, "null table of replicate trees with room asked for");
-    const int32_t R = d->n_rows;
-    int32_t n = 0;
-    if (R > 0) {
-        if (16 * d->n_blocks >= KP_TREE_MAX_COLUMNS) return kp_fail(ctx, KP_EINVAL, "too many columns for weighted counts (KP_TREE_MAX_COLUMNS)");
-        KP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-        if ((rc = dist_nj_taxa(ctx, d, min_compared, &n))) return rc;
-    }
-    if (n > KP_NJ_MAX_TAXA) return kp_fail(ctx, KP_EINVAL, "more taxa than a neighbour-joining tree may have (KP_NJ_MAX_TAXA)");
-    const int64_t n_rec = kp_nj_records(n), S = kp_boot_splits(n);
-    if (n_ref != n_rec) return kp_fail(ctx, KP_EINVAL, "the supported tree has other than the records of the tree of the handle's taxa (n_taxa - 2; one for two taxa)");
-    if (cap_support < n_ref) return kp_fail(ctx, KP_EINVAL, "room for fewer support values than the tree has records");
-    if (trees && cap_trees < (int64_t)replicates * n_rec) return kp_fail(ctx, KP_EINVAL, "room for fewer records than the replicate trees have (replicates x records)");
-    for (int64_t t = 0; t < n_ref; ++t) {  // (the walk below reads children made before their record only; say so here)
-        const kp_nj_node &p = ref_nodes[t];
-        const int32_t child[3] = {p.a, p.b, p.c};
-        for (int k = 0; k < (t == n_ref - 1 && n > 2 ? 3 : 2); ++k)
-            if (child[k] < 0 || child[k] >= n + t) return kp_fail(ctx, KP_EINVAL, "a node id of the supported tree outside the nodes made before its record");
-    }
-    if (S == 0 && !trees) {  // two or three taxa, or none: no inner edge, nothing to join
-        for (int64_t t = 0; t < n_ref; ++t) support[t] = -1;
-        return KP_OK;
-    }
-    if (n_rec == 0) return KP_OK;
-    const int64_t W = 16 * d->n_blocks, NW = d->n_words;
-    kp_dist::Boot &bt = d->boot;
-    const size_t rows = (size_t)R;
-    if ((rc = DistReserve()(bt.ref, rows)(bt.ref_rec, rows)(bt.support, rows).done(ctx, "bootstrap tables"))) return rc;
-    const uint64_t total = kp_boot_total_key(n);
-    // ---- the splits of the supported tree, sorted
-    if (S > 0) {
-        std::vector<KpBootSplit> ref((size_t)S);
-        kp_boot_walk(ref_nodes, n, total, ref.data());
-        std::vector<int32_t> order((size_t)S);
-        for (int64_t t = 0; t < S; ++t) order[(size_t)t] = (int32_t)t;
-        std::sort(order.begin(), order.end(), [&ref](int32_t x, int32_t y) { return kp_boot_split_less(ref[(size_t)x], ref[(size_t)y]) || (!kp_boot_split_less(ref[(size_t)y], ref[(size_t)x]) && x < y); });
-        std::vector<KpBootSplit> sorted((size_t)S);
-        for (int64_t t = 0; t < S; ++t) sorted[(size_t)t] = ref[(size_t)order[(size_t)t]];
-        KP_HIP_CHECK(ctx, hipMemcpyAsync(bt.ref.p, sorted.data(), (size_t)S * sizeof(KpBootSplit), hipMemcpyHostToDevice, ctx->stream));
-        KP_HIP_CHECK(ctx, hipMemcpyAsync(bt.ref_rec.p, order.data(), (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        KP_HIP_CHECK(ctx, hipMemsetAsync(bt.support.p, 0, (size_t)S * sizeof(uint32_t), ctx->stream));
-        KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // (the host vectors go away)
-    }
-    // ---- a batch's tables: this call's own, freed when it returns
-    const int32_t batch = kp_boot_batch(n, replicates, max_batch);
-    const size_t B = (size_t)batch, N = (size_t)n;
-    const int32_t parts = dist_nj_parts(n);
-    DevBuf<uint32_t> count;
-    DevBuf<uint64_t> wplane;
-    DevBuf<int32_t> top, node, cell;
-    DevBuf<double> D, sum;
-    DevBuf<kp_nj_node> rec;
-    DevBuf<NjBest> part;
-    DevBuf<KpBootSplit> splits;
-    if ((rc = DistReserve()(count, B * (size_t)W)(wplane, B * KP_BOOT_PLANES * (size_t)NW)(top, B)(D, B * N * N)(sum, B * N)(node, B * N)(cell, 2 * B)(rec, B * (size_t)n_rec)
-                  (part, B * (size_t)parts)(splits, B * (size_t)std::max<int64_t>(S, 1)).done(ctx, "bootstrap matrices")))
-        return rc;
-    const NjBatch tables{D.p, sum.p, node.p, cell.p, rec.p, part.p, (int64_t)(N * N), n, (int32_t)n_rec, parts};
-    const int64_t tiles = kp_dist_tiles(d->nt);
-    if (tiles <= 0 || tiles * DIST_THREADS >= (1ll << 32)) return kp_fail(ctx, KP_EINVAL, "too many tiles for one grid (KP_DIST_MAX_ROWS)");
-    for (int32_t r0 = 0; r0 < replicates; r0 += batch) {
-        const int32_t b = std::min<int32_t>(batch, replicates - r0);
-        if ((rc = boot_weigh(ctx, d, seed, r0, b, count.p, wplane.p, top.p))) return rc;
-        hipLaunchKernelGGL(kp_dist_boot_kernel, dim3((unsigned)tiles, (unsigned)b), dim3(DIST_THREADS), 0, ctx->stream, d->d_planes.p, R, NW, d->nt, wplane.p, top.p,
-                           d->nj.taxon.p, n, D.p);
-        KP_HIP_CHECK(ctx, hipGetLastError());
-        int64_t made = 0;
-        if ((rc = dist_nj_joins(ctx, tables, n, b, &made))) return rc;
-        if (made != n_rec) return kp_fail(ctx, KP_ESTATE, "the joins do not add up to the tree's records");
-        if (S > 0) {
-            hipLaunchKernelGGL(kp_boot_walk_kernel, dim3(dist_grid(b)), dim3(DIST_THREADS), 0, ctx->stream, rec.p, n_rec, n, total, b, splits.p);
-            hipLaunchKernelGGL(kp_boot_count_kernel, dim3(dist_grid((int64_t)b * S)), dim3(DIST_THREADS), 0, ctx->stream, splits.p, (int64_t)b * S, bt.ref.p, bt.ref_rec.p,
-                               (int32_t)S, bt.support.p);
-            KP_HIP_CHECK(ctx, hipGetLastError());
-        }
-        if (trees) KP_HIP_CHECK(ctx, hipMemcpyAsync(trees + (size_t)r0 * (size_t)n_rec, rec.p, (size_t)b * (size_t)n_rec * sizeof(kp_nj_node), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    std::vector<uint32_t> got((size_t)S);
-    if (S > 0) KP_HIP_CHECK(ctx, hipMemcpyAsync(got.data(), bt.support.p, (size_t)S * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    KP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));  // (the matrices go away behind it)
-    if (trees)
-        for (int64_t r = 0; r < (int64_t)replicates * n_rec; ++r)
-            if (trees[r].a < 0) return kp_fail(ctx, KP_ESTATE, "a join found no pair");
-    for (int64_t t = 0; t < n_ref; ++t) support[t] = t < S ? (int32_t)got[(size_t)t] : -1;
-    return KP_OK;
+    return dist_boot_run(ctx, d, min_compared, seed, replicates, max_batch, ref_nodes, n_ref, support, cap_support, trees, cap_trees, nullptr);
 }
 
 }  // extern "C"

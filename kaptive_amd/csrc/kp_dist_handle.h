@@ -1,6 +1,6 @@
 // kp_dist_handle.h -- what the units of the pair reports share: the handle, the tile geometry, the chunk loop of the tile kernels and
 // the host helpers of their entry points.  The units: kp_dist.hip (kp_spec.h, DISTANCES), kp_dist_graph.hip (CLUSTERS, TREE),
-// kp_dist_sites.hip (SITES), kp_dist_nj.hip (NJ), kp_dist_boot.hip (BOOTSTRAP).  Internal; includes HIP headers.
+// kp_dist_sites.hip (SITES), kp_dist_nj.hip (NJ), kp_dist_boot.hip (BOOTSTRAP), kp_dist_transfer.hip (TRANSFER).  Internal; includes HIP headers.
 //
 // A handle (kp_dist) holds the bit planes of one matrix of R locus rows of NB blocks -- kp_dist.hip makes them, once -- and the state
 // of every report's most recent call, each in a struct of its own that only its unit touches.
@@ -72,10 +72,12 @@ struct kp_dist {
         DevBuf<int32_t> cell;              // [2] the pair (i, j) of the join under way
         DevBuf<kp_nj_node> rec;            // [n_rows] the records
     } nj;
-    struct Boot {  // kp_dist_nj_bootstrap: allocated on its first call.  Only these O(n_rows) tables stay: the matrices, the weights and every table of a batch live for one call
+    struct Boot {  // kp_dist_nj_bootstrap, kp_dist_nj_transfer: allocated on their first call.  Only these O(n_rows) tables stay: the matrices, the weights and every table of a batch live for one call
         DevBuf<KpBootSplit> ref;           // [n_rows] the splits of the tree the call supports, ascending by (size, key)
         DevBuf<int32_t> ref_rec;           // [n_rows] the record of every one of them
         DevBuf<uint32_t> support;          // [n_rows] by record: the replicates that hold its split
+        DevBuf<unsigned long long> transfer;  // [n_rows] kp_dist_nj_transfer, by record: the sum of its transfer distances
+        DevBuf<uint32_t> exact;            // [n_rows] kp_dist_nj_transfer, by record: the replicates at distance 0
     } boot;
 };
 
@@ -94,6 +96,38 @@ struct NjBatch {
 int dist_nj_taxa(kp_ctx *ctx, kp_dist *d, int32_t min_compared, int32_t *n_taxa);
 int32_t dist_nj_parts(int32_t n);  // partials of the picks of a tree of n taxa
 int dist_nj_joins(kp_ctx *ctx, const NjBatch &t, int32_t n, int32_t batch, int64_t *n_rec);
+
+// ---- the batch loop of kp_dist_boot.hip, for kp_dist_nj_bootstrap and kp_dist_nj_transfer ---------------------------------------------
+// What kp_dist_nj_transfer adds to a bootstrap (kp_spec.h, TRANSFER; kp_dist_transfer.hip): the call's own tables -- the membership
+// of the supported tree, O(n) tables of it and the transfer distances of one batch --, freed with the pass.  The batch loop calls
+// reserve and begin once, before the first batch, batch after the joins of every batch, and fetch behind the last one.
+struct TransferPass {
+    int64_t *transfer = nullptr;        // [cap_transfer] the caller's
+    int64_t cap_transfer = 0;
+    int32_t *per_replicate = nullptr;   // null, or [cap_per]
+    int64_t cap_per = 0;
+    DevBuf<uint32_t> member;            // [n][MW] bit t % 32 of word t / 32 of row k: taxon k lies in A_t
+    DevBuf<uint32_t> turn;              // [MW] bit t: the node of record t holds taxon 0 below it
+    DevBuf<int32_t> parent;             // [n + records] the node a node is a child of, -1 for none
+    DevBuf<int32_t> size;               // [n - 3] |A_t|
+    DevBuf<int32_t> phi;                // [batch][records] the transfer distances of a batch, -1 at a record without an inner edge
+    int32_t n = 0, n_rec = 0, S = 0, MW = 0;
+    int reserve(kp_ctx *ctx, kp_dist *d, int32_t n_taxa, int32_t batch);
+    int begin(kp_ctx *ctx, kp_dist *d, const kp_nj_node *ref_nodes);
+    // rec [b][records]: the batch's trees; D: its matrices, sD doubles apart, which the joins are done with
+    int batch(kp_ctx *ctx, kp_dist *d, const kp_nj_node *rec, double *D, int64_t sD, int32_t b);
+    int fetch(kp_ctx *ctx, kp_dist *d);  // queues the copies of the sums into got_*, for the caller to read behind its synchronisation
+    std::vector<unsigned long long> got_transfer;
+    std::vector<uint32_t> got_exact;
+    void none(int32_t replicates, int64_t n_ref) {  // a tree without an inner edge: -1 everywhere
+        for (int64_t t = 0; t < n_ref; ++t) transfer[t] = -1;
+        if (per_replicate)
+            for (int64_t e = 0; e < (int64_t)replicates * n_ref; ++e) per_replicate[e] = -1;
+    }
+};
+// kp_dist_nj_bootstrap's arguments; `pass` null for it
+int dist_boot_run(kp_ctx *ctx, kp_dist *d, int32_t min_compared, uint64_t seed, int32_t replicates, int32_t max_batch, const kp_nj_node *ref_nodes, int64_t n_ref,
+                  int32_t *support, int64_t cap_support, kp_nj_node *trees, int64_t cap_trees, TransferPass *pass);
 
 constexpr int DIST_THREADS = 256;
 constexpr int T = KP_DIST_TILE, CH = KP_DIST_CHUNK, RG = KP_DIST_REG;

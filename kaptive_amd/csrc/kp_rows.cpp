@@ -18,6 +18,7 @@
 #include "kp_clust.h"
 #include "kp_sites.h"
 #include "kp_boot.h"
+#include "kp_transfer.h"
 #include "kp_nj.h"
 
 namespace {
@@ -712,9 +713,10 @@ extern "C" int64_t kp_format_newick(const char *locus_name, int32_t locus_name_l
 // One line for one locus's tree, none for fewer than two taxa: the unrooted tree written from its last record, inner nodes unnamed,
 // lengths with %.9g, with a stack of its own -- a caterpillar of 16384 taxa is a legal tree.
 // With `support` (kp_spec.h, BOOTSTRAP) the line has the Replicates column, and the node of a record with an inner edge its label.
+// With `transfer` (kp_spec.h, TRANSFER) instead, the label is the transfer support in thousandths, three decimals.
 static int64_t format_nj_line(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names, const int32_t *rows,
-                              const int32_t *taxa, int32_t n_taxa, const kp_nj_node *nodes, int64_t n_nodes, const int32_t *support, int32_t replicates, char *out,
-                              int64_t cap) {
+                              const int32_t *taxa, int32_t n_taxa, const kp_nj_node *nodes, int64_t n_nodes, const int32_t *support, const int64_t *transfer,
+                              int32_t replicates, char *out, int64_t cap) {
     const RowNames t{names, name_off, n_names, rows};
     if (!locus_and_out_ok(locus_name, locus_name_len, out, cap) || !t.valid() || n_taxa < 0 || n_taxa > n_names || n_nodes < 0) return KP_EINVAL;
     if ((n_taxa > 0 && !taxa) || (n_nodes > 0 && !nodes)) return KP_EINVAL;
@@ -738,12 +740,20 @@ static int64_t format_nj_line(const char *locus_name, int32_t locus_name_len, co
     if (support)
         for (int64_t r = 0; r < n_nodes; ++r)
             if (r < labelled ? (support[r] < 0 || support[r] > replicates) : support[r] != -1) return KP_EINVAL;
+    std::vector<int32_t> depth;  // of every record with an inner edge: the light side of its split
+    if (transfer) {
+        depth.resize((size_t)labelled);
+        kp_transfer_sizes(nodes, (int32_t)n, depth.data());
+        for (int64_t r = 0; r < labelled; ++r) depth[(size_t)r] = kp_transfer_depth(depth[(size_t)r], (int32_t)n);
+        for (int64_t r = 0; r < n_nodes; ++r)
+            if (r < labelled ? (transfer[r] < 0 || transfer[r] > (int64_t)replicates * (depth[(size_t)r] - 1)) : transfer[r] != -1) return KP_EINVAL;
+    }
     Out o{out, cap};
     if (n_nodes == 0) return 0;
     put_locus(o, locus_name, locus_name_len); o.put('\t');
     o.num(n_names); o.put('\t');
     o.num(n); o.put('\t');
-    if (support) { o.num(replicates); o.put('\t'); }
+    if (support || transfer) { o.num(replicates); o.put('\t'); }
     const auto put_length = [&o](double v) {
         char buf[40];
         o.put(':');
@@ -760,6 +770,11 @@ static int64_t format_nj_line(const char *locus_name, int32_t locus_name_len, co
             o.put(')');
             stack.pop_back();
             if (support && f.rec < labelled) o.num(support[f.rec]);
+            if (transfer && f.rec < labelled) {
+                char buf[16];
+                const int64_t K = kp_transfer_label(transfer[f.rec], replicates, depth[(size_t)f.rec]);
+                o.put(buf, std::snprintf(buf, sizeof buf, "%d.%03d", (int)(K / 1000), (int)(K % 1000)));
+            }
             if (!stack.empty()) {
                 const Frame &up = stack.back();
                 const kp_nj_node &q = nodes[up.rec];
@@ -784,14 +799,21 @@ static int64_t format_nj_line(const char *locus_name, int32_t locus_name_len, co
 }
 extern "C" int64_t kp_format_nj(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
                                 const int32_t *rows, const int32_t *taxa, int32_t n_taxa, const kp_nj_node *nodes, int64_t n_nodes, char *out, int64_t cap) {
-    return format_nj_line(locus_name, locus_name_len, names, name_off, n_names, rows, taxa, n_taxa, nodes, n_nodes, nullptr, 0, out, cap);
+    return format_nj_line(locus_name, locus_name_len, names, name_off, n_names, rows, taxa, n_taxa, nodes, n_nodes, nullptr, nullptr, 0, out, cap);
 }
 extern "C" int64_t kp_format_nj_support(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
                                         const int32_t *rows, const int32_t *taxa, int32_t n_taxa, const kp_nj_node *nodes, int64_t n_nodes, const int32_t *support,
                                         int32_t replicates, char *out, int64_t cap) {
     if (replicates < 1 || replicates > KP_BOOT_MAX_REPLICATES || (n_nodes > 0 && !support)) return KP_EINVAL;
     static const int32_t none = -1;  // (no record: the shared body still writes the five-column form of nothing)
-    return format_nj_line(locus_name, locus_name_len, names, name_off, n_names, rows, taxa, n_taxa, nodes, n_nodes, support ? support : &none, replicates, out, cap);
+    return format_nj_line(locus_name, locus_name_len, names, name_off, n_names, rows, taxa, n_taxa, nodes, n_nodes, support ? support : &none, nullptr, replicates, out, cap);
+}
+extern "C" int64_t kp_format_nj_transfer(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
+                                         const int32_t *rows, const int32_t *taxa, int32_t n_taxa, const kp_nj_node *nodes, int64_t n_nodes, const int64_t *transfer,
+                                         int32_t replicates, char *out, int64_t cap) {
+    if (replicates < 1 || replicates > KP_BOOT_MAX_REPLICATES || (n_nodes > 0 && !transfer)) return KP_EINVAL;
+    static const int64_t none = -1;  // (no record: as above)
+    return format_nj_line(locus_name, locus_name_len, names, name_off, n_names, rows, taxa, n_taxa, nodes, n_nodes, nullptr, transfer ? transfer : &none, replicates, out, cap);
 }
 
 // ---- site table (kp_spec.h, SITES) ---------------------------------------------------------------------------------------------------

@@ -3,7 +3,7 @@
 Every other report answers a question about one assembly; this one is about pairs: which isolates carry the same or nearly the same
 locus, and how many bases apart they are.  ``LocusRows`` collects, batch after batch, one LOCUS ROW per assembly -- the aligned rows of
 the primary kept records of its best locus's genes, strung together in database order, padding flagged -- and, when the run is over,
-hands the rows of every locus to the device as one matrix (``_native.Distances``: kp_dist.hip compares them all against all; kp_dist_graph.hip, kp_dist_nj.hip, kp_dist_boot.hip and kp_dist_sites.hip hold the reports below).  Two
+hands the rows of every locus to the device as one matrix (``_native.Distances``: kp_dist.hip compares them all against all; kp_dist_graph.hip, kp_dist_nj.hip, kp_dist_boot.hip, kp_dist_transfer.hip and kp_dist_sites.hip hold the reports below).  Two
 tables come of a matrix: the listed pairs (``distances`` / ``tsv``) and, with no pair listed, every row's single-linkage cluster at a
 few thresholds and its nearest neighbour (``clusters`` / ``clusters_tsv``; include/kp_spec.h, CLUSTERS), and the minimum spanning forest
 of the rows as an edge table and as Newick text (``tree`` / ``tree_tsv`` / ``newick_tsv``; include/kp_spec.h, TREE), and the
@@ -273,21 +273,25 @@ class LocusRows:
             return idx, np.zeros(0, np.int32), np.zeros(0, _native.NJ_NODE_DTYPE)
         return (idx, *self._handle(ctx, locus).nj(min_compared))
 
-    def nj_support(self, ctx, locus: int, replicates: int, seed: int = 1, min_compared: int = _native.DIST_MIN_COMPARED):
+    def nj_support(self, ctx, locus: int, replicates: int, seed: int = 1, min_compared: int = _native.DIST_MIN_COMPARED, transfer: bool = False):
         """(assembly numbers [R], taxa, nodes, support int32 [len(nodes)]) of one locus: ``nj``'s tree and the bootstrap support of
         every record out of ``replicates`` resamplings under ``seed`` (include/kp_spec.h, BOOTSTRAP), -1 for a record without an
-        inner edge."""
+        inner edge.  With ``transfer`` a fifth entry, int64 [len(nodes)]: the sums of the records' transfer distances
+        (include/kp_spec.h, TRANSFER), and ``support`` is counted on exact sets by the same call."""
         idx, taxa, nodes = self.nj(ctx, locus, min_compared)
         if len(nodes) == 0:
-            return idx, taxa, nodes, np.zeros(0, np.int32)
+            return (idx, taxa, nodes, np.zeros(0, np.int32), np.zeros(0, np.int64)) if transfer else (idx, taxa, nodes, np.zeros(0, np.int32))
+        if transfer:
+            return (idx, taxa, nodes, *self._handle(ctx, locus).nj_transfer(min_compared, nodes, replicates, seed))
         return idx, taxa, nodes, self._handle(ctx, locus).nj_support(min_compared, nodes, replicates, seed)
 
-    def nj_tsv(self, ctx, min_compared: int = _native.DIST_MIN_COMPARED, bootstrap: int = 0, seed: int = 1) -> tuple[bytes, list]:
+    def nj_tsv(self, ctx, min_compared: int = _native.DIST_MIN_COMPARED, bootstrap: int = 0, seed: int = 1, transfer: bool = False) -> tuple[bytes, list]:
         """(the lines of the neighbour-joining table, the loci that were skipped) (``--nj``; no header: ``_native.nj_header()``),
         formatted by the native library (kp_format_nj): loci in database order, a line for every locus with at least two taxa.  A
         locus of more than ``_native.NJ_MAX_TAXA`` taxa gets no line: its dense matrix is not built, and its number is returned.
         With ``bootstrap`` replicates (``--nj-bootstrap``; ``seed``: ``--nj-seed``) the lines carry support values
-        (kp_format_nj_support; header: ``_native.nj_support_header()``)."""
+        (kp_format_nj_support; header: ``_native.nj_support_header()``); with ``transfer`` beside it (``--nj-transfer``) the labels
+        are transfer support in three decimals (kp_format_nj_transfer; the same header)."""
         out, skipped = [], []
         for L in self.loci():
             idx, mat = self.locus_matrix(L)
@@ -297,7 +301,10 @@ class LocusRows:
                 skipped.append(L)
                 continue
             names = [self.ids[i] for i in idx]
-            if bootstrap:
+            if bootstrap and transfer:
+                _, taxa, nodes, _, sums = self.nj_support(ctx, L, bootstrap, seed, min_compared, transfer=True)
+                out.append(_native.format_nj_transfer(self.db.loci.ids[L], names, taxa, nodes, sums, bootstrap))
+            elif bootstrap:
                 _, taxa, nodes, support = self.nj_support(ctx, L, bootstrap, seed, min_compared)
                 out.append(_native.format_nj_support(self.db.loci.ids[L], names, taxa, nodes, support, bootstrap))
             else:
