@@ -5,6 +5,7 @@
 //     windows that no N run touches: both must agree where the shortcut applies).
 //   * kpy_rs_coords: an aligned stretch back on the contig, and its edge bits.
 //   * kpy_rs_layout: the record's size, the frames per unit and the strip limits.
+//   * kpy_rs_lanes: KP_RS_LANES -- the rows a wave takes per turn (tests/rescue_paths_util.py restates it as ROW_CHUNK).
 #include <cstddef>
 #include <cstdint>
 
@@ -48,5 +49,7 @@ void kpy_rs_layout(int32_t *out8) {
     out8[0] = (int32_t)sizeof(kp_rescue); out8[1] = KP_RS_FRAMES; out8[2] = KP_RS_LANES * KP_RS_NC_SMALL; out8[3] = KP_RS_LANES * KP_RS_NC_MID;
     out8[4] = KP_RS_LANES * KP_RS_NC_WIDE; out8[5] = KP_RESCUE_FLANK; out8[6] = KP_RESCUE_MIN_SCORE; out8[7] = KP_RESCUE_FLANK_MAX;
 }
+
+int kpy_rs_lanes() { return KP_RS_LANES; }
 
 }  // extern "C"

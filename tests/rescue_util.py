@@ -23,7 +23,9 @@ HEADER = b"\t".join([b"Assembly", b"Locus", b"Gene", b"Protein length", b"Call",
 FLANK, FLANK_MAX, MIN_SCORE = 4096, 65535, 80
 MAX_LOCUS_GENES = 256
 # columns of the protein a wave of the fill kernel holds with 2, 4 and 6 columns per lane (kp_rescue.h: KP_RS_LANES x KP_RS_NC_*): a
-# protein beyond the last is cut into strips of that width.  Change them together.
+# protein beyond the last is cut into strips of that width.  Change them together.  (The rows a wave takes per turn, 64 = KP_RS_LANES,
+# and the residues of its LDS ring, 128, are restated in tests/rescue_paths_util.py as ROW_CHUNK and RING;
+# tests/test_rescue_paths_cpu.py ties them to the header.)
 STRIP_LIMITS = (128, 256, 384)
 
 
