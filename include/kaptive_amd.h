@@ -732,6 +732,48 @@ KP_API int64_t kp_format_sites(const char *locus_name, int32_t locus_name_len, c
  * n_names), a column that is flagged both N and GAP, and a column at or beyond n_sites that is not GAP-flagged. */
 KP_API int64_t kp_format_site_rows(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
                                    const int32_t *rows /* [n_names] or null */, int64_t n_sites, const uint64_t *blocks, char *out, int64_t cap);
+/* Small parsimony of every column of a handle's rows on a neighbour-joining tree (kp_spec.h, PARSIMONY): on which branch a base
+ * changes, and how many changes a column needs.  The taxa are numbered as kp_dist_nj numbers them for min_compared; ref_nodes
+ * [n_ref] is a record list of those taxa -- kp_dist_nj's own, or any other tree in its form.
+ *   kp_dist_nj_parsimony: runs the up- and the down-pass on the device, 64 columns to a lane, and lists the columns with a step and
+ *                         the changes; *n_sites and *n_changes are their numbers.
+ *   kp_dist_pars_sites  : the kp_pars_site records of the last call, ascending by column; KP_ESTATE without one, KP_EINVAL if cap
+ *                         is short.
+ *   kp_dist_pars_changes: its kp_pars_change records, ascending by (node, column); likewise.
+ * The records are checked on the host before anything is launched for them: KP_EINVAL for a third child anywhere but in the last
+ * record (and none there, for more than two taxa), a node id outside the nodes made before its record, a node that is a child twice
+ * or -- but for the last -- never, and n_ref other than the tree of the handle's taxa has (n_taxa - 2; one for two taxa; none
+ * below that).  KP_EINVAL also for a null context, handle or count pointer, a handle of another device, a negative n_ref, null
+ * records with n_ref > 0, a null table with room asked for, and a matrix of more than KP_NJ_MAX_TAXA taxa, which this call alone
+ * refuses.  Fewer than two taxa: no site, no change.  A refused call leaves the results of the call before it.  The call leaves the
+ * handle's listing state, its cluster, tree and site tables and the bootstrap's alone; like kp_dist_nj it renumbers the taxa.  Only
+ * the two record lists stay with the handle, each replaced when a list is longer than every one before it; the node tables -- of
+ * the order of 7 * n_taxa * ceil(n_blocks / 4) words: 370 MB for 16384 taxa of 25 kb -- and the scans are allocated by every call
+ * and freed before it returns: all of them or KP_ENOMEM.  kp_device_allocations counts none of it. */
+KP_API int kp_dist_nj_parsimony(kp_ctx *ctx, kp_dist *d, int32_t min_compared, const kp_nj_node *ref_nodes, int64_t n_ref, int64_t *n_sites, int64_t *n_changes);
+KP_API int kp_dist_pars_sites(kp_ctx *ctx, kp_dist *d, kp_pars_site *out, int64_t cap);
+KP_API int kp_dist_pars_changes(kp_ctx *ctx, kp_dist *d, kp_pars_change *out, int64_t cap);
+/* The homoplasy table of one locus (host only): one tab-separated line per kp_pars_site, in the records' order: Locus, Gene,
+ * Position, Column (the three as kp_format_sites has them, from the same gene names and lengths), Alleles (the bases that occur),
+ * Steps, Excess = Steps - (Alleles - 1).  No header line.  Return value as kp_format_variants has it; KP_EINVAL also for a site in
+ * a padding column or outside the matrix, allele bits beyond the four bases, fewer than two alleles, fewer steps than Alleles - 1,
+ * sites that do not ascend, and an entry of genes outside [0, n_genes). */
+KP_API int64_t kp_format_nj_homoplasy(const char *locus_name, int32_t locus_name_len, const char *gene_names, const int64_t *gene_name_off, int32_t n_genes,
+                                      const int32_t *genes /* [n_genes] or null */, const int32_t *gene_len, const kp_pars_site *sites, int64_t n_sites, char *out,
+                                      int64_t cap);
+/* The change table of one locus (host only): one tab-separated line per kp_pars_change, in the records' order: Locus, Node, Tip A,
+ * Tip B, Tips, Gene, Position, Column, From, To.  A leaf: Node is the assembly's name under the quoting rule of kp_format_newick,
+ * Tip A the same, Tip B `.`, Tips 1.  An inner node: Node is #t, t the 1-based number of its record; Tip A and Tip B the
+ * lowest-numbered taxa below its first and its second child -- the node is their most recent common ancestor when the tree is read
+ * from its last record, as kp_format_nj writes it --; Tips the taxa below it.  From and To are one of acgt, the parent's state and
+ * the node's: relative to the last join, not to a root.  names, rows, taxa and nodes as kp_format_nj takes them, the genes as
+ * kp_format_sites does.  No header line.  Written without recursion.  Return value as kp_format_variants has it; KP_EINVAL as
+ * kp_format_nj, and for a change at the top node or outside the nodes, a parent other than the tree's, a state beyond 3, From
+ * equal to To, a column in padding or outside the matrix, and changes that do not ascend by (node, column). */
+KP_API int64_t kp_format_nj_changes(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names,
+                                    const int32_t *rows /* [n_names] or null */, const int32_t *taxa, int32_t n_taxa, const kp_nj_node *nodes, int64_t n_nodes,
+                                    const char *gene_names, const int64_t *gene_name_off, int32_t n_genes, const int32_t *genes /* [n_genes] or null */,
+                                    const int32_t *gene_len, const kp_pars_change *changes, int64_t n_changes, char *out, int64_t cap);
 
 /* ---- JSON lines of a whole batch (host only) ----------------------------------------------------------------------------------
  * Replaces orjson.dumps(SerotypingResult.to_dict(), OPT_SERIALIZE_NUMPY | OPT_APPEND_NEWLINE) per genome

@@ -888,4 +888,62 @@ typedef struct kp_nj_node {
  * OUT OF SCOPE.  The transfer SET (which taxa move; lists of rogue taxa); percentages; a consensus tree; any change to a byte of
  * --nj or of --nj-bootstrap without the new flag. */
 
+/* ---- PARSIMONY (optional; the columns of SITES' matrix put on the tree of NJ: no byte of NJ, of SITES or of any other report depends
+ * on it) ----
+ * SITES says at which columns the isolates of a locus differ, NJ how they are related.  This section says on which branch of the
+ * tree a base changed, and which columns the tree cannot explain with one change for every further base: Fitch's small parsimony,
+ * in Hartigan's form for the one node of three children, of every column of the matrix on the record list of NJ.  Everything is
+ * set and integer arithmetic, 64 columns to a machine word on the planes of DISTANCES.
+ *
+ * TREE.  The records of NJ for the same matrix and min_compared: n taxa, node n + t made by record t.  The last record is the TOP
+ * node: of three children for n >= 3, of two for n = 2.  It is where the joins ended, NOT A ROOT in the biological sense: nothing
+ * below says which end of a branch is older.  Fewer than two taxa: no record, nothing to report.
+ * LEAF SET of taxon k at column c of [0, 64 NW), NW = ceil(NB / 4) -- padding columns included, and the columns at or beyond 16 NB
+ * of the last plane word, which no row holds: {code} where the row holds a base (its `valid` plane is set), {a, c, g, t} otherwise:
+ * N and GAP are missing data.
+ * UP-PASS, records ascending.  For a node with the children's sets X, Y [, Z]: K(s) is the number of children whose set holds s, M
+ * the largest K; the node's set is {s : K(s) = M}, and the column's STEPS grow by (children - M).  For two children this is Fitch's
+ * rule: the intersection if it is not empty, otherwise the union and one step.
+ * DOWN-PASS, records descending.  The top node's STATE is the smallest code in its set.  A child's state is its parent's state if
+ * the child's set holds it, otherwise the smallest code in the child's set.  A leaf without a base therefore takes its parent's
+ * state and carries no change.
+ * CHANGE.  Branch (parent, child) changes at column c iff the two states differ; `from` is the parent's state, `to` the child's:
+ * read from the last join, not from a root.
+ * ALLELES of a column: bit k is set iff some taxon holds base k there.
+ * PROPERTIES.  The changes of a column number exactly its steps.  steps is the minimum over all assignments of states to the inner
+ * nodes and does not depend on which record is last.  steps >= alleles - 1, counting the bits; steps = 0 iff at most one bit is
+ * set.  A leaf's state is its base wherever it holds one.  EXCESS = steps - (alleles - 1) is the homoplasy of the column: changes
+ * the tree needs beyond one for every further base.
+ * RECORDS, two 8-byte words each.  kp_pars_site: column, steps, alleles, pad_ -- one per column with steps >= 1, ascending by
+ * column.  kp_pars_change: column, node (the child end), parent, from, to, pad_ -- ascending by (node, column).
+ * PURE FUNCTION of the matrix, min_compared and the records: not of a launch shape, not of scheduling.
+ * KNOWN ANSWERS, on the tree of NJ's first known answer: five taxa, (0, 1, -1), (5, 2, -1), (6, 4, 3), node 7 the top.  A column
+ * is written as the taxa's bases in order.
+ *   "aaaaa": no step, no record.
+ *   "ccaaa": node 5 {c}, node 6 {a, c} with a step, the top {a}.  steps 1, alleles a and c (3), excess 0; one change, node 5 under
+ *            6, a to c.
+ *   "gagaa": node 5 {a, g} with a step, node 6 {g}, the top {a} with a step (two of three).  steps 2, alleles 5, excess 1; the
+ *            changes node 1 under 5, g to a, and node 6 under 7, a to g.
+ *   "ccctg": the top's children hold {c}, {g}, {t}: a tie of three, the set {c, g, t}, two steps, and the smallest code, c, is the
+ *            state.  steps 2, alleles 14, excess 0; the changes node 3 under 7, c to t, and node 4 under 7, c to g.
+ *   "ccnaa": taxon 2 holds no base: node 6 is {c} and not {a, c}.  steps 1, alleles 3; one change, node 6 under 7, a to c -- taxon
+ *            2 takes c from its parent and carries none.
+ * LIMITS.  KP_NJ_MAX_TAXA taxa, as NJ: a column has at most n - 1 steps, 14 bits.  The node tables are of order n x NW words and
+ * live for one call.
+ * OUT OF SCOPE.  Gaps as a fifth state, indels as events; all most-parsimonious reconstructions, ACCTRAN / DELTRAN; weighted or
+ * likelihood reconstruction; parsimony branch lengths in the Newick text; rooting; any change to an existing report byte. */
+typedef struct kp_pars_site {
+    int32_t column;  /* of the matrix, 0-based, padding columns counted: kp_site's */
+    int32_t steps;   /* changes the tree needs there, >= 1 */
+    int32_t alleles; /* bit k: some taxon holds base k */
+    int32_t pad_;    /* zero */
+} kp_pars_site;
+typedef struct kp_pars_change {
+    int32_t column;   /* as above */
+    int32_t node;     /* the child end of the branch: a taxon below n, the node of record node - n otherwise */
+    int32_t parent;   /* the other end */
+    uint8_t from, to; /* the parent's state, the child's: 0..3 */
+    uint16_t pad_;    /* zero */
+} kp_pars_change;
+
 #endif /* KP_SPEC_H */

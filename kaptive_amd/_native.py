@@ -147,6 +147,23 @@ SITES_THREADS = 256  # KP_SITES_THREADS of kaptive_amd/csrc/kp_sites.h: lanes of
 SITES_LANE_ROWS = 15  # KP_SITES_LANE_ROWS: rows a lane adds into its four-plane bit-sliced counters
 SITES_SLAB = SITES_THREADS * SITES_LANE_ROWS  # KP_SITES_SLAB: rows of one workgroup
 
+# Small parsimony of those columns on the neighbour-joining tree (include/kp_spec.h, PARSIMONY)
+PARS_SITE_DTYPE = np.dtype([("column", "<i4"), ("steps", "<i4"), ("alleles", "<i4"), ("pad", "<i4")])  # kp_pars_site: 16 bytes
+PARS_CHANGE_DTYPE = np.dtype([("column", "<i4"), ("node", "<i4"), ("parent", "<i4"), ("from", "u1"), ("to", "u1"), ("pad", "<u2")])  # kp_pars_change: 16 bytes
+NJ_HOMOPLASY_HEADER = b"Locus\tGene\tPosition\tColumn\tAlleles\tSteps\tExcess\n"  # the columns of kp_format_nj_homoplasy
+NJ_CHANGES_HEADER = b"Locus\tNode\tTip A\tTip B\tTips\tGene\tPosition\tColumn\tFrom\tTo\n"  # the columns of kp_format_nj_changes
+
+
+def nj_homoplasy_header() -> bytes:
+    """The header line of the homoplasy table (the columns of kp_format_nj_homoplasy)."""
+    return NJ_HOMOPLASY_HEADER
+
+
+def nj_changes_header() -> bytes:
+    """The header line of the change table (the columns of kp_format_nj_changes)."""
+    return NJ_CHANGES_HEADER
+
+
 JOIN_MAX_PIECES = 8  # KP_JOIN_MAX_PIECES
 JOIN_DTYPE = np.dtype(
     [("gs", "<i4"), ("contig", "<i4"), ("n_pieces", "<i4"), ("n_anchors", "<i4"), ("chain_score", "<i4"), ("width", "<i4"),
@@ -164,6 +181,7 @@ EXPORTS = (
     "kp_dist_create", "kp_dist_count", "kp_dist_pairs", "kp_dist_destroy", "kp_format_distances", "kp_dist_clusters", "kp_format_clusters",
     "kp_dist_tree", "kp_dist_tree_rounds", "kp_format_newick", "kp_dist_nj", "kp_format_nj", "kp_dist_nj_bootstrap", "kp_dist_boot_weights", "kp_format_nj_support", "kp_dist_nj_transfer", "kp_format_nj_transfer",
     "kp_dist_profile", "kp_dist_sites_count", "kp_dist_sites", "kp_dist_site_rows", "kp_format_sites", "kp_format_site_rows",
+    "kp_dist_nj_parsimony", "kp_dist_pars_sites", "kp_dist_pars_changes", "kp_format_nj_homoplasy", "kp_format_nj_changes",
 )  # fmt: skip
 
 
@@ -883,6 +901,54 @@ def format_site_rows(locus_name: str, names, n_sites: int, blocks, rows=None) ->
     h.kp_format_site_rows.restype = C.c_int64
     return _sized("kp_format_site_rows", R * (S + 64) + len(nm_b), lambda out, cap: h.kp_format_site_rows(
         C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows), C.c_int64(S), _p(blocks), out, cap))  # fmt: skip
+
+
+def _gene_table(gene_names, gene_lengths, genes):
+    """(name blob, offsets, int32 lengths, int32 mapping or None) of a locus's genes, as the site formatters take them."""
+    nm_b, nm_o = _blob64(gene_names)
+    lens = np.ascontiguousarray(gene_lengths, np.int32)
+    if len(nm_o) - 1 != len(lens) or (genes is not None and len(genes) != len(lens)):
+        raise ValueError("a name and a length for every gene")
+    return nm_b, nm_o, lens, None if genes is None else np.ascontiguousarray(genes, np.int32)
+
+
+def format_nj_homoplasy(locus_name: str, gene_names, gene_lengths, sites, genes=None) -> bytes:
+    """The lines of one locus's homoplasy table (kp_format_nj_homoplasy; host only; no header: ``nj_homoplasy_header``): one per
+    record of ``sites`` (PARS_SITE_DTYPE, as ``Distances.nj_parsimony`` returns them) -- the column's gene and position as
+    ``format_sites`` names them, the bases that occur, the changes the tree needs and how many of them are beyond one per further
+    base.  ``gene_names``, ``gene_lengths`` and ``genes`` as ``format_sites`` takes them."""
+    nm_b, nm_o, lens, genes = _gene_table(gene_names, gene_lengths, genes)
+    sites = np.ascontiguousarray(sites, dtype=PARS_SITE_DTYPE)
+    locus = locus_name.encode("utf-8")
+    h = lib()
+    h.kp_format_nj_homoplasy.restype = C.c_int64
+    return _sized("kp_format_nj_homoplasy", 96 * len(sites), lambda out, cap: h.kp_format_nj_homoplasy(
+        C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(len(lens)), None if genes is None else _p(genes), _p(lens),
+        _p(sites) if len(sites) else None, C.c_int64(len(sites)), out, cap))  # fmt: skip
+
+
+def format_nj_changes(locus_name: str, names, taxa, nodes, gene_names, gene_lengths, changes, rows=None, genes=None) -> bytes:
+    """The lines of one locus's change table (kp_format_nj_changes; host only; no header: ``nj_changes_header``): one per record of
+    ``changes`` (PARS_CHANGE_DTYPE, as ``Distances.nj_parsimony`` returns them) -- the branch by its child end, a leaf by its
+    assembly's name, an inner node as ``#t`` with the two tips it is the last common ancestor of when the tree is read from its last
+    record, the column's gene and position, and the base on either end.  ``names``, ``taxa``, ``nodes`` and ``rows`` as
+    ``format_nj`` takes them; the genes as ``format_sites`` does."""
+    nm_b, nm_o = _blob64(names)
+    g_b, g_o, lens, genes = _gene_table(gene_names, gene_lengths, genes)
+    taxa = np.ascontiguousarray(taxa, np.int32)
+    nodes = np.ascontiguousarray(nodes, dtype=NJ_NODE_DTYPE)
+    changes = np.ascontiguousarray(changes, dtype=PARS_CHANGE_DTYPE)
+    R = len(nm_o) - 1
+    if rows is not None and len(rows) != R:
+        raise ValueError("a name for every row")
+    rows = None if rows is None else np.ascontiguousarray(rows, np.int32)
+    locus = locus_name.encode("utf-8")
+    h = lib()
+    h.kp_format_nj_changes.restype = C.c_int64
+    return _sized("kp_format_nj_changes", 160 * len(changes), lambda out, cap: h.kp_format_nj_changes(
+        C.c_char_p(locus), C.c_int32(len(locus)), _p(nm_b), _p(nm_o), C.c_int32(R), None if rows is None else _p(rows), _p(taxa) if len(taxa) else None,
+        C.c_int32(len(taxa)), _p(nodes) if len(nodes) else None, C.c_int64(len(nodes)), _p(g_b), _p(g_o), C.c_int32(len(lens)), None if genes is None else _p(genes), _p(lens),
+        _p(changes) if len(changes) else None, C.c_int64(len(changes)), out, cap))  # fmt: skip
 
 
 class JsonTables(C.Structure):  # kp_json_tables
@@ -1628,6 +1694,22 @@ class Distances:
                                                   _p(phi) if per_replicate and phi.size else None, C.c_int64(phi.size if per_replicate else 0),
                                                   _p(reps) if trees and reps.size else None, C.c_int64(reps.size if trees else 0)), "kp_dist_nj_transfer")  # fmt: skip
         return (support, transfer, *((phi,) if per_replicate else ()), *((reps,) if trees else ()))
+
+    def nj_parsimony(self, min_compared: int, nodes):
+        """``(sites PARS_SITE_DTYPE, changes PARS_CHANGE_DTYPE)``: small parsimony of every column of the matrix on the tree
+        ``nodes`` -- ``nj(min_compared)``'s records, or any record list of the handle's taxa in their form -- (kp_dist_nj_parsimony;
+        include/kp_spec.h, PARSIMONY): ``sites`` the columns the tree needs a change for, ascending, with their steps and the bases
+        that occur; ``changes`` every change, ascending by (node, column): the branch by its child end, its parent, the parent's
+        state and the node's.  States are relative to the last record, which is no root.  A list that is no tree of the handle's
+        taxa is refused.  The state of every other report is left alone."""
+        nodes = np.ascontiguousarray(nodes, dtype=NJ_NODE_DTYPE)
+        ns, nc = C.c_int64(0), C.c_int64(0)
+        self.ctx._check(lib().kp_dist_nj_parsimony(self.ctx._h, self._h, C.c_int32(int(min_compared)), _p(nodes) if len(nodes) else None, C.c_int64(len(nodes)),
+                                                   C.byref(ns), C.byref(nc)), "kp_dist_nj_parsimony")  # fmt: skip
+        sites, changes = np.zeros(ns.value, PARS_SITE_DTYPE), np.zeros(nc.value, PARS_CHANGE_DTYPE)
+        self.ctx._check(lib().kp_dist_pars_sites(self.ctx._h, self._h, _p(sites) if len(sites) else None, C.c_int64(len(sites))), "kp_dist_pars_sites")
+        self.ctx._check(lib().kp_dist_pars_changes(self.ctx._h, self._h, _p(changes) if len(changes) else None, C.c_int64(len(changes))), "kp_dist_pars_changes")
+        return sites, changes
 
     def boot_weights(self, seed: int, replicate: int) -> np.ndarray:
         """uint8 [16 * n_blocks]: how often every block column of the matrix, padding included, is drawn in replicate ``replicate`` of

@@ -18,7 +18,7 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 INCLUDE = PKG.parent / "include"
 LIB = PKG / "libkaptive_amd.so"
-SOURCES = ("kp_ctx.hip", "kp_db.hip", "kp_batch.hip", "kp_align.hip", "kp_typing.hip", "kp_scan.hip", "kp_sort.hip", "kp_bsort.hip", "kp_chain.hip", "kp_join.hip", "kp_sw.hip", "kp_cigar.hip", "kp_cs.hip", "kp_variants.hip", "kp_breakpoints.hip", "kp_alleles.hip", "kp_aligned.hip", "kp_rescue.hip", "kp_dist.hip", "kp_dist_graph.hip", "kp_dist_sites.hip", "kp_dist_nj.hip", "kp_dist_boot.hip", "kp_dist_transfer.hip", "kp_prot.hip", "kp_reduce.hip",
+SOURCES = ("kp_ctx.hip", "kp_db.hip", "kp_batch.hip", "kp_align.hip", "kp_typing.hip", "kp_scan.hip", "kp_sort.hip", "kp_bsort.hip", "kp_chain.hip", "kp_join.hip", "kp_sw.hip", "kp_cigar.hip", "kp_cs.hip", "kp_variants.hip", "kp_breakpoints.hip", "kp_alleles.hip", "kp_aligned.hip", "kp_rescue.hip", "kp_dist.hip", "kp_dist_graph.hip", "kp_dist_sites.hip", "kp_dist_nj.hip", "kp_dist_boot.hip", "kp_dist_transfer.hip", "kp_dist_pars.hip", "kp_prot.hip", "kp_reduce.hip",
            "kp_fasta.cpp", "kp_rows.cpp", "kp_json.cpp", "kp_kmers.cpp")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fvisibility=hidden", "-Wall", "-Wno-unused-function",

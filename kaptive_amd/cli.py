@@ -166,6 +166,14 @@ def _add_outputs(p: argparse.ArgumentParser, tsv_flags, include_json: bool) -> N
         g.add_argument("--nj-transfer", action="store_true", default=argparse.SUPPRESS,
                        help="With --nj-bootstrap: label every inner branch with its transfer support instead, 0.000 .. 1.000: one "
                             "minus the share of its lighter side that must move, on average, for a replicate tree to hold it")
+        g.add_argument("--nj-changes", metavar="FILE", default=argparse.SUPPRESS,
+                       help="With --nj: put every base change on the branch of the tree where parsimony places it -- the branch by the "
+                            "node below it, the gene position, the base on either end, read from the tree's last join, which is no "
+                            "root -- as a TSV table to a file")
+        g.add_argument("--nj-homoplasy", metavar="FILE", default=argparse.SUPPRESS,
+                       help="With --nj: list the gene positions the tree needs a change for, with the changes it needs and how many of "
+                            "them are beyond one per further base (Excess > 0: homoplasy, the signal of recombination), as a TSV "
+                            "table to a file")
         g.add_argument("--sites", metavar="FILE", default=argparse.SUPPRESS,
                        help="List the gene positions at which the assemblies that carry the same locus hold different bases, with the "
                             "number of assemblies that carry each base there, as a TSV table to a file; no pair is looked at for it")
@@ -210,6 +218,9 @@ class _Parser(argparse.ArgumentParser):
                 self.error("--nj-seed is out of range")
         if getattr(ns, "nj_transfer", False) and getattr(ns, "nj_bootstrap", None) is None:
             self.error("--nj-transfer requires --nj-bootstrap N")
+        for flag in NJ_TABLES:
+            if getattr(ns, flag, None) and not getattr(ns, "nj", None):
+                self.error(f"--{flag.replace('_', '-')} requires --nj FILE")
         if getattr(ns, "core_sites", False) and not (getattr(ns, "sites", None) or getattr(ns, "snp_alignment", None)):
             self.error("--core-sites requires --sites FILE or --snp-alignment FILE")
         if getattr(ns, "cluster_levels", None) is not None:
@@ -255,6 +266,7 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 PAIR_TABLES = ("distances", "clusters", "mst", "newick", "nj", "sites", "snp_alignment")  # the flags whose tables are made of the run's locus rows
+NJ_TABLES = ("nj_changes", "nj_homoplasy")  # further tables of the same rows, each beside --nj only: they never ask for the rows on their own
 
 
 def pipeline_options(args: argparse.Namespace, threads: "int | None" = None, read_ahead_share: int = 1) -> PipelineOptions:
@@ -272,7 +284,7 @@ def pipeline_options(args: argparse.Namespace, threads: "int | None" = None, rea
 
 
 class _RunDistances:
-    """``--distances``, ``--clusters``, ``--mst``, ``--newick``, ``--nj``, ``--sites`` and ``--snp-alignment``: the locus rows of the whole run, collected once for all of them,
+    """``--distances``, ``--clusters``, ``--mst``, ``--newick``, ``--nj`` (with ``--nj-changes`` and ``--nj-homoplasy``), ``--sites`` and ``--snp-alignment``: the locus rows of the whole run, collected once for all of them,
     merged chunk by chunk in input order -- one ``LocusRows`` per database -- and, after the last chunk, compared on a device and
     written: one table each, or with ``--db`` one per database (``per_database_path``).  All tables of a locus come from one device
     handle."""
@@ -324,11 +336,15 @@ class _RunDistances:
             ("mst", _native.DISTANCES_HEADER, "tree_tsv", (mc,)),
             ("newick", _native.newick_header(), "newick_tsv", (mc,)),
             ("nj", _native.nj_support_header() if self.bootstrap else _native.nj_header(), "nj_tsv", (mc, self.bootstrap, 1 if self.seed is None else self.seed, self.transfer)),
+            ("nj_changes", _native.nj_changes_header(), "nj_changes_tsv", (mc,)),
+            ("nj_homoplasy", _native.nj_homoplasy_header(), "nj_homoplasy_tsv", (mc,)),
             ("sites", _native.SITES_HEADER, "sites_tsv", (self.core_sites,)),
             ("snp_alignment", _native.SNP_ALIGNMENT_HEADER, "snp_alignment_tsv", (self.core_sites,)),
         )
         for kw, rows in self.rows or []:
-            tables = [(path, header + self._lines(rows, getattr(rows, method)(ctx, *a))) for flag, header, method, a in kinds if (path := getattr(self.args, flag, None))]
+            # (the loci --nj skips are skipped by its two companions as well: --nj's line to stderr says so once)
+            tables = [(path, header + (self._lines(rows, made) if flag not in NJ_TABLES else made[0]))
+                      for flag, header, method, a in kinds if (path := getattr(self.args, flag, None)) for made in (getattr(rows, method)(ctx, *a),)]  # fmt: skip
             rows.close()  # (the handles of this database's loci: every table has been made of them)
             for path, text in tables:
                 if kw is None and _is_stdout(path):
@@ -498,7 +514,7 @@ def run_type(args: argparse.Namespace) -> int:
             except OSError:
                 raise FileNotFoundError(f"{p} does not exist") from None
     t_check = time.perf_counter() - t_check
-    for flag in (*(r.name for r in REPORTS), *PAIR_TABLES):
+    for flag in (*(r.name for r in REPORTS), *PAIR_TABLES, *NJ_TABLES):
         if getattr(args, "db", None) and (v := getattr(args, flag, None)) and _is_stdout(v):
             raise ValueError(f"--{flag.replace('_', '-')} with --db writes a table per database: it needs a file name, not stdout")
     databases = [args.database, *(args.db or [])]

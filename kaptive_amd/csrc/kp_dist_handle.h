@@ -1,6 +1,7 @@
 // kp_dist_handle.h -- what the units of the pair reports share: the handle, the tile geometry, the chunk loop of the tile kernels and
 // the host helpers of their entry points.  The units: kp_dist.hip (kp_spec.h, DISTANCES), kp_dist_graph.hip (CLUSTERS, TREE),
-// kp_dist_sites.hip (SITES), kp_dist_nj.hip (NJ), kp_dist_boot.hip (BOOTSTRAP), kp_dist_transfer.hip (TRANSFER).  Internal; includes HIP headers.
+// kp_dist_sites.hip (SITES), kp_dist_nj.hip (NJ), kp_dist_boot.hip (BOOTSTRAP), kp_dist_transfer.hip (TRANSFER), kp_dist_pars.hip
+// (PARSIMONY).  Internal; includes HIP headers.
 //
 // A handle (kp_dist) holds the bit planes of one matrix of R locus rows of NB blocks -- kp_dist.hip makes them, once -- and the state
 // of every report's most recent call, each in a struct of its own that only its unit touches.
@@ -79,6 +80,12 @@ struct kp_dist {
         DevBuf<unsigned long long> transfer;  // [n_rows] kp_dist_nj_transfer, by record: the sum of its transfer distances
         DevBuf<uint32_t> exact;            // [n_rows] kp_dist_nj_transfer, by record: the replicates at distance 0
     } boot;
+    struct Pars {  // kp_dist_nj_parsimony / kp_dist_pars_sites / kp_dist_pars_changes.  Only the two record lists stay: the node tables, the counters and the scans live for one call
+        DevBuf<kp_pars_site> site;         // the sites of the last call
+        DevBuf<kp_pars_change> change;     // the changes of the last call
+        bool done = false;
+        int64_t n_sites = 0, n_changes = 0;
+    } pars;
 };
 
 // ---- the join loop of kp_dist_nj.hip, for one tree or a batch of them -------------------------------------------------------------------

@@ -20,6 +20,7 @@
 #include "kp_boot.h"
 #include "kp_transfer.h"
 #include "kp_nj.h"
+#include "kp_pars.h"
 
 namespace {
 
@@ -880,6 +881,113 @@ extern "C" int64_t kp_format_site_rows(const char *locus_name, int32_t locus_nam
             if (((v >> KP_DIST_N_SHIFT) & (v >> KP_DIST_GAP_SHIFT) & 0xffffu) || (v & pad) != pad) return KP_EINVAL;  // (N and gap never both)
             put_block_text(o, v, (int)std::min<int64_t>(KP_SITES_BLOCK, n_sites - b * KP_SITES_BLOCK));
         }
+        o.put('\n');
+    }
+    return o.n;
+}
+
+// ---- parsimony tables (kp_spec.h, PARSIMONY) ---------------------------------------------------------------------------------------------
+namespace {
+// The genes of one locus as the site table has them: a column of the matrix -> its gene, its position there and its column among the
+// real columns; false for a column outside the matrix or in padding.
+struct GeneColumns {
+    RowNames t;
+    const int32_t *gene_len;
+    std::vector<int64_t> blocks, before;
+    bool valid() {
+        if (!t.valid() || (t.n > 0 && !gene_len)) return false;
+        blocks.resize((size_t)t.n); before.resize((size_t)t.n);
+        int64_t real = 0;
+        for (int32_t g = 0; g < t.n; ++g) {
+            if (gene_len[g] < 0) return false;
+            blocks[(size_t)g] = ((int64_t)gene_len[g] + 15) / 16;
+            before[(size_t)g] = real;
+            real += gene_len[g];
+        }
+        return true;
+    }
+    bool put(Out &o, int64_t column) const {  // Gene, Position, Column
+        int64_t pos = 0;
+        const int32_t g = kp_site_gene(blocks.data(), t.n, column, &pos);
+        if (g < 0 || pos >= gene_len[g]) return false;
+        t.put(o, g); o.put('\t');
+        o.num(pos + 1); o.put('\t');
+        o.num(before[(size_t)g] + pos + 1);
+        return true;
+    }
+};
+}  // namespace
+
+// One line per column the tree needs a step for, in the records' order.
+extern "C" int64_t kp_format_nj_homoplasy(const char *locus_name, int32_t locus_name_len, const char *gene_names, const int64_t *gene_name_off, int32_t n_genes,
+                                          const int32_t *genes, const int32_t *gene_len, const kp_pars_site *sites, int64_t n_sites, char *out, int64_t cap) {
+    GeneColumns gc{RowNames{gene_names, gene_name_off, n_genes, genes}, gene_len, {}, {}};
+    if (!locus_and_out_ok(locus_name, locus_name_len, out, cap) || !gc.valid() || n_sites < 0 || (n_sites > 0 && !sites)) return KP_EINVAL;
+    Out o{out, cap};
+    for (int64_t i = 0; i < n_sites; ++i) {
+        const kp_pars_site &s = sites[i];
+        const int32_t held = kp_pars_allele_count(s.alleles);
+        if ((s.alleles & ~15) || held < 2 || s.steps < held - 1) return KP_EINVAL;  // (a column of one base has no step)
+        if (i > 0 && s.column <= sites[i - 1].column) return KP_EINVAL;
+        put_locus(o, locus_name, locus_name_len); o.put('\t');
+        if (!gc.put(o, s.column)) return KP_EINVAL;
+        o.put('\t');
+        o.num(held); o.put('\t');
+        o.num(s.steps); o.put('\t');
+        o.num(s.steps - (held - 1));
+        o.put('\n');
+    }
+    return o.n;
+}
+
+// One line per change, in the records' order.  What lies below every node -- its lowest taxon, the number of its taxa -- is made in
+// one pass over the records, children before parents: no recursion.
+extern "C" int64_t kp_format_nj_changes(const char *locus_name, int32_t locus_name_len, const char *names, const int64_t *name_off, int32_t n_names, const int32_t *rows,
+                                        const int32_t *taxa, int32_t n_taxa, const kp_nj_node *nodes, int64_t n_nodes, const char *gene_names, const int64_t *gene_name_off,
+                                        int32_t n_genes, const int32_t *genes, const int32_t *gene_len, const kp_pars_change *changes, int64_t n_changes, char *out, int64_t cap) {
+    const RowNames t{names, name_off, n_names, rows};
+    GeneColumns gc{RowNames{gene_names, gene_name_off, n_genes, genes}, gene_len, {}, {}};
+    if (!locus_and_out_ok(locus_name, locus_name_len, out, cap) || !t.valid() || !gc.valid() || n_taxa < 0 || n_taxa > n_names || n_nodes < 0 || n_changes < 0) return KP_EINVAL;
+    if ((n_taxa > 0 && !taxa) || (n_nodes > 0 && !nodes) || (n_changes > 0 && !changes)) return KP_EINVAL;
+    const int64_t n = n_taxa, all = n + n_nodes;
+    for (int64_t k = 0; k < n; ++k)
+        if (taxa[k] < 0 || taxa[k] >= n_names || (k > 0 && taxa[k] <= taxa[k - 1])) return KP_EINVAL;
+    std::vector<int32_t> up((size_t)all), low((size_t)all), tips((size_t)all);
+    if (!kp_pars_tree_ok(nodes, n_nodes, n_taxa, up.data())) return KP_EINVAL;
+    for (int64_t k = 0; k < n; ++k) { low[(size_t)k] = (int32_t)k; tips[(size_t)k] = 1; }
+    for (int64_t r = 0; r < n_nodes; ++r) {
+        int32_t least = INT32_MAX, sum = 0;
+        for (int k = 0; k < kp_pars_children(nodes[r]); ++k) {
+            const int32_t id = kp_pars_child_id(nodes[r], k);
+            least = std::min(least, low[(size_t)id]);
+            sum += tips[(size_t)id];
+        }
+        low[(size_t)(n + r)] = least; tips[(size_t)(n + r)] = sum;
+    }
+    Out o{out, cap};
+    const auto name = [&](int32_t k) {
+        const int32_t at = t.at(taxa[k]);
+        put_newick_name(o, names + name_off[at], name_off[at + 1] - name_off[at]);
+    };
+    for (int64_t i = 0; i < n_changes; ++i) {
+        const kp_pars_change &c = changes[i];
+        if (c.node < 0 || c.node >= all - 1 || c.parent != up[(size_t)c.node] || c.from > 3 || c.to > 3 || c.from == c.to) return KP_EINVAL;
+        if (i > 0 && (c.node < changes[i - 1].node || (c.node == changes[i - 1].node && c.column <= changes[i - 1].column))) return KP_EINVAL;
+        put_locus(o, locus_name, locus_name_len); o.put('\t');
+        if (c.node < n) {
+            name(c.node); o.put('\t');
+            name(c.node); o.lit("\t.\t");
+        } else {
+            const kp_nj_node &p = nodes[c.node - n];
+            o.put('#'); o.num(c.node - n + 1); o.put('\t');
+            name(low[(size_t)p.a]); o.put('\t');
+            name(low[(size_t)p.b]); o.put('\t');
+        }
+        o.num(tips[(size_t)c.node]); o.put('\t');
+        if (!gc.put(o, c.column)) return KP_EINVAL;
+        o.put('\t');
+        o.put("acgt"[c.from]); o.put('\t');
+        o.put("acgt"[c.to]);
         o.put('\n');
     }
     return o.n;

@@ -3,13 +3,15 @@
 Every other report answers a question about one assembly; this one is about pairs: which isolates carry the same or nearly the same
 locus, and how many bases apart they are.  ``LocusRows`` collects, batch after batch, one LOCUS ROW per assembly -- the aligned rows of
 the primary kept records of its best locus's genes, strung together in database order, padding flagged -- and, when the run is over,
-hands the rows of every locus to the device as one matrix (``_native.Distances``: kp_dist.hip compares them all against all; kp_dist_graph.hip, kp_dist_nj.hip, kp_dist_boot.hip, kp_dist_transfer.hip and kp_dist_sites.hip hold the reports below).  Two
+hands the rows of every locus to the device as one matrix (``_native.Distances``: kp_dist.hip compares them all against all; kp_dist_graph.hip, kp_dist_nj.hip, kp_dist_boot.hip, kp_dist_transfer.hip, kp_dist_pars.hip and kp_dist_sites.hip hold the reports below).  Two
 tables come of a matrix: the listed pairs (``distances`` / ``tsv``) and, with no pair listed, every row's single-linkage cluster at a
 few thresholds and its nearest neighbour (``clusters`` / ``clusters_tsv``; include/kp_spec.h, CLUSTERS), and the minimum spanning forest
 of the rows as an edge table and as Newick text (``tree`` / ``tree_tsv`` / ``newick_tsv``; include/kp_spec.h, TREE), and the
 neighbour-joining tree of the rows that hold most of the locus (``nj`` / ``nj_tsv``; include/kp_spec.h, NJ).  Another reads
 the matrix by columns, not by pairs: the variable sites of a locus with every base's count, and the rows cut down to those sites
-(``profile`` / ``sites`` / ``site_rows`` / ``sites_tsv`` / ``snp_alignment_tsv``; include/kp_spec.h, SITES).  One device handle
+(``profile`` / ``sites`` / ``site_rows`` / ``sites_tsv`` / ``snp_alignment_tsv``; include/kp_spec.h, SITES).  The last puts those
+columns on the neighbour-joining tree: on which branch a base changes, and which columns the tree cannot explain with one change per
+base (``nj_parsimony`` / ``nj_changes_tsv`` / ``nj_homoplasy_tsv``; include/kp_spec.h, PARSIMONY).  One device handle
 per locus serves them all: it is kept until the rows change or ``close()``.
 
 It spans batches and, on a multi-GPU run, processes: ``state()`` is a picklable payload of what was added, ``merge()`` absorbs one.
@@ -311,6 +313,52 @@ class LocusRows:
                 _, taxa, nodes = self.nj(ctx, L, min_compared)
                 out.append(_native.format_nj(self.db.loci.ids[L], names, taxa, nodes))
         return b"".join(out), skipped
+
+    def nj_parsimony(self, ctx, locus: int, min_compared: int = _native.DIST_MIN_COMPARED):
+        """(assembly numbers [R], taxa, nodes, sites ``_native.PARS_SITE_DTYPE``, changes ``_native.PARS_CHANGE_DTYPE``) of one
+        locus: ``nj``'s tree and small parsimony of every column of the locus's matrix on it (include/kp_spec.h, PARSIMONY) -- the
+        columns the tree needs a change for, and every change by the child end of its branch.  Columns are those of the matrix,
+        padding counted; states are relative to the last record, which is no root."""
+        idx, taxa, nodes = self.nj(ctx, locus, min_compared)
+        if len(nodes) == 0:
+            return idx, taxa, nodes, np.zeros(0, _native.PARS_SITE_DTYPE), np.zeros(0, _native.PARS_CHANGE_DTYPE)
+        return (idx, taxa, nodes, *self._handle(ctx, locus).nj_parsimony(min_compared, nodes))
+
+    def _nj_parsimony_tsv(self, ctx, min_compared: int, lines) -> tuple[bytes, list]:
+        """``lines(L, names, taxa, nodes, sites, changes)`` of every locus ``nj_tsv`` writes a line for, joined, and the loci skipped."""
+        out, skipped = [], []
+        for L in self.loci():
+            idx, mat = self.locus_matrix(L)
+            if len(idx) < 2:
+                continue
+            if self._handle(ctx, L).nj_taxa(min_compared) > _native.NJ_MAX_TAXA:
+                skipped.append(L)
+                continue
+            _, taxa, nodes, sites, changes = self.nj_parsimony(ctx, L, min_compared)
+            out.append(lines(L, [self.ids[i] for i in idx], taxa, nodes, sites, changes))
+        return b"".join(out), skipped
+
+    def nj_homoplasy_tsv(self, ctx, min_compared: int = _native.DIST_MIN_COMPARED) -> tuple[bytes, list]:
+        """(the lines of the homoplasy table, the loci that were skipped) (``--nj-homoplasy``; no header:
+        ``_native.nj_homoplasy_header()``), formatted by the native library (kp_format_nj_homoplasy): loci in database order -- those
+        ``nj_tsv`` writes a tree for --, a line per column the locus's tree needs a change for, in column order."""
+
+        def lines(L, names, taxa, nodes, sites, changes):
+            g0, g1 = self.locus_genes(L)
+            return _native.format_nj_homoplasy(self.db.loci.ids[L], list(self.db.genes.ids[g0:g1]), self._gene_lengths[g0:g1], sites)
+
+        return self._nj_parsimony_tsv(ctx, min_compared, lines)
+
+    def nj_changes_tsv(self, ctx, min_compared: int = _native.DIST_MIN_COMPARED) -> tuple[bytes, list]:
+        """(the lines of the change table, the loci that were skipped) (``--nj-changes``; no header: ``_native.nj_changes_header()``),
+        formatted by the native library (kp_format_nj_changes): loci in database order -- those ``nj_tsv`` writes a tree for --, a
+        line per change, by (node, column)."""
+
+        def lines(L, names, taxa, nodes, sites, changes):
+            g0, g1 = self.locus_genes(L)
+            return _native.format_nj_changes(self.db.loci.ids[L], names, taxa, nodes, list(self.db.genes.ids[g0:g1]), self._gene_lengths[g0:g1], changes)
+
+        return self._nj_parsimony_tsv(ctx, min_compared, lines)
 
     # -- sites: the matrix by columns ---------------------------------------------------------------------------------------------------
     def profile(self, ctx, locus: int) -> np.ndarray:

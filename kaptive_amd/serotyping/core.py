@@ -65,7 +65,7 @@ class Serotyper:
         ``distances.LocusRows`` of this database (include/kp_spec.h, DISTANCES) -- it implies ``aligned``.  The one keyword feeds every
         table of the rows: the listed pairs (``locus_rows.distances`` / ``tsv``), the clusters and nearest neighbours
         (``locus_rows.clusters`` / ``clusters_tsv``; CLUSTERS), the minimum spanning trees (``locus_rows.tree`` / ``tree_tsv`` /
-        ``newick_tsv``; TREE), the neighbour-joining trees (``locus_rows.nj`` / ``nj_tsv``; NJ) with their bootstrap and transfer support (``locus_rows.nj_support``; BOOTSTRAP, TRANSFER) and the variable sites (``locus_rows.sites`` / ``sites_tsv`` / ``snp_alignment_tsv``; SITES)."""
+        ``newick_tsv``; TREE), the neighbour-joining trees (``locus_rows.nj`` / ``nj_tsv``; NJ) with their bootstrap and transfer support (``locus_rows.nj_support``; BOOTSTRAP, TRANSFER) and the base changes on their branches (``locus_rows.nj_parsimony`` / ``nj_changes_tsv`` / ``nj_homoplasy_tsv``; PARSIMONY), and the variable sites (``locus_rows.sites`` / ``sites_tsv`` / ``snp_alignment_tsv``; SITES)."""
         self._db = db
         self._variants = bool(variants)
         self._breakpoints = bool(breakpoints)
